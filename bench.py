@@ -12,7 +12,11 @@ step; then the final no-grad pass over all windows, the on-device stitch and the
 timed region starts.  Weak scaling: every rank adapts on its own recordings (they are independent: weights restored,
 fresh optimiser per call); the only collective is the WER-counter all-reduce after the timed region.
 
-Prints ONE JSON line on rank 0 with `roofline` (fp32-MFMA GEMM family, measured live with HIP events on the launch
+A plain run sets up, prewarms (captures every launch sequence the timed region replays, on a short recording of the same window
+structure), runs the W warm-up steps, times the K steps and prints ONE JSON line on rank 0: the headline `value`, `ms_per_step`
+and the run's `config`.  `--dump-outputs DIR` also writes what the last timed step returned (see dump_outputs).
+
+With `--full` the line also holds `roofline` (fp32-MFMA GEMM family, measured live with HIP events on the launch
 stream) and, at N=1, `cpu_baseline` (the CPU oracle restatement timed on the host cores on a bounded sample: ONE weight-carrying
 recording of 8 windows + tail), `parity` (that recording through the HIP path with the same weights and masks, offline and online,
 compared with the oracle's outputs), `other_workloads` (AWMC, wav2vec2 dynamic_eval_su, enc-dec teacher_ce: audio-s/s of the path's other loops),
@@ -31,6 +35,9 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense, 256 CUs x 2.4 GHz
+FULL_PREWARM_S = 40.0
+PLAIN_PREWARM_S = 10.0         # a plain run is repeated for every change: its untimed set-up stays within 30 s
+DUMP_BYTES = 32 << 20          # rows of the last step's log-probs written by --dump-outputs (a seeded sample when larger)
 
 
 def progress(msg):
@@ -67,11 +74,12 @@ def parse():
     ap.add_argument("--side_steps", type=int, default=-1, help="recordings per side measurement (value_degenerate_labels, value_boundary); "
                     "-1 = one round of the chains, 0 = skip them")
     ap.add_argument("--graphs", type=int, default=1, help="hipGraph replay of the per-window launch sequences")
-    ap.add_argument("--prewarm_s", type=float, default=40.0, help="seconds of the untimed workload BEFORE the W warm-up steps: the first "
+    ap.add_argument("--prewarm_s", type=float, default=None, help="seconds of the untimed workload BEFORE the W warm-up steps: the first "
                     "process on an idle MI355X reads 3-10 %% low until the GPU has been under this load for some tens of seconds "
-                    "(743 -> 772 audio-s/s with 40 s; 12 s of plain GEMMs do not do it); steady state is what is reported")
-    ap.add_argument("--sample_every", type=int, default=32, help="every n-th window step runs eagerly for the live roofline sampling "
-                    "(costs 0.7 %% of the throughput at 32: 771 vs 776 audio-s/s at 96, 775 with sampling off)")
+                    f"(743 -> 772 audio-s/s with 40 s; 12 s of plain GEMMs do not do it); default {FULL_PREWARM_S:g} with --full, "
+                    f"{PLAIN_PREWARM_S:g} otherwise (a plain run keeps its set-up short)")
+    ap.add_argument("--sample_every", type=int, default=32, help="with --full, every n-th window step runs eagerly for the live roofline "
+                    "sampling (costs 0.7 %% of the throughput at 32: 771 vs 776 audio-s/s at 96, 775 with sampling off)")
     ap.add_argument("--final_batch", type=int, default=4, help="windows per forward in the final pass (they are independent)")
     ap.add_argument("--pcie", type=int, default=0, help="1: recordings start in HOST memory and results come back as numpy (the "
                     "PCIe-inclusive rate quoted in DESIGN.md; never the headline value)")
@@ -80,7 +88,15 @@ def parse():
                     "step in one batch (SCConformerXL(group=R): one launch per layer for all R, each recording with its own weights); chains x R "
                     "recordings in flight.  Default 2 chains x 4 (r04, driver form on one box: 805 audio-s/s against 791 for 3 chains x 1, "
                     "profiles/r04_ab_lockstep_driver_form.log); --lockstep 1 --chains 3 is the r03 configuration")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the live roofline sampling in the "
+                    "timed region, and after it the side rates (value_degenerate_labels, value_boundary, value_online), other_workloads and "
+                    "cpu_baseline + parity (each as selected by the options above)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None, help="after the timed steps, write what the last "
+                    "timed step returned as DIR/<name>.npy (see dump_outputs)")
+    a = ap.parse_args()
+    if a.prewarm_s is None:
+        a.prewarm_s = FULL_PREWARM_S if a.full else PLAIN_PREWARM_S
+    return a
 
 
 def self_launch(a):
@@ -142,6 +158,32 @@ def pick_chains(max_chains, steps):
         if cost <= best_cost + 1e-9:
             best, best_cost = c, cost
     return best
+
+
+def prewarm_frames(n_frames, seq_len, overlap, final_batch):
+    """Length of the prewarm recording: the timed recording cut short from its end, so that it keeps every shape the timed recording
+    launches — the same short last window, and in the final pass the same batches of `final_batch` full windows plus the same
+    remainder batch — with two full batches instead of all of them (a shape is captured the second time a chain sees it)."""
+    stride = seq_len - overlap
+    n_win = 1
+    while n_frames > seq_len and n_frames - (n_win - 1) * stride >= seq_len:   # prepare_chunks: up to and including the first shorter window
+        n_win += 1
+    keep = 1 + (n_win - 1) % final_batch + 2 * final_batch
+    return n_frames - max(0, n_win - keep) * stride
+
+
+def dump_outputs(out_dir, log_probs, hyp_ids):
+    """What the last timed step returned, as float32 / float64 .npy files: `log_probs` — the stitched log-probs [T_ds, V+1] of its
+    recording (all rows when they fit in DUMP_BYTES, else a fixed seeded sample of rows), `log_probs_rows` — the row index of every
+    dumped row, `hyp_ids` — its greedy transcript ids."""
+    import numpy as np
+    lp = log_probs.float().cpu().numpy() if torch.is_tensor(log_probs) else np.asarray(log_probs, dtype=np.float32)
+    n = max(1, min(lp.shape[0], DUMP_BYTES // (4 * lp.shape[1])))
+    rows = np.arange(lp.shape[0]) if n == lp.shape[0] else np.sort(np.random.default_rng(0).choice(lp.shape[0], n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "log_probs.npy"), np.ascontiguousarray(lp[rows], dtype=np.float32))
+    np.save(os.path.join(out_dir, "log_probs_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "hyp_ids.npy"), np.asarray(hyp_ids, dtype=np.float64).reshape(-1))
 
 
 def make_args(a):
@@ -454,6 +496,38 @@ def other_workloads(a, model, dev, which=('awmc', 'wav2vec2_su', 'enc_dec_teache
     return out
 
 
+def roofline(a, prof, dt, n_chains):
+    """The `roofline` object of a --full run: the fp32-MFMA GEMM family, from the live sampling of the timed region (ops.gemm_profile_*)."""
+    WEVERY = max(2, a.sample_every)
+    def tfs(k):
+        return prof[k]["flops"] / (prof[k]["ms"] * 1e-3) / 1e12 if prof and prof[k]["ms"] > 0 else None
+    shared, excl = tfs("shared"), tfs("exclusive")
+    if n_chains == 1 and shared is not None and excl is not None:   # one chain: both kinds are the same measurement
+        fl = prof["shared"]["flops"] + prof["exclusive"]["flops"]
+        shared = excl = fl / ((prof["shared"]["ms"] + prof["exclusive"]["ms"]) * 1e-3) / 1e12
+    achieved = excl if excl is not None else shared
+    return {"bound": "mfma", "achieved": None if achieved is None else round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS,
+            "unit": "TFLOP/s", "frac": None if achieved is None else round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
+            "traffic": pmc_traffic(), "kernel": "gemm_f32_kernel (v_mfma_f32_32x32x2_f32)",
+            "algorithmic_bytes_per_launch": round(prof["bytes"] / prof["calls"]) if prof and prof["calls"] else None,
+            "flop_per_launch": round(prof["flops"] / prof["calls"]) if prof and prof["calls"] else None,
+            "achieved_shared": None if shared is None else round(shared, 2),
+            # whole-job check: all matrix-core flops of the timed region (GEMM launches + the fused attention of the final pass) / its wall
+            # time (every kernel, sync and gap included)
+            # extrapolated from the eagerly run (sampled) steps: only quoted when there are enough of them (>= 30; the driver's 20-step form has ~65)
+            "job_gemm_tflops": round((prof["flops"] + prof["attn_flops"]) * (WEVERY if a.graphs else 1) / dt / 1e12, 2)
+                               if prof and (not a.graphs or prof.get("sampled_steps", 0) >= 30) else None,
+            "gemm_launches": prof["calls"] if prof else 0,
+            "sampled_launches": (prof["exclusive"]["sampled"], prof["shared"]["sampled"]) if prof else 0,
+            "gemm_tflop_per_step": round(prof["flops"] * (WEVERY if a.graphs else 1) / a.steps / 1e12, 2)
+                                   if prof and (not a.graphs or prof.get("sampled_steps", 0) >= 30) else None,
+            "sampled_steps": prof.get("sampled_steps") if prof else None,
+            "sampling": f"every 4th GEMM launch of every {WEVERY}th window step (those steps run eagerly; the rest replay "
+                        "hipGraphs); `achieved` = launches timed with the other chains drained (kernel's own duration), "
+                        "`achieved_shared` = launches timed while the other chains share the GPU"
+                        if a.graphs else "every 4th GEMM launch"}
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:       # not under torchrun: become the launcher (nothing has touched the GPU yet)
@@ -493,8 +567,9 @@ def main():
 
     decoder = GreedyCTCDecoder(tok, blank_id=a.vocab, device=dev)
 
-    def run_many(spec_list, tokenizer=None, pcie=None, online=None, group_sizes=None):
-        """`n_chains` recordings in flight: one stream + one model replica each, advanced round-robin by one host thread."""
+    def run_many(spec_list, tokenizer=None, pcie=None, online=None, group_sizes=None, keep_last=None):
+        """`n_chains` recordings in flight: one stream + one model replica each, advanced round-robin by one host thread.
+        `keep_last`: a list that receives the last recording's log-probs."""
         pcie = a.pcie if pcie is None else pcie
         run_args = args
         if online is not None and bool(online) != bool(a.online):
@@ -502,6 +577,8 @@ def main():
         n_groups = len(group_sizes) if group_sizes and R > 1 else len(lib.lockstep_group_sizes(len(spec_list), R, len(models)))
         outs = lib.dynamic_eval_many(run_args, models[:max(1, min(len(models), n_groups))], spec_list, a.seq_len, a.overlap, tokenizer or tok,
                                      use_tqdm=False, return_device=not pcie, **({"group_sizes": group_sizes} if group_sizes and R > 1 else {}))
+        if keep_last is not None:
+            keep_last.append(outs[-1])
         if pcie:   # the reference's contract: np.float32 [T_ds, V+1] back on the host (lib.py:640), decoded from there
             return [decoder.ids(torch.from_numpy(o).to(dev)) for o in outs]
         return [decoder.ids(o) for o in outs]
@@ -528,36 +605,45 @@ def main():
     for m in models[1:]:                       # every chain starts from the same weights
         m.flat_params.copy_(model.flat_params)
     progress("models built, calibrated; prewarm")
-    if a.prewarm_s > 0:     # untimed, before the W warm-up steps: the workload itself, until the GPU has been under load for prewarm_s
-        t_end = time.perf_counter() + a.prewarm_s
-        while time.perf_counter() < t_end:
-            run_many(specs[:1] * (n_chains * R))
-        if R > 1 and a.graphs:
-            # lib.lockstep_group_sizes may cut the K recordings into groups SMALLER than R (20 on 2 chains: 4 4 3 3 3 3); a partial group's replica
-            # range has graphs of its own (model.py::_graph_pool), captured the second time it is seen — here, on every chain, not inside the timed region
-            for n in sorted({sz for sz in lib.lockstep_group_sizes(a.steps, R, n_chains) if sz != R}, reverse=True):
-                for _ in range(2):
-                    run_many(specs[:1] * (n * n_chains), group_sizes=[n] * n_chains)
-                    progress(f"prewarmed groups of {n}")
+    # Untimed, before the W warm-up steps.  Every launch sequence of the timed region is captured here, on every chain and for every
+    # lockstep group size the timed recordings are cut into (lib.lockstep_group_sizes: 20 on 2 chains -> 4 4 3 3 3 3; a group size's
+    # replica range has graphs of its own, model.py::_graph_pool, captured the second time a chain sees a shape), on a short recording
+    # of the same window structure (prewarm_frames); then that load until the GPU has been under it for prewarm_s.
+    t_end = time.perf_counter() + a.prewarm_s
+    short = [specs[0][:, :, :prewarm_frames(n_frames, a.seq_len, a.overlap, a.final_batch)].contiguous()]
+    sizes = sorted(set(lib.lockstep_group_sizes(a.steps, R, n_chains))) if R > 1 else [1]
+    for _ in range(2 if a.graphs else 1):
+        for n in sizes:
+            run_many(short * (n * n_chains), group_sizes=[n] * n_chains)
+    progress(f"captured groups of {sizes}")
+    while time.perf_counter() < t_end:
+        run_many(short * (sizes[-1] * n_chains), group_sizes=[sizes[-1]] * n_chains)
     progress("warm-up steps")
     if a.warmup:
         run_many(specs[:a.warmup])              # W untimed steps (every chain's stream and workspace was already warmed by the prewarm)
     ddist.barrier()
     torch.cuda.synchronize(dev)
-    # Live roofline sampling.  Graph replays cannot be timed per launch, so every WEVERY-th window step of the timed region
-    # runs eagerly with a HIP-event pair around every 4th GEMM launch.  Sampled steps alternate between "shared" (the other
-    # chains keep the GPU busy: the duration a launch sees in this job, what rocprofv3 of this command averages) and
-    # "exclusive" (the device is drained around the step: the kernel's own duration, what rocprofv3 --chains 1 averages).
-    WEVERY = max(2, a.sample_every)
-    ops.gemm_profile_start(every=4, window_every=WEVERY if a.graphs else 0)
+    torch.manual_seed(1234 + rank)              # the SpecAugment masks of the timed steps do not depend on how long the prewarm ran
+    prof = None
+    if a.full:
+        # Live roofline sampling.  Graph replays cannot be timed per launch, so every WEVERY-th window step of the timed region
+        # runs eagerly with a HIP-event pair around every 4th GEMM launch.  Sampled steps alternate between "shared" (the other
+        # chains keep the GPU busy: the duration a launch sees in this job, what rocprofv3 of this command averages) and
+        # "exclusive" (the device is drained around the step: the kernel's own duration, what rocprofv3 --chains 1 averages).
+        ops.gemm_profile_start(every=4, window_every=max(2, a.sample_every) if a.graphs else 0)
     progress(f"timed region: {a.steps} steps")
+    last = []
     t0 = time.perf_counter()
-    hyps = run_many(specs[a.warmup:a.warmup + a.steps])
+    hyps = run_many(specs[a.warmup:a.warmup + a.steps], keep_last=last)
     torch.cuda.synchronize(dev)
     ddist.barrier()
     dt = time.perf_counter() - t0
-    progress(f"timed region done in {dt:.1f} s; side measurements")
-    prof = ops.gemm_profile_stop()
+    progress(f"timed region done in {dt:.1f} s")
+    if a.full:
+        prof = ops.gemm_profile_stop()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last[0], hyps[-1])
+    del last
     if os.environ.get("DYN_DEBUG_HOST"):
         print(f"[host] wall {dt:.3f} s, blocked on pseudo-label ids {lib.HOST_WAIT[0]:.3f} s (incl. warm-up)", file=sys.stderr)
     dt = ddist.max_over_ranks(dt)
@@ -567,7 +653,7 @@ def main():
     # boundary-faithful rate (host spectrogram in, numpy log-probs out, decoded from the host copy: reference lib.py:549,640)
     side = {}
     n_side = n_chains * R if a.side_steps < 0 else a.side_steps
-    if world == 1 and n_side > 0:
+    if a.full and world == 1 and n_side > 0:
         sl = specs[a.warmup:a.warmup + min(n_side, a.steps)]
         if a.label_tokens > 0:
             side["value_degenerate_labels"] = round(a.seconds * len(sl) / timed(sl, tokenizer=plain_tok), 3)
@@ -581,13 +667,6 @@ def main():
 
     if rank == 0:
         audio_s = a.seconds * a.steps * world
-        def tfs(k):
-            return prof[k]["flops"] / (prof[k]["ms"] * 1e-3) / 1e12 if prof and prof[k]["ms"] > 0 else None
-        shared, excl = tfs("shared"), tfs("exclusive")
-        if n_chains == 1 and shared is not None and excl is not None:   # one chain: both kinds are the same measurement
-            fl = prof["shared"]["flops"] + prof["exclusive"]["flops"]
-            shared = excl = fl / ((prof["shared"]["ms"] + prof["exclusive"]["ms"]) * 1e-3) / 1e12
-        achieved = excl if excl is not None else shared
         out = {
             "metric": "audio-sec/s dynamic-eval (fwd+1 adapt step)", "value": round(audio_s / dt, 3), "unit": "audio-s/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
@@ -599,38 +678,20 @@ def main():
                        "sharding": f"{world} ranks x {a.steps} recordings, no data-path collective",
                        "chains_per_gpu": n_chains, "lockstep_group": R, "hip_graphs": bool(a.graphs), "pcie_inclusive": bool(a.pcie), "prewarm_s": a.prewarm_s,
                        "blank_bias": round(a.blank_bias, 4), "hyp_tokens_per_recording": [len(h) for h in hyps]},
-            "roofline": {"bound": "mfma", "achieved": None if achieved is None else round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": None if achieved is None else round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
-                         "traffic": pmc_traffic(), "kernel": "gemm_f32_kernel (v_mfma_f32_32x32x2_f32)",
-                         "algorithmic_bytes_per_launch": round(prof["bytes"] / prof["calls"]) if prof and prof["calls"] else None,
-                         "flop_per_launch": round(prof["flops"] / prof["calls"]) if prof and prof["calls"] else None,
-                         "achieved_shared": None if shared is None else round(shared, 2),
-                         # whole-job check: all matrix-core flops of the timed region (GEMM launches + the fused attention of the final pass) / its wall
-                         # time (every kernel, sync and gap included)
-                         # extrapolated from the eagerly run (sampled) steps: only quoted when there are enough of them (>= 30; the driver's 20-step form has ~65)
-                         "job_gemm_tflops": round((prof["flops"] + prof["attn_flops"]) * (WEVERY if a.graphs else 1) / dt / 1e12, 2)
-                                            if prof and (not a.graphs or prof.get("sampled_steps", 0) >= 30) else None,
-                         "gemm_launches": prof["calls"] if prof else 0,
-                         "sampled_launches": (prof["exclusive"]["sampled"], prof["shared"]["sampled"]) if prof else 0,
-                         "gemm_tflop_per_step": round(prof["flops"] * (WEVERY if a.graphs else 1) / a.steps / 1e12, 2)
-                                                if prof and (not a.graphs or prof.get("sampled_steps", 0) >= 30) else None,
-                         "sampled_steps": prof.get("sampled_steps") if prof else None,
-                         "sampling": f"every 4th GEMM launch of every {WEVERY}th window step (those steps run eagerly; the rest replay "
-                                     "hipGraphs); `achieved` = launches timed with the other chains drained (kernel's own duration), "
-                                     "`achieved_shared` = launches timed while the other chains share the GPU"
-                                     if a.graphs else "every 4th GEMM launch"},
             "hyp_tokens_total": int(tokens_total[0]),
         }
+        if a.full:
+            out["roofline"] = roofline(a, prof, dt, n_chains)
         out.update(side)
         out["config"]["label_tokens_per_window"] = a.label_tokens
         side_model = model
-        if R > 1 and world == 1 and (a.side_workloads or not a.no_cpu_baseline):   # the side legs drive one recording at a time: a plain model
+        if a.full and R > 1 and world == 1 and (a.side_workloads or not a.no_cpu_baseline):   # the side legs drive one recording at a time: a plain model
             side_model = SCConformerXL(vocab_size=a.vocab, device=dev)
             side_model.load_state_dict(model.state_dict())
-        if world == 1 and a.side_workloads:
+        if a.full and world == 1 and a.side_workloads:
             progress("side: online done; other workloads")
             out["other_workloads"] = other_workloads(a, side_model, dev)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             progress("cpu baseline + parity")
             for m in models + [side_model]:                            # the parity leg runs on the bench's own (restored) weights
                 m.use_graphs = bool(a.graphs)

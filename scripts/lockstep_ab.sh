@@ -2,7 +2,7 @@
 # Lockstep A/B on ONE box (r04): chains vs lockstep groups, before and after tuning the GEMM table for the group's batched shapes.
 #   scripts/lockstep_ab.sh out_dir           (run from the repository root on the GPU box)
 out=${1:-gpurun_out/lockstep_ab}; mkdir -p "$out"
-COMMON="--warmup 0 --prewarm_s 20 --no_cpu_baseline --side_steps 0 --side_workloads 0"
+COMMON="--warmup 0 --prewarm_s 20 --full --no_cpu_baseline --side_steps 0 --side_workloads 0"
 run() {  # name, bench args...
     name=$1; shift
     python bench.py $COMMON "$@" > "$out/$name.json" 2> "$out/$name.err" || { echo "$name FAILED"; tail -n 5 "$out/$name.err"; return; }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Second lockstep A/B (r04), driver-form runs on ONE box: which (chains, lockstep) becomes bench.py's default.
 out=${1:-gpurun_out/lockstep_ab2}; mkdir -p "$out"
-COMMON="--no_cpu_baseline --side_steps 0 --side_workloads 0"
+COMMON="--full --no_cpu_baseline --side_steps 0 --side_workloads 0"
 run() {
     name=$1; shift
     python bench.py $COMMON "$@" > "$out/$name.json" 2> "$out/$name.err" || { echo "$name FAILED"; tail -n 5 "$out/$name.err"; return; }

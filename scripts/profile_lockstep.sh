@@ -5,7 +5,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-common="--warmup 0 --no_cpu_baseline --side_steps 0 --side_workloads 0"
+common="--warmup 0 --full --no_cpu_baseline --side_steps 0 --side_workloads 0"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$out/l${R}c${CH}" -o p -- python3 "$root/bench.py" --steps $ST --prewarm_s 10 --chains $CH --lockstep $R $common > "$out/l${R}c${CH}.json" 2> "$out/l${R}c${CH}.err" && echo "profile done"
 cd "$root"
 mkdir -p "$out/summary"

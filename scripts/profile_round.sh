@@ -8,7 +8,7 @@ out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 B="$root/bench.py"
-common="--warmup 0 --no_cpu_baseline --side_steps 0 --side_workloads 0"
+common="--warmup 0 --full --no_cpu_baseline --side_steps 0 --side_workloads 0"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$out/c1" -o p -- python3 "$B" --steps 2 --prewarm_s 10 --chains 1 --lockstep 1 $common > "$out/c1.json" 2> "$out/c1.err" && echo "c1 done" \
 && rocprofv3 --output-format csv --kernel-trace --stats -d "$out/c3" -o p -- python3 "$B" --steps 8 --prewarm_s 10 $common > "$out/c3.json" 2> "$out/c3.err" && echo "c3 done" \
 && rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d "$out/fetch" -o p -- python3 "$B" --steps 1 --seconds 300 --prewarm_s 0 --graphs 0 --chains 1 --lockstep 1 $common > "$out/fetch.json" 2> "$out/fetch.err" && echo "fetch done" \

@@ -198,11 +198,11 @@ def test_run_in_dataset_eval_and_run_alias(cuda, tmp_path, capsys):
 
 
 def test_bench_contract(cuda):
-    """bench.py prints ONE JSON line with the driver's keys plus `roofline` (and `cpu_baseline` unless disabled)."""
+    """bench.py --full prints ONE JSON line with the driver's keys plus `roofline` (and `cpu_baseline` unless disabled)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--seconds", "200", "--steps", "2", "--warmup", "1", "--no_cpu_baseline", "--prewarm_s", "0"],
-                       capture_output=True, text=True, timeout=600, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--seconds", "200", "--steps", "2", "--warmup", "1", "--no_cpu_baseline", "--prewarm_s", "0",
+                        "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -223,6 +223,28 @@ def test_bench_contract(cuda):
     assert all(v.get("value", 0) > 0 and v["unit"] == "audio-s/s" for k, v in ow.items() if k != "soft_dtw"), ow
     assert len(ow["soft_dtw"]) == 4 and all(r["value_matches_oracle"] and r["us_per_diagonal"] > 0 for r in ow["soft_dtw"]), ow["soft_dtw"]
     assert 0 < ow["wav2vec2_su"]["roofline"]["frac"] < 1
+
+
+def test_bench_plain_run_and_dump_outputs(cuda, tmp_path):
+    """A plain bench.py run prints the headline line only (no side legs), and --dump-outputs writes the last timed step's
+    stitched log-probs and transcript ids as float32 / float64 .npy files."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--seconds", "200", "--steps", "3", "--warmup", "1", "--prewarm_s", "0",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True and d["unit"] == "audio-s/s"
+    assert abs(d["value"] - 3 * 200.0 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-3
+    assert not {"roofline", "cpu_baseline", "parity", "other_workloads", "value_boundary", "value_online", "value_degenerate_labels"} & set(d), d.keys()
+    lp, rows, ids = (np.load(tmp_path / f) for f in ("log_probs.npy", "log_probs_rows.npy", "hyp_ids.npy"))
+    assert lp.dtype == np.float32 and rows.dtype == np.float64 and ids.dtype == np.float64
+    assert lp.ndim == 2 and lp.shape[1] == 4096 and rows.shape == (lp.shape[0],) and np.all(np.diff(rows) > 0)
+    assert np.isfinite(lp).all()
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
 
 
 def test_run_cross_speaker_gender(cuda, tmp_path, capsys):

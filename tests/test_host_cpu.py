@@ -304,6 +304,26 @@ def test_bench_chain_count_avoids_a_lone_last_recording():
     assert m.pick_chains(1, 7) == 1
 
 
+def test_bench_prewarm_recording_keeps_the_timed_window_shapes():
+    """The prewarm recording is the timed one cut short: the same last window and the same final-pass batch shapes, each full
+    batch twice, so the prewarm captures every graph the timed region replays (1 h at 16384 / 14336: 9 of 169 windows)."""
+    import importlib.util
+    from dynamic_asr_eval_amd.lib import prepare_chunks
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
+
+    def lens(n, seq_len, overlap):
+        d, keys = prepare_chunks(torch.empty(1, 1, n), seq_len, overlap)
+        return [d[k].shape[-1] for k in keys]
+    assert m.prewarm_frames(360000, 16384, 14336, 4) == 32320 and len(lens(32320, 16384, 14336)) == 9
+    for seq_len, overlap in ((16384, 14336), (4096, 1024), (2048, 0)):
+        for n in list(range(1000, 40000, 997)) + [360000, 415990, 16384 + 5 * 2048]:
+            for fb in (1, 4, 5):
+                short, full = lens(m.prewarm_frames(n, seq_len, overlap, fb), seq_len, overlap), lens(n, seq_len, overlap)
+                n_full = sum(1 for x in full if x == seq_len)
+                assert short[-1] == full[-1] and sum(1 for x in short if x == seq_len) in (n_full, n_full % fb + 2 * fb)
+
+
 def test_product_package_never_imports_the_oracle():
     """The oracle is a checker: no module of the product package (or bench.py outside its cpu_baseline leg) may import it."""
     import ast, glob
