@@ -33,6 +33,59 @@ except Exception:  # pragma: no cover
         return x
 
 
+# ------------------------------------------------------------------------------------------------ LM beam search
+class BeamSearchFactory:
+    """What reference lcasr/lib.py:37-72 `load_beamsearch` returns (a functools.partial of BeamSearch): call it with
+    `log_probs=` ([T, V+1] device tensor, CPU tensor or numpy) and `beam_width=`."""
+
+    def __init__(self, language_model, tokenizer, bos_id, **kw):
+        self.language_model, self.tokenizer, self.bos_id, self.kwargs = language_model, tokenizer, bos_id, kw
+
+    def __call__(self, log_probs, beam_width, stream=None):
+        from .decoding import BeamSearch
+        return BeamSearch(tokenizer=self.tokenizer, beam_width=beam_width, log_probs=log_probs, language_model=self.language_model,
+                          bos_id=self.bos_id, stream=stream, **self.kwargs)
+
+
+def load_beamsearch(path=None, alpha=0.45, beta=1.53, prune_less_than_val=3.17, top_am_threshold=-6, tokenizer=None, device=None,
+                    lm_config=None, lm_seed=0, allow_missing=False):
+    """Reference lcasr/lib.py:37-72: the LM checkpoint ({'model': state_dict, 'config': {...}}, `module.` prefixes stripped),
+    blank_id = vocab size, max_cache_length = 128, bos_id = tokenizer.bos_id() (0 where the tokenizer has none).  Without `path`
+    a seeded synthetic LM (lm.DEFAULT_LM_CONFIG or `lm_config`, seed `lm_seed`) is built, with a warning."""
+    from .lm import TransformerLM
+    if tokenizer is None:
+        from .tokenizer import SyntheticTokenizer
+        tokenizer = SyntheticTokenizer(128)
+    if not isinstance(beta, (int, float)) or not isinstance(alpha, (int, float)):
+        raise TypeError('load_beamsearch: alpha and beta must be numbers')
+    if prune_less_than_val is not None and not prune_less_than_val >= 0:
+        raise ValueError(f'load_beamsearch: prune_less_than_val must be >= 0 or None (got {prune_less_than_val})')
+    if not top_am_threshold <= 0:
+        raise ValueError(f'load_beamsearch: top_am_threshold must be <= 0 (got {top_am_threshold})')
+    if device is None:
+        if not torch.cuda.is_available():
+            raise ops.DynError('load_beamsearch: the beam search runs on the GPU and none is available')
+        device = torch.device('cuda', torch.cuda.current_device())
+    vocab = tokenizer.vocab_size()
+    if path:
+        lm = TransformerLM.from_checkpoint(path, vocab, device, allow_missing=allow_missing)
+    else:
+        print(f'WARNING: no LM checkpoint given: the beam search uses a seeded synthetic LM (seed {lm_seed})')
+        lm = TransformerLM.synthetic(vocab, device, cfg=lm_config, seed=lm_seed)
+    bos = tokenizer.bos_id() if hasattr(tokenizer, 'bos_id') else -1
+    return BeamSearchFactory(lm, tokenizer, bos if bos is not None and bos >= 0 else 0, blank_id=vocab, alpha=alpha, beta=beta,
+                             prune_less_than_val=prune_less_than_val, top_am_threshold=top_am_threshold)
+
+
+def beamsearch_from_args(args, tokenizer, device):
+    """-beamsearch with -kwargs lm_alpha / lm_beta / lm_prune_less_than_val / lm_top_am_threshold / lm_checkpoint."""
+    a = args.__dict__
+    return load_beamsearch(a.get('lm_checkpoint') or None, alpha=a.get('lm_alpha', 0.45), beta=a.get('lm_beta', 1.53),
+                           prune_less_than_val=a.get('lm_prune_less_than_val', 3.17), top_am_threshold=a.get('lm_top_am_threshold', -6),
+                           tokenizer=tokenizer, device=device, lm_seed=int(a.get('lm_seed', 0)),
+                           allow_missing=bool(a.get('allow_missing', False)))
+
+
 # ------------------------------------------------------------------------------------------------ arg -> config helpers
 def get_specaugment_config_from_args(args):
     a = {k.replace('spec_augment_', ''): v for k, v in args.__dict__.items() if k.startswith('spec_augment')}
@@ -195,8 +248,10 @@ def _dynamic_eval_gen(
     """Generator form of dynamic_eval_ctc_loss: yields where the host would otherwise block on the GPU (the per-window
     pseudo-label ids) or has queued a batch of independent work, so a driver can interleave several recording chains on
     separate streams from ONE host thread (dynamic_eval_many).  The return value travels in StopIteration.value."""
-    if beam_search_fn is not None and args.__dict__.get('lm_tta_beams', 3) != 0:
+    tta_beams = int(args.__dict__.get('lm_tta_beams', 3))
+    if beam_search_fn is not None and tta_beams != 0 and not isinstance(beam_search_fn, BeamSearchFactory):
         _unsupported("LM beam-search pseudo-labels (beam_search_fn)")
+    beam_tta = beam_search_fn is not None and tta_beams != 0
     device = model.device
     if torch.device(device).type != "cuda":
         raise ops.DynError("dynamic_eval: model.device must be a GPU (no CPU fallback)")
@@ -330,23 +385,28 @@ def _dynamic_eval_gen(
                 out = model(audio_signal=audio_chunk)
             post = out['final_posteriors']  # [B, N, C] on device
 
-            # greedy ids on device (reference lib.py:559); only the ids cross PCIe, asynchronously into pinned memory
-            ids_dev, n_dev = ops.ctc_greedy(post[-1].detach(), blank)
-            if pinned is None or pinned[0].shape[1] < ids_dev.shape[1]:
-                pinned = (torch.empty(1, ids_dev.shape[1], dtype=torch.int32, pin_memory=True), torch.empty(1, dtype=torch.int32, pin_memory=True))
-            pinned[0][:, :ids_dev.shape[1]].copy_(ids_dev, non_blocking=True)
-            pinned[1].copy_(n_dev, non_blocking=True)
-            ready = torch.cuda.Event()
-            ready.record()
-            if sampled:
-                ops.gemm_profile_before_yield(sampled, ready)
-            yield                                            # another chain may use the host while this forward runs
-            _t0 = time.perf_counter()
-            if ops.gemm_profile_active():        # also for unsampled steps: the mode is per model call, chains interleave on this thread
-                ops.gemm_profile_resume_step(device, sampled)
-            ready.synchronize()
-            HOST_WAIT[0] += time.perf_counter() - _t0
-            pseudo_targets = tokenizer.decode(pinned[0][0, :int(pinned[1][0])].tolist())
+            if beam_tta:    # reference lib.py:560-563: the clean copy's posteriors through the LM beam search, on the device
+                bs = beam_search_fn(log_probs=post[-1].detach(), beam_width=tta_beams)
+                bs.run_search(use_tqdm=False)     # enqueued whole; only the final beams come back
+                pseudo_targets = bs.return_text(idx=0)
+            else:
+                # greedy ids on device (reference lib.py:559); only the ids cross PCIe, asynchronously into pinned memory
+                ids_dev, n_dev = ops.ctc_greedy(post[-1].detach(), blank)
+                if pinned is None or pinned[0].shape[1] < ids_dev.shape[1]:
+                    pinned = (torch.empty(1, ids_dev.shape[1], dtype=torch.int32, pin_memory=True), torch.empty(1, dtype=torch.int32, pin_memory=True))
+                pinned[0][:, :ids_dev.shape[1]].copy_(ids_dev, non_blocking=True)
+                pinned[1].copy_(n_dev, non_blocking=True)
+                ready = torch.cuda.Event()
+                ready.record()
+                if sampled:
+                    ops.gemm_profile_before_yield(sampled, ready)
+                yield                                            # another chain may use the host while this forward runs
+                _t0 = time.perf_counter()
+                if ops.gemm_profile_active():        # also for unsampled steps: the mode is per model call, chains interleave on this thread
+                    ops.gemm_profile_resume_step(device, sampled)
+                ready.synchronize()
+                HOST_WAIT[0] += time.perf_counter() - _t0
+                pseudo_targets = tokenizer.decode(pinned[0][0, :int(pinned[1][0])].tolist())
             if verbose and not args.__dict__.get('not_verbose', False) and args.__dict__.get('print_predictions', False):
                 print(f'Pseudo targets: {pseudo_targets}')
                 print(f'Noisy predictions: {decoder(post[0].detach())}\n--\n')

@@ -81,12 +81,26 @@ def main(args):
     if args.consistency:
         raise NotImplementedError('dynamic_eval_consistency_ctc_loss is out of scope (SURVEY.md §2 row 3)')
     eval_fn = lib.AWMC if args.awmc else dynamic_eval                   # reference run_dynamic_eval_full.py:67-72
+    # -beamsearch (reference :56-65,99-104): final texts from the LM beam search with lm_eval_beams; TTA pseudo-labels from it
+    # too unless lm_tta_beams=0 (then no beam_search_fn reaches the eval function: the reference's `beams == 0` branch)
+    beamsearch = lib.beamsearch_from_args(args, tokenizer, device) if args.__dict__.get('beamsearch', False) else None
+    eval_beams = int(args.__dict__.get('lm_eval_beams', 20))
+    beam_search_fn = beamsearch if beamsearch is not None and int(args.__dict__.get('lm_tta_beams', 3)) != 0 else None
+
+    def final_text(log_probs):
+        if beamsearch is None:
+            return decoder(log_probs)
+        bs = beamsearch(log_probs=log_probs, beam_width=eval_beams)
+        bs.run_search(use_tqdm=False)
+        return bs.return_text(idx=0)
     mine = ddist.shard_longest_first([d.get('frames', 1) for d in data], world)[rank]
 
     chains = int(args.__dict__.get('chains', 1))    # -kwargs chains=N: N recordings in flight per GPU (lib.dynamic_eval_many)
     lockstep = int(args.__dict__.get('lockstep', 1))   # -kwargs lockstep=R: every chain is a lockstep group of R recordings (lib._dynamic_eval_group_gen)
     models = None
-    if lockstep > 1 and not args.awmc and len(mine) > 1:
+    if beam_search_fn is not None:
+        pass                                        # beam-search pseudo-labels: single-chain path (lib.lockstep_supported)
+    elif lockstep > 1 and not args.awmc and len(mine) > 1:
         from .run_seq_eval import replicate
         models = replicate(model, max(1, min(chains, (len(mine) + lockstep - 1) // lockstep)), group=lockstep)
     elif chains > 1 and not args.awmc and len(mine) > 1:
@@ -101,7 +115,7 @@ def main(args):
             stime = time.time()
             outs = lib.dynamic_eval_many(args, models, [a for a, _ in loaded], args.seq_len, args.overlap, tokenizer,
                                          use_tqdm=False, return_device=True)
-            texts = [decoder(o) for o in outs]
+            texts = [final_text(o) for o in outs]
             torch.cuda.synchronize(device)
             per_rec = (time.time() - stime) / max(1, len(mine))      # chains overlap: only the mean is meaningful
             for rec, (_, gold_text), out_text in zip(mine, loaded, texts):
@@ -113,9 +127,9 @@ def main(args):
                 print('\n-------\n' + data[rec]['id'] + '\n-------\n')
             audio_spec, gold_text = data[rec]['process_fn'](data[rec])
             stime = time.time()
-            logits = eval_fn(args, model, audio_spec, args.seq_len, args.overlap, tokenizer, beam_search_fn=None,
+            logits = eval_fn(args, model, audio_spec, args.seq_len, args.overlap, tokenizer, beam_search_fn=beam_search_fn,
                              use_tqdm=(rank == 0 and not args.not_verbose), return_device=True)
-            out_text = decoder(logits)
+            out_text = final_text(logits)
             torch.cuda.synchronize(device)
             etime = time.time()
             out = normalize(out_text).lower()

@@ -527,6 +527,29 @@ int dyn_softdtw_fwd(const float* D, double* R, float* value, int64_t B, int64_t 
 int dyn_softdtw_bwd(const float* D, const double* R, float* E, int64_t B, int64_t N, int64_t M, float gamma, float bandwidth,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CTC + transformer-LM beam search (reference lcasr/ctc_beam_search.py:89-319 with max_cache_length = 128, lcasr/lib.py:37-72).
+ *   dyn_beam_search   the whole search over log_probs [frames, ld] (n_classes = vocab + 1, blank = n_classes - 1), enqueued on
+ *                     `stream` without a host synchronisation: per frame one bookkeeping kernel (candidates, CTC prefix rules, exact
+ *                     merge, stable top-k, relative prune when use_prune != 0) and one LM step for the new beams.  The final beams
+ *                     stay in the workspace (dyn_beam_layout gives the offsets); header word 2 != 0 reports a failed search.
+ *   dyn_beam_lm_rows  one LM step for the rows the workspace's row arrays describe (token, position, history slots, output slot)
+ *   lm_ptrs: host array of device pointers — embed [vocab, d], positions [max_positions, d], norm_out w / b, head w [vocab, d] / b,
+ *            then per layer: self.norm w / b, self.qkv w [3d, d] / b, self.out w / b, ff.norm w / b, ff.w1 [d_ff, d], ff.w2 [d, d_ff].
+ *   dyn_beam_layout   offsets[18]: header, beam node / trailing blank / score / history length / history, node parent / token,
+ *                     pool log-probs, row token / position / history length / slot / history, pool K/V, node capacity, pool slots,
+ *                     total bytes.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t dyn_beam_workspace_bytes(int32_t width, int64_t frames, int32_t layers, int32_t d_model, int32_t d_ff, int32_t vocab);
+int dyn_beam_layout(int32_t width, int64_t frames, int32_t layers, int32_t d_model, int32_t d_ff, int32_t vocab, int64_t* offsets);
+int dyn_beam_lm_rows(const void* lm_ptrs, int32_t layers, int32_t d_model, int32_t heads, int32_t d_ff, int32_t vocab,
+                     int32_t max_positions, float eps, int32_t width, int64_t frames, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int dyn_beam_search(const float* log_probs, int64_t frames, int64_t ld, int32_t n_classes, const void* lm_ptrs, int32_t layers,
+                    int32_t d_model, int32_t heads, int32_t d_ff, int32_t vocab, int32_t max_positions, float eps, int32_t bos,
+                    int32_t width, float alpha, float beta, float blank_penalty, float repetition_penalty, float top_am_threshold,
+                    float prune_less_than, int32_t use_prune, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
