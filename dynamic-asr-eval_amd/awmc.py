@@ -14,6 +14,7 @@ import time
 import torch
 
 from . import ops
+from ._loop import Stitcher, window_fill_value, window_rule
 from .augment import SpecAugment
 from .decoding import GreedyCTCDecoder
 from .optim import MADGRAD
@@ -61,7 +62,6 @@ def AWMC(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=MA
     device = model.device
     spec_n = spec.shape[-1]
     downsampling_factor = args.config['model']['subsampling_factor']
-    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']
     original_flat = model.flat_params.clone()
     frozen_before = set(model.frozen)
     if args.__dict__.get('bitfit', False):                          # reference lib.py:234-235
@@ -85,19 +85,12 @@ def AWMC(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=MA
     decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=blank, device=device)
     augmentation = SpecAugment(**spec_augment_config)
     fixed_masks = args.__dict__.get('spec_augment_fixed_masks', None)
-    if seq_len > spec_n:
-        seq_len, overlap = spec_n, 0
-    else:
-        overlap = overlap if overlap != -1 else args.config['audio_chunking']['overlap']
-    assert args.config['training'].get("max_seq_len", 0) == 0, 'caching is not used anymore'
-    assert overlap / downsampling_factor == overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
+    seq_len, overlap = window_rule(args, spec_n, seq_len, overlap, downsampling_factor)
     epochs = args.__dict__.get('epochs', 1)
     print_runtimes = args.__dict__.get('print_runtimes', False)
     spec_dev = spec.to(device=device, dtype=torch.float32)
     Fq = spec_dev.shape[1]
-    acc = torch.zeros(spec_n // 4 + seq_len, num_classes, device=device, dtype=torch.float32)
-    cnt = torch.zeros(spec_n // 4 + seq_len, device=device, dtype=torch.float32)
-    pos = end = 0
+    stitch = Stitcher.for_recording(spec_n, seq_len, num_classes, device)
     training_data, training_keys = lib.prepare_chunks(spec_dev, seq_len, overlap)
     training_keys = list(training_data.keys())
     pbar = tqdm(training_keys) if use_tqdm else training_keys
@@ -120,7 +113,7 @@ def AWMC(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=MA
             noisy = clean.clone()
             masks = fixed_masks[i] if fixed_masks is not None else augmentation.draw(Fq, u_len)
             if masks[0][0] or masks[1][0]:
-                augmentation.apply(noisy[0], masks, lib._window_fill_value(noisy[0], augmentation.zero_masking))
+                augmentation.apply(noisy[0], masks, window_fill_value(noisy[0], augmentation.zero_masking))
             with torch.enable_grad():
                 out = model(audio_signal=noisy)
             post = out['final_posteriors']           # [1, N, C]
@@ -146,16 +139,11 @@ def AWMC(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=MA
             if j == epochs - 1:
                 with torch.no_grad():
                     lp = model(audio_signal=clean)['final_posteriors'][0]
-                ds_len = lp.shape[0]
-                overlap_ds = int(overlap / (u_len / ds_len))
-                pos -= overlap_ds if i != 0 else 0
-                ops.stitch_accumulate(lp, acc, cnt, pos)
-                pos += ds_len
-                end = max(end, pos)
+                stitch.add(i, lp, u_len, overlap)
     if print_runtimes:
         torch.cuda.synchronize(device)
         print(f'Runtime: {time.time() - stime}')
-    logits_dev = ops.stitch_finalize(acc, cnt, end)
+    logits_dev = stitch.finalize()
     if return_params:
         updated = [p.clone().detach().cpu() for p in model.parameters()]
     model.flat_params.copy_(original_flat)

@@ -27,10 +27,11 @@ import torch
 
 from . import ops
 from ._lib import DEC_PTRS_PER_LAYER, DecoderDesc, check, load
+from ._loop import augmented_batch, window_rule
 from .augment import SpecAugment
 from .decoding import GreedyCTCDecoder
 from .enc_dec_teacher_filters import should_skip_faulty_teacher_prediction
-from .lib import _window_fill_value, get_lr_args_from_args, get_specaugment_config_from_args, prepare_chunks
+from .lib import get_lr_args_from_args, get_specaugment_config_from_args, prepare_chunks
 from .model import SCConformerXL
 from .optim import MADGRAD
 
@@ -531,17 +532,13 @@ def enc_dec_dynamic_eval(args, model, spec, seq_len, overlap, tokenizer, use_tqd
     device = model.device
     spec = spec.to(device=device, dtype=torch.float32)
     spec_n = spec.shape[-1]
-    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']
     original_flat = model.flat_params.clone()
     optimizer = optim(model.parameters(), **lr_args)
     if optimizer_state is not None:
         optimizer.load_state_dict(optimizer_state)
     augmentation = SpecAugment(**spec_augment_config)
     fixed_masks = args.__dict__.get('spec_augment_fixed_masks', None)
-    if seq_len > spec_n:
-        seq_len, overlap = spec_n, 0
-    else:
-        overlap = overlap if overlap != -1 else args.config['audio_chunking']['overlap']
+    seq_len, overlap = window_rule(args, spec_n, seq_len, overlap, args.config['model']['subsampling_factor'])
     assert overlap == 0, 'Overlap > 0 not implemented for encoder-decoder model'
     print(f'Using seq_len: {seq_len}')
     ctc_decoder = None
@@ -556,13 +553,8 @@ def enc_dec_dynamic_eval(args, model, spec, seq_len, overlap, tokenizer, use_tqd
         for idx in (tqdm(idxs) if use_tqdm else idxs):
             view = training_data[training_keys[idx]][0]                                    # [F, T]
             Fq, u_len = view.shape
-            audio_chunk = torch.empty(num_negatives + 1, Fq, u_len, device=device, dtype=torch.float32)
-            for b in range(num_negatives + 1):
-                audio_chunk[b].copy_(view)
-            for b in range(num_negatives):
-                masks = fixed_masks[training_keys[idx]] if fixed_masks is not None else augmentation.draw(Fq, u_len)
-                if masks[0][0] or masks[1][0]:
-                    augmentation.apply(audio_chunk[b], masks, _window_fill_value(audio_chunk[b], augmentation.zero_masking))
+            audio_chunk = augmented_batch(
+                [view], lambda k: fixed_masks[training_keys[idx]] if fixed_masks is not None else augmentation.draw(Fq, u_len), augmentation)
             with torch.no_grad():
                 encoder_out_for_teacher = model.forward(audio_signal=audio_chunk[-1:].contiguous())
             teacher_pred_tokens = _check_ids(model.generate(audio_chunk[-1:], encoder_states=encoder_out_for_teacher)["text_sequence"],

@@ -20,7 +20,7 @@ import time
 
 import torch
 
-from . import ops
+from . import _loop, ops
 from . import augment as _aug
 from .augment import SpecAugment
 from .decoding import GreedyCTCDecoder
@@ -198,19 +198,6 @@ def _is_native(model):
     return hasattr(model, "flat_params") and hasattr(model, "backward")
 
 
-def _window_fill_value(window, zero_masking):
-    """Fill value of the SpecAugment masks: 0, or the window mean as a 1-element DEVICE tensor (dyn_moments) so that it
-    never makes a host round trip."""
-    if zero_masking:
-        return 0.0
-    from ._lib import check, load
-    out = torch.empty(3, device=window.device, dtype=torch.float32)
-    ws = ops.workspace(window.device)
-    check(load().dyn_moments(window.data_ptr(), window.numel(), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                             torch.cuda.current_stream().cuda_stream), "dyn_moments")
-    return out[1:2]
-
-
 def _unsupported(name):
     raise NotImplementedError(f"{name} is an optional augmentation of the reference that the HIP path does not implement "
                               "yet; refusing to silently run without it")
@@ -257,7 +244,7 @@ def _dynamic_eval_gen(
         raise ops.DynError("dynamic_eval: model.device must be a GPU (no CPU fallback)")
     spec_n = spec.shape[-1]
     downsampling_factor = args.config['model']['subsampling_factor']
-    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']
+    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']    # the cutout density takes it before the window rule
 
     spec_augment_config = get_specaugment_config_from_args(args)
     random_noise = args.__dict__.get('random_noise', 0.0)
@@ -298,13 +285,7 @@ def _dynamic_eval_gen(
     augmentation = SpecAugment(**spec_augment_config)
     fixed_masks = args.__dict__.get('spec_augment_fixed_masks', None)  # test hook: {window_key: masks}
 
-    if seq_len > spec_n:
-        seq_len, overlap = spec_n, 0
-    else:
-        overlap = overlap if overlap != -1 else args.config['audio_chunking']['overlap']
-
-    assert args.config['training'].get("max_seq_len", 0) == 0, 'caching is not used anymore'
-    assert overlap / downsampling_factor == overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
+    seq_len, overlap = _loop.window_rule(args, spec_n, seq_len, overlap, downsampling_factor)
     if verbose:
         print(f'Using seq_len: {seq_len} and overlap: {overlap}')
     assert tokenizer.vocab_size() + 1 == num_classes, 'tokenizer vocabulary does not match the CTC head'
@@ -326,58 +307,38 @@ def _dynamic_eval_gen(
         raise ops.DynError(f"spec must be [1, F, T], got {tuple(spec.shape)}")
     Fq = spec_dev.shape[1]
 
-    # on-device stitch accumulators (reference: two host buffers of spec_n//4 + seq_len rows, lib.py:510)
-    acc_rows = spec_n // 4 + seq_len
-    acc = torch.zeros(acc_rows, num_classes, device=device, dtype=torch.float32)
-    cnt = torch.zeros(acc_rows, device=device, dtype=torch.float32)
-    stitch = {"pos": 0, "end": 0}
-
-    def stitch_window(key, log_probs_2d, u_len):
-        ds_len = log_probs_2d.shape[0]
-        ratio = u_len / ds_len
-        overlap_ds = int(overlap / ratio)
-        stitch["pos"] -= overlap_ds if key != 0 else 0
-        ops.stitch_accumulate(log_probs_2d, acc, cnt, stitch["pos"])
-        stitch["pos"] += ds_len
-        stitch["end"] = max(stitch["end"], stitch["pos"])
-
-    pinned = None
-    tgt_ring, tgt_turn = None, 0
+    stitch = _loop.Stitcher.for_recording(spec_n, seq_len, num_classes, device)
+    labels = _loop.PseudoLabels(1, device, HOST_WAIT)
     if native:
         model.use_graphs = bool(args.__dict__.get('use_graphs', True))   # hipGraph replay of the per-window launch sequences
         # only the augmented copies are differentiated (lib.py:570-575): the clean copy's attention need not keep its probabilities
         model.grad_samples = num_negatives if (skip_zero and _CLEAN_COPY_FUSED_ATTN) else None
     model.eval()  # don't update batchrenorm (reference lib.py:525)
     training_data, training_keys = prepare_chunks(spec_dev, seq_len, overlap)
+
+    def augment_extra(row):     # the optional augmentations of the augmented copy
+        _aug.frame_shuffle(row, **frame_shuffle_args)                 # reference lib.py:542
+        _aug.add_random_noise(row, noise_factor=random_noise)         # lib.py:543
+        _aug.cutout(row, **cutout_args)                               # lib.py:544
+
     for epoch in range(args.__dict__.get('epochs', 1)):
         if verbose:
             print(f'Epoch {epoch + 1} / {epochs}')
         if online and epoch > 0:
             # the reference's loop runs range(args.epochs) even in online mode (lib.py:527) and every epoch overwrites
             # model_outputs[i] (lib.py:589): only the last epoch's posteriors are stitched
-            acc.zero_(); cnt.zero_()
-            stitch["pos"] = stitch["end"] = 0
+            stitch.reset()
         training_keys = list(training_data.keys())
         training_keys = random.sample(training_keys, len(training_keys)) if shuffle else training_keys
         epochs_stime = time.time()
         pbar = tqdm(training_keys) if use_tqdm else training_keys
         for i in pbar:
-            sampled = 0
-            if ops.gemm_profile_active():        # bench.py's live roofline sampling; everything it needs in the loop is in these blocks
-                sampled = ops.gemm_profile_begin_step(device)
+            step = _loop.ProfileStep(device)
             view = training_data[i][0]  # [F, u_len] view into the recording
             u_len = view.shape[-1]
-            audio_chunk = torch.empty(num_negatives + 1, Fq, u_len, device=device, dtype=torch.float32)
-            for b in range(num_negatives + 1):
-                audio_chunk[b].copy_(view)
-            for b in range(num_negatives):  # augment copy 0, copy -1 stays clean (reference lib.py:541)
-                masks = fixed_masks[i] if fixed_masks is not None else augmentation.draw(Fq, u_len)
-                if masks[0][0] or masks[1][0]:
-                    fill = _window_fill_value(audio_chunk[b], augmentation.zero_masking)
-                    augmentation.apply(audio_chunk[b], masks, fill)
-                _aug.frame_shuffle(audio_chunk[b], **frame_shuffle_args)                 # reference lib.py:542
-                _aug.add_random_noise(audio_chunk[b], noise_factor=random_noise)         # lib.py:543
-                _aug.cutout(audio_chunk[b], **cutout_args)                               # lib.py:544
+            # copy 0 augmented, copy -1 clean (reference lib.py:540-544)
+            audio_chunk = _loop.augmented_batch(
+                [view], lambda k: fixed_masks[i] if fixed_masks is not None else augmentation.draw(Fq, u_len), augmentation, augment_extra)
             if entropy_args.get('enabled', False):
                 entropy_augmentation(audio_chunk[:num_negatives], model, **entropy_args)  # lib.py:545
 
@@ -390,43 +351,21 @@ def _dynamic_eval_gen(
                 bs.run_search(use_tqdm=False)     # enqueued whole; only the final beams come back
                 pseudo_targets = bs.return_text(idx=0)
             else:
-                # greedy ids on device (reference lib.py:559); only the ids cross PCIe, asynchronously into pinned memory
-                ids_dev, n_dev = ops.ctc_greedy(post[-1].detach(), blank)
-                if pinned is None or pinned[0].shape[1] < ids_dev.shape[1]:
-                    pinned = (torch.empty(1, ids_dev.shape[1], dtype=torch.int32, pin_memory=True), torch.empty(1, dtype=torch.int32, pin_memory=True))
-                pinned[0][:, :ids_dev.shape[1]].copy_(ids_dev, non_blocking=True)
-                pinned[1].copy_(n_dev, non_blocking=True)
-                ready = torch.cuda.Event()
-                ready.record()
-                if sampled:
-                    ops.gemm_profile_before_yield(sampled, ready)
+                # greedy ids on device (reference lib.py:559); only the ids cross PCIe
+                labels.fetch(*ops.ctc_greedy(post[-1].detach(), blank))
+                step.before_yield(labels.record())
                 yield                                            # another chain may use the host while this forward runs
-                _t0 = time.perf_counter()
-                if ops.gemm_profile_active():        # also for unsampled steps: the mode is per model call, chains interleave on this thread
-                    ops.gemm_profile_resume_step(device, sampled)
-                ready.synchronize()
-                HOST_WAIT[0] += time.perf_counter() - _t0
-                pseudo_targets = tokenizer.decode(pinned[0][0, :int(pinned[1][0])].tolist())
+                labels.wait(step.resume)
+                pseudo_targets = tokenizer.decode(labels.ids())
             if verbose and not args.__dict__.get('not_verbose', False) and args.__dict__.get('print_predictions', False):
                 print(f'Pseudo targets: {pseudo_targets}')
                 print(f'Noisy predictions: {decoder(post[0].detach())}\n--\n')
             target_ids = tokenizer.encode(pseudo_targets)  # text hop kept (reference lib.py:569)
-            S = len(target_ids)
-            # pseudo-label ids go up through a small ring of pinned buffers with an async copy (a pageable upload would
-            # block the host on this stream); a slot is reused 4 windows later, long after its copy has run
-            if tgt_ring is None or tgt_ring[0].shape[1] < max(S, 1):
-                tgt_ring = [torch.empty(num_negatives, max(2 * S, 256), dtype=torch.int32, pin_memory=True) for _ in range(4)]
-            slot = tgt_ring[tgt_turn % 4]
-            tgt_turn += 1
-            row = torch.as_tensor(target_ids if S else [0], dtype=torch.int32)
-            slot[:, :row.numel()] = row
-            targets = torch.empty(num_negatives, max(S, 1), dtype=torch.int32, device=device)
-            targets.copy_(slot[:, :max(S, 1)], non_blocking=True)
+            targets, tlen = labels.targets([target_ids] * num_negatives)
             augmented_outs = post[:num_negatives]
             N, B = augmented_outs.shape[1], augmented_outs.shape[0]
             total_tokens_in_loss = N * B
             ilen = torch.full((B,), N, dtype=torch.int32, device=device)
-            tlen = torch.full((B,), S, dtype=torch.int32, device=device)
 
             if native:
                 # CTCLoss(reduction='sum') / (N*B) and its gradient w.r.t. the log-probs (reference lib.py:575,579)
@@ -447,9 +386,8 @@ def _dynamic_eval_gen(
             optimizer.step()
 
             if online:
-                stitch_window(i, post[-1].detach(), u_len)
-            if sampled:
-                ops.gemm_profile_end_step(device, sampled)
+                stitch.add(i, post[-1].detach(), u_len, overlap)
+            step.end()
         epochs_etime = time.time()
         if print_runtimes:
             torch.cuda.synchronize(device)
@@ -469,26 +407,23 @@ def _dynamic_eval_gen(
             while len(group) < final_batch and idx + len(group) < len(keys) and \
                     training_data[keys[idx + len(group)]].shape[-1] == u_len:
                 group.append(keys[idx + len(group)])
-            sampled = 0
-            if ops.gemm_profile_active():
-                sampled = ops.gemm_profile_begin_step(device)
+            step = _loop.ProfileStep(device)
             batch = torch.empty(len(group), Fq, u_len, device=device, dtype=torch.float32)
             for b, k in enumerate(group):
                 batch[b].copy_(training_data[k][0])
             with torch.no_grad():   # never held across a yield: interleaved generators would restore each other's grad mode
                 post = model(audio_signal=batch)['final_posteriors']
                 for b, k in enumerate(group):
-                    stitch_window(k, post[b], u_len)
+                    stitch.add(k, post[b], u_len, overlap)
             idx += len(group)
-            if sampled:
-                ops.gemm_profile_end_step(device, sampled)
+            step.end()
             yield                                        # independent forwards are queued: let another chain enqueue
         if print_runtimes:
             torch.cuda.synchronize(device)
             print(f'Final pass runtime: {time.time() - final_pass_stime}')
         model.train()
 
-    logits_dev = ops.stitch_finalize(acc, cnt, stitch["end"])  # log(sum / count) over the covered rows
+    logits_dev = stitch.finalize()
 
     if return_params:
         updated_model_params = [p.clone().detach().cpu() for p in model.parameters()]
@@ -547,15 +482,16 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
     a recording's short last window runs on its own replica, a finished recording's replica is no longer stepped, and every recording keeps
     its own optimiser step count (over several epochs, or under shuffle, recordings of different lengths get out of step).  Recordings stay
     independent (own weights, own optimiser state, own stitch buffers): per recording the results are those of `dynamic_eval` up to the GEMM
-    planner's choice of tile for the larger launches.  Generator with the same yield points as _dynamic_eval_gen; returns the list of
-    per-recording results (in `specs` order) in StopIteration.value."""
+    planner's choice of tile for the larger launches.  Under `shuffle` the group draws ONE permutation over the union of its recordings'
+    window keys, so its host RNG stream differs from that of `dynamic_eval` on each recording alone (one permutation per recording).
+    Generator with the same yield points as _dynamic_eval_gen; returns the list of per-recording results (in `specs` order) in
+    StopIteration.value."""
     if not lockstep_supported(args, model, specs, beam_search_fn, optimizer_state):
         raise ops.DynError("dynamic_eval lockstep group: unsupported configuration (see lockstep_supported)")
     device = model.device
     Rn = len(specs)
     order = sorted(range(Rn), key=lambda j: (-int(specs[j].shape[-1]), j))        # replica q holds recording order[q]: longest first
     downsampling_factor = args.config['model']['subsampling_factor']
-    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']
     spec_augment_config = get_specaugment_config_from_args(args)
     lr_args = get_lr_args_from_args(args)
     num_negatives = 1
@@ -568,7 +504,6 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
     optimizer = optim(model.parameters(), **lr_args)             # flat [R', n_flat] buffers: one launch per step for the whole group
     augmentation = SpecAugment(**spec_augment_config)
     fixed_masks = args.__dict__.get('spec_augment_fixed_masks', None)  # test hook: {window_key: masks} or one such dict per recording
-    assert args.config['training'].get("max_seq_len", 0) == 0, 'caching is not used anymore'
     assert tokenizer.vocab_size() + 1 == num_classes, 'tokenizer vocabulary does not match the CTC head'
     epochs = args.__dict__.get('epochs', 1)
     shuffle = args.__dict__.get('shuffle', False)
@@ -582,107 +517,58 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
             raise ops.DynError(f"spec must be [1, F, T], got {tuple(sp.shape)}")
         specs_dev.append(sp)
     Fq = specs_dev[0].shape[1]
-    # per recording: window rule and accumulators exactly as the single path (a recording shorter than seq_len is one window, overlap 0)
-    seqs, ovls, data, acc, cnt, stitch = [], [], [], [], [], []
+    # per recording: window rule and stitch exactly as the single path (a recording shorter than seq_len is one window, overlap 0)
+    seqs, ovls, data, stitch = [], [], [], []
     for q in range(Rn):
         spec_n = specs_dev[q].shape[-1]
-        sl, ov = (spec_n, 0) if seq_len > spec_n else (seq_len, overlap if overlap != -1 else args.config['audio_chunking']['overlap'])
-        assert ov / downsampling_factor == ov // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
+        sl, ov = _loop.window_rule(args, spec_n, seq_len, overlap, downsampling_factor)
         seqs.append(sl); ovls.append(ov)
         data.append(prepare_chunks(specs_dev[q], sl, ov)[0])
-        rows = spec_n // 4 + sl
-        acc.append(torch.zeros(rows, num_classes, device=device, dtype=torch.float32))
-        cnt.append(torch.zeros(rows, device=device, dtype=torch.float32))
-        stitch.append({"pos": 0, "end": 0})
+        stitch.append(_loop.Stitcher.for_recording(spec_n, sl, num_classes, device))
     if len({(sl - ov) for sl, ov, d in zip(seqs, ovls, data) if len(d) > 1}) > 1:
         raise ops.DynError("lockstep group: recordings must share the window stride")
 
-    def stitch_window(q, key, log_probs_2d, u_len):
-        ds_len = log_probs_2d.shape[0]
-        overlap_ds = int(ovls[q] / (u_len / ds_len))
-        st = stitch[q]
-        st["pos"] -= overlap_ds if key != 0 else 0
-        ops.stitch_accumulate(log_probs_2d, acc[q], cnt[q], st["pos"])
-        st["pos"] += ds_len
-        st["end"] = max(st["end"], st["pos"])
+    def draw_masks(q, key, u_len):
+        fm = fixed_masks[order[q]] if isinstance(fixed_masks, (list, tuple)) else fixed_masks
+        return fm[key] if fm is not None else augmentation.draw(Fq, u_len)
 
     model.use_graphs = bool(args.__dict__.get('use_graphs', True))
     model.eval()
     all_keys = sorted(set().union(*[set(d.keys()) for d in data]))
     ksteps = [0] * Rn            # every recording keeps its own optimiser step count (recordings of different lengths get out of step after one epoch)
-    pinned = None
-    tgt_ring, tgt_turn = None, 0
+    labels = _loop.PseudoLabels(Rn, device, HOST_WAIT)     # row q: replica q
     results = [None] * Rn
     try:
         for epoch in range(args.__dict__.get('epochs', 1)):
             if online and epoch > 0:
-                for q in range(Rn):
-                    acc[q].zero_(); cnt[q].zero_()
-                    stitch[q]["pos"] = stitch[q]["end"] = 0
+                for st in stitch:
+                    st.reset()
             training_keys = random.sample(all_keys, len(all_keys)) if shuffle else list(all_keys)
             for i in (tqdm(training_keys) if use_tqdm else training_keys):
                 members = [q for q in range(Rn) if i in data[q]]
                 u_lens = {q: data[q][i].shape[-1] for q in members}
                 classes = _shape_classes(members, u_lens)
-                sampled = 0
-                if ops.gemm_profile_active():
-                    sampled = ops.gemm_profile_begin_step(device)
+                step = _loop.ProfileStep(device)
                 posts = []
                 for lo, hi in classes:               # forward of every shape class; the labels of all of them cross PCIe together
                     n = hi - lo
-                    u_len = u_lens[lo]
-                    audio_chunk = torch.empty(2 * n, Fq, u_len, device=device, dtype=torch.float32)
-                    for q in range(lo, hi):
-                        view = data[q][i][0]
-                        audio_chunk[q - lo].copy_(view)
-                        audio_chunk[n + q - lo].copy_(view)
-                        fm = fixed_masks[order[q]] if isinstance(fixed_masks, (list, tuple)) else fixed_masks
-                        masks = fm[i] if fm is not None else augmentation.draw(Fq, u_len)
-                        if masks[0][0] or masks[1][0]:
-                            augmentation.apply(audio_chunk[q - lo], masks, _window_fill_value(audio_chunk[q - lo], augmentation.zero_masking))
+                    audio_chunk = _loop.augmented_batch([data[q][i][0] for q in range(lo, hi)],
+                                                        lambda k: draw_masks(lo + k, i, u_lens[lo]), augmentation)
                     model.set_range(lo, hi)
                     model.grad_samples = num_negatives * n if _CLEAN_COPY_FUSED_ATTN else None
                     with torch.enable_grad():
                         post = model(audio_signal=audio_chunk)['final_posteriors']     # [2 n, N, C]
                     ctx = (model._ctx, model._ctx_static, model._ctx_key)
-                    ids_dev, n_dev = ops.ctc_greedy(post[n:].detach(), blank)       # pseudo-labels of the clean copies
-                    if pinned is None or pinned[0].shape[1] < ids_dev.shape[1]:
-                        pinned = (torch.empty(Rn, max(ids_dev.shape[1], seq_len // downsampling_factor), dtype=torch.int32, pin_memory=True),
-                                  torch.empty(Rn, dtype=torch.int32, pin_memory=True))
-                    pinned[0][lo:hi, :ids_dev.shape[1]].copy_(ids_dev, non_blocking=True)
-                    pinned[1][lo:hi].copy_(n_dev, non_blocking=True)
+                    labels.fetch(*ops.ctc_greedy(post[n:].detach(), blank), lo, hi)  # pseudo-labels of the clean copies
                     posts.append((post, ctx))
-                ready = torch.cuda.Event()
-                ready.record()
-                if sampled:
-                    ops.gemm_profile_before_yield(sampled, ready)
+                step.before_yield(labels.record())
                 yield
-                _t0 = time.perf_counter()
-                if ops.gemm_profile_active():
-                    ops.gemm_profile_resume_step(device, sampled)
-                ready.synchronize()
-                HOST_WAIT[0] += time.perf_counter() - _t0
+                labels.wait(step.resume)
                 optimizer.zero_grad()
                 for (lo, hi), (post, ctx) in zip(classes, posts):
                     n = hi - lo
-                    target_ids = []
-                    for q in range(lo, hi):
-                        pseudo_targets = tokenizer.decode(pinned[0][q, :int(pinned[1][q])].tolist())
-                        target_ids.append(tokenizer.encode(pseudo_targets))                   # text hop kept (reference lib.py:569)
-                    S_max = max(1, max(len(t) for t in target_ids))
-                    if tgt_ring is None or tgt_ring[0][0].shape[1] < S_max:
-                        tgt_ring = [(torch.zeros(Rn, max(2 * S_max, 256), dtype=torch.int32, pin_memory=True),
-                                     torch.zeros(Rn, dtype=torch.int32, pin_memory=True)) for _ in range(4 * max(1, len(classes)))]
-                    slot, lens = tgt_ring[tgt_turn % len(tgt_ring)]
-                    tgt_turn += 1
-                    for k, t in enumerate(target_ids):
-                        if t:
-                            slot[k, :len(t)] = torch.as_tensor(t, dtype=torch.int32)
-                        lens[k] = len(t)
-                    targets = torch.empty(n, S_max, dtype=torch.int32, device=device)
-                    targets.copy_(slot[:n, :S_max], non_blocking=True)
-                    tlen = torch.empty(n, dtype=torch.int32, device=device)
-                    tlen.copy_(lens[:n], non_blocking=True)
+                    # text hop kept (reference lib.py:569)
+                    targets, tlen = labels.targets([tokenizer.encode(tokenizer.decode(labels.ids(q))) for q in range(lo, hi)])
                     N = post.shape[1]
                     ilen = torch.full((n,), N, dtype=torch.int32, device=device)
                     # per recording: CTCLoss(reduction='sum') / (N * B) with B = num_negatives = 1 (reference lib.py:572-575); 'sum' over the
@@ -693,7 +579,7 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
                     model.backward(g_aug, n_active=n)
                     if online:
                         for q in range(lo, hi):
-                            stitch_window(q, i, post[n + q - lo].detach(), u_lens[q])
+                            stitch[q].add(i, post[n + q - lo].detach(), u_lens[q], ovls[q])
                 # one optimiser launch per run of recordings with the same step count (one launch when they are in step), over the recordings that
                 # had a window at this position; a finished recording's replica is left alone
                 runs, start, prev = [], members[0], members[0]
@@ -707,8 +593,7 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
                 optimizer.step_ranges(runs)
                 for q in members:
                     ksteps[q] += 1
-                if sampled:
-                    ops.gemm_profile_end_step(device, sampled)
+                step.end()
         if not online:
             model.eval()
             idx = 0
@@ -726,9 +611,7 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
                     if not mem_n or _shape_classes(mem_n, ul_n)[0] != (lo, hi) or ul_n[lo] != u_lens[lo]:
                         break
                     group.append(kn)
-                sampled = 0
-                if ops.gemm_profile_active():
-                    sampled = ops.gemm_profile_begin_step(device)
+                step = _loop.ProfileStep(device)
                 n = hi - lo
                 batch = torch.empty(len(group) * n, Fq, u_lens[lo], device=device, dtype=torch.float32)
                 for c, k in enumerate(group):
@@ -739,7 +622,7 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
                     post = model(audio_signal=batch)['final_posteriors']
                     for c, k in enumerate(group):
                         for q in range(lo, hi):
-                            stitch_window(q, k, post[c * n + q - lo], u_lens[lo])
+                            stitch[q].add(k, post[c * n + q - lo], u_lens[lo], ovls[q])
                     for k in group:                 # the other classes at these positions (short last windows): one forward each
                         mem_k = [q for q in range(Rn) if k in data[q] and not (lo <= q < hi)]
                         ul_k = {q: data[q][k].shape[-1] for q in mem_k}
@@ -750,14 +633,13 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
                             model.set_range(l2, h2)
                             p2 = model(audio_signal=b2)['final_posteriors']
                             for q in range(l2, h2):
-                                stitch_window(q, k, p2[q - l2], ul_k[l2])
+                                stitch[q].add(k, p2[q - l2], ul_k[l2], ovls[q])
                 idx += len(group)
-                if sampled:
-                    ops.gemm_profile_end_step(device, sampled)
+                step.end()
                 yield
             model.train()
         for q in range(Rn):
-            logits_dev = ops.stitch_finalize(acc[q], cnt[q], stitch[q]["end"])
+            logits_dev = stitch[q].finalize()
             logits = logits_dev if return_device else logits_dev.cpu().numpy()
             if return_params:
                 results[order[q]] = (logits, [p.clone().detach().cpu() for p in model.replica_params(q)])
@@ -771,13 +653,9 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
 
 
 def dynamic_eval_lockstep(args, model, specs, seq_len, overlap, tokenizer, **kw):
-    """`specs` (<= model.R recordings of equal length) through one lockstep group; list of per-recording results (see _dynamic_eval_group_gen)."""
-    gen = _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, **kw)
-    try:
-        while True:
-            next(gen)
-    except StopIteration as stop:
-        return stop.value
+    """`specs` (<= model.R recordings, of any lengths that share the window stride) through one lockstep group; list of per-recording
+    results (see _dynamic_eval_group_gen)."""
+    return _loop.drain(_dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, **kw))
 
 
 def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=MADGRAD, optimizer_state=None,
@@ -789,46 +667,15 @@ def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, use_tq
                             optimizer_state=optimizer_state, beam_search_fn=beam_search_fn, return_params=return_params,
                             return_device=return_device)
     try:
-        while True:
-            next(gen)
-    except StopIteration as stop:
-        return stop.value
+        return _loop.drain(gen)
     finally:
         if _is_native(model):
             model.grad_samples = None      # also when the loop raised: a stale value would make a later full-batch backward fail
 
 
-def _new_chain_stream(device, k):
-    """Stream of recording chain k.  DYN_CHAIN_CU_MASK=<n>[:stride] (experiment switch, off by default) gives chain k a stream whose
-    kernels may not use a group of n of the 256 CUs — CUs k*n .. k*n+n-1, or with `:stride` every (256/n)-th CU starting at k — so the
-    short kernels of the OTHER chains can start there while a matrix kernel of chain k holds the rest of the chip
-    (dyn_stream_create_cu_mask = hipExtStreamCreateWithCUMask).  Measured: DESIGN.md §5."""
-    import ctypes
-    import os
-    spec = os.environ.get("DYN_CHAIN_CU_MASK", "")
-    if not spec or spec == "0":
-        return torch.cuda.Stream(device=device)
-    from ._lib import check, load
-    n = int(spec.split(":")[0])
-    strided = spec.endswith(":stride")
-    n_cu = torch.cuda.get_device_properties(device).multi_processor_count
-    if not 0 < n < n_cu:
-        raise ops.DynError(f"DYN_CHAIN_CU_MASK={spec!r}: hole size must be in 1..{n_cu - 1}")
-    hole = {(k + j * (n_cu // n)) % n_cu for j in range(n)} if strided else {(k * n + j) % n_cu for j in range(n)}
-    words = (ctypes.c_uint32 * ((n_cu + 31) // 32))()
-    for cu in range(n_cu):
-        if cu not in hole:
-            words[cu // 32] |= 1 << (cu % 32)
-    out = ctypes.c_void_p()
-    with torch.cuda.device(device):
-        check(load().dyn_stream_create_cu_mask(words, len(words), ctypes.byref(out)), "dyn_stream_create_cu_mask")
-    return torch.cuda.ExternalStream(out.value, device=device)
-
-
 import os as _os
 
 _CLEAN_COPY_FUSED_ATTN = _os.environ.get("DYN_CLEAN_FUSED_ATTN", "1") != "0"     # A/B switch (DESIGN.md §3.5)
-_CHAIN_STREAMS = {}
 HOST_WAIT = [0.0]   # seconds the host spent blocked on the per-window pseudo-label ids (diagnostic)
 
 
@@ -851,24 +698,10 @@ def dynamic_eval_many(args, models, specs, seq_len, overlap, tokenizer, **kw):
     runs one recording at a time; the chains are advanced round-robin at their yield points, so the GEMMs of one chain fill
     the latency-bound stretches of the other (CTC scans, the pseudo-label round trip, short HBM-bound kernels).
     Recordings are independent (reference lib.py:494,636-637).  Returns the per-recording results in `specs` order."""
-    device = models[0].device
-    key = torch.device(device).index
-    while len(_CHAIN_STREAMS.setdefault(key, [])) < len(models):    # streams are kept: the caching allocator's per-stream
-        _CHAIN_STREAMS[key].append(_new_chain_stream(device, len(_CHAIN_STREAMS[key])))  # pools stay warm across calls (no hipMalloc in the loop)
-    streams = _CHAIN_STREAMS[key][:len(models)]
-    main = torch.cuda.current_stream(device)
-    for st in streams:
-        st.wait_stream(main)
     # Identical chains started together stay phase-locked (same kernels at the same time: when all of them are in their HBM-bound or
     # latency-bound stretches the matrix cores idle).  Chain k therefore starts `k * stagger` later, by a device-side delay on its stream.
-    import os
-    stagger_us = int(float(os.environ.get("DYN_CHAIN_STAGGER_MS", "0")) * 1000)
-    if stagger_us > 0:
-        from ._lib import check, load
-        for k, st in enumerate(streams):
-            if k:
-                check(load().dyn_sleep_us(min(k * stagger_us, 2000000), st.cuda_stream), "dyn_sleep_us")
-    pending = list(enumerate(specs))
+    stagger_us = int(float(_os.environ.get("DYN_CHAIN_STAGGER_MS", "0")) * 1000)
+    jobs = list(enumerate(specs))
     R = getattr(models[0], "R", 1)
     group_sizes = kw.pop('group_sizes', None)    # explicit sizes of the lockstep groups, in order (bench.py's prewarm); default: lockstep_group_sizes
     if R > 1:
@@ -886,47 +719,14 @@ def dynamic_eval_many(args, models, specs, seq_len, overlap, tokenizer, **kw):
             k += n
             if n != n_plan:     # the plan no longer adds up: plan the rest again
                 sizes = lockstep_group_sizes(len(specs) - k, R, len(models))
-        pending = items
-    results = [None] * len(specs)
-    free, active = list(range(len(models)))[::-1], []
+        jobs = items
+    gen = _dynamic_eval_group_gen if R > 1 else _dynamic_eval_gen
     try:
-        _run_chains(args, models, streams, pending, results, free, active, seq_len, overlap, tokenizer, kw)
+        return _loop.run_chains(models, jobs, lambda m, sp: gen(args, m, sp, seq_len, overlap, tokenizer, **kw), stagger_us)
     finally:
-        _reset_grad_samples(models)
-    for st in streams:
-        main.wait_stream(st)
-    return results
-
-
-def _run_chains(args, models, streams, pending, results, free, active, seq_len, overlap, tokenizer, kw):
-    """Round-robin over the chains' generators (see dynamic_eval_many)."""
-    while pending or active:
-        while pending and free:
-            ci = free.pop()
-            idx, spec = pending.pop(0)
-            if isinstance(idx, list):     # a lockstep group of recordings on a group model
-                active.append([_dynamic_eval_group_gen(args, models[ci], spec, seq_len, overlap, tokenizer, **kw), ci, idx])
-            else:
-                active.append([_dynamic_eval_gen(args, models[ci], spec, seq_len, overlap, tokenizer, **kw), ci, idx])
-        for item in list(active):
-            gen, ci, idx = item
-            with torch.cuda.stream(streams[ci]):
-                try:
-                    next(gen)
-                except StopIteration as stop:
-                    if isinstance(idx, list):
-                        for j, res in zip(idx, stop.value):
-                            results[j] = res
-                    else:
-                        results[idx] = stop.value
-                    active.remove(item)
-                    free.append(ci)
-
-
-def _reset_grad_samples(models):
-    for m in models:
-        if _is_native(m):
-            m.grad_samples = None
+        for m in models:
+            if _is_native(m):
+                m.grad_samples = None
 
 
 dynamic_eval = dynamic_eval_ctc_loss

@@ -7,6 +7,7 @@ import random
 import torch
 
 from . import lib, ops
+from ._loop import augmented_batch, window_rule
 from .augment import SpecAugment
 from .awmc import AWMC
 from .decoding import GreedyCTCDecoder
@@ -37,12 +38,11 @@ def adapt_on_concat_only(args, model, concat_spec, tokenizer, beamsearch=None, a
     device = model.device
     spec_n = concat_spec.shape[-1]
     downsampling_factor = args.config['model']['subsampling_factor']
-    seq_len = args.seq_len if args.seq_len != -1 else args.config['audio_chunking']['size']
     spec_augment_config = lib.get_specaugment_config_from_args(args)
     lr_args = lib.get_lr_args_from_args(args)
     fs = lib.get_frame_shuffle_config_from_args(args)
     if args.__dict__.get('random_noise', 0.0) or fs['time_dimension'] or fs['freq_dimension'] or \
-            lib.get_cutout_params_from_args(args, seq_len)['num_rectangles'] or args.__dict__.get('entropy_augmentation_enabled', False):
+            lib.get_cutout_params_from_args(args, args.seq_len)['num_rectangles'] or args.__dict__.get('entropy_augmentation_enabled', False):
         lib._unsupported("random_noise / frame_shuffle / cutout / entropy_augmentation")
     num_negatives = 1
     original_flat = model.flat_params.clone()
@@ -52,12 +52,7 @@ def adapt_on_concat_only(args, model, concat_spec, tokenizer, beamsearch=None, a
     decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=blank, device=device)
     augmentation = SpecAugment(**spec_augment_config)
     fixed_masks = args.__dict__.get('spec_augment_fixed_masks', None)
-    if seq_len > spec_n:
-        seq_len, adapt_overlap = spec_n, 0
-    else:
-        adapt_overlap = adapt_overlap if adapt_overlap != -1 else args.config['audio_chunking']['overlap']
-    assert args.config['training'].get('max_seq_len', 0) == 0, 'caching is not used anymore'
-    assert adapt_overlap / downsampling_factor == adapt_overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
+    seq_len, adapt_overlap = window_rule(args, spec_n, args.seq_len, adapt_overlap, downsampling_factor)
     epochs = args.__dict__.get('epochs', 1)
     shuffle = args.__dict__.get('shuffle', False)
     model.eval()
@@ -72,13 +67,8 @@ def adapt_on_concat_only(args, model, concat_spec, tokenizer, beamsearch=None, a
         for i in cur_keys:
             view = training_data[i][0]
             u_len = view.shape[-1]
-            audio_chunk = torch.empty(num_negatives + 1, Fq, u_len, device=device, dtype=torch.float32)
-            for b in range(num_negatives + 1):
-                audio_chunk[b].copy_(view)
-            for b in range(num_negatives):
-                masks = fixed_masks[i] if fixed_masks is not None else augmentation.draw(Fq, u_len)
-                if masks[0][0] or masks[1][0]:
-                    augmentation.apply(audio_chunk[b], masks, lib._window_fill_value(audio_chunk[b], augmentation.zero_masking))
+            audio_chunk = augmented_batch(
+                [view], lambda k: fixed_masks[i] if fixed_masks is not None else augmentation.draw(Fq, u_len), augmentation)
             with torch.enable_grad():
                 post = model(audio_signal=audio_chunk)['final_posteriors']
             target_ids = tokenizer.encode(decoder(post[-1].detach()))

@@ -17,7 +17,8 @@ import pickle
 import torch
 
 from . import dist as ddist
-from . import lib, ops
+from . import lib
+from ._loop import Stitcher
 from .datasets import datasets_functions
 from .decoding import GreedyCTCDecoder
 from .harness_common import normalize
@@ -30,18 +31,10 @@ from .wer import edit_counts, rates_from_counts
 def outer_stitch(windows, overlap, num_classes, device):
     """windows: [(key, log_probs [ds_len, C] CUDA, u_len)] -> stitched log-probs [T_ds, C] on device.
     reference run_seq_eval.py:120-142 (logit_position -= overlap_ds except for key 0; sum / count; log)."""
-    total = sum(lp.shape[0] for _, lp, _ in windows)
-    acc = torch.zeros(total, num_classes, device=device, dtype=torch.float32)
-    cnt = torch.zeros(total, device=device, dtype=torch.float32)
-    pos = end = 0
+    stitch = Stitcher(sum(lp.shape[0] for _, lp, _ in windows), num_classes, device)
     for key, lp, u_len in sorted(windows, key=lambda w: w[0]):
-        ds_len = lp.shape[0]
-        overlap_ds = int(overlap / (u_len / ds_len))
-        pos -= overlap_ds if key != 0 else 0
-        ops.stitch_accumulate(lp, acc, cnt, pos)
-        pos += ds_len
-        end = max(end, pos)
-    return ops.stitch_finalize(acc, cnt, end)
+        stitch.add(key, lp, u_len, overlap)
+    return stitch.finalize()
 
 
 def replicate(model, n, group=1):

@@ -16,6 +16,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
+from ._loop import PseudoLabels, Stitcher, drain, run_chains
 from .decoding import GreedyCTCDecoder
 from .optim import MADGRAD, Adam  # noqa: F401
 
@@ -122,7 +123,7 @@ def _su_gen(args, model, utterances, seq_len, overlap, tokenizer, processor, opt
     waves = host.to(device, non_blocking=True)
     frames = [model.conv_lengths(L)[-1] for L in lens]
     foffs = [sum(frames[:i]) for i in range(len(frames))]
-    probs_host, pinned, tgt_ring, tgt_turn = None, None, None, 0
+    probs_host, labels = None, PseudoLabels(1, device)
     for epoch in range(args.__dict__.get('epochs', 1)):
         indexes = list(range(len(utterances)))
         indexes = random.sample(indexes, len(indexes)) if args.__dict__.get('shuffle', False) else indexes
@@ -135,29 +136,15 @@ def _su_gen(args, model, utterances, seq_len, overlap, tokenizer, processor, opt
                 out = model(input_values)
             log_p = ops.log_softmax(out.logits)                                                  # F.log_softmax, lib.py:417
             N = out.frames                      # < log_p.shape[1] when the utterance ran zero-padded in its length bucket: the frames past N are not its own
-            ids_dev, n_dev = ops.ctc_greedy(log_p[-1, :N], blank)                                # decoder(log_p[-1]), lib.py:419: only the ids cross PCIe
-            if pinned is None or pinned[0].shape[1] < ids_dev.shape[1]:
-                pinned = (torch.empty(1, 2 * ids_dev.shape[1], dtype=torch.int32, pin_memory=True), torch.empty(1, dtype=torch.int32, pin_memory=True))
-            pinned[0][:, :ids_dev.shape[1]].copy_(ids_dev, non_blocking=True)
-            pinned[1].copy_(n_dev, non_blocking=True)
-            ready = torch.cuda.Event()
-            ready.record()
+            labels.fetch(*ops.ctc_greedy(log_p[-1, :N], blank))                                  # decoder(log_p[-1]), lib.py:419: only the ids cross PCIe
+            labels.record()
             yield                                                                                # another recording may use the host meanwhile
-            ready.synchronize()
-            pseudo_targets = tokenizer.decode(pinned[0][0, :int(pinned[1][0])].tolist())
-            ids = tokenizer(pseudo_targets).input_ids
-            S = len(ids)
-            if tgt_ring is None or tgt_ring[0].shape[1] < max(S, 1):
-                tgt_ring = [torch.empty(num_negatives, max(2 * S, 256), dtype=torch.int32, pin_memory=True) for _ in range(4)]
-            slot = tgt_ring[tgt_turn % 4]                                                        # reused 4 utterances later: its upload is long done
-            tgt_turn += 1
-            slot[:, :max(S, 1)] = torch.as_tensor(ids if S else [0], dtype=torch.int32)
-            targets = torch.empty(num_negatives, max(S, 1), dtype=torch.int32, device=device)
-            targets.copy_(slot[:, :max(S, 1)], non_blocking=True)
+            labels.wait()
+            pseudo_targets = tokenizer.decode(labels.ids())
+            targets, tlen = labels.targets([tokenizer(pseudo_targets).input_ids] * num_negatives)
             aug = log_p[:num_negatives].contiguous()
             B = aug.shape[0]
             ilen = torch.full((B,), N, dtype=torch.int32, device=device)                         # CTC over the utterance's own frames; zero gradient past them
-            tlen = torch.full((B,), S, dtype=torch.int32, device=device)
             _, _, g_lp = ops.ctc_loss(aug, targets, ilen, tlen, blank, reduction="mean", grad_scale=1.0)   # lib.py:351,434
             g_logits = ops.log_softmax_bwd(aug, g_lp)
             model.backward(g_logits, n_active=num_negatives)                                     # loss.backward(), lib.py:438
@@ -182,12 +169,7 @@ def _su_gen(args, model, utterances, seq_len, overlap, tokenizer, processor, opt
 def dynamic_eval_ctc_loss_su(args, model, utterances, seq_len, overlap, tokenizer, processor, use_tqdm=True, optim=MADGRAD,
                              num_negatives=1, lr_args={'lr': 1e-15}, ngram_decoder=None):
     """reference wav2vec2/lib.py:293-462 (one recording's utterances, weights carried from utterance to utterance and restored at the end)."""
-    gen = _su_gen(args, model, utterances, seq_len, overlap, tokenizer, processor, optim, num_negatives, lr_args, ngram_decoder, use_tqdm)
-    try:
-        while True:
-            next(gen)
-    except StopIteration as stop:
-        return stop.value
+    return drain(_su_gen(args, model, utterances, seq_len, overlap, tokenizer, processor, optim, num_negatives, lr_args, ngram_decoder, use_tqdm))
 
 
 def dynamic_eval_su_many(args, models, utterance_lists, seq_len, overlap, tokenizer, processor, optim=MADGRAD, num_negatives=1,
@@ -197,35 +179,8 @@ def dynamic_eval_su_many(args, models, utterance_lists, seq_len, overlap, tokeni
     lib.py:455-460), so talks are independent.  One utterance step of wav2vec2-base is ~200 matrix products of 40 - 500 tiles each
     (profiles/r04_kernel_stats_wav2vec2_su.csv): alone they leave most of the 256 CUs idle; the steps of other talks fill them.  Each model
     replica in `models` owns a HIP stream and runs one talk at a time; returns the utterance lists in order."""
-    from .lib import _CHAIN_STREAMS, _new_chain_stream
-    device = models[0].device
-    key = torch.device(device).index
-    while len(_CHAIN_STREAMS.setdefault(key, [])) < len(models):
-        _CHAIN_STREAMS[key].append(_new_chain_stream(device, len(_CHAIN_STREAMS[key])))
-    streams = _CHAIN_STREAMS[key][:len(models)]
-    main = torch.cuda.current_stream(device)
-    for st in streams:
-        st.wait_stream(main)
-    pending = list(enumerate(utterance_lists))
-    results = [None] * len(utterance_lists)
-    free, active = list(range(len(models)))[::-1], []
-    while pending or active:
-        while pending and free:
-            ci = free.pop()
-            idx, utts = pending.pop(0)
-            active.append([_su_gen(args, models[ci], utts, seq_len, overlap, tokenizer, processor, optim, num_negatives, lr_args), ci, idx])
-        for item in list(active):
-            gen, ci, idx = item
-            with torch.cuda.stream(streams[ci]):
-                try:
-                    next(gen)
-                except StopIteration as stop:
-                    results[idx] = stop.value
-                    active.remove(item)
-                    free.append(ci)
-    for st in streams:
-        main.wait_stream(st)
-    return results
+    return run_chains(models, list(enumerate(utterance_lists)),
+                      lambda m, utts: _su_gen(args, m, utts, seq_len, overlap, tokenizer, processor, optim, num_negatives, lr_args))
 
 
 def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, processor, use_tqdm=True, optim=MADGRAD, num_negatives=1,
@@ -242,9 +197,7 @@ def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, proces
     if seq_len > spec_n:
         seq_len, overlap = spec_n, 0
     assert overlap / downsampling_factor == overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
-    V = tokenizer.vocab_size
-    acc = torch.zeros(spec_n // 4 + seq_len, V, device=device, dtype=torch.float32)
-    cnt = torch.zeros(spec_n // 4 + seq_len, device=device, dtype=torch.float32)
+    stitch = Stitcher.for_recording(spec_n, seq_len, tokenizer.vocab_size, device)
     last_ulen, kill_next, training_data = None, False, {}
     for i in range(0, spec_n, seq_len - overlap):                                               # lib.py:116-126
         chunk = spec[:, i:i + seq_len]
@@ -285,16 +238,10 @@ def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, proces
             optimizer.zero_grad()
             model.backward(ops.log_softmax_bwd(aug, g_lp), n_active=num_negatives)
             optimizer.step()
-            ds_len = N
-            outputs[i] = (log_p[-1, :N], ds_len, int(overlap / (u_len / ds_len)))
-    pos = end = 0
+            outputs[i] = (log_p[-1, :N], u_len)
     for i in sorted(outputs):
-        lp, ds_len, ov = outputs[i]
-        pos -= ov if i != 0 else 0
-        ops.stitch_accumulate(lp, acc, cnt, pos)
-        pos += ds_len
-        end = max(end, pos)
-    logits = ops.stitch_finalize(acc, cnt, end)
+        stitch.add(i, *outputs[i], overlap)
+    logits = stitch.finalize()
     model.flat_params.copy_(original)
     model.use_graphs = was_graphs
     return logits if return_device else logits.cpu().numpy()

@@ -700,3 +700,44 @@ def test_lockstep_dynamic_eval_matches_one_recording_at_a_time(cuda):
     for r in range(R):
         assert got[r].shape == want[r].shape and np.abs(got[r] - want[r]).max() < 5e-4, (r, np.abs(got[r] - want[r]).max())
         assert np.array_equal(got[r].argmax(-1), want[r].argmax(-1))
+
+
+def test_lockstep_five_shape_classes_in_one_step(cuda):
+    """Five recordings whose last windows all sit at key 768 with five different lengths: that window step runs five shape classes, more
+    than a 4-slot ring of pinned upload buffers holds, and each class uploads its own targets.  lib.dynamic_eval_lockstep against
+    lib.dynamic_eval on each recording alone with per-recording stored masks, offline and online, with the tolerances of
+    test_lockstep_dynamic_eval_matches_one_recording_at_a_time."""
+    from dynamic_asr_eval_amd import lib
+    from dynamic_asr_eval_amd.model import SCConformerXL
+    from dynamic_asr_eval_amd.tokenizer import SyntheticTokenizer
+    from oracle import dynamic_eval_ref as R_
+    from oracle.conformer_ref import SCConformerXLRef
+    R, vocab = 5, 128
+    ref = SCConformerXLRef(SMALL, vocab_size=vocab, seed=5, blank_bias=1.5)
+    single = SCConformerXL(SMALL, vocab_size=vocab, device=cuda)
+    single.load_state_dict(ref.state_dict())
+    grp = SCConformerXL(SMALL, vocab_size=vocab, device=cuda, group=R)
+    grp.load_state_dict(ref.state_dict())
+    tok = SyntheticTokenizer(vocab)
+    g = torch.Generator().manual_seed(27)
+    lens = (1100, 1150, 1200, 1250, 1270)
+    specs = [torch.randn(1, 80, n, generator=g) for n in lens]
+    last = [R_.prepare_chunks(sp, 512, 256)[0] for sp in specs]
+    assert all(sorted(d) == [0, 256, 512, 768] for d in last) and len({d[768].shape[-1] for d in last}) == R
+    masks = [_masks_for(range(0, 1024, 256), 80, None, seed=70 + r) for r in range(R)]
+    for online in (False, True):
+        want = []
+        for r in range(R):
+            a = _args(optim_lr=1e-4, epochs=1, shuffle=False, online=online, spec_augment_fixed_masks=masks[r], quiet=True)
+            want.append(lib.dynamic_eval(a, single, specs[r], 512, 256, tok, use_tqdm=False, return_params=True))
+        a = _args(optim_lr=1e-4, epochs=1, shuffle=False, online=online, spec_augment_fixed_masks=masks, quiet=True)
+        before = grp.flat_params.clone()
+        got = lib.dynamic_eval_lockstep(a, grp, specs, 512, 256, tok, use_tqdm=False, return_params=True)
+        assert torch.equal(grp.flat_params, before), "the group's weights must be restored"
+        assert len(got) == R
+        for r in range(R):
+            (o, p), (ow, pw) = got[r], want[r]
+            assert o.shape == ow.shape and np.abs(o - ow).max() < 2e-4, (online, r, np.abs(o - ow).max())
+            assert np.array_equal(o.argmax(-1), ow.argmax(-1))
+            for x, y in zip(p, pw):
+                assert (x - y).abs().max().item() < 1e-3      # MADGRAD's cube root: a gradient element near zero takes a step of ~lr^(2/3) |g|^(1/3) either way

@@ -150,7 +150,7 @@ def test_device_stitch_reproduces_the_reference_statements(cuda, pins):
         C, rows = case["classes"], case["acc_rows"]
         acc = torch.zeros(rows, C, device=cuda); cnt = torch.zeros(rows, device=cuda)
         pos = end = 0
-        for k in sorted(mo):                                    # the position rule of lib._dynamic_eval_gen.stitch_window
+        for k in sorted(mo):                                    # the position rule of _loop.Stitcher.add
             pos -= mo[k]["overlap_ds"] if k != 0 else 0
             ops.stitch_accumulate(torch.log(mo[k]["logits"][0]).to(cuda).contiguous(), acc, cnt, pos)
             pos += mo[k]["ds_len"]
