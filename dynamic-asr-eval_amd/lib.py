@@ -24,7 +24,7 @@ from . import _loop, ops
 from . import augment as _aug
 from .augment import SpecAugment
 from .decoding import GreedyCTCDecoder
-from .optim import MADGRAD, Adam  # noqa: F401  (re-exported: `optim=lib.MADGRAD`)
+from .optim import MADGRAD, Adafactor, Adam, ParamList  # noqa: F401  (re-exported: `optim=lib.MADGRAD`)
 
 try:  # tqdm is optional plumbing
     from tqdm import tqdm
@@ -727,6 +727,217 @@ def dynamic_eval_many(args, models, specs, seq_len, overlap, tokenizer, **kw):
         for m in models:
             if _is_native(m):
                 m.grad_samples = None
+
+
+# ------------------------------------------------------------------------------------------------ the consistency loop
+def _consistency_bytes(n_windows, n_flat, state_floats):
+    """Device memory of the loop's banks: parameters and gradients [W, P] float32, plus every window's optimiser state."""
+    return 2 * n_windows * n_flat * 4 + n_windows * state_floats * 4
+
+
+def dynamic_eval_consistency_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=Adafactor, optimizer_state=None,
+                                      beam_search_fn=None, return_params=False, return_device=False, consistency_final_pass='last_loaded',
+                                      trace=None):
+    """Reference lcasr/lib.py:646-903: one parameter set and one optimiser PER WINDOW.  Per epoch every window's gradient is taken at its
+    own set (no step inside the window loop), the gradients are mixed across windows with weights 0.95^|i-q| (sequentially in i, in
+    place: ops.grad_mix_decay), then every window's optimiser steps its own set.
+    Drop-in quirk kept on purpose: the reference's final pass discards the load of each window's set (:861), so the model keeps the set
+    loaded LAST in the window loop - the last trained window's, as it was before the last epoch's step - and the stitched log-probs and
+    `return_params` are that set's (with epochs=1: the unadapted model's).  `consistency_final_pass='per_window'` (extension, off by
+    default) runs every window of the final pass with its own adapted set instead.
+    The two banks are [W, P] device tensors; "load window i" is a device copy into `model.flat_params`, so captured graphs stay valid.
+    `optimizer_state` is accepted and ignored, as in the reference.  `trace` (tests): a dict that receives 'labels' [(epoch, key, ids)],
+    and per epoch 'grads' (the mixed gradient bank) and 'params' (the parameter bank after the steps) as CPU tensors."""
+    if consistency_final_pass not in ('last_loaded', 'per_window'):
+        raise ValueError(f"consistency_final_pass must be 'last_loaded' or 'per_window', got {consistency_final_pass!r}")
+    if not _is_native(model):
+        raise ops.DynError("dynamic_eval_consistency_ctc_loss: only the HIP SCConformerXL is supported (no foreign torch.nn.Module)")
+    if getattr(model, "R", 1) != 1:
+        raise ops.DynError("dynamic_eval_consistency_ctc_loss: no lockstep groups")
+    tta_beams = int(args.__dict__.get('lm_tta_beams', 3))
+    if beam_search_fn is not None and tta_beams != 0 and not isinstance(beam_search_fn, BeamSearchFactory):
+        _unsupported("LM beam-search pseudo-labels (beam_search_fn)")
+    beam_tta = beam_search_fn is not None and tta_beams != 0
+    device = model.device
+    spec_n = spec.shape[-1]
+    downsampling_factor = args.config['model']['subsampling_factor']
+    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']
+
+    spec_augment_config = get_specaugment_config_from_args(args)
+    random_noise = args.__dict__.get('random_noise', 0.0)
+    lr_args = get_lr_args_from_args(args)
+    frame_shuffle_args = get_frame_shuffle_config_from_args(args)
+    cutout_args = get_cutout_params_from_args(args, seq_len)
+    verbose = bool(args.__dict__.get('verbose', False)) and not args.__dict__.get('quiet', False)
+    if verbose:
+        print(spec_augment_config, lr_args, frame_shuffle_args, cutout_args)
+    num_negatives = 1
+
+    frozen_before = set(model.frozen)
+    original_flat = None
+    try:
+        if args.__dict__.get('freeze_subsampling', False):
+            model = freeze_subsampling(model)
+        if args.__dict__.get('freeze_all_but_last_block_and_head', False):
+            model = freeze_all_but_last_block_and_head(model)
+        if args.__dict__.get('train_subsampling_only', False):
+            model = train_subsampling_only(model)
+
+        num_classes = model.decoder.num_classes
+        blank = num_classes - 1
+        augmentation = SpecAugment(**spec_augment_config)
+        fixed_masks = args.__dict__.get('spec_augment_fixed_masks', None)  # test hook: {window_key: masks}
+        seq_len, overlap = _loop.window_rule(args, spec_n, seq_len, overlap, downsampling_factor)
+        if verbose:
+            print(f'Using seq_len: {seq_len} and overlap: {overlap}')
+        assert tokenizer.vocab_size() + 1 == num_classes, 'tokenizer vocabulary does not match the CTC head'
+
+        epochs = args.__dict__.get('epochs', 1)
+        shuffle = args.__dict__.get('shuffle', False)
+        online = args.__dict__.get('online', False)
+        epochs = 1 if online else epochs
+        shuffle = False if online else shuffle
+        print_runtimes = args.__dict__.get('print_runtimes', False)
+        skip_zero = args.__dict__.get('skip_zero_grad_samples', True)
+        final_batch = int(args.__dict__.get('final_pass_batch', 4))
+
+        # the banks: sized before anything is allocated (the reference keeps these sets in host memory, lib.py:732-735)
+        _, window_keys = prepare_chunks(spec, seq_len, overlap)
+        order = sorted(window_keys)
+        W, P = len(order), model.n_flat
+        params0 = model.parameters()
+        slots = [(o, p.numel()) for o, p, t in zip(params0.offsets, params0, params0.trainable) if t]
+        state_floats = 3 * P
+        if optim is Adafactor:
+            state_floats = ops.adafactor_segments([tuple(p.shape) for p, t in zip(params0, params0.trainable) if t], [o for o, _ in slots])[1]["n_state"]
+        need = _consistency_bytes(W, P, state_floats)
+        free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+        if need > free:
+            raise ops.DynError(f"dynamic_eval_consistency_ctc_loss: {W} windows x {P} parameters need {need} bytes of device memory for the "
+                               f"parameter and gradient banks and the optimiser states ({need / 2 ** 30:.1f} GiB), {free} bytes are free")
+        if W > ops.grad_mix_max_windows():
+            raise ops.DynError(f"dynamic_eval_consistency_ctc_loss: {W} windows, the gradient mix handles at most {ops.grad_mix_max_windows()}")
+
+        original_flat = model.flat_params.clone()
+        spec_dev = spec.to(device=device, dtype=torch.float32)
+        if spec_dev.dim() != 3 or spec_dev.shape[0] != 1:
+            raise ops.DynError(f"spec must be [1, F, T], got {tuple(spec.shape)}")
+        Fq = spec_dev.shape[1]
+        param_bank = original_flat.unsqueeze(0).repeat(W, 1)                      # lib.py:732-735
+        grad_bank = torch.zeros(W, P, device=device, dtype=torch.float32)
+        row_of = {key: w for w, key in enumerate(order)}
+        # elements that carry a gradient: the trainable tensors with the padding behind them (whose gradient is zero and stays zero)
+        mix_ranges = ops.merge_ranges([(o, (o + n + 63) // 64 * 64) for o, n in slots])
+
+        def window_params(w):           # window w's set as the optimiser sees it (lib.py:737)
+            pl = ParamList(param_bank[w, o:o + p.numel()].view(p.shape) for o, p in zip(params0.offsets, params0))
+            pl.flat_params, pl.flat_grads, pl.offsets, pl.trainable = param_bank[w], grad_bank[w], params0.offsets, params0.trainable
+            return pl
+        optimizers = [optim(window_params(w), **lr_args) for w in range(W)]
+
+        stitch = _loop.Stitcher.for_recording(spec_n, seq_len, num_classes, device)
+        labels = _loop.PseudoLabels(1, device, HOST_WAIT)
+        model.use_graphs = bool(args.__dict__.get('use_graphs', True))
+        model.grad_samples = num_negatives if (skip_zero and _CLEAN_COPY_FUSED_ATTN) else None
+        model.eval()
+        training_data, training_keys = prepare_chunks(spec_dev, seq_len, overlap)
+
+        def augment_extra(row):
+            _aug.frame_shuffle(row, **frame_shuffle_args)                 # reference lib.py:756
+            _aug.add_random_noise(row, noise_factor=random_noise)         # lib.py:757
+            _aug.cutout(row, **cutout_args)                               # lib.py:758
+
+        for epoch in range(args.__dict__.get('epochs', 1)):
+            if verbose:
+                print(f'Epoch {epoch + 1} / {epochs}')
+            if online and epoch > 0:
+                stitch.reset()          # every epoch overwrites model_outputs[i] (lib.py:813): the last epoch is what gets stitched
+            training_keys = list(training_data.keys())
+            training_keys = random.sample(training_keys, len(training_keys)) if shuffle else training_keys
+            epochs_stime = time.time()
+            pbar = tqdm(training_keys) if use_tqdm else training_keys
+            for i in pbar:
+                view = training_data[i][0]
+                u_len = view.shape[-1]
+                audio_chunk = _loop.augmented_batch(
+                    [view], lambda k: fixed_masks[i] if fixed_masks is not None else augmentation.draw(Fq, u_len), augmentation, augment_extra)
+                model.flat_params.copy_(param_bank[row_of[i]])                # lib.py:765-766, a device copy
+                with torch.enable_grad():
+                    out = model(audio_signal=audio_chunk)
+                post = out['final_posteriors']
+                if beam_tta:
+                    bs = beam_search_fn(log_probs=post[-1].detach(), beam_width=tta_beams)
+                    bs.run_search(use_tqdm=False)
+                    pseudo_targets = bs.return_text(idx=0)
+                else:
+                    labels.fetch(*ops.ctc_greedy(post[-1].detach(), blank))
+                    labels.record()
+                    labels.wait()
+                    pseudo_targets = tokenizer.decode(labels.ids())
+                target_ids = tokenizer.encode(pseudo_targets)
+                if trace is not None:
+                    trace.setdefault('labels', []).append((epoch, i, list(target_ids)))
+                targets, tlen = labels.targets([target_ids] * num_negatives)
+                augmented_outs = post[:num_negatives]
+                N, B = augmented_outs.shape[1], augmented_outs.shape[0]
+                ilen = torch.full((B,), N, dtype=torch.int32, device=device)
+                _, _, g_aug = ops.ctc_loss(augmented_outs.contiguous(), targets, ilen, tlen, blank, reduction="sum", grad_scale=1.0 / (N * B))
+                model.zero_grad()
+                if skip_zero:
+                    model.backward(g_aug, n_active=num_negatives)
+                else:
+                    g_full = torch.zeros_like(post)
+                    g_full[:num_negatives].copy_(g_aug)
+                    model.backward(g_full)
+                grad_bank[row_of[i]].copy_(model.flat_grads)                  # lib.py:796-801: stored, no step here
+                if online:
+                    stitch.add(i, post[-1].detach(), u_len, overlap)
+            if print_runtimes:
+                torch.cuda.synchronize(device)
+                print(f'Epoch runtime: {time.time() - epochs_stime}')
+
+            ops.grad_mix_decay(grad_bank, mix_ranges)                         # lib.py:817-841
+            if trace is not None:
+                trace.setdefault('grads', []).append(grad_bank.cpu())
+            for opt in optimizers:                                            # lib.py:845-848
+                opt.step()
+                opt.zero_grad()
+            if trace is not None:
+                trace.setdefault('params', []).append(param_bank.cpu())
+
+        if not online:
+            model.eval()
+            per_window = consistency_final_pass == 'per_window'
+            keys = sorted(training_data.keys())
+            idx = 0
+            while idx < len(keys):
+                group = [keys[idx]]
+                u_len = training_data[keys[idx]].shape[-1]
+                while not per_window and len(group) < final_batch and idx + len(group) < len(keys) and \
+                        training_data[keys[idx + len(group)]].shape[-1] == u_len:
+                    group.append(keys[idx + len(group)])
+                if per_window:
+                    model.flat_params.copy_(param_bank[row_of[keys[idx]]])
+                batch = torch.empty(len(group), Fq, u_len, device=device, dtype=torch.float32)
+                for b, k in enumerate(group):
+                    batch[b].copy_(training_data[k][0])
+                with torch.no_grad():
+                    post = model(audio_signal=batch)['final_posteriors']
+                    for b, k in enumerate(group):
+                        stitch.add(k, post[b], u_len, overlap)
+                idx += len(group)
+            model.train()
+
+        logits_dev = stitch.finalize()
+        if return_params:
+            updated_model_params = [p.clone().detach().cpu() for p in model.parameters()]
+    finally:
+        if original_flat is not None:
+            model.flat_params.copy_(original_flat)                            # lib.py:899-900 (also when the loop raised)
+        model.frozen = frozen_before
+        model.grad_samples = None
+    logits = logits_dev if return_device else logits_dev.cpu().numpy()
+    return logits if not return_params else (logits, updated_model_params)
 
 
 dynamic_eval = dynamic_eval_ctc_loss

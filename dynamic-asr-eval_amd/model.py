@@ -278,6 +278,8 @@ class SCConformerXL:
         pl = ParamList(self.P[n] for n, _ in self.spec)
         lo, hi = self._lo * self.n_flat, (self._lo + self._n) * self.n_flat      # a lockstep group steps its active replicas' buffers in one launch
         pl.flat_params, pl.flat_grads = self.flat_params[lo:hi], self.flat_grads[lo:hi]
+        pl.offsets = [self._slots[n][0] for n, _ in self.spec]
+        pl.trainable = [self.trainable(n) for n, _ in self.spec]
         return pl
 
     def grads(self):

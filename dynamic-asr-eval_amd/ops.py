@@ -961,6 +961,106 @@ def clip_grad_norm(g, max_norm):
     return out
 
 
+# ---- the consistency loop (csrc/consistency.hip)
+MIX_DECAY_PER_DISTANCE = 0.95       # reference lcasr/lib.py:818
+
+
+def grad_mix_tables(n_windows, decay_per_distance=MIX_DECAY_PER_DISTANCE):
+    """(decay[k] = decay_per_distance ** k, total_sum[i]) as Python doubles, formed exactly as the reference forms them
+    (lcasr/lib.py:828-834: `total_sum = 1`, then `+= decay ** abs(i - q)` over q != i in ascending q)."""
+    decay = [decay_per_distance ** k for k in range(n_windows)]
+    denom = []
+    for i in range(n_windows):
+        total = 1
+        for q in range(n_windows):
+            if q != i:
+                total += decay[abs(i - q)]
+        denom.append(float(total))
+    return decay, denom
+
+
+def merge_ranges(ranges):
+    """Sorted [lo, hi) ranges with touching ones joined."""
+    out = []
+    for lo, hi in sorted((int(a), int(b)) for a, b in ranges if b > a):
+        if out and lo <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], hi)
+        else:
+            out.append([lo, hi])
+    return [tuple(r) for r in out]
+
+
+def grad_mix_max_windows():
+    return int(_L().dyn_grad_mix_decay_max_windows())
+
+
+def grad_mix_decay(bank, ranges=None, decay_per_distance=MIX_DECAY_PER_DISTANCE):
+    """In-place distance-decayed mix of the gradient bank `bank` [W, P] (rows = windows in key order), reference lcasr/lib.py:817-841,
+    bit for bit.  `ranges`: [lo, hi) element ranges that carry a gradient (default: the whole row); the rest is not touched."""
+    _chk(bank, "grad_mix.bank")
+    if bank.dim() != 2 or bank.stride(1) != 1:
+        raise DynError("grad_mix.bank: expected [W, P] with contiguous rows")
+    W, P = bank.shape
+    if W > grad_mix_max_windows():
+        raise DynError(f"grad_mix_decay: {W} windows, the kernel stages at most {grad_mix_max_windows()} per element in LDS")
+    ranges = merge_ranges([(0, P)] if ranges is None else ranges)
+    if any(lo < 0 or hi > P for lo, hi in ranges):
+        raise DynError(f"grad_mix_decay: range outside a row of {P} elements")
+    if not ranges:
+        return bank
+    decay, denom = grad_mix_tables(W, decay_per_distance)
+    tables = torch.tensor([decay, denom], dtype=torch.float64).to(bank.device)
+    host = (ctypes.c_int64 * (2 * len(ranges)))(*[v for r in ranges for v in r])
+    check(_L().dyn_grad_mix_decay(bank.data_ptr(), bank.stride(0), W, ctypes.cast(host, ctypes.c_void_p), len(ranges),
+                                  tables[0].data_ptr(), tables[1].data_ptr(), _stream()), "dyn_grad_mix_decay")
+    return bank
+
+
+ADAFACTOR_SEG_COLS = 9
+
+
+def adafactor_segments(shapes, offsets):
+    """Segment table of dyn_adafactor_step for tensors of `shapes` at `offsets` of a flat buffer (include/dyneval.h): ->
+    (rows [n, 9] as a list, totals dict(n_rows, n_batches, n_cols, n_state)).  A tensor of dimension >= 2 is factored over its last two
+    dimensions with the leading ones as batch, as torch.optim.Adafactor does; 0-d and 1-D tensors keep a full second moment."""
+    import math
+    rows_tab, row0, batch0, col0, state0, extent = [], 0, 0, 0, 0, 0
+    for shape, off in zip(shapes, offsets):
+        shape = tuple(int(s) for s in shape)
+        n = math.prod(shape)
+        if n == 0:
+            continue
+        if len(shape) >= 2:
+            batch, rows, cols, factored = math.prod(shape[:-2]), shape[-2], shape[-1], 1
+        else:
+            batch, rows, cols, factored = 1, 1, n, 0
+        rows_tab.append([int(off), batch, rows, cols, state0, factored, row0, batch0, col0])
+        row0 += batch * rows
+        batch0 += batch
+        col0 += batch * cols if factored else 0
+        state0 += batch * (rows + cols) if factored else n
+        extent = max(extent, int(off) + n)
+    return rows_tab, dict(n_rows=row0, n_batches=batch0, n_cols=col0, n_state=state0, extent=extent)
+
+
+def adafactor_scratch_bytes(totals, n_segments):
+    return int(_L().dyn_adafactor_scratch_bytes(totals["n_rows"], totals["n_batches"], n_segments))
+
+
+def adafactor_step(p, g, state, seg_dev, totals, scratch, lr, beta2_decay, eps1, eps2, d, weight_decay, step):
+    """One torch.optim.Adafactor step (`step` counts from 1) of the flat buffers p / g with `state` (zeros when fresh) and the device
+    segment table `seg_dev` [n, 9] int64 of adafactor_segments()."""
+    _cc(p, "adafactor.p"); _cc(g, "adafactor.g"); _cc(state, "adafactor.state")
+    _cc(seg_dev, "adafactor.segments", torch.int64)
+    if state.numel() < totals["n_state"] or p.numel() < totals["extent"] or g.numel() < totals["extent"]:
+        raise DynError("adafactor: the segment table reaches beyond the parameter, gradient or state buffer")
+    if eps1 is None:
+        eps1 = torch.finfo(torch.float32).eps
+    check(_L().dyn_adafactor_step(p.data_ptr(), g.data_ptr(), state.data_ptr(), seg_dev.data_ptr(), seg_dev.shape[0], totals["n_rows"],
+                                  totals["n_batches"], totals["n_cols"], lr, beta2_decay, eps1, eps2, d, weight_decay, step,
+                                  scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream()), "dyn_adafactor_step")
+
+
 def stitch_accumulate(log_probs, acc, count, pos):
     _c(log_probs, "stitch.log_probs"); _cc(acc, "stitch.acc"); _cc(count, "stitch.count")
     rows, C = log_probs.shape

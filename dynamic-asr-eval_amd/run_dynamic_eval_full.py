@@ -78,9 +78,9 @@ def main(args):
     model, tokenizer = load_model_and_tokenizer(args, device)
     decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=model.decoder.num_classes - 1, device=device)
     data = datasets_functions[args.dataset](args.split)
-    if args.consistency:
-        raise NotImplementedError('dynamic_eval_consistency_ctc_loss is out of scope (SURVEY.md §2 row 3)')
-    eval_fn = lib.AWMC if args.awmc else dynamic_eval                   # reference run_dynamic_eval_full.py:67-72
+    consistency = bool(args.__dict__.get('consistency', False)) and not args.awmc
+    # reference run_dynamic_eval_full.py:67-72: -awmc first, then --consistency (looked up on `lib` at call time)
+    eval_fn = lib.AWMC if args.awmc else lib.dynamic_eval_consistency_ctc_loss if consistency else dynamic_eval
     # -beamsearch (reference :56-65,99-104): final texts from the LM beam search with lm_eval_beams; TTA pseudo-labels from it
     # too unless lm_tta_beams=0 (then no beam_search_fn reaches the eval function: the reference's `beams == 0` branch)
     beamsearch = lib.beamsearch_from_args(args, tokenizer, device) if args.__dict__.get('beamsearch', False) else None
@@ -98,8 +98,8 @@ def main(args):
     chains = int(args.__dict__.get('chains', 1))    # -kwargs chains=N: N recordings in flight per GPU (lib.dynamic_eval_many)
     lockstep = int(args.__dict__.get('lockstep', 1))   # -kwargs lockstep=R: every chain is a lockstep group of R recordings (lib._dynamic_eval_group_gen)
     models = None
-    if beam_search_fn is not None:
-        pass                                        # beam-search pseudo-labels: single-chain path (lib.lockstep_supported)
+    if beam_search_fn is not None or consistency:
+        pass                                        # beam-search pseudo-labels, the consistency loop: single-chain path (lib.lockstep_supported)
     elif lockstep > 1 and not args.awmc and len(mine) > 1:
         from .run_seq_eval import replicate
         models = replicate(model, max(1, min(chains, (len(mine) + lockstep - 1) // lockstep)), group=lockstep)

@@ -453,6 +453,31 @@ int dyn_clip_grad_norm(float* grads, int64_t n, float max_norm, float* norm_and_
                        int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The consistency loop (reference lcasr/lib.py:646-903): one parameter set and one gradient per window.
+ * dyn_grad_mix_decay: in-place distance-decayed mix of a gradient bank grads[n_windows][row_stride] (reference :817-841), for
+ * i = 0 .. n_windows-1 IN THIS ORDER (rows q < i are read already mixed):
+ *   grads[i] <- fl32( ( f64(grads[i]) + sum_{q != i, ascending q} f64(fl32(fl32(decay[|i-q|]) * grads[q])) ) / denom[i] )
+ * bit-identical to the reference's torch statements.  `ranges`: HOST array of n_ranges [lo, hi) element ranges of a row that are
+ * mixed (elements outside are not touched: parameters without a gradient); `decay` / `denom`: DEVICE arrays of n_windows doubles,
+ * decay[k] = 0.95 ** k and denom[i] = the reference's `total_sum` of window i, both formed on the host.  The windows of an element
+ * are staged in LDS: at most dyn_grad_mix_decay_max_windows() windows, more is DYN_E_ARG.
+ * dyn_adafactor_step: torch.optim.Adafactor's single-tensor rule (maximize=False) over a flat buffer.  `segments`: DEVICE table of
+ * n_segments x 9 int64 per tensor {offset, batch, rows, cols, state offset, factored, first row, first batch, first factored column}:
+ * a tensor of dimension >= 2 is batch x rows x cols (its last two dimensions) with row_var [batch * rows] then col_var [batch * cols] at
+ * `state offset` of `state`; a 1-D tensor is 1 x 1 x n, not factored, with variance [n] there.  first row / batch / factored column are
+ * the running sums of batch * rows, batch and (factored only) batch * cols over the table; n_rows, n_batches, n_factored_cols their
+ * totals.  `step` counts from 1 (torch's step_t after the increment); a fresh state is all zeros.  Six launches whatever the number of
+ * tensors; every reduction runs in a fixed order, so a step is reproducible bit for bit.  `scratch`: dyn_adafactor_scratch_bytes().
+ * ------------------------------------------------------------------------------------------------ */
+int64_t dyn_grad_mix_decay_max_windows(void);
+int dyn_grad_mix_decay(float* grads, int64_t row_stride, int32_t n_windows, const int64_t* ranges, int32_t n_ranges,
+                       const double* decay, const double* denom, void* stream);
+int64_t dyn_adafactor_scratch_bytes(int64_t n_rows, int64_t n_batches, int64_t n_segments);
+int dyn_adafactor_step(float* params, const float* grads, float* state, const int64_t* segments, int32_t n_segments,
+                       int64_t n_rows, int64_t n_batches, int64_t n_factored_cols, double lr, double beta2_decay, double eps1,
+                       double eps2, double d, double weight_decay, int64_t step, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Window stitching on device (reference lcasr/lib.py:583-589,604-609,615-629): acc[pos+r, c] += exp(lp[r, c]),
  * count[pos+r] += 1, then out = log(acc / count) over the covered prefix.
  * ------------------------------------------------------------------------------------------------ */
