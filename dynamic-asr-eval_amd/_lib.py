@@ -51,6 +51,14 @@ class DecoderDesc(ctypes.Structure):
     ]
 
 
+class DecoderBatchDesc(ctypes.Structure):
+    """Mirror of dyn_decoder_batch_desc (include/dyneval.h)."""
+    _fields_ = [
+        ("base", DecoderDesc), ("rows", ctypes.c_int32), ("eos_id", ctypes.c_int32),
+        ("token_stride", ctypes.c_int64), ("cache_stride", ctypes.c_int64), ("finished", ctypes.c_void_p),
+    ]
+
+
 DEC_PTRS_PER_LAYER = 18
 
 
@@ -115,7 +123,8 @@ def prototypes():
         for a in [x.strip() for x in args.split(",") if x.strip() and x.strip() != "void"]:
             if "*" in a:
                 argtypes.append(ctypes.POINTER(GemmDesc) if "dyn_gemm_desc" in a else
-                                ctypes.POINTER(DecoderDesc) if "dyn_decoder_desc" in a else ctypes.c_void_p)
+                                ctypes.POINTER(DecoderDesc) if "dyn_decoder_desc" in a else
+                                ctypes.POINTER(DecoderBatchDesc) if "dyn_decoder_batch_desc" in a else ctypes.c_void_p)
             else:
                 argtypes.append(_CTYPES[a.replace("const ", "").split()[0]])
         protos[name] = (restype, argtypes)

@@ -1,6 +1,7 @@
 // Small kernels of the encoder-decoder `teacher_ce` adaptation path (reference lcasr/lib.py:1228-1322 `calc_loss_enc_dec`,
 // :1475-1732 `enc_dec_dynamic_eval`): token-embedding gather and its deterministic gradient, the causal mask of the decoder's
-// self-attention scores, and cross-entropy (sum over rows, ignore_index) with its gradient w.r.t. the logits.  Everything dense in
+// self-attention scores, and cross-entropy (sum over rows, ignore_index) with its gradient w.r.t. the logits — also in the row-weighted
+// form of the RL modes' policy-gradient loss (update_grpo / update_maxrl, :1400-1472).  Everything dense in
 // the decoder (projections, attention products, FFN) goes through dyn_gemm_f32; norms / softmax / SiLU reuse the encoder's kernels.
 #include "common.h"
 
@@ -57,6 +58,20 @@ __global__ __launch_bounds__(256) void nll_grad_kernel(const float* __restrict__
         if (live) g = scale * (__expf(logp[r * C + c]) - (c == t ? 1.f : 0.f));
         grad[r * C + c] = g;
     }
+}
+
+// The row-weighted form (policy gradient of the RL modes): row_loss[r] = -w[r] * logp[r, target_r], grad[r, :] = w[r] * (exp(logp) - onehot).
+__global__ __launch_bounds__(256) void nll_weighted_kernel(const float* __restrict__ logp, const int32_t* __restrict__ targets,
+                                                           const float* __restrict__ weights, float* __restrict__ row_loss,
+                                                           float* __restrict__ grad, int64_t rows, int C) {
+    const int64_t r = blockIdx.x;
+    const int t = targets[r];
+    const bool live = t >= 0 && t < C;
+    const float wr = weights[r];
+    if (threadIdx.x == 0) row_loss[r] = live ? -wr * logp[r * C + t] : 0.f;
+    if (grad == nullptr) return;
+    for (int c = threadIdx.x; c < C; c += blockDim.x)
+        grad[r * C + c] = live ? wr * (__expf(logp[r * C + c]) - (c == t ? 1.f : 0.f)) : 0.f;
 }
 
 // ---- counter-based randomness: a draw is a pure function of (seed, stream, index); see include/dyneval.h (dyn::mix64 in common.h)
@@ -136,6 +151,16 @@ extern "C" int dyn_nll_loss(const float* log_probs, const int32_t* targets, floa
                            (int)ignore_index, grad_scale);
     hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, st, row_loss, loss, rows);
     return dyn::check_launch("dyn_nll_loss");
+}
+
+extern "C" int dyn_nll_loss_weighted(const float* log_probs, const int32_t* targets, const float* weights, float* loss, float* row_loss,
+                                     float* grad, int64_t rows, int64_t C, void* stream) {
+    DYN_REQUIRE(log_probs && targets && weights && loss && row_loss && rows >= 0 && C > 0, DYN_E_ARG, "dyn_nll_loss_weighted: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (rows > 0)
+        hipLaunchKernelGGL(nll_weighted_kernel, dim3((unsigned)rows), dim3(256), 0, st, log_probs, targets, weights, row_loss, grad, rows, (int)C);
+    hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, st, row_loss, loss, rows);      // fixed element-to-thread assignment
+    return dyn::check_launch("dyn_nll_loss_weighted");
 }
 
 extern "C" int dyn_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, uint64_t stream_id, void* stream) {

@@ -1,6 +1,7 @@
-"""Encoder-decoder test-time adaptation, `teacher_ce` mode: mirror of the reference's
-`calc_loss_enc_dec` (lcasr/lib.py:1228-1322), `enc_dec_inference` (:1112-1134), `generate_enc_dec` call sites (:1128) and
-`enc_dec_dynamic_eval` (:1475-1732), same names / argument meaning / printed lines, on the HIP kernels.
+"""Encoder-decoder test-time adaptation: mirror of the reference's `calc_loss_enc_dec` (lcasr/lib.py:1228-1322),
+`enc_dec_inference` (:1112-1134), `generate_enc_dec` (:1172-1226), `calc_rewards` / `_policy_forward` / `update_grpo` /
+`update_maxrl` (:1330-1472) and `enc_dec_dynamic_eval` (:1475-1732), same names / argument meaning / printed lines, on the HIP
+kernels.  `training_mode == 'teacher_ce'` runs as is; the RL modes `grpo` / `maxrl` are OPT-IN through `rl_reward` (below).
 
 The reference takes the model from the un-vendored `lcasr` package (`get_model_class(config)`, an SCConformerXL encoder with a
 CTC head plus `language_model_decoder`; enc_dec_dynamic_eval_test.py:45-46).  Only its call surface is visible in the reference:
@@ -14,9 +15,21 @@ vocabulary; bos = eos = 0 as in calc_loss_enc_dec's defaults (:1236-1237).  orac
 Scope: `training_mode == 'teacher_ce'` (:1638-1658) with every flag of that path: the teacher filters incl. the sampled-decode
 agreement filter (`model.generate(sample=True, temperature=...)`, :1620-1627) and the decoder dropout knobs `dropout_emb /
 dropout_post_ff / dropout_attn` (:1511-1522,1636-1637,1703-1707).  Randomness is counter-based (dyn_dropout / dyn_gumbel_argmax_rows:
-a draw is a pure function of (seed, stream, index)), so it is reproducible and the oracle restates it exactly.  The RL modes
-(`grpo`, `maxrl`: sampled rollouts, reward models) are out of scope and raise.  Decoder parameters live in the encoder's flat
-buffers (SCConformerXL(extra_spec=...)), so snapshot / restore / MADGRAD step are the same single operations as on the CTC path."""
+a draw is a pure function of (seed, stream, index)), so it is reproducible and the oracle restates it exactly.  Decoder parameters
+live in the encoder's flat buffers (SCConformerXL(extra_spec=...)), so snapshot / restore / MADGRAD step are the same single
+operations as on the CTC path.
+
+RL modes (`training_mode` 'grpo' / 'maxrl', :1659-1702): run only when `args.rl_reward` is set (harness: `-kwargs
+rl_reward="'wer_cer'"`); without it they raise NotImplementedError as before.  `rl_reward='wer_cer'` is the reference's
+`calc_rewards` WITHOUT ITS BLEU TERM — reward = ((1 - WER) + (1 - CER)) / 2 instead of (1 - WER + 1 - CER + BLEU) / 3, because
+`sacrebleu` is not vendored; a callable `(ref, hyps) -> [float]` is accepted in its place, so a site that has sacrebleu can pass the
+reference's exact reward.  Per window: 4 sampled rollouts of the augmented copy in ONE batched decode (`generate_batch`:
+dyn_decoder_steps_batch, row r draws with seed + r), rewards against the teacher's text, then `update_grpo` / `update_maxrl`: the
+rollouts are scored teacher-forced one at a time (causal, padded at the end only: exact), the policy-gradient loss is
+dyn_nll_loss_weighted with the per-rollout weight of `rl_row_weights`, and its gradient is ACCUMULATED into the flat gradient buffer
+(decoder gradients summed over rollouts, one encoder backward with the summed cross-attention gradient) — there is no autograd graph,
+the update functions return the loss as a float.  Rollouts come back in row order (the reference appends them in finishing order;
+every consumer pairs hypotheses and rewards by index).  With decoder dropout on, every rollout's scoring pass draws its own masks."""
 import ctypes
 import math
 import os
@@ -26,7 +39,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from ._lib import DEC_PTRS_PER_LAYER, DecoderDesc, check, load
+from ._lib import DEC_PTRS_PER_LAYER, DecoderBatchDesc, DecoderDesc, check, load
 from ._loop import augmented_batch, window_rule
 from .augment import SpecAugment
 from .decoding import GreedyCTCDecoder
@@ -34,6 +47,7 @@ from .enc_dec_teacher_filters import should_skip_faulty_teacher_prediction
 from .lib import get_lr_args_from_args, get_specaugment_config_from_args, prepare_chunks
 from .model import SCConformerXL
 from .optim import MADGRAD
+from .wer import word_error_rate_detail
 
 try:
     from tqdm import tqdm
@@ -151,10 +165,11 @@ class EncDecSCConformerXL(SCConformerXL):
 
     __call__ = forward
 
-    def generate(self, audio_signal, encoder_states=None, sample=False, temperature=1.0, max_tokens=None, seed=None, check_every=8):
+    def generate(self, audio_signal, encoder_states=None, sample=False, temperature=1.0, max_tokens=None, seed=None, check_every=8, step0=0):
         """Autoregressive decode of ONE window -> {'text_sequence': [ids]} (reference call sites lib.py:1128,1579-1582,1620-1625):
         greedy, or with `sample=True` a draw from softmax(logits / temperature) per step (Gumbel-max on counter-based uniforms:
-        dyn_gumbel_argmax_rows; `seed` defaults to a fresh stream of this model's random_seed).
+        dyn_gumbel_argmax_rows; `seed` defaults to a fresh stream of this model's random_seed, an explicit seed draws from stream
+        `step0` + t).
         Incremental: every step runs ONE token through the decoder against per-layer caches — the self-attention keys / values of
         the prefix live in a packed [limit + 1, 3 * dd] buffer the QKV projection writes row t of, the cross-attention keys /
         values of the encoder states are projected once.  The chosen id goes straight into the device token buffer; the host
@@ -170,8 +185,6 @@ class EncDecSCConformerXL(SCConformerXL):
                     raise ops.DynError("generate(sample=True): temperature must be > 0")
                 if seed is None:
                     seed, step0 = self.random_seed, self._next_stream()
-                else:
-                    step0 = 0
             st = torch.cuda.current_stream().cuda_stream
             with ops.use_workspace(self._scratch()):
                 kv = [ops.linear(h, P[f"{DEC}layers.{l}.cross.kv.weight"], P[f"{DEC}layers.{l}.cross.kv.bias"]) for l in range(L)]
@@ -200,7 +213,60 @@ class EncDecSCConformerXL(SCConformerXL):
                 toks = tok_dev[1:t + 1].tolist()[:n_tok] if n_tok is not None else tok_dev[1:t + 1].tolist()
         return {"text_sequence": toks}
 
-    def _decoder_desc(self, kv, cache, tok_dev, n_enc):
+    def generate_batch(self, audio_signal, rows, encoder_states=None, temperature=1.0, max_tokens=None, seed=None, check_every=8,
+                       bos_id=0, eos_id=0, fill=None):
+        """`rows` (1 .. 8) SAMPLED decodes of one window in lockstep -> {'text_sequences': [[ids] per row]}: row r is what
+        `generate(sample=True, temperature=..., seed=seed + r, max_tokens=...)` returns, token for token (dyn_decoder_steps_batch:
+        every weight row is read once per step for all live rows, each row's sums in the single-row kernel's order).  The
+        cross-attention keys / values are projected once and shared; every row has its own self-attention cache, token buffer and
+        device-side `finished` flag — a row that drew eos runs no more work and writes nothing.  The host reads the flags every
+        `check_every` steps.  `fill`: value the fresh caches / scratch are filled with (tests: NaN exposes a read of a row never written).
+        With `fused_decode` off the rows are decoded one after the other through the tile-kernel path of `generate`."""
+        rows = int(rows)
+        if not 1 <= rows <= 8:
+            raise ops.DynError(f"generate_batch: {rows} rows (1 .. 8)")
+        if not temperature > 0.0:
+            raise ops.DynError("generate_batch: temperature must be > 0")
+        with torch.no_grad():
+            enc = encoder_states if encoder_states is not None else self.forward(audio_signal)
+            h = enc["hidden"][0]
+            limit = max_tokens if max_tokens is not None else max(1, min(self.dec["dec_max_positions"] - 1, h.shape[0] // 2))
+            limit = min(int(limit), self.dec["dec_max_positions"] - 1)
+            seed, step0 = (self.random_seed, self._next_stream()) if seed is None else (seed, 0)
+            if not self.fused_decode or bos_id != 0 or eos_id != 0:
+                if bos_id != 0 or eos_id != 0:
+                    raise ops.DynError("generate_batch: bos = eos = 0 only (calc_loss_enc_dec's defaults, lib.py:1236-1237)")
+                return {"text_sequences": [self.generate(audio_signal, encoder_states=enc, sample=True, temperature=temperature, max_tokens=limit,
+                                                         seed=int(seed) + r, step0=step0, check_every=check_every)["text_sequence"]
+                                           for r in range(rows)]}                                  # the same draws: (seed + r, step0 + t)
+            dc, P = self.dec, self.P
+            dd, L = dc["dec_d_model"], dc["dec_layers"]
+            st = torch.cuda.current_stream().cuda_stream
+            new = (lambda *shape: torch.empty(*shape, device=self.device, dtype=torch.float32)) if fill is None else \
+                (lambda *shape: torch.full(shape, float(fill), device=self.device, dtype=torch.float32))
+            with ops.use_workspace(self._scratch()):
+                kv = [ops.linear(h, P[f"{DEC}layers.{l}.cross.kv.weight"], P[f"{DEC}layers.{l}.cross.kv.bias"]) for l in range(L)]
+                cache = [new(rows, limit + 1, 3 * dd) for _ in range(L)]
+                tok_dev = torch.zeros(rows, limit + 2, dtype=torch.int32, device=self.device)
+                tok_dev[:, 0] = bos_id
+                finished = torch.zeros(rows, dtype=torch.int32, device=self.device)
+                per_row = int(load().dyn_decoder_row_scratch_floats(dd, dd * dc["dec_ff_mult"], dc["dec_heads"]))
+                base, keep = self._decoder_desc(kv, cache, tok_dev, h.shape[0], logits=new(rows, self.vocab), scratch=new(rows, per_row))
+                desc = DecoderBatchDesc(base=base, rows=rows, eos_id=int(eos_id), token_stride=limit + 2, cache_stride=(limit + 1) * 3 * dd,
+                                        finished=finished.data_ptr())
+                t = 0
+                while t < limit:
+                    n = min(check_every, limit - t)
+                    check(load().dyn_decoder_steps_batch(ctypes.byref(desc), t, n, 1, 1.0 / float(temperature), int(seed), int(step0), st),
+                          "dyn_decoder_steps_batch")
+                    t += n
+                    if all(finished.tolist()):                                                     # one sync per `check_every` tokens
+                        break
+                got = tok_dev[:, 1:t + 1].tolist()
+            del keep
+        return {"text_sequences": [g[:g.index(eos_id)] if eos_id in g else g for g in got]}
+
+    def _decoder_desc(self, kv, cache, tok_dev, n_enc, logits=None, scratch=None):
         """dyn_decoder_desc of one generate() call (include/dyneval.h): returns (descriptor, objects it points into)."""
         P, dc = self.P, self.dec
         dd, L = dc["dec_d_model"], dc["dec_layers"]
@@ -214,8 +280,8 @@ class EncDecSCConformerXL(SCConformerXL):
                 ptrs[l * DEC_PTRS_PER_LAYER + i] = P[f"{DEC}layers.{l}.{nm}"].data_ptr()
             ptrs[l * DEC_PTRS_PER_LAYER + 16] = cache[l].data_ptr()
             ptrs[l * DEC_PTRS_PER_LAYER + 17] = kv[l].data_ptr()
-        logits = torch.empty(self.vocab, device=self.device, dtype=torch.float32)
-        scratch = torch.empty(6 * dd + ff + 16 * dc["dec_heads"], device=self.device, dtype=torch.float32)
+        logits = torch.empty(self.vocab, device=self.device, dtype=torch.float32) if logits is None else logits
+        scratch = torch.empty(6 * dd + ff + 16 * dc["dec_heads"], device=self.device, dtype=torch.float32) if scratch is None else scratch
         d = DecoderDesc(d_model=dd, heads=dc["dec_heads"], d_ff=ff, vocab=self.vocab, layers=L, n_enc=int(n_enc),
                         max_positions=dc["dec_max_positions"], eps=float(self.config["norm_eps"]),
                         embed=P[DEC + "embed.weight"].data_ptr(), pos_table=self.pos_table.data_ptr(),
@@ -477,12 +543,159 @@ def calc_loss_enc_dec(model, audio_signal, text_sequence, a_lengths, t_lengths, 
             "ctc_posteriors": ctc_out, "lm_posteriors": lm_out, "length": out["length"]}
 
 
-def generate_enc_dec(model, audio_signal, **kw):
-    """reference call site lib.py:1128: `generate_enc_dec(model, audio_chunk)[0]` -> token ids of the greedy decode.  The
-    `sample=4, greedy=False` form is the RL rollout of the grpo / maxrl modes (lib.py:1667-1673): out of scope."""
-    if kw.get("sample", 1) != 1 or kw.get("greedy", True) is False:
-        raise NotImplementedError("sampled rollouts (RL modes) are out of scope")
-    return [torch.tensor(model.generate(audio_signal)["text_sequence"], dtype=torch.long)]
+def generate_enc_dec(model, audio_signal, max_generate=256, bos_id=0, eos_id=0, sample=1, greedy=True, temperature=1.0, seed=None):
+    """reference lcasr/lib.py:1172-1226.  `sample=1, greedy=True` (call site :1128, `generate_enc_dec(model, audio_chunk)[0]`):
+    [token ids of the greedy decode].  Any other combination is the sampled form (the RL rollouts, :1665-1671): `sample` rows drawn
+    in one batched decode -> (text_sequence [R, Lmax] long, padded with 0, bos removed; encoder_out; text_lengths [R]) as :1220-1226.
+    Kept from the reference: the softmax input is `logits * temperature` (:1200 multiplies; the one call site passes 1.0); a row
+    retires when its draw is `eos_id` or when its length including bos exceeds `max_generate` — the draw made at retirement is
+    discarded, so a row holds at most `max_generate` tokens; the decoder's `dec_max_positions` caps a row as well.  Different: rows
+    come back in ROW order (the reference appends in finishing order).  `seed`: row r draws with seed + r (default: a fresh stream
+    block of `model.random_seed`)."""
+    if sample == 1 and greedy:
+        return [torch.tensor(model.generate(audio_signal)["text_sequence"], dtype=torch.long)]
+    if not temperature > 0.0:
+        raise ValueError("generate_enc_dec: temperature must be > 0")
+    with torch.no_grad():
+        encoder_out = model.forward(audio_signal=audio_signal)
+    limit = max(1, min(int(max_generate), model.dec["dec_max_positions"] - 1))
+    seqs = model.generate_batch(audio_signal, sample, encoder_states=encoder_out, temperature=1.0 / float(temperature), max_tokens=limit,
+                                seed=seed, bos_id=bos_id, eos_id=eos_id)["text_sequences"]
+    text_lengths = torch.LongTensor([len(q) for q in seqs])
+    text_sequence = torch.zeros(len(seqs), max(len(q) for q in seqs), dtype=torch.long)
+    for r, q in enumerate(seqs):
+        text_sequence[r, :len(q)] = torch.tensor(q, dtype=torch.long)
+    return text_sequence.to(model.device), encoder_out, text_lengths
+
+
+WER_CER_NOTE = ("rl_reward='wer_cer': reward = ((1 - WER) + (1 - CER)) / 2 - the reference's BLEU term (sacrebleu.corpus_bleu, lib.py:1350) is "
+                "dropped: sacrebleu is not available; pass a callable (ref, hyps) -> [float] as rl_reward for another reward")
+
+
+def calc_rewards(ref, hyps):
+    """reference lcasr/lib.py:1330-1359 WITHOUT THE BLEU TERM (`rl_reward='wer_cer'`): per hypothesis ((1 - WER) + (1 - CER)) / 2
+    where the reference averages 1 - WER, 1 - CER and sacrebleu.corpus_bleu / 100 (sacrebleu is not vendored).  The two empty-string
+    branches (:1341-1346) are kept as written: both empty -> 1.0, empty reference and a non-empty hypothesis -> -(number of words)."""
+    rewards = []
+    for hyp in hyps:
+        if len(hyp.strip()) == 0 and len(ref.strip()) == 0:
+            rewards.append(1.0)
+            continue
+        elif len(ref.strip()) == 0 and len(hyp.strip()) > 0:
+            rewards.append(len(hyp.strip().split()) * -1.0)
+            continue
+        wer = word_error_rate_detail([hyp], [ref])[0] * -1.0 + 1
+        cer = word_error_rate_detail([hyp], [ref], use_cer=True)[0] * -1.0 + 1
+        rewards.append((wer + cer) / 2.0)
+    print(sum(rewards) / len(rewards), "avg reward")
+    return rewards
+
+
+def _reward_fn(rl_reward):
+    if rl_reward == 'wer_cer':
+        return calc_rewards
+    if callable(rl_reward):
+        return lambda ref, hyps: [float(r) for r in rl_reward(ref, hyps)]
+    raise ValueError(f"rl_reward {rl_reward!r}: 'wer_cer' or a callable (ref: str, hyps: list[str]) -> list[float]")
+
+
+def rl_row_weights(mode, rewards, lengths, normalize_std=True, std_epsilon=1e-7, success_threshold=0.9, epsilon=1e-6):
+    """Per-rollout weight w_j of the policy-gradient loss `sum_j w_j * sum_t (-log p(y_jt))` over the n_j = lengths[j] + 1 scored
+    tokens (hypothesis + eos) of rollout j — the reference's losses with their advantages folded in, in its float32 arithmetic:
+      'grpo'  (lib.py:1411-1420): A = r - mean(r) [/ (std(r, unbiased=False) + std_epsilon)];  w_j = A_j / (n_j * R)
+      'maxrl' (:1450-1470): r binarised at success_threshold, pass rate m; None when m <= 0 or m >= 1 (the skip cases);
+                            A = (r - m) / (m + epsilon);  w_j = A_j / sum_j n_j
+    Returns (weights [R] float32 tensor, advantage [R]) or None."""
+    counts = torch.as_tensor([int(n) + 1 for n in lengths], dtype=torch.float32)
+    R = len(rewards)
+    assert R == counts.shape[0] and R > 0
+    if mode == 'grpo':
+        r = torch.as_tensor(rewards, dtype=torch.float32)
+        advantage = r - r.mean()
+        if normalize_std:
+            advantage = advantage / (r.std(unbiased=False) + std_epsilon)
+        return advantage / R / counts, advantage
+    if mode == 'maxrl':
+        r = torch.as_tensor([1.0 if x >= success_threshold else 0.0 for x in rewards], dtype=torch.float32)
+        mean = r.mean()
+        if mean.item() <= 0 or mean.item() >= 1:
+            return None
+        advantage = (r - mean) / (mean + epsilon)
+        return advantage / counts.sum(), advantage
+    raise ValueError(f"rl_row_weights: mode {mode!r}")
+
+
+def policy_forward(model, audio_signal, tokenizer, hyps, weights=None):
+    """reference lcasr/lib.py:1361-1397 (`_policy_forward`): teacher-forced log-probabilities of the rollouts' own tokens ->
+    (log_probs [R, Lmax] float32, mask [R, Lmax] bool) on the host, row j valid for len(encode(hyps[j])) + 1 positions (tokens, then
+    eos).  The rollouts are causal and padded at the end only, so each runs through the B = 1 decoder at its own length: exact.
+    With `weights` [R] it is also the backward of loss = sum_j weights[j] * sum_t (-log_probs[j, t]): one encoder forward in grad
+    mode, per rollout decoder forward / dyn_nll_loss_weighted / decoder backward (parameter gradients ACCUMULATE in the flat
+    buffer), then one encoder backward with the cross-attention gradients on the encoder states summed over rollouts (the CTC
+    head receives a zero gradient).  Returns (log_probs, mask, loss as a python float) then."""
+    assert audio_signal.shape[0] == 1, 'Must be bsz of 1 for audio signal'
+    dev = model.device
+    ids = [_check_ids(tokenizer.encode(t), model.vocab, "policy_forward: hypothesis") for t in hyps]
+    R, Lmax = len(ids), max(len(q) for q in ids) + 1
+    grad = weights is not None
+    st = torch.cuda.current_stream().cuda_stream
+    with (torch.enable_grad() if grad else torch.no_grad()):
+        enc = model.forward(audio_signal)
+        h = enc["hidden"][0]
+        log_probs = torch.zeros(R, Lmax, dtype=torch.float32, device=dev)
+        mask = torch.zeros(R, Lmax, dtype=torch.bool)
+        losses = torch.zeros(R, dtype=torch.float32, device=dev)
+        dh = None
+        with ops.use_workspace(model._scratch()):
+            for j, seq in enumerate(ids):
+                S = len(seq) + 1
+                tokens = torch.tensor([0] + seq, dtype=torch.int32, device=dev)                      # bos first
+                targets = torch.tensor(seq + [0], dtype=torch.int32, device=dev)                     # eos last
+                logp = ops.log_softmax(model._decoder_forward(tokens, h))
+                log_probs[j, :S] = logp.gather(1, targets.long()[:, None])[:, 0]
+                mask[j, :S] = True
+                if grad:
+                    w = torch.full((S,), float(weights[j]), dtype=torch.float32, device=dev)
+                    g, row = torch.empty_like(logp), torch.empty(S, dtype=torch.float32, device=dev)
+                    check(load().dyn_nll_loss_weighted(logp.data_ptr(), targets.data_ptr(), w.data_ptr(), losses[j:].data_ptr(), row.data_ptr(),
+                                                       g.data_ptr(), S, model.vocab, st), "dyn_nll_loss_weighted")
+                    d = model._decoder_backward(g)
+                    dh = d if dh is None else ops.axpby(d, dh)
+    if not grad:
+        return log_probs.cpu(), mask
+    model.backward(torch.zeros_like(enc["final_posteriors_ctc"]), grad_hidden=dh[None])
+    return log_probs.cpu(), mask, float(sum(losses.tolist()))
+
+
+def update_grpo(model, audio_signal, tokenizer, hyps, rewards, normalize_std=True, std_epsilon=1e-7):
+    """reference lcasr/lib.py:1400-1422: loss = -mean_j(A_j * mean_t log p(y_jt)).  Returns the loss as a python float and accumulates
+    its gradient into the model's flat gradient buffer (the reference returns a tensor and the loop calls .backward())."""
+    lengths = [len(tokenizer.encode(t)) for t in hyps]
+    weights, advantage = rl_row_weights('grpo', rewards, lengths, normalize_std=normalize_std, std_epsilon=std_epsilon)
+    print(advantage)
+    _, _, loss = policy_forward(model, audio_signal, tokenizer, hyps, weights=weights.tolist())
+    print(loss, "loss")
+    return loss
+
+
+def update_maxrl(model, audio_signal, tokenizer, hyps, rewards, success_threshold=0.9, epsilon=1e-6):
+    """reference lcasr/lib.py:1425-1472 (Maximum Likelihood RL, on-policy): rewards binarised at `success_threshold`, advantage
+    (r - pass rate) / (pass rate + epsilon), loss = sum of -log p * A over the valid tokens / their number.  None (and no gradient)
+    when the pass rate is 0 or 1.  Otherwise the loss as a python float, its gradient accumulated as update_grpo does."""
+    lengths = [len(tokenizer.encode(t)) for t in hyps]
+    out = rl_row_weights('maxrl', rewards, lengths, success_threshold=success_threshold, epsilon=epsilon)
+    if out is None:
+        if not any(r >= success_threshold for r in rewards):
+            print(f'maxrl: pass rate=0 (no rollout >= {success_threshold}), skipping task')
+        else:
+            print(f'maxrl: pass rate=1 (all rollouts >= {success_threshold}), skipping task (zero advantage)')
+        return None
+    weights, advantage = out
+    mean = sum(1.0 for r in rewards if r >= success_threshold) / len(rewards)
+    print(f'maxrl: pass rate={mean:.3f}, advantages={advantage.tolist()}')
+    _, _, loss = policy_forward(model, audio_signal, tokenizer, hyps, weights=weights.tolist())
+    print(loss, "loss (maxrl)")
+    return loss
 
 
 def enc_dec_inference(model, spec, seq_len, overlap, tokenizer, use_tqdm=True):
@@ -504,13 +717,23 @@ def enc_dec_inference(model, spec, seq_len, overlap, tokenizer, use_tqdm=True):
 
 def enc_dec_dynamic_eval(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=MADGRAD, optimizer_state=None,
                          return_params=False, **kwargs):
-    """reference lcasr/lib.py:1475-1732, `training_mode == 'teacher_ce'`: per window — augmented + clean copy (:1574-1576), teacher =
-    greedy decode of the clean copy from one no-grad encoder pass (:1580-1588), the teacher filters (:1596-1633), then one
-    supervised step on the augmented copy with the teacher's tokens as target: calc_loss_enc_dec -> zero_grad / backward / step
-    (:1638-1658); afterwards the whole recording is decoded with the adapted weights (:1714-1722) and the weights restored (:1728-1729)."""
+    """reference lcasr/lib.py:1475-1732: per window — augmented + clean copy (:1574-1576), teacher = greedy decode of the clean copy
+    from one no-grad encoder pass (:1580-1588), the teacher filters (:1596-1633), then the update.  `training_mode == 'teacher_ce'`:
+    one supervised step on the augmented copy with the teacher's tokens as target: calc_loss_enc_dec -> zero_grad / backward / step
+    (:1638-1658).  `training_mode` 'grpo' / 'maxrl' WITH `args.rl_reward` set ('wer_cer' = the reference's reward without its BLEU
+    term, or a callable (ref, hyps) -> [float]), :1659-1702: ctc_loss_weight zeroed for the step, 4 sampled rollouts of the augmented
+    copy at temperature 1.0, rewards against the teacher's text, no update when the mean reward exceeds 0.95, `skipping` when all
+    rewards are zero or equal, else update_maxrl (`args.maxrl_success_threshold`) / update_grpo (`args.grpo_normalize_std`) ->
+    zero_grad / step.  Without `rl_reward` those modes raise NotImplementedError.  Afterwards the whole recording is decoded with
+    the adapted weights (:1714-1722) and the weights restored (:1728-1729)."""
     mode = getattr(args, 'training_mode', 'grpo')
-    if mode != 'teacher_ce':
+    rl_reward = args.__dict__.get('rl_reward')
+    if mode != 'teacher_ce' and (rl_reward is None or mode not in ('grpo', 'maxrl')):
         raise NotImplementedError(f"training_mode {mode!r}: only 'teacher_ce' is implemented (the RL modes grpo / maxrl are out of scope)")
+    reward_fn = None
+    if mode != 'teacher_ce':
+        reward_fn = _reward_fn(rl_reward)
+        print(WER_CER_NOTE if rl_reward == 'wer_cer' else f'rl_reward: {getattr(rl_reward, "__name__", rl_reward)!r} (caller-supplied reward)')
     dropout_emb = args.__dict__.get('dropout_emb', 0.0)
     dropout_post_ff = args.__dict__.get('dropout_post_ff', 0.0)
     dropout_attn = args.__dict__.get('dropout_attn', 0.0)
@@ -591,11 +814,38 @@ def enc_dec_dynamic_eval(args, model, spec, seq_len, overlap, tokenizer, use_tqd
             for layer in model.language_model_decoder.layers:                            # lib.py:1636-1637
                 layer[0].fn.dropout_p = dropout_attn
             model.language_model_decoder.train()   # for dropout
-            optimizer.zero_grad()
-            out = calc_loss_enc_dec(model=model, audio_signal=audio_chunk[:num_negatives].contiguous(), text_sequence=teacher_pred[None, :],
-                                    a_lengths=acoustic_length, t_lengths=text_lengths, tokenizer=tokenizer)
-            print(out['loss'], "loss (teacher_ce)")
-            optimizer.step()
+            if mode == 'teacher_ce':
+                optimizer.zero_grad()
+                out = calc_loss_enc_dec(model=model, audio_signal=audio_chunk[:num_negatives].contiguous(), text_sequence=teacher_pred[None, :],
+                                        a_lengths=acoustic_length, t_lengths=text_lengths, tokenizer=tokenizer)
+                print(out['loss'], "loss (teacher_ce)")
+                optimizer.step()
+            else:                                                                        # lib.py:1659-1702
+                original_ctc_loss_weight = model.ctc_loss_weight
+                model.ctc_loss_weight = 0.0
+                rl_audio = audio_chunk[:num_negatives].contiguous()
+                student_rollouts, _, rollout_lengths = generate_enc_dec(model=model, audio_signal=rl_audio, sample=4, greedy=False, temperature=1.0)
+                # the reference decodes the padded rows (`seq.tolist()`, :1673); the padding is cut here: id 0 is a word of the
+                # synthetic tokenizer, and `_policy_forward` re-encodes the text, so padding would become tokens of the hypothesis
+                student_rollouts_text = [tokenizer.decode(seq[:int(n)].tolist()).strip() for seq, n in zip(student_rollouts, rollout_lengths)]
+                print(f'Student rollouts: {student_rollouts_text} \n--------------------------------\n')
+                rewards = reward_fn(teacher_pred_text, student_rollouts_text)
+                print(rewards)
+                if sum(rewards) / len(rewards) > 0.95:                                   # :1679-1682: no update for this window
+                    pass
+                elif all(r == 0.0 for r in rewards) or all(r == rewards[0] for r in rewards):
+                    print('skipping')
+                else:
+                    optimizer.zero_grad()        # before the update: the gradient is accumulated by update_*, not by a later .backward()
+                    if mode == 'maxrl':
+                        loss = update_maxrl(model, audio_signal=rl_audio, tokenizer=tokenizer, hyps=student_rollouts_text, rewards=rewards,
+                                            success_threshold=getattr(args, 'maxrl_success_threshold', 0.9))
+                    else:
+                        loss = update_grpo(model, audio_signal=rl_audio, tokenizer=tokenizer, hyps=student_rollouts_text, rewards=rewards,
+                                           normalize_std=getattr(args, 'grpo_normalize_std', True))
+                    if loss is not None:
+                        optimizer.step()
+                model.ctc_loss_weight = original_ctc_loss_weight
             model.language_model_decoder.eval()                                          # lib.py:1703-1707
             for layer in model.language_model_decoder.layers:
                 layer[0].fn.dropout_p = 0

@@ -56,11 +56,12 @@ def _align(hyp, ref):
     return int(ins[m]), int(dele[m]), int(sub[m])
 
 
-def edit_counts(hypotheses, references):
-    """(insertions, deletions, substitutions, reference_words) summed over the corpus."""
+def edit_counts(hypotheses, references, use_cer=False):
+    """(insertions, deletions, substitutions, reference_words) summed over the corpus; with `use_cer` the units are the
+    characters of each string, spaces included (`list(h)`, as the NeMo-derived `lcasr.eval.wer` the reference imports)."""
     tot = [0, 0, 0, 0]
     for h, r in zip(hypotheses, references):
-        hw, rw = h.split(), r.split()
+        hw, rw = (list(h), list(r)) if use_cer else (h.split(), r.split())
         vocab = {}
         hi = [vocab.setdefault(w, len(vocab)) for w in hw]
         ri = [vocab.setdefault(w, len(vocab)) for w in rw]
@@ -75,5 +76,5 @@ def rates_from_counts(ins, dele, sub, words):
     return (ins + dele + sub) / words, words, ins / words, dele / words, sub / words
 
 
-def word_error_rate_detail(hypotheses, references):
-    return rates_from_counts(*edit_counts(hypotheses, references))
+def word_error_rate_detail(hypotheses, references, use_cer=False):
+    return rates_from_counts(*edit_counts(hypotheses, references, use_cer=use_cer))

@@ -365,6 +365,12 @@ int dyn_embedding_bwd(const int32_t* ids, const float* dy, float* dtable, int64_
 int dyn_causal_mask(float* scores, int64_t nb, int64_t S, void* stream);
 int dyn_nll_loss(const float* log_probs, const int32_t* targets, float* loss, float* row_loss, float* grad, int64_t rows, int64_t C,
                  int32_t ignore_index, float grad_scale, void* stream);
+/* Row-weighted form, the policy-gradient loss of the RL modes (update_grpo / update_maxrl, reference lcasr/lib.py:1400-1472, where
+ * the weight of a token row of rollout j is A_j / (n_j * R) resp. A_j / sum(mask)): loss = sum_r w[r] * (-logp[r, target[r]]),
+ * row_loss[r] = that term, grad[r, :] = w[r] * (exp(logp[r, :]) - onehot(target[r])); fixed reduction order.  A target outside
+ * [0, C) is an argument the caller must not pass: such a row contributes nothing. */
+int dyn_nll_loss_weighted(const float* log_probs, const int32_t* targets, const float* weights, float* loss, float* row_loss, float* grad,
+                          int64_t rows, int64_t C, void* stream);
 /* Counter-based randomness of the teacher_ce path (no device RNG state, a draw is a pure function of (seed, stream, index)):
  *   z = splitmix64_finish(seed ^ (stream + 1) * 0x9E3779B97F4A7C15 ^ (index + 1) * 0xC2B2AE3D27D4EB4F)
  *   dropout:  keep element i iff (z >> 40) * 2^-24 >= p;  y = keep ? x * 1 / (1 - p) : 0   (in place allowed; the backward is the same
@@ -410,6 +416,28 @@ typedef struct {
 } dyn_decoder_desc;
 int dyn_decoder_steps(const dyn_decoder_desc* d, int32_t t0, int32_t n_steps, int32_t sample, float inv_temperature, uint64_t seed,
                       uint64_t step0, void* stream);
+
+/* The same decode for `rows` (1 .. 8) sequences over the SAME encoder states, one position per step for all of them: the sampled
+ * rollouts of the RL modes (`generate_enc_dec(sample=4, greedy=False)`, reference lcasr/lib.py:1172-1226,1665-1671).  The launch
+ * count per token is that of dyn_decoder_steps; every row-times-matrix kernel reads a weight row ONCE and applies it to all rows of a
+ * group of four, each row's dot product accumulated in the single-row kernel's order (a row's logits are bit-identical to
+ * dyn_decoder_steps on that row alone).  `base` describes row 0; row r lives at
+ *   tokens + r * token_stride, layer cache + r * cache_stride, logits + r * vocab, scratch + r * (scratch_floats / rows);
+ * the cross-attention keys / values (layer pointer 17) are shared.  Row r draws with seed + r, stream step0 + t.
+ * finished[r] != 0 on entry or set here when row r draws `eos_id`: from then on the row runs no kernel work, writes nothing to its
+ * cache and every later token slot of it receives eos_id.  The caller reads `finished` / the tokens back when it likes.
+ * base.scratch_floats >= rows * dyn_decoder_row_scratch_floats(d_model, d_ff, heads); token_stride > t0 + n_steps;
+ * cache_stride >= (t0 + n_steps) * 3 * d_model; cache_stride and the per-row scratch are multiples of 4 floats. */
+typedef struct {
+    dyn_decoder_desc base;
+    int32_t rows, eos_id;
+    int64_t token_stride;      /* int32 entries between the token buffers of consecutive rows */
+    int64_t cache_stride;      /* floats between the self-attention caches of consecutive rows (every layer) */
+    int32_t* finished;         /* device [rows] */
+} dyn_decoder_batch_desc;
+int64_t dyn_decoder_row_scratch_floats(int64_t d_model, int64_t d_ff, int64_t heads);
+int dyn_decoder_steps_batch(const dyn_decoder_batch_desc* d, int32_t t0, int32_t n_steps, int32_t sample, float inv_temperature,
+                            uint64_t seed, uint64_t step0, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * CTC.  dyn_ctc_greedy replaces GreedyCTCDecoder on a CPU copy of the posteriors (reference lcasr/lib.py:498,
