@@ -37,7 +37,11 @@ __global__ __launch_bounds__(TPB) void gelu_bwd_kernel(const float* __restrict__
 }
 
 // ---- per-(batch, channel) normalisation over time: x [B, T, C] ----------------------------------------------------
-// stage 1: partial[(b, chunk), 0:C] = sum_t x, partial[(b, chunk), C:2C] = sum_t x^2 over the chunk's rows
+// The statistics are SHIFTED sums: E[x^2] - mean^2 cancels the leading digits when |mean| >> std (audio with a DC offset, a conv
+// channel with a large mean), so every chunk sums d = x - k with k = its own first row of that column and the chunks are merged from
+// (count, mean, M2) with Chan's update.  Still one pass over x.  What is left cancels in |k - chunk mean| / std instead of |mean| / std:
+// a few units for a stationary column, more only where a chunk's first row is itself an outlier of that chunk.
+// stage 1: partial[(b, chunk), 0:C] = sum_t (x - k), partial[(b, chunk), C:2C] = sum_t (x - k)^2 over the chunk's rows, k = x[b, r0, c]
 // `valid` (device scalar, may be null): only the first *valid rows of every batch entry count (a zero-padded bucket, see dyn_colnorm_fwd_len)
 __device__ __forceinline__ int64_t valid_rows(const int32_t* valid, int64_t T) {
     if (!valid) return T;
@@ -56,39 +60,55 @@ __global__ __launch_bounds__(TPB) void colstats_partial_kernel(const float* __re
     const int64_t r1 = (r0 + rows_per_chunk < Tv) ? r0 + rows_per_chunk : Tv;
     float s = 0.f, q = 0.f;
     const float* xb = x + b * T * C + c;
-    for (int64_t t = r0; t < r1; ++t) {
-        const float v = xb[t * C];
-        s += v;
-        q += v * v;
+    if (r0 < r1) {
+        const float k = xb[r0 * C];
+        for (int64_t t = r0; t < r1; ++t) {
+            const float d = xb[t * C] - k;
+            s += d;
+            q += d * d;
+        }
     }
     float* p = partial + ((b * chunks + ch) * 2) * C;
     p[c] = s;
     p[C + c] = q;
 }
 
-// stage 2 (per batch): mean/rstd [B, C] from the chunk partials, summed in chunk order
-__global__ __launch_bounds__(TPB) void colstats_final_kernel(const float* __restrict__ partial, float* __restrict__ mean,
-                                                             float* __restrict__ rstd, int64_t T, int C, int chunks, float eps,
+// stage 2 (per batch): mean/rstd [B, C] from the chunk partials, merged in chunk order in double.  The shift k of a chunk is re-read
+// from x; a chunk whose rows are all past *valid has no rows and contributes nothing.
+__global__ __launch_bounds__(TPB) void colstats_final_kernel(const float* __restrict__ x, const float* __restrict__ partial,
+                                                             float* __restrict__ mean, float* __restrict__ mean_lo, float* __restrict__ rstd,
+                                                             int64_t T, int C, int64_t rows_per_chunk, int chunks, float eps,
                                                              const int32_t* __restrict__ valid) {
     const int c = blockIdx.x * TPB + threadIdx.x;
     const int64_t b = blockIdx.y;
     if (c >= C) return;
-    T = valid_rows(valid, T);
-    if (T < 1) T = 1;
-    double s = 0.0, q = 0.0;
+    const int64_t Tv = valid_rows(valid, T);
+    double n = 0.0, m = 0.0, m2 = 0.0;
     for (int ch = 0; ch < chunks; ++ch) {
+        const int64_t r0 = (int64_t)ch * rows_per_chunk;
+        const int64_t r1 = (r0 + rows_per_chunk < Tv) ? r0 + rows_per_chunk : Tv;
+        if (r0 >= r1) break;
         const float* p = partial + ((b * chunks + ch) * 2) * C;
-        s += (double)p[c];
-        q += (double)p[C + c];
+        const double nc = (double)(r1 - r0), s = (double)p[c], q = (double)p[C + c];
+        const double mc = (double)x[(b * T + r0) * C + c] + s / nc;
+        double m2c = q - s * s / nc;
+        if (m2c < 0.0) m2c = 0.0;
+        const double tot = n + nc, delta = mc - m;
+        m += delta * (nc / tot);
+        m2 += m2c + delta * delta * (n * nc / tot);
+        n = tot;
     }
-    const double m = s / (double)T;
-    double var = q / (double)T - m * m;  // biased variance (GroupNorm / InstanceNorm)
-    if (var < 0.0) var = 0.0;
-    mean[b * C + c] = (float)m;
+    const double var = n > 0.0 ? m2 / n : 0.0;  // biased variance (GroupNorm / InstanceNorm); no valid row: mean 0, var 0
+    const float mh = (float)m;
+    mean[b * C + c] = mh;
+    mean_lo[b * C + c] = (float)(m - (double)mh);   // what fp32 cannot hold of the mean (up to ulp(mean) / 2): the forward subtracts it too
     rstd[b * C + c] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
+// y = ((x - mean) - mean_lo) * rstd * gamma + beta: x - mean is exact where x is within a factor 2 of the mean, so the rounding of the fp32
+// mean (times rstd: 3e-5 at mean / std = 1000) does not reach y
 __global__ __launch_bounds__(TPB) void colnorm_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                            const float* __restrict__ mean_lo,
                                                             const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ y, int64_t B,
                                                             int64_t T, int C) {
@@ -96,7 +116,7 @@ __global__ __launch_bounds__(TPB) void colnorm_apply_kernel(const float* __restr
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (int64_t)gridDim.x * TPB) {
         const int c = (int)(i % C);
         const int64_t b = i / (T * C);
-        y[i] = (x[i] - mean[b * C + c]) * rstd[b * C + c] * gamma[c] + beta[c];
+        y[i] = ((x[i] - mean[b * C + c]) - mean_lo[b * C + c]) * rstd[b * C + c] * gamma[c] + beta[c];
     }
 }
 
@@ -345,11 +365,12 @@ extern "C" int dyn_colnorm_fwd_len(const float* x, const float* gamma, const flo
     const int chunks = chunks_for(T, &per);
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
+    float* mean_lo = partial + (int64_t)B * chunks * 2 * C;  // [B, C], in the [B, 2, C] tail of the workspace the backward keeps its sums in
     hipLaunchKernelGGL(colstats_partial_kernel, dim3((unsigned)dyn::cdiv(C, TPB), (unsigned)chunks, (unsigned)B), dim3(TPB), 0, st, x, partial,
                        T, (int)C, per, chunks, valid_rows);
-    hipLaunchKernelGGL(colstats_final_kernel, dim3((unsigned)dyn::cdiv(C, TPB), (unsigned)B), dim3(TPB), 0, st, partial, mean, rstd, T, (int)C,
-                       chunks, eps, valid_rows);
-    hipLaunchKernelGGL(colnorm_apply_kernel, dim3(grid_for(B * T * C)), dim3(TPB), 0, st, x, mean, rstd, gamma, beta, y, B, T, (int)C);
+    hipLaunchKernelGGL(colstats_final_kernel, dim3((unsigned)dyn::cdiv(C, TPB), (unsigned)B), dim3(TPB), 0, st, x, partial, mean, mean_lo, rstd,
+                       T, (int)C, per, chunks, eps, valid_rows);
+    hipLaunchKernelGGL(colnorm_apply_kernel, dim3(grid_for(B * T * C)), dim3(TPB), 0, st, x, mean, mean_lo, rstd, gamma, beta, y, B, T, (int)C);
     return dyn::check_launch("dyn_colnorm_fwd");
 }
 extern "C" int dyn_colnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int64_t B,

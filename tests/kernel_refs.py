@@ -1,0 +1,391 @@
+"""Float64 restatements of the operations behind the C-ABI kernels that only whole-model tests used to reach, each written from the
+operation's definition (no call into the torch op it mirrors).  tests/test_kernel_refs_cpu.py checks every one of them against torch's own
+op and autograd in float64 to 1e-12, so a wrong reference cannot hide a wrong kernel; tests/test_kernel_parity_f64_gpu.py compares the HIP
+kernels with them.  Also here: the inputs both files share, the tolerance rule, and a CPU replay of the summation order the column norm
+used before its statistics were made stable (E[x^2] - mean^2 from fp32 running sums)."""
+import math
+
+import numpy as np
+import torch
+
+F64 = torch.float64
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def d(t):
+    return t.detach().cpu().to(F64)
+
+
+def max_err(got, want, rel=False):
+    """max |got - want| (divided by |want| elementwise when `rel`) in float64."""
+    got, want = d(got), d(want)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    if got.numel() == 0:
+        return 0.0
+    e = (got - want).abs()
+    if rel:
+        e = e / want.abs()
+    return e.max().item()
+
+
+def measured_tol(torch_fp32, ref64, floor, rel=False):
+    """The rule for results the project had no tolerance for: torch's own fp32 CPU result of the same op on the same inputs is measured
+    against float64, and the kernel is allowed 4 x that (another, equally valid fp32 summation order) plus the absolute floor the
+    project already uses for that kind of result.  Returns (tolerance, torch's fp32 error)."""
+    e32 = max_err(torch_fp32, ref64, rel)
+    return 4.0 * e32 + floor, e32
+
+
+def wgrad_tol(base, rows, base_rows):
+    """Weight-gradient tolerance: `base` is what tests/test_ops_gpu.py asserts at `base_rows` summed rows (5e-4 for the norm gradients at
+    531 rows, 3e-4 for the depthwise-conv taps at 400); the rounding error of an fp32 sum of `rows` O(1) terms grows like sqrt(rows),
+    so longer sums scale by sqrt(rows / base_rows) (test_fused_first_two_subsampling_stages scales the same way), shorter ones keep `base`."""
+    return base * max(1.0, math.sqrt(rows / base_rows))
+
+
+def wgrad_tol_ill_conditioned(base, rows):
+    """base * max(1, sqrt(rows)), the scaling of test_fused_first_two_subsampling_stages taken literally, for the one weight gradient whose
+    terms are not O(1) quantities known to fp32 precision: the column norm's dgamma on offset inputs.  Its backward receives the mean as an
+    fp32 INPUT, up to ulp(mean) / 2 from the float64 mean; xhat = (x - mean) * rstd carries that as a shift common to a whole column, and
+    dgamma = sum dy * xhat collects it times |sum_t dy| ~ sqrt(T) (3e-5 * sqrt(300) = 5e-4 at mean / std = 1000, T = 300) — the property
+    of a format, whatever the kernel does, and one wgrad_tol's sqrt(rows / base_rows) of rounding noise does not cover."""
+    return base * max(1.0, math.sqrt(rows))
+
+
+# ----------------------------------------------------------------------------------------------------------- column norm (GroupNorm, groups == C)
+COLNORM_SHAPES = [(2, 1, 3), (3, 63, 5), (2, 64, 257), (2, 65, 64), (1, 300, 512), (1, 16500, 8), (1, 480000, 1)]
+COLNORM_RATIOS = (30.0, 100.0, 1000.0)
+
+
+def colnorm_eps(shape):
+    return 1e-7 if shape[2] == 1 else 1e-5      # C == 1 is the waveform normaliser (eps 1e-7)
+
+
+def colnorm_ratios(shape):
+    """mean / std of every (b, c) column of the offset input: the three ratios cycle over the columns (rotated per batch entry), so every
+    shape with three columns or more carries 30, 100 and 1000 at once; the one-column waveform shape carries 100."""
+    B, T, C = shape
+    if C == 1:
+        return torch.full((B, 1), 100.0)
+    idx = (torch.arange(C)[None, :] + torch.arange(B)[:, None]) % 3
+    return torch.tensor(COLNORM_RATIOS)[idx]
+
+
+def colnorm_inputs(shape, offset, seed=0):
+    """x [B, T, C] fp32 (std `s` per column, plus ratio * s per column when `offset`), gamma, beta, dy — all fp32, seeded."""
+    B, T, C = shape
+    g = gen(1000 + seed + T + C)
+    s = 0.01 if C == 1 else 1.0                 # waveform amplitude for the one-column shape
+    x = torch.randn(B, T, C, generator=g) * s
+    if offset:
+        sign = torch.where(torch.arange(C) % 2 == 0, 1.0, -1.0)
+        x = x + (colnorm_ratios(shape) * s * sign[None, :])[:, None, :]
+    gamma = torch.randn(C, generator=g) * 0.5 + 1.0
+    beta = torch.randn(C, generator=g)
+    dy = torch.randn(B, T, C, generator=g)
+    return x.float().contiguous(), gamma.float(), beta.float(), dy.float()
+
+
+def colnorm_ref(x, gamma, beta, eps):
+    """x [B, T, C]: per (b, c) mean and BIASED variance over T, two passes in float64.  Returns y, mean [B, C], rstd [B, C]."""
+    x, gamma, beta = d(x), d(gamma), d(beta)
+    mean = x.sum(1) / x.shape[1]
+    var = ((x - mean[:, None]) ** 2).sum(1) / x.shape[1]
+    rstd = 1.0 / torch.sqrt(var + eps)
+    y = (x - mean[:, None]) * rstd[:, None] * gamma + beta
+    return y, mean, rstd
+
+
+def colnorm_bwd_ref(x, gamma, dy, eps):
+    """dx = rstd * gamma * (dy - mean_t(dy) - xhat * mean_t(dy * xhat)), dgamma = sum_{b,t} dy * xhat, dbeta = sum_{b,t} dy."""
+    x, gamma, dy = d(x), d(gamma), d(dy)
+    T = x.shape[1]
+    mean = x.sum(1, keepdim=True) / T
+    var = ((x - mean) ** 2).sum(1, keepdim=True) / T
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xh = (x - mean) * rstd
+    s1 = dy.sum(1, keepdim=True) / T
+    s2 = (dy * xh).sum(1, keepdim=True) / T
+    dx = rstd * gamma * (dy - s1 - xh * s2)
+    return dx, (dy * xh).sum((0, 1)), dy.sum((0, 1))
+
+
+def colnorm_chunks(T):
+    """chunks_for of csrc/wav2vec2.hip: at most 256 chunks of at least 64 rows.  Returns (chunks, rows per chunk)."""
+    ch = min(max(-(-T // 64), 1), 256)
+    per = -(-T // ch)
+    return -(-T // per), per
+
+
+def colnorm_unshifted_replay(x, eps):
+    """The summation order the column norm had BEFORE its statistics were made stable, replayed on the CPU: per chunk fp32 running sums of
+    x and x^2 in row order, the chunk sums added in double in chunk order, var = E[x^2] - mean^2 (biased, clamped at 0), mean and rstd
+    rounded to fp32.  (The device contracts q += v * v into an fma, numpy does not: a difference of half an ulp per step, far below the
+    cancellation this function exists to show.)  Returns xhat = (x - mean) * rstd in fp32 arithmetic, mean and rstd [B, C] fp32."""
+    xn = x.detach().cpu().numpy().astype(np.float32)
+    B, T, C = xn.shape
+    chunks, per = colnorm_chunks(T)
+    pad = np.zeros((B, chunks * per, C), np.float32)
+    pad[:, :T] = xn
+    pad = pad.reshape(B, chunks, per, C)
+    s = np.zeros((B, chunks, C), np.float32)
+    q = np.zeros((B, chunks, C), np.float32)
+    for t in range(per):                         # zero rows past T add nothing, as the rows the kernel does not visit
+        v = pad[:, :, t]
+        s = (s + v).astype(np.float32)
+        q = (q + (v * v).astype(np.float32)).astype(np.float32)
+    sd, qd = np.zeros((B, C)), np.zeros((B, C))
+    for ch in range(chunks):
+        sd += s[:, ch].astype(np.float64)
+        qd += q[:, ch].astype(np.float64)
+    m = sd / T
+    var = np.maximum(qd / T - m * m, 0.0)
+    mean = m.astype(np.float32)
+    rstd = (1.0 / np.sqrt(var + eps)).astype(np.float32)
+    xhat = ((xn - mean[:, None]) * rstd[:, None]).astype(np.float32)
+    return torch.from_numpy(xhat), torch.from_numpy(mean), torch.from_numpy(rstd)
+
+
+def colnorm_torch_fp32(x, gamma, beta, eps):
+    """torch's fp32 CPU GroupNorm (groups == channels) of the channels-last x: y [B, T, C], mean [B, C], rstd [B, C]."""
+    B, T, C = x.shape
+    y, mean, rstd = torch.native_group_norm(x.transpose(1, 2).contiguous(), gamma, beta, B, C, T, C, eps)
+    return y.transpose(1, 2).contiguous(), mean.view(B, C), rstd.view(B, C)
+
+
+# ----------------------------------------------------------------------------------------------------------- elementwise
+GELU_EDGES = [0.0, -0.0, 1e-30, -1e-30, 0.5, -0.5, 3.0, -3.0, 6.0, -6.0, 10.0, -10.0]
+
+
+def gelu_inputs(n, seed=0):
+    g = gen(2000 + seed + n % 977)
+    x = torch.randn(n, generator=g) * 3
+    k = min(n, len(GELU_EDGES))
+    x[:k] = torch.tensor(GELU_EDGES[:k])
+    return x.float(), torch.randn(n, generator=g).float()
+
+
+def gelu_ref(x):
+    x = d(x)
+    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def gelu_bwd_ref(x, dy):
+    x, dy = d(x), d(dy)
+    cdf = 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
+    pdf = torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+    return dy * (cdf + x * pdf)
+
+
+# ----------------------------------------------------------------------------------------------------------- weight norm (per tap)
+def weight_norm_ref(v, g):
+    """v [rows, kw, cg], g [kw]: w = g[j] * v / ||v[:, j, :]||_F."""
+    v, g = d(v), d(g)
+    n = torch.sqrt((v * v).sum((0, 2)))
+    return g[None, :, None] * v / n[None, :, None]
+
+
+def weight_norm_bwd_ref(v, g, dw):
+    """dv = g / ||v_j|| * (dw - v <dw, v>_j / ||v_j||^2), dg[j] = <dw, v>_j / ||v_j||."""
+    v, g, dw = d(v), d(g), d(dw)
+    nn = (v * v).sum((0, 2))
+    dot = (dw * v).sum((0, 2))
+    dv = (g / torch.sqrt(nn))[None, :, None] * (dw - v * (dot / nn)[None, :, None])
+    return dv, dot / torch.sqrt(nn)
+
+
+# ----------------------------------------------------------------------------------------------------------- strided conv1d, channels-last
+def conv1d_rows(x, kw, stride):
+    """x [B, T, Cin] -> the overlapping rows [B, Tout, kw * Cin] (tap-major, then input channel) the implicit GEMM reads."""
+    B, T, Cin = x.shape
+    Tout = (T - kw) // stride + 1
+    idx = torch.arange(Tout)[:, None] * stride + torch.arange(kw)[None, :]
+    return x[:, idx].reshape(B, Tout, kw * Cin)
+
+
+def conv1d_ref(x, w, kw, stride):
+    """Valid strided conv: y[b, t, co] = sum_{j, ci} x[b, t * stride + j, ci] * w[co, j * Cin + ci]."""
+    return conv1d_rows(d(x), kw, stride) @ d(w).T
+
+
+def conv1d_wgrad_ref(x, dy, kw, stride):
+    rows, dy = conv1d_rows(d(x), kw, stride), d(dy)
+    return torch.einsum("bto,btk->ok", dy, rows)
+
+
+def conv1d_dgrad_ref(dy, w, T, Cin, kw, stride):
+    """dx[b, r, ci] = sum over (t, j) with t * stride + j == r of (dy[b, t] @ w)[j * Cin + ci]; rows no window covers stay 0."""
+    dy, w = d(dy), d(w)
+    B, Tout, _ = dy.shape
+    dA = (dy @ w).view(B, Tout, kw, Cin)
+    dx = torch.zeros(B, T, Cin, dtype=F64)
+    for j in range(kw):
+        dx[:, j:j + (Tout - 1) * stride + 1:stride] += dA[:, :, j]
+    return dx
+
+
+def torch_conv_weight(w, kw):
+    """[Cout, kw * Cin] (tap-major) -> torch's [Cout, Cin, kw]."""
+    return w.view(w.shape[0], kw, -1).permute(0, 2, 1).contiguous()
+
+
+# ----------------------------------------------------------------------------------------------------------- grouped positional conv layout
+def group_pack_ref(x, G, pad):
+    """[B, T, C] -> [B, G, T + 2 pad, C / G], zero padded in time."""
+    B, T, C = x.shape
+    xg = torch.zeros(B, G, T + 2 * pad, C // G, dtype=x.dtype)
+    xg[:, :, pad:pad + T] = x.view(B, T, G, C // G).permute(0, 2, 1, 3)
+    return xg
+
+
+def group_unpack_ref(yg, bias, T, C):
+    """[B, G, Tg, cg] -> [B, T, C] from the first T rows of every group (+ bias)."""
+    B = yg.shape[0]
+    y = yg[:, :, :T].permute(0, 2, 1, 3).reshape(B, T, C)
+    return y if bias is None else y + bias
+
+
+def group_pack_grad_ref(dy, G, Tg):
+    B, T, C = dy.shape
+    dyg = torch.zeros(B, G, Tg, C // G, dtype=dy.dtype)
+    dyg[:, :, :T] = dy.view(B, T, G, C // G).permute(0, 2, 1, 3)
+    return dyg
+
+
+def group_unpack_grad_ref(dxg, dx, pad, beta):
+    B, T, C = dx.shape
+    v = dxg[:, :, pad:pad + T].permute(0, 2, 1, 3).reshape(B, T, C)
+    return v + beta * dx if beta != 0.0 else v
+
+
+def grouped_conv_ref(x, wg, bias, G, kw):
+    """pack -> valid conv per group -> unpack of the first T frames: the `same`-padded grouped conv with an EVEN kernel whose last output
+    frame is dropped.  x [B, T, C], wg [G, C/G (out), kw * C/G] tap-major."""
+    x, wg = d(x), d(wg)
+    B, T, C = x.shape
+    xg = group_pack_ref(x, G, kw // 2)
+    yg = torch.stack([conv1d_ref(xg[:, g], wg[g], kw, 1) for g in range(G)], 1)      # [B, G, T + 1, cg]
+    return group_unpack_ref(yg, None if bias is None else d(bias), T, C)
+
+
+def torch_grouped_weight(wg, kw):
+    """[G, cg_out, kw * cg_in] -> torch's grouped layout [C, cg_in, kw]."""
+    G, co, _ = wg.shape
+    return wg.view(G * co, kw, -1).permute(0, 2, 1).contiguous()
+
+
+# ----------------------------------------------------------------------------------------------------------- row norms, channel affine
+def layernorm_ref(x, gamma, beta, eps):
+    x, gamma, beta = d(x), d(gamma), d(beta)
+    C = x.shape[-1]
+    mean = x.sum(-1, keepdim=True) / C
+    rstd = 1.0 / torch.sqrt(((x - mean) ** 2).sum(-1, keepdim=True) / C + eps)
+    return (x - mean) * rstd * gamma + beta, mean.squeeze(-1), rstd.squeeze(-1)
+
+
+def layernorm_bwd_ref(x, gamma, dy, eps):
+    x, gamma, dy = d(x), d(gamma), d(dy)
+    C = x.shape[-1]
+    mean = x.sum(-1, keepdim=True) / C
+    rstd = 1.0 / torch.sqrt(((x - mean) ** 2).sum(-1, keepdim=True) / C + eps)
+    xh = (x - mean) * rstd
+    gy = dy * gamma
+    dx = rstd * (gy - gy.sum(-1, keepdim=True) / C - xh * (gy * xh).sum(-1, keepdim=True) / C)
+    return dx, (dy * xh).sum(0), dy.sum(0)
+
+
+def rmsnorm_ref(x, gamma, eps):
+    x, gamma = d(x), d(gamma)
+    rstd = 1.0 / torch.sqrt((x * x).sum(-1, keepdim=True) / x.shape[-1] + eps)
+    return x * rstd * gamma, rstd.squeeze(-1)
+
+
+def rmsnorm_bwd_ref(x, gamma, dy, eps):
+    x, gamma, dy = d(x), d(gamma), d(dy)
+    C = x.shape[-1]
+    rstd = 1.0 / torch.sqrt((x * x).sum(-1, keepdim=True) / C + eps)
+    gy = dy * gamma
+    dx = rstd * gy - x * rstd ** 3 * (gy * x).sum(-1, keepdim=True) / C
+    return dx, (dy * x * rstd).sum(0)
+
+
+def chanaffine_ref(x, mean, var, weight, bias, eps):
+    x, mean, var, weight = d(x), d(mean), d(var), d(weight)
+    y = (x - mean) / torch.sqrt(var + eps) * weight
+    return y if bias is None else y + d(bias)
+
+
+def chanaffine_bwd_ref(x, mean, var, weight, dy, eps):
+    """dx = dy * weight / sqrt(var + eps), dweight = sum_r dy * xhat, dbias = sum_r dy."""
+    x, mean, var, weight, dy = d(x), d(mean), d(var), d(weight), d(dy)
+    rs = 1.0 / torch.sqrt(var + eps)
+    return dy * rs * weight, (dy * (x - mean) * rs).sum(0), dy.sum(0)
+
+
+# ----------------------------------------------------------------------------------------------------------- softmax, entropy
+def masked_softmax_ref(x, valid):
+    """Row softmax over the first `valid` columns; the columns past them are exactly 0."""
+    x = d(x)
+    e = torch.exp(x[:, :valid] - x[:, :valid].max(-1, keepdim=True).values)
+    y = torch.zeros_like(x)
+    y[:, :valid] = e / e.sum(-1, keepdim=True)
+    return y
+
+
+def entropy_grad_ref(logp, scale):
+    """H_r = -sum_c p log p with p = exp(logp), logp normalised rows; the gradient of scale * sum_r H_r w.r.t. the LOGITS behind them
+    (the simplex projection included): -p (logp + H_r) * scale.  Returns (grad, H)."""
+    y = d(logp)
+    p = torch.exp(y)
+    H = -(p * y).sum(-1)
+    return -p * (y + H[:, None]) * scale, H
+
+
+# ----------------------------------------------------------------------------------------------------------- encoder-decoder pieces
+def embedding_ref(ids, table, pos, pos_period):
+    """out[s] = table[ids[s]] (+ pos[s % pos_period])."""
+    out = d(table)[ids.long()]
+    if pos is not None:
+        out = out + d(pos)[torch.arange(ids.numel()) % pos_period]
+    return out
+
+
+def embedding_bwd_ref(ids, dy, old, beta):
+    """dtable[v] = beta * old[v] + sum_{s: ids[s] == v} dy[s]."""
+    out = beta * d(old) if beta != 0.0 else torch.zeros_like(d(old))
+    for s in range(ids.numel()):
+        out[int(ids[s])] += d(dy)[s]
+    return out
+
+
+def causal_mask_ref(scores):
+    """[nb, S, S]: entries with column > row become -inf, the rest keep their bits."""
+    S = scores.shape[-1]
+    out = scores.clone()
+    out[:, torch.arange(S)[None, :] > torch.arange(S)[:, None]] = -math.inf
+    return out
+
+
+def nll_ref(logp, targets, ignore_index, scale, weights=None):
+    """row_loss[r] = -w_r logp[r, t_r], loss = sum, grad = w_r * scale * (exp(logp[r]) - onehot(t_r)) w.r.t. the logits; a row whose target
+    is `ignore_index` or outside [0, C) contributes 0 loss and a zero gradient row."""
+    y = d(logp)
+    rows, C = y.shape
+    w = torch.ones(rows, dtype=F64) if weights is None else d(weights)
+    row_loss = torch.zeros(rows, dtype=F64)
+    grad = torch.zeros_like(y)
+    for r in range(rows):
+        t = int(targets[r])
+        if t == ignore_index or t < 0 or t >= C:
+            continue
+        row_loss[r] = -w[r] * y[r, t]
+        grad[r] = w[r] * scale * torch.exp(y[r])
+        grad[r, t] -= w[r] * scale
+    return row_loss.sum(), row_loss, grad
+
+
+def stitch_finalize_rows_ref(acc, count, row_index):
+    return torch.log(d(acc)[row_index.cpu()] / d(count)[row_index.cpu()][:, None])

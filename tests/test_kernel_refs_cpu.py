@@ -1,0 +1,241 @@
+"""tests/kernel_refs.py against torch's own ops and autograd in float64, to 1e-12 relative: the float64 restatements the GPU parity tests
+compare the HIP kernels with must themselves be right.  Also pins that the column-norm parity test discriminates: the summation order
+the kernel had before its statistics were made stable misses that test's bound on the offset inputs, torch's fp32 result meets it."""
+import os
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import kernel_refs as K  # noqa: E402
+
+F64 = torch.float64
+
+
+def _same(got, want, what, torch_form=0.0):
+    """1e-12 relative to the result's magnitude.  `torch_form`: the float64 rounding of the form TORCH evaluates, where that is larger."""
+    scale = max(1.0, want.abs().max().item()) if want.numel() else 1.0
+    err = (got - want).abs().max().item() if want.numel() else 0.0
+    assert got.shape == want.shape and err <= 1e-12 * scale + torch_form, f"{what}: {err} (scale {scale}, torch's form {torch_form})"
+
+
+def _r(*shape, seed=0):
+    return torch.randn(*shape, generator=K.gen(seed), dtype=F64)
+
+
+@pytest.mark.parametrize("shape", K.COLNORM_SHAPES[:5])
+@pytest.mark.parametrize("offset", [False, True])
+def test_colnorm_ref_is_group_norm(shape, offset):
+    x, gamma, beta, dy = (t.double() for t in K.colnorm_inputs(shape, offset))
+    B, T, C = shape
+    eps = K.colnorm_eps(shape)
+    xr, gr, br = (t.clone().requires_grad_() for t in (x, gamma, beta))
+    want = F.group_norm(xr.transpose(1, 2), C, gr, br, eps).transpose(1, 2)
+    want.backward(dy)
+    y, mean, rstd = K.colnorm_ref(x, gamma, beta, eps)
+    # torch evaluates y = x * scale + (beta - mean * scale) with scale = rstd * gamma: two products of size |x| rstd |gamma| that cancel, each
+    # rounded to eps64 / 2 of itself.  At T = 1 with the offset (|x| = 1000, rstd = 1 / sqrt(eps) = 316) torch's float64 y is 2.3e-11 from
+    # beta, which the restatement returns exactly; everywhere else this term is below the 1e-12.
+    form = 2.0 ** -52 * (x.abs().amax(1) * rstd * gamma.abs()).max().item()
+    _same(y, want.detach(), "y", form)
+    _, m_t, r_t = torch.native_group_norm(x.transpose(1, 2).contiguous(), gamma, beta, B, C, T, C, eps)
+    _same(mean, m_t.view(B, C), "mean")
+    _same(rstd, r_t.view(B, C), "rstd")
+    dx, dgamma, dbeta = K.colnorm_bwd_ref(x, gamma, dy, eps)
+    _same(dx, xr.grad, "dx"); _same(dgamma, gr.grad, "dgamma"); _same(dbeta, br.grad, "dbeta")
+
+
+def test_gelu_ref_is_gelu():
+    x, dy = (t.double() for t in K.gelu_inputs(257))
+    xr = x.clone().requires_grad_()
+    F.gelu(xr).backward(dy)
+    _same(K.gelu_ref(x), F.gelu(x), "gelu")
+    _same(K.gelu_bwd_ref(x, dy), xr.grad, "gelu_bwd")
+
+
+@pytest.mark.parametrize("rows,kw,cg", [(5, 3, 4), (17, 3, 4), (9, 300, 1)])
+def test_weight_norm_ref_is_weight_norm(rows, kw, cg):
+    v, g, dw = _r(rows, kw, cg, seed=1), _r(kw, seed=2) + 2.0, _r(rows, kw, cg, seed=3)
+    vr, gr = v.clone().requires_grad_(), g.clone().requires_grad_()
+    lin = torch.nn.Module()
+    lin.weight = torch.nn.Parameter(v.clone())
+    torch.nn.utils.parametrizations.weight_norm(lin, "weight", dim=1)
+    with torch.no_grad():
+        lin.parametrizations.weight.original0.copy_(g.view(1, kw, 1))
+        lin.parametrizations.weight.original1.copy_(v)
+    _same(K.weight_norm_ref(v, g), lin.weight.detach(), "w vs the parametrization")
+    want = gr[None, :, None] * vr / vr.pow(2).sum((0, 2), keepdim=True).sqrt()
+    want.backward(dw)
+    _same(K.weight_norm_ref(v, g), want.detach(), "w")
+    dv, dg = K.weight_norm_bwd_ref(v, g, dw)
+    _same(dv, vr.grad, "dv"); _same(dg, gr.grad, "dg")
+
+
+@pytest.mark.parametrize("B,T,Cin,Cout,kw,stride", [(2, 400, 1, 32, 10, 5), (2, 37, 32, 48, 3, 2), (1, 38, 32, 48, 2, 2),
+                                                    (1, 10, 1, 32, 10, 5), (2, 403, 1, 32, 10, 5)])
+def test_conv1d_refs_are_conv1d(B, T, Cin, Cout, kw, stride):
+    x, w = _r(B, T, Cin, seed=4), _r(Cout, kw * Cin, seed=5)
+    xr, wr = x.clone().requires_grad_(), w.clone().requires_grad_()
+    want = F.conv1d(xr.transpose(1, 2), K.torch_conv_weight(wr, kw), stride=stride).transpose(1, 2)
+    dy = _r(*want.shape, seed=6)
+    want.backward(dy)
+    _same(K.conv1d_ref(x, w, kw, stride), want.detach(), "conv1d")
+    _same(K.conv1d_wgrad_ref(x, dy, kw, stride), wr.grad, "wgrad")
+    dx = K.conv1d_dgrad_ref(dy, w, T, Cin, kw, stride)
+    _same(dx, xr.grad, "dgrad")
+    covered = (T - kw) // stride * stride + kw
+    assert torch.equal(dx[:, covered:], torch.zeros(B, T - covered, Cin, dtype=F64))
+
+
+@pytest.mark.parametrize("B,T,C,G,pad", [(2, 5, 32, 4, 8), (1, 50, 32, 4, 8), (2, 7, 48, 16, 64)])
+def test_grouped_conv_ref_is_grouped_conv1d_without_its_last_frame(B, T, C, G, pad):
+    kw, cg = 2 * pad, C // G
+    x, wg, bias = _r(B, T, C, seed=7), _r(G, cg, kw * cg, seed=8), _r(C, seed=9)
+    want = F.conv1d(x.transpose(1, 2), K.torch_grouped_weight(wg, kw), bias, padding=kw // 2, groups=G)[..., :-1].transpose(1, 2)
+    _same(K.grouped_conv_ref(x, wg, bias, G, kw), want, "grouped conv")
+    # the four layout maps are each other's adjoints: <pack(x), u> == <x, unpack_grad(u)> and <unpack(v), z> == <v, pack_grad(z)>
+    u = _r(B, G, T + 2 * pad, cg, seed=10)
+    lhs = (K.group_pack_ref(x, G, pad) * u).sum()
+    rhs = (x * K.group_unpack_grad_ref(u, torch.zeros_like(x), pad, 0.0)).sum()
+    assert abs(lhs - rhs) <= 1e-12 * abs(lhs)
+    v, z = _r(B, G, T + 3, cg, seed=11), _r(B, T, C, seed=12)
+    lhs = (K.group_unpack_ref(v, None, T, C) * z).sum()
+    rhs = (v * K.group_pack_grad_ref(z, G, T + 3)).sum()
+    assert abs(lhs - rhs) <= 1e-12 * abs(lhs)
+    old = _r(B, T, C, seed=13)
+    _same(K.group_unpack_grad_ref(u, old, pad, 1.0), K.group_unpack_grad_ref(u, old, pad, 0.0) + old, "unpack_grad beta")
+
+
+def test_row_norm_refs_are_layer_norm():
+    rows, C, eps = 7, 300, 1e-5
+    x, g, b, dy = _r(rows, C, seed=14) * 2 + 100.0, _r(C, seed=15), _r(C, seed=16), _r(rows, C, seed=17)
+    xr, gr, br = (t.clone().requires_grad_() for t in (x, g, b))
+    want = F.layer_norm(xr, (C,), gr, br, eps)
+    want.backward(dy)
+    y, mean, rstd = K.layernorm_ref(x, g, b, eps)
+    _same(y, want.detach(), "ln y")
+    _same(mean, x.mean(-1), "ln mean"); _same(rstd, 1.0 / torch.sqrt(x.var(-1, unbiased=False) + eps), "ln rstd")
+    dx, dg, db = K.layernorm_bwd_ref(x, g, dy, eps)
+    _same(dx, xr.grad, "ln dx"); _same(dg, gr.grad, "ln dgamma"); _same(db, br.grad, "ln dbeta")
+    xr, gr = x.clone().requires_grad_(), g.clone().requires_grad_()
+    want = F.rms_norm(xr, (C,), gr, eps) if hasattr(F, "rms_norm") else xr * torch.rsqrt(xr.pow(2).mean(-1, keepdim=True) + eps) * gr
+    want.backward(dy)
+    y, rstd = K.rmsnorm_ref(x, g, eps)
+    _same(y, want.detach(), "rms y")
+    dx, dg = K.rmsnorm_bwd_ref(x, g, dy, eps)
+    _same(dx, xr.grad, "rms dx"); _same(dg, gr.grad, "rms dgamma")
+
+
+def test_chanaffine_ref_is_eval_batch_norm():
+    rows, C, eps = 11, 300, 1e-5
+    x, w, b, dy = _r(rows, C, seed=18), _r(C, seed=19), _r(C, seed=20), _r(rows, C, seed=21)
+    mean, var = _r(C, seed=22), torch.rand(C, generator=K.gen(23), dtype=F64)
+    var[::7] = 1e-9
+    xr, wr, br = (t.clone().requires_grad_() for t in (x, w, b))
+    want = F.batch_norm(xr, mean, var, wr, br, training=False, eps=eps)
+    want.backward(dy)
+    _same(K.chanaffine_ref(x, mean, var, w, b, eps), want.detach(), "chanaffine")
+    _same(K.chanaffine_ref(x, mean, var, w, None, eps), want.detach() - b, "chanaffine without bias")
+    dx, dw, db = K.chanaffine_bwd_ref(x, mean, var, w, dy, eps)
+    _same(dx, xr.grad, "dx"); _same(dw, wr.grad, "dweight"); _same(db, br.grad, "dbias")
+
+
+@pytest.mark.parametrize("L,valid", [(64, 1), (300, 299), (300, 300)])
+def test_masked_softmax_ref_is_softmax_with_minus_inf_keys(L, valid):
+    x = _r(5, L, seed=24) * 4
+    masked = x.clone()
+    masked[:, valid:] = -float("inf")
+    y = K.masked_softmax_ref(x, valid)
+    _same(y, F.softmax(masked, -1), "masked softmax")
+    assert torch.equal(y[:, valid:], torch.zeros(5, L - valid, dtype=F64))
+
+
+@pytest.mark.parametrize("L", [1, 129])
+def test_entropy_grad_ref_is_autograd_through_log_softmax(L):
+    rows = 6
+    z = (_r(rows, L, seed=25) * 3).requires_grad_()
+    logp = F.log_softmax(z, -1)
+    ent = -(logp.exp() * logp).sum(-1)
+    ent.mean().backward()
+    grad, H = K.entropy_grad_ref(logp.detach(), 1.0 / rows)
+    _same(H, ent.detach(), "entropy")
+    _same(grad, z.grad, "entropy grad")
+
+
+def test_embedding_refs_are_embedding():
+    vocab, dm, S, period = 11, 6, 9, 4
+    ids = torch.tensor([3, 3, 0, 10, 7, 3, 0, 1, 10])
+    table, pos, dy, old = _r(vocab, dm, seed=26), _r(period, dm, seed=27), _r(S, dm, seed=28), _r(vocab, dm, seed=29)
+    tr = table.clone().requires_grad_()
+    want = F.embedding(ids, tr)
+    want.backward(dy)
+    _same(K.embedding_ref(ids, table, None, 1), want.detach(), "embedding")
+    _same(K.embedding_ref(ids, table, pos, period), want.detach() + pos.repeat(3, 1)[:S], "embedding + pos")
+    _same(K.embedding_bwd_ref(ids, dy, old, 0.0), tr.grad, "embedding_bwd")
+    _same(K.embedding_bwd_ref(ids, dy, old, 1.0), tr.grad + old, "embedding_bwd beta 1")
+    unused = [v for v in range(vocab) if v not in ids.tolist()]
+    assert torch.equal(K.embedding_bwd_ref(ids, dy, old, 1.0)[unused], old[unused])
+
+
+def test_nll_ref_is_nll_loss_through_log_softmax():
+    rows, C, ignore = 9, 5, -100
+    z = (_r(rows, C, seed=30) * 2).requires_grad_()
+    tgt = torch.tensor([0, 4, ignore, 2, 2, ignore, 1, 3, 0])
+    logp = F.log_softmax(z, -1)
+    F.nll_loss(logp, tgt, ignore_index=ignore, reduction="sum").mul(0.25).backward()
+    loss, row_loss, grad = K.nll_ref(logp.detach(), tgt, ignore, 0.25)
+    _same(loss, F.nll_loss(logp.detach(), tgt, ignore_index=ignore, reduction="sum"), "loss")
+    _same(row_loss, F.nll_loss(logp.detach(), tgt, ignore_index=ignore, reduction="none"), "row loss")
+    _same(grad, z.grad, "grad w.r.t. the logits")
+    # weighted rows (zero and negative weights included), an out-of-range target contributing nothing
+    w = torch.tensor([0.5, 0.0, 1.0, -2.0, 1.5, 0.25, 1.0, 1.0, 3.0], dtype=F64)
+    tgt2 = torch.tensor([0, 4, 1, 2, 2, 7, 1, 3, 0])
+    live = tgt2 < C
+    z2 = z.detach().clone().requires_grad_()
+    lp2 = F.log_softmax(z2, -1)
+    want = (w[live] * F.nll_loss(lp2[live], tgt2[live], reduction="none")).sum()
+    want.backward()
+    loss, row_loss, grad = K.nll_ref(lp2.detach(), tgt2, None, 1.0, weights=w)
+    _same(loss, want.detach(), "weighted loss")
+    _same(grad, z2.grad, "weighted grad")
+    assert row_loss[5] == 0 and torch.equal(grad[5], torch.zeros(C, dtype=F64)) and torch.equal(grad[1], torch.zeros(C, dtype=F64))
+
+
+def test_small_refs():
+    s = _r(3, 7, 7, seed=31)
+    want = s.masked_fill(torch.triu(torch.ones(7, 7, dtype=torch.bool), 1), -float("inf"))
+    assert torch.equal(K.causal_mask_ref(s), want)
+    acc, cnt = torch.rand(10, 4, generator=K.gen(32), dtype=F64) + 0.1, torch.arange(1, 11, dtype=F64)
+    idx = torch.tensor([9, 0, 4])
+    _same(K.stitch_finalize_rows_ref(acc, cnt, idx), (acc / cnt[:, None]).log()[idx], "stitch rows")
+    assert K.colnorm_chunks(300) == (5, 60) and K.colnorm_chunks(16500) == (254, 65) and K.colnorm_chunks(480000) == (256, 1875)
+    assert K.colnorm_chunks(1) == (1, 1) and K.colnorm_chunks(65) == (2, 33)
+
+
+@pytest.mark.parametrize("shape", K.COLNORM_SHAPES[1:])
+def test_unshifted_column_statistics_miss_the_parity_bound_on_offset_inputs(shape):
+    """The bound of test_kernel_parity_f64_gpu.py::test_colnorm (4 x torch's fp32 error + 5e-6, on y with gamma = 1, beta = 0 and on rstd
+    relative) on that test's offset inputs: E[x^2] - mean^2 from fp32 running sums exceeds it, torch's fp32 GroupNorm stays inside —
+    and on the zero-mean inputs both stay inside, so the offset is what the test catches."""
+    eps = K.colnorm_eps(shape)
+    C = shape[2]
+    ones, zeros = torch.ones(C), torch.zeros(C)
+    for offset in (True, False):
+        x = K.colnorm_inputs(shape, offset)[0]
+        y64, _, rstd64 = K.colnorm_ref(x, ones, zeros, eps)
+        y32, _, rstd32 = K.colnorm_torch_fp32(x, ones, zeros, eps)
+        tol_y, e_y = K.measured_tol(y32, y64, 5e-6)
+        tol_r, e_r = K.measured_tol(rstd32, rstd64, 5e-6, rel=True)
+        xhat, _, rstd = K.colnorm_unshifted_replay(x, eps)
+        got_y, got_r = K.max_err(xhat, y64), K.max_err(rstd, rstd64, rel=True)
+        print(f"{shape} offset={offset}: replay y {got_y:.2e} rstd {got_r:.2e} | torch fp32 y {e_y:.2e} rstd {e_r:.2e} | bound y {tol_y:.2e} rstd {tol_r:.2e}")
+        assert e_y <= tol_y and e_r <= tol_r
+        if offset:
+            assert got_y > tol_y and got_r > tol_r, (shape, got_y, tol_y, got_r, tol_r)
+        else:
+            assert got_y <= tol_y and got_r <= tol_r, (shape, got_y, tol_y, got_r, tol_r)
