@@ -29,7 +29,9 @@ rollouts are scored teacher-forced one at a time (causal, padded at the end only
 dyn_nll_loss_weighted with the per-rollout weight of `rl_row_weights`, and its gradient is ACCUMULATED into the flat gradient buffer
 (decoder gradients summed over rollouts, one encoder backward with the summed cross-attention gradient) — there is no autograd graph,
 the update functions return the loss as a float.  Rollouts come back in row order (the reference appends them in finishing order;
-every consumer pairs hypotheses and rewards by index).  With decoder dropout on, every rollout's scoring pass draws its own masks."""
+every consumer pairs hypotheses and rewards by index).  With decoder dropout on, every rollout's scoring pass draws its own masks.
+The 'wer_cer' reward's word and character edit counts of a window come from one dyn_edit_counts call on the model's device (the
+integers of the host dynamic programme, so the rewards are the same floats); `rl_reward_on_host=True` scores on the host."""
 import ctypes
 import math
 import os
@@ -47,7 +49,7 @@ from .enc_dec_teacher_filters import should_skip_faulty_teacher_prediction
 from .lib import get_lr_args_from_args, get_specaugment_config_from_args, prepare_chunks
 from .model import SCConformerXL
 from .optim import MADGRAD
-from .wer import word_error_rate_detail
+from .wer import _pair_ids, edit_counts, edit_counts_ids, rates_from_counts
 
 try:
     from tqdm import tqdm
@@ -572,28 +574,38 @@ WER_CER_NOTE = ("rl_reward='wer_cer': reward = ((1 - WER) + (1 - CER)) / 2 - the
                 "dropped: sacrebleu is not available; pass a callable (ref, hyps) -> [float] as rl_reward for another reward")
 
 
-def calc_rewards(ref, hyps):
+def calc_rewards(ref, hyps, device=None):
     """reference lcasr/lib.py:1330-1359 WITHOUT THE BLEU TERM (`rl_reward='wer_cer'`): per hypothesis ((1 - WER) + (1 - CER)) / 2
     where the reference averages 1 - WER, 1 - CER and sacrebleu.corpus_bleu / 100 (sacrebleu is not vendored).  The two empty-string
-    branches (:1341-1346) are kept as written: both empty -> 1.0, empty reference and a non-empty hypothesis -> -(number of words)."""
-    rewards = []
-    for hyp in hyps:
+    branches (:1341-1346) are kept as written: both empty -> 1.0, empty reference and a non-empty hypothesis -> -(number of words).
+    With a GPU `device` the word and character counts of all remaining hypotheses come from ONE dyn_edit_counts call; the counts are
+    the host path's integers and the reward is formed by the same expression, so the floats are identical."""
+    rewards = [None] * len(hyps)
+    scored = []
+    for k, hyp in enumerate(hyps):
         if len(hyp.strip()) == 0 and len(ref.strip()) == 0:
-            rewards.append(1.0)
-            continue
+            rewards[k] = 1.0
         elif len(ref.strip()) == 0 and len(hyp.strip()) > 0:
-            rewards.append(len(hyp.strip().split()) * -1.0)
-            continue
-        wer = word_error_rate_detail([hyp], [ref])[0] * -1.0 + 1
-        cer = word_error_rate_detail([hyp], [ref], use_cer=True)[0] * -1.0 + 1
-        rewards.append((wer + cer) / 2.0)
+            rewards[k] = len(hyp.strip().split()) * -1.0
+        else:
+            scored.append(k)
+    if device is None:
+        counts = [(edit_counts([hyps[k]], [ref]), edit_counts([hyps[k]], [ref], use_cer=True)) for k in scored]
+    else:
+        ids = [_pair_ids(hyps[k], ref, use_cer) for k in scored for use_cer in (False, True)]
+        rows = edit_counts_ids([h for h, _ in ids], [r for _, r in ids], device)
+        counts = [(tuple(int(x) for x in rows[2 * q]), tuple(int(x) for x in rows[2 * q + 1])) for q in range(len(scored))]
+    for k, (words, chars) in zip(scored, counts):
+        wer = rates_from_counts(*words)[0] * -1.0 + 1
+        cer = rates_from_counts(*chars)[0] * -1.0 + 1
+        rewards[k] = (wer + cer) / 2.0
     print(sum(rewards) / len(rewards), "avg reward")
     return rewards
 
 
-def _reward_fn(rl_reward):
+def _reward_fn(rl_reward, device=None):
     if rl_reward == 'wer_cer':
-        return calc_rewards
+        return calc_rewards if device is None else (lambda ref, hyps: calc_rewards(ref, hyps, device=device))
     if callable(rl_reward):
         return lambda ref, hyps: [float(r) for r in rl_reward(ref, hyps)]
     raise ValueError(f"rl_reward {rl_reward!r}: 'wer_cer' or a callable (ref: str, hyps: list[str]) -> list[float]")
@@ -732,7 +744,10 @@ def enc_dec_dynamic_eval(args, model, spec, seq_len, overlap, tokenizer, use_tqd
         raise NotImplementedError(f"training_mode {mode!r}: only 'teacher_ce' is implemented (the RL modes grpo / maxrl are out of scope)")
     reward_fn = None
     if mode != 'teacher_ce':
-        reward_fn = _reward_fn(rl_reward)
+        # 'wer_cer' is scored on the model's device (dyn_edit_counts); `rl_reward_on_host=True` keeps the host dynamic programme
+        reward_fn = _reward_fn(rl_reward)                 # an unknown name is refused here, before the model is touched
+        if rl_reward == 'wer_cer' and not args.__dict__.get('rl_reward_on_host', False):
+            reward_fn = _reward_fn(rl_reward, model.device)
         print(WER_CER_NOTE if rl_reward == 'wer_cer' else f'rl_reward: {getattr(rl_reward, "__name__", rl_reward)!r} (caller-supplied reward)')
     dropout_emb = args.__dict__.get('dropout_emb', 0.0)
     dropout_post_ff = args.__dict__.get('dropout_post_ff', 0.0)

@@ -25,8 +25,20 @@ def restore_params(model, snap):
         set_params(model, snap)
 
 
-def score_texts(preds, golds, reduce_over_ranks=False):
-    counts = edit_counts(preds, golds)
+_score_device = None
+
+
+def set_score_device(device):
+    """Device on which `score_texts` counts edits when its caller names none (None: the host dynamic programme).  A harness sets
+    it once to its model's device, so its `score_texts(preds, golds, reduce_over_ranks)` call sites stay as the reference's."""
+    global _score_device
+    _score_device = device
+
+
+def score_texts(preds, golds, reduce_over_ranks=False, device=None):
+    """Corpus WER record.  The counts are integers and equal on the host (`device=None` and no `set_score_device`) and on the GPU
+    (dyn_edit_counts, one call for the whole corpus), so every rate, log line and pickle is the same either way."""
+    counts = edit_counts(preds, golds, device=device if device is not None else _score_device)
     if reduce_over_ranks:
         counts = ddist.all_reduce_counts(counts)       # RCCL: 4 int64 counters
     wer, words, ins_rate, del_rate, sub_rate = rates_from_counts(*counts)

@@ -15,7 +15,7 @@ from . import dist as ddist
 from . import lib
 from .decoding import GreedyCTCDecoder
 from .datasets import datasets_functions
-from .harness_common import clone_params, restore_params, score_texts, set_params, transcribe
+from .harness_common import clone_params, restore_params, score_texts, set_params, set_score_device, transcribe
 from .run_dynamic_eval_full import load_model_and_tokenizer
 
 
@@ -23,6 +23,7 @@ def main(args):
     assert args.split in ['test', 'dev'], f'Split must be either test or dev (got {args.split})'
     rank, local_rank, world = ddist.init()
     device = torch.device('cuda', ddist.local_device_index(local_rank))
+    set_score_device(device)      # corpus WER on the GPU that holds the model (same integers as the host path)
     torch.cuda.set_device(device)
     model, tokenizer = load_model_and_tokenizer(args, device)
     decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=model.decoder.num_classes - 1, device=device)

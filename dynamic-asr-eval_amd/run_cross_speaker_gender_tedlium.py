@@ -20,7 +20,7 @@ from . import dist as ddist
 from . import lib
 from .datasets import datasets_functions
 from .decoding import GreedyCTCDecoder
-from .harness_common import clone_params, restore_params, score_texts, set_params, transcribe
+from .harness_common import clone_params, restore_params, score_texts, set_params, set_score_device, transcribe
 from .run_dynamic_eval_full import load_model_and_tokenizer
 
 DEFAULT_SPEAKER_MANIFEST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "speaker_manifest_15x15.json")
@@ -47,6 +47,7 @@ def main(args):
     assert args.split in ['test', 'dev', 'train'], f'Split must be either test, dev, or train (got {args.split})'
     rank, local_rank, world = ddist.init()
     device = torch.device('cuda', ddist.local_device_index(local_rank))
+    set_score_device(device)      # corpus WER on the GPU that holds the model (same integers as the host path)
     torch.cuda.set_device(device)
     speaker_manifest, speaker_gender = load_speaker_manifest(args.speaker_manifest)
     if rank == 0:

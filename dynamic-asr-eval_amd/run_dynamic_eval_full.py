@@ -134,7 +134,7 @@ def main(args):
             etime = time.time()
             out = normalize(out_text).lower()
             records.append({'index': rec, 'id': data[rec]['id'], 'hyp': out, 'gold': gold_text, 'elapsed': etime - stime})
-        counts = edit_counts([r['hyp'] for r in records], [r['gold'] for r in records])
+        counts = edit_counts([r['hyp'] for r in records], [r['gold'] for r in records], device=device)
         counts = ddist.all_reduce_counts(counts)           # RCCL over xGMI: 4 int64 counters
         records = ddist.gather_records(records)            # hypotheses for the pickle (small strings)
         wer, words, ins_rate, del_rate, sub_rate = rates_from_counts(*counts)

@@ -64,7 +64,7 @@ def main(args):
                 print('\n-------\n' + rest[j]['id'] + '\n-------\n')
                 print(gold_text, '\n', out, '\n\n')
             records.append({'index': j, 'id': rest[j]['id'], 'hyp': out, 'gold': gold_text})
-        counts = ddist.all_reduce_counts(edit_counts([r['hyp'] for r in records], [r['gold'] for r in records]))
+        counts = ddist.all_reduce_counts(edit_counts([r['hyp'] for r in records], [r['gold'] for r in records], device=device))
         records = ddist.gather_records(records)
         wer, words, ins_rate, del_rate, sub_rate = rates_from_counts(*counts)
         if rank == 0:

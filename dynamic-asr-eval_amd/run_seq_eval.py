@@ -116,7 +116,7 @@ def main(args):
             if rank == 0 and not args.not_verbose:
                 print(gold_text, '\n', out, '\n\n')
             records.append({'index': rec, 'id': data[rec]['id'], 'hyp': out, 'gold': gold_text})
-        counts = ddist.all_reduce_counts(edit_counts([r['hyp'] for r in records], [r['gold'] for r in records]))
+        counts = ddist.all_reduce_counts(edit_counts([r['hyp'] for r in records], [r['gold'] for r in records], device=device))
         records = ddist.gather_records(records)
         wer, words, ins_rate, del_rate, sub_rate = rates_from_counts(*counts)
         if rank == 0:

@@ -121,8 +121,8 @@ def main(args):
             print(f'GOLD:     {gold_text}')
             print(f'LOO PRED: {pred}')
             records.append({'index': rec_idx, 'id': rec['id'], 'hyp': pred, 'baseline': baseline_pred, 'gold': gold_text, 'meta': info})
-        loo_counts = ddist.all_reduce_counts(edit_counts([r['hyp'] for r in records], [r['gold'] for r in records]))
-        base_counts = ddist.all_reduce_counts(edit_counts([r['baseline'] for r in records], [r['gold'] for r in records]))
+        loo_counts = ddist.all_reduce_counts(edit_counts([r['hyp'] for r in records], [r['gold'] for r in records], device=device))
+        base_counts = ddist.all_reduce_counts(edit_counts([r['baseline'] for r in records], [r['gold'] for r in records], device=device))
         records = ddist.gather_records(records)
         def scores(counts):
             wer, words, ins, dele, sub = rates_from_counts(*counts)

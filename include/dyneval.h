@@ -581,6 +581,26 @@ int dyn_softdtw_bwd(const float* D, const double* R, float* E, int64_t B, int64_
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Edit-distance counts of a ragged batch of P token-id pairs — replaces the host dynamic programme behind every WER / CER
+ * (`word_error_rate_detail` at reference lcasr/lib.py:1348-1349 inside calc_rewards and run_dynamic_eval_full.py:112-115).
+ *   counts [P, 4] int32 = (insertions, deletions, substitutions, reference length) of the alignment the cell rule
+ *   "diagonal if diag <= up, else up; left only when strictly smaller" picks (substitution / match, then deletion, then
+ *   insertion); an empty reference gives (m, 0, 0), an empty hypothesis (0, n, 0).
+ *   hyp / ref: device int32 ids, pair p at [hyp_off[p], hyp_off[p + 1]) / [ref_off[p], ref_off[p + 1]).
+ *   hyp_off / ref_off: HOST arrays of P + 1 offsets (the entry plans its launches from them); dev_off: their DEVICE copy,
+ *   hyp_off [P + 1] followed by ref_off [P + 1].
+ * Pairs with both sides <= dyn_edit_counts_resident_limit() are scored by one workgroup each with the lattice's live
+ * diagonals in LDS; longer pairs are cut into tile x tile blocks whose boundary rows / columns live in the workspace, one
+ * launch per block anti-diagonal.  tile = 0 is the default (1024); an explicit tile in [8, 2048] also sends every pair with
+ * a side >= tile through the tiled regime (tests, tuning).  dyn_edit_counts_workspace_bytes returns bytes or a negative
+ * DYN_E_* code.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t dyn_edit_counts_resident_limit(void);
+int64_t dyn_edit_counts_workspace_bytes(const int64_t* hyp_off, const int64_t* ref_off, int64_t P, int64_t tile);
+int dyn_edit_counts(const int32_t* hyp, const int32_t* ref, const int64_t* hyp_off, const int64_t* ref_off, const int64_t* dev_off,
+                    int32_t* counts, void* workspace, int64_t workspace_bytes, int64_t P, int64_t tile, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * CTC + transformer-LM beam search (reference lcasr/ctc_beam_search.py:89-319 with max_cache_length = 128, lcasr/lib.py:37-72).
  *   dyn_beam_search   the whole search over log_probs [frames, ld] (n_classes = vocab + 1, blank = n_classes - 1), enqueued on
  *                     `stream` without a host synchronisation: per frame one bookkeeping kernel (candidates, CTC prefix rules, exact
