@@ -144,7 +144,6 @@ class EncDecSCConformerXL(SCConformerXL):
         # the attributes the reference's loop sets on `model.language_model_decoder` (lib.py:1519-1522,1636-1637,1703-1707)
         self.language_model_decoder = _DecoderKnobs(self.dec["dec_layers"])
         self.pos_enc = _NoParams()
-        self.use_graphs = False
         self._dctx = None
         # generate(): the lean one-token kernels of dyn_decoder_steps (default) or, with DYN_FUSED_DECODE=0, the tile kernels at M = 1
         hd = self.dec["dec_d_model"] // self.dec["dec_heads"]

@@ -558,7 +558,7 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
                     model.grad_samples = num_negatives * n if _CLEAN_COPY_FUSED_ATTN else None
                     with torch.enable_grad():
                         post = model(audio_signal=audio_chunk)['final_posteriors']     # [2 n, N, C]
-                    ctx = (model._ctx, model._ctx_static, model._ctx_key)
+                    ctx = model.saved_forward()
                     labels.fetch(*ops.ctc_greedy(post[n:].detach(), blank), lo, hi)  # pseudo-labels of the clean copies
                     posts.append((post, ctx))
                 step.before_yield(labels.record())
@@ -575,7 +575,7 @@ def _dynamic_eval_group_gen(args, model, specs, seq_len, overlap, tokenizer, use
                     # class's samples leaves every sample its own gradient
                     _, _, g_aug = ops.ctc_loss(post[:n].contiguous(), targets, ilen, tlen, blank, reduction="sum", grad_scale=1.0 / (N * num_negatives))
                     model.set_range(lo, hi)
-                    model._ctx, model._ctx_static, model._ctx_key = ctx
+                    model.use_saved_forward(ctx)
                     model.backward(g_aug, n_active=n)
                     if online:
                         for q in range(lo, hi):

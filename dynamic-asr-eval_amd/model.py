@@ -19,8 +19,8 @@ from types import SimpleNamespace
 
 import torch
 
-from . import ops
-from .optim import ParamList
+from . import _graphs, ops
+from ._flat import FlatModel
 
 DEFAULT_CONFIG = dict(
     feat_in=80, n_layers=6, d_model=768, n_heads=6, head_dim=128, ff_mult=4, subsampling_factor=8,
@@ -100,46 +100,6 @@ def _parse_fused_attn_grad(value):
     return mode
 
 
-class _no_gc:
-    """No cyclic garbage collection while a hipGraph is being captured: a collection that happens to run inside the capture can
-    finalise objects of an EARLIER model (its CUDAGraphs, their private memory pool), and freeing device memory / destroying a graph
-    from the capturing thread aborts the process ("Fatal Python error: Aborted ... Garbage-collecting" in the middle of a capture).
-    torch.cuda.graph collects once on entry; after that the collector stays off until the capture has ended."""
-
-    def __enter__(self):
-        import gc
-        self._was = gc.isenabled()
-        gc.disable()
-
-    def __exit__(self, *exc):
-        import gc
-        if self._was:
-            gc.enable()
-        return False
-
-
-class _capture_guard:
-    """Entered INSIDE `torch.cuda.graph(...)` (whose own entry empties the allocator's cache): VERDICT r03 weak 9 — the collector is not the only
-    way memory can go back to the driver on the capturing thread (an object dropped by refcount mid-capture would do it too).  The caching
-    allocator counts the segments it has freed: none may have been while the launch sequence was being captured."""
-
-    @staticmethod
-    def _segments_freed():
-        try:
-            return int(torch.cuda.memory_stats().get("segment.all.freed", 0))
-        except Exception:
-            return 0
-
-    def __enter__(self):
-        self._freed = self._segments_freed()
-
-    def __exit__(self, *exc):
-        if exc[0] is None and self._segments_freed() != self._freed:
-            raise ops.DynError("device memory was released to the driver inside a hipGraph capture (an object holding device memory was dropped "
-                               "mid-capture): the captured graph may reference freed memory")
-        return False
-
-
 class _Group:
     """A named slice of the parameter list (`model.subsampling`, `model.layers[i]`, `model.decoder`): what the
     reference's freeze helpers iterate (reference lcasr/lib.py:163-204)."""
@@ -152,7 +112,9 @@ class _Group:
         return [p for n, p in self._model.named_parameters() if n.startswith(self._prefix)]
 
 
-class SCConformerXL:
+class SCConformerXL(FlatModel):
+    _input = "audio_signal"
+
     def __init__(self, config=None, vocab_size=128, device="cuda:0", extra_spec=None, group=1):
         """`extra_spec`: [(name, shape)] of further parameters placed in the SAME flat buffers (the enc-dec model appends its
         decoder there, so snapshot / restore / optimiser step stay single operations).
@@ -163,53 +125,31 @@ class SCConformerXL:
         module, depthwise convolutions, fused subsampling) run once per sample.  Per replica the arithmetic is that of a single model
         (tests/test_model_gpu.py::test_lockstep_group_matches_separate_models)."""
         self.config = make_config(**(config or {}))
-        self.R = int(group)
-        if self.R < 1:
+        if int(group) < 1:
             raise ValueError("group must be >= 1")
-        self._lo, self._n = 0, self.R   # replicas [lo, lo + n) take part in the current batches (see `active` / set_range)
+        self._lo, self._n = 0, int(group)   # replicas [lo, lo + n) take part in the current batches (see `active` / set_range)
         cfg = self.config
         if cfg["conv_norm"] not in ("rms_norm", "layer_norm", "batch_renorm"):
             raise ValueError(f"unknown conv_norm {cfg['conv_norm']}")
         if cfg["d_model"] % 256:
             raise ValueError("d_model must be a multiple of 256 (wave-per-row norm kernels)")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ops.DynError("SCConformerXL runs only on the HIP path (device must be cuda)")
         self.num_classes = vocab_size + 1
-        self.spec = param_spec(cfg, self.num_classes) + list(extra_spec or [])
-        off, self._slots = 0, {}
-        for name, shape in self.spec:
-            n = math.prod(shape)
-            self._slots[name] = (off, n, shape)
-            off += (n + 63) // 64 * 64
-        self.n_flat = off
-        R = self.R
-        self.flat_params = torch.zeros(R * off, device=self.device, dtype=torch.float32)
-        self.flat_grads = torch.zeros(R * off, device=self.device, dtype=torch.float32)
-        self.P, self.G = {}, {}          # replica 0's views (the whole model when R == 1)
-        self.PR, self.GR = {}, {}        # [R, *shape] views over the group
-        fp, fg = self.flat_params.view(R, off), self.flat_grads.view(R, off)
-        for name, (o, n, shape) in self._slots.items():
-            self.P[name] = self.flat_params[o:o + n].view(shape)
-            self.G[name] = self.flat_grads[o:o + n].view(shape)
-            self.PR[name] = fp[:, o:o + n].view(R, *shape)
-            self.GR[name] = fg[:, o:o + n].view(R, *shape)
+        super().__init__(param_spec(cfg, self.num_classes) + list(extra_spec or []), device, replicas=group)
         self.buffers = {}
         if cfg["conv_norm"] == "batch_renorm":
             for l in range(cfg["n_layers"]):
                 self.buffers[f"layers.{l}.conv.cnorm.running_mean"] = torch.zeros(cfg["d_model"], device=self.device)
                 self.buffers[f"layers.{l}.conv.cnorm.running_var"] = torch.ones(cfg["d_model"], device=self.device)
-        self.frozen = set()  # parameter-name prefixes excluded from adaptation
         self.subsampling = _Group(self, "subsampling.")
         self.layers = [_Group(self, f"layers.{l}.") for l in range(cfg["n_layers"])]
         self.decoder = _Group(self, "decoder.", num_classes=self.num_classes)
         self._rot = {}
         self.fused_attention = True   # no-grad passes use dyn_attention_fwd when the launch fills the chip (see _attn_fwd)
-        self._ws = None             # this model's scratch buffer (ops.use_workspace): never shared with another chain
         self._ctx = None
         self._skip_wgrad = False
         self.use_graphs = False     # hipGraph replay of the forward / backward launch sequences (see forward())
-        self._graphs = {"fwd": {}, "bwd": {}, "seen": {}, "pool": {}}
+        self._graphs = {"fwd": {}, "bwd": {}, "pool": {}}
+        self._seen = _graphs.Seen()
         self._ctx_static = False
         self._ctx_key = None
         self.fused_convmod = True   # GLU + dwconv + norm + SiLU in one kernel (csrc/convmod.hip)
@@ -217,19 +157,13 @@ class SCConformerXL:
         # first two subsampling stages fused (csrc/conv.hip sub12_*): z1 = conv2d_first(x), the largest activation of the model, is
         # recomputed from x in forward and backward instead of making four trips through HBM (DYN_FUSED_SUB=0: the separate kernels)
         self.fused_subsampling = os.environ.get("DYN_FUSED_SUB", "1") != "0" and cfg["subsampling_conv_channels"] % 4 == 0
-        # A/B switches (measurements only): DYN_FUSED_SILU=0 / DYN_GROUPED_WGRAD=0 restore the separate kernels / launches
-        self.fused_silu = os.environ.get("DYN_FUSED_SILU", "0") != "0"        # SiLU / SiLU' in the epilogue of the producing GEMM: OFF
-        # the backward's launch-bound weight-gradient / bias-sum reductions as one launch at its end (DYN_DEFER_REDUCE=0: one launch each)
-        self.defer_reduces = os.environ.get("DYN_DEFER_REDUCE", "1") != "0"
-        # the shared CTC head / re-projection weight gradients (one product per block) through the grouped launch (DYN_STACK_SHARED_WGRAD=0: one launch per use)
-        self.stack_shared_wgrads = os.environ.get("DYN_STACK_SHARED_WGRAD", "1") != "0"
-        self._shared = {}
-        self._defer_arena = None
+        # A/B switch (measurements only): SiLU / SiLU' in the epilogue of the producing GEMM: OFF
         # by default (A/B on one box, 3 chains: 739 vs 738 audio-s/s, while the GEMM's own rate drops 110 -> 101 TFLOP/s: the
         # activation runs with the MFMA pipe idle, whereas the separate HBM-bound kernels hide under the other chains' GEMMs)
-        self.grouped_wgrad = os.environ.get("DYN_GROUPED_WGRAD", "1") != "0"  # block weight gradients deferred to ONE grouped launch
-                                                                              # at the end of the backward (+ bias column sums)
-        self._wq = None
+        self.fused_silu = os.environ.get("DYN_FUSED_SILU", "0") != "0"
+        # the shared CTC head / re-projection weight gradients (one product per block) through the grouped launch (DYN_STACK_SHARED_WGRAD=0: one launch per use)
+        self.stack_shared_wgrads = os.environ.get("DYN_STACK_SHARED_WGRAD", "1") != "0"
+        self._shared = {}           # (weight name, replica) -> slabs of a weight used once per block (see _shared_slab)
         # Number of LEADING samples of a grad-mode batch whose activations the backward will need (None = all).  The dynamic-eval loss
         # uses only the augmented copies (reference lcasr/lib.py:570-575; backward(n_active=...) below), so the clean copy's attention
         # can take the fused no-grad kernel: its probabilities are never read again.  Set by lib.dynamic_eval around its loop.
@@ -237,7 +171,6 @@ class SCConformerXL:
         # grad-mode attention without the [B, H, T', T'] score matrix (forward keeps one log-sum-exp per row, the backward re-forms P
         # tile by tile: 7 products instead of 4): "0" never, "1" always, otherwise from T' >= this many frames
         self.fused_attention_grad = _parse_fused_attn_grad(os.environ.get("DYN_FUSED_ATTN_GRAD", "4096"))
-        self.training = False
 
     # ------------------------------------------------------------------ lockstep group helpers
     @property
@@ -271,19 +204,8 @@ class SCConformerXL:
         return self.flat_params.view(self.R, self.n_flat)[r]
 
     # ------------------------------------------------------------------ nn.Module-like surface
-    def named_parameters(self):
-        return [(n, self.P[n]) for n, _ in self.spec]
-
-    def parameters(self):
-        pl = ParamList(self.P[n] for n, _ in self.spec)
-        lo, hi = self._lo * self.n_flat, (self._lo + self._n) * self.n_flat      # a lockstep group steps its active replicas' buffers in one launch
-        pl.flat_params, pl.flat_grads = self.flat_params[lo:hi], self.flat_grads[lo:hi]
-        pl.offsets = [self._slots[n][0] for n, _ in self.spec]
-        pl.trainable = [self.trainable(n) for n, _ in self.spec]
-        return pl
-
-    def grads(self):
-        return [self.G[n] for n, _ in self.spec]
+    def _flat_range(self):
+        return self._lo * self.n_flat, (self._lo + self._n) * self.n_flat      # a lockstep group steps its active replicas' buffers in one launch
 
     def state_dict(self):
         sd = {n: p.detach().clone() for n, p in self.named_parameters()}
@@ -305,27 +227,8 @@ class SCConformerXL:
                 self.buffers[n].copy_(sd[n].to(self.device, torch.float32))
         return SimpleNamespace(missing_keys=missing, unexpected_keys=unexpected)
 
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def to(self, device):
-        if torch.device(device) != self.device and torch.device(device).type != "cuda":
-            raise ops.DynError("SCConformerXL cannot leave the GPU: there is no CPU path")
-        return self
-
     def print_total_params(self):
         print(f"Total params: {sum(math.prod(s) for _, s in self.spec) / 1e6:.2f}M")
-
-    def zero_grad(self):
-        self.flat_grads.zero_()
-
-    def trainable(self, name):
-        return not any(name.startswith(f) for f in self.frozen)
 
     # ------------------------------------------------------------------ helpers
     def _rotary(self, T):
@@ -351,20 +254,8 @@ class SCConformerXL:
             bg = False
         elif wg and self._wq is not None and self.stack_shared_wgrads and wname in ("decoder.ff.weight", "decoder.reproj.weight") \
                 and alpha == 1.0 and ops.wgrad_groupable(dy, x, self.G[wname]):
-            # a weight used once per block (CTC head / re-projection of the self-conditioning): every use writes its OWN slab in the grouped
-            # launch (outputs of one launch must not alias), the slabs are summed into the gradient after it — instead of one small launch
-            # with a read-modify-write of the whole gradient per use
-            sh = self._shared.get(wname)
-            if sh is None:
-                cap = self.config["n_layers"] + 1
-                sh = {"w": torch.empty(cap, *self.G[wname].shape, device=self.device, dtype=torch.float32),
-                      "b": torch.empty(cap, self.G[bname].numel(), device=self.device, dtype=torch.float32) if bg else None, "bname": bname, "k": 0}
-                self._shared[wname] = sh
-            k = sh["k"]
-            sh["k"] = k + 1
-            self._wq.append(ops.wgrad_desc(dy, x, sh["w"][k], alpha=1.0, beta=0.0, colsum=sh["b"][k] if sh["b"] is not None else None, colsum_beta=0.0))
-            if sh["b"] is not None:
-                bg = False
+            self._wq.append(self._shared_slab(dy, x, wname, 0, self.G[wname], self.G[bname] if bg else None))
+            bg = False
         elif wg:
             ops.linear_wgrad(dy, x, self.G[wname], alpha=alpha, beta=1.0)
         if bg:
@@ -375,6 +266,27 @@ class SCConformerXL:
             return ops.linear_dgrad(dy, self.P[wname], alpha=alpha, epilogue=ops.EPI_SILU_GRAD, aux=silu_of)
         dx = ops.linear_dgrad(dy, self.P[wname], alpha=alpha)
         return ops.silu_bwd(silu_of, dx, out=dx) if silu_of is not None else dx
+
+    def _shared_slab(self, dy, x, wname, r, gw, gb):
+        """Descriptor of dy^T x (+ column sums of dy with a bias gradient `gb`) for a weight used once per block (CTC head / re-projection of the
+        self-conditioning): every use of (weight, replica r) writes its OWN slab in the grouped launch (outputs of one launch must not alias), and
+        `_flush_shared` sums the slabs into the gradient views `gw` / `gb` after it, in use order — instead of one small launch with a
+        read-modify-write of the whole gradient per use."""
+        sh = self._shared.get((wname, r))
+        if sh is None:
+            cap = self.config["n_layers"] + 1
+            sh = self._shared[(wname, r)] = {"w": torch.empty(cap, *gw.shape, device=self.device, dtype=torch.float32), "gw": gw, "gb": gb, "k": 0,
+                                             "b": torch.empty(cap, gb.numel(), device=self.device, dtype=torch.float32) if gb is not None else None}
+        k = sh["k"]
+        sh["k"] = k + 1
+        return ops.wgrad_desc(dy, x, sh["w"][k], alpha=1.0, beta=0.0, colsum=sh["b"][k] if sh["b"] is not None else None, colsum_beta=0.0)
+
+    def _flush_shared(self):
+        for sh in self._shared.values():
+            ops.reduce_partials(sh["w"][:sh["k"]], sh["gw"], beta=1.0)
+            if sh["b"] is not None:
+                ops.reduce_partials(sh["b"][:sh["k"]], sh["gb"], beta=1.0)
+        self._shared = {}
 
     def _lin_bwd_group(self, dy, x, wname, bname, wg, bg, need_dx, alpha, silu_of):
         """_lin_bwd over a lockstep group (the backward batch holds ONE chunk: sample r = replica r): every replica's weight gradient is its
@@ -390,18 +302,8 @@ class SCConformerXL:
         block_local = wname.startswith("layers.") or wname == "subsampling.out.weight"      # the deep-K subsampling products stay immediate (split-K)
         if wg and self._wq is not None and (block_local or shared) and ops.wgrad_groupable(dy[0], x[0], GR[wname][0]):
             for r in range(R):
-                if shared:      # one slab per use and replica, summed in use order after the grouped launch (see _lin_bwd)
-                    sh = self._shared.get((wname, r))
-                    if sh is None:
-                        cap = self.config["n_layers"] + 1
-                        sh = {"w": torch.empty(cap, *GR[wname][r].shape, device=self.device, dtype=torch.float32),
-                              "b": torch.empty(cap, GR[bname][r].numel(), device=self.device, dtype=torch.float32) if bg else None, "bname": bname, "k": 0,
-                              "wname": wname, "r": lo + r}
-                        self._shared[(wname, r)] = sh
-                    k = sh["k"]
-                    sh["k"] = k + 1
-                    self._wq.append(ops.wgrad_desc(dy[r], x[r], sh["w"][k], alpha=1.0, beta=0.0, colsum=sh["b"][k] if sh["b"] is not None else None,
-                                                   colsum_beta=0.0))
+                if shared:
+                    self._wq.append(self._shared_slab(dy[r], x[r], wname, r, GR[wname][r], GR[bname][r] if bg else None))
                 else:
                     self._wq.append(ops.wgrad_desc(dy[r], x[r], GR[wname][r], alpha=alpha, beta=1.0, colsum=GR[bname][r] if bg else None, colsum_beta=1.0))
             bg = False
@@ -436,17 +338,6 @@ class SCConformerXL:
         return out
 
     # ------------------------------------------------------------------ forward
-    def __call__(self, audio_signal=None, **kw):
-        return self.forward(audio_signal)
-
-    def _scratch(self):
-        if self._ws is None:
-            self._ws = torch.empty(ops.WORKSPACE_BYTES * self.R, dtype=torch.uint8, device=self.device)
-            ops.counters(self._ws)          # zeroed arrival counters of this replica's GEMMs, allocated outside any graph capture
-            if self.defer_reduces:          # partial sums of the backward's deferred column reductions (ops.reduce_defer)
-                self._defer_arena = torch.empty(ops.DEFER_ARENA_BYTES * self.R, dtype=torch.uint8, device=self.device)
-        return self._ws
-
     def forward(self, audio_signal):
         with ops.use_workspace(self._scratch()):
             return self._forward(audio_signal)
@@ -481,21 +372,12 @@ class SCConformerXL:
                self.fused_subsampling, self.grad_samples, self._lo, self._n)
         ent = G["fwd"].get(key)
         if ent is None:
-            G["seen"][key] = G["seen"].get(key, 0) + 1
-            if G["seen"][key] < 2:
+            if not self._seen(key, 2):
                 self._ctx_static = False
                 return self._forward_eager(x)
-            self._graph_pool()
-            # capture_error_mode="thread_local": other threads of the process (the RCCL watchdog of a multi-rank run) may
-            # touch the HIP runtime while this thread captures; only this thread's calls are part of the capture
+            pool = self._graph_pool()
             static_in = x.clone()
-            graph = torch.cuda.CUDAGraph()
-            prof, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None      # no event records inside a capture
-            try:
-                with _no_gc(), torch.cuda.graph(graph, pool=self._graph_pool(), capture_error_mode="thread_local"), _capture_guard():
-                    out = self._forward_eager(static_in)
-            finally:
-                ops.GEMM_PROFILE = prof
+            graph, out = _graphs.capture(pool, lambda: self._forward_eager(static_in))
             ent = {"graph": graph, "in": static_in, "out": out, "ctx": self._ctx}
             G["fwd"][key] = ent
         ent["in"].copy_(x)
@@ -709,7 +591,6 @@ class SCConformerXL:
                 return self._backward(grad_posteriors, n_active, input_grad)
         finally:
             self._skip_wgrad = False
-            self._wq = None
             self._shared = {}
             self._grad_hidden = None
 
@@ -719,23 +600,26 @@ class SCConformerXL:
         ent = G["bwd"].get(key)
         if ent is None:
             static_g = grad_posteriors.contiguous().clone()
-            graph = torch.cuda.CUDAGraph()
-            prof, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None
-            try:
-                with _no_gc(), torch.cuda.graph(graph, pool=self._graph_pool(), capture_error_mode="thread_local"), _capture_guard():
-                    self._backward(static_g, n_active, False)
-            finally:
-                ops.GEMM_PROFILE = prof
+            graph, _ = _graphs.capture(self._graph_pool(), lambda: self._backward(static_g, n_active, False))
             ent = {"graph": graph, "g": static_g}
             G["bwd"][key] = ent
         ent["g"].copy_(grad_posteriors)
         ent["graph"].replay()
         return None
 
+    def saved_forward(self):
+        """Opaque handle of what the last forward saved for its backward.  A loop that runs several forwards before their backwards takes the
+        handle after each forward and hands it to `use_saved_forward` before the matching backward()."""
+        return self._ctx, self._ctx_static, self._ctx_key
+
+    def use_saved_forward(self, handle):
+        self._ctx, self._ctx_static, self._ctx_key = handle
+
     def _backward(self, grad_posteriors, n_active, input_grad):
-        self._scratch()
-        with ops.reduce_defer(self._defer_arena if self.defer_reduces else None):
-            dx = self._backward_body(grad_posteriors, n_active, input_grad)
+        with self._reduce_defer():
+            with self._wgrad_queue(self.grouped_wgrad and not self._skip_wgrad):    # every block weight gradient (+ bias sums) of this backward: one launch
+                dx = self._backward_body(grad_posteriors, n_active, input_grad)
+            self._flush_shared()
         for name, _ in self.spec:                   # after the deferred reductions have been queued: they write gradients too
             if not self.trainable(name):
                 self.GR[name].zero_()
@@ -768,7 +652,6 @@ class SCConformerXL:
             ctx["sub"] = cut(ctx["sub"])
             ctx["dims"] = (nb, T, T3, F3)
         h, mean, rstd, n, logp = ctx["head"]
-        self._wq = [] if (self.grouped_wgrad and not self._skip_wgrad) else None
         dz = ops.log_softmax_bwd(logp, grad_posteriors.contiguous())
         dn = self._lin_bwd(dz, n, "decoder.ff.weight", "decoder.ff.bias")
         dh = torch.empty_like(h)
@@ -798,16 +681,6 @@ class SCConformerXL:
             dh = self._ff_bwd(dh, p + "ff1", lc["ff1"])
             ctx["layers"][l] = None  # release this block's activations (queued weight gradients keep what they read)
         dx = self._sub_bwd(dh, ctx, input_grad)
-        if self._wq:
-            ops.gemm_grouped(self._wq)      # every block weight gradient (+ bias sums) of this backward: one launch
-            for key, sh in self._shared.items():      # the per-use slabs of the shared weights, summed in use order
-                k = sh["k"]
-                gw = self.G[key] if self.R == 1 else self.GR[sh["wname"]][sh["r"]]
-                ops.reduce_partials(sh["w"][:k], gw, beta=1.0)
-                if sh["b"] is not None:
-                    ops.reduce_partials(sh["b"][:k], self.G[sh["bname"]] if self.R == 1 else self.GR[sh["bname"]][sh["r"]], beta=1.0)
-        self._wq = None
-        self._shared = {}
         if not static:
             self._ctx = None
         return dx

@@ -9,16 +9,13 @@ first, feature projection LN + Linear(512 -> 768), grouped positional conv (k = 
 Parameter NAMES are HF's (state_dict interchange with transformers, which is the oracle in tests); the native HBM layout
 of conv kernels is [C_out][kernel][C_in] so each strided Conv1d is one implicit GEMM over overlapping rows of the
 channels-last activation (ops.conv1d), converted on load / save."""
-import math
-import os
 from collections import OrderedDict
 from types import SimpleNamespace
 
 import torch
 
-from . import ops
-from .model import _capture_guard, _no_gc
-from .optim import ParamList
+from . import _graphs, ops
+from ._flat import FlatModel
 
 DEFAULT_CONFIG = dict(
     conv_dim=(512,) * 7, conv_stride=(5, 2, 2, 2, 2, 2, 2), conv_kernel=(10, 3, 3, 3, 3, 2, 2), hidden_size=768,
@@ -51,55 +48,52 @@ def _conv_to_hf(w):       # native [Cout, k, Cin] -> HF [Cout, Cin, k]
 _RELEASED = object()      # Wav2Vec2ForCTC._ctx after a bucket replay whose saved activations are owned by its graphs only
 
 
-class Wav2Vec2ForCTC:
+def param_spec(c):
+    """[(name, shape, kind)] with HF's names; kind "conv": a conv kernel kept as [C_out][kernel][C_in], "g": the weight norm's magnitudes."""
+    H = c["hidden_size"]
+    spec = [("wav2vec2.masked_spec_embed", (H,), None)]
+    fe = "wav2vec2.feature_extractor.conv_layers."
+    cin = 1
+    for i, (co, k) in enumerate(zip(c["conv_dim"], c["conv_kernel"])):
+        spec.append((f"{fe}{i}.conv.weight", (co, k, cin), "conv"))
+        if i == 0:
+            spec += [(f"{fe}0.layer_norm.weight", (co,), None), (f"{fe}0.layer_norm.bias", (co,), None)]
+        cin = co
+    fp = "wav2vec2.feature_projection."
+    spec += [(fp + "layer_norm.weight", (cin,), None), (fp + "layer_norm.bias", (cin,), None),
+             (fp + "projection.weight", (H, cin), None), (fp + "projection.bias", (H,), None)]
+    pc = "wav2vec2.encoder.pos_conv_embed.conv."
+    K, G = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
+    spec += [(pc + "bias", (H,), None), (pc + "parametrizations.weight.original0", (K,), "g"),
+             (pc + "parametrizations.weight.original1", (H, K, H // G), "conv")]
+    spec += [("wav2vec2.encoder.layer_norm.weight", (H,), None), ("wav2vec2.encoder.layer_norm.bias", (H,), None)]
+    for l in range(c["num_hidden_layers"]):
+        p = f"wav2vec2.encoder.layers.{l}."
+        # q | k | v weights side by side in the flat buffers (then their biases): one [3H, H] projection instead of three launches
+        spec += [(p + f"attention.{n}.weight", (H, H), None) for n in ("q_proj", "k_proj", "v_proj")]
+        spec += [(p + f"attention.{n}.bias", (H,), None) for n in ("q_proj", "k_proj", "v_proj")]
+        spec += [(p + "attention.out_proj.weight", (H, H), None), (p + "attention.out_proj.bias", (H,), None)]
+        spec += [(p + "layer_norm.weight", (H,), None), (p + "layer_norm.bias", (H,), None),
+                 (p + "feed_forward.intermediate_dense.weight", (c["intermediate_size"], H), None),
+                 (p + "feed_forward.intermediate_dense.bias", (c["intermediate_size"],), None),
+                 (p + "feed_forward.output_dense.weight", (H, c["intermediate_size"]), None),
+                 (p + "feed_forward.output_dense.bias", (H,), None),
+                 (p + "final_layer_norm.weight", (H,), None), (p + "final_layer_norm.bias", (H,), None)]
+    spec += [("lm_head.weight", (c["vocab_size"], H), None), ("lm_head.bias", (c["vocab_size"],), None)]
+    return spec
+
+
+class Wav2Vec2ForCTC(FlatModel):
+    _input = "input_values"
+
     def __init__(self, config=None, device="cuda:0"):
         self.cfg = make_config(config)
         c = self.cfg
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ops.DynError("Wav2Vec2ForCTC runs only on the HIP path (device must be cuda)")
-        self._defer_arena = None
         H = c["hidden_size"]
         assert H % 256 == 0 and c["conv_dim"][-1] % 256 == 0, "LayerNorm kernels need C % 256 == 0"
-        spec, self._conv = [("wav2vec2.masked_spec_embed", (H,), None)], {}
-        fe = "wav2vec2.feature_extractor.conv_layers."
-        cin = 1
-        for i, (co, k) in enumerate(zip(c["conv_dim"], c["conv_kernel"])):
-            spec.append((f"{fe}{i}.conv.weight", (co, k, cin), "conv"))
-            if i == 0:
-                spec += [(f"{fe}0.layer_norm.weight", (co,), None), (f"{fe}0.layer_norm.bias", (co,), None)]
-            cin = co
-        fp = "wav2vec2.feature_projection."
-        spec += [(fp + "layer_norm.weight", (cin,), None), (fp + "layer_norm.bias", (cin,), None),
-                 (fp + "projection.weight", (H, cin), None), (fp + "projection.bias", (H,), None)]
-        pc = "wav2vec2.encoder.pos_conv_embed.conv."
-        K, G = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
-        spec += [(pc + "bias", (H,), None), (pc + "parametrizations.weight.original0", (K,), "g"),
-                 (pc + "parametrizations.weight.original1", (H, K, H // G), "conv")]
-        spec += [("wav2vec2.encoder.layer_norm.weight", (H,), None), ("wav2vec2.encoder.layer_norm.bias", (H,), None)]
-        for l in range(c["num_hidden_layers"]):
-            p = f"wav2vec2.encoder.layers.{l}."
-            # q | k | v weights side by side in the flat buffers (then their biases): one [3H, H] projection instead of three launches
-            spec += [(p + f"attention.{n}.weight", (H, H), None) for n in ("q_proj", "k_proj", "v_proj")]
-            spec += [(p + f"attention.{n}.bias", (H,), None) for n in ("q_proj", "k_proj", "v_proj")]
-            spec += [(p + "attention.out_proj.weight", (H, H), None), (p + "attention.out_proj.bias", (H,), None)]
-            spec += [(p + "layer_norm.weight", (H,), None), (p + "layer_norm.bias", (H,), None),
-                     (p + "feed_forward.intermediate_dense.weight", (c["intermediate_size"], H), None),
-                     (p + "feed_forward.intermediate_dense.bias", (c["intermediate_size"],), None),
-                     (p + "feed_forward.output_dense.weight", (H, c["intermediate_size"]), None),
-                     (p + "feed_forward.output_dense.bias", (H,), None),
-                     (p + "final_layer_norm.weight", (H,), None), (p + "final_layer_norm.bias", (H,), None)]
-        spec += [("lm_head.weight", (c["vocab_size"], H), None), ("lm_head.bias", (c["vocab_size"],), None)]
-        self.spec = spec
-        off, slots = 0, {}
-        for name, shape, _ in spec:
-            n = math.prod(shape)
-            slots[name] = (off, n, shape)
-            off += (n + 63) // 64 * 64
-        self.flat_params = torch.zeros(off, device=self.device, dtype=torch.float32)
-        self.flat_grads = torch.zeros(off, device=self.device, dtype=torch.float32)
-        self.P = {n: self.flat_params[o:o + k].view(s) for n, (o, k, s) in slots.items()}
-        self.G = {n: self.flat_grads[o:o + k].view(s) for n, (o, k, s) in slots.items()}
+        spec = param_spec(c)
+        super().__init__([(n, shape) for n, shape, _ in spec], device)
+        slots = self._slots
         self._kind = {n: kind for n, _, kind in spec}
         # packed views of the attention input projections: [3H, H] weights / [3H] biases (the slots are contiguous when H % 64 == 0)
         self.packed_qkv = H % 64 == 0
@@ -112,10 +106,6 @@ class Wav2Vec2ForCTC:
                 assert slots[f"wav2vec2.encoder.layers.{l}.attention.v_proj.bias"][0] == ob + 2 * H
                 self.Pqkv.append((self.flat_params[ow:ow + 3 * H * H].view(3 * H, H), self.flat_params[ob:ob + 3 * H]))
                 self.Gqkv.append((self.flat_grads[ow:ow + 3 * H * H].view(3 * H, H), self.flat_grads[ob:ob + 3 * H]))
-        self.frozen = set()
-        self._ctx = None
-        self._wq = None
-        self.grouped_wgrad = os.environ.get("DYN_GROUPED_WGRAD", "1") != "0"     # A/B switch: 0 = one launch per weight gradient
         self.config = SimpleNamespace(**c)
         # hipGraph replay over LENGTH BUCKETS (see forward()): off unless a loop turns it on (wav2vec2_lib: args.use_graphs)
         self.use_graphs = False
@@ -124,24 +114,16 @@ class Wav2Vec2ForCTC:
         self.graph_budget_bytes = 64 << 30       # device memory the buckets' graphs may hold (their shared pool + static buffers); beyond it all are dropped
         self._graphs = OrderedDict()             # bucket key -> {"graph", "in", "out", "ctx", "bwd": {...}, "bytes"}
         self._pool = None                        # ONE private memory pool for all buckets of this model (see _forward_bucketed)
-        self._seen = {}
-        self._valid = None                       # device int32 [n_conv]: valid frames after every conv layer of the utterance in flight
+        self._seen = _graphs.Seen()
+        # device int32 [n_conv]: valid frames after every conv layer of the utterance in flight
+        self._valid = torch.zeros(len(c["conv_kernel"]), dtype=torch.int32, device=self.device)
         self._vl = None                          # = self._valid while a bucketed launch sequence is being issued / captured, else None
-        self._ws = None
-        self._ctx_static, self._ctx_key = False, None
+        self._ctx, self._ctx_static, self._ctx_key = None, False, None
 
     # ------------------------------------------------------------------ nn.Module-like surface
-    def named_parameters(self):
-        return [(n, self.P[n]) for n, _, _ in self.spec]
-
-    def parameters(self):
-        pl = ParamList(self.P[n] for n, _, _ in self.spec)
-        pl.flat_params, pl.flat_grads = self.flat_params, self.flat_grads
-        return pl
-
     def grads_hf(self):
         """{name: gradient in HF layout} (tests)."""
-        return {n: self._to_hf(n, self.G[n]) for n, _, _ in self.spec}
+        return {n: self._to_hf(n, self.G[n]) for n, _ in self.spec}
 
     def _to_hf(self, name, t):
         kind = self._kind[name]
@@ -155,37 +137,22 @@ class Wav2Vec2ForCTC:
         return {n: self._to_hf(n, p).detach().clone() for n, p in self.named_parameters()}
 
     def load_state_dict(self, sd, strict=True):
-        missing = [n for n, _, _ in self.spec if n not in sd]
+        missing = [n for n, _ in self.spec if n not in sd]
         if strict and missing:
             raise KeyError(f"missing {missing[:4]}…")
-        for n, _, kind in self.spec:
+        for n, _ in self.spec:
             if n not in sd:
                 continue
             t = sd[n].to(torch.float32)
-            if kind == "conv":
+            if self._kind[n] == "conv":
                 t = _conv_to_native(t)
             self.P[n].copy_(t.reshape(self.P[n].shape).to(self.device))
         return SimpleNamespace(missing_keys=missing, unexpected_keys=[k for k in sd if k not in self.P])
 
-    def eval(self):
-        return self
-
-    def train(self, mode=True):
-        return self
-
-    def to(self, device):
-        return self
-
     def modules(self):
         return []
 
-    def zero_grad(self):
-        self.flat_grads.zero_()
-
     # ------------------------------------------------------------------ forward
-    def __call__(self, input_values, **kw):
-        return self.forward(input_values)
-
     def conv_lengths(self, L):
         """Frames after every layer of the feature extractor for L input samples."""
         out = []
@@ -200,13 +167,6 @@ class Wav2Vec2ForCTC:
         for k, st in zip(reversed(self.cfg["conv_kernel"]), reversed(self.cfg["conv_stride"])):
             L = (L - 1) * st + k
         return L
-
-    def _scratch(self):
-        if self._ws is None:        # the model's own scratch (ops.use_workspace): a stream-keyed buffer is wrong inside a capture
-            self._ws = torch.empty(ops.WORKSPACE_BYTES, dtype=torch.uint8, device=self.device)
-            ops.counters(self._ws)
-            self._valid = torch.zeros(len(self.cfg["conv_kernel"]), dtype=torch.int32, device=self.device)
-        return self._ws
 
     def forward(self, input_values):
         """input_values [B, L] float32 on the device (already zero-mean / unit-variance) -> SimpleNamespace(logits [B, T', V], frames).
@@ -263,8 +223,7 @@ class Wav2Vec2ForCTC:
         key = (B, Lb, torch.is_grad_enabled())
         ent = self._graphs.get(key)
         if ent is None:
-            n = self._seen[key] = self._seen.get(key, 0) + 1
-            if n < self.graph_after:
+            if not self._seen(key, self.graph_after):
                 self._vl, self._ctx_static = None, False
                 return self._forward_eager(x)
             if self.graph_bytes() > self.graph_budget_bytes:
@@ -278,14 +237,11 @@ class Wav2Vec2ForCTC:
                 self._pool = torch.cuda.graph_pool_handle()
             r0 = torch.cuda.memory_reserved(self.device)
             static_in = torch.zeros(B, Lb, device=self.device, dtype=torch.float32)
-            graph = torch.cuda.CUDAGraph()
-            prof, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None
             self._vl = self._valid
             try:
-                with _no_gc(), torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"), _capture_guard():
-                    out = self._forward_eager(static_in)
+                graph, out = _graphs.capture(self._pool, lambda: self._forward_eager(static_in))
             finally:
-                ops.GEMM_PROFILE, self._vl = prof, None
+                self._vl = None
             ent = {"graph": graph, "in": static_in, "out": out.logits, "ctx": self._ctx, "bwd": {}, "len": 0,
                    "bytes": max(0, torch.cuda.memory_reserved(self.device) - r0)}
             self._graphs[key] = ent
@@ -412,8 +368,6 @@ class Wav2Vec2ForCTC:
     def backward(self, grad_logits, n_active=None):
         """Accumulates dL/dparam into flat_grads given dL/dlogits [nb, T', V] for the first nb samples of the batch.  The launch-bound
         column reductions of the norm / bias gradients run as one batched launch at the end (ops.reduce_defer; bit-identical)."""
-        if self._defer_arena is None and os.environ.get("DYN_DEFER_REDUCE", "1") != "0":
-            self._defer_arena = torch.empty(ops.DEFER_ARENA_BYTES, dtype=torch.uint8, device=self.device)
         with ops.use_workspace(self._scratch()):
             if self._ctx_static and self.use_graphs and self._ctx is not None:
                 return self._backward_graphed(grad_logits, n_active)
@@ -439,13 +393,7 @@ class Wav2Vec2ForCTC:
             self._ctx = ent["ctx"]
             r0 = torch.cuda.memory_reserved(self.device)
             static_g = grad_logits.contiguous().clone()
-            graph = torch.cuda.CUDAGraph()
-            prof, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None
-            try:
-                with _no_gc(), torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"), _capture_guard():
-                    self._backward_eager(static_g, n_active)
-            finally:
-                ops.GEMM_PROFILE = prof
+            graph, _ = _graphs.capture(self._pool, lambda: self._backward_eager(static_g, n_active))
             b = ent["bwd"][key] = {"graph": graph, "g": static_g}
             ent["bytes"] += max(0, torch.cuda.memory_reserved(self.device) - r0)
             ent["ctx"] = None                                    # released: both graphs hold the addresses, nobody needs the tensors
@@ -454,21 +402,12 @@ class Wav2Vec2ForCTC:
         self._ctx = None
 
     def _backward_eager(self, grad_logits, n_active):
-        with ops.reduce_defer(self._defer_arena):
-            self._backward_body(grad_logits, n_active)
-        for name in self.frozen:                    # after the deferred reductions have been queued: they write gradients too
-            for n, _, _ in self.spec:
-                if n.startswith(name):
-                    self.G[n].zero_()
-
-    def _backward_body(self, grad_logits, n_active=None):
-        self._wq = [] if self.grouped_wgrad else None
-        try:
+        # every linear layer's weight gradient (+ bias sums) of this backward: one launch
+        with self._reduce_defer(), self._wgrad_queue(self.grouped_wgrad):
             self._backward_layers(grad_logits, n_active)
-            if self._wq:
-                ops.gemm_grouped(self._wq)      # every linear layer's weight gradient (+ bias sums) of this backward: one launch
-        finally:
-            self._wq = None
+        for n, _ in self.spec:                      # after the deferred reductions have been queued: they write gradients too
+            if not self.trainable(n):
+                self.G[n].zero_()
 
     def _backward_layers(self, grad_logits, n_active=None):
         ctx = self._ctx
