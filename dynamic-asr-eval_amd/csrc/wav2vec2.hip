@@ -10,6 +10,7 @@
 //   * weight normalisation of the positional conv (w = g * v / ||v||, norm over (out, in) per tap) forward / backward.
 // All HBM-bound single passes with coalesced channel-contiguous accesses; reductions are fixed-order (deterministic).
 #include "common.h"
+#include "gelu.h"
 #include "reduce.h"
 
 namespace {
@@ -22,12 +23,8 @@ inline unsigned grid_for(int64_t n) {
     return (unsigned)g;
 }
 
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float gelu_grad(float x) {
-    const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
-    const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
-    return cdf + x * pdf;
-}
+using dyn::gelu_f;
+using dyn::gelu_grad;
 
 __global__ __launch_bounds__(TPB) void gelu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) y[i] = gelu_f(x[i]);

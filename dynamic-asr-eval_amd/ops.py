@@ -1101,6 +1101,42 @@ def gelu_bwd(x, dy, out=None):
     return out
 
 
+def bias_layernorm_gelu(z, conv_bias, gamma, beta, eps=1e-5):
+    """act = gelu(LayerNorm_C(z + conv_bias)) in one pass (layer-norm feature extractor).  z [..., C] is left unmodified; conv_bias may be
+    None.  Returns (act, mean [rows], rstd [rows])."""
+    _cc(z, "bias_layernorm_gelu.z"); _cc(gamma, "bias_layernorm_gelu.gamma"); _cc(beta, "bias_layernorm_gelu.beta")
+    C = z.shape[-1]
+    rows = z.numel() // C
+    act = torch.empty_like(z)
+    mean = torch.empty(rows, device=z.device, dtype=F32)
+    rstd = torch.empty(rows, device=z.device, dtype=F32)
+    check(_L().dyn_bias_layernorm_gelu_fwd(z.data_ptr(), _opt(conv_bias, "bias_layernorm_gelu.conv_bias"), gamma.data_ptr(), beta.data_ptr(),
+                                           act.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, C, eps, _stream()),
+          "dyn_bias_layernorm_gelu_fwd")
+    return act, mean, rstd
+
+
+def bias_layernorm_gelu_bwd(z, conv_bias, gamma, beta, mean, rstd, dact, dgamma, dbeta, dconv_bias, wgrad_beta=1.0, out=None):
+    """Backward of bias_layernorm_gelu from z, mean, rstd (the normalised tensor is recomputed): returns dz (`out`, which may be dact);
+    dgamma / dbeta / dconv_bias = wgrad_beta * old + column sums, each may be None (frozen)."""
+    _cc(z, "bias_layernorm_gelu_bwd.z"); _cc(dact, "bias_layernorm_gelu_bwd.dact")
+    _cc(gamma, "bias_layernorm_gelu_bwd.gamma"); _cc(beta, "bias_layernorm_gelu_bwd.beta")
+    _cc(mean, "bias_layernorm_gelu_bwd.mean"); _cc(rstd, "bias_layernorm_gelu_bwd.rstd")
+    C = z.shape[-1]
+    rows = z.numel() // C
+    if dact.numel() != z.numel() or mean.numel() != rows or rstd.numel() != rows:
+        raise DynError("bias_layernorm_gelu_bwd: dact / mean / rstd do not match z")
+    dz = torch.empty_like(z) if out is None else _cc(out, "bias_layernorm_gelu_bwd.out")
+    if dz.numel() != z.numel():
+        raise DynError("bias_layernorm_gelu_bwd: out does not match z")
+    ws = workspace(z.device)
+    check(_L().dyn_bias_layernorm_gelu_bwd(z.data_ptr(), _opt(conv_bias, "bias_layernorm_gelu_bwd.conv_bias"), gamma.data_ptr(), beta.data_ptr(),
+                                           mean.data_ptr(), rstd.data_ptr(), dact.data_ptr(), dz.data_ptr(), _opt(dgamma, "dgamma"),
+                                           _opt(dbeta, "dbeta"), _opt(dconv_bias, "dconv_bias"), wgrad_beta, rows, C, ws.data_ptr(),
+                                           ws.numel(), _stream()), "dyn_bias_layernorm_gelu_bwd")
+    return dz
+
+
 def _valid_ptr(valid, what):
     """`valid`: None, or a one-element int32 CUDA tensor holding a row / column count that the kernel reads when it RUNS (so a captured launch
     follows later updates of the tensor)."""

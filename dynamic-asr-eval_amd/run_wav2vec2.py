@@ -9,10 +9,13 @@ Like both reference drivers it processes the FIRST recording only (they `break` 
 
 `AutoModelForCTC.from_pretrained("facebook/wav2vec2-base-960h")` and the corpora cannot be fetched offline, so the harness builds
 the base architecture (HF `Wav2Vec2Config()` defaults: 7 conv layers of 512 channels, positional conv k=128 g=16, 12 x 768, vocab 32)
-with seeded weights, or loads a local HF state_dict (`-c file.pt`, torch.load(weights_only=True)), and evaluates a synthetic
+or the one a `config.json` names (`--config`, or `-c DIR` = a local HF model directory; the layer-norm / stable-LN layout of
+large-960h-lv60-self included) with seeded weights, or loads a local HF state_dict (`-c file.pt` / `DIR/pytorch_model.bin`,
+torch.load(weights_only=True)), and evaluates a synthetic
 TEDLIUM-shape talk (`--seconds`, utterances of 2-15 s).  Reported WERs use this package's reduced text
 normaliser (wer.basic_normalize), not whisper's EnglishTextNormalizer (un-vendored)."""
 import argparse
+import os
 import time
 
 import torch
@@ -20,7 +23,7 @@ import torch
 from . import wav2vec2_lib as lib
 from .datasets import fetch_utterances_from_lines, synthetic_text, synthetic_waveform
 from .decoding import GreedyCTCDecoder
-from .wav2vec2_model import Wav2Vec2ForCTC
+from .wav2vec2_model import Wav2Vec2ForCTC, config_from_json
 from .wer import basic_normalize as normalize, word_error_rate_detail
 
 
@@ -80,13 +83,23 @@ def replicate(model, n):
 
 
 def load_pretrained_model(args, device):
-    """reference wav2vec2/lib.py:20-23 (`AutoModelForCTC.from_pretrained`) — offline: local state_dict or seeded weights."""
-    model = Wav2Vec2ForCTC(None, device=device)
-    if args.checkpoint:
-        res = model.load_state_dict(torch.load(args.checkpoint, map_location='cpu', weights_only=True), strict=False)
+    """reference wav2vec2/lib.py:20-23 (`AutoModelForCTC.from_pretrained(checkpoint)`) — offline: `-c DIR` is a local HF model directory
+    (`config.json` read as plain JSON for the architecture and the layout flags + `pytorch_model.bin`), `-c FILE` a bare state_dict at the
+    base-960h architecture or at `--config PATH.json`; without a checkpoint: seeded weights at that architecture."""
+    cfg_path, ckpt = getattr(args, 'config', '') or '', args.checkpoint
+    if ckpt and os.path.isdir(ckpt):
+        cfg_path, ckpt = cfg_path or os.path.join(ckpt, 'config.json'), os.path.join(ckpt, 'pytorch_model.bin')
+    model = Wav2Vec2ForCTC(config_from_json(cfg_path) if cfg_path else None, device=device)
+    if ckpt:
+        res = model.load_state_dict(torch.load(ckpt, map_location='cpu', weights_only=True), strict=False)
         missing = getattr(res, 'missing_keys', [])
         if missing:
-            raise KeyError(f'checkpoint {args.checkpoint}: {len(missing)} parameters of the model are missing (e.g. {missing[:3]})')
+            raise KeyError(f'checkpoint {ckpt}: {len(missing)} parameters of the model are missing (e.g. {missing[:3]})')
+        # extractor parameters the configuration has no slot for: the other extractor layout, which would otherwise run with them dropped
+        extra = [k for k in getattr(res, 'unexpected_keys', []) if k.startswith('wav2vec2.feature_extractor.conv_layers.')]
+        if extra:
+            raise KeyError(f'checkpoint {ckpt}: {len(extra)} feature-extractor parameters do not belong to the configured layout '
+                           f'(e.g. {extra[:3]}): pass its config.json (-c DIR or --config)')
     else:
         init_synthetic(model, args.seed)
     return model, lib.CharTokenizer()
@@ -152,6 +165,8 @@ def build_parser():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--stm', type=str, default='', help='TEDLIUM .stm file: its segments define the utterances (reference tedlium/run.py:56-83)')
     ap.add_argument('--talks', type=int, default=1, help='synthetic talks of --seconds each (the reference walks the talks of the split)')
+    ap.add_argument('--config', type=str, default='', help='HF config.json: architecture and layout (feat_extract_norm, conv_bias, do_stable_layer_norm) '
+                                                           'for -c FILE or seeded weights; -c DIR reads DIR/config.json')
     ap.add_argument('--chains', type=int, default=1, help='talks in flight on the GPU (mode su): one model replica + HIP stream each')
     return ap
 

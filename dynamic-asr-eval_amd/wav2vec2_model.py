@@ -6,6 +6,10 @@ Architecture = HF `Wav2Vec2Config()` defaults (= base-960h: 7 strided Conv1d lay
 first, feature projection LN + Linear(512 -> 768), grouped positional conv (k = 128, 16 groups, weight-normed) + GELU,
 12 post-LN transformer layers with 12 x 64 heads and GELU FFN 3072, lm_head 768 -> 32); `feat_extract_norm="group"`,
 `do_stable_layer_norm=False`, eval mode (no dropout, no SpecAugment masking) as in the reference loop.
+The other layout transformers has (wav2vec2-large-960h-lv60-self, large-robust, XLSR) is built too, the two choices independently:
+`feat_extract_norm="layer"` + `conv_bias=True` (every extractor layer is conv -> + bias -> LayerNorm(C) -> GELU, the last three in one
+kernel each way: ops.bias_layernorm_gelu) and `do_stable_layer_norm=True` (pre-LN encoder: x + attn(LN(x)), x + ffn(LN(x)), the
+encoder's LayerNorm after the last layer).
 Parameter NAMES are HF's (state_dict interchange with transformers, which is the oracle in tests); the native HBM layout
 of conv kernels is [C_out][kernel][C_in] so each strided Conv1d is one implicit GEMM over overlapping rows of the
 channels-last activation (ops.conv1d), converted on load / save."""
@@ -24,17 +28,39 @@ DEFAULT_CONFIG = dict(
 )
 
 
+LAYOUT_FLAGS = dict(feat_extract_norm="group", do_stable_layer_norm=False, conv_bias=False)     # the base layout
+EXTRACTOR_EPS = 1e-5      # transformers builds the extractor's GroupNorm / LayerNorm with torch's default eps, not config.layer_norm_eps
+
+
 def make_config(cfg=None):
+    """DEFAULT_CONFIG + LAYOUT_FLAGS overridden by `cfg` (a dict, or an object with those attributes such as transformers'
+    Wav2Vec2Config); keys it does not carry keep the base value, other keys are ignored."""
     out = dict(DEFAULT_CONFIG)
+    out.update(LAYOUT_FLAGS)
     if cfg is not None:
         src = cfg if isinstance(cfg, dict) else cfg.__dict__
         for k in DEFAULT_CONFIG:
             if k in src:
                 out[k] = tuple(src[k]) if isinstance(src[k], (list, tuple)) else src[k]
-        if not isinstance(cfg, dict):
-            assert getattr(cfg, "feat_extract_norm", "group") == "group" and not getattr(cfg, "do_stable_layer_norm", False) and \
-                not getattr(cfg, "conv_bias", False), "only the base (group-norm, post-LN, bias-free conv) variant is built"
+        for k in LAYOUT_FLAGS:
+            v = src.get(k, None) if isinstance(cfg, dict) else getattr(cfg, k, None)
+            if v is not None:
+                out[k] = v
+    out["do_stable_layer_norm"], out["conv_bias"] = bool(out["do_stable_layer_norm"]), bool(out["conv_bias"])
+    if (out["feat_extract_norm"], out["conv_bias"]) not in (("group", False), ("layer", True)):
+        raise ops.DynError(f"feat_extract_norm={out['feat_extract_norm']!r} with conv_bias={out['conv_bias']} is not built: the feature "
+                           "extractor is either (\"group\", conv_bias=False) or (\"layer\", conv_bias=True)")
     return out
+
+
+def config_from_json(path):
+    """An HF `config.json` as plain JSON -> make_config (only DEFAULT_CONFIG's keys and the three layout flags are read)."""
+    import json
+    with open(path) as f:
+        src = json.load(f)
+    if not isinstance(src, dict):
+        raise ops.DynError(f"{path}: expected a JSON object")
+    return make_config({k: v for k, v in src.items() if k in DEFAULT_CONFIG or k in LAYOUT_FLAGS})
 
 
 def _conv_to_native(w):   # HF [Cout, Cin, k] -> native [Cout, k, Cin]
@@ -43,6 +69,30 @@ def _conv_to_native(w):   # HF [Cout, Cin, k] -> native [Cout, k, Cin]
 
 def _conv_to_hf(w):       # native [Cout, k, Cin] -> HF [Cout, Cin, k]
     return w.permute(0, 2, 1).contiguous()
+
+
+WEIGHT_NORM_MAX_ROW = 6144     # dyn_weight_norm_*: kernel * C/G floats of one (out-channel) row must fit its LDS buffer (128 * 48 at base-960h)
+
+
+def _wn_parts(K, cg):
+    """1 where a row of the positional conv's weight fits dyn_weight_norm_*; else the smallest power of two s dividing cg with K * cg / s floats
+    per row that does (2 at the large layout: 128 taps x 64 channels per group)."""
+    s = 1
+    while K * cg // s > WEIGHT_NORM_MAX_ROW and cg % (2 * s) == 0:
+        s *= 2
+    return s
+
+
+def _wn_split(t, s):
+    """[H, K, cg] -> [s * H, K, cg / s]: the channel slices of every row become rows of their own.  A tap's norm runs over (rows, channels), so the
+    weight norm of the result is the weight norm of `t` (same terms) and existing kernels serve rows wider than their LDS buffer.  Copy only."""
+    H, K, cg = t.shape
+    return t.view(H, K, s, cg // s).permute(2, 0, 1, 3).contiguous().view(s * H, K, cg // s)
+
+
+def _wn_join(t, s):
+    sH, K, c = t.shape
+    return t.view(s, sH // s, K, c).permute(1, 2, 0, 3).contiguous().view(sH // s, K, s * c)
 
 
 _RELEASED = object()      # Wav2Vec2ForCTC._ctx after a bucket replay whose saved activations are owned by its graphs only
@@ -56,8 +106,10 @@ def param_spec(c):
     cin = 1
     for i, (co, k) in enumerate(zip(c["conv_dim"], c["conv_kernel"])):
         spec.append((f"{fe}{i}.conv.weight", (co, k, cin), "conv"))
-        if i == 0:
-            spec += [(f"{fe}0.layer_norm.weight", (co,), None), (f"{fe}0.layer_norm.bias", (co,), None)]
+        if c.get("conv_bias", False):
+            spec.append((f"{fe}{i}.conv.bias", (co,), None))
+        if i == 0 or c.get("feat_extract_norm", "group") == "layer":
+            spec += [(f"{fe}{i}.layer_norm.weight", (co,), None), (f"{fe}{i}.layer_norm.bias", (co,), None)]
         cin = co
     fp = "wav2vec2.feature_projection."
     spec += [(fp + "layer_norm.weight", (cin,), None), (fp + "layer_norm.bias", (cin,), None),
@@ -91,6 +143,10 @@ class Wav2Vec2ForCTC(FlatModel):
         c = self.cfg
         H = c["hidden_size"]
         assert H % 256 == 0 and c["conv_dim"][-1] % 256 == 0, "LayerNorm kernels need C % 256 == 0"
+        self.layer_extractor = c["feat_extract_norm"] == "layer"
+        self.stable_ln = c["do_stable_layer_norm"]
+        if self.layer_extractor and any(d % 256 for d in c["conv_dim"]):
+            raise ops.DynError(f"feat_extract_norm=\"layer\" needs every conv_dim to be a multiple of 256 (got {c['conv_dim']})")
         spec = param_spec(c)
         super().__init__([(n, shape) for n, shape, _ in spec], device)
         slots = self._slots
@@ -144,6 +200,10 @@ class Wav2Vec2ForCTC(FlatModel):
             if n not in sd:
                 continue
             t = sd[n].to(torch.float32)
+            native = tuple(self.P[n].shape)
+            want = (native[0], native[2], native[1]) if self._kind[n] == "conv" else native
+            if t.numel() != self.P[n].numel() or (self._kind[n] == "conv" and tuple(t.shape) != want):
+                raise ops.DynError(f"{n}: shape {tuple(t.shape)} in the state dict does not fit this configuration's {want}")
             if self._kind[n] == "conv":
                 t = _conv_to_native(t)
             self.P[n].copy_(t.reshape(self.P[n].shape).to(self.device))
@@ -180,9 +240,14 @@ class Wav2Vec2ForCTC(FlatModel):
         (dyn_colnorm_fwd_len), the frames past the end are zeroed before the positional conv (dyn_mask_rows: what its zero padding
         holds there), and attention masks the keys past the end (dyn_softmax_fwd_len).  Everything else is per frame, or (the strided
         convs) looks only backwards from a valid frame.  The backward gets exact zeros on the padded frames (CTC gives them zero
-        gradient, every per-frame kernel maps 0 to 0, the masked softmax cuts the attention path, dyn_mask_rows / dyn_colnorm_bwd_len
-        cut the other two), so every weight gradient sums the same terms plus zeros: equal to the unpadded run up to the summation
-        order of a longer K (tests/test_wav2vec2_gpu.py)."""
+        gradient, every per-frame BACKWARD kernel maps a zero gradient row to a zero gradient row, the masked softmax cuts the
+        attention path, dyn_mask_rows / dyn_colnorm_bwd_len cut the other two), so every weight gradient sums the same terms plus
+        zeros: equal to the unpadded run up to the summation order of a longer K (tests/test_wav2vec2_gpu.py).
+        In the forward the padded rows hold zeros only in the base layout, where every per-frame kernel maps 0 to 0.  With the
+        layer-norm extractor they do not (the conv bias and the LayerNorm's beta put finite non-zero values there, the stable encoder's
+        LayerNorms likewise): nothing reads them — the statistics of that layout are per row (no ops.colnorm, `_valid[0]` unused),
+        dyn_mask_rows zeroes them before the positional conv and the masked softmax drops them as keys — and their gradients are
+        still exactly zero because every op that layout adds is per row (tests/test_wav2vec2_layernorm_gpu.py)."""
         x = input_values
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
             raise ops.DynError("input_values must be a float32 CUDA tensor [B, L]")
@@ -275,7 +340,12 @@ class Wav2Vec2ForCTC(FlatModel):
         for i, (k, s) in enumerate(zip(c["conv_kernel"], c["conv_stride"])):
             w = P[f"{fe}{i}.conv.weight"]
             z = ops.conv1d(a, w.view(w.shape[0], -1), k, s)
-            if i == 0:
+            if self.layer_extractor:                                # conv -> + bias -> LayerNorm(C) -> GELU; only (a, z, mean, rstd) are kept
+                act, mean, rstd = ops.bias_layernorm_gelu(z, P[f"{fe}{i}.conv.bias"], P[f"{fe}{i}.layer_norm.weight"],
+                                                          P[f"{fe}{i}.layer_norm.bias"], EXTRACTOR_EPS)
+                if save:
+                    ctx["conv"].append((a, z, (mean, rstd)))
+            elif i == 0:
                 n0, mean, rstd = ops.colnorm(z, P[fe + "0.layer_norm.weight"], P[fe + "0.layer_norm.bias"], c["layer_norm_eps"], valid=v0)
                 act = ops.gelu(n0)
                 if save:
@@ -298,7 +368,8 @@ class Wav2Vec2ForCTC(FlatModel):
         H, K, G = c["hidden_size"], c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
         cg, pad = H // G, K // 2
         v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
-        w = ops.weight_norm(v, g)                                   # [H, K, cg]
+        parts = _wn_parts(K, cg)
+        w = ops.weight_norm(v, g) if parts == 1 else _wn_join(ops.weight_norm(_wn_split(v, parts), g), parts)   # [H, K, cg]
         xg = ops.group_pack(h, G, pad)                              # [B, G, T + 2 pad, cg]
         Tp = T + 2 * pad
         yg = torch.empty(B, G, T, cg, device=h.device, dtype=torch.float32)
@@ -308,28 +379,16 @@ class Wav2Vec2ForCTC(FlatModel):
         pos = ops.gelu(pre)
         hs = h.clone() if save else h
         ops.axpby(pos, hs, 1.0, 1.0)
+        if self.stable_ln:
+            return self._encoder_stable(hs, ctx, (xg, w, pre), vT, (B, L, T), v0)
         h2, mean, rstd = ops.layernorm(hs, P["wav2vec2.encoder.layer_norm.weight"], P["wav2vec2.encoder.layer_norm.bias"], c["layer_norm_eps"])
         if save:
             ctx["pos"] = (xg, w, pre, hs, mean, rstd)
             ctx["layers"] = []
         h = h2
-        nh = c["num_attention_heads"]
-        D = H // nh
         for l in range(c["num_hidden_layers"]):
             p = f"wav2vec2.encoder.layers.{l}."
-            qkv = torch.empty(B, T, 3 * H, device=h.device, dtype=torch.float32)
-            if self.packed_qkv:
-                ops.linear(h, self.Pqkv[l][0], self.Pqkv[l][1], out=qkv)
-            for j, nm in enumerate(() if self.packed_qkv else ("q_proj", "k_proj", "v_proj")):
-                ops.gemm(h, P[p + f"attention.{nm}.weight"], qkv, trans_b=True, M=B * T, N=H, K=H, lda=H, ldb=H, ldc=3 * H,
-                         c_off=j * H, bias=P[p + f"attention.{nm}.bias"])
-            S = torch.empty(B, nh, T, T, device=h.device, dtype=torch.float32)
-            ops.gemm(qkv, qkv, S, trans_b=True, M=T, N=T, K=D, lda=3 * H, ldb=3 * H, ldc=T, nb1=B, nb2=nh,
-                     sa=(T * 3 * H, D), sb=(T * 3 * H, D), sc=(nh * T * T, T * T), b_off=H, alpha=D ** -0.5)
-            ops.softmax(S, out=S, valid=vT)
-            O = torch.empty(B, T, H, device=h.device, dtype=torch.float32)
-            ops.gemm(S, qkv, O, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=H, nb1=B, nb2=nh, sa=(nh * T * T, T * T),
-                     sb=(T * 3 * H, D), sc=(T * H, D), b_off=2 * H)
+            qkv, S, O = self._attention(h, l, vT)
             r1 = h.clone() if save else h
             ops.linear(O, P[p + "attention.out_proj.weight"], P[p + "attention.out_proj.bias"], out=r1, beta=1.0)
             h1, m1, s1 = ops.layernorm(r1, P[p + "layer_norm.weight"], P[p + "layer_norm.bias"], c["layer_norm_eps"])
@@ -348,6 +407,98 @@ class Wav2Vec2ForCTC(FlatModel):
             ctx["valid"] = (v0, vT)
         self._ctx = ctx
         return SimpleNamespace(logits=logits, frames=T)
+
+    def _attention(self, h, l, vT):
+        """Self-attention of layer l on h [B, T, H] up to (not including) the output projection: returns (qkv, S, O)."""
+        c, P = self.cfg, self.P
+        B, T, H = h.shape
+        nh = c["num_attention_heads"]
+        D = H // nh
+        p = f"wav2vec2.encoder.layers.{l}."
+        qkv = torch.empty(B, T, 3 * H, device=h.device, dtype=torch.float32)
+        if self.packed_qkv:
+            ops.linear(h, self.Pqkv[l][0], self.Pqkv[l][1], out=qkv)
+        for j, nm in enumerate(() if self.packed_qkv else ("q_proj", "k_proj", "v_proj")):
+            ops.gemm(h, P[p + f"attention.{nm}.weight"], qkv, trans_b=True, M=B * T, N=H, K=H, lda=H, ldb=H, ldc=3 * H,
+                     c_off=j * H, bias=P[p + f"attention.{nm}.bias"])
+        S = torch.empty(B, nh, T, T, device=h.device, dtype=torch.float32)
+        ops.gemm(qkv, qkv, S, trans_b=True, M=T, N=T, K=D, lda=3 * H, ldb=3 * H, ldc=T, nb1=B, nb2=nh,
+                 sa=(T * 3 * H, D), sb=(T * 3 * H, D), sc=(nh * T * T, T * T), b_off=H, alpha=D ** -0.5)
+        ops.softmax(S, out=S, valid=vT)
+        O = torch.empty(B, T, H, device=h.device, dtype=torch.float32)
+        ops.gemm(S, qkv, O, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=H, nb1=B, nb2=nh, sa=(nh * T * T, T * T),
+                 sb=(T * 3 * H, D), sc=(T * H, D), b_off=2 * H)
+        return qkv, S, O
+
+    def _encoder_stable(self, x, ctx, pos, vT, dims, v0):
+        """The pre-LN encoder (transformers Wav2Vec2EncoderStableLayerNorm) from x = h + gelu(pos_conv(h)): per layer
+        x = x + out_proj(attn(LN1(x))), x = x + ffn(LN2(x)); the encoder's LayerNorm after the last layer; lm_head."""
+        c, P = self.cfg, self.P
+        save = ctx is not None
+        eps = c["layer_norm_eps"]
+        if save:
+            ctx["pos"] = pos + (None, None, None)
+            ctx["layers"] = []
+        for l in range(c["num_hidden_layers"]):
+            p = f"wav2vec2.encoder.layers.{l}."
+            n1, m1, s1 = ops.layernorm(x, P[p + "layer_norm.weight"], P[p + "layer_norm.bias"], eps)
+            qkv, S, O = self._attention(n1, l, vT)
+            r1 = x.clone() if save else x
+            ops.linear(O, P[p + "attention.out_proj.weight"], P[p + "attention.out_proj.bias"], out=r1, beta=1.0)
+            n2, m2, s2 = ops.layernorm(r1, P[p + "final_layer_norm.weight"], P[p + "final_layer_norm.bias"], eps)
+            u = ops.linear(n2, P[p + "feed_forward.intermediate_dense.weight"], P[p + "feed_forward.intermediate_dense.bias"])
+            ga = ops.gelu(u)
+            r2 = r1.clone() if save else r1
+            ops.linear(ga, P[p + "feed_forward.output_dense.weight"], P[p + "feed_forward.output_dense.bias"], out=r2, beta=1.0)
+            if save:
+                ctx["layers"].append((x, m1, s1, n1, qkv, S, O, r1, m2, s2, n2, u, ga))
+            x = r2
+        h, mean, rstd = ops.layernorm(x, P["wav2vec2.encoder.layer_norm.weight"], P["wav2vec2.encoder.layer_norm.bias"], eps)
+        logits = ops.linear(h, P["lm_head.weight"], P["lm_head.bias"])
+        if save:
+            ctx["final"] = (x, mean, rstd)
+            ctx["head"] = h
+            ctx["dims"] = dims
+            ctx["valid"] = (v0, vT)
+        self._ctx = ctx
+        return SimpleNamespace(logits=logits, frames=dims[2])
+
+    def _attention_bwd(self, dO, qkv, S, h, l, nb, T, residual):
+        """Backward of _attention: queues / accumulates the q | k | v weight gradients and returns d h (+ `residual` when given, out of
+        place: it may be a queued operand)."""
+        c, P, G = self.cfg, self.P, self.G
+        H, nh = c["hidden_size"], c["num_attention_heads"]
+        D = H // nh
+        p = f"wav2vec2.encoder.layers.{l}."
+        dqkv = torch.empty_like(qkv)
+        sS, sQ, sO = (nh * T * T, T * T), (T * 3 * H, D), (T * H, D)
+        ops.gemm(S, dO, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sO, sc=sQ, c_off=2 * H)
+        dP = torch.empty_like(S)
+        ops.gemm(dO, qkv, dP, trans_b=True, M=T, N=T, K=D, lda=H, ldb=3 * H, ldc=T, nb1=nb, nb2=nh, sa=sO, sb=sQ, sc=sS, b_off=2 * H)
+        ops.softmax_bwd(S, dP, out=dP, scale=1.0)
+        sc = D ** -0.5
+        ops.gemm(dP, qkv, dqkv, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sQ, b_off=H, c_off=0, alpha=sc)
+        ops.gemm(dP, qkv, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sQ,
+                 b_off=0, c_off=H, alpha=sc)
+        M = nb * T
+        if self.packed_qkv:                                      # the three projections as one [3H, H] product each way
+            self._wgrad(dqkv.view(M, 3 * H), h.view(M, H), self.Gqkv[l][0], self.Gqkv[l][1])
+            dh_in = torch.empty_like(dO)                         # the residual path may be a queued operand: not accumulated in place
+            if residual is not None:
+                ops.gemm(dqkv, self.Pqkv[l][0], dh_in, M=M, N=H, K=3 * H, lda=3 * H, ldb=H, ldc=H, beta=1.0, c_in=residual)
+            else:
+                ops.gemm(dqkv, self.Pqkv[l][0], dh_in, M=M, N=H, K=3 * H, lda=3 * H, ldb=H, ldc=H)
+        elif residual is None:
+            dh_in = torch.zeros_like(dO)
+        else:
+            dh_in = residual.clone() if self._wq is not None else residual
+        for j, nm in enumerate(() if self.packed_qkv else ("q_proj", "k_proj", "v_proj")):
+            # dW += dqkv_j^T h ; db += colsum ; dh += dqkv_j W      (dqkv_j is a strided [M, H] slice, lda = 3H)
+            ops.gemm(dqkv, h, G[p + f"attention.{nm}.weight"], trans_a=True, M=H, N=H, K=M, lda=3 * H, ldb=H, ldc=H, a_off=j * H, beta=1.0)
+            dj = dqkv.view(M, 3, H)[:, j, :].contiguous()
+            ops.colsum(dj, G[p + f"attention.{nm}.bias"], beta=1.0)
+            ops.gemm(dqkv, P[p + f"attention.{nm}.weight"], dh_in, M=M, N=H, K=H, lda=3 * H, ldb=H, ldc=H, a_off=j * H, beta=1.0)
+        return dh_in
 
     # ------------------------------------------------------------------ backward
     def _wgrad(self, dy, x, dw, db):
@@ -436,7 +587,29 @@ class Wav2Vec2ForCTC(FlatModel):
         eps = c["layer_norm_eps"]
         h_last = cut(ctx["head"])
         dh = self._lin_bwd(grad_logits.contiguous(), h_last, "lm_head.weight", "lm_head.bias")
-        for l in reversed(range(c["num_hidden_layers"])):
+        if self.stable_ln:
+            x, mean, rstd = cut(ctx["final"])
+            dx = torch.empty_like(dh)
+            ops.layernorm_bwd(x, P["wav2vec2.encoder.layer_norm.weight"], mean, rstd, dh, dx, G["wav2vec2.encoder.layer_norm.weight"],
+                              G["wav2vec2.encoder.layer_norm.bias"], dx_beta=0.0)
+        for l in reversed(range(c["num_hidden_layers"]) if self.stable_ln else ()):
+            # x -> r1 = x + out_proj(attn(LN1(x))) -> r2 = r1 + ffn(LN2(r1)); dx is dL/dr2.  Each residual sum rides on the LayerNorm
+            # backward's dx = grad + dx_in form (out of place: dx / dr1 are queued weight-gradient operands), so no add pass of its own.
+            p = f"wav2vec2.encoder.layers.{l}."
+            x, m1, s1, n1, qkv, S, O, r1, m2, s2, n2, u, ga = cut(ctx["layers"][l])
+            dga = self._lin_bwd(dx, ga, p + "feed_forward.output_dense.weight", p + "feed_forward.output_dense.bias")
+            du = ops.gelu_bwd(u, dga, out=dga)
+            dn2 = self._lin_bwd(du, n2, p + "feed_forward.intermediate_dense.weight", p + "feed_forward.intermediate_dense.bias")
+            dr1 = torch.empty_like(dx)
+            ops.layernorm_bwd(r1, P[p + "final_layer_norm.weight"], m2, s2, dn2, dr1, G[p + "final_layer_norm.weight"],
+                              G[p + "final_layer_norm.bias"], dx_beta=1.0, dx_in=dx)
+            dO = self._lin_bwd(dr1, O, p + "attention.out_proj.weight", p + "attention.out_proj.bias")
+            dn1 = self._attention_bwd(dO, qkv, S, n1, l, nb, T, None)
+            dx = torch.empty_like(dr1)
+            ops.layernorm_bwd(x, P[p + "layer_norm.weight"], m1, s1, dn1, dx, G[p + "layer_norm.weight"], G[p + "layer_norm.bias"],
+                              dx_beta=1.0, dx_in=dr1)
+            ctx["layers"][l] = None
+        for l in reversed(() if self.stable_ln else range(c["num_hidden_layers"])):
             p = f"wav2vec2.encoder.layers.{l}."
             h, qkv, S, O, r1, m1, s1, h1, u, ga, r2, m2, s2 = cut(ctx["layers"][l])
             dr2 = torch.empty_like(dh)
@@ -450,29 +623,7 @@ class Wav2Vec2ForCTC(FlatModel):
             ops.layernorm_bwd(r1, P[p + "layer_norm.weight"], m1, s1, dh1, dr1, G[p + "layer_norm.weight"], G[p + "layer_norm.bias"],
                               dx_beta=0.0)
             dO = self._lin_bwd(dr1, O, p + "attention.out_proj.weight", p + "attention.out_proj.bias")
-            dqkv = torch.empty_like(qkv)
-            sS, sQ, sO = (nh * T * T, T * T), (T * 3 * H, D), (T * H, D)
-            ops.gemm(S, dO, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sO, sc=sQ, c_off=2 * H)
-            dP = torch.empty_like(S)
-            ops.gemm(dO, qkv, dP, trans_b=True, M=T, N=T, K=D, lda=H, ldb=3 * H, ldc=T, nb1=nb, nb2=nh, sa=sO, sb=sQ, sc=sS, b_off=2 * H)
-            ops.softmax_bwd(S, dP, out=dP, scale=1.0)
-            sc = D ** -0.5
-            ops.gemm(dP, qkv, dqkv, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sQ, b_off=H, c_off=0, alpha=sc)
-            ops.gemm(dP, qkv, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sQ,
-                     b_off=0, c_off=H, alpha=sc)
-            M = nb * T
-            if self.packed_qkv:                                      # the three projections as one [3H, H] product each way
-                self._wgrad(dqkv.view(M, 3 * H), h.view(M, H), self.Gqkv[l][0], self.Gqkv[l][1])
-                dh_in = torch.empty_like(dr1)                        # dr1 (residual path) may be a queued operand: not accumulated in place
-                ops.gemm(dqkv, self.Pqkv[l][0], dh_in, M=M, N=H, K=3 * H, lda=3 * H, ldb=H, ldc=H, beta=1.0, c_in=dr1)
-            else:
-                dh_in = dr1.clone() if self._wq is not None else dr1
-            for j, nm in enumerate(() if self.packed_qkv else ("q_proj", "k_proj", "v_proj")):
-                # dW += dqkv_j^T h ; db += colsum ; dh += dqkv_j W      (dqkv_j is a strided [M, H] slice, lda = 3H)
-                ops.gemm(dqkv, h, G[p + f"attention.{nm}.weight"], trans_a=True, M=H, N=H, K=M, lda=3 * H, ldb=H, ldc=H, a_off=j * H, beta=1.0)
-                dj = dqkv.view(M, 3, H)[:, j, :].contiguous()
-                ops.colsum(dj, G[p + f"attention.{nm}.bias"], beta=1.0)
-                ops.gemm(dqkv, P[p + f"attention.{nm}.weight"], dh_in, M=M, N=H, K=H, lda=3 * H, ldb=H, ldc=H, a_off=j * H, beta=1.0)
+            dh_in = self._attention_bwd(dO, qkv, S, h, l, nb, T, dr1)
             dh = dh_in
             ctx["layers"][l] = None
         # encoder LayerNorm, positional conv
@@ -482,9 +633,12 @@ class Wav2Vec2ForCTC(FlatModel):
         K, Gn = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
         cg, pad = H // Gn, K // 2
         Tp = T + 2 * pad
-        dhs = torch.empty_like(dh)
-        ops.layernorm_bwd(hs, P["wav2vec2.encoder.layer_norm.weight"], mean, rstd, dh, dhs, G["wav2vec2.encoder.layer_norm.weight"],
-                          G["wav2vec2.encoder.layer_norm.bias"], dx_beta=0.0)
+        if self.stable_ln:
+            dhs = dx                                                 # dL/d(h + pos): no queued product reads it, so the pos path adds in place
+        else:
+            dhs = torch.empty_like(dh)
+            ops.layernorm_bwd(hs, P["wav2vec2.encoder.layer_norm.weight"], mean, rstd, dh, dhs, G["wav2vec2.encoder.layer_norm.weight"],
+                              G["wav2vec2.encoder.layer_norm.bias"], dx_beta=0.0)
         dpre = ops.gelu_bwd(pre, dhs)
         ops.colsum(dpre, G[pc + "bias"], beta=1.0)
         dyg = ops.group_pack_grad(dpre, Gn, T)                       # [nb, G, T, cg]
@@ -493,7 +647,13 @@ class Wav2Vec2ForCTC(FlatModel):
             ops.gemm(dyg, xg, dw, trans_a=True, M=cg, N=K * cg, K=T, lda=cg, ldb=cg, ldc=K * cg, nb1=1, nb2=Gn,
                      sa=(0, T * cg), sb=(0, Tp * cg), sc=(0, cg * K * cg), a_off=b * Gn * T * cg, b_off=b * Gn * Tp * cg, beta=1.0)
         v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
-        ops.weight_norm_bwd(v, g, dw, G[pc + "parametrizations.weight.original1"], G[pc + "parametrizations.weight.original0"], beta=1.0)
+        parts = _wn_parts(K, cg)
+        if parts == 1:
+            ops.weight_norm_bwd(v, g, dw, G[pc + "parametrizations.weight.original1"], G[pc + "parametrizations.weight.original0"], beta=1.0)
+        else:                                                        # rows wider than the kernel's LDS buffer: see _wn_split
+            dv = torch.zeros(parts * H, K, cg // parts, device=dh.device, dtype=torch.float32)
+            ops.weight_norm_bwd(_wn_split(v, parts), g, _wn_split(dw, parts), dv, G[pc + "parametrizations.weight.original0"], beta=1.0)
+            ops.axpby(_wn_join(dv, parts), G[pc + "parametrizations.weight.original1"], 1.0, 1.0)
         dA = torch.empty(nb, Gn, T, K * cg, device=dh.device, dtype=torch.float32)
         ops.gemm(dyg, w, dA, M=T, N=K * cg, K=cg, lda=cg, ldb=K * cg, ldc=K * cg, nb1=nb, nb2=Gn, sa=(Gn * T * cg, T * cg),
                  sb=(0, cg * K * cg), sc=(Gn * T * K * cg, T * K * cg))
@@ -517,7 +677,12 @@ class Wav2Vec2ForCTC(FlatModel):
             a_in, z, norm = cut(ctx["conv"][i])
             wname = f"{fe}{i}.conv.weight"
             wmat = P[wname].view(P[wname].shape[0], -1)
-            if i == 0:
+            if self.layer_extractor:                                 # GELU', LayerNorm backward and the three column sums in one pass, dz over da
+                mean, rstd = norm
+                gw, gb, cb = (f"{fe}{i}.layer_norm.weight", f"{fe}{i}.layer_norm.bias", f"{fe}{i}.conv.bias")
+                dz = ops.bias_layernorm_gelu_bwd(z, P[cb], P[gw], P[gb], mean, rstd, da, *(G[n] if self.trainable(n) else None for n in (gw, gb, cb)),
+                                                 out=da)
+            elif i == 0:
                 mean, rstd, n0 = norm
                 dn0 = ops.gelu_bwd(n0, da)
                 dz = ops.colnorm_bwd(z, P[fe + "0.layer_norm.weight"], mean, rstd, dn0, G[fe + "0.layer_norm.weight"], G[fe + "0.layer_norm.bias"],

@@ -530,6 +530,23 @@ int dyn_stitch_finalize_rows(const float* acc, const float* count, const int64_t
  * ------------------------------------------------------------------------------------------------ */
 int dyn_gelu_fwd(const float* x, float* y, int64_t n, void* stream);
 int dyn_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream);
+/* Feature-extractor layer of the layer-norm layout (`feat_extract_norm: "layer"`, `conv_bias: true`: wav2vec2-large-960h-lv60-self,
+ * large-robust, XLSR), which the reference reaches through the same `AutoModelForCTC.from_pretrained(checkpoint)` (wav2vec2/lib.py:20-23)
+ * and `model(input_values).logits` (:163,413) / `loss.backward()` (:194,437).  Replaces, after the bias-free conv GEMM, the rest of
+ * transformers' Wav2Vec2LayerNormConvLayer.forward (modeling_wav2vec2.py: `self.conv` bias add, `transpose`, `self.layer_norm`,
+ * `transpose`, `self.activation`) and its autograd in one pass each way over rows x C (C % 256 == 0 else DYN_E_ARG; C <= 1024):
+ *   fwd: act = gelu(LN(z + conv_bias)), exact erf GELU as dyn_gelu_fwd; writes mean / rstd [rows]; z is not modified; conv_bias may be null.
+ *   bwd: recomputes xhat and n = xhat * gamma + beta from z, mean, rstd (the normalised tensor is never stored); dn = dact * gelu'(n);
+ *        dz = LayerNorm backward of dn (dz may be dact itself); dgamma = sum dn * xhat, dbeta = sum dn, dconv_bias = sum dz over the rows,
+ *        each `= wgrad_beta * old + sum` and each may be null (a frozen parameter).  The column sums go through per-workgroup partial
+ *        rows in `workspace` and the fixed-order reducers (bit-reproducible; recorded instead while a dyn_reduce_defer context is open).
+ * No call synchronises or allocates: both are captured into the length buckets' hipGraphs. */
+int dyn_bias_layernorm_gelu_fwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, float* act, float* mean,
+                                float* rstd, int64_t rows, int64_t C, float eps, void* stream);
+int64_t dyn_bias_layernorm_gelu_bwd_workspace_bytes(int64_t rows, int64_t C);
+int dyn_bias_layernorm_gelu_bwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, const float* mean,
+                                const float* rstd, const float* dact, float* dz, float* dgamma, float* dbeta, float* dconv_bias,
+                                float wgrad_beta, int64_t rows, int64_t C, void* workspace, int64_t workspace_bytes, void* stream);
 int64_t dyn_colnorm_workspace_bytes(int64_t B, int64_t T, int64_t C);
 int dyn_colnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int64_t B,
                     int64_t T, int64_t C, float eps, void* workspace, int64_t workspace_bytes, void* stream);
