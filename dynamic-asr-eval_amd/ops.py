@@ -677,6 +677,91 @@ def softmax_bwd(y, dy, out=None, scale=1.0):
     return out
 
 
+# ----------------------------------------------------------------------------------------------- WavLM gated relative-position bias
+def relative_position_buckets(Tmax, num_buckets, max_distance):
+    """int32 CPU table [2 Tmax - 1]: entry d + Tmax - 1 is the bucket of the signed distance d = key - query, d in (-Tmax, Tmax).  The
+    expressions are those of transformers' WavLMAttention._relative_positions_bucket, evaluated by torch on the host: the logarithmic half
+    goes through a float32 log and a truncation, so any other evaluation can land in the neighbouring bucket at an edge."""
+    import math
+    d = torch.arange(-(Tmax - 1), Tmax, dtype=torch.long)
+    half = num_buckets // 2
+    out = (d > 0).to(torch.long) * half
+    d = torch.abs(d)
+    max_exact = half // 2
+    large = torch.log(d.float() / max_exact)
+    large = large / math.log(max_distance / max_exact)
+    large = large * (half - max_exact)
+    large = (max_exact + large).to(torch.long)
+    large = torch.min(large, torch.full_like(large, half - 1))
+    return (out + torch.where(d < max_exact, d, large)).to(I32)
+
+
+def _relbias_dims(who, S, nh, D, E, table):
+    if S.dim() != 4 or S.shape[1] != nh or S.shape[2] != S.shape[3]:
+        raise DynError(f"{who}: scores must be [B, {nh}, T, T], got {tuple(S.shape)}")
+    _cc(E, who + ".E"); _c(table, who + ".table", I32)
+    if E.dim() != 2 or E.shape[1] != nh:
+        raise DynError(f"{who}: E must be [num_buckets, {nh}], got {tuple(E.shape)}")
+    if table.dim() != 1 or table.numel() % 2 != 1:
+        raise DynError(f"{who}: the bucket table must hold 2 * Tmax - 1 entries")
+    return S.shape[0], S.shape[2], nh * D, (table.numel() + 1) // 2, E.shape[0]
+
+
+def relpos_gate(h, W, bias, const, nh):
+    """WavLM's gate on the relative-position bias: h [B, T, H], W [8, H / nh], bias [8], const [nh] -> (gate, a, c), each [B, nh, T]
+    (a, c: the two sigmoids, kept for relpos_gate_bwd)."""
+    _cc(h, "relpos_gate.h"); _cc(W, "relpos_gate.W"); _c(bias, "relpos_gate.bias"); _c(const, "relpos_gate.const")
+    B, T, H = h.shape
+    if H % nh or W.shape != (8, H // nh) or bias.numel() != 8 or const.numel() != nh:
+        raise DynError(f"relpos_gate: W {tuple(W.shape)} / bias {tuple(bias.shape)} / const {tuple(const.shape)} do not fit H={H}, heads={nh}")
+    gate, a, c = (torch.empty(B, nh, T, device=h.device, dtype=F32) for _ in range(3))
+    check(_L().dyn_relpos_gate_fwd(h.data_ptr(), W.data_ptr(), bias.data_ptr(), const.data_ptr(), gate.data_ptr(), a.data_ptr(), c.data_ptr(),
+                                   B, T, H, nh, _stream()), "dyn_relpos_gate_fwd")
+    return gate, a, c
+
+
+def relpos_gate_bwd(dgate, a, c, h, W, const, dh, dW, dbias, dconst, dh_beta=1.0, beta=1.0):
+    """Backward of relpos_gate: dh [B, T, H] = dh_beta * dh + its gradient (the attention's input gradient), dW / dbias / dconst = beta * old + sums."""
+    for t, n in ((dgate, "dgate"), (a, "a"), (c, "c"), (h, "h"), (W, "W"), (dh, "dh"), (dW, "dW")):
+        _cc(t, "relpos_gate_bwd." + n)
+    _c(const, "relpos_gate_bwd.const"); _c(dbias, "relpos_gate_bwd.dbias"); _c(dconst, "relpos_gate_bwd.dconst")
+    B, T, H = h.shape
+    nh = const.numel()
+    if tuple(dgate.shape) != (B, nh, T) or a.shape != dgate.shape or c.shape != dgate.shape or dh.shape != h.shape or dW.shape != W.shape \
+            or dbias.numel() != 8 or dconst.numel() != nh:
+        raise DynError("relpos_gate_bwd: operand shapes do not match")
+    ws = workspace(h.device)
+    check(_L().dyn_relpos_gate_bwd(dgate.data_ptr(), a.data_ptr(), c.data_ptr(), h.data_ptr(), W.data_ptr(), const.data_ptr(), dh.data_ptr(),
+                                   dh_beta, dW.data_ptr(), dbias.data_ptr(), dconst.data_ptr(), beta, B, T, H, nh, ws.data_ptr(), ws.numel(),
+                                   _stream()), "dyn_relpos_gate_bwd")
+    return dh
+
+
+def softmax_relbias(S, gate, E, table, D, out=None, valid=None):
+    """softmax over the keys of S [B, nh, T, T] + gate[b, head, t] * E[table[s - t + Tmax - 1], head]; `valid` as in softmax()."""
+    _cc(S, "softmax_relbias.S"); _cc(gate, "softmax_relbias.gate")
+    B, T, H, Tmax, nbk = _relbias_dims("softmax_relbias", S, gate.shape[1] if gate.dim() == 3 else -1, D, E, table)
+    if tuple(gate.shape) != (B, S.shape[1], T):
+        raise DynError("softmax_relbias: gate does not match the scores")
+    out = torch.empty_like(S) if out is None else _cc(out, "softmax_relbias.out")
+    check(_L().dyn_softmax_relbias_fwd_len(S.data_ptr(), out.data_ptr(), gate.data_ptr(), E.data_ptr(), table.data_ptr(), B, T, H, S.shape[1],
+                                           Tmax, nbk, _valid_ptr(valid, "softmax_relbias"), _stream()), "dyn_softmax_relbias_fwd_len")
+    return out
+
+
+def relbias_bwd(dS, gate, E, table, D, dE, beta=1.0):
+    """From dS [B, nh, T, T] (gradient w.r.t. the pre-softmax sum): returns dgate [B, nh, T]; dE = beta * dE + the bias table's gradient."""
+    _cc(dS, "relbias_bwd.dS"); _cc(gate, "relbias_bwd.gate"); _cc(dE, "relbias_bwd.dE")
+    B, T, H, Tmax, nbk = _relbias_dims("relbias_bwd", dS, gate.shape[1] if gate.dim() == 3 else -1, D, E, table)
+    if tuple(gate.shape) != (B, dS.shape[1], T) or dE.shape != E.shape:
+        raise DynError("relbias_bwd: gate / dE do not match the scores / E")
+    dgate = torch.empty_like(gate)
+    ws = workspace(dS.device)
+    check(_L().dyn_relbias_bwd(dS.data_ptr(), gate.data_ptr(), E.data_ptr(), table.data_ptr(), dgate.data_ptr(), dE.data_ptr(), beta, B, T, H,
+                               dS.shape[1], Tmax, nbk, ws.data_ptr(), ws.numel(), _stream()), "dyn_relbias_bwd")
+    return dgate
+
+
 def log_softmax(x, out=None):
     _cc(x, "log_softmax.x")
     rows, L = _rows_L(x)

@@ -23,6 +23,7 @@ import torch
 from . import wav2vec2_lib as lib
 from .datasets import fetch_utterances_from_lines, synthetic_text, synthetic_waveform
 from .decoding import GreedyCTCDecoder
+from . import wavlm_model
 from .wav2vec2_model import Wav2Vec2ForCTC, config_from_json
 from .wer import basic_normalize as normalize, word_error_rate_detail
 
@@ -74,7 +75,7 @@ def replicate(model, n):
     """n - 1 more replicas of `model` (same configuration and weights) for lib.dynamic_eval_su_many."""
     out = [model]
     for _ in range(max(0, n - 1)):
-        m = Wav2Vec2ForCTC(model.cfg, device=model.device)
+        m = type(model)(model.cfg, device=model.device)
         m.flat_params.copy_(model.flat_params)
         m.frozen = set(model.frozen)
         m.bucket_frames, m.graph_after, m.graph_budget_bytes = model.bucket_frames, model.graph_after, model.graph_budget_bytes
@@ -82,21 +83,33 @@ def replicate(model, n):
     return out
 
 
+def model_type(cfg_path):
+    """`model_type` of an HF config.json ('' when it names none)."""
+    import json
+    with open(cfg_path) as f:
+        src = json.load(f)
+    return src.get('model_type', '') if isinstance(src, dict) else ''
+
+
 def load_pretrained_model(args, device):
     """reference wav2vec2/lib.py:20-23 (`AutoModelForCTC.from_pretrained(checkpoint)`) — offline: `-c DIR` is a local HF model directory
     (`config.json` read as plain JSON for the architecture and the layout flags + `pytorch_model.bin`), `-c FILE` a bare state_dict at the
-    base-960h architecture or at `--config PATH.json`; without a checkpoint: seeded weights at that architecture."""
+    base-960h architecture or at `--config PATH.json`; without a checkpoint: seeded weights at that architecture.  A config.json whose
+    `model_type` is "wavlm" builds WavLMForCTC (wavlm_model.py), under `-c DIR` and under `--config` alike; anything else Wav2Vec2ForCTC."""
     cfg_path, ckpt = getattr(args, 'config', '') or '', args.checkpoint
     if ckpt and os.path.isdir(ckpt):
         cfg_path, ckpt = cfg_path or os.path.join(ckpt, 'config.json'), os.path.join(ckpt, 'pytorch_model.bin')
-    model = Wav2Vec2ForCTC(config_from_json(cfg_path) if cfg_path else None, device=device)
+    if cfg_path and model_type(cfg_path) == 'wavlm':        # what AutoModelForCTC dispatches on
+        model = wavlm_model.WavLMForCTC(wavlm_model.config_from_json(cfg_path), device=device)
+    else:
+        model = Wav2Vec2ForCTC(config_from_json(cfg_path) if cfg_path else None, device=device)
     if ckpt:
         res = model.load_state_dict(torch.load(ckpt, map_location='cpu', weights_only=True), strict=False)
         missing = getattr(res, 'missing_keys', [])
         if missing:
             raise KeyError(f'checkpoint {ckpt}: {len(missing)} parameters of the model are missing (e.g. {missing[:3]})')
         # extractor parameters the configuration has no slot for: the other extractor layout, which would otherwise run with them dropped
-        extra = [k for k in getattr(res, 'unexpected_keys', []) if k.startswith('wav2vec2.feature_extractor.conv_layers.')]
+        extra = [k for k in getattr(res, 'unexpected_keys', []) if k.startswith(model._prefix + 'feature_extractor.conv_layers.')]
         if extra:
             raise KeyError(f'checkpoint {ckpt}: {len(extra)} feature-extractor parameters do not belong to the configured layout '
                            f'(e.g. {extra[:3]}): pass its config.json (-c DIR or --config)')

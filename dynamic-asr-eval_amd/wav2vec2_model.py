@@ -32,14 +32,14 @@ LAYOUT_FLAGS = dict(feat_extract_norm="group", do_stable_layer_norm=False, conv_
 EXTRACTOR_EPS = 1e-5      # transformers builds the extractor's GroupNorm / LayerNorm with torch's default eps, not config.layer_norm_eps
 
 
-def make_config(cfg=None):
-    """DEFAULT_CONFIG + LAYOUT_FLAGS overridden by `cfg` (a dict, or an object with those attributes such as transformers'
-    Wav2Vec2Config); keys it does not carry keep the base value, other keys are ignored."""
-    out = dict(DEFAULT_CONFIG)
+def make_config(cfg=None, defaults=DEFAULT_CONFIG):
+    """`defaults` (DEFAULT_CONFIG; a model of the family may add keys of its own) + LAYOUT_FLAGS overridden by `cfg` (a dict, or an object with
+    those attributes such as transformers' Wav2Vec2Config); keys it does not carry keep the base value, other keys are ignored."""
+    out = dict(defaults)
     out.update(LAYOUT_FLAGS)
     if cfg is not None:
         src = cfg if isinstance(cfg, dict) else cfg.__dict__
-        for k in DEFAULT_CONFIG:
+        for k in defaults:
             if k in src:
                 out[k] = tuple(src[k]) if isinstance(src[k], (list, tuple)) else src[k]
         for k in LAYOUT_FLAGS:
@@ -53,14 +53,16 @@ def make_config(cfg=None):
     return out
 
 
-def config_from_json(path):
-    """An HF `config.json` as plain JSON -> make_config (only DEFAULT_CONFIG's keys and the three layout flags are read)."""
+def config_from_json(path, make=make_config):
+    """An HF `config.json` as plain JSON -> make_config (only DEFAULT_CONFIG's keys and the three layout flags are read; `make`: the
+    configuration reader of another model of the family)."""
     import json
     with open(path) as f:
         src = json.load(f)
     if not isinstance(src, dict):
         raise ops.DynError(f"{path}: expected a JSON object")
-    return make_config({k: v for k, v in src.items() if k in DEFAULT_CONFIG or k in LAYOUT_FLAGS})
+    known = make()
+    return make({k: v for k, v in src.items() if k in known})
 
 
 def _conv_to_native(w):   # HF [Cout, Cin, k] -> native [Cout, k, Cin]
@@ -98,11 +100,12 @@ def _wn_join(t, s):
 _RELEASED = object()      # Wav2Vec2ForCTC._ctx after a bucket replay whose saved activations are owned by its graphs only
 
 
-def param_spec(c):
-    """[(name, shape, kind)] with HF's names; kind "conv": a conv kernel kept as [C_out][kernel][C_in], "g": the weight norm's magnitudes."""
+def param_spec(c, pf="wav2vec2."):
+    """[(name, shape, kind)] with HF's names (`pf`: the base model's prefix); kind "conv": a conv kernel kept as [C_out][kernel][C_in],
+    "g": the weight norm's magnitudes."""
     H = c["hidden_size"]
-    spec = [("wav2vec2.masked_spec_embed", (H,), None)]
-    fe = "wav2vec2.feature_extractor.conv_layers."
+    spec = [(pf + "masked_spec_embed", (H,), None)]
+    fe = pf + "feature_extractor.conv_layers."
     cin = 1
     for i, (co, k) in enumerate(zip(c["conv_dim"], c["conv_kernel"])):
         spec.append((f"{fe}{i}.conv.weight", (co, k, cin), "conv"))
@@ -111,16 +114,16 @@ def param_spec(c):
         if i == 0 or c.get("feat_extract_norm", "group") == "layer":
             spec += [(f"{fe}{i}.layer_norm.weight", (co,), None), (f"{fe}{i}.layer_norm.bias", (co,), None)]
         cin = co
-    fp = "wav2vec2.feature_projection."
+    fp = pf + "feature_projection."
     spec += [(fp + "layer_norm.weight", (cin,), None), (fp + "layer_norm.bias", (cin,), None),
              (fp + "projection.weight", (H, cin), None), (fp + "projection.bias", (H,), None)]
-    pc = "wav2vec2.encoder.pos_conv_embed.conv."
+    pc = pf + "encoder.pos_conv_embed.conv."
     K, G = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
     spec += [(pc + "bias", (H,), None), (pc + "parametrizations.weight.original0", (K,), "g"),
              (pc + "parametrizations.weight.original1", (H, K, H // G), "conv")]
-    spec += [("wav2vec2.encoder.layer_norm.weight", (H,), None), ("wav2vec2.encoder.layer_norm.bias", (H,), None)]
+    spec += [(pf + "encoder.layer_norm.weight", (H,), None), (pf + "encoder.layer_norm.bias", (H,), None)]
     for l in range(c["num_hidden_layers"]):
-        p = f"wav2vec2.encoder.layers.{l}."
+        p = f"{pf}encoder.layers.{l}."
         # q | k | v weights side by side in the flat buffers (then their biases): one [3H, H] projection instead of three launches
         spec += [(p + f"attention.{n}.weight", (H, H), None) for n in ("q_proj", "k_proj", "v_proj")]
         spec += [(p + f"attention.{n}.bias", (H,), None) for n in ("q_proj", "k_proj", "v_proj")]
@@ -137,17 +140,22 @@ def param_spec(c):
 
 class Wav2Vec2ForCTC(FlatModel):
     _input = "input_values"
+    # what a model of the same family (wavlm_model.WavLMForCTC) replaces: the base model's parameter prefix, its configuration reader and
+    # parameter list, and the two attention hooks _softmax / _softmax_bwd
+    _prefix = "wav2vec2."
+    _make_config = staticmethod(make_config)
+    _param_spec = staticmethod(param_spec)
 
     def __init__(self, config=None, device="cuda:0"):
-        self.cfg = make_config(config)
-        c = self.cfg
+        self.cfg = self._make_config(config)
+        c, pf = self.cfg, self._prefix
         H = c["hidden_size"]
         assert H % 256 == 0 and c["conv_dim"][-1] % 256 == 0, "LayerNorm kernels need C % 256 == 0"
         self.layer_extractor = c["feat_extract_norm"] == "layer"
         self.stable_ln = c["do_stable_layer_norm"]
         if self.layer_extractor and any(d % 256 for d in c["conv_dim"]):
             raise ops.DynError(f"feat_extract_norm=\"layer\" needs every conv_dim to be a multiple of 256 (got {c['conv_dim']})")
-        spec = param_spec(c)
+        spec = self._param_spec(c, pf)
         super().__init__([(n, shape) for n, shape, _ in spec], device)
         slots = self._slots
         self._kind = {n: kind for n, _, kind in spec}
@@ -156,10 +164,10 @@ class Wav2Vec2ForCTC(FlatModel):
         self.Pqkv, self.Gqkv = [], []
         if self.packed_qkv:
             for l in range(c["num_hidden_layers"]):
-                ow = slots[f"wav2vec2.encoder.layers.{l}.attention.q_proj.weight"][0]
-                ob = slots[f"wav2vec2.encoder.layers.{l}.attention.q_proj.bias"][0]
-                assert slots[f"wav2vec2.encoder.layers.{l}.attention.v_proj.weight"][0] == ow + 2 * H * H
-                assert slots[f"wav2vec2.encoder.layers.{l}.attention.v_proj.bias"][0] == ob + 2 * H
+                ow = slots[f"{pf}encoder.layers.{l}.attention.q_proj.weight"][0]
+                ob = slots[f"{pf}encoder.layers.{l}.attention.q_proj.bias"][0]
+                assert slots[f"{pf}encoder.layers.{l}.attention.v_proj.weight"][0] == ow + 2 * H * H
+                assert slots[f"{pf}encoder.layers.{l}.attention.v_proj.bias"][0] == ob + 2 * H
                 self.Pqkv.append((self.flat_params[ow:ow + 3 * H * H].view(3 * H, H), self.flat_params[ob:ob + 3 * H]))
                 self.Gqkv.append((self.flat_grads[ow:ow + 3 * H * H].view(3 * H, H), self.flat_grads[ob:ob + 3 * H]))
         self.config = SimpleNamespace(**c)
@@ -187,6 +195,8 @@ class Wav2Vec2ForCTC(FlatModel):
             return _conv_to_hf(t)
         if kind == "g":
             return t.reshape(1, 1, -1)
+        if kind == "heads":
+            return t.reshape(1, -1, 1, 1)
         return t
 
     def state_dict(self):
@@ -247,7 +257,9 @@ class Wav2Vec2ForCTC(FlatModel):
         layer-norm extractor they do not (the conv bias and the LayerNorm's beta put finite non-zero values there, the stable encoder's
         LayerNorms likewise): nothing reads them — the statistics of that layout are per row (no ops.colnorm, `_valid[0]` unused),
         dyn_mask_rows zeroes them before the positional conv and the masked softmax drops them as keys — and their gradients are
-        still exactly zero because every op that layout adds is per row (tests/test_wav2vec2_layernorm_gpu.py)."""
+        still exactly zero because every op that layout adds is per row (tests/test_wav2vec2_layernorm_gpu.py).
+        WavLM's attention bias (wavlm_model.py) keeps the argument: a padded query row has dS = 0 (CTC), so its gate gradient, its terms of
+        the bias table's gradient and its terms of the gate's input gradient are exact zeros (tests/test_wavlm_gpu.py)."""
         x = input_values
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
             raise ops.DynError("input_values must be a float32 CUDA tensor [B, L]")
@@ -323,7 +335,7 @@ class Wav2Vec2ForCTC(FlatModel):
         return SimpleNamespace(logits=ent["out"], frames=T)
 
     def _forward_eager(self, x):
-        c, P = self.cfg, self.P
+        c, P, pf = self.cfg, self.P, self._prefix
         vl = self._vl
         v0 = vl[0:1] if vl is not None else None             # valid frames after the first conv (its GroupNorm runs over time)
         vT = vl[-1:] if vl is not None else None             # valid frames of the encoder
@@ -335,7 +347,7 @@ class Wav2Vec2ForCTC(FlatModel):
             need = (need - 1) * st + k
         if L < need:
             raise ops.DynError(f"input of {L} samples is shorter than the feature extractor's receptive field ({need} samples)")
-        fe = "wav2vec2.feature_extractor.conv_layers."
+        fe = pf + "feature_extractor.conv_layers."
         a = x.contiguous().view(B, L, 1)
         for i, (k, s) in enumerate(zip(c["conv_kernel"], c["conv_stride"])):
             w = P[f"{fe}{i}.conv.weight"]
@@ -356,7 +368,7 @@ class Wav2Vec2ForCTC(FlatModel):
                     ctx["conv"].append((a, z, None))
             a = act
         T = a.shape[1]
-        fp = "wav2vec2.feature_projection."
+        fp = pf + "feature_projection."
         n, mean, rstd = ops.layernorm(a, P[fp + "layer_norm.weight"], P[fp + "layer_norm.bias"], c["layer_norm_eps"])
         h = ops.linear(n, P[fp + "projection.weight"], P[fp + "projection.bias"])
         if vT is not None:
@@ -364,7 +376,7 @@ class Wav2Vec2ForCTC(FlatModel):
         if save:
             ctx["proj"] = (a, mean, rstd, n)
         # positional conv embedding (grouped, weight-normed), GELU, residual, LayerNorm
-        pc = "wav2vec2.encoder.pos_conv_embed.conv."
+        pc = pf + "encoder.pos_conv_embed.conv."
         H, K, G = c["hidden_size"], c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
         cg, pad = H // G, K // 2
         v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
@@ -381,13 +393,13 @@ class Wav2Vec2ForCTC(FlatModel):
         ops.axpby(pos, hs, 1.0, 1.0)
         if self.stable_ln:
             return self._encoder_stable(hs, ctx, (xg, w, pre), vT, (B, L, T), v0)
-        h2, mean, rstd = ops.layernorm(hs, P["wav2vec2.encoder.layer_norm.weight"], P["wav2vec2.encoder.layer_norm.bias"], c["layer_norm_eps"])
+        h2, mean, rstd = ops.layernorm(hs, P[pf + "encoder.layer_norm.weight"], P[pf + "encoder.layer_norm.bias"], c["layer_norm_eps"])
         if save:
             ctx["pos"] = (xg, w, pre, hs, mean, rstd)
             ctx["layers"] = []
         h = h2
         for l in range(c["num_hidden_layers"]):
-            p = f"wav2vec2.encoder.layers.{l}."
+            p = f"{pf}encoder.layers.{l}."
             qkv, S, O = self._attention(h, l, vT)
             r1 = h.clone() if save else h
             ops.linear(O, P[p + "attention.out_proj.weight"], P[p + "attention.out_proj.bias"], out=r1, beta=1.0)
@@ -410,11 +422,11 @@ class Wav2Vec2ForCTC(FlatModel):
 
     def _attention(self, h, l, vT):
         """Self-attention of layer l on h [B, T, H] up to (not including) the output projection: returns (qkv, S, O)."""
-        c, P = self.cfg, self.P
+        c, P, pf = self.cfg, self.P, self._prefix
         B, T, H = h.shape
         nh = c["num_attention_heads"]
         D = H // nh
-        p = f"wav2vec2.encoder.layers.{l}."
+        p = f"{pf}encoder.layers.{l}."
         qkv = torch.empty(B, T, 3 * H, device=h.device, dtype=torch.float32)
         if self.packed_qkv:
             ops.linear(h, self.Pqkv[l][0], self.Pqkv[l][1], out=qkv)
@@ -424,23 +436,34 @@ class Wav2Vec2ForCTC(FlatModel):
         S = torch.empty(B, nh, T, T, device=h.device, dtype=torch.float32)
         ops.gemm(qkv, qkv, S, trans_b=True, M=T, N=T, K=D, lda=3 * H, ldb=3 * H, ldc=T, nb1=B, nb2=nh,
                  sa=(T * 3 * H, D), sb=(T * 3 * H, D), sc=(nh * T * T, T * T), b_off=H, alpha=D ** -0.5)
-        ops.softmax(S, out=S, valid=vT)
+        kept = self._softmax(S, h, l, vT)
         O = torch.empty(B, T, H, device=h.device, dtype=torch.float32)
         ops.gemm(S, qkv, O, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=H, nb1=B, nb2=nh, sa=(nh * T * T, T * T),
                  sb=(T * 3 * H, D), sc=(T * H, D), b_off=2 * H)
-        return qkv, S, O
+        return qkv, (S if kept is None else (S,) + tuple(kept)), O
+
+    def _softmax(self, S, h, l, vT):
+        """The scores S [B, nh, T, T] of layer l -> probabilities, in place (keys past `vT` masked).  `h` is the attention's input: a model whose
+        scores depend on it beyond q k^T (WavLM) overrides this together with _softmax_bwd and returns the tensors its backward needs; they
+        travel with S through the saved context (batch-major, so an `n_active` backward cuts them like every other activation)."""
+        ops.softmax(S, out=S, valid=vT)
+        return None
+
+    def _softmax_bwd(self, dS, kept, h, l, dh):
+        """After _attention_bwd: dS is the gradient w.r.t. the pre-softmax scores, `kept` what _softmax returned, dh the gradient of the
+        attention's input, to be added to in place.  Nothing here."""
 
     def _encoder_stable(self, x, ctx, pos, vT, dims, v0):
         """The pre-LN encoder (transformers Wav2Vec2EncoderStableLayerNorm) from x = h + gelu(pos_conv(h)): per layer
         x = x + out_proj(attn(LN1(x))), x = x + ffn(LN2(x)); the encoder's LayerNorm after the last layer; lm_head."""
-        c, P = self.cfg, self.P
+        c, P, pf = self.cfg, self.P, self._prefix
         save = ctx is not None
         eps = c["layer_norm_eps"]
         if save:
             ctx["pos"] = pos + (None, None, None)
             ctx["layers"] = []
         for l in range(c["num_hidden_layers"]):
-            p = f"wav2vec2.encoder.layers.{l}."
+            p = f"{pf}encoder.layers.{l}."
             n1, m1, s1 = ops.layernorm(x, P[p + "layer_norm.weight"], P[p + "layer_norm.bias"], eps)
             qkv, S, O = self._attention(n1, l, vT)
             r1 = x.clone() if save else x
@@ -453,7 +476,7 @@ class Wav2Vec2ForCTC(FlatModel):
             if save:
                 ctx["layers"].append((x, m1, s1, n1, qkv, S, O, r1, m2, s2, n2, u, ga))
             x = r2
-        h, mean, rstd = ops.layernorm(x, P["wav2vec2.encoder.layer_norm.weight"], P["wav2vec2.encoder.layer_norm.bias"], eps)
+        h, mean, rstd = ops.layernorm(x, P[pf + "encoder.layer_norm.weight"], P[pf + "encoder.layer_norm.bias"], eps)
         logits = ops.linear(h, P["lm_head.weight"], P["lm_head.bias"])
         if save:
             ctx["final"] = (x, mean, rstd)
@@ -466,10 +489,11 @@ class Wav2Vec2ForCTC(FlatModel):
     def _attention_bwd(self, dO, qkv, S, h, l, nb, T, residual):
         """Backward of _attention: queues / accumulates the q | k | v weight gradients and returns d h (+ `residual` when given, out of
         place: it may be a queued operand)."""
-        c, P, G = self.cfg, self.P, self.G
+        c, P, G, pf = self.cfg, self.P, self.G, self._prefix
         H, nh = c["hidden_size"], c["num_attention_heads"]
         D = H // nh
-        p = f"wav2vec2.encoder.layers.{l}."
+        p = f"{pf}encoder.layers.{l}."
+        S, kept = (S[0], S[1:]) if isinstance(S, tuple) else (S, None)
         dqkv = torch.empty_like(qkv)
         sS, sQ, sO = (nh * T * T, T * T), (T * 3 * H, D), (T * H, D)
         ops.gemm(S, dO, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sO, sc=sQ, c_off=2 * H)
@@ -498,6 +522,8 @@ class Wav2Vec2ForCTC(FlatModel):
             dj = dqkv.view(M, 3, H)[:, j, :].contiguous()
             ops.colsum(dj, G[p + f"attention.{nm}.bias"], beta=1.0)
             ops.gemm(dqkv, P[p + f"attention.{nm}.weight"], dh_in, M=M, N=H, K=H, lda=3 * H, ldb=H, ldc=H, a_off=j * H, beta=1.0)
+        if kept is not None:
+            self._softmax_bwd(dP, kept, h, l, dh_in)
         return dh_in
 
     # ------------------------------------------------------------------ backward
@@ -568,7 +594,7 @@ class Wav2Vec2ForCTC(FlatModel):
             ctx = dict(ctx)
             ctx["layers"], ctx["conv"] = list(ctx["layers"]), list(ctx["conv"])
         v0, vT = ctx["valid"]
-        c, P, G = self.cfg, self.P, self.G
+        c, P, G, pf = self.cfg, self.P, self.G, self._prefix
         B, L, T = ctx["dims"]
         nb = B if n_active is None else int(n_active)
         assert grad_logits.shape[0] == nb
@@ -590,12 +616,12 @@ class Wav2Vec2ForCTC(FlatModel):
         if self.stable_ln:
             x, mean, rstd = cut(ctx["final"])
             dx = torch.empty_like(dh)
-            ops.layernorm_bwd(x, P["wav2vec2.encoder.layer_norm.weight"], mean, rstd, dh, dx, G["wav2vec2.encoder.layer_norm.weight"],
-                              G["wav2vec2.encoder.layer_norm.bias"], dx_beta=0.0)
+            ops.layernorm_bwd(x, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dx, G[pf + "encoder.layer_norm.weight"],
+                              G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
         for l in reversed(range(c["num_hidden_layers"]) if self.stable_ln else ()):
             # x -> r1 = x + out_proj(attn(LN1(x))) -> r2 = r1 + ffn(LN2(r1)); dx is dL/dr2.  Each residual sum rides on the LayerNorm
             # backward's dx = grad + dx_in form (out of place: dx / dr1 are queued weight-gradient operands), so no add pass of its own.
-            p = f"wav2vec2.encoder.layers.{l}."
+            p = f"{pf}encoder.layers.{l}."
             x, m1, s1, n1, qkv, S, O, r1, m2, s2, n2, u, ga = cut(ctx["layers"][l])
             dga = self._lin_bwd(dx, ga, p + "feed_forward.output_dense.weight", p + "feed_forward.output_dense.bias")
             du = ops.gelu_bwd(u, dga, out=dga)
@@ -610,7 +636,7 @@ class Wav2Vec2ForCTC(FlatModel):
                               dx_beta=1.0, dx_in=dr1)
             ctx["layers"][l] = None
         for l in reversed(() if self.stable_ln else range(c["num_hidden_layers"])):
-            p = f"wav2vec2.encoder.layers.{l}."
+            p = f"{pf}encoder.layers.{l}."
             h, qkv, S, O, r1, m1, s1, h1, u, ga, r2, m2, s2 = cut(ctx["layers"][l])
             dr2 = torch.empty_like(dh)
             ops.layernorm_bwd(r2, P[p + "final_layer_norm.weight"], m2, s2, dh, dr2, G[p + "final_layer_norm.weight"],
@@ -629,7 +655,7 @@ class Wav2Vec2ForCTC(FlatModel):
         # encoder LayerNorm, positional conv
         w = ctx["pos"][1]                                            # the normalised weight is not batch-indexed
         xg, _, pre, hs, mean, rstd = cut(ctx["pos"])
-        pc = "wav2vec2.encoder.pos_conv_embed.conv."
+        pc = pf + "encoder.pos_conv_embed.conv."
         K, Gn = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
         cg, pad = H // Gn, K // 2
         Tp = T + 2 * pad
@@ -637,8 +663,8 @@ class Wav2Vec2ForCTC(FlatModel):
             dhs = dx                                                 # dL/d(h + pos): no queued product reads it, so the pos path adds in place
         else:
             dhs = torch.empty_like(dh)
-            ops.layernorm_bwd(hs, P["wav2vec2.encoder.layer_norm.weight"], mean, rstd, dh, dhs, G["wav2vec2.encoder.layer_norm.weight"],
-                              G["wav2vec2.encoder.layer_norm.bias"], dx_beta=0.0)
+            ops.layernorm_bwd(hs, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dhs, G[pf + "encoder.layer_norm.weight"],
+                              G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
         dpre = ops.gelu_bwd(pre, dhs)
         ops.colsum(dpre, G[pc + "bias"], beta=1.0)
         dyg = ops.group_pack_grad(dpre, Gn, T)                       # [nb, G, T, cg]
@@ -666,12 +692,12 @@ class Wav2Vec2ForCTC(FlatModel):
             ops.mask_rows(dhs, vT)                                   # the windows of the last valid frames reach into the zeroed tail: no gradient there
         # feature projection
         a, mean, rstd, n = cut(ctx["proj"])
-        fp = "wav2vec2.feature_projection."
+        fp = pf + "feature_projection."
         dn = self._lin_bwd(dhs, n, fp + "projection.weight", fp + "projection.bias")
         da = torch.empty_like(dn)
         ops.layernorm_bwd(a, P[fp + "layer_norm.weight"], mean, rstd, dn, da, G[fp + "layer_norm.weight"], G[fp + "layer_norm.bias"], dx_beta=0.0)
         # conv feature extractor
-        fe = "wav2vec2.feature_extractor.conv_layers."
+        fe = pf + "feature_extractor.conv_layers."
         for i in reversed(range(len(c["conv_kernel"]))):
             k, s = c["conv_kernel"][i], c["conv_stride"][i]
             a_in, z, norm = cut(ctx["conv"][i])

@@ -580,6 +580,47 @@ int dyn_weight_norm_bwd(const float* v, const float* g, const float* dw, float* 
                         int64_t kw, int64_t cg, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * WavLM attention: gated relative-position bias.  The reference's loader, `AutoModelForCTC.from_pretrained(checkpoint)`
+ * (wav2vec2/lib.py:20-23), builds transformers' WavLMForCTC for a WavLM checkpoint; `model(x).logits` (:163,413) and
+ * `loss.backward()` (:194,437) then run WavLMAttention.forward (modeling_wavlm.py) in every layer.  With h [B, T, H] the attention's
+ * input, nh heads of D = H / nh channels, E = rel_attn_embed.weight [num_buckets, nh] (layer 0's, used by every layer) and
+ * bucket[d + Tmax - 1] the int32 table of _relative_positions_bucket(d), d in (-Tmax, Tmax), built ON THE HOST (it depends on a
+ * float32 log; a kernel's rounding at a bucket edge would be a wrong bucket) and resident in device memory:
+ *   dyn_relpos_gate_fwd          steps 1-3 of WavLMAttention.forward (`gru_rel_pos_linear`, `.view(.., 2, 4).sum(-1)`, sigmoid,
+ *                                `gate_a * (gate_b * gru_rel_pos_const - 1.0) + 2.0`): p = W h[b, t, head*D:(head+1)*D] + bias
+ *                                (W [8, D], bias [8]), a = sigmoid(p0+p1+p2+p3), c = sigmoid(p4+p5+p6+p7),
+ *                                gate = a * (c * konst[head] - 1) + 2; gate, a, c are [B, nh, T].  One pass over h.
+ *   dyn_softmax_relbias_fwd_len  compute_bias + step 4 + the softmax inside F.multi_head_attention_forward:
+ *                                y[b,head,t,:] = softmax_s(x[b,head,t,s] + gate[b,head,t] * E[bucket[s - t + Tmax - 1], head]);
+ *                                x = scale * q k^T [B, nh, T, T], y may be x.  `valid_cols` as dyn_softmax_fwd_len (device int32
+ *                                scalar read when the kernel runs; columns >= it are outside max / sum and get probability 0);
+ *                                NULL = all T columns.  T <= 16384; num_buckets even and <= 1024; T <= Tmax.
+ *   dyn_relbias_bwd              autograd of the bias term from dS [B, nh, T, T], the gradient w.r.t. the pre-softmax sum (what
+ *                                dyn_softmax_bwd leaves): dgate[b,head,t] = sum_s dS[b,head,t,s] * E[bucket(s-t), head] and
+ *                                dE[k, head] = beta * dE[k, head] + sum_{b,t,s: bucket(s-t) = k} gate[b,head,t] * dS[b,head,t,s].
+ *                                No float atomics: row blocks sum the diagonals of gate (.) dS in row order into per-distance
+ *                                vectors (workspace), a second kernel adds them over (b, row block) in index order, a third folds
+ *                                the 2T-1 distances into buckets in distance order.  Bit-reproducible.  T <= 8192.
+ *   dyn_relpos_gate_bwd          autograd of dyn_relpos_gate_fwd: dh = beta_dh * dh + (d gate / d h) dgate (the attention's input
+ *                                gradient, accumulated), dW [8, D], dbias [8], dkonst [nh] each = beta * old + sum, through
+ *                                per-workgroup partial rows in `workspace` summed in index order.  D <= 256.
+ * All four take the attention's (B, T, H, nh): null pointer, H % nh != 0, D % 4 != 0, odd or too large num_buckets, T beyond the row limit -> DYN_E_ARG before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int dyn_relpos_gate_fwd(const float* h, const float* W, const float* bias, const float* konst, float* gate, float* a, float* c,
+                        int64_t B, int64_t T, int64_t H, int64_t nh, void* stream);
+int dyn_softmax_relbias_fwd_len(const float* x, float* y, const float* gate, const float* E, const int32_t* bucket, int64_t B,
+                                int64_t T, int64_t H, int64_t nh, int64_t Tmax, int64_t num_buckets, const int32_t* valid_cols,
+                                void* stream);
+int64_t dyn_relbias_bwd_workspace_bytes(int64_t B, int64_t nh, int64_t T, int64_t num_buckets);
+int dyn_relbias_bwd(const float* dS, const float* gate, const float* E, const int32_t* bucket, float* dgate, float* dE, float beta,
+                    int64_t B, int64_t T, int64_t H, int64_t nh, int64_t Tmax, int64_t num_buckets, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+int64_t dyn_relpos_gate_bwd_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t nh);
+int dyn_relpos_gate_bwd(const float* dgate, const float* a, const float* c, const float* h, const float* W, const float* konst,
+                        float* dh, float beta_dh, float* dW, float* dbias, float* dkonst, float beta, int64_t B, int64_t T, int64_t H,
+                        int64_t nh, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Soft-DTW — replaces the reference's Numba CUDA kernels compute_softdtw_cuda / compute_softdtw_backward_cuda
  * (reference wav2vec2/soft_dtw_cuda.py:33-111), their autograd wrapper (:114-175) and _euclidean_dist_func (:319-329).
  *   dyn_sqdist       D[b,i,j] = sum_k (x[b,i,k] - y[b,j,k])^2            x [B,N,d], y [B,M,d] -> D [B,N,M]
