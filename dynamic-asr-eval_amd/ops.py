@@ -762,6 +762,94 @@ def relbias_bwd(dS, gate, E, table, D, dE, beta=1.0):
     return dgate
 
 
+# ----------------------------------------------------------------------------------------------- Wav2Vec2-Conformer relative positions
+def relative_position_table(T, H):
+    """float32 CPU table [2 T - 1, H]: row k is the sinusoid of relative position T - 1 - k (positive ones first, reversed), what
+    transformers' Wav2Vec2ConformerRelPositionalEmbedding returns for T frames.  Its own torch expressions, evaluated on the host: every
+    entry depends on its position alone, so the slice transformers cuts out of a longer table (max_source_positions) holds the same floats."""
+    import math
+    pe_positive = torch.zeros(T, H)
+    pe_negative = torch.zeros(T, H)
+    position = torch.arange(0, T, dtype=torch.int64).float().unsqueeze(1)
+    div_term = torch.exp(torch.arange(0, H, 2, dtype=torch.int64).float() * -(math.log(10000.0) / H))
+    pe_positive[:, 0::2] = torch.sin(position * div_term)
+    pe_positive[:, 1::2] = torch.cos(position * div_term)
+    pe_negative[:, 0::2] = torch.sin(-1 * position * div_term)
+    pe_negative[:, 1::2] = torch.cos(-1 * position * div_term)
+    return torch.cat([torch.flip(pe_positive, [0]), pe_negative[1:]], dim=0).contiguous()
+
+
+def rotary_tables(T, D, base):
+    """(cos, sin) float32 CPU tables [T, D / 2] of transformers' Wav2Vec2ConformerRotaryPositionalEmbedding (the first half of its
+    cat((freqs, freqs)) tables: ops.rotary's half-split convention), its own torch expressions on the host."""
+    inv_freq = 1.0 / (base ** (torch.arange(0, D, 2, dtype=torch.int64).float() / D))
+    freqs = torch.einsum("i,j->ij", torch.arange(T).type_as(inv_freq), inv_freq)
+    return freqs.cos().contiguous(), freqs.sin().contiguous()
+
+
+def _relshift_dims(who, S, ld_bd):
+    if S.dim() != 4 or S.shape[2] != S.shape[3]:
+        raise DynError(f"{who}: scores must be [B, heads, T, T], got {tuple(S.shape)}")
+    T = S.shape[-1]
+    ld = 2 * T - 1 if ld_bd is None else int(ld_bd)
+    return S.shape[0] * S.shape[1], T, ld
+
+
+def softmax_relshift(S, BD, out=None, valid=None, ld_bd=None):
+    """softmax over the keys of S [B, nh, T, T] + BD[b, h, i, T - 1 - i + j] (BD [B, nh, T, ld_bd >= 2T - 1], both scaled already: the
+    Transformer-XL shift read in place); `valid` as in softmax().  `out` may be S."""
+    _cc(S, "softmax_relshift.S"); _c(BD, "softmax_relshift.BD")
+    M, T, ld = _relshift_dims("softmax_relshift", S, ld_bd)
+    if BD.numel() != M * T * ld:
+        raise DynError(f"softmax_relshift: BD holds {BD.numel()} floats, {M} x {T} x {ld} expected")
+    out = torch.empty_like(S) if out is None else _cc(out, "softmax_relshift.out")
+    check(_L().dyn_softmax_relshift_fwd_len(S.data_ptr(), out.data_ptr(), BD.data_ptr(), M, T, ld, _valid_ptr(valid, "softmax_relshift"),
+                                            _stream()), "dyn_softmax_relshift_fwd_len")
+    return out
+
+
+def relshift_bwd(dS, out=None, ld_bd=None):
+    """dBD [B, nh, T, ld_bd] from dS [B, nh, T, T]: dS in every row's window, zeros written everywhere else (`out` may be stale scratch)."""
+    _cc(dS, "relshift_bwd.dS")
+    M, T, ld = _relshift_dims("relshift_bwd", dS, ld_bd)
+    if out is None:
+        out = torch.empty(*dS.shape[:3], ld, device=dS.device, dtype=F32)
+    elif _c(out, "relshift_bwd.out").numel() != M * T * ld:
+        raise DynError(f"relshift_bwd: out holds {out.numel()} floats, {M} x {T} x {ld} expected")
+    check(_L().dyn_relshift_bwd(dS.data_ptr(), out.data_ptr(), M, T, ld, _stream()), "dyn_relshift_bwd")
+    return out
+
+
+def head_bias_add(q, u, v, H=None, ldq=None, q_off=0):
+    """q [rows, H] inside a packed projection output (row stride `ldq` floats, first column `q_off`) + the per-head biases u, v [nh, D]
+    -> (q + u, q + v), each [..., H] contiguous; q is read once."""
+    _chk(q, "head_bias_add.q"); _cc(u, "head_bias_add.u"); _cc(v, "head_bias_add.v")
+    H = u.numel() if H is None else H
+    ldq = q.shape[-1] if ldq is None else ldq
+    if not q.is_contiguous() or u.numel() != H or v.numel() != H or q.numel() % ldq or q_off + H > ldq:
+        raise DynError("head_bias_add: operand shapes do not match")
+    rows = q.numel() // ldq
+    qu = torch.empty(*q.shape[:-1], H, device=q.device, dtype=F32)
+    qv = torch.empty_like(qu)
+    check(_L().dyn_head_bias_add(q.data_ptr() + 4 * q_off, ldq, u.data_ptr(), v.data_ptr(), qu.data_ptr(), qv.data_ptr(), rows, H, _stream()),
+          "dyn_head_bias_add")
+    return qu, qv
+
+
+def head_bias_bwd(dqu, dqv, dq, du, dv, beta=1.0, ldq=None, q_off=0):
+    """Backward of head_bias_add: dq (strided like q) = dqu + dqv; du = beta * du + column sums of dqu, dv likewise (fixed order)."""
+    _cc(dqu, "head_bias_bwd.dqu"); _cc(dqv, "head_bias_bwd.dqv"); _c(dq, "head_bias_bwd.dq"); _cc(du, "head_bias_bwd.du"); _cc(dv, "head_bias_bwd.dv")
+    H = du.numel()
+    ldq = dq.shape[-1] if ldq is None else ldq
+    rows = dqu.numel() // H
+    if dqv.shape != dqu.shape or dv.numel() != H or dqu.numel() != rows * H or dq.numel() != rows * ldq or q_off + H > ldq:
+        raise DynError("head_bias_bwd: operand shapes do not match")
+    ws = workspace(dqu.device)
+    check(_L().dyn_head_bias_bwd(dqu.data_ptr(), dqv.data_ptr(), dq.data_ptr() + 4 * q_off, ldq, du.data_ptr(), dv.data_ptr(), beta, rows, H,
+                                 ws.data_ptr(), ws.numel(), _stream()), "dyn_head_bias_bwd")
+    return dq
+
+
 def log_softmax(x, out=None):
     _cc(x, "log_softmax.x")
     rows, L = _rows_L(x)

@@ -23,7 +23,7 @@ import torch
 from . import wav2vec2_lib as lib
 from .datasets import fetch_utterances_from_lines, synthetic_text, synthetic_waveform
 from .decoding import GreedyCTCDecoder
-from . import wavlm_model
+from . import wav2vec2_conformer_model, wavlm_model
 from .wav2vec2_model import Wav2Vec2ForCTC, config_from_json
 from .wer import basic_normalize as normalize, word_error_rate_detail
 
@@ -77,6 +77,8 @@ def replicate(model, n):
     for _ in range(max(0, n - 1)):
         m = type(model)(model.cfg, device=model.device)
         m.flat_params.copy_(model.flat_params)
+        if hasattr(model, 'buffers_'):                           # the conformer's batch-norm statistics live outside the flat vector
+            m.copy_buffers_from(model)
         m.frozen = set(model.frozen)
         m.bucket_frames, m.graph_after, m.graph_budget_bytes = model.bucket_frames, model.graph_after, model.graph_budget_bytes
         out.append(m.eval())
@@ -95,12 +97,16 @@ def load_pretrained_model(args, device):
     """reference wav2vec2/lib.py:20-23 (`AutoModelForCTC.from_pretrained(checkpoint)`) — offline: `-c DIR` is a local HF model directory
     (`config.json` read as plain JSON for the architecture and the layout flags + `pytorch_model.bin`), `-c FILE` a bare state_dict at the
     base-960h architecture or at `--config PATH.json`; without a checkpoint: seeded weights at that architecture.  A config.json whose
-    `model_type` is "wavlm" builds WavLMForCTC (wavlm_model.py), under `-c DIR` and under `--config` alike; anything else Wav2Vec2ForCTC."""
+    `model_type` is "wavlm" builds WavLMForCTC (wavlm_model.py), "wav2vec2-conformer" Wav2Vec2ConformerForCTC (wav2vec2_conformer_model.py),
+    under `-c DIR` and under `--config` alike; anything else Wav2Vec2ForCTC."""
     cfg_path, ckpt = getattr(args, 'config', '') or '', args.checkpoint
     if ckpt and os.path.isdir(ckpt):
         cfg_path, ckpt = cfg_path or os.path.join(ckpt, 'config.json'), os.path.join(ckpt, 'pytorch_model.bin')
-    if cfg_path and model_type(cfg_path) == 'wavlm':        # what AutoModelForCTC dispatches on
+    kind = model_type(cfg_path) if cfg_path else ''         # what AutoModelForCTC dispatches on
+    if kind == 'wavlm':
         model = wavlm_model.WavLMForCTC(wavlm_model.config_from_json(cfg_path), device=device)
+    elif kind == 'wav2vec2-conformer':
+        model = wav2vec2_conformer_model.Wav2Vec2ConformerForCTC(wav2vec2_conformer_model.config_from_json(cfg_path), device=device)
     else:
         model = Wav2Vec2ForCTC(config_from_json(cfg_path) if cfg_path else None, device=device)
     if ckpt:

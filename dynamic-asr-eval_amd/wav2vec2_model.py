@@ -141,8 +141,10 @@ def param_spec(c, pf="wav2vec2."):
 class Wav2Vec2ForCTC(FlatModel):
     _input = "input_values"
     # what a model of the same family (wavlm_model.WavLMForCTC) replaces: the base model's parameter prefix, its configuration reader and
-    # parameter list, and the two attention hooks _softmax / _softmax_bwd
+    # parameter list, and the two attention hooks _softmax / _softmax_bwd; a model with another encoder (wav2vec2_conformer_model) also the
+    # names of the q | k | v projections inside a layer and the two encoder hooks _encode / _backward_encoder
     _prefix = "wav2vec2."
+    _qkv_fmt = "attention.{}_proj"
     _make_config = staticmethod(make_config)
     _param_spec = staticmethod(param_spec)
 
@@ -163,11 +165,12 @@ class Wav2Vec2ForCTC(FlatModel):
         self.packed_qkv = H % 64 == 0
         self.Pqkv, self.Gqkv = [], []
         if self.packed_qkv:
+            q, v = self._qkv_fmt.format("q"), self._qkv_fmt.format("v")
             for l in range(c["num_hidden_layers"]):
-                ow = slots[f"{pf}encoder.layers.{l}.attention.q_proj.weight"][0]
-                ob = slots[f"{pf}encoder.layers.{l}.attention.q_proj.bias"][0]
-                assert slots[f"{pf}encoder.layers.{l}.attention.v_proj.weight"][0] == ow + 2 * H * H
-                assert slots[f"{pf}encoder.layers.{l}.attention.v_proj.bias"][0] == ob + 2 * H
+                ow = slots[f"{pf}encoder.layers.{l}.{q}.weight"][0]
+                ob = slots[f"{pf}encoder.layers.{l}.{q}.bias"][0]
+                assert slots[f"{pf}encoder.layers.{l}.{v}.weight"][0] == ow + 2 * H * H
+                assert slots[f"{pf}encoder.layers.{l}.{v}.bias"][0] == ob + 2 * H
                 self.Pqkv.append((self.flat_params[ow:ow + 3 * H * H].view(3 * H, H), self.flat_params[ob:ob + 3 * H]))
                 self.Gqkv.append((self.flat_grads[ow:ow + 3 * H * H].view(3 * H, H), self.flat_grads[ob:ob + 3 * H]))
         self.config = SimpleNamespace(**c)
@@ -375,6 +378,15 @@ class Wav2Vec2ForCTC(FlatModel):
             ops.mask_rows(h, vT)                                    # the positional conv must see zeros past the utterance's last frame
         if save:
             ctx["proj"] = (a, mean, rstd, n)
+        return self._encode(h, ctx, vT, (B, L, T), v0)
+
+    def _encode(self, h, ctx, vT, dims, v0):
+        """The encoder and lm_head from the feature projection's output h [B, T, H] (rows past `vT` zeroed): fills ctx["pos"], ["layers"],
+        ["head"], ["dims"], ["valid"] (+ ["final"] in the stable-LN layout) for _backward_encoder, sets self._ctx.  A model of the family
+        with another encoder (wav2vec2_conformer_model.py) overrides this together with _backward_encoder."""
+        c, P, pf = self.cfg, self.P, self._prefix
+        save = ctx is not None
+        B, L, T = dims
         # positional conv embedding (grouped, weight-normed), GELU, residual, LayerNorm
         pc = pf + "encoder.pos_conv_embed.conv."
         H, K, G = c["hidden_size"], c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
@@ -608,6 +620,45 @@ class Wav2Vec2ForCTC(FlatModel):
                 return t[:nb * (t.shape[0] // B)]
             return t[:nb]
 
+        dhs = self._backward_encoder(ctx, grad_logits, nb, cut)
+        # feature projection
+        a, mean, rstd, n = cut(ctx["proj"])
+        fp = pf + "feature_projection."
+        dn = self._lin_bwd(dhs, n, fp + "projection.weight", fp + "projection.bias")
+        da = torch.empty_like(dn)
+        ops.layernorm_bwd(a, P[fp + "layer_norm.weight"], mean, rstd, dn, da, G[fp + "layer_norm.weight"], G[fp + "layer_norm.bias"], dx_beta=0.0)
+        # conv feature extractor
+        fe = pf + "feature_extractor.conv_layers."
+        for i in reversed(range(len(c["conv_kernel"]))):
+            k, s = c["conv_kernel"][i], c["conv_stride"][i]
+            a_in, z, norm = cut(ctx["conv"][i])
+            wname = f"{fe}{i}.conv.weight"
+            wmat = P[wname].view(P[wname].shape[0], -1)
+            if self.layer_extractor:                                 # GELU', LayerNorm backward and the three column sums in one pass, dz over da
+                mean, rstd = norm
+                gw, gb, cb = (f"{fe}{i}.layer_norm.weight", f"{fe}{i}.layer_norm.bias", f"{fe}{i}.conv.bias")
+                dz = ops.bias_layernorm_gelu_bwd(z, P[cb], P[gw], P[gb], mean, rstd, da, *(G[n] if self.trainable(n) else None for n in (gw, gb, cb)),
+                                                 out=da)
+            elif i == 0:
+                mean, rstd, n0 = norm
+                dn0 = ops.gelu_bwd(n0, da)
+                dz = ops.colnorm_bwd(z, P[fe + "0.layer_norm.weight"], mean, rstd, dn0, G[fe + "0.layer_norm.weight"], G[fe + "0.layer_norm.bias"],
+                                     valid=v0)
+            else:
+                dz = ops.gelu_bwd(z, da)
+            ops.conv1d_wgrad(a_in, dz, G[wname].view(wmat.shape), k, s, beta=1.0)
+            if i > 0:
+                da = ops.conv1d_dgrad(dz, wmat, a_in.shape[1], a_in.shape[2], k, s)
+            ctx["conv"][i] = None
+        self._ctx = None
+
+    def _backward_encoder(self, ctx, grad_logits, nb, cut):
+        """Backward of _encode from dL/dlogits [nb, T', V]: accumulates the gradients of lm_head and the encoder, returns the gradient of the
+        feature projection's output (rows past the utterance's last frame zero).  `ctx` is this backward's own copy of the saved context
+        (entries are dropped as they are used), `cut` trims a saved activation to the first nb samples."""
+        v0, vT = ctx["valid"]
+        c, P, G, pf = self.cfg, self.P, self.G, self._prefix
+        B, L, T = ctx["dims"]
         H, nh = c["hidden_size"], c["num_attention_heads"]
         D = H // nh
         eps = c["layer_norm_eps"]
@@ -690,33 +741,4 @@ class Wav2Vec2ForCTC(FlatModel):
         ops.group_unpack_grad(dxg.view(nb, Gn, Tp, cg), dhs, pad, beta=1.0)   # dh (pre-pos) = dhs (residual) + pos-conv path
         if vT is not None:
             ops.mask_rows(dhs, vT)                                   # the windows of the last valid frames reach into the zeroed tail: no gradient there
-        # feature projection
-        a, mean, rstd, n = cut(ctx["proj"])
-        fp = pf + "feature_projection."
-        dn = self._lin_bwd(dhs, n, fp + "projection.weight", fp + "projection.bias")
-        da = torch.empty_like(dn)
-        ops.layernorm_bwd(a, P[fp + "layer_norm.weight"], mean, rstd, dn, da, G[fp + "layer_norm.weight"], G[fp + "layer_norm.bias"], dx_beta=0.0)
-        # conv feature extractor
-        fe = pf + "feature_extractor.conv_layers."
-        for i in reversed(range(len(c["conv_kernel"]))):
-            k, s = c["conv_kernel"][i], c["conv_stride"][i]
-            a_in, z, norm = cut(ctx["conv"][i])
-            wname = f"{fe}{i}.conv.weight"
-            wmat = P[wname].view(P[wname].shape[0], -1)
-            if self.layer_extractor:                                 # GELU', LayerNorm backward and the three column sums in one pass, dz over da
-                mean, rstd = norm
-                gw, gb, cb = (f"{fe}{i}.layer_norm.weight", f"{fe}{i}.layer_norm.bias", f"{fe}{i}.conv.bias")
-                dz = ops.bias_layernorm_gelu_bwd(z, P[cb], P[gw], P[gb], mean, rstd, da, *(G[n] if self.trainable(n) else None for n in (gw, gb, cb)),
-                                                 out=da)
-            elif i == 0:
-                mean, rstd, n0 = norm
-                dn0 = ops.gelu_bwd(n0, da)
-                dz = ops.colnorm_bwd(z, P[fe + "0.layer_norm.weight"], mean, rstd, dn0, G[fe + "0.layer_norm.weight"], G[fe + "0.layer_norm.bias"],
-                                     valid=v0)
-            else:
-                dz = ops.gelu_bwd(z, da)
-            ops.conv1d_wgrad(a_in, dz, G[wname].view(wmat.shape), k, s, beta=1.0)
-            if i > 0:
-                da = ops.conv1d_dgrad(dz, wmat, a_in.shape[1], a_in.shape[2], k, s)
-            ctx["conv"][i] = None
-        self._ctx = None
+        return dhs

@@ -621,6 +621,31 @@ int dyn_relpos_gate_bwd(const float* dgate, const float* a, const float* c, cons
                         int64_t nh, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Wav2Vec2-Conformer attention, `position_embeddings_type: "relative"` (transformers Wav2Vec2ConformerSelfAttention.
+ * _apply_relative_embeddings; what `AutoModelForCTC.from_pretrained` builds for wav2vec2-conformer-rel-pos-*): the Transformer-XL score
+ * ((q + u) k^T + shift((q + v) P^T)) / sqrt(D), P = linear_pos(pe) with pe [2T - 1, H] (row k = relative position T - 1 - k).  The
+ * products are dyn_gemm_f32's; M = B * nh score matrices, x = (q + u) k^T [M, T, T] and bd = (q + v) P_h^T [M, T, ld_bd >= 2T - 1], both
+ * already scaled.  transformers' pad / view / slice shift equals bd[i, T - 1 - i + j]: no copy is made of it in either direction.
+ *   dyn_softmax_relshift_fwd_len  y[m,i,:] = softmax_j(x[m,i,j] + bd[m, i, T - 1 - i + j]); y may be x (not bd).  `valid_cols` as
+ *                                 dyn_softmax_fwd_len.  One pass: x and the window of bd read once, y written once.  T <= 16384.
+ *   dyn_relshift_bwd              dBD[m,i,k] = dS[m, i, k - (T - 1) + i] inside the window, 0 WRITTEN in every other column of the
+ *                                 ld_bd-float row: the buffer may be uninitialised scratch.
+ *   dyn_head_bias_add             u, v [nh, D] = [H]: qu[r,c] = q[r * ldq + c] + u[c], qv likewise (q strided inside a packed
+ *                                 projection output, qu / qv [rows, H] contiguous).  H % 4 == 0, ldq % 4 == 0, 16-byte aligned.
+ *   dyn_head_bias_bwd             dq[r * ldq + c] = dqu[r,c] + dqv[r,c]; du[c] = beta * du[c] + sum_r dqu[r,c], dv likewise: partial
+ *                                 rows per workgroup in `workspace`, added in workgroup order (bit-reproducible, deferrable).
+ * Null pointer, T < 1, ld_bd < 2T - 1, T beyond the row limit, unaligned operands -> DYN_E_ARG before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int dyn_softmax_relshift_fwd_len(const float* x, float* y, const float* bd, int64_t M, int64_t T, int64_t ld_bd, const int32_t* valid_cols,
+                                 void* stream);
+int dyn_relshift_bwd(const float* dS, float* dBD, int64_t M, int64_t T, int64_t ld_bd, void* stream);
+int dyn_head_bias_add(const float* q, int64_t ldq, const float* u, const float* v, float* qu, float* qv, int64_t rows, int64_t H,
+                      void* stream);
+int64_t dyn_head_bias_bwd_workspace_bytes(int64_t rows, int64_t H);
+int dyn_head_bias_bwd(const float* dqu, const float* dqv, float* dq, int64_t ldq, float* du, float* dv, float beta, int64_t rows, int64_t H,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Soft-DTW — replaces the reference's Numba CUDA kernels compute_softdtw_cuda / compute_softdtw_backward_cuda
  * (reference wav2vec2/soft_dtw_cuda.py:33-111), their autograd wrapper (:114-175) and _euclidean_dist_func (:319-329).
  *   dyn_sqdist       D[b,i,j] = sum_k (x[b,i,k] - y[b,j,k])^2            x [B,N,d], y [B,M,d] -> D [B,N,M]
