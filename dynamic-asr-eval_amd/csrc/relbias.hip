@@ -8,15 +8,13 @@
 // of one (batch, head); the distances those rows can see are the T + ROWS - 1 consecutive table entries it stages in LDS (as uint16: at
 // most 1024 buckets) next to the head's column of E, so the per-element cost of the bias is two LDS reads.
 // The backward is bit-reproducible: no float atomics anywhere, every sum has a fixed order (see dyn_relbias_bwd below).
-#include "common.h"
+#include "softmax_row.h"
 
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = dyn::ROW_TPB;
 constexpr int ROWS = 16;            // query rows per workgroup (staging T + 15 table entries is 1/16 of the rows' own traffic)
 constexpr int MAX_BUCKETS = 1024;   // E's column in LDS, bucket ids as uint16
-constexpr int MAX_T_FWD = 16384;    // dyn_softmax_fwd's row limit
-constexpr int MAX_T_BWD = 8192;     // dyn_softmax_bwd's row limit
 constexpr int GATE_LANES = 16;      // lanes that share one (b, t, head) item of the gate kernels: a float4 each per 64 channels
 constexpr int GATE_MAX_D = 256;     // gate backward: <= 4 float4 accumulators per lane and operand
 constexpr int GATE_MAX_PARTIALS = 512;
@@ -49,38 +47,13 @@ __global__ __launch_bounds__(TPB) void softmax_relbias_fwd_kernel(const float* x
     const int t0 = blk * ROWS;
     stage_bias(ecol, tab, E, bucket, (int)(bh % nh), nh, nbk, t0, T, Tmax);
     __syncthreads();
-    int Lv = T;                                                // as softmax_fwd_kernel: columns >= *valid are masked keys
-    if (valid) { const int v = *valid; Lv = v < 1 ? 1 : (v < T ? v : T); }
+    const int Lv = dyn::valid_len(valid, T);
     for (int r = 0; r < ROWS && t0 + r < T; ++r) {
         const int64_t row = bh * T + t0 + r;
         const float g = gate[row];
         const float* xr = x + row * T;
-        const int off = ROWS - 1 - r;
-        float v[ITEMS];
-        float m = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int c = threadIdx.x + j * TPB;
-            v[j] = c < Lv ? xr[c] + g * ecol[tab[c + off]] : -INFINITY;
-            m = fmaxf(m, v[j]);
-        }
-        m = dyn::block_max(m, red);
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int c = threadIdx.x + j * TPB;
-            const float e = c < Lv ? __expf(v[j] - m) : 0.f;
-            s += e;
-            v[j] = e;
-        }
-        s = dyn::block_sum(s, red);
-        const float inv = 1.f / s;
-        float* yr = y + row * T;
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int c = threadIdx.x + j * TPB;
-            if (c < T) yr[c] = v[j] * inv;
-        }
+        const uint16_t* tr = tab + (ROWS - 1 - r);                 // this row's window of the staged distances: key column s at tr[s]
+        dyn::softmax_row<ITEMS, false>([=](int c) { return xr[c] + g * ecol[tr[c]]; }, y + row * T, T, Lv, red);
     }
 }
 
@@ -362,23 +335,16 @@ extern "C" int dyn_softmax_relbias_fwd_len(const float* x, float* y, const float
                                            void* stream) {
     DYN_REQUIRE(x && y && gate && E && bucket, DYN_E_ARG, "dyn_softmax_relbias_fwd_len: null pointer");
     if (int rc = check_dims("dyn_softmax_relbias_fwd_len", B, T, H, nh)) return rc;
-    if (int rc = check_table("dyn_softmax_relbias_fwd_len", B, T, nh, Tmax, num_buckets, MAX_T_FWD)) return rc;
+    if (int rc = check_table("dyn_softmax_relbias_fwd_len", B, T, nh, Tmax, num_buckets, dyn::MAX_ROW_FWD)) return rc;
     if (B == 0) return DYN_OK;
     const int nblk = (int)dyn::cdiv(T, ROWS);
     const dim3 grid((unsigned)(B * nh * nblk)), blk(TPB);
     const size_t lds = (16 + num_buckets) * sizeof(float) + (T + ROWS - 1) * sizeof(uint16_t);
     hipStream_t st = (hipStream_t)stream;
-    const int items = (int)dyn::cdiv(T, TPB);
-#define GO(I) hipLaunchKernelGGL((softmax_relbias_fwd_kernel<I>), grid, blk, lds, st, x, y, gate, E, bucket, (int)T, (int)nh, (int)Tmax, \
-                                 (int)num_buckets, nblk, valid_cols)
-    if (items <= 1) GO(1);
-    else if (items <= 2) GO(2);
-    else if (items <= 4) GO(4);
-    else if (items <= 8) GO(8);
-    else if (items <= 16) GO(16);
-    else if (items <= 32) GO(32);
-    else GO(64);
-#undef GO
+    if (int rc = dyn::dispatch_items<dyn::MAX_ROW_FWD>("dyn_softmax_relbias_fwd_len", T, [&](auto I) {
+            hipLaunchKernelGGL((softmax_relbias_fwd_kernel<decltype(I)::value>), grid, blk, lds, st, x, y, gate, E, bucket, (int)T, (int)nh, (int)Tmax,
+                               (int)num_buckets, nblk, valid_cols);
+        })) return rc;
     return dyn::check_launch("dyn_softmax_relbias_fwd_len");
 }
 
@@ -394,7 +360,7 @@ extern "C" int dyn_relbias_bwd(const float* dS, const float* gate, const float* 
                                int64_t workspace_bytes, void* stream) {
     DYN_REQUIRE(dS && gate && E && bucket && dgate && dE && workspace, DYN_E_ARG, "dyn_relbias_bwd: null pointer");
     if (int rc = check_dims("dyn_relbias_bwd", B, T, H, nh)) return rc;
-    if (int rc = check_table("dyn_relbias_bwd", B, T, nh, Tmax, num_buckets, MAX_T_BWD)) return rc;
+    if (int rc = check_table("dyn_relbias_bwd", B, T, nh, Tmax, num_buckets, dyn::MAX_ROW_BWD)) return rc;
     DYN_REQUIRE(workspace_bytes >= dyn_relbias_bwd_workspace_bytes(B, nh, T, num_buckets), DYN_E_WORKSPACE,
                 "dyn_relbias_bwd: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
                 (long long)dyn_relbias_bwd_workspace_bytes(B, nh, T, num_buckets));
@@ -406,16 +372,10 @@ extern "C" int dyn_relbias_bwd(const float* dS, const float* gate, const float* 
     if (B > 0) {
         const dim3 grid((unsigned)(B * nh * nblk)), blk(TPB);
         const size_t lds = (16 + num_buckets + W) * sizeof(float) + W * sizeof(uint16_t);
-        const int items = (int)dyn::cdiv(T, TPB);
-#define GO(I) hipLaunchKernelGGL((relbias_bwd_rows_kernel<I>), grid, blk, lds, st, dS, gate, E, bucket, dgate, diag_ws, (int)T, (int)nh, \
-                                 (int)Tmax, (int)num_buckets, nblk)
-        if (items <= 1) GO(1);
-        else if (items <= 2) GO(2);
-        else if (items <= 4) GO(4);
-        else if (items <= 8) GO(8);
-        else if (items <= 16) GO(16);
-        else GO(32);
-#undef GO
+        if (int rc = dyn::dispatch_items<dyn::MAX_ROW_BWD>("dyn_relbias_bwd", T, [&](auto I) {
+                hipLaunchKernelGGL((relbias_bwd_rows_kernel<decltype(I)::value>), grid, blk, lds, st, dS, gate, E, bucket, dgate, diag_ws, (int)T, (int)nh,
+                                   (int)Tmax, (int)num_buckets, nblk);
+            })) return rc;
         if (int rc = dyn::check_launch("dyn_relbias_bwd")) return rc;
     }
     hipLaunchKernelGGL(relbias_bwd_dist_kernel, dim3((unsigned)dyn::cdiv(2 * T - 1, TPB), (unsigned)nh), dim3(TPB), 0, st, diag_ws, dist, (int)B,

@@ -8,12 +8,11 @@
 // The other two entries serve the biases u, v [nh, D] = [H] (head-major, so they are a per-channel vector of the [B, T, H] projections):
 // q + u and q + v in one pass over q, and back dq = dQu + dQv with the column sums du, dv in a fixed order (no float atomics).
 // All four are bandwidth work with 4-byte accesses where a row's start is not aligned (BD's window) and 16-byte ones where it is.
-#include "common.h"
+#include "softmax_row.h"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int MAX_T = 16384;        // 64 row items per thread
+constexpr int TPB = dyn::ROW_TPB;
 constexpr int HB_ROWS = 8;          // rows a workgroup of head_bias_bwd sums at least
 constexpr int HB_MAX_CHUNKS = 512;
 
@@ -23,37 +22,12 @@ template <int ITEMS>
 __global__ __launch_bounds__(TPB) void softmax_relshift_fwd_kernel(const float* x, float* y, const float* __restrict__ bd, int64_t rows, int T,
                                                                     int64_t ld_bd, const int32_t* __restrict__ valid) {   // y may alias x
     __shared__ float red[16];
-    int Lv = T;                                                // as softmax_fwd_kernel: columns >= *valid are masked keys
-    if (valid) { const int v = *valid; Lv = v < 1 ? 1 : (v < T ? v : T); }
+    const int Lv = dyn::valid_len(valid, T);
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
         const int i = (int)(row % T);                          // query position inside its (batch, head)
         const float* xr = x + row * T;
         const float* br = bd + row * ld_bd + (T - 1 - i);      // the row's window: columns T-1-i .. 2T-2-i, inside [0, 2T-1)
-        float v[ITEMS];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int c = threadIdx.x + j * TPB;
-            v[j] = c < Lv ? xr[c] + br[c] : -INFINITY;
-            mx = fmaxf(mx, v[j]);
-        }
-        mx = dyn::block_max(mx, red);
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int c = threadIdx.x + j * TPB;
-            const float e = c < Lv ? __expf(v[j] - mx) : 0.f;
-            s += e;
-            v[j] = e;
-        }
-        s = dyn::block_sum(s, red);
-        const float inv = 1.f / s;
-        float* yr = y + row * T;
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int c = threadIdx.x + j * TPB;
-            if (c < T) yr[c] = v[j] * inv;
-        }
+        dyn::softmax_row<ITEMS, false>([=](int c) { return xr[c] + br[c]; }, y + row * T, T, Lv, red);
     }
 }
 
@@ -110,7 +84,7 @@ __global__ __launch_bounds__(TPB) void head_bias_bwd_kernel(const float* __restr
 
 int check_scores(const char* who, int64_t M, int64_t T, int64_t ld_bd) {
     DYN_REQUIRE(M >= 0 && T >= 1, DYN_E_ARG, "%s: bad sizes rows=%lld T=%lld", who, (long long)M, (long long)T);
-    DYN_REQUIRE(T <= MAX_T, DYN_E_ARG, "%s: row length %lld > %d unsupported", who, (long long)T, MAX_T);
+    DYN_REQUIRE(T <= dyn::MAX_ROW_FWD, DYN_E_ARG, "%s: row length %lld > %d unsupported", who, (long long)T, dyn::MAX_ROW_FWD);
     DYN_REQUIRE(ld_bd >= 2 * T - 1, DYN_E_ARG, "%s: ld_bd=%lld is shorter than the 2T - 1 = %lld relative positions", who, (long long)ld_bd,
                 (long long)(2 * T - 1));
     DYN_REQUIRE(ld_bd <= (1 << 20) && M * T <= (1ll << 40), DYN_E_ARG, "%s: too many rows for one launch", who);
@@ -136,16 +110,9 @@ extern "C" int dyn_softmax_relshift_fwd_len(const float* x, float* y, const floa
     const int64_t rows = M * T;
     const dim3 grid((unsigned)(rows < 65535 * 4 ? rows : 65535 * 4)), blk(TPB);
     hipStream_t st = (hipStream_t)stream;
-    const int items = (int)dyn::cdiv(T, TPB);
-#define GO(I) hipLaunchKernelGGL((softmax_relshift_fwd_kernel<I>), grid, blk, 0, st, x, y, bd, rows, (int)T, ld_bd, valid_cols)
-    if (items <= 1) GO(1);
-    else if (items <= 2) GO(2);
-    else if (items <= 4) GO(4);
-    else if (items <= 8) GO(8);
-    else if (items <= 16) GO(16);
-    else if (items <= 32) GO(32);
-    else GO(64);
-#undef GO
+    if (int rc = dyn::dispatch_items<dyn::MAX_ROW_FWD>("dyn_softmax_relshift_fwd_len", T, [&](auto I) {
+            hipLaunchKernelGGL((softmax_relshift_fwd_kernel<decltype(I)::value>), grid, blk, 0, st, x, y, bd, rows, (int)T, ld_bd, valid_cols);
+        })) return rc;
     return dyn::check_launch("dyn_softmax_relshift_fwd_len");
 }
 

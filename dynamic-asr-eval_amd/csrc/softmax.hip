@@ -4,56 +4,20 @@
 // Reference call sites: attention softmax and the CTC head's log_softmax inside model(audio_signal=...)
 // (reference lcasr/lib.py:550), `F.log_softmax` on wav2vec2 logits (reference wav2vec2/lib.py:169,417),
 // the self-conditioning softmax (yaml `self_conditioning: true`), and their backward passes (lib.py:579).
-#include "common.h"
+#include "softmax_row.h"
 
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = dyn::ROW_TPB;
 
 template <int ITEMS, bool LOG>
 __global__ __launch_bounds__(TPB) void softmax_fwd_kernel(const float* x, float* y, int64_t rows, int L, int64_t ldx,
                                                            int64_t ldy, const int32_t* __restrict__ valid) {  // y may alias x (in-place attention softmax)
     __shared__ float red[8];
-    // `valid` (device scalar, may be null): columns >= *valid are masked keys — outside the max and the sum, written as 0 (-inf for LOG).
-    // The values of the first *valid columns are bit for bit those of a row of length *valid (same per-thread items, same reductions).
-    int Lv = L;
-    if (valid) { const int v = *valid; Lv = v < 1 ? 1 : (v < L ? v : L); }
+    const int Lv = dyn::valid_len(valid, L);
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
         const float* xr = x + row * ldx;
-        float v[ITEMS];
-        float m = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int c = threadIdx.x + j * TPB;
-            v[j] = c < Lv ? xr[c] : -INFINITY;
-            m = fmaxf(m, v[j]);
-        }
-        m = dyn::block_max(m, red);
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            const int c = threadIdx.x + j * TPB;
-            const float e = c < Lv ? __expf(v[j] - m) : 0.f;
-            s += e;
-            if (!LOG) v[j] = e;
-        }
-        s = dyn::block_sum(s, red);
-        float* yr = y + row * ldy;
-        if (LOG) {
-            const float lse = m + __logf(s);
-#pragma unroll
-            for (int j = 0; j < ITEMS; ++j) {
-                const int c = threadIdx.x + j * TPB;
-                if (c < L) yr[c] = v[j] - lse;
-            }
-        } else {
-            const float inv = 1.f / s;
-#pragma unroll
-            for (int j = 0; j < ITEMS; ++j) {
-                const int c = threadIdx.x + j * TPB;
-                if (c < L) yr[c] = v[j] * inv;
-            }
-        }
+        dyn::softmax_row<ITEMS, LOG>([xr](int c) { return xr[c]; }, y + row * ldy, L, Lv, red);
     }
 }
 
@@ -115,38 +79,22 @@ __global__ __launch_bounds__(TPB) void entropy_grad_kernel(const float* __restri
     }
 }
 
+// one workgroup per row, at most 65535 * 4 of them (the kernels stride over the rest)
+dim3 row_grid(int64_t rows) { return dim3((unsigned)(rows < 65535 * 4 ? rows : 65535 * 4)); }
+
 template <bool LOG>
 int launch_fwd(const float* x, float* y, int64_t rows, int64_t L, int64_t ldx, int64_t ldy, hipStream_t st, const int32_t* valid = nullptr) {
-    int64_t g = rows < 65535 * 4 ? rows : 65535 * 4;
-    dim3 grid((unsigned)g), blk(TPB);
-    const int items = (int)dyn::cdiv(L, TPB);
-#define GO(I) hipLaunchKernelGGL((softmax_fwd_kernel<I, LOG>), grid, blk, 0, st, x, y, rows, (int)L, ldx, ldy, valid)
-    if (items <= 1) GO(1);
-    else if (items <= 2) GO(2);
-    else if (items <= 4) GO(4);
-    else if (items <= 8) GO(8);
-    else if (items <= 16) GO(16);
-    else if (items <= 32) GO(32);
-    else if (items <= 64) GO(64);
-    else { dyn::set_error("softmax: row length %lld > 16384 unsupported", (long long)L); return DYN_E_UNSUPPORTED; }
-#undef GO
+    if (int rc = dyn::dispatch_items<dyn::MAX_ROW_FWD>("softmax", L, [&](auto I) {
+            hipLaunchKernelGGL((softmax_fwd_kernel<decltype(I)::value, LOG>), row_grid(rows), dim3(TPB), 0, st, x, y, rows, (int)L, ldx, ldy, valid);
+        })) return rc;
     return dyn::check_launch("dyn_softmax_fwd");
 }
 
 template <bool LOG>
 int launch_bwd(const float* y, const float* dy, float* dx, int64_t rows, int64_t L, int64_t ld, float scale, hipStream_t st) {
-    int64_t g = rows < 65535 * 4 ? rows : 65535 * 4;
-    dim3 grid((unsigned)g), blk(TPB);
-    const int items = (int)dyn::cdiv(L, TPB);
-#define GO(I) hipLaunchKernelGGL((softmax_bwd_kernel<I, LOG>), grid, blk, 0, st, y, dy, dx, rows, (int)L, ld, scale)
-    if (items <= 1) GO(1);
-    else if (items <= 2) GO(2);
-    else if (items <= 4) GO(4);
-    else if (items <= 8) GO(8);
-    else if (items <= 16) GO(16);
-    else if (items <= 32) GO(32);
-    else { dyn::set_error("softmax_bwd: row length %lld > 8192 unsupported", (long long)L); return DYN_E_UNSUPPORTED; }
-#undef GO
+    if (int rc = dyn::dispatch_items<dyn::MAX_ROW_BWD>("softmax_bwd", L, [&](auto I) {
+            hipLaunchKernelGGL((softmax_bwd_kernel<decltype(I)::value, LOG>), row_grid(rows), dim3(TPB), 0, st, y, dy, dx, rows, (int)L, ld, scale);
+        })) return rc;
     return dyn::check_launch("dyn_softmax_bwd");
 }
 
@@ -180,19 +128,11 @@ extern "C" int dyn_entropy_grad(const float* log_probs, float* grad, float* entr
                                 float scale, void* stream) {
     DYN_REQUIRE(log_probs && grad && rows >= 0 && L > 0 && ld >= L, DYN_E_ARG, "dyn_entropy_grad: bad arguments");
     if (rows == 0) return DYN_OK;
-    int64_t gq = rows < 65535 * 4 ? rows : 65535 * 4;
-    dim3 grid((unsigned)gq), blk(TPB);
     hipStream_t st = (hipStream_t)stream;
-    const int items = (int)dyn::cdiv(L, TPB);
-#define GO(I) hipLaunchKernelGGL((entropy_grad_kernel<I>), grid, blk, 0, st, log_probs, grad, entropy_per_row, rows, (int)L, ld, scale)
-    if (items <= 1) GO(1);
-    else if (items <= 2) GO(2);
-    else if (items <= 4) GO(4);
-    else if (items <= 8) GO(8);
-    else if (items <= 16) GO(16);
-    else if (items <= 32) GO(32);
-    else { dyn::set_error("entropy_grad: row length %lld > 8192 unsupported", (long long)L); return DYN_E_UNSUPPORTED; }
-#undef GO
+    if (int rc = dyn::dispatch_items<dyn::MAX_ROW_BWD>("entropy_grad", L, [&](auto I) {
+            hipLaunchKernelGGL((entropy_grad_kernel<decltype(I)::value>), row_grid(rows), dim3(TPB), 0, st, log_probs, grad, entropy_per_row, rows, (int)L,
+                               ld, scale);
+        })) return rc;
     return dyn::check_launch("dyn_entropy_grad");
 }
 

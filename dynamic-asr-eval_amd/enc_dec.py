@@ -40,7 +40,7 @@ from types import SimpleNamespace
 
 import torch
 
-from . import ops
+from . import _attn, ops
 from ._lib import DEC_PTRS_PER_LAYER, DecoderBatchDesc, DecoderDesc, check, load
 from ._loop import augmented_batch, window_rule
 from .augment import SpecAugment
@@ -332,19 +332,19 @@ class EncDecSCConformerXL(SCConformerXL):
 
     # ------------------------------------------------------------------ decoder forward / backward (B = 1)
     def _attend(self, q, k, v, S, Tk, ldq, ldk, causal, save, drop=None):
-        """softmax(q k^T / sqrt(hd)) v per head; q rows have leading dimension ldq, k / v rows ldk (views into packed projections).
+        """softmax(q k^T / sqrt(hd)) v per head (the products: _attn.py); q rows have leading dimension ldq, k / v rows ldk (views into packed
+        projections).
         `drop` = (p, stream id): dropout on the probabilities (training mode); returns (O, P[, dropped P])."""
         Hh, dd = self.dec["dec_heads"], self.dec["dec_d_model"]
         hd = dd // Hh
         Pm = torch.empty(Hh, S, Tk, device=self.device, dtype=torch.float32)
-        ops.gemm(q, k, Pm, trans_b=True, M=S, N=Tk, K=hd, lda=ldq, ldb=ldk, ldc=Tk, nb1=1, nb2=Hh, sa=(0, hd), sb=(0, hd), sc=(0, S * Tk),
-                 alpha=1.0 / math.sqrt(hd))
+        _attn.scores(_attn.plain(q, hd, ldq), _attn.plain(k, hd, ldk), Pm, 1.0 / math.sqrt(hd))
         if causal:
             check(load().dyn_causal_mask(Pm.data_ptr(), Hh, S, torch.cuda.current_stream().cuda_stream), "dyn_causal_mask")
         ops.softmax(Pm, out=Pm)
         Pd = self._dropout(Pm, drop[0], drop[1]) if drop is not None else Pm
         O = torch.empty(S, dd, device=self.device, dtype=torch.float32)
-        ops.gemm(Pd, v, O, M=S, N=hd, K=Tk, lda=Tk, ldb=ldk, ldc=dd, nb1=1, nb2=Hh, sa=(0, S * Tk), sb=(0, hd), sc=(0, hd))
+        _attn.context(Pd, _attn.plain(v, hd, ldk), _attn.plain(O, hd))
         if drop is not None:
             return O, ((Pm, Pd) if save else None)
         return O, (Pm if save else None)
@@ -354,17 +354,13 @@ class EncDecSCConformerXL(SCConformerXL):
         exactly once (beta = 0).  With dropout `Pm` = (probabilities, dropped probabilities) and `drop` = (p, stream id)."""
         Hh, dd = self.dec["dec_heads"], self.dec["dec_d_model"]
         hd = dd // Hh
-        sP = (0, S * Tk)
         Pm, Pd = Pm if drop is not None else (Pm, Pm)
-        ops.gemm(Pd, dO, dv, trans_a=True, M=Tk, N=hd, K=S, lda=Tk, ldb=dd, ldc=ldk, nb1=1, nb2=Hh, sa=sP, sb=(0, hd), sc=(0, hd))
         dP = torch.empty_like(Pm)
-        ops.gemm(dO, v, dP, trans_b=True, M=S, N=Tk, K=hd, lda=dd, ldb=ldk, ldc=Tk, nb1=1, nb2=Hh, sa=(0, hd), sb=(0, hd), sc=sP)
+        _attn.grad_v_dP(Pd, _attn.plain(dO, hd), _attn.plain(v, hd, ldk), _attn.plain(dv, hd, ldk), dP)
         if drop is not None:
             self._dropout(dP, drop[0], drop[1], out=dP)            # same mask, same 1 / (1 - p)
         ops.softmax_bwd(Pm, dP, out=dP, scale=1.0)
-        sc = 1.0 / math.sqrt(hd)
-        ops.gemm(dP, k, dq, M=S, N=hd, K=Tk, lda=Tk, ldb=ldk, ldc=ldq, nb1=1, nb2=Hh, sa=sP, sb=(0, hd), sc=(0, hd), alpha=sc)
-        ops.gemm(dP, q, dk, trans_a=True, M=Tk, N=hd, K=S, lda=Tk, ldb=ldq, ldc=ldk, nb1=1, nb2=Hh, sa=sP, sb=(0, hd), sc=(0, hd), alpha=sc)
+        _attn.grad_qk(dP, _attn.plain(q, hd, ldq), _attn.plain(k, hd, ldk), _attn.plain(dq, hd, ldq), _attn.plain(dk, hd, ldk), 1.0 / math.sqrt(hd))
 
     def _decoder_forward(self, tokens, h_enc, cached_kv=None):
         """tokens int32 [S] (bos first), h_enc [T', d_enc] -> logits [S, V].  Saves activations in grad mode."""

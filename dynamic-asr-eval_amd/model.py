@@ -13,13 +13,14 @@ second, so the adaptation step is a single fused launch over ~90 M elements and 
 one device-to-device copy (the reference round-trips them through host memory, lib.py:482-483,636-637).
 Activations are channels-last ([B, T, C]) so pointwise convs and linears are plain row-major GEMMs and every
 elementwise kernel is coalesced along C.  Architecture: see oracle/conformer_ref.py (same definition, shared names).
+Attention is the fused kernel (csrc/attention.hip) where it applies, else materialised scores: the products of _attn.py around ops.softmax.
 """
 import math
 from types import SimpleNamespace
 
 import torch
 
-from . import _graphs, ops
+from . import _attn, _graphs, ops
 from ._flat import FlatModel
 
 DEFAULT_CONFIG = dict(
@@ -515,11 +516,9 @@ class SCConformerXL(FlatModel):
         O = torch.empty(B, T, HD, device=h.device, dtype=torch.float32)
         S = torch.empty(Bs, H, T, T, device=h.device, dtype=torch.float32)
         if Bs > 0:
-            ops.gemm(qkv, qkv, S, trans_b=True, M=T, N=T, K=D, lda=3 * HD, ldb=3 * HD, ldc=T, nb1=Bs, nb2=H,
-                     sa=(T * 3 * HD, D), sb=(T * 3 * HD, D), sc=(H * T * T, T * T), b_off=HD, alpha=1.0 / math.sqrt(D))
+            _attn.scores(_attn.packed(qkv, 0, D), _attn.packed(qkv, 1, D), S, 1.0 / math.sqrt(D))     # the leading Bs samples: S's batch
             ops.softmax(S, out=S)
-            ops.gemm(S, qkv, O, M=T, N=D, K=T, lda=T, ldb=3 * HD, ldc=HD, nb1=Bs, nb2=H, sa=(H * T * T, T * T),
-                     sb=(T * 3 * HD, D), sc=(T * HD, D), b_off=2 * HD)
+            _attn.context(S, _attn.packed(qkv, 2, D), _attn.plain(O, D))
         if Bs < B:      # the clean copies: scores stay on chip (key-split fused kernel), nothing kept for a backward
             ops.attention_fwd(qkv[Bs:], B - Bs, T, H, D, 1.0 / math.sqrt(D), out=O[Bs:])
         if lc is not None:
@@ -709,20 +708,11 @@ class SCConformerXL(FlatModel):
             dn = self._lin_bwd(dqkv, n, p + ".qkv.weight", p + ".qkv.bias")
             return self._res_norm_bwd(h, p + ".norm.weight", p + ".norm.bias", mean, rstd, dn, dh)
         dqkv = torch.empty_like(qkv)
-        sS, sQ, sO = (H * T * T, T * T), (T * 3 * HD, D), (T * HD, D)
-        # dV = P^T dO
-        ops.gemm(S, dO, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=HD, ldc=3 * HD, nb1=B, nb2=H, sa=sS, sb=sO, sc=sQ,
-                 c_off=2 * HD)
-        # dP = dO V^T, then dS = softmax_bwd in place
+        (q, k, v), (dq, dk, dv) = ([_attn.packed(t, j, D) for j in range(3)] for t in (qkv, dqkv))
         dP = torch.empty_like(S)
-        ops.gemm(dO, qkv, dP, trans_b=True, M=T, N=T, K=D, lda=HD, ldb=3 * HD, ldc=T, nb1=B, nb2=H, sa=sO, sb=sQ, sc=sS,
-                 b_off=2 * HD)
-        ops.softmax_bwd(S, dP, out=dP, scale=1.0)
-        # dQ = scale * dS K ;  dK = scale * dS^T Q
-        ops.gemm(dP, qkv, dqkv, M=T, N=D, K=T, lda=T, ldb=3 * HD, ldc=3 * HD, nb1=B, nb2=H, sa=sS, sb=sQ, sc=sQ, b_off=HD,
-                 c_off=0, alpha=scale)
-        ops.gemm(dP, qkv, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=3 * HD, ldc=3 * HD, nb1=B, nb2=H, sa=sS, sb=sQ,
-                 sc=sQ, b_off=0, c_off=HD, alpha=scale)
+        _attn.grad_v_dP(S, _attn.plain(dO, D), v, dv, dP)
+        ops.softmax_bwd(S, dP, out=dP, scale=1.0)               # dP is now dS
+        _attn.grad_qk(dP, q, k, dq, dk, scale)
         cos, sin = self._rotary(T)
         ops.rotary(dqkv, cos, sin, B, T, 2 * H, D, 3 * HD, inverse=True)
         dn = self._lin_bwd(dqkv, n, p + ".qkv.weight", p + ".qkv.bias")

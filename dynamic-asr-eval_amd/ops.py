@@ -1382,8 +1382,12 @@ def conv1d_dgrad(dy, w, T, Cin, kw, stride):
     B, Tout, Cout = dy.shape
     dA = torch.empty(B, Tout, kw * Cin, device=dy.device, dtype=F32)
     gemm(dy, w, dA, M=B * Tout, N=kw * Cin, K=Cout, lda=Cout, ldb=kw * Cin, ldc=kw * Cin)
-    dx = torch.empty(B, T, Cin, device=dy.device, dtype=F32)
-    check(_L().dyn_col2im_1d(dA.data_ptr(), dx.data_ptr(), B, T, Tout, Cin, kw, stride, _stream()), "dyn_col2im_1d")
+    return col2im_1d(dA, torch.empty(B, T, Cin, device=dy.device, dtype=F32), B, T, Tout, Cin, kw, stride)
+
+
+def col2im_1d(dA, dx, B, T, Tout, C, kw, stride):
+    """dx [B, T, C] = the dense row gradients dA [B, Tout, kw * C] added over the rows' overlaps (row t covers frames t * stride .. + kw)."""
+    check(_L().dyn_col2im_1d(dA.data_ptr(), dx.data_ptr(), B, T, Tout, C, kw, stride, _stream()), "dyn_col2im_1d")
     return dx
 
 

@@ -15,16 +15,18 @@ with gradients that stay exactly zero.  The batch-norm buffers live OUTSIDE the 
 weight restore touches them.
 Attention, by `position_embeddings_type`:
   "relative"  Transformer-XL scores ((q + u) k^T + shift((q + v) P^T)) / sqrt(D), P = linear_pos(pe), pe = ops.relative_position_table(T, H);
-              the shift and the softmax are one kernel (csrc/relshift.hip), the products are ops.gemm.
+              the shift and the softmax are one kernel (csrc/relshift.hip), the BD products are ops.gemm.
   "rotary"    the LayerNormed states are rotated per head (ops.rotary: x cos + cat(-x2, x1) sin) before linear_q / linear_k, linear_v reads
               them unrotated; plain q k^T / sqrt(D).
+Both schemes differ only in how q, k and the score extras are formed: the five products around the softmax (S, O, dV, dP, dQ | dK) are
+_attn.py's, as in every model of the family.
 The tables are built on the host with transformers' own torch expressions, once per frame count, resident on the device, never inside a
 capture (the rule of WavLMForCTC.bucket_table)."""
 from types import SimpleNamespace
 
 import torch
 
-from . import ops
+from . import _attn, ops
 from . import wav2vec2_model as W2
 
 DEFAULT_CONFIG = dict(W2.DEFAULT_CONFIG, position_embeddings_type="relative", rotary_embedding_base=10000, max_source_positions=5000,
@@ -212,16 +214,16 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         Wqkv, bqkv = self.Pqkv[l]
         qkv = torch.empty(B, T, 3 * H, device=x.device, dtype=torch.float32)
         S = torch.empty(B, nh, T, T, device=x.device, dtype=torch.float32)
-        sS, sQ, sO = (nh * T * T, T * T), (T * 3 * H, D), (T * H, D)
+        q, k, v = (_attn.packed(qkv, j, D) for j in range(3))
         if self.relative:
             ops.linear(n, Wqkv, bqkv, out=qkv)
             qu, qv = ops.head_bias_add(qkv, P[p + "self_attn.pos_bias_u"], P[p + "self_attn.pos_bias_v"], H=H, ldq=3 * H)
             pos = ops.linear(tab, P[p + "self_attn.linear_pos.weight"])                  # [2T - 1, H]: head h's P_h is columns h D .. h D + D
             R = 2 * T - 1
-            ops.gemm(qu, qkv, S, trans_b=True, M=T, N=T, K=D, lda=H, ldb=3 * H, ldc=T, nb1=B, nb2=nh, sa=sO, sb=sQ, sc=sS, b_off=H, alpha=scale)
+            _attn.scores(_attn.plain(qu, D), k, S, scale)
             BD = torch.empty(B, nh, T, R, device=x.device, dtype=torch.float32)          # all 2T - 1 columns: twice the window's flops, accepted
-            ops.gemm(qv, pos, BD, trans_b=True, M=T, N=R, K=D, lda=H, ldb=H, ldc=R, nb1=B, nb2=nh, sa=sO, sb=(0, D), sc=(nh * T * R, T * R),
-                     alpha=scale)
+            ops.gemm(qv, pos, BD, trans_b=True, M=T, N=R, K=D, lda=H, ldb=H, ldc=R, nb1=B, nb2=nh, sa=(T * H, D), sb=(0, D),
+                     sc=(nh * T * R, T * R), alpha=scale)
             ops.softmax_relshift(S, BD, out=S, valid=vT)
             extra = (qu, qv, pos)
         else:
@@ -231,11 +233,11 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
             ops.gemm(nrot, Wqkv, qkv, trans_b=True, M=B * T, N=2 * H, K=H, lda=H, ldb=H, ldc=3 * H, bias=bqkv)             # q | k from the rotated
             ops.gemm(n, Wqkv, qkv, trans_b=True, M=B * T, N=H, K=H, lda=H, ldb=H, ldc=3 * H, b_off=2 * H * H, c_off=2 * H,   # v from the plain states
                      bias=bqkv[2 * H:])
-            ops.gemm(qkv, qkv, S, trans_b=True, M=T, N=T, K=D, lda=3 * H, ldb=3 * H, ldc=T, nb1=B, nb2=nh, sa=sQ, sb=sQ, sc=sS, b_off=H, alpha=scale)
+            _attn.scores(q, k, S, scale)
             ops.softmax(S, out=S, valid=vT)
             extra = (nrot,)
         O = torch.empty(B, T, H, device=x.device, dtype=torch.float32)
-        ops.gemm(S, qkv, O, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=H, nb1=B, nb2=nh, sa=sS, sb=sQ, sc=sO, b_off=2 * H)
+        _attn.context(S, v, _attn.plain(O, D))
         r = x.clone() if save else x
         ops.linear(O, P[p + "self_attn.linear_out.weight"], P[p + "self_attn.linear_out.bias"], out=r, beta=1.0)
         return r, (x, m, s, n, qkv, S, O) + extra
@@ -252,18 +254,16 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         M = nb * T
         dO = self._lin_bwd(dr, O, p + "self_attn.linear_out.weight", p + "self_attn.linear_out.bias")
         dqkv = torch.empty_like(qkv)
-        sS, sQ, sO = (nh * T * T, T * T), (T * 3 * H, D), (T * H, D)
-        ops.gemm(S, dO, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sO, sc=sQ, c_off=2 * H)
+        (q, k, v), (dq, dk, dv) = ([_attn.packed(t, j, D) for j in range(3)] for t in (qkv, dqkv))
         dP = torch.empty_like(S)
-        ops.gemm(dO, qkv, dP, trans_b=True, M=T, N=T, K=D, lda=H, ldb=3 * H, ldc=T, nb1=nb, nb2=nh, sa=sO, sb=sQ, sc=sS, b_off=2 * H)
+        _attn.grad_v_dP(S, _attn.plain(dO, D), v, dv, dP)
         ops.softmax_bwd(S, dP, out=dP, scale=1.0)                # dP is now dS, the gradient of the pre-softmax sum
         if self.relative:
             qu, qv = kept[7], kept[8]
             R = 2 * T - 1
-            sB = (nh * T * R, T * R)
+            sB, sO = (nh * T * R, T * R), (T * H, D)
             dqu = torch.empty(nb, T, H, device=dr.device, dtype=torch.float32)
-            ops.gemm(dP, qkv, dqu, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sO, b_off=H, alpha=sc)
-            ops.gemm(dP, qu, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sO, sc=sQ, c_off=H, alpha=sc)
+            _attn.grad_qk(dP, _attn.plain(qu, D), k, _attn.plain(dqu, D), dk, sc)    # q + u took q's place: dQ is d(q + u), dK reads q + u
             dBD = ops.relshift_bwd(dP)                           # dS in every row's window, zeros written around it
             dqv = torch.empty_like(dqu)
             ops.gemm(dBD, pos, dqv, M=T, N=D, K=R, lda=R, ldb=H, ldc=H, nb1=nb, nb2=nh, sa=sB, sb=(0, D), sc=sO, alpha=sc)
@@ -279,9 +279,7 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         else:
             cos, sin = tab
             nrot = kept[7]
-            ops.gemm(dP, qkv, dqkv, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sQ, b_off=H, c_off=0, alpha=sc)
-            ops.gemm(dP, qkv, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sQ,
-                     b_off=0, c_off=H, alpha=sc)
+            _attn.grad_qk(dP, q, k, dq, dk, sc)
             # q | k read the rotated states, v the plain ones: two weight-gradient products into the packed [3H, H] gradient, one bias sum
             ops.gemm(dqkv, nrot, gW, trans_a=True, M=2 * H, N=H, K=M, lda=3 * H, ldb=H, ldc=H, beta=1.0)
             ops.gemm(dqkv, n, gW, trans_a=True, M=H, N=H, K=M, lda=3 * H, ldb=H, ldc=H, a_off=2 * H, c_off=2 * H * H, beta=1.0)

@@ -12,13 +12,15 @@ kernel each way: ops.bias_layernorm_gelu) and `do_stable_layer_norm=True` (pre-L
 encoder's LayerNorm after the last layer).
 Parameter NAMES are HF's (state_dict interchange with transformers, which is the oracle in tests); the native HBM layout
 of conv kernels is [C_out][kernel][C_in] so each strided Conv1d is one implicit GEMM over overlapping rows of the
-channels-last activation (ops.conv1d), converted on load / save."""
+channels-last activation (ops.conv1d), converted on load / save.
+Attention keeps its scores in memory: the products are _attn.py's on the packed q | k | v projection, the softmax between them is a hook
+(_softmax / _softmax_bwd) a model of the family replaces (WavLM's gated relative-position bias)."""
 from collections import OrderedDict
 from types import SimpleNamespace
 
 import torch
 
-from . import _graphs, ops
+from . import _attn, _graphs, ops
 from ._flat import FlatModel
 
 DEFAULT_CONFIG = dict(
@@ -446,12 +448,10 @@ class Wav2Vec2ForCTC(FlatModel):
             ops.gemm(h, P[p + f"attention.{nm}.weight"], qkv, trans_b=True, M=B * T, N=H, K=H, lda=H, ldb=H, ldc=3 * H,
                      c_off=j * H, bias=P[p + f"attention.{nm}.bias"])
         S = torch.empty(B, nh, T, T, device=h.device, dtype=torch.float32)
-        ops.gemm(qkv, qkv, S, trans_b=True, M=T, N=T, K=D, lda=3 * H, ldb=3 * H, ldc=T, nb1=B, nb2=nh,
-                 sa=(T * 3 * H, D), sb=(T * 3 * H, D), sc=(nh * T * T, T * T), b_off=H, alpha=D ** -0.5)
+        _attn.scores(_attn.packed(qkv, 0, D), _attn.packed(qkv, 1, D), S, D ** -0.5)
         kept = self._softmax(S, h, l, vT)
         O = torch.empty(B, T, H, device=h.device, dtype=torch.float32)
-        ops.gemm(S, qkv, O, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=H, nb1=B, nb2=nh, sa=(nh * T * T, T * T),
-                 sb=(T * 3 * H, D), sc=(T * H, D), b_off=2 * H)
+        _attn.context(S, _attn.packed(qkv, 2, D), _attn.plain(O, D))
         return qkv, (S if kept is None else (S,) + tuple(kept)), O
 
     def _softmax(self, S, h, l, vT):
@@ -507,15 +507,11 @@ class Wav2Vec2ForCTC(FlatModel):
         p = f"{pf}encoder.layers.{l}."
         S, kept = (S[0], S[1:]) if isinstance(S, tuple) else (S, None)
         dqkv = torch.empty_like(qkv)
-        sS, sQ, sO = (nh * T * T, T * T), (T * 3 * H, D), (T * H, D)
-        ops.gemm(S, dO, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sO, sc=sQ, c_off=2 * H)
+        (q, k, v), (dq, dk, dv) = ([_attn.packed(t, j, D) for j in range(3)] for t in (qkv, dqkv))
         dP = torch.empty_like(S)
-        ops.gemm(dO, qkv, dP, trans_b=True, M=T, N=T, K=D, lda=H, ldb=3 * H, ldc=T, nb1=nb, nb2=nh, sa=sO, sb=sQ, sc=sS, b_off=2 * H)
-        ops.softmax_bwd(S, dP, out=dP, scale=1.0)
-        sc = D ** -0.5
-        ops.gemm(dP, qkv, dqkv, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sQ, b_off=H, c_off=0, alpha=sc)
-        ops.gemm(dP, qkv, dqkv, trans_a=True, M=T, N=D, K=T, lda=T, ldb=3 * H, ldc=3 * H, nb1=nb, nb2=nh, sa=sS, sb=sQ, sc=sQ,
-                 b_off=0, c_off=H, alpha=sc)
+        _attn.grad_v_dP(S, _attn.plain(dO, D), v, dv, dP)
+        ops.softmax_bwd(S, dP, out=dP, scale=1.0)                # dP is now dS, the gradient of the pre-softmax scores
+        _attn.grad_qk(dP, q, k, dq, dk, D ** -0.5)
         M = nb * T
         if self.packed_qkv:                                      # the three projections as one [3H, H] product each way
             self._wgrad(dqkv.view(M, 3 * H), h.view(M, H), self.Gqkv[l][0], self.Gqkv[l][1])
@@ -735,9 +731,7 @@ class Wav2Vec2ForCTC(FlatModel):
         ops.gemm(dyg, w, dA, M=T, N=K * cg, K=cg, lda=cg, ldb=K * cg, ldc=K * cg, nb1=nb, nb2=Gn, sa=(Gn * T * cg, T * cg),
                  sb=(0, cg * K * cg), sc=(Gn * T * K * cg, T * K * cg))
         dxg = torch.empty(nb * Gn, Tp, cg, device=dh.device, dtype=torch.float32)
-        from ._lib import check, load
-        check(load().dyn_col2im_1d(dA.data_ptr(), dxg.data_ptr(), nb * Gn, Tp, T, cg, K, 1, torch.cuda.current_stream().cuda_stream),
-              "dyn_col2im_1d")
+        ops.col2im_1d(dA, dxg, nb * Gn, Tp, T, cg, K, 1)
         ops.group_unpack_grad(dxg.view(nb, Gn, Tp, cg), dhs, pad, beta=1.0)   # dh (pre-pos) = dhs (residual) + pos-conv path
         if vT is not None:
             ops.mask_rows(dhs, vT)                                   # the windows of the last valid frames reach into the zeroed tail: no gradient there
