@@ -1,7 +1,7 @@
 """Float64 restatements of the operations behind the C-ABI kernels that only whole-model tests used to reach, each written from the
 operation's definition (no call into the torch op it mirrors).  tests/test_kernel_refs_cpu.py checks every one of them against torch's own
 op and autograd in float64 to 1e-12, so a wrong reference cannot hide a wrong kernel; tests/test_kernel_parity_f64_gpu.py compares the HIP
-kernels with them.  Also here: the inputs both files share, the tolerance rule, and a CPU replay of the summation order the column norm
+kernels with them (the row softmax family: tests/test_row_kernels_gpu.py, on the device).  Also here: the inputs both files share, the tolerance rule, and a CPU replay of the summation order the column norm
 used before its statistics were made stable (E[x^2] - mean^2 from fp32 running sums)."""
 import math
 
@@ -20,8 +20,10 @@ def d(t):
 
 
 def max_err(got, want, rel=False):
-    """max |got - want| (divided by |want| elementwise when `rel`) in float64."""
-    got, want = d(got), d(want)
+    """max |got - want| (divided by |want| elementwise when `rel`) in float64, computed where `want` lives (the CPU for the references
+    built there; the device for the row-kernel references, whose square cases are too large to bring back)."""
+    want = want.detach().to(F64)
+    got = got.detach().to(device=want.device, dtype=F64)
     assert got.shape == want.shape, (got.shape, want.shape)
     if got.numel() == 0:
         return 0.0
@@ -335,13 +337,118 @@ def masked_softmax_ref(x, valid):
     return y
 
 
-def entropy_grad_ref(logp, scale):
-    """H_r = -sum_c p log p with p = exp(logp), logp normalised rows; the gradient of scale * sum_r H_r w.r.t. the LOGITS behind them
-    (the simplex projection included): -p (logp + H_r) * scale.  Returns (grad, H)."""
-    y = d(logp)
+def entropy_grad_expr(y, scale):
+    """entropy_grad_ref's expression where `y` lives and in its dtype (see "the row softmax family" below)."""
     p = torch.exp(y)
     H = -(p * y).sum(-1)
     return -p * (y + H[:, None]) * scale, H
+
+
+def entropy_grad_ref(logp, scale):
+    """H_r = -sum_c p log p with p = exp(logp), logp normalised rows; the gradient of scale * sum_r H_r w.r.t. the LOGITS behind them
+    (the simplex projection included): -p (logp + H_r) * scale.  Returns (grad, H)."""
+    return entropy_grad_expr(d(logp), scale)
+
+
+# ----------------------------------------------------------------------------------------------------------- the row softmax family
+# csrc/softmax_row.h and the kernels built on it (softmax.hip, relshift.hip, relbias.hip), from the definitions.  Unlike the functions above
+# these stay on the device and in the dtype of their operands: tests/test_row_kernels_gpu.py evaluates each one twice on the GPU, in float64
+# (the reference; the square cases are too large for the CPU) and in float32 (torch's own fp32 result of the same expression: measured_tol).
+def clamped_valid(valid, L):
+    """The key length the kernels use for a device-side `valid` (valid_len of csrc/softmax_row.h): clamped into [1, L]; None is L."""
+    return L if valid is None else min(max(int(valid), 1), L)
+
+
+def row_softmax_ref(x, valid=None):
+    """softmax over the first clamped_valid(valid, L) columns of the last axis; the columns past them are exactly 0."""
+    Lv = clamped_valid(valid, x.shape[-1])
+    xv = x[..., :Lv]
+    e = torch.exp(xv - xv.max(-1, keepdim=True).values)
+    y = torch.zeros_like(x)
+    y[..., :Lv] = e / e.sum(-1, keepdim=True)
+    return y
+
+
+def row_log_softmax_ref(x, valid=None):
+    """log-softmax over the first clamped_valid(valid, L) columns; the columns past them are -inf."""
+    Lv = clamped_valid(valid, x.shape[-1])
+    xv = x[..., :Lv]
+    m = xv.max(-1, keepdim=True).values
+    y = torch.full_like(x, -math.inf)
+    y[..., :Lv] = xv - (m + torch.log(torch.exp(xv - m).sum(-1, keepdim=True)))
+    return y
+
+
+def softmax_bwd_ref(y, dy, scale=1.0):
+    """dx = y * (dy - sum(dy * y)) * scale from the probabilities y."""
+    return y * (dy - (dy * y).sum(-1, keepdim=True)) * scale
+
+
+def log_softmax_bwd_ref(y, dy):
+    """dx = dy - exp(y) * sum(dy) from the log-probabilities y."""
+    return dy - torch.exp(y) * dy.sum(-1, keepdim=True)
+
+
+def shift_pad_view_slice(bd):
+    """transformers' pad / view / slice (_apply_relative_embeddings, step 5) restated: [B, nh, T, 2T - 1] -> [B, nh, T, T]."""
+    B, nh, T, R = bd.shape
+    padded = torch.cat([torch.zeros(B, nh, T, 1, dtype=bd.dtype, device=bd.device), bd], dim=-1).view(B, nh, R + 1, T)
+    return padded[:, :, 1:].view_as(bd)[..., :R // 2 + 1]
+
+
+def relshift_index(T, device=None):
+    """[T, T] int64: the column T - 1 - i + j of BD's row i that key j of query i reads."""
+    return T - 1 - torch.arange(T, device=device)[:, None] + torch.arange(T, device=device)[None, :]
+
+
+def relshift_scores_ref(S, BD):
+    """S [B, nh, T, T] + BD[b, h, i, T - 1 - i + j] by gather; BD [B, nh, T, ld >= 2T - 1], columns past 2T - 1 are never read."""
+    T = S.shape[-1]
+    return S + BD.gather(-1, relshift_index(T, S.device).expand(S.shape))
+
+
+def relshift_bwd_ref(dS, ld):
+    """dBD [B, nh, T, ld]: dS[b, h, i, j] at column T - 1 - i + j of row i, zeros everywhere else (a copy: exact in any dtype)."""
+    T = dS.shape[-1]
+    out = torch.zeros(*dS.shape[:-1], ld, dtype=dS.dtype, device=dS.device)
+    return out.scatter_(-1, relshift_index(T, dS.device).expand(dS.shape), dS)
+
+
+def bias_ref(gate, E, table, T, Tmax):
+    """gate[b, head, t] * E[bucket(s - t), head] as [B, nh, T, T] (the restatement the WavLM tests differentiate)."""
+    dev = gate.device
+    idx = torch.arange(T, device=dev)[None, :] - torch.arange(T, device=dev)[:, None] + Tmax - 1                # [t, s]
+    return gate.unsqueeze(-1) * E[table.to(dev).long()[idx]].permute(2, 0, 1).unsqueeze(0)
+
+
+def relbias_buckets(table, T, Tmax):
+    """[T, T] int64: bucket[i, j] = table[j - i + Tmax - 1], table [2 Tmax - 1]."""
+    ar = torch.arange(T, device=table.device)
+    return table.long()[ar[None, :] - ar[:, None] + Tmax - 1]
+
+
+def relbias_scores_ref(S, gate, E, table, Tmax):
+    """S[b, h, i, j] + gate[b, h, i] * E[table[j - i + Tmax - 1], h]; S [B, nh, T, T], gate [B, nh, T], E [num_buckets, nh]."""
+    T = S.shape[-1]
+    return S + gate[..., None] * E.t()[:, relbias_buckets(table, T, Tmax)][None]
+
+
+def relbias_bwd_ref(dS, gate, E, table, Tmax):
+    """Gradients of sum(dS * gate * E[bucket]) : dgate[b, h, i] = sum_j dS[b, h, i, j] * E[bucket[i, j], h] (the row dot product);
+    dE[k, h] = sum over b and the (i, j) of bucket k of gate * dS (an index_add_ over buckets).  Returns (dgate, dE)."""
+    B, nh, T, _ = dS.shape
+    bucket = relbias_buckets(table, T, Tmax)
+    dgate = (dS * E.t()[:, bucket][None]).sum(-1)
+    per_pair = (gate[..., None] * dS).sum(0).permute(1, 2, 0).reshape(T * T, nh)
+    dE = torch.zeros_like(E).index_add_(0, bucket.reshape(-1), per_pair)
+    return dgate, dE
+
+
+def relbias_fullest_bucket(table, T, Tmax, B):
+    """The largest number of products one bucket of dE sums: distance d occurs B (T - |d|) times (as tests/test_wavlm_gpu.py counts it)."""
+    dist = torch.arange(-(T - 1), T)
+    counts = torch.zeros(int(table.max()) + 1, dtype=torch.long)
+    return int(counts.index_add_(0, table.cpu().long()[dist + Tmax - 1], B * (T - dist.abs())).max())
 
 
 # ----------------------------------------------------------------------------------------------------------- encoder-decoder pieces

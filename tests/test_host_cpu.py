@@ -44,6 +44,27 @@ def test_abi_argument_errors_are_codes_not_crashes():
     assert lib.dyn_gemm_f32_workspace_bytes(ctypes.byref(d)) == 0
 
 
+def test_row_softmax_entries_refuse_rows_beyond_their_widest_instance():
+    """The plain row kernels hold a row in registers: 64 items per thread forward (16384 columns), 32 backward (8192).  One column more is
+    DYN_E_UNSUPPORTED from the host-side dispatch, before any launch (dummy pointers are never dereferenced); the limit itself passes the
+    checks (rows = 0 launches nothing).  tests/test_row_kernels_gpu.py runs every instance up to both limits."""
+    from dynamic_asr_eval_amd import _lib
+    lib = _lib.load()
+    p, rows = 256, 3
+    fwd = {"dyn_softmax_fwd": lambda r, L: lib.dyn_softmax_fwd(p, p, r, L, L, L, None),
+           "dyn_softmax_fwd_len": lambda r, L: lib.dyn_softmax_fwd_len(p, p, r, L, L, L, p, None),
+           "dyn_log_softmax_fwd": lambda r, L: lib.dyn_log_softmax_fwd(p, p, r, L, L, L, None)}
+    bwd = {"dyn_softmax_bwd": lambda r, L: lib.dyn_softmax_bwd(p, p, p, r, L, L, 0.5, None),
+           "dyn_log_softmax_bwd": lambda r, L: lib.dyn_log_softmax_bwd(p, p, p, r, L, L, None),
+           "dyn_entropy_grad": lambda r, L: lib.dyn_entropy_grad(p, p, p, r, L, L, 1.0, None)}
+    for calls, limit in ((fwd, 16384), (bwd, 8192)):
+        for name, call in calls.items():
+            assert call(rows, limit + 1) == -4, (name, lib.dyn_last_error())                   # DYN_E_UNSUPPORTED
+            msg = lib.dyn_last_error()
+            assert b"row length" in msg and str(limit + 1).encode() in msg and b"> %d" % limit in msg, (name, msg)
+            assert call(0, limit) == 0, (name, lib.dyn_last_error())                           # DYN_OK
+
+
 def test_product_path_fails_loudly_without_gpu():
     from dynamic_asr_eval_amd import ops
     from dynamic_asr_eval_amd._lib import DynError

@@ -167,6 +167,81 @@ def test_entropy_grad_ref_is_autograd_through_log_softmax(L):
     _same(grad, z.grad, "entropy grad")
 
 
+@pytest.mark.parametrize("L,valid", [(37, None), (37, 29), (37, 0), (37, 40), (1, None), (300, 299)])
+def test_row_softmax_refs_are_softmax_and_its_autograd(L, valid):
+    rows = 5
+    x, dy = _r(rows, L, seed=40) * 4, _r(rows, L, seed=41)
+    Lv = K.clamped_valid(valid, L)
+    assert Lv == (L if valid is None else min(max(valid, 1), L))
+    masked = x.clone()
+    masked[:, Lv:] = -float("inf")
+    y, logy = K.row_softmax_ref(x, valid), K.row_log_softmax_ref(x, valid)
+    _same(y, F.softmax(masked, -1), "softmax")
+    assert torch.equal(y[:, Lv:], torch.zeros(rows, L - Lv, dtype=F64))
+    _same(logy[:, :Lv], F.log_softmax(masked, -1)[:, :Lv], "log_softmax")
+    assert torch.equal(logy[:, Lv:], torch.full((rows, L - Lv), -float("inf"), dtype=F64))
+    _same(K.masked_softmax_ref(x, Lv), y, "the earlier masked softmax")
+    xr = x.clone().requires_grad_()
+    F.softmax(xr, -1).backward(dy)
+    _same(K.softmax_bwd_ref(F.softmax(x, -1), dy, 0.5), 0.5 * xr.grad, "softmax_bwd")
+    xr = x.clone().requires_grad_()
+    F.log_softmax(xr, -1).backward(dy)
+    _same(K.log_softmax_bwd_ref(F.log_softmax(x, -1), dy), xr.grad, "log_softmax_bwd")
+    assert K.row_softmax_ref(x.float()).dtype == torch.float32 and K.softmax_bwd_ref(y.float(), dy.float()).dtype == torch.float32
+
+
+def test_entropy_grad_expr_keeps_dtype_and_is_entropy_grad_ref():
+    logp = F.log_softmax(_r(6, 37, seed=42) * 3, -1)
+    g, H = K.entropy_grad_expr(logp, 0.25)
+    g_ref, H_ref = K.entropy_grad_ref(logp, 0.25)
+    assert torch.equal(g, g_ref) and torch.equal(H, H_ref)
+    assert K.entropy_grad_expr(logp.float(), 0.25)[0].dtype == torch.float32
+
+
+@pytest.mark.parametrize("pad", [0, 4])
+def test_relshift_refs_are_pad_view_slice_and_its_autograd(pad):
+    B, nh, T = 2, 3, 37
+    R = 2 * T - 1
+    S, dS = _r(B, nh, T, T, seed=43), _r(B, nh, T, T, seed=44)
+    BD = torch.full((B, nh, T, R + pad), float("nan"), dtype=F64)
+    BD[..., :R] = _r(B, nh, T, R, seed=45)
+    leaf = BD[..., :R].clone().requires_grad_()
+    want = S + K.shift_pad_view_slice(leaf)
+    (want * dS).sum().backward()
+    _same(K.relshift_scores_ref(S, BD), want.detach(), "scores + shifted BD")
+    got = K.relshift_bwd_ref(dS, R + pad)
+    assert torch.equal(got[..., :R], leaf.grad) and torch.equal(got[..., R:], torch.zeros(B, nh, T, pad, dtype=F64))
+    for T1 in (1, 2):                                                  # the whole row / all but one element
+        bd = _r(1, 2, T1, 2 * T1 - 1, seed=46)
+        s = torch.zeros(1, 2, T1, T1, dtype=F64)
+        assert torch.equal(K.relshift_scores_ref(s, bd), K.shift_pad_view_slice(bd))
+    assert K.relshift_scores_ref(S.float(), BD.float()).dtype == torch.float32
+
+
+@pytest.mark.parametrize("nbk,maxd,Tmax", [(8, 12, 37), (8, 12, 44), (320, 800, 37)])
+def test_relbias_refs_are_bias_ref_and_its_autograd(nbk, maxd, Tmax):
+    from dynamic_asr_eval_amd import ops
+    B, nh, T = 2, 3, 37
+    table = ops.relative_position_buckets(Tmax, nbk, maxd)
+    S, dS = _r(B, nh, T, T, seed=47), _r(B, nh, T, T, seed=48)
+    gate, E = (torch.rand(B, nh, T, generator=K.gen(49), dtype=F64) * 3).requires_grad_(), _r(nbk, nh, seed=50).requires_grad_()
+    want = S + K.bias_ref(gate, E, table, T, Tmax)
+    (want * dS).sum().backward()
+    _same(K.relbias_scores_ref(S, gate.detach(), E.detach(), table, Tmax), want.detach(), "scores + gated bias")
+    dgate, dE = K.relbias_bwd_ref(dS, gate.detach(), E.detach(), table, Tmax)
+    _same(dgate, gate.grad, "dgate"); _same(dE, E.grad, "dE")
+    dist = torch.arange(-(T - 1), T)                                   # the count tests/test_wavlm_gpu.py takes from the table
+    fullest = int(torch.zeros(nbk, dtype=torch.long).index_add_(0, table.long()[dist + Tmax - 1], B * (T - dist.abs())).max())
+    assert K.relbias_fullest_bucket(table, T, Tmax, B) == fullest
+    assert K.relbias_scores_ref(S.float(), gate.detach().float(), E.detach().float(), table, Tmax).dtype == torch.float32
+
+
+def test_max_err_stays_where_the_reference_lives():
+    a, b = torch.tensor([1.0, 2.0, 4.0]), torch.tensor([1.0, 2.5, 3.0], dtype=F64)
+    assert K.max_err(a, b) == 1.0 and K.max_err(a, b, rel=True) == 1.0 / 3.0
+    assert K.max_err(torch.empty(0), torch.empty(0, dtype=F64)) == 0.0
+
+
 def test_embedding_refs_are_embedding():
     vocab, dm, S, period = 11, 6, 9, 4
     ids = torch.tensor([3, 3, 0, 10, 7, 3, 0, 1, 10])

@@ -83,6 +83,8 @@ def test_layernorm_rmsnorm(cuda, C):
 
 @pytest.mark.parametrize("L", [1, 63, 129, 256, 1992, 2048, 4096])
 def test_softmax_family(cuda, L):
+    """Rows up to 4096 (ITEMS <= 16).  Rows beyond that, both edges of every instance up to the limits (16384 forward, 8192 backward),
+    more rows than a grid, padded strides and the masked forms: tests/test_row_kernels_gpu.py."""
     from dynamic_asr_eval_amd import ops
     rows = 77
     x = torch.randn(rows, L, generator=_g(12)) * 4

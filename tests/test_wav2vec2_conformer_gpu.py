@@ -125,11 +125,7 @@ def test_wide_shape_forward_and_every_gradient(cuda, pos):
 
 
 # ----------------------------------------------------------------------------------------------------------- the four kernels
-def _shift_ref(bd):
-    """transformers' pad / view / slice (_apply_relative_embeddings, step 5) restated: [B, nh, T, 2T - 1] -> [B, nh, T, T]."""
-    B, nh, T, R = bd.shape
-    padded = torch.cat([torch.zeros(B, nh, T, 1, dtype=bd.dtype), bd], dim=-1).view(B, nh, R + 1, T)
-    return padded[:, :, 1:].view_as(bd)[..., :R // 2 + 1]
+_shift_ref = K.shift_pad_view_slice      # transformers' pad / view / slice: [B, nh, T, 2T - 1] -> [B, nh, T, T]
 
 
 @pytest.mark.parametrize("shape,valid,pad", [((2, 3, 37, 64), None, 0), ((2, 3, 37, 64), 29, 0), ((1, 2, 300, 32), None, 0),

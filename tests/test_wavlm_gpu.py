@@ -152,10 +152,7 @@ def _gate_ref(h, W, bias, const, nh):
     return a * (c * const.view(1, nh, 1) - 1.0) + 2.0, a, c
 
 
-def _bias_ref(gate, E, table, T, Tmax):
-    """gate[b, head, t] * E[bucket(s - t), head] as [B, nh, T, T]."""
-    idx = torch.arange(T)[None, :] - torch.arange(T)[:, None] + Tmax - 1                # [t, s]
-    return gate.unsqueeze(-1) * E[table.long()[idx]].permute(2, 0, 1).unsqueeze(0)
+_bias_ref = K.bias_ref      # gate[b, head, t] * E[bucket(s - t), head] as [B, nh, T, T]
 
 
 SMALL = (2, 3, 37, 64, 8, 12)          # B, nh, T, D, num_buckets, max_bucket_distance
