@@ -68,15 +68,30 @@ __global__ __launch_bounds__(TPB) void convmod_fwd_kernel(const float* __restric
 #pragma unroll
     for (int k = 0; k < TT; ++k) {
         const float a = dyn::wave_sum(s1[k]), q = dyn::wave_sum(s2[k]);
-        if (lane == 0) { red[0][wv][k] = a; red[1][wv][k] = q; }
+        if (lane == 0) { red[0][wv][k] = a; if (!LAYERNORM) red[1][wv][k] = q; }
     }
     __syncthreads();
+    if (LAYERNORM) {
+        // LayerNorm centres first, as layernorm_fwd (norm.hip) and torch do: E[x^2] - mean^2 from fp32 sums cancels once |mean| >> std
+        // (a conv bias with a component common to the channels).  Every thread forms the same mean from the four wave sums, then the
+        // squares of the centred conv outputs, still in registers, go through the same wavefront + LDS reduction.
+#pragma unroll
+        for (int k = 0; k < TT; ++k) {
+            const float mean = ((red[0][0][k] + red[0][1][k]) + (red[0][2][k] + red[0][3][k])) / C;
+            float d2 = 0.f;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) { const float dv = cv[j][k] - mean; d2 += dv * dv; }
+            const float q = dyn::wave_sum(d2);
+            if (lane == 0) red[1][wv][k] = q;
+        }
+        __syncthreads();
+    }
     if (threadIdx.x < TT) {
         const int k = threadIdx.x;
         const float a = (red[0][0][k] + red[0][1][k]) + (red[0][2][k] + red[0][3][k]);
         const float q = (red[1][0][k] + red[1][1][k]) + (red[1][2][k] + red[1][3][k]);
         const float mean = LAYERNORM ? a / C : 0.f;
-        const float var = LAYERNORM ? fmaxf(q / C - mean * mean, 0.f) : q / C;
+        const float var = q / C;                 // LAYERNORM: of the centred values (biased), RMSNorm: the mean square
         const float rstd = rsqrtf(var + eps);
         stat[0][k] = mean;
         stat[1][k] = rstd;

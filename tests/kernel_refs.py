@@ -1,8 +1,9 @@
 """Float64 restatements of the operations behind the C-ABI kernels that only whole-model tests used to reach, each written from the
 operation's definition (no call into the torch op it mirrors).  tests/test_kernel_refs_cpu.py checks every one of them against torch's own
 op and autograd in float64 to 1e-12, so a wrong reference cannot hide a wrong kernel; tests/test_kernel_parity_f64_gpu.py compares the HIP
-kernels with them (the row softmax family: tests/test_row_kernels_gpu.py, on the device).  Also here: the inputs both files share, the tolerance rule, and a CPU replay of the summation order the column norm
-used before its statistics were made stable (E[x^2] - mean^2 from fp32 running sums)."""
+kernels with them (the row softmax family: tests/test_row_kernels_gpu.py, on the device; the conformer's own convolutions, dtype- and
+device-agnostic: tests/test_conv_kernels_gpu.py).  Also here: the inputs both files share, the tolerance rule, and a CPU replay of the
+summation order the column norm used before its statistics were made stable (E[x^2] - mean^2 from fp32 running sums)."""
 import math
 
 import numpy as np
@@ -496,3 +497,170 @@ def nll_ref(logp, targets, ignore_index, scale, weights=None):
 
 def stitch_finalize_rows_ref(acc, count, row_index):
     return torch.log(d(acc)[row_index.cpu()] / d(count)[row_index.cpu()][:, None])
+
+
+# ----------------------------------------------------------------------------------------------------------- conformer convolutions
+# csrc/conv.hip and csrc/convmod.hip from the definitions, by index gathers.  Dtype- and device-agnostic: the result has the dtype of the
+# operands (tests/test_conv_kernels_gpu.py passes float64 copies; tests/test_kernel_refs_cpu.py holds every function to torch's conv1d /
+# conv2d / layer_norm / silu and autograd in float64).  Activations are channels-last, filters [C, KW] and [C, 3, 3].
+def sigmoid_expr(x):
+    return 1.0 / (1.0 + torch.exp(-x))
+
+
+def silu_expr(x):
+    return x * sigmoid_expr(x)
+
+
+def silu_grad_expr(x):
+    s = sigmoid_expr(x)
+    return s * (1.0 + x * (1.0 - s))
+
+
+def dwconv1d_windows(x, KW):
+    """x [B, T, C] -> [B, T, KW, C]: window[b, t, j, c] = x[b, t + j - P, c] with P = (KW - 1) / 2, zeros outside [0, T) ('same')."""
+    B, T, C = x.shape
+    P = (KW - 1) // 2
+    xp = torch.zeros(B, T + 2 * P, C, dtype=x.dtype, device=x.device)
+    xp[:, P:P + T] = x
+    idx = torch.arange(T, device=x.device)[:, None] + torch.arange(KW, device=x.device)[None, :]
+    return xp[:, idx]
+
+
+def dwconv1d_ref(x, w, bias=None):
+    """y[b, t, c] = bias[c] + sum_j w[c, j] * x[b, t + j - P, c]."""
+    y = (dwconv1d_windows(x, w.shape[1]) * w.t()[None, None]).sum(2)
+    return y if bias is None else y + bias
+
+
+def dwconv1d_dgrad_ref(dy, w):
+    """dx[b, t, c] = sum_j w[c, j] * dy[b, t - j + P, c]: the same windows read with the taps reversed."""
+    KW = w.shape[1]
+    rev = w[:, torch.arange(KW - 1, -1, -1, device=w.device)]
+    return (dwconv1d_windows(dy, KW) * rev.t()[None, None]).sum(2)
+
+
+def dwconv1d_wgrad_ref(x, dy, KW):
+    """dw[c, j] = sum_{b, t} dy[b, t, c] * x[b, t + j - P, c]  [C, KW];  dbias[c] = sum_{b, t} dy[b, t, c]."""
+    dw = (dwconv1d_windows(x, KW) * dy[:, :, None, :]).sum((0, 1)).t()
+    return dw, dy.sum((0, 1))
+
+
+def group_samples(B, R, r):
+    """The samples of replica r in a lockstep batch ordered sample = chunk * R + replica."""
+    return torch.arange(r, B, R)
+
+
+def dwconv1d_dgrad_group_ref(dy, w):
+    """w [R, C, KW]: sample b is convolved with the filters of replica b % R."""
+    R = w.shape[0]
+    return torch.stack([dwconv1d_dgrad_ref(dy[b:b + 1], w[b % R])[0] for b in range(dy.shape[0])])
+
+
+def dwconv1d_wgrad_group_ref(x, dy, old_w, old_b, beta):
+    """old_w [R, C, KW], old_b [R, C]: replica r's gradient is beta * old + the sum over the samples b = r (mod R)."""
+    R, _, KW = old_w.shape
+    dws, dbs = [], []
+    for r in range(R):
+        sel = group_samples(x.shape[0], R, r).to(x.device)
+        dw, db = dwconv1d_wgrad_ref(x[sel], dy[sel], KW)
+        dws.append(dw + beta * old_w[r] if beta != 0.0 else dw)
+        dbs.append(db + beta * old_b[r] if beta != 0.0 else db)
+    return torch.stack(dws), torch.stack(dbs)
+
+
+def s2_out_len(n):
+    """Output length of a 3-wide, stride-2, pad-1 convolution."""
+    return (n - 1) // 2 + 1
+
+
+def s2_patches(a):
+    """a [B, T, F, ...] -> [B, To, 3, Fo, 3, ...]: patch[b, to, dt, fo, df] = a[b, 2 to + dt - 1, 2 fo + df - 1], zeros outside the input."""
+    B, T, Fq = a.shape[:3]
+    To, Fo = s2_out_len(T), s2_out_len(Fq)
+    ap = torch.zeros(B, 2 * To + 1, 2 * Fo + 1, *a.shape[3:], dtype=a.dtype, device=a.device)
+    ap[:, 1:T + 1, 1:Fq + 1] = a
+    ti = 2 * torch.arange(To, device=a.device)[:, None] + torch.arange(3, device=a.device)[None, :]
+    fi = 2 * torch.arange(Fo, device=a.device)[:, None] + torch.arange(3, device=a.device)[None, :]
+    return ap[:, ti][:, :, :, fi]
+
+
+def s2_scatter(contrib, T, Fq):
+    """The adjoint of s2_patches: contrib [B, To, 3, Fo, 3, ...] -> [B, T, F, ...], every patch element added back where it was read."""
+    B, To, _, Fo = contrib.shape[:4]
+    out = torch.zeros(B, 2 * To + 1, 2 * Fo + 1, *contrib.shape[5:], dtype=contrib.dtype, device=contrib.device)
+    for dt in range(3):
+        for df in range(3):
+            out[:, dt:dt + 2 * To:2, df:df + 2 * Fo:2] += contrib[:, :, dt, :, df]
+    return out[:, 1:T + 1, 1:Fq + 1]
+
+
+def conv2d_first_ref(x, w, bias):
+    """x [B, T, F] (one input channel), w [C, 3, 3] -> z[b, to, fo, c] = bias[c] + sum_{dt, df} w[c, dt, df] * x[b, 2 to + dt - 1, 2 fo + df - 1]."""
+    return torch.einsum("btifj,cij->btfc", s2_patches(x), w) + bias
+
+
+def conv2d_first_dgrad_ref(dz, w, T, Fq):
+    """dx[b, t, f] = sum_c sum over the (to, dt), (fo, df) that read (t, f) of w[c, dt, df] * dz[b, to, fo, c]."""
+    return s2_scatter(torch.einsum("btfc,cij->btifj", dz, w), T, Fq)
+
+
+def conv2d_first_wgrad_ref(x, dz):
+    """dw [C, 3, 3], dbias [C]."""
+    return torch.einsum("btfc,btifj->cij", dz, s2_patches(x)), dz.sum((0, 1, 2))
+
+
+def dwconv2d_s2_ref(z, w, bias):
+    """z [B, T, F, C] -> u[b, to, fo, c] = bias[c] + sum_{dt, df} w[c, dt, df] * silu(z[b, 2 to + dt - 1, 2 fo + df - 1, c])."""
+    return torch.einsum("btifjc,cij->btfc", s2_patches(silu_expr(z)), w) + bias
+
+
+def dwconv2d_s2_dgrad_ref(z, w, du):
+    """dz = silu'(z) * (the depthwise transposed conv of du)."""
+    B, T, Fq, C = z.shape
+    return s2_scatter(torch.einsum("btfc,cij->btifjc", du, w), T, Fq) * silu_grad_expr(z)
+
+
+def dwconv2d_s2_wgrad_ref(z, du):
+    return torch.einsum("btfc,btifjc->cij", du, s2_patches(silu_expr(z))), du.sum((0, 1, 2))
+
+
+def sub12_ref(x, w1, b1, w2, b2):
+    """The first two subsampling stages: dw3x3_s2(silu(conv3x3_s2(x)))."""
+    return dwconv2d_s2_ref(conv2d_first_ref(x, w1, b1), w2, b2)
+
+
+def sub12_bwd_ref(x, du2, w1, b1, w2):
+    """(dw1, db1, dw2, db2) of sub12_ref given du2."""
+    z1 = conv2d_first_ref(x, w1, b1)
+    dw2, db2 = dwconv2d_s2_wgrad_ref(z1, du2)
+    dw1, db1 = conv2d_first_wgrad_ref(x, dwconv2d_s2_dgrad_ref(z1, w2, du2))
+    return dw1, db1, dw2, db2
+
+
+def convmod_ref(u, w, bias, gamma, beta, layernorm, eps):
+    """The fused conv-module core: u [B, T, 2C] -> GLU -> depthwise conv (w [C, 9], 'same', optional bias) -> LayerNorm (optional beta) or
+    RMSNorm over the channels -> SiLU.  Returns (s, g, c, nn, mean, rstd): the output, the GLU output, the conv output, the norm output, and
+    the per-frame statistics flattened to [B * T] (mean is None for RMSNorm)."""
+    C = u.shape[-1] // 2
+    g = u[..., :C] * sigmoid_expr(u[..., C:])
+    c = dwconv1d_ref(g, w, bias)
+    if layernorm:
+        mean = c.sum(-1, keepdim=True) / C
+        rstd = 1.0 / torch.sqrt(((c - mean) ** 2).sum(-1, keepdim=True) / C + eps)
+        nn = (c - mean) * rstd * gamma
+        if beta is not None:
+            nn = nn + beta
+        mean = mean.reshape(-1)
+    else:
+        mean = None
+        rstd = 1.0 / torch.sqrt((c * c).sum(-1, keepdim=True) / C + eps)
+        nn = c * rstd * gamma
+    return silu_expr(nn), g, c, nn, mean, rstd.reshape(-1)
+
+
+def convmod_group_ref(u, w, bias, gamma, beta, layernorm, eps):
+    """Parameters [R, ...]: sample b takes replica b % R's.  Same tuple as convmod_ref."""
+    R = w.shape[0]
+    per = [convmod_ref(u[b:b + 1], w[b % R], None if bias is None else bias[b % R], gamma[b % R], None if beta is None else beta[b % R],
+                       layernorm, eps) for b in range(u.shape[0])]
+    return tuple(None if per[0][i] is None else torch.cat([p[i] for p in per]) for i in range(6))

@@ -65,6 +65,42 @@ def test_row_softmax_entries_refuse_rows_beyond_their_widest_instance():
             assert call(0, limit) == 0, (name, lib.dyn_last_error())                           # DYN_OK
 
 
+def test_conv_entries_refuse_what_they_have_no_instance_for():
+    """csrc/conv.hip and csrc/convmod.hip dispatch on the host: a depthwise width outside {3, 5, 7, 9, 15, 31}, a conv module that is not
+    width 9 with C in {256, 512, 768, 1024}, the fused subsampling pair with C % 4 != 0 (DYN_E_UNSUPPORTED) and a lockstep batch that does not
+    hold whole groups (DYN_E_ARG) all return before any launch, so dummy pointers are never dereferenced.  tests/test_conv_kernels_gpu.py runs
+    every instance that exists."""
+    from dynamic_asr_eval_amd import _lib
+    lib = _lib.load()
+    p, big = 256, 1 << 40
+    B, T, C = 2, 8, 8
+    for KW in (1, 4, 11, 33):
+        assert lib.dyn_dwconv1d_fwd(p, p, p, p, B, T, C, KW, None) == -4, (KW, lib.dyn_last_error())
+        assert b"unsupported kernel width %d" % KW in lib.dyn_last_error()
+        assert lib.dyn_dwconv1d_dgrad(p, p, p, B, T, C, KW, 0.0, None) == -4, (KW, lib.dyn_last_error())
+        assert lib.dyn_dwconv1d_dgrad_g(p, p, p, B, T, C, KW, 0.0, 2, 4096, None) == -4, (KW, lib.dyn_last_error())
+        assert lib.dyn_dwconv1d_wgrad(p, p, p, p, 0.0, B, T, C, KW, p, big, None) == -4, (KW, lib.dyn_last_error())
+        assert b"dwconv1d_wgrad: unsupported kernel width %d" % KW in lib.dyn_last_error()
+        assert lib.dyn_dwconv1d_wgrad_g(p, p, p, p, 0.0, B, T, C, KW, 2, 4096, p, big, None) == -4, (KW, lib.dyn_last_error())
+    for KW, Cm in ((7, 256), (9, 300), (9, 1280)):
+        for ln in (0, 1):
+            assert lib.dyn_convmod_fwd(p, p, p, p, p, p, p, p, p, p, p, B, T, Cm, KW, ln, 1e-5, None) == -4, (KW, Cm, lib.dyn_last_error())
+            assert b"needs kernel width 9" in lib.dyn_last_error()
+            assert lib.dyn_convmod_fwd_g(p, p, p, p, p, p, p, p, p, p, p, B, T, Cm, KW, ln, 1e-5, 2, 4096, None) == -4, (KW, Cm, lib.dyn_last_error())
+    assert lib.dyn_sub12_fwd(p, p, p, p, p, p, B, T, 8, 6, None) == -4, lib.dyn_last_error()
+    assert b"dyn_sub12_fwd" in lib.dyn_last_error()
+    assert lib.dyn_sub12_bwd(p, p, p, p, p, p, p, p, p, 1.0, B, T, 8, 6, p, big, None) == -4, lib.dyn_last_error()
+    assert b"dyn_sub12_bwd" in lib.dyn_last_error()
+    for Bn, R in ((3, 2), (4, 3)):                                                                 # B % n_groups != 0
+        assert lib.dyn_dwconv1d_dgrad_g(p, p, p, Bn, T, C, 9, 0.0, R, 4096, None) == -1, lib.dyn_last_error()
+        assert b"dyn_dwconv1d_dgrad_g" in lib.dyn_last_error()
+        assert lib.dyn_dwconv1d_wgrad_g(p, p, p, p, 0.0, Bn, T, C, 9, R, 4096, p, big, None) == -1, lib.dyn_last_error()
+        assert b"dyn_dwconv1d_wgrad_g" in lib.dyn_last_error()
+        assert lib.dyn_convmod_fwd_g(p, p, p, p, p, p, p, p, p, p, p, Bn, T, 256, 9, 0, 1e-5, R, 4096, None) == -1, lib.dyn_last_error()
+        assert b"dyn_convmod_fwd_g" in lib.dyn_last_error()
+    assert lib.dyn_dwconv1d_fwd(p, p, p, p, 0, T, C, 9, None) == 0 and lib.dyn_convmod_fwd_g(p, p, p, p, p, p, p, p, p, p, p, 0, T, 256, 9, 1, 1e-5, 2, 4096, None) == 0
+
+
 def test_product_path_fails_loudly_without_gpu():
     from dynamic_asr_eval_amd import ops
     from dynamic_asr_eval_amd._lib import DynError

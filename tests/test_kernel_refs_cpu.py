@@ -314,3 +314,102 @@ def test_unshifted_column_statistics_miss_the_parity_bound_on_offset_inputs(shap
             assert got_y > tol_y and got_r > tol_r, (shape, got_y, tol_y, got_r, tol_r)
         else:
             assert got_y <= tol_y and got_r <= tol_r, (shape, got_y, tol_y, got_r, tol_r)
+
+
+# ----------------------------------------------------------------------------------------------------------- conformer convolutions
+@pytest.mark.parametrize("B,T,C,KW", [(2, 1, 5, 3), (2, 6, 3, 9), (1, 7, 4, 31), (3, 33, 2, 15), (2, 16, 3, 5)])     # T < P: (1, 3), (6, 9), (7, 31)
+def test_dwconv1d_refs_are_depthwise_conv1d(B, T, C, KW):
+    x, w, bias = _r(B, T, C, seed=40), _r(C, KW, seed=41), _r(C, seed=42)
+    dy = _r(B, T, C, seed=43)
+    xr, wr, br = (t.clone().requires_grad_() for t in (x, w, bias))
+    want = F.conv1d(xr.transpose(1, 2), wr.unsqueeze(1), br, padding=(KW - 1) // 2, groups=C).transpose(1, 2)
+    want.backward(dy)
+    _same(K.dwconv1d_ref(x, w, bias), want.detach(), "dwconv1d")
+    _same(K.dwconv1d_ref(x, w), want.detach() - bias, "dwconv1d, bias None")
+    _same(K.dwconv1d_dgrad_ref(dy, w), xr.grad, "dgrad")
+    dw, db = K.dwconv1d_wgrad_ref(x, dy, KW)
+    _same(dw, wr.grad, "wgrad"); _same(db, br.grad, "bgrad")
+
+
+@pytest.mark.parametrize("B,R,T", [(4, 2, 6), (6, 3, 5), (3, 1, 4)])
+def test_dwconv1d_group_refs_are_per_replica_autograd(B, R, T):
+    C, KW = 3, 9
+    x, w, dy = _r(B, T, C, seed=44), _r(R, C, KW, seed=45), _r(B, T, C, seed=46)
+    old_w, old_b = _r(R, C, KW, seed=47), _r(R, C, seed=48)
+    xr, wr, br = x.clone().requires_grad_(), w.clone().requires_grad_(), torch.zeros(R, C, dtype=F64, requires_grad=True)
+    y = torch.stack([F.conv1d(xr[b:b + 1].transpose(1, 2), wr[b % R].unsqueeze(1), br[b % R], padding=4, groups=C).transpose(1, 2)[0] for b in range(B)])
+    y.backward(dy)
+    _same(K.dwconv1d_dgrad_group_ref(dy, w), xr.grad, "group dgrad")
+    for beta in (0.0, 1.0, 0.5):
+        dw, db = K.dwconv1d_wgrad_group_ref(x, dy, old_w, old_b, beta)
+        _same(dw, wr.grad + beta * old_w, f"group wgrad beta {beta}"); _same(db, br.grad + beta * old_b, f"group bgrad beta {beta}")
+    assert K.group_samples(6, 3, 1).tolist() == [1, 4]
+
+
+@pytest.mark.parametrize("B,T,Fq,C", [(2, 1, 1, 3), (1, 2, 3, 4), (2, 5, 4, 2), (1, 8, 7, 5)])
+def test_subsampling_refs_are_conv2d(B, T, Fq, C):
+    x, w1, b1, w2, b2 = _r(B, T, Fq, seed=50), _r(C, 3, 3, seed=51), _r(C, seed=52), _r(C, 3, 3, seed=53), _r(C, seed=54)
+    xr, w1r, b1r = (t.clone().requires_grad_() for t in (x, w1, b1))
+    z = F.conv2d(xr.unsqueeze(1), w1r.unsqueeze(1), b1r, stride=2, padding=1)                      # [B, C, To, Fo]
+    dz = _r(*z.shape, seed=55)
+    z.backward(dz)
+    cl = lambda t: t.permute(0, 2, 3, 1).contiguous()                                            # noqa: E731  channels-last
+    assert tuple(z.shape[2:]) == (K.s2_out_len(T), K.s2_out_len(Fq))
+    _same(K.conv2d_first_ref(x, w1, b1), cl(z.detach()), "conv2d_first")
+    _same(K.conv2d_first_dgrad_ref(cl(dz), w1, T, Fq), xr.grad, "conv2d_first dgrad")
+    dw, db = K.conv2d_first_wgrad_ref(x, cl(dz))
+    _same(dw, w1r.grad, "conv2d_first wgrad"); _same(db, b1r.grad, "conv2d_first bgrad")
+    zin = _r(B, T, Fq, C, seed=56) * 2
+    zr, w2r, b2r = zin.permute(0, 3, 1, 2).clone().requires_grad_(), w2.clone().requires_grad_(), b2.clone().requires_grad_()
+    u = F.conv2d(F.silu(zr), w2r.unsqueeze(1), b2r, stride=2, padding=1, groups=C)
+    du = _r(*u.shape, seed=57)
+    u.backward(du)
+    _same(K.silu_expr(zin), F.silu(zin), "silu")
+    _same(K.dwconv2d_s2_ref(zin, w2, b2), cl(u.detach()), "dwconv2d_s2")
+    _same(K.dwconv2d_s2_dgrad_ref(zin, w2, cl(du)), cl(zr.grad), "dwconv2d_s2 dgrad")
+    dw, db = K.dwconv2d_s2_wgrad_ref(zin, cl(du))
+    _same(dw, w2r.grad, "dwconv2d_s2 wgrad"); _same(db, b2r.grad, "dwconv2d_s2 bgrad")
+
+
+@pytest.mark.parametrize("B,T,Fq,C", [(2, 1, 1, 3), (1, 6, 9, 4), (2, 7, 8, 2), (1, 4, 11, 3)])
+def test_sub12_refs_are_the_conv2d_chain(B, T, Fq, C):
+    x, w1, b1, w2, b2 = _r(B, T, Fq, seed=60), _r(C, 3, 3, seed=61), _r(C, seed=62), _r(C, 3, 3, seed=63), _r(C, seed=64)
+    w1r, b1r, w2r, b2r = (t.clone().requires_grad_() for t in (w1, b1, w2, b2))
+    u = F.conv2d(F.silu(F.conv2d(x.unsqueeze(1), w1r.unsqueeze(1), b1r, stride=2, padding=1)), w2r.unsqueeze(1), b2r, stride=2, padding=1, groups=C)
+    du = _r(*u.shape, seed=65)
+    u.backward(du)
+    _same(K.sub12_ref(x, w1, b1, w2, b2), u.detach().permute(0, 2, 3, 1), "sub12")
+    for got, want, name in zip(K.sub12_bwd_ref(x, du.permute(0, 2, 3, 1).contiguous(), w1, b1, w2), (w1r, b1r, w2r, b2r), ("dw1", "db1", "dw2", "db2")):
+        _same(got, want.grad, name)
+
+
+@pytest.mark.parametrize("layernorm", [False, True])
+@pytest.mark.parametrize("B,T,C", [(2, 1, 4), (1, 3, 6), (2, 8, 5), (1, 13, 3)])                  # T < P = 4: 1 and 3
+def test_convmod_ref_is_glu_conv_norm_silu(B, T, C, layernorm):
+    eps = 1e-5
+    u, w, bias, gamma, beta = _r(B, T, 2 * C, seed=70), _r(C, 9, seed=71), _r(C, seed=72) + 3.0, _r(C, seed=73), _r(C, seed=74)
+    for bs, bt in ((bias, beta), (None, None)):
+        g = F.glu(u, -1)
+        c = F.conv1d(g.transpose(1, 2), w.unsqueeze(1), bs, padding=4, groups=C).transpose(1, 2)
+        if layernorm:
+            nn = F.layer_norm(c, (C,), gamma, bt, eps)
+            mean = c.mean(-1).reshape(-1)
+            rstd = torch.rsqrt(c.var(-1, unbiased=False) + eps).reshape(-1)
+        else:
+            rstd = torch.rsqrt(c.pow(2).mean(-1) + eps).reshape(-1)
+            nn = F.rms_norm(c, (C,), gamma, eps) if hasattr(F, "rms_norm") else c * rstd.view(B, T, 1) * gamma
+            mean = None
+        got = K.convmod_ref(u, w, bs, gamma, bt if layernorm else None, layernorm, eps)
+        for name, a, b in zip(("s", "g", "c", "nn", "mean", "rstd"), got, (F.silu(nn), g, c, nn, mean, rstd)):
+            if b is None:
+                assert a is None, name
+            else:
+                _same(a, b, f"convmod {name}")
+    # group form: replica b % R
+    R = 2
+    if B % R == 0:
+        wR, bR, gR, tR = _r(R, C, 9, seed=75), _r(R, C, seed=76), _r(R, C, seed=77), _r(R, C, seed=78)
+        got = K.convmod_group_ref(u, wR, bR, gR, tR if layernorm else None, layernorm, eps)
+        for b in range(B):
+            one = K.convmod_ref(u[b:b + 1], wR[b % R], bR[b % R], gR[b % R], tR[b % R] if layernorm else None, layernorm, eps)
+            assert torch.equal(got[0][b], one[0][0]) and torch.equal(got[5][b * T:(b + 1) * T], one[5])
