@@ -1434,3 +1434,57 @@ def group_unpack_grad(dxg, dx, pad, beta=0.0):
     G = dxg.shape[1]
     check(_L().dyn_group_unpack_grad(dxg.data_ptr(), dx.data_ptr(), B, T, C, G, pad, beta, _stream()), "dyn_group_unpack_grad")
     return dx
+
+
+def _posconv_dims(who, yg, bias, T):
+    if yg.dim() != 4:
+        raise DynError(f"{who}: yg must be [B, G, Tg, cg]")
+    B, G, Tg, cg = yg.shape
+    H = G * cg
+    if H % 256 or H > 1024:
+        raise DynError(f"{who}: H = G * cg = {H} must be a multiple of 256 up to 1024")
+    if cg % 4:
+        raise DynError(f"{who}: cg = {cg} channels per group must be a multiple of 4")
+    if not 0 <= T <= Tg:
+        raise DynError(f"{who}: T = {T} rows of the {Tg} yg holds per group")
+    if bias is None or bias.numel() != H:
+        raise DynError(f"{who}: the conv bias must have H = {H} elements")
+    return B, G, Tg, cg, H
+
+
+def posconv_ln_gelu(yg, bias, T, pad=0, eps=1e-5, valid=None, want_act=True, want_packed=False):
+    """One Data2Vec-Audio positional conv layer after its grouped GEMM: gelu(LayerNorm_H(rows of yg + bias)), no affine parameters.  yg
+    [B, G, Tg >= T, cg] is left unmodified.  Returns (act [B, T, H] or None, xg_next [B, G, T + 2 pad, cg] or None, mean [B T], rstd [B T]):
+    xg_next is the next layer's packed and zero-padded input; rows t >= `valid` (device int32 scalar) are zeros in both."""
+    _cc(yg, "posconv_ln_gelu.yg"); _cc(bias, "posconv_ln_gelu.bias")
+    B, G, Tg, cg, H = _posconv_dims("posconv_ln_gelu", yg, bias, T)
+    if not (want_act or want_packed):
+        raise DynError("posconv_ln_gelu: at least one of the two outputs must be wanted")
+    act = torch.empty(B, T, H, device=yg.device, dtype=F32) if want_act else None
+    xg = torch.empty(B, G, T + 2 * pad, cg, device=yg.device, dtype=F32) if want_packed else None
+    mean = torch.empty(B * T, device=yg.device, dtype=F32)
+    rstd = torch.empty(B * T, device=yg.device, dtype=F32)
+    check(_L().dyn_posconv_ln_gelu_fwd(yg.data_ptr(), bias.data_ptr(), _opt(act, "act"), _opt(xg, "xg_next"), mean.data_ptr(), rstd.data_ptr(),
+                                       B, T, Tg, H, G, pad, eps, _valid_ptr(valid, "posconv_ln_gelu"), _stream()), "dyn_posconv_ln_gelu_fwd")
+    return act, xg, mean, rstd
+
+
+def posconv_ln_gelu_bwd(yg, bias, mean, rstd, dact, dbias, wgrad_beta=1.0, valid=None):
+    """Backward of posconv_ln_gelu from yg, mean, rstd (the normalised row is recomputed) and dact [B, T, H]: returns dyg [B, G, T, cg], the
+    layout the weight- and data-gradient GEMMs read (rows >= `valid` exact zeros); dbias = wgrad_beta * old + column sums, or None (frozen)."""
+    _cc(yg, "posconv_ln_gelu_bwd.yg"); _cc(bias, "posconv_ln_gelu_bwd.bias"); _cc(dact, "posconv_ln_gelu_bwd.dact")
+    _cc(mean, "posconv_ln_gelu_bwd.mean"); _cc(rstd, "posconv_ln_gelu_bwd.rstd")
+    if dact.dim() != 3:
+        raise DynError("posconv_ln_gelu_bwd: dact must be [B, T, H]")
+    T = dact.shape[1]
+    B, G, Tg, cg, H = _posconv_dims("posconv_ln_gelu_bwd", yg, bias, T)
+    if tuple(dact.shape) != (B, T, H) or mean.numel() != B * T or rstd.numel() != B * T:
+        raise DynError("posconv_ln_gelu_bwd: dact / mean / rstd do not match yg")
+    if dbias is not None and dbias.numel() != H:
+        raise DynError("posconv_ln_gelu_bwd: dbias must have H elements")
+    dyg = torch.empty(B, G, T, cg, device=yg.device, dtype=F32)
+    ws = workspace(yg.device)
+    check(_L().dyn_posconv_ln_gelu_bwd(yg.data_ptr(), bias.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dact.data_ptr(), dyg.data_ptr(),
+                                       _opt(dbias, "dbias"), wgrad_beta, B, T, Tg, H, G, _valid_ptr(valid, "posconv_ln_gelu_bwd"),
+                                       ws.data_ptr(), ws.numel(), _stream()), "dyn_posconv_ln_gelu_bwd")
+    return dyg

@@ -55,6 +55,16 @@ def make_config(cfg=None, defaults=DEFAULT_CONFIG):
     return out
 
 
+def config_dict(cfg, keys):
+    """`cfg` (None, a dict, or an object with attributes such as a transformers configuration) as a dict of those of `keys` it carries: what
+    the configuration reader of a model of the family looks at before it calls make_config."""
+    if cfg is None:
+        return {}
+    if isinstance(cfg, dict):
+        return {k: cfg[k] for k in keys if cfg.get(k, None) is not None}
+    return {k: getattr(cfg, k) for k in keys if getattr(cfg, k, None) is not None}
+
+
 def config_from_json(path, make=make_config):
     """An HF `config.json` as plain JSON -> make_config (only DEFAULT_CONFIG's keys and the three layout flags are read; `make`: the
     configuration reader of another model of the family)."""
@@ -144,7 +154,8 @@ class Wav2Vec2ForCTC(FlatModel):
     _input = "input_values"
     # what a model of the same family (wavlm_model.WavLMForCTC) replaces: the base model's parameter prefix, its configuration reader and
     # parameter list, and the two attention hooks _softmax / _softmax_bwd; a model with another encoder (wav2vec2_conformer_model) also the
-    # names of the q | k | v projections inside a layer and the two encoder hooks _encode / _backward_encoder
+    # names of the q | k | v projections inside a layer and the two encoder hooks _encode / _backward_encoder; a model with another positional
+    # embedding (data2vec_audio_model) the pair _pos_embed / _pos_embed_bwd, one with another feature projection (hubert_model) _project / _project_bwd
     _prefix = "wav2vec2."
     _qkv_fmt = "attention.{}_proj"
     _make_config = staticmethod(make_config)
@@ -358,7 +369,7 @@ class Wav2Vec2ForCTC(FlatModel):
             w = P[f"{fe}{i}.conv.weight"]
             z = ops.conv1d(a, w.view(w.shape[0], -1), k, s)
             if self.layer_extractor:                                # conv -> + bias -> LayerNorm(C) -> GELU; only (a, z, mean, rstd) are kept
-                act, mean, rstd = ops.bias_layernorm_gelu(z, P[f"{fe}{i}.conv.bias"], P[f"{fe}{i}.layer_norm.weight"],
+                act, mean, rstd = ops.bias_layernorm_gelu(z, P[f"{fe}{i}.conv.bias"] if c["conv_bias"] else None, P[f"{fe}{i}.layer_norm.weight"],
                                                           P[f"{fe}{i}.layer_norm.bias"], EXTRACTOR_EPS)
                 if save:
                     ctx["conv"].append((a, z, (mean, rstd)))
@@ -373,14 +384,31 @@ class Wav2Vec2ForCTC(FlatModel):
                     ctx["conv"].append((a, z, None))
             a = act
         T = a.shape[1]
-        fp = pf + "feature_projection."
-        n, mean, rstd = ops.layernorm(a, P[fp + "layer_norm.weight"], P[fp + "layer_norm.bias"], c["layer_norm_eps"])
-        h = ops.linear(n, P[fp + "projection.weight"], P[fp + "projection.bias"])
+        h, kept = self._project(a)
         if vT is not None:
             ops.mask_rows(h, vT)                                    # the positional conv must see zeros past the utterance's last frame
         if save:
-            ctx["proj"] = (a, mean, rstd, n)
+            ctx["proj"] = kept
         return self._encode(h, ctx, vT, (B, L, T), v0)
+
+    def _project(self, a):
+        """The feature projection of the extractor's output a [B, T, C]: returns (h [B, T, H], what _project_bwd needs, batch-major).  A
+        model whose projection differs (HuBERT without its LayerNorm) overrides the pair."""
+        c, P = self.cfg, self.P
+        fp = self._prefix + "feature_projection."
+        n, mean, rstd = ops.layernorm(a, P[fp + "layer_norm.weight"], P[fp + "layer_norm.bias"], c["layer_norm_eps"])
+        h = ops.linear(n, P[fp + "projection.weight"], P[fp + "projection.bias"])
+        return h, (a, mean, rstd, n)
+
+    def _project_bwd(self, kept, dhs):
+        """Backward of _project (`kept` already cut to the active samples): accumulates its parameters' gradients, returns dL/da."""
+        P, G = self.P, self.G
+        a, mean, rstd, n = kept
+        fp = self._prefix + "feature_projection."
+        dn = self._lin_bwd(dhs, n, fp + "projection.weight", fp + "projection.bias")
+        da = torch.empty_like(dn)
+        ops.layernorm_bwd(a, P[fp + "layer_norm.weight"], mean, rstd, dn, da, G[fp + "layer_norm.weight"], G[fp + "layer_norm.bias"], dx_beta=0.0)
+        return da
 
     def _encode(self, h, ctx, vT, dims, v0):
         """The encoder and lm_head from the feature projection's output h [B, T, H] (rows past `vT` zeroed): fills ctx["pos"], ["layers"],
@@ -389,27 +417,15 @@ class Wav2Vec2ForCTC(FlatModel):
         c, P, pf = self.cfg, self.P, self._prefix
         save = ctx is not None
         B, L, T = dims
-        # positional conv embedding (grouped, weight-normed), GELU, residual, LayerNorm
-        pc = pf + "encoder.pos_conv_embed.conv."
-        H, K, G = c["hidden_size"], c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
-        cg, pad = H // G, K // 2
-        v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
-        parts = _wn_parts(K, cg)
-        w = ops.weight_norm(v, g) if parts == 1 else _wn_join(ops.weight_norm(_wn_split(v, parts), g), parts)   # [H, K, cg]
-        xg = ops.group_pack(h, G, pad)                              # [B, G, T + 2 pad, cg]
-        Tp = T + 2 * pad
-        yg = torch.empty(B, G, T, cg, device=h.device, dtype=torch.float32)
-        ops.gemm(xg, w, yg, trans_b=True, M=T, N=cg, K=K * cg, lda=cg, ldb=K * cg, ldc=cg, nb1=B, nb2=G,
-                 sa=(G * Tp * cg, Tp * cg), sb=(0, cg * K * cg), sc=(G * T * cg, T * cg))
-        pre = ops.group_unpack(yg, P[pc + "bias"], T, H)
-        pos = ops.gelu(pre)
+        # positional conv embedding, residual, LayerNorm
+        pos, kept = self._pos_embed(h, vT)
         hs = h.clone() if save else h
         ops.axpby(pos, hs, 1.0, 1.0)
         if self.stable_ln:
-            return self._encoder_stable(hs, ctx, (xg, w, pre), vT, (B, L, T), v0)
+            return self._encoder_stable(hs, ctx, kept, vT, (B, L, T), v0)
         h2, mean, rstd = ops.layernorm(hs, P[pf + "encoder.layer_norm.weight"], P[pf + "encoder.layer_norm.bias"], c["layer_norm_eps"])
         if save:
-            ctx["pos"] = (xg, w, pre, hs, mean, rstd)
+            ctx["pos"] = kept + (hs, mean, rstd)
             ctx["layers"] = []
         h = h2
         for l in range(c["num_hidden_layers"]):
@@ -433,6 +449,27 @@ class Wav2Vec2ForCTC(FlatModel):
             ctx["valid"] = (v0, vT)
         self._ctx = ctx
         return SimpleNamespace(logits=logits, frames=T)
+
+    def _pos_embed(self, h, vT):
+        """The positional embedding of h [B, T, H] (rows past `vT` are zero): returns (pos [B, T, H], a tuple of what _pos_embed_bwd needs).
+        Here wav2vec2's: one grouped, weight-normed conv, then GELU.  A model with another positional embedding (data2vec_audio_model.py)
+        overrides the pair."""
+        c, P, pf = self.cfg, self.P, self._prefix
+        B, T, _ = h.shape
+        pc = pf + "encoder.pos_conv_embed.conv."
+        H, K, G = c["hidden_size"], c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
+        cg, pad = H // G, K // 2
+        v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
+        parts = _wn_parts(K, cg)
+        w = ops.weight_norm(v, g) if parts == 1 else _wn_join(ops.weight_norm(_wn_split(v, parts), g), parts)   # [H, K, cg]
+        xg = ops.group_pack(h, G, pad)                              # [B, G, T + 2 pad, cg]
+        Tp = T + 2 * pad
+        yg = torch.empty(B, G, T, cg, device=h.device, dtype=torch.float32)
+        ops.gemm(xg, w, yg, trans_b=True, M=T, N=cg, K=K * cg, lda=cg, ldb=K * cg, ldc=cg, nb1=B, nb2=G,
+                 sa=(G * Tp * cg, Tp * cg), sb=(0, cg * K * cg), sc=(G * T * cg, T * cg))
+        pre = ops.group_unpack(yg, P[pc + "bias"], T, H)
+        pos = ops.gelu(pre)
+        return pos, (xg, w, pre)
 
     def _attention(self, h, l, vT):
         """Self-attention of layer l on h [B, T, H] up to (not including) the output projection: returns (qkv, S, O)."""
@@ -618,11 +655,7 @@ class Wav2Vec2ForCTC(FlatModel):
 
         dhs = self._backward_encoder(ctx, grad_logits, nb, cut)
         # feature projection
-        a, mean, rstd, n = cut(ctx["proj"])
-        fp = pf + "feature_projection."
-        dn = self._lin_bwd(dhs, n, fp + "projection.weight", fp + "projection.bias")
-        da = torch.empty_like(dn)
-        ops.layernorm_bwd(a, P[fp + "layer_norm.weight"], mean, rstd, dn, da, G[fp + "layer_norm.weight"], G[fp + "layer_norm.bias"], dx_beta=0.0)
+        da = self._project_bwd(cut(ctx["proj"]), dhs)
         # conv feature extractor
         fe = pf + "feature_extractor.conv_layers."
         for i in reversed(range(len(c["conv_kernel"]))):
@@ -633,8 +666,9 @@ class Wav2Vec2ForCTC(FlatModel):
             if self.layer_extractor:                                 # GELU', LayerNorm backward and the three column sums in one pass, dz over da
                 mean, rstd = norm
                 gw, gb, cb = (f"{fe}{i}.layer_norm.weight", f"{fe}{i}.layer_norm.bias", f"{fe}{i}.conv.bias")
-                dz = ops.bias_layernorm_gelu_bwd(z, P[cb], P[gw], P[gb], mean, rstd, da, *(G[n] if self.trainable(n) else None for n in (gw, gb, cb)),
-                                                 out=da)
+                has = (True, True, c["conv_bias"])                 # a model of the family may have no conv bias here (Data2Vec-Audio)
+                dz = ops.bias_layernorm_gelu_bwd(z, P[cb] if has[2] else None, P[gw], P[gb], mean, rstd, da,
+                                                 *(G[n] if h and self.trainable(n) else None for n, h in zip((gw, gb, cb), has)), out=da)
             elif i == 0:
                 mean, rstd, n0 = norm
                 dn0 = ops.gelu_bwd(n0, da)
@@ -699,19 +733,28 @@ class Wav2Vec2ForCTC(FlatModel):
             dh_in = self._attention_bwd(dO, qkv, S, h, l, nb, T, dr1)
             dh = dh_in
             ctx["layers"][l] = None
-        # encoder LayerNorm, positional conv
-        w = ctx["pos"][1]                                            # the normalised weight is not batch-indexed
-        xg, _, pre, hs, mean, rstd = cut(ctx["pos"])
-        pc = pf + "encoder.pos_conv_embed.conv."
-        K, Gn = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
-        cg, pad = H // Gn, K // 2
-        Tp = T + 2 * pad
+        # encoder LayerNorm, positional embedding
+        kept = ctx["pos"][:-3]
+        hs, mean, rstd = cut(ctx["pos"][-3:])
         if self.stable_ln:
             dhs = dx                                                 # dL/d(h + pos): no queued product reads it, so the pos path adds in place
         else:
             dhs = torch.empty_like(dh)
             ops.layernorm_bwd(hs, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dhs, G[pf + "encoder.layer_norm.weight"],
                               G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
+        return self._pos_embed_bwd(kept, dhs, nb, cut, vT)
+
+    def _pos_embed_bwd(self, kept, dhs, nb, cut, vT):
+        """Backward of _pos_embed: dhs [nb, T, H] is dL/d(h + pos); accumulates the embedding's parameter gradients, adds its path to dhs in
+        place and returns it = dL/dh (rows past `vT` zero).  `kept` is _pos_embed's tuple, uncut: `cut` trims what is batch-major."""
+        c, P, G, pf = self.cfg, self.P, self.G, self._prefix
+        T, H = dhs.shape[1], dhs.shape[2]
+        w = kept[1]                                                  # the normalised weight is not batch-indexed
+        xg, _, pre = cut(kept)
+        pc = pf + "encoder.pos_conv_embed.conv."
+        K, Gn = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
+        cg, pad = H // Gn, K // 2
+        Tp = T + 2 * pad
         dpre = ops.gelu_bwd(pre, dhs)
         ops.colsum(dpre, G[pc + "bias"], beta=1.0)
         dyg = ops.group_pack_grad(dpre, Gn, T)                       # [nb, G, T, cg]
@@ -724,13 +767,13 @@ class Wav2Vec2ForCTC(FlatModel):
         if parts == 1:
             ops.weight_norm_bwd(v, g, dw, G[pc + "parametrizations.weight.original1"], G[pc + "parametrizations.weight.original0"], beta=1.0)
         else:                                                        # rows wider than the kernel's LDS buffer: see _wn_split
-            dv = torch.zeros(parts * H, K, cg // parts, device=dh.device, dtype=torch.float32)
+            dv = torch.zeros(parts * H, K, cg // parts, device=dhs.device, dtype=torch.float32)
             ops.weight_norm_bwd(_wn_split(v, parts), g, _wn_split(dw, parts), dv, G[pc + "parametrizations.weight.original0"], beta=1.0)
             ops.axpby(_wn_join(dv, parts), G[pc + "parametrizations.weight.original1"], 1.0, 1.0)
-        dA = torch.empty(nb, Gn, T, K * cg, device=dh.device, dtype=torch.float32)
+        dA = torch.empty(nb, Gn, T, K * cg, device=dhs.device, dtype=torch.float32)
         ops.gemm(dyg, w, dA, M=T, N=K * cg, K=cg, lda=cg, ldb=K * cg, ldc=K * cg, nb1=nb, nb2=Gn, sa=(Gn * T * cg, T * cg),
                  sb=(0, cg * K * cg), sc=(Gn * T * K * cg, T * K * cg))
-        dxg = torch.empty(nb * Gn, Tp, cg, device=dh.device, dtype=torch.float32)
+        dxg = torch.empty(nb * Gn, Tp, cg, device=dhs.device, dtype=torch.float32)
         ops.col2im_1d(dA, dxg, nb * Gn, Tp, T, cg, K, 1)
         ops.group_unpack_grad(dxg.view(nb, Gn, Tp, cg), dhs, pad, beta=1.0)   # dh (pre-pos) = dhs (residual) + pos-conv path
         if vT is not None:

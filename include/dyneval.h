@@ -578,6 +578,31 @@ int dyn_weight_norm_fwd(const float* v, const float* g, float* w, int64_t rows, 
                         int64_t workspace_bytes, void* stream);
 int dyn_weight_norm_bwd(const float* v, const float* g, const float* dw, float* dv, float* dg, float beta, int64_t rows,
                         int64_t kw, int64_t cg, void* workspace, int64_t workspace_bytes, void* stream);
+/* One layer of Data2Vec-Audio's positional conv stack after its grouped conv GEMM.  The reference's loader,
+ * `AutoModelForCTC.from_pretrained(checkpoint)` (wav2vec2/lib.py:20-23), builds transformers' Data2VecAudioForCTC for such a checkpoint;
+ * `model(x).logits` (:163,413) and `loss.backward()` (:194,437) then run, `num_conv_pos_embeddings` times per step,
+ * Data2VecAudioPositionalConvLayer.forward (modeling_data2vec_audio.py: `self.conv` bias add, `transpose(1, 2)`, `self.layer_norm`
+ * = LayerNorm(H, elementwise_affine=False), `transpose(1, 2)`, `self.activation`) and its autograd.  Both entries work in the group-major
+ * layouts of the grouped GEMMs (G groups of cg = H / G channels), so no dyn_group_pack / _unpack launch stands between two layers.
+ * H % 256 == 0, H <= 1024, cg % 4 == 0, Tg >= T and non-null required pointers, else DYN_E_ARG:
+ *   fwd: row (b, t) = yg[b, g, t, 0:cg] for g = 0..G-1 side by side (yg [B, G, Tg, cg] as dyn_group_unpack takes it; not modified)
+ *        + bias [H]; out = gelu((row - mean) / sqrt(var + eps)), centred variance, exact erf GELU as dyn_gelu_fwd.  Written to `act`
+ *        [B, T, H] and / or to `xg_next` [B, G, T + 2 pad, cg], the NEXT layer's packed input, including its 2 pad zero rows per (b, g)
+ *        (either may be null, not both; both get the same bits).  mean / rstd [B T] are written for every row.  Rows t >= *valid_rows
+ *        (null = T; a device int32 scalar read when the kernel runs, as dyn_mask_rows) are zeros in both outputs.
+ *   bwd: recomputes xhat from yg, bias, mean, rstd; dn = dact * gelu'(xhat) with dact [B, T, H];
+ *        dyg [B, G, T, cg] = rstd * (dn - mean_H(dn) - xhat * mean_H(dn * xhat)): the layout the weight- and data-gradient GEMMs read
+ *        (replaces dyn_gelu_bwd + a LayerNorm backward + dyn_colsum + dyn_group_pack_grad); rows t >= *valid_rows are exact zeros.
+ *        dbias [H] = wgrad_beta * old + column sums of dyg, may be null (frozen; then no workspace is needed).  The sums go through
+ *        per-workgroup partial rows in `workspace` and the fixed-order reducer (bit-reproducible; recorded instead while a
+ *        dyn_reduce_defer context is open).
+ * No call synchronises or allocates: both are captured into the length buckets' hipGraphs. */
+int dyn_posconv_ln_gelu_fwd(const float* yg, const float* bias, float* act, float* xg_next, float* mean, float* rstd, int64_t B, int64_t T,
+                            int64_t Tg, int64_t H, int64_t G, int64_t pad, float eps, const int32_t* valid_rows, void* stream);
+int64_t dyn_posconv_ln_gelu_bwd_workspace_bytes(int64_t rows, int64_t H);
+int dyn_posconv_ln_gelu_bwd(const float* yg, const float* bias, const float* mean, const float* rstd, const float* dact, float* dyg,
+                            float* dbias, float wgrad_beta, int64_t B, int64_t T, int64_t Tg, int64_t H, int64_t G,
+                            const int32_t* valid_rows, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * WavLM attention: gated relative-position bias.  The reference's loader, `AutoModelForCTC.from_pretrained(checkpoint)`

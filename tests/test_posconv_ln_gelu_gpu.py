@@ -1,0 +1,212 @@
+"""dyn_posconv_ln_gelu_fwd / _bwd (one Data2Vec-Audio positional conv layer after its grouped GEMM: conv bias + non-affine LayerNorm(H) +
+GELU in one pass each way, in the grouped GEMMs' layouts) against float64 torch on the CPU — F.gelu(F.layer_norm(x + b, (H,))) and its
+autograd — in the conventions of test_bias_layernorm_gelu_gpu.py: forward 5e-6 and dyg 2e-5 as floors of kernel_refs.measured_tol (4 x
+torch's own fp32 error + floor), the bias column sum kernel_refs.wgrad_tol(5e-4, rows, 531), and measured_tol for it as well where a row
+mean of 50 makes the plain bound meaningless.  Every check prints `name: kernel error | torch fp32 error | bound` before it asserts."""
+import os
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import kernel_refs as K  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+EPS = 1e-5
+SHAPES = [(2, 7, 256, 16), (1, 33, 768, 16), (2, 18, 1024, 16), (1, 5, 256, 4)]       # (B, T, H, G)
+IDS = ["T7-below-pad-cg16", "H768-cg48", "H1024-NV4", "G4-cg64"]
+PAD, EXTRA = 9, 3             # the 19-tap layer's padding; yg rows per group beyond T (Tg > T)
+
+
+def _check(name, got, want, tol, e32=None, rel=False):
+    err = K.max_err(got, want, rel)
+    print(f"  {name}: kernel {err:.2e} | torch fp32 {'-' if e32 is None else format(e32, '.2e')} | bound {tol:.2e}")
+    assert err <= tol, f"{name}: {'rel' if rel else 'abs'} err {err} > {tol} (torch fp32: {e32})"
+
+
+def _measured(name, got, torch32, want, floor, rel=False):
+    tol, e32 = K.measured_tol(torch32, want, floor, rel)
+    _check(name, got, want, tol, e32, rel)
+
+
+def _bits_equal(a, b):
+    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
+    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def _inputs(B, T, H, G, seed, mean=0.3, std=2.0, extra=EXTRA):
+    """x [B, T, H] token-major and the same numbers as yg [B, G, T + extra, cg] (the extra rows hold NaN: never read)."""
+    g_ = K.gen(7000 + seed + B * T + H + G)
+    x = torch.randn(B, T, H, generator=g_) * std + mean
+    cg = H // G
+    yg = torch.full((B, G, T + extra, cg), float("nan"))
+    yg[:, :, :T] = x.view(B, T, G, cg).permute(0, 2, 1, 3)
+    bias = torch.randn(H, generator=g_)
+    dact = torch.randn(B, T, H, generator=g_)
+    old = torch.randn(H, generator=g_)
+    return x, yg.contiguous(), bias, dact, old
+
+
+def _torch_ref(x, bias, dact, valid, dtype):
+    """(act, mean, rstd, dx, dbias) from torch's own ops and autograd in `dtype`; rows >= valid are zeroed after the GELU (so they carry
+    no gradient), their statistics are those of the row all the same."""
+    xr, br = x.detach().to(dtype).clone().requires_grad_(), bias.detach().to(dtype).clone().requires_grad_()
+    v = xr + br
+    act = F.gelu(F.layer_norm(v, (x.shape[-1],), None, None, EPS))
+    keep = torch.zeros(x.shape[1], dtype=dtype)
+    keep[:x.shape[1] if valid is None else valid] = 1.0
+    act = act * keep[None, :, None]
+    act.backward(dact.to(dtype))
+    vd = v.detach()
+    return act.detach(), vd.mean(-1).reshape(-1), torch.rsqrt(vd.var(-1, unbiased=False) + EPS).reshape(-1), xr.grad, br.grad
+
+
+def _grouped(t, G):            # [B, T, H] -> [B, G, T, cg]
+    B, T, H = t.shape
+    return t.view(B, T, G, H // G).permute(0, 2, 1, 3).contiguous()
+
+
+def _packed(t, G, pad):        # [B, T, H] -> [B, G, T + 2 pad, cg] with zero rows
+    return F.pad(_grouped(t, G), (0, 0, pad, pad))
+
+
+def _vt(valid, cuda):
+    return None if valid is None else torch.tensor([valid], dtype=torch.int32, device=cuda)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+def test_forward_and_backward_against_float64(cuda, shape):
+    """Every shape with valid in {None, T, T - 5 (clamped at 0), 1}; Tg = T + 3.  The tail rows and the pad rows are exact zeros in both
+    forward outputs and the tail rows in dyg; each output alone and both together give the same bits; wgrad_beta 0 / 1 and a null dbias;
+    yg is left unmodified."""
+    from dynamic_asr_eval_amd import ops
+    B, T, H, G = shape
+    x, yg, bias, dact, old = _inputs(B, T, H, G, 0)
+    ygd, bd, dd = yg.to(cuda), bias.to(cuda), dact.to(cuda)
+    yg_before = ygd.clone()
+    wtol = K.wgrad_tol(5e-4, B * T, 531)
+    for valid in (None, T, max(T - 5, 0), 1):
+        tag = f"valid {valid}"
+        Tv = T if valid is None else valid
+        r64, r32 = _torch_ref(x, bias, dact, valid, torch.float64), _torch_ref(x, bias, dact, valid, torch.float32)
+        act, none, mean, rstd = ops.posconv_ln_gelu(ygd, bd, T, PAD, EPS, valid=_vt(valid, cuda), want_act=True, want_packed=False)
+        assert none is None and act.shape == (B, T, H)
+        none, xg, mean2, rstd2 = ops.posconv_ln_gelu(ygd, bd, T, PAD, EPS, valid=_vt(valid, cuda), want_act=False, want_packed=True)
+        assert none is None and xg.shape == (B, G, T + 2 * PAD, H // G)
+        act3, xg3, mean3, rstd3 = ops.posconv_ln_gelu(ygd, bd, T, PAD, EPS, valid=_vt(valid, cuda), want_act=True, want_packed=True)
+        assert _bits_equal(ygd, yg_before), "yg (the GEMM's output) must not be modified"
+        assert _bits_equal(act, act3) and _bits_equal(xg, xg3), "each output alone and both together must give the same bits"
+        assert _bits_equal(mean, mean2) and _bits_equal(mean, mean3) and _bits_equal(rstd, rstd2) and _bits_equal(rstd, rstd3)
+        assert _bits_equal(xg, _packed(act.cpu(), G, PAD)), "the packed output is the token-major one regrouped, with exact zero pad rows"
+        assert xg[:, :, :PAD].abs().max().item() == 0.0 and xg[:, :, PAD + T:].abs().max().item() == 0.0
+        if Tv < T:
+            assert act[:, Tv:].abs().max().item() == 0.0 and xg[:, :, PAD + Tv:].abs().max().item() == 0.0
+        assert torch.isfinite(act).all() and torch.isfinite(mean).all() and torch.isfinite(rstd).all()
+        _measured(f"act ({tag})", act, r32[0], r64[0], 5e-6)
+        _check(f"mean ({tag})", mean, r64[1], 5e-6)
+        _check(f"rstd rel ({tag})", rstd, r64[2], 5e-6, rel=True)
+        for wbeta in (0.0, 1.0):
+            db = old.to(cuda)
+            dyg = ops.posconv_ln_gelu_bwd(ygd, bd, mean, rstd, dd, db, wgrad_beta=wbeta, valid=_vt(valid, cuda))
+            assert dyg.shape == (B, G, T, H // G)
+            if Tv < T:
+                assert dyg[:, :, Tv:].abs().max().item() == 0.0
+            _measured(f"dyg ({tag}, wgrad_beta {wbeta:g})", dyg, _grouped(r32[3], G), _grouped(r64[3], G), 2e-5)
+            _check(f"dbias ({tag}, wgrad_beta {wbeta:g})", db, r64[4] + wbeta * old.double(), wtol)
+        frozen = ops.posconv_ln_gelu_bwd(ygd, bd, mean, rstd, dd, None, valid=_vt(valid, cuda))       # a null dbias: the same dyg
+        assert _bits_equal(frozen, dyg)
+        assert _bits_equal(ygd, yg_before)
+
+
+def test_row_mean_of_fifty(cuda):
+    """Row mean 50, unit variance: x - mean alone carries ulp(50) / 2 = 1.9e-6, so a sum-of-squares variance would lose five digits and
+    every bound is measured (4 x torch's fp32 error + the floor), the sibling file's rule for inputs that make the plain bounds meaningless."""
+    from dynamic_asr_eval_amd import ops
+    B, T, H, G = 3, 177, 512, 16
+    x, yg, bias, dact, old = _inputs(B, T, H, G, 1, mean=50.0, std=1.0, extra=0)
+    r64, r32 = _torch_ref(x, bias, dact, None, torch.float64), _torch_ref(x, bias, dact, None, torch.float32)
+    act, _, mean, rstd = ops.posconv_ln_gelu(yg.to(cuda), bias.to(cuda), T, PAD, EPS)
+    _measured("act", act, r32[0], r64[0], 5e-6)
+    _measured("mean", mean, r32[1], r64[1], 5e-6)
+    _measured("rstd (rel)", rstd, r32[2], r64[2], 5e-6, rel=True)
+    db = old.to(cuda)
+    dyg = ops.posconv_ln_gelu_bwd(yg.to(cuda), bias.to(cuda), mean, rstd, dact.to(cuda), db, wgrad_beta=0.0)
+    _measured("dyg", dyg, _grouped(r32[3], G), _grouped(r64[3], G), 2e-5)
+    _measured("dbias", db, r32[4], r64[4], K.wgrad_tol(5e-4, B * T, 531))
+
+
+def test_bad_shapes_and_null_arguments_are_argument_errors(cuda):
+    """H = 320 (not a multiple of 256), cg = 6 (H = 768, G = 128) and null arguments are refused on the host with DYN_E_ARG (-1) by both
+    entries, with a message that names the constraint, before any launch: the outputs stay untouched."""
+    from dynamic_asr_eval_amd import _lib, ops
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    ws = ops.workspace(cuda)
+    B, T = 2, 5
+    buf = torch.full((B * (T + 2 * PAD) * 1024,), 7.0, device=cuda)
+    src = torch.randn(B * T * 1024, device=cuda)
+    stat = torch.zeros(B * T, device=cuda)
+    for H, G, word in ((320, 16, b"256"), (768, 128, b"multiple of 4")):
+        rc = lib.dyn_posconv_ln_gelu_fwd(src.data_ptr(), src.data_ptr(), buf.data_ptr(), 0, stat.data_ptr(), stat.data_ptr(), B, T, T, H, G, PAD,
+                                         EPS, None, st)
+        assert rc == -1 and b"dyn_posconv_ln_gelu_fwd" in lib.dyn_last_error() and word in lib.dyn_last_error(), lib.dyn_last_error()
+        rc = lib.dyn_posconv_ln_gelu_bwd(src.data_ptr(), src.data_ptr(), stat.data_ptr(), stat.data_ptr(), src.data_ptr(), buf.data_ptr(), 0, 1.0,
+                                         B, T, T, H, G, None, ws.data_ptr(), ws.numel(), st)
+        assert rc == -1 and b"dyn_posconv_ln_gelu_bwd" in lib.dyn_last_error() and word in lib.dyn_last_error(), lib.dyn_last_error()
+    H, G = 256, 16
+    rc = lib.dyn_posconv_ln_gelu_fwd(src.data_ptr(), src.data_ptr(), 0, 0, stat.data_ptr(), stat.data_ptr(), B, T, T, H, G, PAD, EPS, None, st)
+    assert rc == -1 and b"null" in lib.dyn_last_error()                        # neither output wanted
+    rc = lib.dyn_posconv_ln_gelu_fwd(src.data_ptr(), 0, buf.data_ptr(), 0, stat.data_ptr(), stat.data_ptr(), B, T, T, H, G, PAD, EPS, None, st)
+    assert rc == -1 and b"null" in lib.dyn_last_error()                        # no bias
+    rc = lib.dyn_posconv_ln_gelu_bwd(src.data_ptr(), src.data_ptr(), stat.data_ptr(), stat.data_ptr(), 0, buf.data_ptr(), 0, 1.0, B, T, T, H, G,
+                                     None, ws.data_ptr(), ws.numel(), st)
+    assert rc == -1 and b"null" in lib.dyn_last_error()                        # no dact
+    rc = lib.dyn_posconv_ln_gelu_fwd(src.data_ptr(), src.data_ptr(), buf.data_ptr(), 0, stat.data_ptr(), stat.data_ptr(), B, T, T - 1, H, G, PAD,
+                                     EPS, None, st)
+    assert rc == -1 and b"Tg" in lib.dyn_last_error()                          # fewer yg rows than T
+    assert lib.dyn_posconv_ln_gelu_bwd_workspace_bytes(10, 768) == 3 * 768 * 4                    # ceil(10 / 4) partial rows
+    assert lib.dyn_posconv_ln_gelu_bwd_workspace_bytes(1 << 20, 1024) == 1024 * 1024 * 4          # at most 1024 workgroups
+    rc = lib.dyn_posconv_ln_gelu_bwd(src.data_ptr(), src.data_ptr(), stat.data_ptr(), stat.data_ptr(), src.data_ptr(), buf.data_ptr(),
+                                     stat.data_ptr(), 1.0, B, T, T, H, G, None, ws.data_ptr(), 3 * 256 * 4 - 1, st)
+    assert rc == -3                                                            # DYN_E_WORKSPACE
+    torch.cuda.synchronize()
+    assert (buf == 7.0).all() and (stat == 0.0).all()
+    with pytest.raises(ops.DynError):
+        ops.posconv_ln_gelu(torch.randn(1, 16, 5, 20, device=cuda), torch.randn(320, device=cuda), 5, PAD)
+    with pytest.raises(ops.DynError):
+        ops.posconv_ln_gelu(torch.randn(1, 128, 5, 6, device=cuda), torch.randn(768, device=cuda), 5, PAD)
+
+
+def test_reproducible_and_identical_under_reduce_defer(cuda):
+    """Two identical calls give bit-identical outputs (fixed-order column sums, no atomics), and the result with the reduction recorded
+    under ops.reduce_defer (as the model's backward runs it) is bit-identical to the direct call.  1031 rows: several workgroups and a tail."""
+    from dynamic_asr_eval_amd import ops
+    B, T, H, G = 1, 1031, 768, 16
+    x, yg, bias, dact, old = _inputs(B, T, H, G, 2, extra=0)
+    ygd, bd, dd = yg.to(cuda), bias.to(cuda), dact.to(cuda)
+    valid = _vt(1000, cuda)
+    a1, x1, m1, s1 = ops.posconv_ln_gelu(ygd, bd, T, PAD, EPS, valid=valid, want_packed=True)
+    a2, x2, m2, s2 = ops.posconv_ln_gelu(ygd, bd, T, PAD, EPS, valid=valid, want_packed=True)
+    assert _bits_equal(a1, a2) and _bits_equal(x1, x2) and _bits_equal(m1, m2) and _bits_equal(s1, s2)
+
+    def bwd(arena):
+        db = old.to(cuda)
+        with ops.reduce_defer(arena):
+            dyg = ops.posconv_ln_gelu_bwd(ygd, bd, m1, s1, dd, db, wgrad_beta=1.0, valid=valid)
+        return [dyg, db]
+
+    first, second = bwd(None), bwd(None)
+    arena = torch.empty(8 << 20, dtype=torch.uint8, device=cuda)
+    assert arena.data_ptr() % 256 == 0
+    deferred = bwd(arena)
+    for k, name in enumerate(("dyg", "dbias")):
+        assert _bits_equal(first[k], second[k]), f"{name}: two identical calls differ"
+        assert _bits_equal(first[k], deferred[k]), f"{name}: differs under ops.reduce_defer"
+    assert not _bits_equal(deferred[1], old)                # the recorded reduction did run at the flush
+    r64 = _torch_ref(x, bias, dact, 1000, torch.float64)
+    _check("dbias over 1031 rows", first[1], r64[4] + old.double(), K.wgrad_tol(5e-4, B * T, 531))
