@@ -140,6 +140,105 @@ __global__ __launch_bounds__(256) void blg_bwd_kernel(const float* __restrict__ 
     }
 }
 
+// The same two passes for the narrow extractors (SEW: conv_dim 64 and 128): C = 4 * LPR channels, a row on LPR = 16 or 32 lanes (one float4
+// each), so a wave64 holds RPW = 64 / LPR rows at a time and the row statistics are reductions over an aligned group of LPR lanes.  The
+// column sums: per lane over its rows, then over the wave's RPW row groups (xor 32, then 16: a fixed order), then over the 4 waves through
+// LDS in wave order, one partial row of C floats per workgroup.  A lane whose row is past the end loads nothing and stores nothing.
+template <int LPR>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int LPR>
+__device__ __forceinline__ float4 across_groups(float4 v) {
+#pragma unroll
+    for (int o = 32; o >= LPR; o >>= 1) {
+        v.x += __shfl_xor(v.x, o, 64); v.y += __shfl_xor(v.y, o, 64); v.z += __shfl_xor(v.z, o, 64); v.w += __shfl_xor(v.w, o, 64);
+    }
+    return v;
+}
+
+template <int LPR>
+__global__ __launch_bounds__(256) void blg_fwd_narrow_kernel(const float* __restrict__ z, const float* __restrict__ cbias,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              float* __restrict__ act, float* __restrict__ mean_out,
+                                                              float* __restrict__ rstd_out, int64_t rows, float eps) {
+    constexpr int C = 4 * LPR, RPW = 64 / LPR;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, cl = lane % LPR, sub = lane / LPR;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 g = ld4(gamma, cl), b = ld4(beta, cl), cb = cbias ? ld4(cbias, cl) : zero;
+    for (int64_t base = ((int64_t)blockIdx.x * WPB + w) * RPW; base < rows; base += (int64_t)gridDim.x * WPB * RPW) {
+        const int64_t row = base + sub;
+        const bool live = row < rows;
+        float4 v = live ? ld4(z + row * C, cl) : zero;
+        v.x += cb.x; v.y += cb.y; v.z += cb.z; v.w += cb.w;
+        const float mean = group_sum<LPR>(v.x + v.y + v.z + v.w) / C;
+        const float a0 = v.x - mean, a1 = v.y - mean, a2 = v.z - mean, a3 = v.w - mean;
+        const float rstd = rsqrtf(group_sum<LPR>(a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3) / C + eps);
+        if (!live) continue;
+        float4 o;
+        o.x = dyn::gelu_f(a0 * rstd * g.x + b.x); o.y = dyn::gelu_f(a1 * rstd * g.y + b.y);
+        o.z = dyn::gelu_f(a2 * rstd * g.z + b.z); o.w = dyn::gelu_f(a3 * rstd * g.w + b.w);
+        reinterpret_cast<float4*>(act + row * C)[cl] = o;
+        if (cl == 0) {
+            mean_out[row] = mean;
+            rstd_out[row] = rstd;
+        }
+    }
+}
+
+// dz may be dact itself: a lane reads exactly the elements it later writes.
+template <int LPR>
+__global__ __launch_bounds__(256) void blg_bwd_narrow_kernel(const float* __restrict__ z, const float* __restrict__ cbias,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                              const float* dact, float* dz, float* __restrict__ partial_g,
+                                                              float* __restrict__ partial_b, float* __restrict__ partial_c, int64_t rows) {
+    constexpr int C = 4 * LPR, RPW = 64 / LPR;
+    __shared__ float4 red[WPB][LPR];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, cl = lane % LPR, sub = lane / LPR;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 g = ld4(gamma, cl), b = ld4(beta, cl), cb = cbias ? ld4(cbias, cl) : zero;
+    float4 ag = zero, ab = zero, ac = zero;
+    for (int64_t base = ((int64_t)blockIdx.x * WPB + w) * RPW; base < rows; base += (int64_t)gridDim.x * WPB * RPW) {
+        const int64_t row = base + sub;
+        const bool live = row < rows;
+        const float mean = live ? mean_in[row] : 0.f, rstd = live ? rstd_in[row] : 0.f;
+        const float4 v = live ? ld4(z + row * C, cl) : zero, d = live ? ld4(dact + row * C, cl) : zero;
+        float4 xh, dn, gy;
+        xh.x = (v.x + cb.x - mean) * rstd; xh.y = (v.y + cb.y - mean) * rstd; xh.z = (v.z + cb.z - mean) * rstd; xh.w = (v.w + cb.w - mean) * rstd;
+        dn.x = d.x * dyn::gelu_grad(xh.x * g.x + b.x); dn.y = d.y * dyn::gelu_grad(xh.y * g.y + b.y);
+        dn.z = d.z * dyn::gelu_grad(xh.z * g.z + b.z); dn.w = d.w * dyn::gelu_grad(xh.w * g.w + b.w);
+        gy.x = dn.x * g.x; gy.y = dn.y * g.y; gy.z = dn.z * g.z; gy.w = dn.w * g.w;
+        const float s1 = group_sum<LPR>(gy.x + gy.y + gy.z + gy.w) / C;
+        const float s2 = group_sum<LPR>(gy.x * xh.x + gy.y * xh.y + gy.z * xh.z + gy.w * xh.w) / C;
+        if (!live) continue;     // (d = 0 there: nothing to add)
+        ag.x += dn.x * xh.x; ag.y += dn.y * xh.y; ag.z += dn.z * xh.z; ag.w += dn.w * xh.w;
+        ab.x += dn.x; ab.y += dn.y; ab.z += dn.z; ab.w += dn.w;
+        float4 o;
+        o.x = rstd * (gy.x - s1 - xh.x * s2); o.y = rstd * (gy.y - s1 - xh.y * s2);
+        o.z = rstd * (gy.z - s1 - xh.z * s2); o.w = rstd * (gy.w - s1 - xh.w * s2);
+        ac.x += o.x; ac.y += o.y; ac.z += o.z; ac.w += o.w;
+        reinterpret_cast<float4*>(dz + row * C)[cl] = o;
+    }
+    for (int pass = 0; pass < 3; ++pass) {
+        float* partial = pass == 0 ? partial_g : pass == 1 ? partial_b : partial_c;
+        if (!partial) continue;                                      // uniform over the grid
+        const float4 t0 = across_groups<LPR>(pass == 0 ? ag : pass == 1 ? ab : ac);
+        __syncthreads();
+        if (lane < LPR) red[w][lane] = t0;
+        __syncthreads();
+        if (w == 0 && lane < LPR) {
+            float4 t = red[0][lane];
+#pragma unroll
+            for (int k = 1; k < WPB; ++k) { t.x += red[k][lane].x; t.y += red[k][lane].y; t.z += red[k][lane].z; t.w += red[k][lane].w; }
+            reinterpret_cast<float4*>(partial + (int64_t)blockIdx.x * C)[lane] = t;
+        }
+    }
+}
+
 inline int bwd_blocks(int64_t rows) {
     int64_t g = dyn::cdiv(rows, WPB);
     if (g > MAX_BWD_BLOCKS) g = MAX_BWD_BLOCKS;
@@ -153,8 +252,8 @@ inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 extern "C" int dyn_bias_layernorm_gelu_fwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, float* act,
                                            float* mean, float* rstd, int64_t rows, int64_t C, float eps, void* stream) {
-    DYN_REQUIRE(z && gamma && beta && act && mean && rstd && rows >= 0 && C > 0 && C % 256 == 0, DYN_E_ARG,
-                "dyn_bias_layernorm_gelu_fwd: bad arguments (C=%lld must be a multiple of 256)", (long long)C);
+    DYN_REQUIRE(z && gamma && beta && act && mean && rstd && rows >= 0 && C > 0 && (C % 256 == 0 || C == 64 || C == 128), DYN_E_ARG,
+                "dyn_bias_layernorm_gelu_fwd: bad arguments (C=%lld must be a multiple of 256, or 64 or 128)", (long long)C);
     DYN_REQUIRE(aligned16(z) && aligned16(conv_bias) && aligned16(gamma) && aligned16(beta) && aligned16(act), DYN_E_ARG,
                 "dyn_bias_layernorm_gelu_fwd: operands must be 16-byte aligned");
     if (rows == 0) return DYN_OK;
@@ -162,6 +261,13 @@ extern "C" int dyn_bias_layernorm_gelu_fwd(const float* z, const float* conv_bia
     if (gq > 2048) gq = 2048;
     dim3 grid((unsigned)gq), blk(256);
     hipStream_t st = (hipStream_t)stream;
+    if (C < 256) {               // 64 / 128 channels: several rows per wave
+        int64_t gn = dyn::cdiv(rows, WPB * (C == 64 ? 4 : 2));
+        if (gn > 2048) gn = 2048;
+        if (C == 64) hipLaunchKernelGGL(blg_fwd_narrow_kernel<16>, dim3((unsigned)gn), blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps);
+        else hipLaunchKernelGGL(blg_fwd_narrow_kernel<32>, dim3((unsigned)gn), blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps);
+        return dyn::check_launch("dyn_bias_layernorm_gelu_fwd");
+    }
     switch (C / 256) {
         case 1: hipLaunchKernelGGL(blg_fwd_kernel<1>, grid, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps); break;
         case 2: hipLaunchKernelGGL(blg_fwd_kernel<2>, grid, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps); break;
@@ -180,12 +286,12 @@ extern "C" int dyn_bias_layernorm_gelu_bwd(const float* z, const float* conv_bia
                                            const float* mean, const float* rstd, const float* dact, float* dz, float* dgamma,
                                            float* dbeta, float* dconv_bias, float wgrad_beta, int64_t rows, int64_t C,
                                            void* workspace, int64_t workspace_bytes, void* stream) {
-    DYN_REQUIRE(z && gamma && beta && mean && rstd && dact && dz && rows >= 0 && C > 0 && C % 256 == 0, DYN_E_ARG,
-                "dyn_bias_layernorm_gelu_bwd: bad arguments (C=%lld must be a multiple of 256)", (long long)C);
+    DYN_REQUIRE(z && gamma && beta && mean && rstd && dact && dz && rows >= 0 && C > 0 && (C % 256 == 0 || C == 64 || C == 128), DYN_E_ARG,
+                "dyn_bias_layernorm_gelu_bwd: bad arguments (C=%lld must be a multiple of 256, or 64 or 128)", (long long)C);
     DYN_REQUIRE(aligned16(z) && aligned16(conv_bias) && aligned16(gamma) && aligned16(beta) && aligned16(dact) && aligned16(dz), DYN_E_ARG,
                 "dyn_bias_layernorm_gelu_bwd: operands must be 16-byte aligned");
     if (rows == 0) return DYN_OK;
-    const int nb = bwd_blocks(rows);
+    const int nb = bwd_blocks(C < 256 ? dyn::cdiv(rows, C == 64 ? 4 : 2) : rows);     // narrow: 4 or 2 rows per wave, so fewer workgroups
     const int64_t need = dyn_bias_layernorm_gelu_bwd_workspace_bytes(rows, C);
     DYN_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= need, DYN_E_WORKSPACE,
                 "dyn_bias_layernorm_gelu_bwd: workspace too small");
@@ -197,7 +303,9 @@ extern "C" int dyn_bias_layernorm_gelu_bwd(const float* z, const float* conv_bia
     float* wc = dconv_bias ? pc : nullptr;
     dim3 grid(nb), blk(256);
     hipStream_t st = (hipStream_t)stream;
-    switch (C / 256) {
+    if (C == 64) hipLaunchKernelGGL(blg_bwd_narrow_kernel<16>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows);
+    else if (C == 128) hipLaunchKernelGGL(blg_bwd_narrow_kernel<32>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows);
+    else switch (C / 256) {
         case 1: hipLaunchKernelGGL(blg_bwd_kernel<1>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows); break;
         case 2: hipLaunchKernelGGL(blg_bwd_kernel<2>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows); break;
         case 3: hipLaunchKernelGGL(blg_bwd_kernel<3>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows); break;

@@ -1488,3 +1488,99 @@ def posconv_ln_gelu_bwd(yg, bias, mean, rstd, dact, dbias, wgrad_beta=1.0, valid
                                        _opt(dbias, "dbias"), wgrad_beta, B, T, Tg, H, G, _valid_ptr(valid, "posconv_ln_gelu_bwd"),
                                        ws.data_ptr(), ws.numel(), _stream()), "dyn_posconv_ln_gelu_bwd")
     return dyg
+
+
+def _squeeze_dims(who, h, yg, s):
+    if not isinstance(s, int) or not 1 <= s <= 4:
+        raise DynError(f"{who}: squeeze factor s = {s} must be 1, 2, 3 or 4")
+    if h.dim() != 3 or yg.dim() != 4:
+        raise DynError(f"{who}: h must be [B, T, H] and yg [B, G, Tg, cg]")
+    B, T, H = h.shape
+    G, Tg, cg = yg.shape[1:]
+    if H % 256 or H > 1024:
+        raise DynError(f"{who}: H = {H} must be a multiple of 256 up to 1024")
+    if cg % 4:
+        raise DynError(f"{who}: cg = {cg} channels per group must be a multiple of 4")
+    if yg.shape[0] != B or G * cg != H or Tg < T // s:
+        raise DynError(f"{who}: yg {tuple(yg.shape)} does not hold T // s = {T // s} rows of the {H} channels of h {tuple(h.shape)}")
+    return B, T, H, G, Tg, cg
+
+
+def squeeze_ln(h, yg, bias, gamma, beta, s, eps=1e-5, valid=None):
+    """The front of SEW's squeezed encoder after the strided positional conv's grouped GEMM: z [B, T // s, H] = LayerNorm_H(the mean of s
+    frames of h [B, T, H] + gelu(rows of yg [B, G, Tg >= T // s, cg] + bias)) * gamma + beta.  h and yg are left unmodified.  Returns (z,
+    mean [B T2], rstd [B T2]); rows >= `valid` (device int32 scalar, squeezed frames) of z are zeros."""
+    _cc(h, "squeeze_ln.h"); _cc(yg, "squeeze_ln.yg")
+    B, T, H, G, Tg, cg = _squeeze_dims("squeeze_ln", h, yg, s)
+    for t, n in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        if _cc(t, "squeeze_ln." + n).numel() != H:
+            raise DynError(f"squeeze_ln: {n} must have H = {H} elements")
+    T2 = T // s
+    z = torch.empty(B, T2, H, device=h.device, dtype=F32)
+    mean = torch.empty(B * T2, device=h.device, dtype=F32)
+    rstd = torch.empty(B * T2, device=h.device, dtype=F32)
+    check(_L().dyn_squeeze_ln_fwd(h.data_ptr(), yg.data_ptr(), bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(), z.data_ptr(), mean.data_ptr(),
+                                  rstd.data_ptr(), B, T, Tg, H, G, s, eps, _valid_ptr(valid, "squeeze_ln"), _stream()), "dyn_squeeze_ln_fwd")
+    return z, mean, rstd
+
+
+def squeeze_ln_bwd(h, yg, bias, gamma, mean, rstd, dz, s, dgamma, dbeta, dbias, wgrad_beta=1.0, valid=None):
+    """Backward of squeeze_ln from h, yg, bias, mean, rstd (the pre-LayerNorm row is recomputed) and dz [B, T // s, H]: returns (dh [B, T, H],
+    dyg [B, G, T // s, cg]): dh holds the pool's path only (rows >= s * `valid` and rows >= s (T // s) exact zeros), dyg is the layout the
+    weight- and data-gradient GEMMs read (rows >= `valid` exact zeros).  dgamma / dbeta / dbias = wgrad_beta * old + column sums, or None
+    (frozen)."""
+    _cc(h, "squeeze_ln_bwd.h"); _cc(yg, "squeeze_ln_bwd.yg"); _cc(bias, "squeeze_ln_bwd.bias"); _cc(gamma, "squeeze_ln_bwd.gamma")
+    _cc(mean, "squeeze_ln_bwd.mean"); _cc(rstd, "squeeze_ln_bwd.rstd"); _cc(dz, "squeeze_ln_bwd.dz")
+    B, T, H, G, Tg, cg = _squeeze_dims("squeeze_ln_bwd", h, yg, s)
+    T2 = T // s
+    if tuple(dz.shape) != (B, T2, H) or mean.numel() != B * T2 or rstd.numel() != B * T2 or bias.numel() != H or gamma.numel() != H:
+        raise DynError("squeeze_ln_bwd: dz / mean / rstd / bias / gamma do not match h and s")
+    for t, n in ((dgamma, "dgamma"), (dbeta, "dbeta"), (dbias, "dbias")):
+        if t is not None and t.numel() != H:
+            raise DynError(f"squeeze_ln_bwd: {n} must have H elements")
+    dh = torch.empty(B, T, H, device=h.device, dtype=F32)
+    dyg = torch.empty(B, G, T2, cg, device=h.device, dtype=F32)
+    ws = workspace(h.device)
+    check(_L().dyn_squeeze_ln_bwd(h.data_ptr(), yg.data_ptr(), bias.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dz.data_ptr(),
+                                  dh.data_ptr(), dyg.data_ptr(), _opt(dgamma, "dgamma"), _opt(dbeta, "dbeta"), _opt(dbias, "dbias"), wgrad_beta,
+                                  B, T, Tg, H, G, s, _valid_ptr(valid, "squeeze_ln_bwd"), ws.data_ptr(), ws.numel(), _stream()),
+          "dyn_squeeze_ln_bwd")
+    return dh, dyg
+
+
+def _unsqueeze_dims(who, u, T, s):
+    if not isinstance(s, int) or not 1 <= s <= 4:
+        raise DynError(f"{who}: squeeze factor s = {s} must be 1, 2, 3 or 4")
+    if u.dim() != 3 or u.shape[2] % s or (u.shape[2] // s) % 4:
+        raise DynError(f"{who}: u must be [B, T2, s H] with H a multiple of 4")
+    B, T2, sH = u.shape
+    if T2 != T // s:
+        raise DynError(f"{who}: u holds {T2} squeezed frames, T // s = {T} // {s} = {T // s} are expected")
+    return B, T2, sH // s
+
+
+def unsqueeze_act(u, T, s, valid=None):
+    """The back of SEW's squeezed encoder after the upsampling projection u [B, T // s, s H] (bias added): [B, T, H] with gelu(u) in rows
+    < s (T // s), each squeezed frame's s H channels as s frames, and exact zeros after; rows >= s * `valid` are zeros too."""
+    _cc(u, "unsqueeze_act.u")
+    B, T2, H = _unsqueeze_dims("unsqueeze_act", u, T, s)
+    out = torch.empty(B, T, H, device=u.device, dtype=F32)
+    check(_L().dyn_unsqueeze_act_fwd(u.data_ptr(), out.data_ptr(), B, T, H, s, _valid_ptr(valid, "unsqueeze_act"), _stream()),
+          "dyn_unsqueeze_act_fwd")
+    return out
+
+
+def unsqueeze_act_bwd(u, d, s, valid=None):
+    """Backward of unsqueeze_act: du [B, T // s, s H] = d * gelu'(u) with d [B, T, H]; rows >= `valid` exact zeros, d is read below s * `valid`
+    only."""
+    _cc(u, "unsqueeze_act_bwd.u"); _cc(d, "unsqueeze_act_bwd.d")
+    if d.dim() != 3:
+        raise DynError("unsqueeze_act_bwd: d must be [B, T, H]")
+    T = d.shape[1]
+    B, T2, H = _unsqueeze_dims("unsqueeze_act_bwd", u, T, s)
+    if tuple(d.shape) != (B, T, H):
+        raise DynError("unsqueeze_act_bwd: d does not match u")
+    du = torch.empty_like(u)
+    check(_L().dyn_unsqueeze_act_bwd(u.data_ptr(), d.data_ptr(), du.data_ptr(), B, T, H, s, _valid_ptr(valid, "unsqueeze_act_bwd"), _stream()),
+          "dyn_unsqueeze_act_bwd")
+    return du

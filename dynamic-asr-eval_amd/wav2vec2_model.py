@@ -156,6 +156,8 @@ class Wav2Vec2ForCTC(FlatModel):
     # parameter list, and the two attention hooks _softmax / _softmax_bwd; a model with another encoder (wav2vec2_conformer_model) also the
     # names of the q | k | v projections inside a layer and the two encoder hooks _encode / _backward_encoder; a model with another positional
     # embedding (data2vec_audio_model) the pair _pos_embed / _pos_embed_bwd, one with another feature projection (hubert_model) _project / _project_bwd
+    # a model whose layers run at another frame rate (sew_model) _project / _project_bwd and _encode / _backward_encoder around the shared
+    # _post_ln_layers / _post_ln_layers_bwd and _pos_weight / _pos_weight_bwd, plus _fill_valid for its own valid-length scalar
     _prefix = "wav2vec2."
     _qkv_fmt = "attention.{}_proj"
     _make_config = staticmethod(make_config)
@@ -168,8 +170,8 @@ class Wav2Vec2ForCTC(FlatModel):
         assert H % 256 == 0 and c["conv_dim"][-1] % 256 == 0, "LayerNorm kernels need C % 256 == 0"
         self.layer_extractor = c["feat_extract_norm"] == "layer"
         self.stable_ln = c["do_stable_layer_norm"]
-        if self.layer_extractor and any(d % 256 for d in c["conv_dim"]):
-            raise ops.DynError(f"feat_extract_norm=\"layer\" needs every conv_dim to be a multiple of 256 (got {c['conv_dim']})")
+        if self.layer_extractor and any(d % 256 and d not in (64, 128) for d in c["conv_dim"]):
+            raise ops.DynError(f"feat_extract_norm=\"layer\" needs every conv_dim to be 64, 128 or a multiple of 256 (got {c['conv_dim']})")
         spec = self._param_spec(c, pf)
         super().__init__([(n, shape) for n, shape, _ in spec], device)
         slots = self._slots
@@ -343,12 +345,16 @@ class Wav2Vec2ForCTC(FlatModel):
         if L < ent["len"]:
             ent["in"][:, L:ent["len"]].zero_()
         ent["len"] = L                                   # (beyond the previous utterance's end the buffer is still zero)
-        cl = self.conv_lengths(L)
-        self._valid[0:1].fill_(cl[0])                    # (fills, not a pageable upload: that would block the host on this stream and stall the
-        self._valid[-1:].fill_(cl[-1])                   #  other chains of wav2vec2_lib.dynamic_eval_su_many)
+        self._fill_valid(self.conv_lengths(L))
         ent["graph"].replay()
         self._ctx, self._ctx_static, self._ctx_key = (ent["ctx"] if ent["ctx"] is not None else _RELEASED), True, key
         return SimpleNamespace(logits=ent["out"], frames=T)
+
+    def _fill_valid(self, cl):
+        """The utterance's frame counts `cl` (conv_lengths) into the device scalars the captured kernels read.  A model whose encoder runs at
+        another frame rate (sew_model.py) adds its own."""
+        self._valid[0:1].fill_(cl[0])                    # (fills, not a pageable upload: that would block the host on this stream and stall the
+        self._valid[-1:].fill_(cl[-1])                   #  other chains of wav2vec2_lib.dynamic_eval_su_many)
 
     def _forward_eager(self, x):
         c, P, pf = self.cfg, self.P, self._prefix
@@ -426,8 +432,22 @@ class Wav2Vec2ForCTC(FlatModel):
         h2, mean, rstd = ops.layernorm(hs, P[pf + "encoder.layer_norm.weight"], P[pf + "encoder.layer_norm.bias"], c["layer_norm_eps"])
         if save:
             ctx["pos"] = kept + (hs, mean, rstd)
+        h = self._post_ln_layers(h2, ctx, vT)
+        logits = ops.linear(h, P["lm_head.weight"], P["lm_head.bias"])
+        if save:
+            ctx["head"] = h
+            ctx["dims"] = (B, L, T)
+            ctx["valid"] = (v0, vT)
+        self._ctx = ctx
+        return SimpleNamespace(logits=logits, frames=T)
+
+    def _post_ln_layers(self, h, ctx, vT):
+        """The post-LN transformer layers (transformers Wav2Vec2EncoderLayer) on h [B, T, H], keys past `vT` masked: returns the last layer's
+        output and fills ctx["layers"] for _post_ln_layers_bwd.  Shared with a model whose layers run at another frame count (sew_model.py)."""
+        c, P, pf = self.cfg, self.P, self._prefix
+        save = ctx is not None
+        if save:
             ctx["layers"] = []
-        h = h2
         for l in range(c["num_hidden_layers"]):
             p = f"{pf}encoder.layers.{l}."
             qkv, S, O = self._attention(h, l, vT)
@@ -442,13 +462,7 @@ class Wav2Vec2ForCTC(FlatModel):
             if save:
                 ctx["layers"].append((h, qkv, S, O, r1, m1, s1, h1, u, ga, r2, m2, s2))
             h = h2
-        logits = ops.linear(h, P["lm_head.weight"], P["lm_head.bias"])
-        if save:
-            ctx["head"] = h
-            ctx["dims"] = (B, L, T)
-            ctx["valid"] = (v0, vT)
-        self._ctx = ctx
-        return SimpleNamespace(logits=logits, frames=T)
+        return h
 
     def _pos_embed(self, h, vT):
         """The positional embedding of h [B, T, H] (rows past `vT` are zero): returns (pos [B, T, H], a tuple of what _pos_embed_bwd needs).
@@ -459,9 +473,7 @@ class Wav2Vec2ForCTC(FlatModel):
         pc = pf + "encoder.pos_conv_embed.conv."
         H, K, G = c["hidden_size"], c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
         cg, pad = H // G, K // 2
-        v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
-        parts = _wn_parts(K, cg)
-        w = ops.weight_norm(v, g) if parts == 1 else _wn_join(ops.weight_norm(_wn_split(v, parts), g), parts)   # [H, K, cg]
+        w = self._pos_weight()                                      # [H, K, cg]
         xg = ops.group_pack(h, G, pad)                              # [B, G, T + 2 pad, cg]
         Tp = T + 2 * pad
         yg = torch.empty(B, G, T, cg, device=h.device, dtype=torch.float32)
@@ -470,6 +482,30 @@ class Wav2Vec2ForCTC(FlatModel):
         pre = ops.group_unpack(yg, P[pc + "bias"], T, H)
         pos = ops.gelu(pre)
         return pos, (xg, w, pre)
+
+    def _pos_weight(self):
+        """The positional conv's weight [H, K, cg] from its weight-norm parameters."""
+        c, P = self.cfg, self.P
+        pc = self._prefix + "encoder.pos_conv_embed.conv."
+        K, cg = c["num_conv_pos_embeddings"], c["hidden_size"] // c["num_conv_pos_embedding_groups"]
+        v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
+        parts = _wn_parts(K, cg)
+        return ops.weight_norm(v, g) if parts == 1 else _wn_join(ops.weight_norm(_wn_split(v, parts), g), parts)
+
+    def _pos_weight_bwd(self, dw):
+        """Backward of _pos_weight: adds the weight-norm parameters' gradients given dw [H, K, cg]."""
+        c, P, G = self.cfg, self.P, self.G
+        pc = self._prefix + "encoder.pos_conv_embed.conv."
+        H, K = c["hidden_size"], c["num_conv_pos_embeddings"]
+        cg = H // c["num_conv_pos_embedding_groups"]
+        v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
+        parts = _wn_parts(K, cg)
+        if parts == 1:
+            ops.weight_norm_bwd(v, g, dw, G[pc + "parametrizations.weight.original1"], G[pc + "parametrizations.weight.original0"], beta=1.0)
+        else:                                                        # rows wider than the kernel's LDS buffer: see _wn_split
+            dv = torch.zeros(parts * H, K, cg // parts, device=dw.device, dtype=torch.float32)
+            ops.weight_norm_bwd(_wn_split(v, parts), g, _wn_split(dw, parts), dv, G[pc + "parametrizations.weight.original0"], beta=1.0)
+            ops.axpby(_wn_join(dv, parts), G[pc + "parametrizations.weight.original1"], 1.0, 1.0)
 
     def _attention(self, h, l, vT):
         """Self-attention of layer l on h [B, T, H] up to (not including) the output projection: returns (qkv, S, O)."""
@@ -716,7 +752,24 @@ class Wav2Vec2ForCTC(FlatModel):
             ops.layernorm_bwd(x, P[p + "layer_norm.weight"], m1, s1, dn1, dx, G[p + "layer_norm.weight"], G[p + "layer_norm.bias"],
                               dx_beta=1.0, dx_in=dr1)
             ctx["layers"][l] = None
-        for l in reversed(() if self.stable_ln else range(c["num_hidden_layers"])):
+        if not self.stable_ln:
+            dh = self._post_ln_layers_bwd(ctx, dh, nb, T, cut)
+        # encoder LayerNorm, positional embedding
+        kept = ctx["pos"][:-3]
+        hs, mean, rstd = cut(ctx["pos"][-3:])
+        if self.stable_ln:
+            dhs = dx                                                 # dL/d(h + pos): no queued product reads it, so the pos path adds in place
+        else:
+            dhs = torch.empty_like(dh)
+            ops.layernorm_bwd(hs, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dhs, G[pf + "encoder.layer_norm.weight"],
+                              G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
+        return self._pos_embed_bwd(kept, dhs, nb, cut, vT)
+
+    def _post_ln_layers_bwd(self, ctx, dh, nb, T, cut):
+        """Backward of _post_ln_layers from dh [nb, T, H], the gradient of its output: accumulates the layers' gradients, returns the
+        gradient of its input.  Entries of ctx["layers"] are dropped as they are used."""
+        c, P, G, pf = self.cfg, self.P, self.G, self._prefix
+        for l in reversed(range(c["num_hidden_layers"])):
             p = f"{pf}encoder.layers.{l}."
             h, qkv, S, O, r1, m1, s1, h1, u, ga, r2, m2, s2 = cut(ctx["layers"][l])
             dr2 = torch.empty_like(dh)
@@ -733,16 +786,7 @@ class Wav2Vec2ForCTC(FlatModel):
             dh_in = self._attention_bwd(dO, qkv, S, h, l, nb, T, dr1)
             dh = dh_in
             ctx["layers"][l] = None
-        # encoder LayerNorm, positional embedding
-        kept = ctx["pos"][:-3]
-        hs, mean, rstd = cut(ctx["pos"][-3:])
-        if self.stable_ln:
-            dhs = dx                                                 # dL/d(h + pos): no queued product reads it, so the pos path adds in place
-        else:
-            dhs = torch.empty_like(dh)
-            ops.layernorm_bwd(hs, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dhs, G[pf + "encoder.layer_norm.weight"],
-                              G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
-        return self._pos_embed_bwd(kept, dhs, nb, cut, vT)
+        return dh
 
     def _pos_embed_bwd(self, kept, dhs, nb, cut, vT):
         """Backward of _pos_embed: dhs [nb, T, H] is dL/d(h + pos); accumulates the embedding's parameter gradients, adds its path to dhs in
@@ -762,14 +806,7 @@ class Wav2Vec2ForCTC(FlatModel):
         for b in range(nb):                                          # dw[g] += dyg[b, g]^T rows(xg[b, g])
             ops.gemm(dyg, xg, dw, trans_a=True, M=cg, N=K * cg, K=T, lda=cg, ldb=cg, ldc=K * cg, nb1=1, nb2=Gn,
                      sa=(0, T * cg), sb=(0, Tp * cg), sc=(0, cg * K * cg), a_off=b * Gn * T * cg, b_off=b * Gn * Tp * cg, beta=1.0)
-        v, g = P[pc + "parametrizations.weight.original1"], P[pc + "parametrizations.weight.original0"]
-        parts = _wn_parts(K, cg)
-        if parts == 1:
-            ops.weight_norm_bwd(v, g, dw, G[pc + "parametrizations.weight.original1"], G[pc + "parametrizations.weight.original0"], beta=1.0)
-        else:                                                        # rows wider than the kernel's LDS buffer: see _wn_split
-            dv = torch.zeros(parts * H, K, cg // parts, device=dhs.device, dtype=torch.float32)
-            ops.weight_norm_bwd(_wn_split(v, parts), g, _wn_split(dw, parts), dv, G[pc + "parametrizations.weight.original0"], beta=1.0)
-            ops.axpby(_wn_join(dv, parts), G[pc + "parametrizations.weight.original1"], 1.0, 1.0)
+        self._pos_weight_bwd(dw)
         dA = torch.empty(nb, Gn, T, K * cg, device=dhs.device, dtype=torch.float32)
         ops.gemm(dyg, w, dA, M=T, N=K * cg, K=cg, lda=cg, ldb=K * cg, ldc=K * cg, nb1=nb, nb2=Gn, sa=(Gn * T * cg, T * cg),
                  sb=(0, cg * K * cg), sc=(Gn * T * K * cg, T * K * cg))

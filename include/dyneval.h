@@ -534,7 +534,7 @@ int dyn_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* st
  * large-robust, XLSR), which the reference reaches through the same `AutoModelForCTC.from_pretrained(checkpoint)` (wav2vec2/lib.py:20-23)
  * and `model(input_values).logits` (:163,413) / `loss.backward()` (:194,437).  Replaces, after the bias-free conv GEMM, the rest of
  * transformers' Wav2Vec2LayerNormConvLayer.forward (modeling_wav2vec2.py: `self.conv` bias add, `transpose`, `self.layer_norm`,
- * `transpose`, `self.activation`) and its autograd in one pass each way over rows x C (C % 256 == 0 else DYN_E_ARG; C <= 1024):
+ * `transpose`, `self.activation`) and its autograd in one pass each way over rows x C (C % 256 == 0, or C = 64 / 128: SEW's narrow extractor layers, several rows per wave; else DYN_E_ARG; C <= 1024):
  *   fwd: act = gelu(LN(z + conv_bias)), exact erf GELU as dyn_gelu_fwd; writes mean / rstd [rows]; z is not modified; conv_bias may be null.
  *   bwd: recomputes xhat and n = xhat * gamma + beta from z, mean, rstd (the normalised tensor is never stored); dn = dact * gelu'(n);
  *        dz = LayerNorm backward of dn (dz may be dact itself); dgamma = sum dn * xhat, dbeta = sum dn, dconv_bias = sum dz over the rows,
@@ -603,6 +603,45 @@ int64_t dyn_posconv_ln_gelu_bwd_workspace_bytes(int64_t rows, int64_t H);
 int dyn_posconv_ln_gelu_bwd(const float* yg, const float* bias, const float* mean, const float* rstd, const float* dact, float* dyg,
                             float* dbias, float wgrad_beta, int64_t B, int64_t T, int64_t Tg, int64_t H, int64_t G,
                             const int32_t* valid_rows, void* workspace, int64_t workspace_bytes, void* stream);
+/* The two ends of SEW's squeezed encoder.  The reference's loader, `AutoModelForCTC.from_pretrained(checkpoint)` (wav2vec2/lib.py:20-23),
+ * builds transformers' SEWForCTC for a SEW checkpoint; `model(x).logits` (:163,413) and `loss.backward()` (:194,437) then run
+ * SEWEncoder.forward (modeling_sew.py) and its autograd.  T2 = T / s frames (s = squeeze_factor in 1..4, else DYN_E_ARG naming it), G groups
+ * of cg = H / G channels; for the two squeeze entries H % 256 == 0, H <= 1024, cg % 4 == 0, Tg >= T2 and non-null required pointers, for the
+ * two unsqueeze entries H % 4 == 0, else DYN_E_ARG.  `valid_rows` (null = T2; a device int32 scalar read when the kernel runs, as
+ * dyn_mask_rows) counts SQUEEZED frames.
+ *   dyn_squeeze_ln_fwd      SEWEncoder.forward from `position_embeddings = self.pos_conv_embed(hidden_states)` AFTER its conv's product
+ *                           (the bias add inside `self.conv`, SEWSamePadLayer, `self.activation`), `self.pool(hidden_states)` =
+ *                           AvgPool1d(s, s), `pooled_hidden_states[..., :min_length] + position_embeddings[..., :min_length]`, the two
+ *                           transposes and `self.layer_norm`: z [B, T2, H] = LayerNorm_H(mean_j h[b, s t + j] + gelu(yg[b, g, t, 0:cg] for
+ *                           g = 0..G-1 side by side + bias)) * gamma + beta, with h [B, T, H] and yg [B, G, Tg, cg] the strided grouped GEMM's
+ *                           output (as dyn_group_unpack takes it); neither is modified.  Centred variance, exact erf GELU as dyn_gelu_fwd.
+ *                           mean / rstd [B T2] are written for every row; rows t >= *valid_rows of z are zeros.
+ *   dyn_squeeze_ln_bwd      its autograd: the pre-LayerNorm row is recomputed from h, yg, bias; dsum = the LayerNorm backward of dz [B, T2, H];
+ *                           dh [B, T, H] rows s t + j = dsum[t] / s, rows >= s T2 and rows >= s * *valid_rows exact zeros (fully written);
+ *                           dyg [B, G, T2, cg] = dsum * gelu'(yg + bias), the layout the weight- and data-gradient GEMMs read, rows >=
+ *                           *valid_rows exact zeros.  dgamma / dbeta / dbias [H] = wgrad_beta * old + column sums of dz * xhat, dz, dyg over the
+ *                           valid rows; each may be null (frozen; with all three null no workspace is needed; else dyn_squeeze_ln_bwd_workspace_bytes(B * (T2 + 1), H),
+ *                           the rows the kernel walks).  The sums go through
+ *                           per-workgroup partial rows in `workspace` and the fixed-order reducer (bit-reproducible; recorded instead while
+ *                           a dyn_reduce_defer context is open).
+ *   dyn_unsqueeze_act_fwd   SEWUpsampling.forward after `self.projection` (`self.activation`, the two `reshape`s) and SEWEncoder.forward's
+ *                           `nn.functional.pad(hidden_states, (0, 0, 0, n_input_timesteps - hidden_states.shape[1]))`: out [B, T, H] rows
+ *                           t < s T2 = gelu(u[b, t / s, (t % s) H : (t % s + 1) H]) with u [B, T2, s H] (bias already added), rows >= s T2 and
+ *                           rows >= s * *valid_rows exact zeros.
+ *   dyn_unsqueeze_act_bwd   du [B, T2, s H] = d * gelu'(u) with d [B, T, H]; rows >= *valid_rows exact zeros, d is read on rows
+ *                           < s * *valid_rows only.
+ * No call synchronises or allocates: all four are captured into the length buckets' hipGraphs. */
+int dyn_squeeze_ln_fwd(const float* h, const float* yg, const float* bias, const float* gamma, const float* beta, float* z, float* mean,
+                       float* rstd, int64_t B, int64_t T, int64_t Tg, int64_t H, int64_t G, int64_t s, float eps, const int32_t* valid_rows,
+                       void* stream);
+int64_t dyn_squeeze_ln_bwd_workspace_bytes(int64_t rows, int64_t H);
+int dyn_squeeze_ln_bwd(const float* h, const float* yg, const float* bias, const float* gamma, const float* mean, const float* rstd,
+                       const float* dz, float* dh, float* dyg, float* dgamma, float* dbeta, float* dbias, float wgrad_beta, int64_t B,
+                       int64_t T, int64_t Tg, int64_t H, int64_t G, int64_t s, const int32_t* valid_rows, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int dyn_unsqueeze_act_fwd(const float* u, float* out, int64_t B, int64_t T, int64_t H, int64_t s, const int32_t* valid_rows, void* stream);
+int dyn_unsqueeze_act_bwd(const float* u, const float* d, float* du, int64_t B, int64_t T, int64_t H, int64_t s, const int32_t* valid_rows,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * WavLM attention: gated relative-position bias.  The reference's loader, `AutoModelForCTC.from_pretrained(checkpoint)`
