@@ -9,6 +9,8 @@
 //                     dgamma, dbeta, dbias = column sums.
 //   unsqueeze forward / backward: out [B, T, H] rows t < s T2 = gelu(u[b, t / s, (t % s) H ..]) (u [B, T2, s H]: the same floats, another
 //                     batch stride when s T2 < T), zero rows after; du = d * gelu'(u).
+//   dyn_squeeze_fwd / _bwd (SEW-D): the squeeze pair with the LayerNorm compiled out of the same two kernel templates (LN = false): the sum
+//                     itself is the layers' input, dsum = dz, and of the three column sums only the conv bias's remains.
 // `valid` (device int32 scalar, in SQUEEZED frames, read when the kernel runs: a zero-padded length bucket) cuts every output: rows >= valid
 // of z and dyg, rows >= s valid of dh, of the upsampled output and of du are exact zeros, and no input row at or past them is read by the
 // two backwards.
@@ -46,7 +48,8 @@ __device__ __forceinline__ float4 pooled(const float* __restrict__ h, int64_t at
     return p;
 }
 
-template <int NV>
+// LN false (SEW-D, dyn_squeeze_fwd): the row itself is the output, no statistics; gamma, beta, mean_out, rstd_out are not touched.
+template <int NV, bool LN = true>
 __global__ __launch_bounds__(256) void sq_fwd_kernel(const float* __restrict__ h, const float* __restrict__ yg, const float* __restrict__ bias,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ z,
                                                       float* __restrict__ mean_out, float* __restrict__ rstd_out, int64_t B, int64_t T,
@@ -76,6 +79,12 @@ __global__ __launch_bounds__(256) void sq_fwd_kernel(const float* __restrict__ h
             v[j].z = p.z + dyn::gelu_f(a.z + cb[j].z); v[j].w = p.w + dyn::gelu_f(a.w + cb[j].w);
             sum += v[j].x + v[j].y + v[j].z + v[j].w;
         }
+        const bool live = t < Tv;
+        if constexpr (!LN) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) st4(z + row * H + 4 * (lane + 64 * j), live ? v[j] : make_float4(0.f, 0.f, 0.f, 0.f));
+            continue;
+        }
         const float mean = dyn::wave_sum(sum) / H;
         float q = 0.f;
 #pragma unroll
@@ -84,7 +93,6 @@ __global__ __launch_bounds__(256) void sq_fwd_kernel(const float* __restrict__ h
             q += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
         }
         const float rstd = rsqrtf(dyn::wave_sum(q) / H + eps);
-        const bool live = t < Tv;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -104,7 +112,8 @@ __global__ __launch_bounds__(256) void sq_fwd_kernel(const float* __restrict__ h
 
 // Rows walked: B * (T2 + 1); the extra row of every batch entry writes the zeros of the T - s T2 frames no squeezed frame pools.
 // partial_g / partial_b / partial_c [gridDim.x, H]: this workgroup's sums of dz * xhat, dz and dyg (a null pointer: not wanted).
-template <int NV>
+// LN false (SEW-D, dyn_squeeze_bwd): dsum = dz; h, gamma, mean_in, rstd_in, partial_g, partial_b are not touched (null).
+template <int NV, bool LN = true>
 __global__ __launch_bounds__(256) void sq_bwd_kernel(const float* __restrict__ h, const float* __restrict__ yg, const float* __restrict__ bias,
                                                       const float* __restrict__ gamma, const float* __restrict__ mean_in,
                                                       const float* __restrict__ rstd_in, const float* __restrict__ dz, float* __restrict__ dh,
@@ -144,6 +153,21 @@ __global__ __launch_bounds__(256) void sq_bwd_kernel(const float* __restrict__ h
             continue;
         }
         const int64_t r2 = b * T2 + t;
+        if constexpr (!LN) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const float4 y = ld4(yg + ((b * G + gi[j]) * Tg + t) * cg + ci[j]);
+                const float4 d = ld4(dz + r2 * H + 4 * (lane + 64 * j));
+                float4 o, dp;
+                o.x = d.x * dyn::gelu_grad(y.x + cb[j].x); o.y = d.y * dyn::gelu_grad(y.y + cb[j].y);
+                o.z = d.z * dyn::gelu_grad(y.z + cb[j].z); o.w = d.w * dyn::gelu_grad(y.w + cb[j].w);
+                ac[j].x += o.x; ac[j].y += o.y; ac[j].z += o.z; ac[j].w += o.w;
+                st4(dyg + ((b * G + gi[j]) * T2 + t) * cg + ci[j], o);
+                dp.x = d.x / fs; dp.y = d.y / fs; dp.z = d.z / fs; dp.w = d.w / fs;
+                for (int k = 0; k < s; ++k) st4(dh + (b * T + s * t + k) * H + 4 * (lane + 64 * j), dp);
+            }
+            continue;
+        }
         const float mean = mean_in[r2], rstd = rstd_in[r2];
         float4 a[NV], xh[NV], dn[NV];
         float s1 = 0.f, s2 = 0.f;
@@ -356,4 +380,65 @@ extern "C" int dyn_unsqueeze_act_bwd(const float* u, const float* d, float* du, 
     hipLaunchKernelGGL(unsq_bwd_kernel, dim3((unsigned)grid_for(n4)), dim3(256), 0, (hipStream_t)stream, u, d, du, n4, T, T2, H / 4, (int)s,
                        valid_rows);
     return dyn::check_launch("dyn_unsqueeze_act_bwd");
+}
+
+// The same two kernels without the LayerNorm (SEW-D: SEWDEncoder.forward hands the sum to its layers as it is).
+extern "C" int dyn_squeeze_fwd(const float* h, const float* yg, const float* bias, float* z, int64_t B, int64_t T, int64_t Tg, int64_t H,
+                               int64_t G, int64_t s, const int32_t* valid_rows, void* stream) {
+    DYN_REQUIRE(h && yg && bias && z, DYN_E_ARG, "dyn_squeeze_fwd: null argument");
+    const int rc = check_shape("dyn_squeeze_fwd", B, T, Tg, H, G, s);
+    if (rc != DYN_OK) return rc;
+    DYN_REQUIRE(aligned16(h) && aligned16(yg) && aligned16(bias) && aligned16(z), DYN_E_ARG, "dyn_squeeze_fwd: operands must be 16-byte aligned");
+    const int64_t T2 = T / s, rows = B * T2;
+    if (rows == 0) return DYN_OK;
+    int64_t gq = dyn::cdiv(rows, WPB);
+    if (gq > 2048) gq = 2048;
+    dim3 grid((unsigned)gq), blk(256);
+    hipStream_t st = (hipStream_t)stream;
+    const int g = (int)G, cg = (int)(H / G), f = (int)s;
+    const float* none = nullptr;
+    float* nout = nullptr;
+    switch (H / 256) {
+        case 1: hipLaunchKernelGGL((sq_fwd_kernel<1, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows); break;
+        case 2: hipLaunchKernelGGL((sq_fwd_kernel<2, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows); break;
+        case 3: hipLaunchKernelGGL((sq_fwd_kernel<3, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows); break;
+        default: hipLaunchKernelGGL((sq_fwd_kernel<4, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows); break;
+    }
+    return dyn::check_launch("dyn_squeeze_fwd");
+}
+
+extern "C" int64_t dyn_squeeze_bwd_workspace_bytes(int64_t rows, int64_t H) {
+    return (int64_t)bwd_blocks(rows) * H * (int64_t)sizeof(float);
+}
+
+extern "C" int dyn_squeeze_bwd(const float* yg, const float* bias, const float* dz, float* dh, float* dyg, float* dbias, float wgrad_beta,
+                               int64_t B, int64_t T, int64_t Tg, int64_t H, int64_t G, int64_t s, const int32_t* valid_rows, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    DYN_REQUIRE(yg && bias && dz && dh && dyg, DYN_E_ARG, "dyn_squeeze_bwd: null argument (only dbias may be null)");
+    const int rc = check_shape("dyn_squeeze_bwd", B, T, Tg, H, G, s);
+    if (rc != DYN_OK) return rc;
+    DYN_REQUIRE(aligned16(yg) && aligned16(bias) && aligned16(dz) && aligned16(dh) && aligned16(dyg), DYN_E_ARG,
+                "dyn_squeeze_bwd: operands must be 16-byte aligned");
+    const int64_t T2 = T / s, rows = B * (T2 + 1);
+    if (B * T == 0) return DYN_OK;
+    const int nb = bwd_blocks(rows);
+    float* pc = nullptr;
+    if (dbias) {
+        const int64_t need = dyn_squeeze_bwd_workspace_bytes(rows, H);
+        DYN_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= need, DYN_E_WORKSPACE, "dyn_squeeze_bwd: workspace too small");
+        pc = dyn::partials_alloc(workspace, need);                   // the workspace, or the open deferral context's arena
+    }
+    dim3 grid(nb), blk(256);
+    hipStream_t st = (hipStream_t)stream;
+    const int g = (int)G, cg = (int)(H / G), f = (int)s;
+    const float* none = nullptr;
+    float* nout = nullptr;
+    switch (H / 256) {
+        case 1: hipLaunchKernelGGL((sq_bwd_kernel<1, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
+        case 2: hipLaunchKernelGGL((sq_bwd_kernel<2, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
+        case 3: hipLaunchKernelGGL((sq_bwd_kernel<3, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
+        default: hipLaunchKernelGGL((sq_bwd_kernel<4, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
+    }
+    if (dbias) dyn::reduce_or_defer(pc, dbias, (int64_t)nb, H, wgrad_beta, st);
+    return dyn::check_launch("dyn_squeeze_bwd");
 }

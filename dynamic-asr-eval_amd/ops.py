@@ -1584,3 +1584,89 @@ def unsqueeze_act_bwd(u, d, s, valid=None):
     check(_L().dyn_unsqueeze_act_bwd(u.data_ptr(), d.data_ptr(), du.data_ptr(), B, T, H, s, _valid_ptr(valid, "unsqueeze_act_bwd"), _stream()),
           "dyn_unsqueeze_act_bwd")
     return du
+
+
+def squeeze(h, yg, bias, s, valid=None):
+    """squeeze_ln without the LayerNorm (SEW-D): z [B, T // s, H] = the mean of s frames of h [B, T, H] + gelu(rows of yg [B, G, Tg >= T // s,
+    cg] + bias).  h and yg are left unmodified; rows >= `valid` (device int32 scalar, squeezed frames) of z are zeros."""
+    _cc(h, "squeeze.h"); _cc(yg, "squeeze.yg")
+    B, T, H, G, Tg, cg = _squeeze_dims("squeeze", h, yg, s)
+    if _cc(bias, "squeeze.bias").numel() != H:
+        raise DynError(f"squeeze: bias must have H = {H} elements")
+    z = torch.empty(B, T // s, H, device=h.device, dtype=F32)
+    check(_L().dyn_squeeze_fwd(h.data_ptr(), yg.data_ptr(), bias.data_ptr(), z.data_ptr(), B, T, Tg, H, G, s, _valid_ptr(valid, "squeeze"),
+                               _stream()), "dyn_squeeze_fwd")
+    return z
+
+
+def squeeze_bwd(yg, bias, dz, T, s, dbias, wgrad_beta=1.0, valid=None):
+    """Backward of squeeze from yg, bias and dz [B, T // s, H] (`T`: the frames of h): returns (dh [B, T, H], dyg [B, G, T // s, cg]) as
+    squeeze_ln_bwd does; dbias = wgrad_beta * old + column sums of dyg, or None (frozen)."""
+    _cc(yg, "squeeze_bwd.yg"); _cc(bias, "squeeze_bwd.bias"); _cc(dz, "squeeze_bwd.dz")
+    if dz.dim() != 3 or not isinstance(T, int) or T < 0:
+        raise DynError("squeeze_bwd: dz must be [B, T // s, H] and T the frame count of h")
+    B, T2, H = dz.shape
+    B, T, H, G, Tg, cg = _squeeze_dims("squeeze_bwd", torch.empty(B, T, H, device="meta"), yg, s)      # shapes only: h itself is not needed
+    if T2 != T // s or bias.numel() != H:
+        raise DynError("squeeze_bwd: dz / bias do not match T, s and yg")
+    if dbias is not None and dbias.numel() != H:
+        raise DynError("squeeze_bwd: dbias must have H elements")
+    dh = torch.empty(B, T, H, device=dz.device, dtype=F32)
+    dyg = torch.empty(B, G, T2, cg, device=dz.device, dtype=F32)
+    ws = workspace(dz.device)
+    check(_L().dyn_squeeze_bwd(yg.data_ptr(), bias.data_ptr(), dz.data_ptr(), dh.data_ptr(), dyg.data_ptr(), _opt(dbias, "dbias"), wgrad_beta,
+                               B, T, Tg, H, G, s, _valid_ptr(valid, "squeeze_bwd"), ws.data_ptr(), ws.numel(), _stream()), "dyn_squeeze_bwd")
+    return dh, dyg
+
+
+def _disentangled_dims(who, S, table, n_buckets, ldp):
+    """S [..., T, T] contiguous -> (M, T); the table must hold the 2T - 1 relative positions of THIS row length and ldp the n_buckets rows."""
+    if S.dim() < 2 or S.shape[-1] != S.shape[-2]:
+        raise DynError(f"{who}: the scores must be [..., T, T]")
+    T = S.shape[-1]
+    _c(table, who + ".table", I32)
+    if table.numel() != 2 * T - 1:
+        raise DynError(f"{who}: the bucket table holds {table.numel()} entries, 2T - 1 = {2 * T - 1} expected")
+    if not isinstance(n_buckets, int) or n_buckets < 1 or ldp < n_buckets:
+        raise DynError(f"{who}: ldp = {ldp} is shorter than the n_buckets = 2 * span = {n_buckets} relative positions")
+    return S.numel() // (T * T), T
+
+
+def softmax_disentangled(S, c2p, p2ct, table, n_buckets, ldp, out=None, valid=None):
+    """SEW-D's disentangled attention probabilities: softmax_j(S[.., i, j] + c2p[.., i, t(i - j)] + p2ct[.., t(i - j), j]) over the keys, keys
+    >= `valid` (device int32 scalar) masked.  S [B, nh, T, T] scaled content scores, c2p [B, nh, T, ldp] and p2ct [B, nh, ldp, T] the scaled
+    position products (either may be None), `table` int32 [2T - 1] on the device with t(d) at d + T - 1 (sew_d_model.bucket_table).  `out`
+    may be S."""
+    _cc(S, "softmax_disentangled.S")
+    M, T = _disentangled_dims("softmax_disentangled", S, table, n_buckets, ldp)
+    if c2p is None and p2ct is None:
+        raise DynError("softmax_disentangled: both position terms are None")
+    for t, n in ((c2p, "c2p"), (p2ct, "p2ct")):
+        if t is not None and _c(t, "softmax_disentangled." + n).numel() != M * T * ldp:
+            raise DynError(f"softmax_disentangled: {n} holds {t.numel()} floats, {M} x {T} x {ldp} expected")
+    out = torch.empty_like(S) if out is None else _cc(out, "softmax_disentangled.out")
+    check(_L().dyn_softmax_disentangled_fwd(S.data_ptr(), out.data_ptr(), 0 if c2p is None else c2p.data_ptr(),
+                                            0 if p2ct is None else p2ct.data_ptr(), table.data_ptr(), M, T, ldp, n_buckets,
+                                            _valid_ptr(valid, "softmax_disentangled"), _stream()), "dyn_softmax_disentangled_fwd")
+    return out
+
+
+def disentangled_bwd(dS, table, seg_lo, seg_hi, ldp, want_c2p=True, want_p2c=True, valid=None):
+    """The two gathers' backward from dS [B, nh, T, T] (softmax_bwd's output): returns (dC2P [B, nh, T, ldp] or None, dP2CT [B, nh, ldp, T] or
+    None), each element one segment sum in a fixed order (bit-reproducible), both written completely.  Rows / columns >= `valid` of dS are
+    not read.  seg_lo / seg_hi: int32 [n_buckets] on the device (sew_d_model.bucket_table)."""
+    _cc(dS, "disentangled_bwd.dS")
+    _c(seg_lo, "disentangled_bwd.seg_lo", I32); _c(seg_hi, "disentangled_bwd.seg_hi", I32)
+    n_buckets = seg_lo.numel()
+    if seg_hi.numel() != n_buckets:
+        raise DynError("disentangled_bwd: seg_lo and seg_hi differ in length")
+    M, T = _disentangled_dims("disentangled_bwd", dS, table, n_buckets, ldp)
+    if not (want_c2p or want_p2c):
+        raise DynError("disentangled_bwd: at least one of the two outputs must be wanted")
+    lead = tuple(dS.shape[:-2])
+    dc = torch.empty(lead + (T, ldp), device=dS.device, dtype=F32) if want_c2p else None
+    dp = torch.empty(lead + (ldp, T), device=dS.device, dtype=F32) if want_p2c else None
+    check(_L().dyn_disentangled_bwd(dS.data_ptr(), 0 if dc is None else dc.data_ptr(), 0 if dp is None else dp.data_ptr(), table.data_ptr(),
+                                    seg_lo.data_ptr(), seg_hi.data_ptr(), M, T, ldp, n_buckets, _valid_ptr(valid, "disentangled_bwd"),
+                                    _stream()), "dyn_disentangled_bwd")
+    return dc, dp

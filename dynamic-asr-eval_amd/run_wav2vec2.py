@@ -10,7 +10,7 @@ Like both reference drivers it processes the FIRST recording only (they `break` 
 `AutoModelForCTC.from_pretrained("facebook/wav2vec2-base-960h")` and the corpora cannot be fetched offline, so the harness builds
 the base architecture (HF `Wav2Vec2Config()` defaults: 7 conv layers of 512 channels, positional conv k=128 g=16, 12 x 768, vocab 32)
 or the one a `config.json` names (`--config`, or `-c DIR` = a local HF model directory; the layer-norm / stable-LN layout of
-large-960h-lv60-self included, and by `model_type` WavLM, Wav2Vec2-Conformer, Data2Vec-Audio, HuBERT and SEW: load_pretrained_model) with
+large-960h-lv60-self included, and by `model_type` WavLM, Wav2Vec2-Conformer, Data2Vec-Audio, HuBERT, SEW and SEW-D: load_pretrained_model) with
 seeded weights, or loads a local HF state_dict (`-c file.pt` / `DIR/pytorch_model.bin`, torch.load(weights_only=True)), and evaluates a synthetic
 TEDLIUM-shape talk (`--seconds`, utterances of 2-15 s).  Reported WERs use this package's reduced text
 normaliser (wer.basic_normalize), not whisper's EnglishTextNormalizer (un-vendored)."""
@@ -23,7 +23,7 @@ import torch
 from . import wav2vec2_lib as lib
 from .datasets import fetch_utterances_from_lines, synthetic_text, synthetic_waveform
 from .decoding import GreedyCTCDecoder
-from . import data2vec_audio_model, hubert_model, sew_model, wav2vec2_conformer_model, wavlm_model
+from . import data2vec_audio_model, hubert_model, sew_d_model, sew_model, wav2vec2_conformer_model, wavlm_model
 from .wav2vec2_model import Wav2Vec2ForCTC, config_from_json
 from .wer import basic_normalize as normalize, word_error_rate_detail
 
@@ -62,9 +62,10 @@ def fetch_utterances_synthetic(total_seconds=900.0, seed=7, sample_rate=16000, s
 
 def init_synthetic(model, seed=0):
     g = torch.Generator().manual_seed(seed)
+    ones = ("layer_norm.weight", "original0") + tuple(getattr(model, "_norm_weight_suffixes", ()))      # a model's own norm names (SEW-D: `LayerNorm`)
     for name, p in model.named_parameters():
         if p.dim() == 1:
-            v = (1.0 if name.endswith("layer_norm.weight") or name.endswith("original0") else 0.0) + 0.02 * torch.randn(p.shape, generator=g)
+            v = (1.0 if name.endswith(ones) else 0.0) + 0.02 * torch.randn(p.shape, generator=g)
         else:
             fan_in = p[0].numel()
             v = torch.randn(p.shape, generator=g) / fan_in ** 0.5
@@ -99,7 +100,7 @@ def load_pretrained_model(args, device):
     base-960h architecture or at `--config PATH.json`; without a checkpoint: seeded weights at that architecture.  A config.json whose
     `model_type` is "wavlm" builds WavLMForCTC (wavlm_model.py), "wav2vec2-conformer" Wav2Vec2ConformerForCTC (wav2vec2_conformer_model.py),
     "data2vec-audio" Data2VecAudioForCTC (data2vec_audio_model.py), "hubert" HubertForCTC (hubert_model.py), "sew" SEWForCTC
-    (sew_model.py), under `-c DIR` and under `--config` alike; anything else Wav2Vec2ForCTC."""
+    (sew_model.py), "sew-d" SEWDForCTC (sew_d_model.py), under `-c DIR` and under `--config` alike; anything else Wav2Vec2ForCTC."""
     cfg_path, ckpt = getattr(args, 'config', '') or '', args.checkpoint
     if ckpt and os.path.isdir(ckpt):
         cfg_path, ckpt = cfg_path or os.path.join(ckpt, 'config.json'), os.path.join(ckpt, 'pytorch_model.bin')
@@ -114,6 +115,8 @@ def load_pretrained_model(args, device):
         model = hubert_model.HubertForCTC(hubert_model.config_from_json(cfg_path), device=device)
     elif kind == 'sew':
         model = sew_model.SEWForCTC(sew_model.config_from_json(cfg_path), device=device)
+    elif kind == 'sew-d':
+        model = sew_d_model.SEWDForCTC(sew_d_model.config_from_json(cfg_path), device=device)
     else:
         model = Wav2Vec2ForCTC(config_from_json(cfg_path) if cfg_path else None, device=device)
     if ckpt:

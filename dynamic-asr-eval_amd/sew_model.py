@@ -14,7 +14,8 @@ This subclass of Wav2Vec2ForCTC replaces the prefix (`sew.`), the configuration 
 encoder hooks; the layer loop, the weight norm, the extractor, flat parameters and the length-bucket hipGraphs are the parent's.  The
 strided conv's product stays a grouped GEMM on the packed input (lda = s * cg, M = T2, the way ops.conv1d expresses a stride); everything
 between that product and the first layer is ONE kernel each way (ops.squeeze_ln / ops.squeeze_ln_bwd: bias, GELU, regroup, pool, sum,
-LayerNorm), everything between the upsampling projection and lm_head another (ops.unsqueeze_act / _bwd).  `out.frames` and the logits
+LayerNorm; the hook pair _squeeze / _squeeze_bwd, which SEW-D answers without the LayerNorm), everything between the upsampling
+projection and lm_head another (ops.unsqueeze_act / _bwd).  `out.frames` and the logits
 stay at T frames, the extractor's count: the loops and CTC work there.
 
 Bucketed hipGraph replay.  The encoder's valid length is v2 = vT // s (vT: the utterance's frames), a device scalar filled next to the
@@ -142,10 +143,9 @@ class SEWForCTC(W2.Wav2Vec2ForCTC):
         yg = torch.empty(B, G, T2, cg, device=h.device, dtype=torch.float32)
         ops.gemm(xg, w, yg, trans_b=True, M=T2, N=cg, K=K * cg, lda=s * cg, ldb=K * cg, ldc=cg, nb1=B, nb2=G,
                  sa=(G * Tp * cg, Tp * cg), sb=(0, cg * K * cg), sc=(G * T2 * cg, T2 * cg))
-        z, mean, rstd = ops.squeeze_ln(h, yg, P[pc + "bias"], P[pf + "encoder.layer_norm.weight"], P[pf + "encoder.layer_norm.bias"], s,
-                                       c["layer_norm_eps"], valid=v2)
+        z, stats = self._squeeze(h, yg, v2)
         if save:
-            ctx["pos"] = (xg, w, yg, h, mean, rstd)
+            ctx["pos"] = (xg, w, yg, h) + stats
         z = self._post_ln_layers(z, ctx, v2)
         u = ops.linear(z, P[pf + "encoder.upsample.projection.weight"], P[pf + "encoder.upsample.projection.bias"])     # [B, T2, s H]
         up = ops.unsqueeze_act(u, T, s, valid=v2)                   # [B, T, H]
@@ -157,6 +157,24 @@ class SEWForCTC(W2.Wav2Vec2ForCTC):
             ctx["valid"] = (v0, vT)
         self._ctx = ctx
         return SimpleNamespace(logits=logits, frames=T)
+
+    def _squeeze(self, h, yg, v2):
+        """What stands between the strided conv's product yg and the first layer, one kernel: returns (z [B, T2, H], a tuple of what
+        _squeeze_bwd needs besides h and yg, batch-major).  A model without the encoder LayerNorm (sew_d_model.py) overrides the pair."""
+        c, P, pf = self.cfg, self.P, self._prefix
+        z, mean, rstd = ops.squeeze_ln(h, yg, P[pf + "encoder.pos_conv_embed.conv.bias"], P[pf + "encoder.layer_norm.weight"],
+                                       P[pf + "encoder.layer_norm.bias"], c["squeeze_factor"], c["layer_norm_eps"], valid=v2)
+        return z, (mean, rstd)
+
+    def _squeeze_bwd(self, h, yg, stats, dz, v2):
+        """Backward of _squeeze from dz [nb, T2, H] (`h`, `yg`, `stats` cut to the active samples): accumulates its parameters' gradients,
+        returns (dh [nb, T, H]: the pool's path, dyg [nb, G, T2, cg]: the conv product's gradient)."""
+        c, P, G, pf = self.cfg, self.P, self.G, self._prefix
+        mean, rstd = stats
+        pc = pf + "encoder.pos_conv_embed.conv."
+        names = (pf + "encoder.layer_norm.weight", pf + "encoder.layer_norm.bias", pc + "bias")
+        return ops.squeeze_ln_bwd(h, yg, P[pc + "bias"], P[names[0]], mean, rstd, dz, c["squeeze_factor"],
+                                  *(G[n] if self.trainable(n) else None for n in names), wgrad_beta=1.0, valid=v2)
 
     def _backward_encoder(self, ctx, grad_logits, nb, cut):
         v0, vT = ctx["valid"]
@@ -171,11 +189,8 @@ class SEWForCTC(W2.Wav2Vec2ForCTC):
         dz = self._post_ln_layers_bwd(ctx, dz, nb, T2, cut)
         # squeeze: LayerNorm, pool and GELU backward in one kernel, then the strided conv's three products
         w = ctx["pos"][1]                                            # the normalised weight is not batch-indexed
-        xg, _, yg, h, mean, rstd = cut(ctx["pos"])
-        pc = pf + "encoder.pos_conv_embed.conv."
-        names = (pf + "encoder.layer_norm.weight", pf + "encoder.layer_norm.bias", pc + "bias")
-        dh, dyg = ops.squeeze_ln_bwd(h, yg, P[pc + "bias"], P[names[0]], mean, rstd, dz.contiguous(), s,
-                                     *(G[n] if self.trainable(n) else None for n in names), wgrad_beta=1.0, valid=v2)
+        xg, _, yg, h, *stats = cut(ctx["pos"])
+        dh, dyg = self._squeeze_bwd(h, yg, stats, dz.contiguous(), v2)
         dw = torch.zeros_like(w)
         for b in range(nb):                                          # dw[g] += dyg[b, g]^T rows(xg[b, g]), rows s frames apart
             ops.gemm(dyg, xg, dw, trans_a=True, M=cg, N=K * cg, K=T2, lda=cg, ldb=s * cg, ldc=K * cg, nb1=1, nb2=Gn,

@@ -158,6 +158,7 @@ class Wav2Vec2ForCTC(FlatModel):
     # embedding (data2vec_audio_model) the pair _pos_embed / _pos_embed_bwd, one with another feature projection (hubert_model) _project / _project_bwd
     # a model whose layers run at another frame rate (sew_model) _project / _project_bwd and _encode / _backward_encoder around the shared
     # _post_ln_layers / _post_ln_layers_bwd and _pos_weight / _pos_weight_bwd, plus _fill_valid for its own valid-length scalar
+    # a model whose layers carry other parameter names and another attention (sew_d_model) _qv_names and the pair _attention / _attention_bwd
     _prefix = "wav2vec2."
     _qkv_fmt = "attention.{}_proj"
     _make_config = staticmethod(make_config)
@@ -180,12 +181,12 @@ class Wav2Vec2ForCTC(FlatModel):
         self.packed_qkv = H % 64 == 0
         self.Pqkv, self.Gqkv = [], []
         if self.packed_qkv:
-            q, v = self._qkv_fmt.format("q"), self._qkv_fmt.format("v")
             for l in range(c["num_hidden_layers"]):
-                ow = slots[f"{pf}encoder.layers.{l}.{q}.weight"][0]
-                ob = slots[f"{pf}encoder.layers.{l}.{q}.bias"][0]
-                assert slots[f"{pf}encoder.layers.{l}.{v}.weight"][0] == ow + 2 * H * H
-                assert slots[f"{pf}encoder.layers.{l}.{v}.bias"][0] == ob + 2 * H
+                q, v = self._qv_names(l)
+                ow = slots[f"{q}.weight"][0]
+                ob = slots[f"{q}.bias"][0]
+                assert slots[f"{v}.weight"][0] == ow + 2 * H * H
+                assert slots[f"{v}.bias"][0] == ob + 2 * H
                 self.Pqkv.append((self.flat_params[ow:ow + 3 * H * H].view(3 * H, H), self.flat_params[ob:ob + 3 * H]))
                 self.Gqkv.append((self.flat_grads[ow:ow + 3 * H * H].view(3 * H, H), self.flat_grads[ob:ob + 3 * H]))
         self.config = SimpleNamespace(**c)
@@ -201,6 +202,11 @@ class Wav2Vec2ForCTC(FlatModel):
         self._valid = torch.zeros(len(c["conv_kernel"]), dtype=torch.int32, device=self.device)
         self._vl = None                          # = self._valid while a bucketed launch sequence is being issued / captured, else None
         self._ctx, self._ctx_static, self._ctx_key = None, False, None
+
+    def _qv_names(self, l):
+        """The names (without `.weight` / `.bias`) of layer l's query and value projections, the two ends of its packed q | k | v slots."""
+        p = f"{self._prefix}encoder.layers.{l}."
+        return p + self._qkv_fmt.format("q"), p + self._qkv_fmt.format("v")
 
     # ------------------------------------------------------------------ nn.Module-like surface
     def grads_hf(self):

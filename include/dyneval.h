@@ -642,6 +642,48 @@ int dyn_squeeze_ln_bwd(const float* h, const float* yg, const float* bias, const
 int dyn_unsqueeze_act_fwd(const float* u, float* out, int64_t B, int64_t T, int64_t H, int64_t s, const int32_t* valid_rows, void* stream);
 int dyn_unsqueeze_act_bwd(const float* u, const float* d, float* du, int64_t B, int64_t T, int64_t H, int64_t s, const int32_t* valid_rows,
                           void* stream);
+/* SEW-D's squeeze: the same pass without the LayerNorm.  transformers' SEWDForCTC (what the reference's loader builds for `model_type:
+ * "sew-d"`) runs SEWDEncoder.forward (modeling_sew_d.py:1146-1152): `position_embeddings = self.pos_conv_embed(hidden_states)` after its
+ * conv's product, `self.pool(hidden_states)`, `pooled_hidden_states + position_embeddings[..., :pooled_hidden_states.size(-1)]`, the two
+ * `transpose(1, 2)`, and hands the sum to SEWDTransformerEncoder as it is.  Shapes, layouts, `valid_rows` and refusals as the two entries
+ * above (same kernel templates, LayerNorm compiled out):
+ *   dyn_squeeze_fwd   z [B, T2, H] row t = the mean of h rows s t .. s t + s - 1 + gelu(yg row t + bias); rows >= *valid_rows zeros.
+ *   dyn_squeeze_bwd   its autograd from dz [B, T2, H]: dh rows s t + j = dz[t] / s (rows >= s T2 and >= s * *valid_rows exact zeros, fully
+ *                     written), dyg [B, G, T2, cg] = dz * gelu'(yg + bias) (rows >= *valid_rows exact zeros), dbias [H] = wgrad_beta * old +
+ *                     the column sums of dyg (null: frozen, no workspace needed; else dyn_squeeze_bwd_workspace_bytes(B * (T2 + 1), H)),
+ *                     through per-workgroup partial rows and the fixed-order reducer (deferrable).  h is not needed and not passed. */
+int dyn_squeeze_fwd(const float* h, const float* yg, const float* bias, float* z, int64_t B, int64_t T, int64_t Tg, int64_t H, int64_t G,
+                    int64_t s, const int32_t* valid_rows, void* stream);
+int64_t dyn_squeeze_bwd_workspace_bytes(int64_t rows, int64_t H);
+int dyn_squeeze_bwd(const float* yg, const float* bias, const float* dz, float* dh, float* dyg, float* dbias, float wgrad_beta, int64_t B,
+                    int64_t T, int64_t Tg, int64_t H, int64_t G, int64_t s, const int32_t* valid_rows, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * SEW-D attention: DeBERTa-v2's disentangled relative-position score (csrc/disentangled.hip).  For `model_type: "sew-d"` the reference's
+ * loader builds transformers' SEWDForCTC, whose every layer runs DisentangledSelfAttention.forward (modeling_sew_d.py:680-761) with
+ * `share_att_key`.  With M = B * heads, n_buckets = 2 * att_span rows of relative embeddings, and
+ *   table [2T - 1] int32 (device), table[d + T - 1] = t(d) = clamp(bucket(d) + att_span, 0, 2 att_span - 1), built ON THE HOST from
+ *   build_relative_position / make_log_bucket_position (:159-201; a float32 ceil(log) on integer boundaries: a kernel's rounding would be a
+ *   wrong bucket) and monotone non-decreasing in d; seg_lo / seg_hi [n_buckets] int32: bucket r is the run seg_lo[r] <= d <= seg_hi[r]
+ *   (lo > hi: empty):
+ *   dyn_softmax_disentangled_fwd  disentangled_attention_bias (:763-839: the two `torch.gather`s, `c2p_pos` / `p2c_pos`, the
+ *                                 `.transpose(-1, -2)`, both `/ scale`) + `attention_scores + rel_att` (:740) + XSoftmax (:746):
+ *                                 y[m, i, :] = softmax_j(x[m, i, j] + c2p[m, i, t(i - j)] + p2ct[m, t(i - j), j]); x [M, T, T] = the scaled
+ *                                 content scores, c2p [M, T, ldp] = scaled q Pk^T, p2ct [M, ldp, T] = scaled Pq k^T (position -> content,
+ *                                 transposed); either term may be null (`pos_att_type` with one of them), not both.  y may be x.  Columns /
+ *                                 rows >= n_buckets of c2p / p2ct are never read.  `valid_cols` as dyn_softmax_fwd_len.  T <= 16384.
+ *   dyn_disentangled_bwd          the autograd of the two gathers from dS [M, T, T] (what dyn_softmax_bwd leaves):
+ *                                 dC2P[m, i, r] = sum over d in run r of dS[m, i, i - d], dP2CT[m, r, j] = sum over d in run r of
+ *                                 dS[m, j + d, j]; each element ONE sum in ascending key (query) order, no float atomics, no zero-fill,
+ *                                 bit-reproducible; both outputs ([M, T, ldp] and [M, ldp, T]) are written completely, empty buckets and
+ *                                 indices >= n_buckets as exact zeros.  Rows and columns >= *valid of dS are not read; rows >= *valid of
+ *                                 dC2P and columns >= *valid of dP2CT are exact zeros.  Either output may be null, not both.  T <= 8192.
+ * ldp >= n_buckets >= 1, else DYN_E_ARG.  A table entry outside [0, n_buckets) is clamped before use.  No call synchronises or allocates. */
+int dyn_softmax_disentangled_fwd(const float* x, float* y, const float* c2p, const float* p2ct, const int32_t* table, int64_t M, int64_t T,
+                                 int64_t ldp, int64_t n_buckets, const int32_t* valid_cols, void* stream);
+int dyn_disentangled_bwd(const float* dS, float* dC2P, float* dP2CT, const int32_t* table, const int32_t* seg_lo, const int32_t* seg_hi,
+                         int64_t M, int64_t T, int64_t ldp, int64_t n_buckets, const int32_t* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * WavLM attention: gated relative-position bias.  The reference's loader, `AutoModelForCTC.from_pretrained(checkpoint)`
