@@ -168,8 +168,9 @@ int launch_fwd(const float* x, const float* gamma, const float* beta, float* y, 
         case 2: hipLaunchKernelGGL((norm_fwd_kernel<2, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
         case 3: hipLaunchKernelGGL((norm_fwd_kernel<3, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
         case 4: hipLaunchKernelGGL((norm_fwd_kernel<4, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
+        case 5: hipLaunchKernelGGL((norm_fwd_kernel<5, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
         case 8: hipLaunchKernelGGL((norm_fwd_kernel<8, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
-        default: dyn::set_error("norm: unsupported C=%lld (need C in {256,512,768,1024,2048})", (long long)C); return DYN_E_UNSUPPORTED;
+        default: dyn::set_error("norm: unsupported C=%lld (need C in {256,512,768,1024,1280,2048})", (long long)C); return DYN_E_UNSUPPORTED;
     }
     return dyn::check_launch("dyn_norm_fwd");
 }
@@ -195,6 +196,7 @@ int launch_bwd(const float* x, const float* gamma, const float* mean, const floa
         case 2: hipLaunchKernelGGL((norm_bwd_kernel<2, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
         case 3: hipLaunchKernelGGL((norm_bwd_kernel<3, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
         case 4: hipLaunchKernelGGL((norm_bwd_kernel<4, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
+        case 5: hipLaunchKernelGGL((norm_bwd_kernel<5, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
         case 8: hipLaunchKernelGGL((norm_bwd_kernel<8, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
         default: dyn::set_error("norm: unsupported C=%lld", (long long)C); return DYN_E_UNSUPPORTED;
     }

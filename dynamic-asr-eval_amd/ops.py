@@ -1670,3 +1670,62 @@ def disentangled_bwd(dS, table, seg_lo, seg_hi, ldp, want_c2p=True, want_p2c=Tru
                                     seg_lo.data_ptr(), seg_hi.data_ptr(), M, T, ldp, n_buckets, _valid_ptr(valid, "disentangled_bwd"),
                                     _stream()), "dyn_disentangled_bwd")
     return dc, dp
+
+
+# ----------------------------------------------------------------------------------------------- MMS adapter
+def _adapter_dims(who, x, w1, w2):
+    _cc(x, who + ".x"); _cc(w1, who + ".w1"); _cc(w2, who + ".w2")
+    H = x.shape[-1]
+    if w1.dim() != 2 or w1.shape[1] != H or tuple(w2.shape) != (H, w1.shape[0]):
+        raise DynError(f"{who}: w1 {tuple(w1.shape)} / w2 {tuple(w2.shape)} must be [A, H] / [H, A] with H = {H}")
+    A = w1.shape[0]
+    if H % 256 or H > 2048:
+        raise DynError(f"{who}: H = {H} must be a multiple of 256 up to 2048")
+    if A % 4 or not 4 <= A <= 64:
+        raise DynError(f"{who}: A = {A} must be a multiple of 4 from 4 to 64")
+    return x.numel() // H, H, A
+
+
+def attn_adapter(x, gamma, beta, w1, b1, w2, b2, eps=1e-5, out=None, save=False):
+    """transformers' Wav2Vec2AttnAdapterLayer with its residual, one launch: y = x + w2 relu(w1 LayerNorm(x) + b1) + b2 over the last axis of
+    x [..., H]; w1 [A, H], w2 [H, A].  `out` may be x (in place).  Returns (y, mean, rstd, a): with `save` the row statistics [rows] and the
+    post-ReLU bottleneck [..., A] the backward needs, else three Nones."""
+    M, H, A = _adapter_dims("attn_adapter", x, w1, w2)
+    for t, n, k in ((gamma, "gamma", H), (beta, "beta", H), (b1, "b1", A), (b2, "b2", H)):
+        if _cc(t, "attn_adapter." + n).numel() != k:
+            raise DynError(f"attn_adapter: {n} must have {k} elements")
+    y = torch.empty_like(x) if out is None else _cc(out, "attn_adapter.out")
+    if y.shape != x.shape:
+        raise DynError("attn_adapter: out must have the shape of x")
+    mean = rstd = a = None
+    if save:
+        mean = torch.empty(M, device=x.device, dtype=F32)
+        rstd = torch.empty(M, device=x.device, dtype=F32)
+        a = torch.empty(x.shape[:-1] + (A,), device=x.device, dtype=F32)
+    check(_L().dyn_attn_adapter_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                    y.data_ptr(), _opt(mean, "mean"), _opt(rstd, "rstd"), _opt(a, "a"), M, H, A, eps, _stream()),
+          "dyn_attn_adapter_fwd")
+    return y, mean, rstd, a
+
+
+def attn_adapter_bwd(x, gamma, beta, w1, w2, mean, rstd, a, dy, dgamma, dbeta, dw1, db1, dw2, db2, dx=None):
+    """Backward of attn_adapter from its input x, the saved (mean, rstd, a) and dy: returns dx = dy + the adapter path, out of place (dy may be
+    a queued weight-gradient operand; x and dy are left unmodified).  The six gradients += their sums over the rows, each in a fixed order
+    (no atomics; bit-reproducible); None: frozen, not computed."""
+    M, H, A = _adapter_dims("attn_adapter_bwd", x, w1, w2)
+    _cc(dy, "attn_adapter_bwd.dy"); _cc(a, "attn_adapter_bwd.a"); _cc(gamma, "attn_adapter_bwd.gamma"); _cc(beta, "attn_adapter_bwd.beta")
+    _c(mean, "attn_adapter_bwd.mean"); _c(rstd, "attn_adapter_bwd.rstd")
+    if dy.shape != x.shape or a.numel() != M * A or mean.numel() != M or rstd.numel() != M or gamma.numel() != H or beta.numel() != H:
+        raise DynError("attn_adapter_bwd: dy / a / mean / rstd / gamma / beta do not match x and the weights")
+    for t, n, k in ((dgamma, "dgamma", H), (dbeta, "dbeta", H), (dw1, "dw1", A * H), (db1, "db1", A), (dw2, "dw2", A * H), (db2, "db2", H)):
+        if t is not None and _cc(t, "attn_adapter_bwd." + n).numel() != k:
+            raise DynError(f"attn_adapter_bwd: {n} must have {k} elements")
+    dx = torch.empty_like(dy) if dx is None else _cc(dx, "attn_adapter_bwd.dx")
+    if dx.shape != dy.shape or dx.data_ptr() in (dy.data_ptr(), x.data_ptr()):
+        raise DynError("attn_adapter_bwd: dx must have the shape of dy and alias neither dy nor x")
+    ws = workspace(x.device)
+    check(_L().dyn_attn_adapter_bwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w1.data_ptr(), w2.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                    a.data_ptr(), dy.data_ptr(), dx.data_ptr(), _opt(dgamma, "dgamma"), _opt(dbeta, "dbeta"), _opt(dw1, "dw1"),
+                                    _opt(db1, "db1"), _opt(dw2, "dw2"), _opt(db2, "db2"), M, H, A, ws.data_ptr(), ws.numel(), _stream()),
+          "dyn_attn_adapter_bwd")
+    return dx

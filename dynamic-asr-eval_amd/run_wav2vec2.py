@@ -12,7 +12,9 @@ the base architecture (HF `Wav2Vec2Config()` defaults: 7 conv layers of 512 chan
 or the one a `config.json` names (`--config`, or `-c DIR` = a local HF model directory; the layer-norm / stable-LN layout of
 large-960h-lv60-self included, and by `model_type` WavLM, Wav2Vec2-Conformer, Data2Vec-Audio, HuBERT, SEW and SEW-D: load_pretrained_model) with
 seeded weights, or loads a local HF state_dict (`-c file.pt` / `DIR/pytorch_model.bin`, torch.load(weights_only=True)), and evaluates a synthetic
-TEDLIUM-shape talk (`--seconds`, utterances of 2-15 s).  Reported WERs use this package's reduced text
+TEDLIUM-shape talk (`--seconds`, utterances of 2-15 s).  An MMS directory (`adapter_attn_dim` in its config.json) runs with its
+per-layer adapters; `--target-lang LANG` loads `DIR/adapter.LANG.safetensors` (or `.bin`) over the base weights and `DIR/vocab.json` as the tokenizer,
+`--adapter-only` adapts the adapters and lm_head alone (Wav2Vec2ForCTC.adapter_only).  Reported WERs use this package's reduced text
 normaliser (wer.basic_normalize), not whisper's EnglishTextNormalizer (un-vendored)."""
 import argparse
 import os
@@ -24,7 +26,7 @@ from . import wav2vec2_lib as lib
 from .datasets import fetch_utterances_from_lines, synthetic_text, synthetic_waveform
 from .decoding import GreedyCTCDecoder
 from . import data2vec_audio_model, hubert_model, sew_d_model, sew_model, wav2vec2_conformer_model, wavlm_model
-from .wav2vec2_model import Wav2Vec2ForCTC, config_from_json
+from .wav2vec2_model import Wav2Vec2ForCTC, config_from_json, make_config, param_spec
 from .wer import basic_normalize as normalize, word_error_rate_detail
 
 
@@ -86,6 +88,74 @@ def replicate(model, n):
     return out
 
 
+class VocabTokenizer:
+    """A character tokenizer from an HF `vocab.json`, with CharTokenizer's surface (`vocab_size`, `blank_id` = the id of `<pad>`, `decode(ids)`,
+    `tokenizer(text).input_ids`): `|` is the word delimiter, `<unk>` stands for every unknown character.  The file is flat `{token: id}` or
+    MMS's nested `{lang: {token: id}}`, of which `lang` picks one."""
+    SPECIAL = ("<pad>", "<s>", "</s>")
+
+    def __init__(self, vocab):
+        self.vocab = {str(k): int(v) for k, v in vocab.items()}
+        if "<pad>" not in self.vocab:
+            raise KeyError("vocab.json: no <pad> token (the CTC blank)")
+        self.ids = {i: t for t, i in self.vocab.items()}
+        self.blank_id = self.vocab["<pad>"]
+        self.unk_id = self.vocab.get("<unk>", self.blank_id)
+        self.vocab_size = max(self.ids) + 1
+
+    @classmethod
+    def from_json(cls, path, lang=None):
+        import json
+        with open(path) as f:
+            src = json.load(f)
+        if src and all(isinstance(v, dict) for v in src.values()):        # MMS: one vocabulary per language
+            if lang is None and len(src) == 1:
+                lang = next(iter(src))
+            if lang not in src:
+                raise KeyError(f"{path}: no vocabulary for language {lang!r} (it holds {sorted(src)[:8]})")
+            src = src[lang]
+        return cls(src)
+
+    def decode(self, ids):
+        out = []
+        for i in ids:
+            t = self.ids.get(int(i), "<unk>")
+            if t not in self.SPECIAL:
+                out.append(" " if t == "|" else t)
+        return "".join(out)
+
+    def __call__(self, text):
+        from types import SimpleNamespace
+        word = self.vocab.get("|", self.unk_id)
+        return SimpleNamespace(input_ids=[word if ch == " " else self.vocab.get(ch, self.unk_id) for ch in text])
+
+
+def adapter_names(cfg):
+    """The names transformers' `_get_adapters()` lists for this configuration: every adapter layer's parameters and lm_head's."""
+    return [n for n, _, _ in param_spec(make_config(cfg)) if ".adapter_layer." in n or n.startswith("lm_head.")]
+
+
+def load_target_lang(directory, lang, cfg):
+    """transformers' `load_adapter(lang)` from local files only: `DIR/adapter.LANG.safetensors`, else `DIR/adapter.LANG.bin`
+    (torch.load(weights_only=True)).  Its keys must be exactly adapter_names(cfg), else KeyError naming the missing and the unexpected ones.
+    Returns (state dict, vocab size of its lm_head.weight)."""
+    st, pt = (os.path.join(directory, f"adapter.{lang}.{ext}") for ext in ("safetensors", "bin"))
+    if os.path.exists(st):
+        from safetensors.torch import load_file
+        sd, path = load_file(st), st
+    elif os.path.exists(pt):
+        sd, path = torch.load(pt, map_location="cpu", weights_only=True), pt
+    else:
+        raise FileNotFoundError(f"no adapter file for language {lang!r}: neither {st} nor {pt} exists (local files only)")
+    names = adapter_names(cfg)
+    if not names or not any(".adapter_layer." in n for n in names):
+        raise KeyError(f"--target-lang {lang}: this configuration has no adapters (adapter_attn_dim with do_stable_layer_norm)")
+    missing, unexpected = [n for n in names if n not in sd], [k for k in sd if k not in names]
+    if missing or unexpected:
+        raise KeyError(f"{path}: the adapter file does not fit the model: missing keys {missing}, unexpected keys {unexpected}")
+    return sd, int(sd["lm_head.weight"].shape[0])
+
+
 def model_type(cfg_path):
     """`model_type` of an HF config.json ('' when it names none)."""
     import json
@@ -105,6 +175,15 @@ def load_pretrained_model(args, device):
     if ckpt and os.path.isdir(ckpt):
         cfg_path, ckpt = cfg_path or os.path.join(ckpt, 'config.json'), os.path.join(ckpt, 'pytorch_model.bin')
     kind = model_type(cfg_path) if cfg_path else ''         # what AutoModelForCTC dispatches on
+    lang, adapter_sd, tokenizer = getattr(args, 'target_lang', '') or '', None, None
+    if lang:
+        if kind not in ('', 'wav2vec2') or not (args.checkpoint and os.path.isdir(args.checkpoint)):
+            raise KeyError('--target-lang needs -c DIR, a local wav2vec2 (MMS) model directory with adapter.LANG.safetensors / .bin')
+        cfg = config_from_json(cfg_path)
+        adapter_sd, vocab = load_target_lang(args.checkpoint, lang, cfg)
+        cfg = dict(cfg, vocab_size=vocab)                    # the model is built at the adapter file's vocabulary
+    if ckpt and os.path.isdir(args.checkpoint) and os.path.exists(os.path.join(args.checkpoint, 'vocab.json')):
+        tokenizer = VocabTokenizer.from_json(os.path.join(args.checkpoint, 'vocab.json'), lang or None)
     if kind == 'wavlm':
         model = wavlm_model.WavLMForCTC(wavlm_model.config_from_json(cfg_path), device=device)
     elif kind == 'wav2vec2-conformer':
@@ -117,10 +196,16 @@ def load_pretrained_model(args, device):
         model = sew_model.SEWForCTC(sew_model.config_from_json(cfg_path), device=device)
     elif kind == 'sew-d':
         model = sew_d_model.SEWDForCTC(sew_d_model.config_from_json(cfg_path), device=device)
+    elif lang:
+        model = Wav2Vec2ForCTC(cfg, device=device)
     else:
         model = Wav2Vec2ForCTC(config_from_json(cfg_path) if cfg_path else None, device=device)
     if ckpt:
-        res = model.load_state_dict(torch.load(ckpt, map_location='cpu', weights_only=True), strict=False)
+        sd = torch.load(ckpt, map_location='cpu', weights_only=True)
+        if adapter_sd is not None:                           # HF's ignore_mismatched_sizes on this path: the base lm_head of another vocabulary goes
+            sd = {k: v for k, v in sd.items() if k not in adapter_sd or tuple(v.shape) == tuple(adapter_sd[k].shape)}
+            sd.update(adapter_sd)
+        res = model.load_state_dict(sd, strict=False)
         missing = getattr(res, 'missing_keys', [])
         if missing:
             raise KeyError(f'checkpoint {ckpt}: {len(missing)} parameters of the model are missing (e.g. {missing[:3]})')
@@ -129,9 +214,16 @@ def load_pretrained_model(args, device):
         if extra:
             raise KeyError(f'checkpoint {ckpt}: {len(extra)} feature-extractor parameters do not belong to the configured layout '
                            f'(e.g. {extra[:3]}): pass its config.json (-c DIR or --config)')
+        # adapter parameters the configuration has no slot for: an MMS checkpoint, which would otherwise run as another model
+        extra = [k for k in getattr(res, 'unexpected_keys', []) if '.adapter_layer.' in k]
+        if extra:
+            raise KeyError(f'checkpoint {ckpt}: {len(extra)} adapter parameters do not belong to the configured model (e.g. {extra[:3]}): '
+                           f'pass its config.json with adapter_attn_dim (-c DIR or --config)')
     else:
         init_synthetic(model, args.seed)
-    return model, lib.CharTokenizer()
+    if getattr(args, 'adapter_only', False):
+        model.adapter_only()
+    return model, tokenizer if tokenizer is not None else lib.CharTokenizer()
 
 
 def main(args):
@@ -141,7 +233,8 @@ def main(args):
     print(f'Loaded model from {args.checkpoint}')
     print(f'Total number of parameters: {sum(p.numel() for p in model.parameters()) / 1e6:.2f}M')
     model.eval()
-    tokenizer.blank_id = 0
+    if isinstance(tokenizer, lib.CharTokenizer):
+        tokenizer.blank_id = 0
     decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=tokenizer.blank_id, device=device)
     # the reference's driver walks the talks of the split, one dynamic_eval call each (tedlium/run.py:139-160); offline: `--talks` synthetic talks
     # (or the one `--stm` names).  Talks are independent (weights restored per call), so `--chains` of them can be in flight (lib.dynamic_eval_su_many)
@@ -196,6 +289,10 @@ def build_parser():
     ap.add_argument('--talks', type=int, default=1, help='synthetic talks of --seconds each (the reference walks the talks of the split)')
     ap.add_argument('--config', type=str, default='', help='HF config.json: architecture and layout (feat_extract_norm, conv_bias, do_stable_layer_norm) '
                                                            'for -c FILE or seeded weights; -c DIR reads DIR/config.json')
+    ap.add_argument('--target-lang', type=str, default='', help='MMS: load DIR/adapter.LANG.safetensors (or .bin) over the base weights of -c DIR; '
+                                                                'local files only')
+    ap.add_argument('--adapter-only', action='store_true', help='adapt only the adapters and lm_head (the MMS recipe); the rest is frozen and its '
+                                                                'weight gradients are skipped')
     ap.add_argument('--chains', type=int, default=1, help='talks in flight on the GPU (mode su): one model replica + HIP stream each')
     return ap
 

@@ -10,6 +10,11 @@ The other layout transformers has (wav2vec2-large-960h-lv60-self, large-robust, 
 `feat_extract_norm="layer"` + `conv_bias=True` (every extractor layer is conv -> + bias -> LayerNorm(C) -> GELU, the last three in one
 kernel each way: ops.bias_layernorm_gelu) and `do_stable_layer_norm=True` (pre-LN encoder: x + attn(LN(x)), x + ffn(LN(x)), the
 encoder's LayerNorm after the last layer).
+MMS (`facebook/mms-1b-all`, `mms-300m` fine-tunes) is that stable-LN layout plus `adapter_attn_dim: 16`: a bottleneck adapter behind every
+encoder layer, x + linear_2(relu(linear_1(LayerNorm(x)))) (transformers Wav2Vec2AttnAdapterLayer), one kernel forward and two backward
+(ops.attn_adapter / attn_adapter_bwd); `adapter_only()` freezes everything but the adapters and lm_head, and a backward skips the weight
+gradients of frozen parameters and everything below the first encoder layer when nothing there adapts.  No MMS checkpoint is on the machine:
+the oracle in the tests is transformers' Wav2Vec2ForCTC on the CPU with the same random state dict.
 Parameter NAMES are HF's (state_dict interchange with transformers, which is the oracle in tests); the native HBM layout
 of conv kernels is [C_out][kernel][C_in] so each strided Conv1d is one implicit GEMM over overlapping rows of the
 channels-last activation (ops.conv1d), converted on load / save.
@@ -27,10 +32,12 @@ DEFAULT_CONFIG = dict(
     conv_dim=(512,) * 7, conv_stride=(5, 2, 2, 2, 2, 2, 2), conv_kernel=(10, 3, 3, 3, 3, 2, 2), hidden_size=768,
     num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072, num_conv_pos_embeddings=128,
     num_conv_pos_embedding_groups=16, vocab_size=32, layer_norm_eps=1e-5,
+    adapter_attn_dim=None,    # MMS: the width A of a bottleneck adapter behind every stable-LN encoder layer (transformers Wav2Vec2AttnAdapterLayer)
 )
 
 
 LAYOUT_FLAGS = dict(feat_extract_norm="group", do_stable_layer_norm=False, conv_bias=False)     # the base layout
+ADAPTER_EPS = 1e-5        # the adapter's nn.LayerNorm is built with torch's default eps as well
 EXTRACTOR_EPS = 1e-5      # transformers builds the extractor's GroupNorm / LayerNorm with torch's default eps, not config.layer_norm_eps
 
 
@@ -49,6 +56,13 @@ def make_config(cfg=None, defaults=DEFAULT_CONFIG):
             if v is not None:
                 out[k] = v
     out["do_stable_layer_norm"], out["conv_bias"] = bool(out["do_stable_layer_norm"]), bool(out["conv_bias"])
+    A = out.get("adapter_attn_dim", None)
+    if A is not None:
+        if defaults is not DEFAULT_CONFIG:
+            raise ops.DynError(f"adapter_attn_dim={A!r} is not built for this model: the per-layer adapters exist for Wav2Vec2ForCTC only")
+        # with the post-LN encoder transformers builds no adapter whatever the value: nothing to check there
+        if out["do_stable_layer_norm"] and not (isinstance(A, int) and A % 4 == 0 and 4 <= A <= 64):
+            raise ops.DynError(f"adapter_attn_dim={A!r} is not built: the adapter kernels take a multiple of 4 from 4 to 64")
     if (out["feat_extract_norm"], out["conv_bias"]) not in (("group", False), ("layer", True)):
         raise ops.DynError(f"feat_extract_norm={out['feat_extract_norm']!r} with conv_bias={out['conv_bias']} is not built: the feature "
                            "extractor is either (\"group\", conv_bias=False) or (\"layer\", conv_bias=True)")
@@ -66,8 +80,8 @@ def config_dict(cfg, keys):
 
 
 def config_from_json(path, make=make_config):
-    """An HF `config.json` as plain JSON -> make_config (only DEFAULT_CONFIG's keys and the three layout flags are read; `make`: the
-    configuration reader of another model of the family)."""
+    """An HF `config.json` as plain JSON -> make_config (only DEFAULT_CONFIG's keys and the three layout flags are read, `adapter_attn_dim`
+    among them: JSON null or an absent key means no adapters; `make`: the configuration reader of another model of the family)."""
     import json
     with open(path) as f:
         src = json.load(f)
@@ -112,6 +126,14 @@ def _wn_join(t, s):
 _RELEASED = object()      # Wav2Vec2ForCTC._ctx after a bucket replay whose saved activations are owned by its graphs only
 
 
+def adapter_dim(c):
+    """The adapters' width, or None: transformers builds them in the stable-LN encoder's layers only."""
+    return c.get("adapter_attn_dim", None) if c.get("do_stable_layer_norm", False) else None
+
+
+ADAPTER_PARAMS = ("norm.weight", "norm.bias", "linear_1.weight", "linear_1.bias", "linear_2.weight", "linear_2.bias")
+
+
 def param_spec(c, pf="wav2vec2."):
     """[(name, shape, kind)] with HF's names (`pf`: the base model's prefix); kind "conv": a conv kernel kept as [C_out][kernel][C_in],
     "g": the weight norm's magnitudes."""
@@ -146,6 +168,11 @@ def param_spec(c, pf="wav2vec2."):
                  (p + "feed_forward.output_dense.weight", (H, c["intermediate_size"]), None),
                  (p + "feed_forward.output_dense.bias", (H,), None),
                  (p + "final_layer_norm.weight", (H,), None), (p + "final_layer_norm.bias", (H,), None)]
+        A = adapter_dim(c)
+        if A:                                                       # HF's order inside Wav2Vec2AttnAdapterLayer: norm, linear_1, linear_2
+            ad = p + "adapter_layer."
+            spec += [(ad + "norm.weight", (H,), None), (ad + "norm.bias", (H,), None), (ad + "linear_1.weight", (A, H), None),
+                     (ad + "linear_1.bias", (A,), None), (ad + "linear_2.weight", (H, A), None), (ad + "linear_2.bias", (H,), None)]
     spec += [("lm_head.weight", (c["vocab_size"], H), None), ("lm_head.bias", (c["vocab_size"],), None)]
     return spec
 
@@ -163,6 +190,7 @@ class Wav2Vec2ForCTC(FlatModel):
     _qkv_fmt = "attention.{}_proj"
     _make_config = staticmethod(make_config)
     _param_spec = staticmethod(param_spec)
+    _norm_weight_suffixes = ("adapter_layer.norm.weight",)       # run_wav2vec2.init_synthetic starts these around 1 too
 
     def __init__(self, config=None, device="cuda:0"):
         self.cfg = self._make_config(config)
@@ -171,6 +199,7 @@ class Wav2Vec2ForCTC(FlatModel):
         assert H % 256 == 0 and c["conv_dim"][-1] % 256 == 0, "LayerNorm kernels need C % 256 == 0"
         self.layer_extractor = c["feat_extract_norm"] == "layer"
         self.stable_ln = c["do_stable_layer_norm"]
+        self.adapter_dim = adapter_dim(c)
         if self.layer_extractor and any(d % 256 and d not in (64, 128) for d in c["conv_dim"]):
             raise ops.DynError(f"feat_extract_norm=\"layer\" needs every conv_dim to be 64, 128 or a multiple of 256 (got {c['conv_dim']})")
         spec = self._param_spec(c, pf)
@@ -419,7 +448,7 @@ class Wav2Vec2ForCTC(FlatModel):
         fp = self._prefix + "feature_projection."
         dn = self._lin_bwd(dhs, n, fp + "projection.weight", fp + "projection.bias")
         da = torch.empty_like(dn)
-        ops.layernorm_bwd(a, P[fp + "layer_norm.weight"], mean, rstd, dn, da, G[fp + "layer_norm.weight"], G[fp + "layer_norm.bias"], dx_beta=0.0)
+        ops.layernorm_bwd(a, P[fp + "layer_norm.weight"], mean, rstd, dn, da, self._g(fp + "layer_norm.weight"), self._g(fp + "layer_norm.bias"), dx_beta=0.0)
         return da
 
     def _encode(self, h, ctx, vT, dims, v0):
@@ -564,8 +593,13 @@ class Wav2Vec2ForCTC(FlatModel):
             ga = ops.gelu(u)
             r2 = r1.clone() if save else r1
             ops.linear(ga, P[p + "feed_forward.output_dense.weight"], P[p + "feed_forward.output_dense.bias"], out=r2, beta=1.0)
+            kept = ()
+            if self.adapter_dim:                                    # x + adapter(x), one launch; in place when nothing is kept
+                w = [P[p + "adapter_layer." + n] for n in ADAPTER_PARAMS]
+                y, am, ars, aa = ops.attn_adapter(r2, *w, eps=ADAPTER_EPS, out=None if save else r2, save=save)
+                kept, r2 = ((r2, am, ars, aa),), y
             if save:
-                ctx["layers"].append((x, m1, s1, n1, qkv, S, O, r1, m2, s2, n2, u, ga))
+                ctx["layers"].append((x, m1, s1, n1, qkv, S, O, r1, m2, s2, n2, u, ga) + kept)
             x = r2
         h, mean, rstd = ops.layernorm(x, P[pf + "encoder.layer_norm.weight"], P[pf + "encoder.layer_norm.bias"], eps)
         logits = ops.linear(h, P["lm_head.weight"], P["lm_head.bias"])
@@ -593,7 +627,10 @@ class Wav2Vec2ForCTC(FlatModel):
         _attn.grad_qk(dP, q, k, dq, dk, D ** -0.5)
         M = nb * T
         if self.packed_qkv:                                      # the three projections as one [3H, H] product each way
-            self._wgrad(dqkv.view(M, 3 * H), h.view(M, H), self.Gqkv[l][0], self.Gqkv[l][1])
+            q, v = self._qv_names(l)
+            k = q[:-len(self._qkv_fmt.format("q"))] + self._qkv_fmt.format("k")
+            if any(self.trainable(n + s) for n in (q, k, v) for s in (".weight", ".bias")):     # all six frozen: no product
+                self._wgrad(dqkv.view(M, 3 * H), h.view(M, H), self.Gqkv[l][0], self.Gqkv[l][1])
             dh_in = torch.empty_like(dO)                         # the residual path may be a queued operand: not accumulated in place
             if residual is not None:
                 ops.gemm(dqkv, self.Pqkv[l][0], dh_in, M=M, N=H, K=3 * H, lda=3 * H, ldb=H, ldc=H, beta=1.0, c_in=residual)
@@ -625,8 +662,13 @@ class Wav2Vec2ForCTC(FlatModel):
         if db is not None:
             ops.colsum(dy, db, beta=1.0)
 
+    def _g(self, name):
+        """The gradient buffer of a parameter, or None when it is frozen: a kernel that takes a null gradient pointer skips that sum."""
+        return self.G[name] if self.trainable(name) else None
+
     def _lin_bwd(self, dy, x, wname, bname, need_dx=True):
-        self._wgrad(dy, x, self.G[wname], self.G[bname] if bname is not None else None)
+        if self.trainable(wname) or (bname is not None and self.trainable(bname)):      # both frozen: no product, no column sum
+            self._wgrad(dy, x, self.G[wname], self.G[bname] if bname is not None else None)
         return ops.linear_dgrad(dy, self.P[wname]) if need_dx else None
 
     def backward(self, grad_logits, n_active=None):
@@ -696,6 +738,9 @@ class Wav2Vec2ForCTC(FlatModel):
             return t[:nb]
 
         dhs = self._backward_encoder(ctx, grad_logits, nb, cut)
+        if dhs is None:                                              # everything below the encoder's layers is frozen
+            self._ctx = None
+            return
         # feature projection
         da = self._project_bwd(cut(ctx["proj"]), dhs)
         # conv feature extractor
@@ -739,23 +784,28 @@ class Wav2Vec2ForCTC(FlatModel):
         if self.stable_ln:
             x, mean, rstd = cut(ctx["final"])
             dx = torch.empty_like(dh)
-            ops.layernorm_bwd(x, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dx, G[pf + "encoder.layer_norm.weight"],
-                              G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
+            ops.layernorm_bwd(x, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dx, self._g(pf + "encoder.layer_norm.weight"),
+                              self._g(pf + "encoder.layer_norm.bias"), dx_beta=0.0)
         for l in reversed(range(c["num_hidden_layers"]) if self.stable_ln else ()):
             # x -> r1 = x + out_proj(attn(LN1(x))) -> r2 = r1 + ffn(LN2(r1)); dx is dL/dr2.  Each residual sum rides on the LayerNorm
             # backward's dx = grad + dx_in form (out of place: dx / dr1 are queued weight-gradient operands), so no add pass of its own.
             p = f"{pf}encoder.layers.{l}."
-            x, m1, s1, n1, qkv, S, O, r1, m2, s2, n2, u, ga = cut(ctx["layers"][l])
+            x, m1, s1, n1, qkv, S, O, r1, m2, s2, n2, u, ga, *kept = cut(ctx["layers"][l])
+            if kept:                                                 # the adapter behind the layer: dx becomes dL/d(its input), out of place
+                r2, am, ars, aa = kept[0]
+                ad = p + "adapter_layer."
+                dx = ops.attn_adapter_bwd(r2, P[ad + "norm.weight"], P[ad + "norm.bias"], P[ad + "linear_1.weight"], P[ad + "linear_2.weight"],
+                                          am, ars, aa, dx, *(self._g(ad + n) for n in ADAPTER_PARAMS))
             dga = self._lin_bwd(dx, ga, p + "feed_forward.output_dense.weight", p + "feed_forward.output_dense.bias")
             du = ops.gelu_bwd(u, dga, out=dga)
             dn2 = self._lin_bwd(du, n2, p + "feed_forward.intermediate_dense.weight", p + "feed_forward.intermediate_dense.bias")
             dr1 = torch.empty_like(dx)
-            ops.layernorm_bwd(r1, P[p + "final_layer_norm.weight"], m2, s2, dn2, dr1, G[p + "final_layer_norm.weight"],
-                              G[p + "final_layer_norm.bias"], dx_beta=1.0, dx_in=dx)
+            ops.layernorm_bwd(r1, P[p + "final_layer_norm.weight"], m2, s2, dn2, dr1, self._g(p + "final_layer_norm.weight"),
+                              self._g(p + "final_layer_norm.bias"), dx_beta=1.0, dx_in=dx)
             dO = self._lin_bwd(dr1, O, p + "attention.out_proj.weight", p + "attention.out_proj.bias")
             dn1 = self._attention_bwd(dO, qkv, S, n1, l, nb, T, None)
             dx = torch.empty_like(dr1)
-            ops.layernorm_bwd(x, P[p + "layer_norm.weight"], m1, s1, dn1, dx, G[p + "layer_norm.weight"], G[p + "layer_norm.bias"],
+            ops.layernorm_bwd(x, P[p + "layer_norm.weight"], m1, s1, dn1, dx, self._g(p + "layer_norm.weight"), self._g(p + "layer_norm.bias"),
                               dx_beta=1.0, dx_in=dr1)
             ctx["layers"][l] = None
         if not self.stable_ln:
@@ -767,9 +817,23 @@ class Wav2Vec2ForCTC(FlatModel):
             dhs = dx                                                 # dL/d(h + pos): no queued product reads it, so the pos path adds in place
         else:
             dhs = torch.empty_like(dh)
-            ops.layernorm_bwd(hs, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dhs, G[pf + "encoder.layer_norm.weight"],
-                              G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
+            ops.layernorm_bwd(hs, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dhs, self._g(pf + "encoder.layer_norm.weight"),
+                              self._g(pf + "encoder.layer_norm.bias"), dx_beta=0.0)
+        if self._below_frozen():                                    # nothing under the first encoder layer adapts: its backward is not needed
+            return None
         return self._pos_embed_bwd(kept, dhs, nb, cut, vT)
+
+    def _below_frozen(self):
+        """True when no parameter below the encoder's layers (positional embedding, feature projection, extractor) is trainable."""
+        above = (self._prefix + "encoder.layers.", self._prefix + "encoder.layer_norm.", "lm_head.")
+        return not any(self.trainable(n) for n, _ in self.spec if not n.startswith(above))
+
+    def adapter_only(self):
+        """The MMS recipe: freeze everything but the adapters and lm_head (the keys of transformers' `_get_adapters()`)."""
+        if not self.adapter_dim:
+            raise ops.DynError("adapter_only(): this model has no adapters (adapter_attn_dim with do_stable_layer_norm)")
+        self.frozen = {n for n, _ in self.spec if ".adapter_layer." not in n and not n.startswith("lm_head.")}
+        return self
 
     def _post_ln_layers_bwd(self, ctx, dh, nb, T, cut):
         """Backward of _post_ln_layers from dh [nb, T, H], the gradient of its output: accumulates the layers' gradients, returns the
@@ -779,14 +843,14 @@ class Wav2Vec2ForCTC(FlatModel):
             p = f"{pf}encoder.layers.{l}."
             h, qkv, S, O, r1, m1, s1, h1, u, ga, r2, m2, s2 = cut(ctx["layers"][l])
             dr2 = torch.empty_like(dh)
-            ops.layernorm_bwd(r2, P[p + "final_layer_norm.weight"], m2, s2, dh, dr2, G[p + "final_layer_norm.weight"],
-                              G[p + "final_layer_norm.bias"], dx_beta=0.0)
+            ops.layernorm_bwd(r2, P[p + "final_layer_norm.weight"], m2, s2, dh, dr2, self._g(p + "final_layer_norm.weight"),
+                              self._g(p + "final_layer_norm.bias"), dx_beta=0.0)
             dga = self._lin_bwd(dr2, ga, p + "feed_forward.output_dense.weight", p + "feed_forward.output_dense.bias")
             du = ops.gelu_bwd(u, dga, out=dga)
             dh1 = self._lin_bwd(du, h1, p + "feed_forward.intermediate_dense.weight", p + "feed_forward.intermediate_dense.bias")
             ops.axpby(dr2, dh1, 1.0, 1.0)                            # residual: h1 feeds both the FFN and r2
             dr1 = torch.empty_like(dh1)
-            ops.layernorm_bwd(r1, P[p + "layer_norm.weight"], m1, s1, dh1, dr1, G[p + "layer_norm.weight"], G[p + "layer_norm.bias"],
+            ops.layernorm_bwd(r1, P[p + "layer_norm.weight"], m1, s1, dh1, dr1, self._g(p + "layer_norm.weight"), self._g(p + "layer_norm.bias"),
                               dx_beta=0.0)
             dO = self._lin_bwd(dr1, O, p + "attention.out_proj.weight", p + "attention.out_proj.bias")
             dh_in = self._attention_bwd(dO, qkv, S, h, l, nb, T, dr1)

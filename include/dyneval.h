@@ -686,6 +686,30 @@ int dyn_disentangled_bwd(const float* dS, float* dC2P, float* dP2CT, const int32
                          int64_t M, int64_t T, int64_t ldp, int64_t n_buckets, const int32_t* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * MMS adapters (csrc/attn_adapter.hip).  For an MMS checkpoint (`adapter_attn_dim: 16`) the reference's loader,
+ * `AutoModelForCTC.from_pretrained(checkpoint)` (wav2vec2/lib.py:20-23), builds transformers' Wav2Vec2ForCTC with a Wav2Vec2AttnAdapterLayer
+ * behind every stable-LN encoder layer; `model(x).logits` (:163,413) then runs `hidden_states + self.adapter_layer(hidden_states)` =
+ * x + linear_2(relu(linear_1(norm(x)))) per layer and `loss.backward()` its autograd.  x [M, H] row-major, gamma / beta [H] the norm,
+ * W1 [A, H] / b1 [A] linear_1, W2 [H, A] / b2 [H] linear_2.  H % 256 == 0 and H <= 2048, A % 4 == 0 and 4 <= A <= 64, non-null required
+ * pointers, 16-byte aligned operands, else DYN_E_ARG naming the entry.
+ *   dyn_attn_adapter_fwd   y [M, H] = x + W2 relu(W1 LayerNorm(x) + b1) + b2 in one launch (centred variance; the normalised row is never
+ *                          written); y may be x.  mean / rstd [M] and a [M, A] (the post-ReLU bottleneck) are written when non-null.
+ *   dyn_attn_adapter_bwd   from x, mean, rstd, a, dy [M, H]: dx [M, H] = dy + the adapter path, out of place (dx must alias neither dy nor x,
+ *                          both are left unmodified).  dgamma, dbeta, dW1, db1, dW2, db2 += their sums over the M rows (beta = 1); each may be
+ *                          null and is then not computed.  The ReLU mask is a > 0.  A row of dy that is all zeros gives an all-zero row of dx
+ *                          and adds exact zeros to every sum.  Two launches: the rows, then every sum in a fixed order from du [M, A] and
+ *                          per-workgroup partial rows in `workspace` (dyn_attn_adapter_bwd_workspace_bytes(M, H, A), DYN_E_WORKSPACE when
+ *                          smaller; not needed with all six null): no atomics, the same call twice gives the same bits.
+ * No call synchronises or allocates: all are captured into the length buckets' hipGraphs. */
+int dyn_attn_adapter_fwd(const float* x, const float* gamma, const float* beta, const float* W1, const float* b1, const float* W2,
+                         const float* b2, float* y, float* mean, float* rstd, float* a, int64_t M, int64_t H, int64_t A, float eps,
+                         void* stream);
+int64_t dyn_attn_adapter_bwd_workspace_bytes(int64_t M, int64_t H, int64_t A);
+int dyn_attn_adapter_bwd(const float* x, const float* gamma, const float* beta, const float* W1, const float* W2, const float* mean,
+                         const float* rstd, const float* a, const float* dy, float* dx, float* dgamma, float* dbeta, float* dW1, float* db1,
+                         float* dW2, float* db2, int64_t M, int64_t H, int64_t A, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * WavLM attention: gated relative-position bias.  The reference's loader, `AutoModelForCTC.from_pretrained(checkpoint)`
  * (wav2vec2/lib.py:20-23), builds transformers' WavLMForCTC for a WavLM checkpoint; `model(x).logits` (:163,413) and
  * `loss.backward()` (:194,437) then run WavLMAttention.forward (modeling_wavlm.py) in every layer.  With h [B, T, H] the attention's
