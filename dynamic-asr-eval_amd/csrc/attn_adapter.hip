@@ -12,20 +12,21 @@
 // Staging: neither W1 nor W2 is staged in LDS.  Both are read through the vector L1 / L2 with 16-B loads: the 4 waves of a workgroup work
 // on 4 neighbouring rows and read the same weight addresses at nearly the same time, and at the M of one utterance (a few hundred rows over
 // 256 CUs) a workgroup sees a handful of rows, too few to pay for filling 80 KiB of LDS first.  LDS holds the cross-wave combines only.
-// As squeeze.hip / norm.hip: the row in registers (NV = H / 256 float4 per lane), centred variance, statistics by wavefront reductions.
+// The LayerNorm of the two row kernels is layernorm_row.h's (the row in registers, NV = H / 256 float4 per lane).
 // Nothing here synchronises or allocates.
 #include "common.h"
+#include "layernorm_row.h"
 
 namespace {
 
-constexpr int WPB = 4;               // waves (rows in flight) per workgroup of the two row kernels
+using dyn::aligned16;
+using dyn::dot4;
+using dyn::ld4;
+using dyn::st4;
+constexpr int WPB = dyn::ROW_WPB;    // waves (rows in flight) per workgroup of the two row kernels
 constexpr int MAX_BWD_BLOCKS = 512;  // partial rows of the backward's column sums
 constexpr int GW = 16;               // waves per workgroup of the second backward stage
 constexpr int DB1_COLS = 64;         // columns the db1 partials take in a partial row (A <= 64)
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 
 // x and y may be the same buffer: a wave holds its whole row before it writes it.
 template <int NV>
@@ -45,6 +46,8 @@ __global__ __launch_bounds__(256) void adapter_fwd_kernel(const float* x, const 
             v[j] = ld4(x + row * H + 4 * (lane + 64 * j));
             sum += v[j].x + v[j].y + v[j].z + v[j].w;
         }
+        // dyn::row_mean_rstd(v, sum, eps, mean, rstd), spelt out: through the call the compiler fuses other multiply-adds of the NV = 3 and 5
+        // instances, which changes the bits of y there
         const float mean = dyn::wave_sum(sum) / H;
         float q = 0.f;
 #pragma unroll
@@ -174,36 +177,23 @@ __global__ __launch_bounds__(256) void adapter_bwd_kernel(const float* __restric
             ab[j].x += dn[j].x; ab[j].y += dn[j].y; ab[j].z += dn[j].z; ab[j].w += dn[j].w;
             ac[j].x += d[j].x; ac[j].y += d[j].y; ac[j].z += d[j].z; ac[j].w += d[j].w;
             g[j].x = dn[j].x * gm.x; g[j].y = dn[j].y * gm.y; g[j].z = dn[j].z * gm.z; g[j].w = dn[j].w * gm.w;
-            s1 += g[j].x + g[j].y + g[j].z + g[j].w;
-            s2 += dot4(g[j], xh[j]);
+            dyn::bwd_lane_sums(g[j], xh[j], s1, s2);
         }
-        s1 = dyn::wave_sum(s1) / H;
-        s2 = dyn::wave_sum(s2) / H;
+        dyn::bwd_row_means<NV>(s1, s2);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            float4 o;
+            float4 o;                // dy + dyn::bwd4(): the residual is the addend of bwd4's last multiply, so the expression is spelt out here
             o.x = d[j].x + rstd * (g[j].x - s1 - xh[j].x * s2); o.y = d[j].y + rstd * (g[j].y - s1 - xh[j].y * s2);
             o.z = d[j].z + rstd * (g[j].z - s1 - xh[j].z * s2); o.w = d[j].w + rstd * (g[j].w - s1 - xh[j].w * s2);
             st4(dx + row * H + 4 * (lane + 64 * j), o);
         }
     }
     if (!partial) return;                                            // uniform over the grid
-    // Combine the 4 waves' column sums in wave order, then write this workgroup's partial row.
+    // The 4 waves' column sums in wave order into this workgroup's partial row.
     float* prow = partial + (int64_t)blockIdx.x * (3 * H + DB1_COLS);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        for (int pass = 0; pass < 3; ++pass) {
-            __syncthreads();
-            red[w][lane] = pass == 0 ? ag[j] : pass == 1 ? ab[j] : ac[j];
-            __syncthreads();
-            if (w == 0) {
-                float4 t = red[0][lane];
-#pragma unroll
-                for (int k = 1; k < WPB; ++k) { t.x += red[k][lane].x; t.y += red[k][lane].y; t.z += red[k][lane].z; t.w += red[k][lane].w; }
-                st4(prow + pass * H + 4 * (lane + 64 * j), t);
-            }
-        }
-    }
+    dyn::combine_waves(ag, red, prow);
+    dyn::combine_waves(ab, red, prow + H);
+    dyn::combine_waves(ac, red, prow + 2 * H);
     redu[w][lane] = au;
     __syncthreads();
     if (w == 0) {
@@ -296,15 +286,6 @@ __global__ __launch_bounds__(1024) void adapter_bwd_sums_kernel(const float* __r
     }
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-inline int bwd_blocks(int64_t M) {
-    int64_t g = dyn::cdiv(M, WPB);
-    if (g > MAX_BWD_BLOCKS) g = MAX_BWD_BLOCKS;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 inline int64_t du_floats(int64_t M, int64_t A) { return (M * A + 63) / 64 * 64; }
 
 inline int check_shape(const char* who, int64_t M, int64_t H, int64_t A) {
@@ -314,19 +295,11 @@ inline int check_shape(const char* who, int64_t M, int64_t H, int64_t A) {
     return DYN_OK;
 }
 
-}  // namespace
+// The built instances: NV = H / 256 in {1 .. 8}; check_shape admits no other H.
+template <class Go>
+void dispatch(int64_t H, Go go) { dyn::dispatch_nv<1, 2, 3, 4, 5, 6, 7, 8>(H, go); }
 
-#define ADAPTER_BY_NV(KERNEL, ...)                                                                   \
-    switch (H / 256) {                                                                               \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, grid, blk, 0, st, __VA_ARGS__); break;                 \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, grid, blk, 0, st, __VA_ARGS__); break;                 \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, grid, blk, 0, st, __VA_ARGS__); break;                 \
-        case 4: hipLaunchKernelGGL(KERNEL<4>, grid, blk, 0, st, __VA_ARGS__); break;                 \
-        case 5: hipLaunchKernelGGL(KERNEL<5>, grid, blk, 0, st, __VA_ARGS__); break;                 \
-        case 6: hipLaunchKernelGGL(KERNEL<6>, grid, blk, 0, st, __VA_ARGS__); break;                 \
-        case 7: hipLaunchKernelGGL(KERNEL<7>, grid, blk, 0, st, __VA_ARGS__); break;                 \
-        default: hipLaunchKernelGGL(KERNEL<8>, grid, blk, 0, st, __VA_ARGS__); break;                \
-    }
+}  // namespace
 
 extern "C" int dyn_attn_adapter_fwd(const float* x, const float* gamma, const float* beta, const float* W1, const float* b1, const float* W2,
                                     const float* b2, float* y, float* mean, float* rstd, float* a, int64_t M, int64_t H, int64_t A, float eps,
@@ -337,17 +310,17 @@ extern "C" int dyn_attn_adapter_fwd(const float* x, const float* gamma, const fl
     DYN_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(W1) && aligned16(W2) && aligned16(b2) && aligned16(y), DYN_E_ARG,
                 "dyn_attn_adapter_fwd: operands must be 16-byte aligned");
     if (M == 0) return DYN_OK;
-    int64_t gq = dyn::cdiv(M, WPB);
-    if (gq > 2048) gq = 2048;
-    dim3 grid((unsigned)gq), blk(256);
+    dim3 grid(dyn::row_blocks(M, WPB, 2048)), blk(256);
     hipStream_t st = (hipStream_t)stream;
-    ADAPTER_BY_NV(adapter_fwd_kernel, x, gamma, beta, W1, b1, W2, b2, y, mean, rstd, a, M, (int)A, eps)
+    dispatch(H, [&](auto nv) {
+        hipLaunchKernelGGL(adapter_fwd_kernel<decltype(nv)::value>, grid, blk, 0, st, x, gamma, beta, W1, b1, W2, b2, y, mean, rstd, a, M, (int)A, eps);
+    });
     return dyn::check_launch("dyn_attn_adapter_fwd");
 }
 
 extern "C" int64_t dyn_attn_adapter_bwd_workspace_bytes(int64_t M, int64_t H, int64_t A) {
     if (M < 0 || H <= 0 || A <= 0) return 0;
-    return (du_floats(M, A) + (int64_t)bwd_blocks(M) * (3 * H + DB1_COLS)) * (int64_t)sizeof(float);
+    return (du_floats(M, A) + (int64_t)dyn::row_blocks(M, WPB, MAX_BWD_BLOCKS) * (3 * H + DB1_COLS)) * (int64_t)sizeof(float);
 }
 
 extern "C" int dyn_attn_adapter_bwd(const float* x, const float* gamma, const float* beta, const float* W1, const float* W2, const float* mean,
@@ -364,7 +337,7 @@ extern "C" int dyn_attn_adapter_bwd(const float* x, const float* gamma, const fl
                 DYN_E_ARG, "dyn_attn_adapter_bwd: operands must be 16-byte aligned");
     if (M == 0) return DYN_OK;
     const bool vec = dgamma || dbeta || db1 || db2;
-    const int nb = bwd_blocks(M);
+    const int nb = dyn::row_blocks(M, WPB, MAX_BWD_BLOCKS);
     float *du = nullptr, *partial = nullptr;
     if (vec || dW1 || dW2) {
         DYN_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= dyn_attn_adapter_bwd_workspace_bytes(M, H, A), DYN_E_WORKSPACE,
@@ -373,10 +346,9 @@ extern "C" int dyn_attn_adapter_bwd(const float* x, const float* gamma, const fl
         if (vec) partial = (float*)workspace + du_floats(M, A);
     }
     hipStream_t st = (hipStream_t)stream;
-    {
-        dim3 grid(nb), blk(256);
-        ADAPTER_BY_NV(adapter_bwd_kernel, x, gamma, W1, W2, mean, rstd, a, dy, dx, du, partial, M, (int)A)
-    }
+    dispatch(H, [&](auto nv) {
+        hipLaunchKernelGGL(adapter_bwd_kernel<decltype(nv)::value>, dim3(nb), dim3(256), 0, st, x, gamma, W1, W2, mean, rstd, a, dy, dx, du, partial, M, (int)A);
+    });
     if (vec || dW1 || dW2) {
         // The six outputs are written by no other entry, so nothing a deferral context has recorded can be overtaken here.
         const int n_gemm = (dW1 || dW2) ? (int)((H / 256) * (A / 4)) : 0;

@@ -4,22 +4,23 @@
 //   forward:  act = gelu(LN(z + conv_bias));  mean / rstd [rows] kept for the backward; z (the raw conv output) is left alone
 //   backward: xhat and n = xhat * gamma + beta are RECOMPUTED from z, mean, rstd (the normalised tensor is never stored),
 //             dn = dact * gelu'(n), dz = LayerNorm backward of dn, dgamma = sum dn * xhat, dbeta = sum dn, dconv_bias = sum dz.
-// As in norm.hip: one wave64 per row, 16-B accesses, the row in registers (NV = C / 256 float4 per lane and tensor), row statistics
-// by wavefront reductions; the three column sums are accumulated per workgroup in registers, written as partial rows and summed
-// by the fixed-order reducers (reduce.h; deferrable): no atomics, bit-reproducible.  Nothing here synchronises or allocates.
+// The row kernels are layernorm_row.h's (one wave64 per row, NV = C / 256 float4 per lane and tensor); the three column sums are
+// accumulated per workgroup in registers, written as partial rows and summed by the fixed-order reducers.  Nothing here synchronises or allocates.
 // Registers at C = 512 (NV = 2): the backward holds z, dact (16 floats), three accumulators (24) and gamma, beta, bias (24) per lane,
 // 117 VGPRs = 4 waves per SIMD; its LDS is the 4 KiB combine buffer.  HBM-bound, so the backward spreads the rows over up to 1024
 // workgroups of 4 rows in flight (4 waves on every SIMD at the 52428-row layer) at 3 partial rows of C floats per workgroup.
 #include "common.h"
 #include "gelu.h"
+#include "layernorm_row.h"
 #include "reduce.h"
 
 namespace {
 
-constexpr int WPB = 4;           // waves (rows in flight) per workgroup
+using dyn::aligned16;
+using dyn::ld4;
+using dyn::st4;
+constexpr int WPB = dyn::ROW_WPB;
 constexpr int MAX_BWD_BLOCKS = 1024;
-
-__device__ __forceinline__ float4 ld4(const float* p, int i) { return reinterpret_cast<const float4*>(p)[i]; }
 
 template <int NV>
 __global__ __launch_bounds__(256) void blg_fwd_kernel(const float* __restrict__ z, const float* __restrict__ cbias,
@@ -41,17 +42,11 @@ __global__ __launch_bounds__(256) void blg_fwd_kernel(const float* __restrict__ 
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             v[j] = ld4(z + row * C, lane + 64 * j);
-            v[j].x += cb[j].x; v[j].y += cb[j].y; v[j].z += cb[j].z; v[j].w += cb[j].w;
+            dyn::add4(v[j], cb[j]);
             s += v[j].x + v[j].y + v[j].z + v[j].w;
         }
-        const float mean = dyn::wave_sum(s) / C;
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const float a0 = v[j].x - mean, a1 = v[j].y - mean, a2 = v[j].z - mean, a3 = v[j].w - mean;
-            q += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-        }
-        const float rstd = rsqrtf(dyn::wave_sum(q) / C + eps);
+        float mean, rstd;
+        dyn::row_mean_rstd(v, s, eps, mean, rstd);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             float4 o;
@@ -59,7 +54,7 @@ __global__ __launch_bounds__(256) void blg_fwd_kernel(const float* __restrict__ 
             o.y = dyn::gelu_f((v[j].y - mean) * rstd * g[j].y + b[j].y);
             o.z = dyn::gelu_f((v[j].z - mean) * rstd * g[j].z + b[j].z);
             o.w = dyn::gelu_f((v[j].w - mean) * rstd * g[j].w + b[j].w);
-            reinterpret_cast<float4*>(act + row * C)[lane + 64 * j] = o;
+            st4(act + row * C, o, lane + 64 * j);
         }
         if (lane == 0) {
             mean_out[row] = mean;
@@ -105,39 +100,19 @@ __global__ __launch_bounds__(256) void blg_bwd_kernel(const float* __restrict__ 
             ag[j].x += dn.x * xh[j].x; ag[j].y += dn.y * xh[j].y; ag[j].z += dn.z * xh[j].z; ag[j].w += dn.w * xh[j].w;
             ab[j].x += dn.x; ab[j].y += dn.y; ab[j].z += dn.z; ab[j].w += dn.w;
             gy[j].x = dn.x * g[j].x; gy[j].y = dn.y * g[j].y; gy[j].z = dn.z * g[j].z; gy[j].w = dn.w * g[j].w;
-            s1 += gy[j].x + gy[j].y + gy[j].z + gy[j].w;
-            s2 += gy[j].x * xh[j].x + gy[j].y * xh[j].y + gy[j].z * xh[j].z + gy[j].w * xh[j].w;
+            dyn::bwd_lane_sums(gy[j], xh[j], s1, s2);
         }
-        s1 = dyn::wave_sum(s1) / C;
-        s2 = dyn::wave_sum(s2) / C;
+        dyn::bwd_row_means<NV>(s1, s2);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            float4 o;
-            o.x = rstd * (gy[j].x - s1 - xh[j].x * s2);
-            o.y = rstd * (gy[j].y - s1 - xh[j].y * s2);
-            o.z = rstd * (gy[j].z - s1 - xh[j].z * s2);
-            o.w = rstd * (gy[j].w - s1 - xh[j].w * s2);
-            ac[j].x += o.x; ac[j].y += o.y; ac[j].z += o.z; ac[j].w += o.w;
-            reinterpret_cast<float4*>(dz + row * C)[lane + 64 * j] = o;
+            const float4 o = dyn::bwd4(gy[j], xh[j], rstd, s1, s2);
+            dyn::add4(ac[j], o);
+            st4(dz + row * C, o, lane + 64 * j);
         }
     }
-    // Combine the 4 waves' column sums in wave order, then write this workgroup's partial rows.
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        for (int pass = 0; pass < 3; ++pass) {
-            float* partial = pass == 0 ? partial_g : pass == 1 ? partial_b : partial_c;
-            if (!partial) continue;                                  // uniform over the grid
-            __syncthreads();
-            red[w][lane] = pass == 0 ? ag[j] : pass == 1 ? ab[j] : ac[j];
-            __syncthreads();
-            if (w == 0) {
-                float4 t = red[0][lane];
-#pragma unroll
-                for (int k = 1; k < WPB; ++k) { t.x += red[k][lane].x; t.y += red[k][lane].y; t.z += red[k][lane].z; t.w += red[k][lane].w; }
-                reinterpret_cast<float4*>(partial + (int64_t)blockIdx.x * C)[lane + 64 * j] = t;
-            }
-        }
-    }
+    if (partial_g) dyn::combine_waves(ag, red, partial_g + (int64_t)blockIdx.x * C);     // null or not: uniform over the grid
+    if (partial_b) dyn::combine_waves(ab, red, partial_b + (int64_t)blockIdx.x * C);
+    if (partial_c) dyn::combine_waves(ac, red, partial_c + (int64_t)blockIdx.x * C);
 }
 
 // The same two passes for the narrow extractors (SEW: conv_dim 64 and 128): C = 4 * LPR channels, a row on LPR = 16 or 32 lanes (one float4
@@ -239,15 +214,6 @@ __global__ __launch_bounds__(256) void blg_bwd_narrow_kernel(const float* __rest
     }
 }
 
-inline int bwd_blocks(int64_t rows) {
-    int64_t g = dyn::cdiv(rows, WPB);
-    if (g > MAX_BWD_BLOCKS) g = MAX_BWD_BLOCKS;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int dyn_bias_layernorm_gelu_fwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, float* act,
@@ -257,29 +223,23 @@ extern "C" int dyn_bias_layernorm_gelu_fwd(const float* z, const float* conv_bia
     DYN_REQUIRE(aligned16(z) && aligned16(conv_bias) && aligned16(gamma) && aligned16(beta) && aligned16(act), DYN_E_ARG,
                 "dyn_bias_layernorm_gelu_fwd: operands must be 16-byte aligned");
     if (rows == 0) return DYN_OK;
-    int64_t gq = dyn::cdiv(rows, WPB);
-    if (gq > 2048) gq = 2048;
-    dim3 grid((unsigned)gq), blk(256);
+    dim3 grid(dyn::row_blocks(rows, WPB, 2048)), blk(256);
     hipStream_t st = (hipStream_t)stream;
     if (C < 256) {               // 64 / 128 channels: several rows per wave
-        int64_t gn = dyn::cdiv(rows, WPB * (C == 64 ? 4 : 2));
-        if (gn > 2048) gn = 2048;
-        if (C == 64) hipLaunchKernelGGL(blg_fwd_narrow_kernel<16>, dim3((unsigned)gn), blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps);
-        else hipLaunchKernelGGL(blg_fwd_narrow_kernel<32>, dim3((unsigned)gn), blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps);
-        return dyn::check_launch("dyn_bias_layernorm_gelu_fwd");
-    }
-    switch (C / 256) {
-        case 1: hipLaunchKernelGGL(blg_fwd_kernel<1>, grid, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps); break;
-        case 2: hipLaunchKernelGGL(blg_fwd_kernel<2>, grid, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps); break;
-        case 3: hipLaunchKernelGGL(blg_fwd_kernel<3>, grid, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps); break;
-        case 4: hipLaunchKernelGGL(blg_fwd_kernel<4>, grid, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps); break;
-        default: dyn::set_error("dyn_bias_layernorm_gelu_fwd: unsupported C=%lld (need C in {256,512,768,1024})", (long long)C); return DYN_E_UNSUPPORTED;
+        dim3 gn(dyn::row_blocks(rows, WPB * (C == 64 ? 4 : 2), 2048));
+        if (C == 64) hipLaunchKernelGGL(blg_fwd_narrow_kernel<16>, gn, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps);
+        else hipLaunchKernelGGL(blg_fwd_narrow_kernel<32>, gn, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps);
+    } else if (!dyn::dispatch_nv<1, 2, 3, 4>(C, [&](auto nv) {
+                   hipLaunchKernelGGL(blg_fwd_kernel<decltype(nv)::value>, grid, blk, 0, st, z, conv_bias, gamma, beta, act, mean, rstd, rows, eps);
+               })) {
+        dyn::set_error("dyn_bias_layernorm_gelu_fwd: unsupported C=%lld (need C in {256,512,768,1024})", (long long)C);
+        return DYN_E_UNSUPPORTED;
     }
     return dyn::check_launch("dyn_bias_layernorm_gelu_fwd");
 }
 
 extern "C" int64_t dyn_bias_layernorm_gelu_bwd_workspace_bytes(int64_t rows, int64_t C) {
-    return (int64_t)3 * bwd_blocks(rows) * C * (int64_t)sizeof(float);
+    return (int64_t)3 * dyn::row_blocks(rows, WPB, MAX_BWD_BLOCKS) * C * (int64_t)sizeof(float);
 }
 
 extern "C" int dyn_bias_layernorm_gelu_bwd(const float* z, const float* conv_bias, const float* gamma, const float* beta,
@@ -291,7 +251,7 @@ extern "C" int dyn_bias_layernorm_gelu_bwd(const float* z, const float* conv_bia
     DYN_REQUIRE(aligned16(z) && aligned16(conv_bias) && aligned16(gamma) && aligned16(beta) && aligned16(dact) && aligned16(dz), DYN_E_ARG,
                 "dyn_bias_layernorm_gelu_bwd: operands must be 16-byte aligned");
     if (rows == 0) return DYN_OK;
-    const int nb = bwd_blocks(C < 256 ? dyn::cdiv(rows, C == 64 ? 4 : 2) : rows);     // narrow: 4 or 2 rows per wave, so fewer workgroups
+    const int nb = dyn::row_blocks(C < 256 ? dyn::cdiv(rows, C == 64 ? 4 : 2) : rows, WPB, MAX_BWD_BLOCKS);     // narrow: 4 or 2 rows per wave, so fewer workgroups
     const int64_t need = dyn_bias_layernorm_gelu_bwd_workspace_bytes(rows, C);
     DYN_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= need, DYN_E_WORKSPACE,
                 "dyn_bias_layernorm_gelu_bwd: workspace too small");
@@ -305,12 +265,11 @@ extern "C" int dyn_bias_layernorm_gelu_bwd(const float* z, const float* conv_bia
     hipStream_t st = (hipStream_t)stream;
     if (C == 64) hipLaunchKernelGGL(blg_bwd_narrow_kernel<16>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows);
     else if (C == 128) hipLaunchKernelGGL(blg_bwd_narrow_kernel<32>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows);
-    else switch (C / 256) {
-        case 1: hipLaunchKernelGGL(blg_bwd_kernel<1>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows); break;
-        case 2: hipLaunchKernelGGL(blg_bwd_kernel<2>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows); break;
-        case 3: hipLaunchKernelGGL(blg_bwd_kernel<3>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows); break;
-        case 4: hipLaunchKernelGGL(blg_bwd_kernel<4>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows); break;
-        default: dyn::set_error("dyn_bias_layernorm_gelu_bwd: unsupported C=%lld (need C in {256,512,768,1024})", (long long)C); return DYN_E_UNSUPPORTED;
+    else if (!dyn::dispatch_nv<1, 2, 3, 4>(C, [&](auto nv) {
+                 hipLaunchKernelGGL(blg_bwd_kernel<decltype(nv)::value>, grid, blk, 0, st, z, conv_bias, gamma, beta, mean, rstd, dact, dz, wg, wb, wc, rows);
+             })) {
+        dyn::set_error("dyn_bias_layernorm_gelu_bwd: unsupported C=%lld (need C in {256,512,768,1024})", (long long)C);
+        return DYN_E_UNSUPPORTED;
     }
     if (dgamma && dbeta) dyn::reduce_pair_or_defer(pg, dgamma, pb, dbeta, (int64_t)nb, C, wgrad_beta, st);
     else {

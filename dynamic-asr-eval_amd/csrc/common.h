@@ -70,6 +70,13 @@ __device__ __forceinline__ float gumbel_key(float x, float inv_t, uint64_t seed,
     return x * inv_t - logf(-logf(u));
 }
 
+// `valid` (device scalar, may be null): rows t >= *valid of a zero-padded length bucket are padding.  The live row count, clamped into [0, T].
+__device__ __forceinline__ int64_t valid_rows(const int32_t* valid, int64_t T) {
+    if (!valid) return T;
+    const int64_t v = *valid;
+    return v < 0 ? 0 : (v < T ? v : T);
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -19,6 +19,7 @@
 // No implicit multiply-add fusion in this file: where the compiler fuses depends on the surrounding code, and a row of
 // dec_gemv_rows_kernel must round exactly as the same row in dec_gemv_kernel does (dyn_decoder_steps_batch's contract).
 #pragma clang fp contract(off)
+#include "layernorm_row.h"   // after the pragma: its row statistics are compiled without fusion here as well
 
 namespace {
 
@@ -90,18 +91,9 @@ __global__ __launch_bounds__(256) void dec_gemv_kernel(const GemvArgs a) {
 #pragma unroll
         for (int j = 0; j < NV; ++j) xv[j] = reinterpret_cast<const float4*>(a.x)[lane + 64 * j];
     }
-    if (LN) {   // the arithmetic of norm_fwd_kernel<NV, false>, lane for lane
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) s += xv[j].x + xv[j].y + xv[j].z + xv[j].w;
-        const float mean = dyn::wave_sum(s) / K;
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const float a0 = xv[j].x - mean, a1 = xv[j].y - mean, a2 = xv[j].z - mean, a3 = xv[j].w - mean;
-            q += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-        }
-        const float rstd = rsqrtf(dyn::wave_sum(q) / K + a.eps);
+    if (LN) {
+        float mean, rstd;
+        dyn::row_mean_rstd(xv, a.eps, mean, rstd);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const float4 g = reinterpret_cast<const float4*>(a.gamma)[lane + 64 * j], b = reinterpret_cast<const float4*>(a.beta)[lane + 64 * j];
@@ -215,17 +207,8 @@ __global__ __launch_bounds__(256) void dec_gemv_rows_kernel(const GemvRowsArgs b
             for (int j = 0; j < NV; ++j) xv[rr][j] = reinterpret_cast<const float4*>(a.x + row * b.s_scr)[lane + 64 * j];
         }
         if (LN) {
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < NV; ++j) s += xv[rr][j].x + xv[rr][j].y + xv[rr][j].z + xv[rr][j].w;
-            const float mean = dyn::wave_sum(s) / K;
-            float q = 0.f;
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                const float a0 = xv[rr][j].x - mean, a1 = xv[rr][j].y - mean, a2 = xv[rr][j].z - mean, a3 = xv[rr][j].w - mean;
-                q += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-            }
-            const float rstd = rsqrtf(dyn::wave_sum(q) / K + a.eps);
+            float mean, rstd;
+            dyn::row_mean_rstd(xv[rr], a.eps, mean, rstd);
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
                 const float4 g = reinterpret_cast<const float4*>(a.gamma)[lane + 64 * j], bt = reinterpret_cast<const float4*>(a.beta)[lane + 64 * j];
@@ -419,35 +402,19 @@ __global__ __launch_bounds__(1024) void dec_pick_kernel(const float* __restrict_
 template <bool LN, bool SILU, bool EMBED, bool MERGE = false>
 int launch_gemv(const GemvArgs& a, int K, hipStream_t st) {
     const dim3 grid((unsigned)dyn::cdiv(a.N, 4 * a.rpw)), blk(256);
-    switch (K / 256) {
-        case 1: hipLaunchKernelGGL((dec_gemv_kernel<1, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((dec_gemv_kernel<2, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((dec_gemv_kernel<3, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a); break;
-        case 4: hipLaunchKernelGGL((dec_gemv_kernel<4, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a); break;
-        case 5: hipLaunchKernelGGL((dec_gemv_kernel<5, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a); break;
-        case 6: hipLaunchKernelGGL((dec_gemv_kernel<6, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a); break;
-        case 7: hipLaunchKernelGGL((dec_gemv_kernel<7, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a); break;
-        case 8: hipLaunchKernelGGL((dec_gemv_kernel<8, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a); break;
-        default: return DYN_E_UNSUPPORTED;
-    }
-    return DYN_OK;
+    const bool built = dyn::dispatch_nv<1, 2, 3, 4, 5, 6, 7, 8>(K, [&](auto nv) {
+        hipLaunchKernelGGL((dec_gemv_kernel<decltype(nv)::value, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, a);
+    });
+    return built ? DYN_OK : DYN_E_UNSUPPORTED;
 }
 
 template <bool LN, bool SILU, bool EMBED, bool MERGE = false>
 int launch_gemv_rows(const GemvRowsArgs& b, int K, hipStream_t st) {
     const dim3 grid((unsigned)dyn::cdiv(b.g.N, 4 * b.g.rpw), (unsigned)dyn::cdiv(b.rows, RB)), blk(256);
-    switch (K / 256) {
-        case 1: hipLaunchKernelGGL((dec_gemv_rows_kernel<1, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b); break;
-        case 2: hipLaunchKernelGGL((dec_gemv_rows_kernel<2, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b); break;
-        case 3: hipLaunchKernelGGL((dec_gemv_rows_kernel<3, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b); break;
-        case 4: hipLaunchKernelGGL((dec_gemv_rows_kernel<4, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b); break;
-        case 5: hipLaunchKernelGGL((dec_gemv_rows_kernel<5, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b); break;
-        case 6: hipLaunchKernelGGL((dec_gemv_rows_kernel<6, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b); break;
-        case 7: hipLaunchKernelGGL((dec_gemv_rows_kernel<7, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b); break;
-        case 8: hipLaunchKernelGGL((dec_gemv_rows_kernel<8, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b); break;
-        default: return DYN_E_UNSUPPORTED;
-    }
-    return DYN_OK;
+    const bool built = dyn::dispatch_nv<1, 2, 3, 4, 5, 6, 7, 8>(K, [&](auto nv) {
+        hipLaunchKernelGGL((dec_gemv_rows_kernel<decltype(nv)::value, LN, SILU, EMBED, MERGE>), grid, blk, 0, st, b);
+    });
+    return built ? DYN_OK : DYN_E_UNSUPPORTED;
 }
 
 inline int rows_per_wave(int N) { return N >= 4096 ? 4 : (N >= 512 ? 2 : 1); }

@@ -1,15 +1,18 @@
-// LayerNorm / RMSNorm forward + backward over the channel dim (rows x C, C % 256 == 0, C <= 2048).
-// One wave64 per row: 16-B loads, the row lives in registers, mean / variance / gradient dot-products are
-// wavefront reductions (no LDS, no barrier on the forward path).  Weight gradients are accumulated per
-// workgroup in registers, written as partial rows and summed in a fixed order (deterministic).
+// LayerNorm / RMSNorm forward + backward over the channel dim (rows x C, C % 256 == 0, C <= 2048): layernorm_row.h's wave-per-row
+// kernels in their plainest form, plus the lockstep-group indexing.  Weight gradients are accumulated per workgroup in registers, written
+// as partial rows and summed in a fixed order (deterministic).
 // Reference call sites: every LayerNorm / conv-module norm inside model(audio_signal=...) and its backward
 // (reference lcasr/lib.py:550,579); `default_norm: layer_norm` (earnings_finetune/lcasr160rb1.yaml:24).
 #include "common.h"
+#include "layernorm_row.h"
 #include "reduce.h"
 
 namespace {
 
-constexpr int WPB = 4;  // waves (rows in flight) per workgroup
+using dyn::ld4;
+using dyn::st4;
+constexpr int WPB = dyn::ROW_WPB;
+constexpr int MAX_BWD_BLOCKS = 256;
 
 // NV = C / 256 float4 per lane.
 template <int NV, bool RMS>
@@ -29,42 +32,23 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const float* __restrict__
     float4 g[NV], b[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-        g[j] = reinterpret_cast<const float4*>(gamma)[lane + 64 * j];
-        b[j] = (!RMS && beta) ? reinterpret_cast<const float4*>(beta)[lane + 64 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
+        g[j] = ld4(gamma, lane + 64 * j);
+        b[j] = (!RMS && beta) ? ld4(beta, lane + 64 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (int64_t row = row_lo + (int64_t)blockIdx.x * WPB + w; row < row_hi; row += (int64_t)gridDim.x * WPB) {
         float4 v[NV];
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            v[j] = reinterpret_cast<const float4*>(x + row * C)[lane + 64 * j];
+            v[j] = ld4(x + row * C, lane + 64 * j);
             s += RMS ? (v[j].x * v[j].x + v[j].y * v[j].y + v[j].z * v[j].z + v[j].w * v[j].w)
                      : (v[j].x + v[j].y + v[j].z + v[j].w);
         }
-        s = dyn::wave_sum(s);
-        float mean = 0.f, var;
-        if (RMS) {
-            var = s / C;
-        } else {
-            mean = s / C;
-            float q = 0.f;
+        float mean = 0.f, rstd;
+        if (RMS) rstd = rsqrtf(dyn::wave_sum(s) / C + eps);      // the one norm without a mean: the uncentred squares
+        else dyn::row_mean_rstd(v, s, eps, mean, rstd);
 #pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                const float a0 = v[j].x - mean, a1 = v[j].y - mean, a2 = v[j].z - mean, a3 = v[j].w - mean;
-                q += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-            }
-            var = dyn::wave_sum(q) / C;
-        }
-        const float rstd = rsqrtf(var + eps);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            float4 o;
-            o.x = (v[j].x - mean) * rstd * g[j].x + b[j].x;
-            o.y = (v[j].y - mean) * rstd * g[j].y + b[j].y;
-            o.z = (v[j].z - mean) * rstd * g[j].z + b[j].z;
-            o.w = (v[j].w - mean) * rstd * g[j].w + b[j].w;
-            reinterpret_cast<float4*>(y + row * C)[lane + 64 * j] = o;
-        }
+        for (int j = 0; j < NV; ++j) st4(y + row * C, dyn::affine4(v[j], mean, rstd, g[j], b[j]), lane + 64 * j);
         if (lane == 0) {
             if (mean_out) mean_out[row] = mean;
             rstd_out[row] = rstd;
@@ -88,9 +72,8 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const float* __restrict__
     float4 g[NV], ag[NV], ab[NV];
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-        g[j] = reinterpret_cast<const float4*>(gamma)[lane + 64 * j];
-        ag[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        ab[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        g[j] = ld4(gamma, lane + 64 * j);
+        ag[j] = ab[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (int64_t row = row_lo + (int64_t)blockIdx.x * WPB + w; row < row_hi; row += (int64_t)gridDim.x * WPB) {
         const float mean = RMS ? 0.f : mean_in[row];
@@ -99,57 +82,32 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const float* __restrict__
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            const float4 v = reinterpret_cast<const float4*>(x + row * C)[lane + 64 * j];
-            const float4 d = reinterpret_cast<const float4*>(dy + row * C)[lane + 64 * j];
-            xh[j].x = (v.x - mean) * rstd; xh[j].y = (v.y - mean) * rstd;
-            xh[j].z = (v.z - mean) * rstd; xh[j].w = (v.w - mean) * rstd;
-            ag[j].x += d.x * xh[j].x; ag[j].y += d.y * xh[j].y; ag[j].z += d.z * xh[j].z; ag[j].w += d.w * xh[j].w;
-            ab[j].x += d.x; ab[j].y += d.y; ab[j].z += d.z; ab[j].w += d.w;
-            gy[j].x = d.x * g[j].x; gy[j].y = d.y * g[j].y; gy[j].z = d.z * g[j].z; gy[j].w = d.w * g[j].w;
-            s1 += gy[j].x + gy[j].y + gy[j].z + gy[j].w;
-            s2 += gy[j].x * xh[j].x + gy[j].y * xh[j].y + gy[j].z * xh[j].z + gy[j].w * xh[j].w;
+            const float4 d = ld4(dy + row * C, lane + 64 * j);
+            xh[j] = dyn::xhat4(ld4(x + row * C, lane + 64 * j), mean, rstd);
+            dyn::addmul4(ag[j], d, xh[j]);
+            dyn::add4(ab[j], d);
+            gy[j] = dyn::mul4(d, g[j]);
+            dyn::bwd_lane_sums(gy[j], xh[j], s1, s2);
         }
-        s2 = dyn::wave_sum(s2) / C;
-        s1 = RMS ? 0.f : dyn::wave_sum(s1) / C;
+        dyn::bwd_row_means<NV, RMS>(s1, s2);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            float4 o;
-            o.x = rstd * (gy[j].x - s1 - xh[j].x * s2);
-            o.y = rstd * (gy[j].y - s1 - xh[j].y * s2);
-            o.z = rstd * (gy[j].z - s1 - xh[j].z * s2);
-            o.w = rstd * (gy[j].w - s1 - xh[j].w * s2);
-            float4* p = reinterpret_cast<float4*>(dx + row * C) + lane + 64 * j;
+            float4 o = dyn::bwd4(gy[j], xh[j], rstd, s1, s2);
             if (dx_beta != 0.f) {
-                const float4 old = reinterpret_cast<const float4*>(dx_in + row * C)[lane + 64 * j];   // dx_in == dx: in place
+                const float4 old = ld4(dx_in + row * C, lane + 64 * j);   // dx_in == dx: in place
                 o.x += dx_beta * old.x; o.y += dx_beta * old.y; o.z += dx_beta * old.z; o.w += dx_beta * old.w;
             }
-            *p = o;
+            st4(dx + row * C, o, lane + 64 * j);
         }
     }
-    // Combine the 4 waves' weight-gradient sums in wave order, then write this workgroup's partial row.
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        for (int pass = 0; pass < (RMS ? 1 : 2); ++pass) {
-            __syncthreads();
-            red[w][lane] = pass == 0 ? ag[j] : ab[j];
-            __syncthreads();
-            if (w == 0) {
-                float4 t = red[0][lane];
-#pragma unroll
-                for (int k = 1; k < WPB; ++k) { t.x += red[k][lane].x; t.y += red[k][lane].y; t.z += red[k][lane].z; t.w += red[k][lane].w; }
-                float* dst = (pass == 0 ? partial_g : partial_b) + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * C;
-                reinterpret_cast<float4*>(dst)[lane + 64 * j] = t;
-            }
-        }
-    }
+    const int64_t prow = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * C;
+    dyn::combine_waves(ag, red, partial_g + prow);
+    if (!RMS) dyn::combine_waves(ab, red, partial_b + prow);
 }
 
-inline int bwd_blocks(int64_t rows) {
-    int64_t g = dyn::cdiv(rows, WPB);
-    if (g > 256) g = 256;
-    if (g < 1) g = 1;
-    return (int)g;
-}
+// The built instances: NV = C / 256 in {1, 2, 3, 4, 5, 8}.
+template <class Go>
+bool dispatch(int64_t C, Go go) { return dyn::dispatch_nv<1, 2, 3, 4, 5, 8>(C, go); }
 
 struct Grouping { int64_t rps; int n; int64_t pstride; };   // rows per sample, groups, parameter stride (elements); n <= 1: ungrouped
 
@@ -160,17 +118,12 @@ int launch_fwd(const float* x, const float* gamma, const float* beta, float* y, 
     const int64_t rps = grouped ? gr.rps : rows;
     const int ngroups = grouped ? gr.n : 1;
     const int64_t pstride = grouped ? gr.pstride : 0;
-    int64_t gq = dyn::cdiv(rps, WPB);
-    if (gq > 2048) gq = 2048;
-    dim3 grid((unsigned)gq, grouped ? (unsigned)dyn::cdiv(rows, rps) : 1u), blk(256);
-    switch (C / 256) {
-        case 1: hipLaunchKernelGGL((norm_fwd_kernel<1, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
-        case 2: hipLaunchKernelGGL((norm_fwd_kernel<2, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
-        case 3: hipLaunchKernelGGL((norm_fwd_kernel<3, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
-        case 4: hipLaunchKernelGGL((norm_fwd_kernel<4, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
-        case 5: hipLaunchKernelGGL((norm_fwd_kernel<5, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
-        case 8: hipLaunchKernelGGL((norm_fwd_kernel<8, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride); break;
-        default: dyn::set_error("norm: unsupported C=%lld (need C in {256,512,768,1024,1280,2048})", (long long)C); return DYN_E_UNSUPPORTED;
+    dim3 grid(dyn::row_blocks(rps, WPB, 2048), grouped ? (unsigned)dyn::cdiv(rows, rps) : 1u), blk(256);
+    if (!dispatch(C, [&](auto nv) {
+            hipLaunchKernelGGL((norm_fwd_kernel<decltype(nv)::value, RMS>), grid, blk, 0, st, x, gamma, beta, y, mean, rstd, rows, eps, rps, ngroups, pstride);
+        })) {
+        dyn::set_error("norm: unsupported C=%lld (need C in {256,512,768,1024,1280,2048})", (long long)C);
+        return DYN_E_UNSUPPORTED;
     }
     return dyn::check_launch("dyn_norm_fwd");
 }
@@ -185,20 +138,17 @@ int launch_bwd(const float* x, const float* gamma, const float* mean, const floa
     const int ngroups = grouped ? gr.n : 1;
     const int64_t pstride = grouped ? gr.pstride : 0;
     const int nsamp = grouped ? (int)dyn::cdiv(rows, rps) : 1;
-    const int nbs = bwd_blocks(rps);            // workgroups (= partial rows) per sample
+    const int nbs = dyn::row_blocks(rps, WPB, MAX_BWD_BLOCKS);           // workgroups (= partial rows) per sample
     const int nb = nbs * nsamp;
     DYN_REQUIRE(ws && ws_bytes >= (int64_t)2 * nb * C * (int64_t)sizeof(float), DYN_E_WORKSPACE, "norm_bwd: workspace too small");
     float* pg = dyn::partials_alloc(ws, (int64_t)2 * nb * C * (int64_t)sizeof(float));   // the workspace, or the open deferral context's arena
     float* pb = pg + (int64_t)nb * C;
     dim3 grid(nbs, nsamp), blk(256);
-    switch (C / 256) {
-        case 1: hipLaunchKernelGGL((norm_bwd_kernel<1, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
-        case 2: hipLaunchKernelGGL((norm_bwd_kernel<2, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
-        case 3: hipLaunchKernelGGL((norm_bwd_kernel<3, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
-        case 4: hipLaunchKernelGGL((norm_bwd_kernel<4, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
-        case 5: hipLaunchKernelGGL((norm_bwd_kernel<5, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
-        case 8: hipLaunchKernelGGL((norm_bwd_kernel<8, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride); break;
-        default: dyn::set_error("norm: unsupported C=%lld", (long long)C); return DYN_E_UNSUPPORTED;
+    if (!dispatch(C, [&](auto nv) {
+            hipLaunchKernelGGL((norm_bwd_kernel<decltype(nv)::value, RMS>), grid, blk, 0, st, x, gamma, mean, rstd, dy, dx, dx_beta, pg, pb, rows, dx_in, rps, ngroups, pstride);
+        })) {
+        dyn::set_error("norm: unsupported C=%lld", (long long)C);
+        return DYN_E_UNSUPPORTED;
     }
     // one reduction per sample into its group's gradient; a group's second sample accumulates onto the first (recording order = sample order)
     for (int sidx = 0; sidx < nsamp; ++sidx) {
@@ -287,12 +237,12 @@ extern "C" int dyn_chanaffine_bwd(const float* x, const float* mean, const float
 }
 
 extern "C" int64_t dyn_norm_bwd_workspace_bytes(int64_t rows, int64_t C) {
-    return (int64_t)2 * bwd_blocks(rows) * C * (int64_t)sizeof(float);
+    return (int64_t)2 * dyn::row_blocks(rows, WPB, MAX_BWD_BLOCKS) * C * (int64_t)sizeof(float);
 }
 
 extern "C" int64_t dyn_norm_bwd_workspace_bytes_g(int64_t rows, int64_t C, int64_t rows_per_sample) {
     const int64_t rps = rows_per_sample > 0 ? rows_per_sample : rows;
-    return (int64_t)2 * bwd_blocks(rps) * dyn::cdiv(rows, rps > 0 ? rps : 1) * C * (int64_t)sizeof(float);
+    return (int64_t)2 * dyn::row_blocks(rps, WPB, MAX_BWD_BLOCKS) * dyn::cdiv(rows, rps > 0 ? rps : 1) * C * (int64_t)sizeof(float);
 }
 
 // ---- lockstep-group variants: `rows` = n_samples * rows_per_sample rows; sample s uses the parameters of group s % n_groups, stored

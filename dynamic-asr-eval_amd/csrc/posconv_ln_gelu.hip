@@ -8,27 +8,22 @@
 //             written in the [B, G, T, cg] layout the weight- and data-gradient GEMMs read; dbias = column sums of dyg.
 // Rows t >= *valid (a zero-padded length bucket; device scalar read when the kernel runs) are zeros in every output: the rows just past
 // the utterance see valid rows through the conv, so they are NOT zero on their own, and the next layer must see its zero padding there.
-// As bias_ln_gelu.hip / norm.hip: one wave64 per row, 16-B accesses (cg % 4 == 0: a float4 never straddles two segments), the row in
-// registers (NV = H / 256 float4 per lane), centred variance, row statistics by wavefront reductions; the column sum is accumulated per
-// workgroup in registers, written as one partial row and summed by the fixed-order reducer (reduce.h; deferrable): no atomics,
-// bit-reproducible.  Nothing here synchronises or allocates.
+// The row kernels are layernorm_row.h's (one wave64 per row, NV = H / 256 float4 per lane; cg % 4 == 0: a float4 never straddles two
+// segments); the column sum is accumulated per workgroup in registers, written as one partial row and summed by the fixed-order reducer.
+// Nothing here synchronises or allocates.
 #include "common.h"
 #include "gelu.h"
+#include "layernorm_row.h"
 #include "reduce.h"
 
 namespace {
 
-constexpr int WPB = 4;           // waves (rows in flight) per workgroup
+using dyn::aligned16;
+using dyn::ld4;
+using dyn::st4;
+using dyn::valid_rows;
+constexpr int WPB = dyn::ROW_WPB;
 constexpr int MAX_BWD_BLOCKS = 1024;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-__device__ __forceinline__ int64_t valid_rows(const int32_t* valid, int64_t T) {
-    if (!valid) return T;
-    const int64_t v = *valid;
-    return v < 0 ? 0 : (v < T ? v : T);
-}
 
 // Rows walked: B * (T + 2 pad) when the packed output is wanted (the pad rows are written as zeros), else B * T.
 template <int NV>
@@ -62,17 +57,11 @@ __global__ __launch_bounds__(256) void pclg_fwd_kernel(const float* __restrict__
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             v[j] = ld4(yg + ((b * G + gi[j]) * Tg + t) * cg + ci[j]);
-            v[j].x += cb[j].x; v[j].y += cb[j].y; v[j].z += cb[j].z; v[j].w += cb[j].w;
+            dyn::add4(v[j], cb[j]);
             s += v[j].x + v[j].y + v[j].z + v[j].w;
         }
-        const float mean = dyn::wave_sum(s) / H;
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const float a0 = v[j].x - mean, a1 = v[j].y - mean, a2 = v[j].z - mean, a3 = v[j].w - mean;
-            q += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-        }
-        const float rstd = rsqrtf(dyn::wave_sum(q) / H + eps);
+        float mean, rstd;
+        dyn::row_mean_rstd(v, s, eps, mean, rstd);
         const bool live = t < Tv;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -125,52 +114,24 @@ __global__ __launch_bounds__(256) void pclg_bwd_kernel(const float* __restrict__
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            const float4 v = ld4(yg + ((b * G + gi[j]) * Tg + t) * cg + ci[j]);
+            float4 v = ld4(yg + ((b * G + gi[j]) * Tg + t) * cg + ci[j]);
             const float4 d = ld4(dact + row * H + 4 * (lane + 64 * j));
-            xh[j].x = (v.x + cb[j].x - mean) * rstd; xh[j].y = (v.y + cb[j].y - mean) * rstd;
-            xh[j].z = (v.z + cb[j].z - mean) * rstd; xh[j].w = (v.w + cb[j].w - mean) * rstd;
+            dyn::add4(v, cb[j]);
+            xh[j] = dyn::xhat4(v, mean, rstd);
             dn[j].x = d.x * dyn::gelu_grad(xh[j].x); dn[j].y = d.y * dyn::gelu_grad(xh[j].y);
             dn[j].z = d.z * dyn::gelu_grad(xh[j].z); dn[j].w = d.w * dyn::gelu_grad(xh[j].w);
-            s1 += dn[j].x + dn[j].y + dn[j].z + dn[j].w;
-            s2 += dn[j].x * xh[j].x + dn[j].y * xh[j].y + dn[j].z * xh[j].z + dn[j].w * xh[j].w;
+            dyn::bwd_lane_sums(dn[j], xh[j], s1, s2);
         }
-        s1 = dyn::wave_sum(s1) / H;
-        s2 = dyn::wave_sum(s2) / H;
+        dyn::bwd_row_means<NV>(s1, s2);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            float4 o;
-            o.x = rstd * (dn[j].x - s1 - xh[j].x * s2);
-            o.y = rstd * (dn[j].y - s1 - xh[j].y * s2);
-            o.z = rstd * (dn[j].z - s1 - xh[j].z * s2);
-            o.w = rstd * (dn[j].w - s1 - xh[j].w * s2);
-            ac[j].x += o.x; ac[j].y += o.y; ac[j].z += o.z; ac[j].w += o.w;
+            const float4 o = dyn::bwd4(dn[j], xh[j], rstd, s1, s2);
+            dyn::add4(ac[j], o);
             st4(dyg + ((b * G + gi[j]) * T + t) * cg + ci[j], o);
         }
     }
-    if (!partial) return;                                            // uniform over the grid
-    // Combine the 4 waves' column sums in wave order, then write this workgroup's partial row.
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        __syncthreads();
-        red[w][lane] = ac[j];
-        __syncthreads();
-        if (w == 0) {
-            float4 t = red[0][lane];
-#pragma unroll
-            for (int k = 1; k < WPB; ++k) { t.x += red[k][lane].x; t.y += red[k][lane].y; t.z += red[k][lane].z; t.w += red[k][lane].w; }
-            st4(partial + (int64_t)blockIdx.x * H + 4 * (lane + 64 * j), t);
-        }
-    }
+    if (partial) dyn::combine_waves(ac, red, partial + (int64_t)blockIdx.x * H);     // null or not: uniform over the grid
 }
-
-inline int bwd_blocks(int64_t rows) {
-    int64_t g = dyn::cdiv(rows, WPB);
-    if (g > MAX_BWD_BLOCKS) g = MAX_BWD_BLOCKS;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // The shape rules both entries share; `who` names the entry in the message.
 inline int check_shape(const char* who, int64_t B, int64_t T, int64_t Tg, int64_t H, int64_t G) {
@@ -196,22 +157,17 @@ extern "C" int dyn_posconv_ln_gelu_fwd(const float* yg, const float* bias, float
                 "dyn_posconv_ln_gelu_fwd: operands must be 16-byte aligned");
     const int64_t rows = B * (T + (xg_next ? 2 * pad : 0));
     if (rows == 0) return DYN_OK;
-    int64_t gq = dyn::cdiv(rows, WPB);
-    if (gq > 2048) gq = 2048;
-    dim3 grid((unsigned)gq), blk(256);
+    dim3 grid(dyn::row_blocks(rows, WPB, 2048)), blk(256);
     hipStream_t st = (hipStream_t)stream;
     const int g = (int)G, cg = (int)(H / G);
-    switch (H / 256) {
-        case 1: hipLaunchKernelGGL(pclg_fwd_kernel<1>, grid, blk, 0, st, yg, bias, act, xg_next, mean, rstd, B, T, Tg, g, cg, pad, eps, valid_rows); break;
-        case 2: hipLaunchKernelGGL(pclg_fwd_kernel<2>, grid, blk, 0, st, yg, bias, act, xg_next, mean, rstd, B, T, Tg, g, cg, pad, eps, valid_rows); break;
-        case 3: hipLaunchKernelGGL(pclg_fwd_kernel<3>, grid, blk, 0, st, yg, bias, act, xg_next, mean, rstd, B, T, Tg, g, cg, pad, eps, valid_rows); break;
-        default: hipLaunchKernelGGL(pclg_fwd_kernel<4>, grid, blk, 0, st, yg, bias, act, xg_next, mean, rstd, B, T, Tg, g, cg, pad, eps, valid_rows); break;
-    }
+    dyn::dispatch_nv<1, 2, 3, 4>(H, [&](auto nv) {           // check_shape admits no other H
+        hipLaunchKernelGGL(pclg_fwd_kernel<decltype(nv)::value>, grid, blk, 0, st, yg, bias, act, xg_next, mean, rstd, B, T, Tg, g, cg, pad, eps, valid_rows);
+    });
     return dyn::check_launch("dyn_posconv_ln_gelu_fwd");
 }
 
 extern "C" int64_t dyn_posconv_ln_gelu_bwd_workspace_bytes(int64_t rows, int64_t H) {
-    return (int64_t)bwd_blocks(rows) * H * (int64_t)sizeof(float);
+    return (int64_t)dyn::row_blocks(rows, WPB, MAX_BWD_BLOCKS) * H * (int64_t)sizeof(float);
 }
 
 extern "C" int dyn_posconv_ln_gelu_bwd(const float* yg, const float* bias, const float* mean, const float* rstd, const float* dact, float* dyg,
@@ -225,7 +181,7 @@ extern "C" int dyn_posconv_ln_gelu_bwd(const float* yg, const float* bias, const
                 "dyn_posconv_ln_gelu_bwd: operands must be 16-byte aligned");
     const int64_t rows = B * T;
     if (rows == 0) return DYN_OK;
-    const int nb = bwd_blocks(rows);
+    const int nb = dyn::row_blocks(rows, WPB, MAX_BWD_BLOCKS);
     float* partial = nullptr;
     if (dbias) {
         const int64_t need = dyn_posconv_ln_gelu_bwd_workspace_bytes(rows, H);
@@ -236,12 +192,9 @@ extern "C" int dyn_posconv_ln_gelu_bwd(const float* yg, const float* bias, const
     dim3 grid(nb), blk(256);
     hipStream_t st = (hipStream_t)stream;
     const int g = (int)G, cg = (int)(H / G);
-    switch (H / 256) {
-        case 1: hipLaunchKernelGGL(pclg_bwd_kernel<1>, grid, blk, 0, st, yg, bias, mean, rstd, dact, dyg, partial, B, T, Tg, g, cg, valid_rows); break;
-        case 2: hipLaunchKernelGGL(pclg_bwd_kernel<2>, grid, blk, 0, st, yg, bias, mean, rstd, dact, dyg, partial, B, T, Tg, g, cg, valid_rows); break;
-        case 3: hipLaunchKernelGGL(pclg_bwd_kernel<3>, grid, blk, 0, st, yg, bias, mean, rstd, dact, dyg, partial, B, T, Tg, g, cg, valid_rows); break;
-        default: hipLaunchKernelGGL(pclg_bwd_kernel<4>, grid, blk, 0, st, yg, bias, mean, rstd, dact, dyg, partial, B, T, Tg, g, cg, valid_rows); break;
-    }
+    dyn::dispatch_nv<1, 2, 3, 4>(H, [&](auto nv) {           // check_shape admits no other H
+        hipLaunchKernelGGL(pclg_bwd_kernel<decltype(nv)::value>, grid, blk, 0, st, yg, bias, mean, rstd, dact, dyg, partial, B, T, Tg, g, cg, valid_rows);
+    });
     if (dbias) dyn::reduce_or_defer(partial, dbias, (int64_t)nb, H, wgrad_beta, st);
     return dyn::check_launch("dyn_posconv_ln_gelu_bwd");
 }

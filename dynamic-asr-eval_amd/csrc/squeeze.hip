@@ -14,27 +14,22 @@
 // `valid` (device int32 scalar, in SQUEEZED frames, read when the kernel runs: a zero-padded length bucket) cuts every output: rows >= valid
 // of z and dyg, rows >= s valid of dh, of the upsampled output and of du are exact zeros, and no input row at or past them is read by the
 // two backwards.
-// As posconv_ln_gelu.hip / norm.hip: one wave64 per row, 16-B accesses (cg % 4 == 0: a float4 never straddles two segments), the row in
-// registers (NV = H / 256 float4 per lane), centred variance, row statistics by wavefront reductions; the three column sums are accumulated
-// per workgroup in registers, written as partial rows and summed by the fixed-order reducer (reduce.h; deferrable): no atomics,
-// bit-reproducible.  Nothing here synchronises or allocates.
+// The row kernels are layernorm_row.h's (one wave64 per row, NV = H / 256 float4 per lane; cg % 4 == 0: a float4 never straddles two
+// segments); the three column sums are accumulated per workgroup in registers, written as partial rows and summed by the fixed-order
+// reducer.  Nothing here synchronises or allocates.
 #include "common.h"
 #include "gelu.h"
+#include "layernorm_row.h"
 #include "reduce.h"
 
 namespace {
 
-constexpr int WPB = 4;           // waves (rows in flight) per workgroup
+using dyn::aligned16;
+using dyn::ld4;
+using dyn::st4;
+using dyn::valid_rows;
+constexpr int WPB = dyn::ROW_WPB;
 constexpr int MAX_BWD_BLOCKS = 1024;
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-__device__ __forceinline__ int64_t valid_rows(const int32_t* valid, int64_t T) {
-    if (!valid) return T;
-    const int64_t v = *valid;
-    return v < 0 ? 0 : (v < T ? v : T);
-}
 
 // The pre-LayerNorm row element: the pool of the s frames + gelu(a), a = yg + bias.
 __device__ __forceinline__ float4 pooled(const float* __restrict__ h, int64_t at, int64_t H, int s) {
@@ -85,14 +80,8 @@ __global__ __launch_bounds__(256) void sq_fwd_kernel(const float* __restrict__ h
             for (int j = 0; j < NV; ++j) st4(z + row * H + 4 * (lane + 64 * j), live ? v[j] : make_float4(0.f, 0.f, 0.f, 0.f));
             continue;
         }
-        const float mean = dyn::wave_sum(sum) / H;
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const float a0 = v[j].x - mean, a1 = v[j].y - mean, a2 = v[j].z - mean, a3 = v[j].w - mean;
-            q += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-        }
-        const float rstd = rsqrtf(dyn::wave_sum(q) / H + eps);
+        float mean, rstd;
+        dyn::row_mean_rstd(v, sum, eps, mean, rstd);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -183,16 +172,13 @@ __global__ __launch_bounds__(256) void sq_bwd_kernel(const float* __restrict__ h
             ag[j].x += d.x * xh[j].x; ag[j].y += d.y * xh[j].y; ag[j].z += d.z * xh[j].z; ag[j].w += d.w * xh[j].w;
             ab[j].x += d.x; ab[j].y += d.y; ab[j].z += d.z; ab[j].w += d.w;
             dn[j].x = d.x * gm.x; dn[j].y = d.y * gm.y; dn[j].z = d.z * gm.z; dn[j].w = d.w * gm.w;
-            s1 += dn[j].x + dn[j].y + dn[j].z + dn[j].w;
-            s2 += dn[j].x * xh[j].x + dn[j].y * xh[j].y + dn[j].z * xh[j].z + dn[j].w * xh[j].w;
+            dyn::bwd_lane_sums(dn[j], xh[j], s1, s2);
         }
-        s1 = dyn::wave_sum(s1) / H;
-        s2 = dyn::wave_sum(s2) / H;
+        dyn::bwd_row_means<NV>(s1, s2);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
-            float4 ds, o, dp;
-            ds.x = rstd * (dn[j].x - s1 - xh[j].x * s2); ds.y = rstd * (dn[j].y - s1 - xh[j].y * s2);
-            ds.z = rstd * (dn[j].z - s1 - xh[j].z * s2); ds.w = rstd * (dn[j].w - s1 - xh[j].w * s2);
+            const float4 ds = dyn::bwd4(dn[j], xh[j], rstd, s1, s2);
+            float4 o, dp;
             o.x = ds.x * dyn::gelu_grad(a[j].x); o.y = ds.y * dyn::gelu_grad(a[j].y);
             o.z = ds.z * dyn::gelu_grad(a[j].z); o.w = ds.w * dyn::gelu_grad(a[j].w);
             ac[j].x += o.x; ac[j].y += o.y; ac[j].z += o.z; ac[j].w += o.w;
@@ -201,23 +187,9 @@ __global__ __launch_bounds__(256) void sq_bwd_kernel(const float* __restrict__ h
             for (int k = 0; k < s; ++k) st4(dh + (b * T + s * t + k) * H + 4 * (lane + 64 * j), dp);
         }
     }
-    // Combine the 4 waves' column sums in wave order, then write this workgroup's partial rows.
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        for (int pass = 0; pass < 3; ++pass) {
-            float* partial = pass == 0 ? partial_g : pass == 1 ? partial_b : partial_c;
-            if (!partial) continue;                                  // uniform over the grid
-            __syncthreads();
-            red[w][lane] = pass == 0 ? ag[j] : pass == 1 ? ab[j] : ac[j];
-            __syncthreads();
-            if (w == 0) {
-                float4 t = red[0][lane];
-#pragma unroll
-                for (int k = 1; k < WPB; ++k) { t.x += red[k][lane].x; t.y += red[k][lane].y; t.z += red[k][lane].z; t.w += red[k][lane].w; }
-                st4(partial + (int64_t)blockIdx.x * H + 4 * (lane + 64 * j), t);
-            }
-        }
-    }
+    if (partial_g) dyn::combine_waves(ag, red, partial_g + (int64_t)blockIdx.x * H);     // null or not: uniform over the grid
+    if (partial_b) dyn::combine_waves(ab, red, partial_b + (int64_t)blockIdx.x * H);
+    if (partial_c) dyn::combine_waves(ac, red, partial_c + (int64_t)blockIdx.x * H);
 }
 
 // One float4 per thread and step: n4 = B * T * H / 4 elements of the output; a row t of it is live when t < s * valid.
@@ -251,14 +223,9 @@ __global__ __launch_bounds__(256) void unsq_bwd_kernel(const float* __restrict__
     }
 }
 
-inline int bwd_blocks(int64_t rows) {
-    int64_t g = dyn::cdiv(rows, WPB);
-    if (g > MAX_BWD_BLOCKS) g = MAX_BWD_BLOCKS;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// The built instances: NV = H / 256 in {1, 2, 3, 4}; check_shape admits no other H.
+template <class Go>
+void dispatch(int64_t H, Go go) { dyn::dispatch_nv<1, 2, 3, 4>(H, go); }
 
 inline int check_factor(const char* who, int64_t s) {
     DYN_REQUIRE(s >= 1 && s <= 4, DYN_E_ARG, "%s: squeeze factor s=%lld must be 1, 2, 3 or 4", who, (long long)s);
@@ -294,22 +261,17 @@ extern "C" int dyn_squeeze_ln_fwd(const float* h, const float* yg, const float* 
                 "dyn_squeeze_ln_fwd: operands must be 16-byte aligned");
     const int64_t T2 = T / s, rows = B * T2;
     if (rows == 0) return DYN_OK;
-    int64_t gq = dyn::cdiv(rows, WPB);
-    if (gq > 2048) gq = 2048;
-    dim3 grid((unsigned)gq), blk(256);
+    dim3 grid(dyn::row_blocks(rows, WPB, 2048)), blk(256);
     hipStream_t st = (hipStream_t)stream;
     const int g = (int)G, cg = (int)(H / G), f = (int)s;
-    switch (H / 256) {
-        case 1: hipLaunchKernelGGL(sq_fwd_kernel<1>, grid, blk, 0, st, h, yg, bias, gamma, beta, z, mean, rstd, B, T, T2, Tg, g, cg, f, eps, valid_rows); break;
-        case 2: hipLaunchKernelGGL(sq_fwd_kernel<2>, grid, blk, 0, st, h, yg, bias, gamma, beta, z, mean, rstd, B, T, T2, Tg, g, cg, f, eps, valid_rows); break;
-        case 3: hipLaunchKernelGGL(sq_fwd_kernel<3>, grid, blk, 0, st, h, yg, bias, gamma, beta, z, mean, rstd, B, T, T2, Tg, g, cg, f, eps, valid_rows); break;
-        default: hipLaunchKernelGGL(sq_fwd_kernel<4>, grid, blk, 0, st, h, yg, bias, gamma, beta, z, mean, rstd, B, T, T2, Tg, g, cg, f, eps, valid_rows); break;
-    }
+    dispatch(H, [&](auto nv) {
+        hipLaunchKernelGGL(sq_fwd_kernel<decltype(nv)::value>, grid, blk, 0, st, h, yg, bias, gamma, beta, z, mean, rstd, B, T, T2, Tg, g, cg, f, eps, valid_rows);
+    });
     return dyn::check_launch("dyn_squeeze_ln_fwd");
 }
 
 extern "C" int64_t dyn_squeeze_ln_bwd_workspace_bytes(int64_t rows, int64_t H) {
-    return (int64_t)3 * bwd_blocks(rows) * H * (int64_t)sizeof(float);
+    return (int64_t)3 * dyn::row_blocks(rows, WPB, MAX_BWD_BLOCKS) * H * (int64_t)sizeof(float);
 }
 
 extern "C" int dyn_squeeze_ln_bwd(const float* h, const float* yg, const float* bias, const float* gamma, const float* mean, const float* rstd,
@@ -324,7 +286,7 @@ extern "C" int dyn_squeeze_ln_bwd(const float* h, const float* yg, const float* 
                 DYN_E_ARG, "dyn_squeeze_ln_bwd: operands must be 16-byte aligned");
     const int64_t T2 = T / s, rows = B * (T2 + 1);
     if (B * T == 0) return DYN_OK;
-    const int nb = bwd_blocks(rows);
+    const int nb = dyn::row_blocks(rows, WPB, MAX_BWD_BLOCKS);
     float *pg = nullptr, *pb = nullptr, *pc = nullptr;
     if (dgamma || dbeta || dbias) {
         const int64_t need = dyn_squeeze_ln_bwd_workspace_bytes(rows, H);
@@ -337,12 +299,9 @@ extern "C" int dyn_squeeze_ln_bwd(const float* h, const float* yg, const float* 
     dim3 grid(nb), blk(256);
     hipStream_t st = (hipStream_t)stream;
     const int g = (int)G, cg = (int)(H / G), f = (int)s;
-    switch (H / 256) {
-        case 1: hipLaunchKernelGGL(sq_bwd_kernel<1>, grid, blk, 0, st, h, yg, bias, gamma, mean, rstd, dz, dh, dyg, pg, pb, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
-        case 2: hipLaunchKernelGGL(sq_bwd_kernel<2>, grid, blk, 0, st, h, yg, bias, gamma, mean, rstd, dz, dh, dyg, pg, pb, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
-        case 3: hipLaunchKernelGGL(sq_bwd_kernel<3>, grid, blk, 0, st, h, yg, bias, gamma, mean, rstd, dz, dh, dyg, pg, pb, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
-        default: hipLaunchKernelGGL(sq_bwd_kernel<4>, grid, blk, 0, st, h, yg, bias, gamma, mean, rstd, dz, dh, dyg, pg, pb, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
-    }
+    dispatch(H, [&](auto nv) {
+        hipLaunchKernelGGL(sq_bwd_kernel<decltype(nv)::value>, grid, blk, 0, st, h, yg, bias, gamma, mean, rstd, dz, dh, dyg, pg, pb, pc, B, T, T2, Tg, g, cg, f, valid_rows);
+    });
     if (dgamma && dbeta) dyn::reduce_pair_or_defer(pg, dgamma, pb, dbeta, (int64_t)nb, H, wgrad_beta, st);
     else {
         if (dgamma) dyn::reduce_or_defer(pg, dgamma, (int64_t)nb, H, wgrad_beta, st);
@@ -391,24 +350,19 @@ extern "C" int dyn_squeeze_fwd(const float* h, const float* yg, const float* bia
     DYN_REQUIRE(aligned16(h) && aligned16(yg) && aligned16(bias) && aligned16(z), DYN_E_ARG, "dyn_squeeze_fwd: operands must be 16-byte aligned");
     const int64_t T2 = T / s, rows = B * T2;
     if (rows == 0) return DYN_OK;
-    int64_t gq = dyn::cdiv(rows, WPB);
-    if (gq > 2048) gq = 2048;
-    dim3 grid((unsigned)gq), blk(256);
+    dim3 grid(dyn::row_blocks(rows, WPB, 2048)), blk(256);
     hipStream_t st = (hipStream_t)stream;
     const int g = (int)G, cg = (int)(H / G), f = (int)s;
     const float* none = nullptr;
     float* nout = nullptr;
-    switch (H / 256) {
-        case 1: hipLaunchKernelGGL((sq_fwd_kernel<1, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows); break;
-        case 2: hipLaunchKernelGGL((sq_fwd_kernel<2, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows); break;
-        case 3: hipLaunchKernelGGL((sq_fwd_kernel<3, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows); break;
-        default: hipLaunchKernelGGL((sq_fwd_kernel<4, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows); break;
-    }
+    dispatch(H, [&](auto nv) {
+        hipLaunchKernelGGL((sq_fwd_kernel<decltype(nv)::value, false>), grid, blk, 0, st, h, yg, bias, none, none, z, nout, nout, B, T, T2, Tg, g, cg, f, 0.f, valid_rows);
+    });
     return dyn::check_launch("dyn_squeeze_fwd");
 }
 
 extern "C" int64_t dyn_squeeze_bwd_workspace_bytes(int64_t rows, int64_t H) {
-    return (int64_t)bwd_blocks(rows) * H * (int64_t)sizeof(float);
+    return (int64_t)dyn::row_blocks(rows, WPB, MAX_BWD_BLOCKS) * H * (int64_t)sizeof(float);
 }
 
 extern "C" int dyn_squeeze_bwd(const float* yg, const float* bias, const float* dz, float* dh, float* dyg, float* dbias, float wgrad_beta,
@@ -421,7 +375,7 @@ extern "C" int dyn_squeeze_bwd(const float* yg, const float* bias, const float* 
                 "dyn_squeeze_bwd: operands must be 16-byte aligned");
     const int64_t T2 = T / s, rows = B * (T2 + 1);
     if (B * T == 0) return DYN_OK;
-    const int nb = bwd_blocks(rows);
+    const int nb = dyn::row_blocks(rows, WPB, MAX_BWD_BLOCKS);
     float* pc = nullptr;
     if (dbias) {
         const int64_t need = dyn_squeeze_bwd_workspace_bytes(rows, H);
@@ -433,12 +387,9 @@ extern "C" int dyn_squeeze_bwd(const float* yg, const float* bias, const float* 
     const int g = (int)G, cg = (int)(H / G), f = (int)s;
     const float* none = nullptr;
     float* nout = nullptr;
-    switch (H / 256) {
-        case 1: hipLaunchKernelGGL((sq_bwd_kernel<1, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
-        case 2: hipLaunchKernelGGL((sq_bwd_kernel<2, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
-        case 3: hipLaunchKernelGGL((sq_bwd_kernel<3, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
-        default: hipLaunchKernelGGL((sq_bwd_kernel<4, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows); break;
-    }
+    dispatch(H, [&](auto nv) {
+        hipLaunchKernelGGL((sq_bwd_kernel<decltype(nv)::value, false>), grid, blk, 0, st, none, yg, bias, none, none, none, dz, dh, dyg, nout, nout, pc, B, T, T2, Tg, g, cg, f, valid_rows);
+    });
     if (dbias) dyn::reduce_or_defer(pc, dbias, (int64_t)nb, H, wgrad_beta, st);
     return dyn::check_launch("dyn_squeeze_bwd");
 }

@@ -25,6 +25,7 @@ inline unsigned grid_for(int64_t n) {
 
 using dyn::gelu_f;
 using dyn::gelu_grad;
+using dyn::valid_rows;
 
 __global__ __launch_bounds__(TPB) void gelu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) y[i] = gelu_f(x[i]);
@@ -40,12 +41,6 @@ __global__ __launch_bounds__(TPB) void gelu_bwd_kernel(const float* __restrict__
 // a few units for a stationary column, more only where a chunk's first row is itself an outlier of that chunk.
 // stage 1: partial[(b, chunk), 0:C] = sum_t (x - k), partial[(b, chunk), C:2C] = sum_t (x - k)^2 over the chunk's rows, k = x[b, r0, c]
 // `valid` (device scalar, may be null): only the first *valid rows of every batch entry count (a zero-padded bucket, see dyn_colnorm_fwd_len)
-__device__ __forceinline__ int64_t valid_rows(const int32_t* valid, int64_t T) {
-    if (!valid) return T;
-    const int64_t v = *valid;
-    return v < 0 ? 0 : (v < T ? v : T);
-}
-
 __global__ __launch_bounds__(TPB) void colstats_partial_kernel(const float* __restrict__ x, float* __restrict__ partial, int64_t T,
                                                                int C, int64_t rows_per_chunk, int chunks, const int32_t* __restrict__ valid) {
     const int c = blockIdx.x * TPB + threadIdx.x;

@@ -19,8 +19,9 @@ import kernel_refs as K  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 EPS = 1e-5
-SHAPES = [(1, 256, 16), (37, 256, 16), (130, 1024, 16), (67, 1280, 16), (5, 256, 4), (33, 512, 64)]       # (M, H, A)
-IDS = ["one-row", "partial-row-tile", "H1024-many-tiles", "mms-1b-width", "A4", "A64"]
+SHAPES = [(1, 256, 16), (37, 256, 16), (130, 1024, 16), (67, 1280, 16), (5, 256, 4), (33, 512, 64),       # (M, H, A)
+          (37, 768, 16), (37, 1536, 16), (37, 1792, 16), (37, 2048, 16)]                                      # the other built widths
+IDS = ["one-row", "partial-row-tile", "H1024-many-tiles", "mms-1b-width", "A4", "A64", "H768", "H1536", "H1792", "H2048"]
 PARAMS = ("gamma", "beta", "W1", "b1", "W2", "b2")
 _CACHE = {}
 

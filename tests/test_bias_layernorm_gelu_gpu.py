@@ -66,8 +66,8 @@ def _run_bwd(ops, cuda, z, cb, g, b, mean, rstd, dact, old, wbeta, skip=None):
     return dz, outs
 
 
-@pytest.mark.parametrize("C", [256, 512])
-@pytest.mark.parametrize("rows", [1, 7, 1031])        # one row; fewer rows than two workgroups' waves; several workgroups plus a tail
+# rows: one row; fewer rows than two workgroups' waves; several workgroups plus a tail.  The two widest instances at the row count that idles a wave.
+@pytest.mark.parametrize("rows,C", [(r, c) for c in (256, 512) for r in (1, 7, 1031)] + [(7, 768), (7, 1024)], ids=lambda v: str(v))
 def test_forward_and_backward_against_float64(cuda, rows, C):
     from dynamic_asr_eval_amd import ops
     z, cb, g, b, dact, old = _inputs(rows, C, 0)

@@ -305,8 +305,8 @@ def test_chanaffine(cuda, rows, C):
 
 
 # ----------------------------------------------------------------------------------------------------------- row norms
-@pytest.mark.parametrize("C", [512, 2048])
-@pytest.mark.parametrize("rows", [1, 3, 1029])             # fewer rows than waves; more than 256 blocks x 4 rows
+# rows: fewer than waves; more than 256 blocks x 4 rows.  C = 1280: the instance between the two, at the row count that idles a wave.
+@pytest.mark.parametrize("rows,C", [(r, c) for c in (512, 2048) for r in (1, 3, 1029)] + [(3, 1280)], ids=lambda v: str(v))
 def test_layernorm_rmsnorm_row_edges(cuda, rows, C):
     """The tolerances of test_ops_gpu.py::test_layernorm_rmsnorm on its input distribution, at the widths and row counts it does not run;
     plus the residual variant of layernorm_bwd (dx = grad + dx_in, dx_in untouched)."""

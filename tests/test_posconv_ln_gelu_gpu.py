@@ -18,8 +18,8 @@ import kernel_refs as K  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 EPS = 1e-5
-SHAPES = [(2, 7, 256, 16), (1, 33, 768, 16), (2, 18, 1024, 16), (1, 5, 256, 4)]       # (B, T, H, G)
-IDS = ["T7-below-pad-cg16", "H768-cg48", "H1024-NV4", "G4-cg64"]
+SHAPES = [(2, 7, 256, 16), (1, 33, 768, 16), (2, 18, 1024, 16), (1, 5, 256, 4), (1, 7, 512, 16)]       # (B, T, H, G)
+IDS = ["T7-below-pad-cg16", "H768-cg48", "H1024-NV4", "G4-cg64", "H512-NV2"]
 PAD, EXTRA = 9, 3             # the 19-tap layer's padding; yg rows per group beyond T (Tg > T)
 
 
