@@ -69,6 +69,78 @@ class LogMel:
         return out
 
 
+FBANK_STACK = 2                                                              # SeamlessM4TFeatureExtractor.stride: frames stacked per row
+FBANK_SCALE, FBANK_PREEMPHASIS, FBANK_MIN_HZ = 2.0 ** 15, 0.97, 20.0
+
+
+def kaldi_fbank_frames(n_samples):
+    """Filter-bank frames of n_samples samples (`center=False`: 1 + (L - 400) // 160) and the rows the extractor keeps of them (an odd last
+    frame is dropped by its reshape to two frames per row)."""
+    F = 1 + (int(n_samples) - WIN) // HOP if n_samples >= WIN else 0
+    return F, F // FBANK_STACK
+
+
+def kaldi_fbank_matrices():
+    """(basis [400, 2 * 260], mel [260, 80]) in float64: what SeamlessM4TFeatureExtractor._extract_fbank_features does to one 400-sample
+    frame before its power spectrum, folded into one matrix, and its Kaldi-scale mel filters.
+    transformers' audio_utils.spectrogram, per frame, in float64: x * 2^15 (the extractor, before the call), `buffer -= buffer.mean()`
+    (remove_dc_offset), `buffer[1:] -= 0.97 * buffer[:-1]; buffer[0] *= 1 - 0.97` (preemphasis), `buffer *= window` (povey, symmetric),
+    rfft of the frame zero-padded to 512.  All five are linear in the frame: with A = diag(w) Pre Centre 2^15 the spectrum of frame x is
+    x^T (A^T [cos | -sin]), so the whole chain is the strided-row GEMM LogMel runs with another basis.  The filters are
+    audio_utils.mel_filter_bank's own values (20 Hz .. 8 kHz, Kaldi mel scale, triangles in mel space): computed, not downloaded."""
+    from transformers.audio_utils import mel_filter_bank, window_function
+    n = torch.arange(WIN, dtype=torch.float64)
+    w = torch.from_numpy(window_function(WIN, "povey", periodic=False)).to(torch.float64)
+    centre = torch.eye(WIN, dtype=torch.float64) - 1.0 / WIN
+    pre = torch.eye(WIN, dtype=torch.float64)
+    pre[0, 0] = 1.0 - FBANK_PREEMPHASIS
+    pre[n[1:].long(), n[:-1].long()] = -FBANK_PREEMPHASIS
+    A = w[:, None] * (pre @ centre) * FBANK_SCALE                            # y = A x: the windowed frame
+    k = torch.arange(N_FFT // 2 + 1, dtype=torch.float64)
+    ang = 2 * math.pi * k[None, :] * n[:, None] / N_FFT
+    basis = torch.zeros(WIN, 2 * KP, dtype=torch.float64)
+    basis[:, :N_FFT // 2 + 1] = A.T @ torch.cos(ang)
+    basis[:, KP:KP + N_FFT // 2 + 1] = -(A.T @ torch.sin(ang))
+    fb = torch.zeros(KP, N_MELS, dtype=torch.float64)
+    fb[:N_FFT // 2 + 1] = torch.from_numpy(mel_filter_bank(num_frequency_bins=N_FFT // 2 + 1, num_mel_filters=N_MELS, min_frequency=FBANK_MIN_HZ,
+                                                           max_frequency=SAMPLE_RATE // 2, sampling_rate=SAMPLE_RATE, norm=None, mel_scale="kaldi",
+                                                           triangularize_in_mel_space=True)).to(torch.float64)
+    return basis, fb
+
+
+class KaldiFbank:
+    """Waveforms [B, L] on the device -> Wav2Vec2-BERT's `input_features` [B, F // 2, 160], F = 1 + (L - 400) // 160: the device form of
+    SeamlessM4TFeatureExtractor (which runs in numpy, one Python iteration per frame).  Four launches for the whole batch: the framing +
+    DFT GEMM over overlapping rows (lda = 160, no frame matrix), dyn_stft_power, the mel GEMM, dyn_fbank_finish (floor, log, per-bin
+    normalisation over the valid frames, two frames per row).  `valid` (device int32 scalar): the utterance's own frame count inside a
+    zero-padded length bucket; its rows equal the unpadded call's (a frame never reads past its own 400 samples) and the rows past them
+    are zeros.  The features do not depend on the waveform's gain except through the mel floor (log of a scaled energy moves every frame
+    of a bin by the same constant, which the per-bin mean removes)."""
+
+    def __init__(self, device="cuda:0"):
+        self.device = torch.device(device)
+        basis, fb = kaldi_fbank_matrices()
+        self.basis = basis.float().to(self.device).contiguous()                # [400, 520]
+        self.fb = fb.float().to(self.device).contiguous()                      # [260, 80]
+
+    def __call__(self, x, valid=None):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
+            raise ops.DynError("KaldiFbank: expected a contiguous float32 CUDA tensor [B, L]")
+        B, L = x.shape
+        F, T = kaldi_fbank_frames(L)
+        if T < 1:
+            raise ops.DynError(f"KaldiFbank: {L} samples give {F} filter-bank frame(s); two are needed ({WIN + HOP} samples): the unbiased "
+                               "per-bin variance of one frame is undefined")
+        st = torch.cuda.current_stream().cuda_stream
+        reim = torch.empty(B, F, 2 * KP, device=self.device, dtype=torch.float32)
+        ops.gemm(x, self.basis, reim, M=F, N=2 * KP, K=WIN, lda=HOP, ldb=2 * KP, ldc=2 * KP, nb1=B, sa=(L, 0), sc=(F * 2 * KP, 0))
+        power = torch.empty(B * F, KP, device=self.device, dtype=torch.float32)
+        check(load().dyn_stft_power(reim.data_ptr(), power.data_ptr(), B * F, KP, st), "dyn_stft_power")
+        mel = torch.empty(B, F, N_MELS, device=self.device, dtype=torch.float32)
+        ops.gemm(power, self.fb, mel, M=B * F, N=N_MELS, K=KP, lda=KP, ldb=N_MELS, ldc=N_MELS)
+        return ops.fbank_finish(mel, valid)
+
+
 def processing_chain(waveform, device="cuda:0"):
     """Same role as upstream `lcasr.utils.audio_tools.processing_chain`: waveform -> normalised log-mel [1, 80, T]."""
     return LogMel(device)(waveform)

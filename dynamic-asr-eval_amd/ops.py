@@ -1729,3 +1729,128 @@ def attn_adapter_bwd(x, gamma, beta, w1, w2, mean, rstd, a, dy, dgamma, dbeta, d
                                     _opt(db1, "db1"), _opt(dw2, "dw2"), _opt(db2, "db2"), M, H, A, ws.data_ptr(), ws.numel(), _stream()),
           "dyn_attn_adapter_bwd")
     return dx
+
+
+# ----------------------------------------------------------------------------------------------- Wav2Vec2-BERT
+CAUSAL_ACTS = {"swish": 0, "silu": 0, "gelu": 1}
+
+
+def convmod_causal(u, w, gamma, beta, act="swish", eps=1e-5, save=False, time_tile=0):
+    """Wav2Vec2-BERT's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = act(LayerNorm_C(causal depthwise conv(GLU(u)))), w [C, 31],
+    zeros left of frame 0.  Returns (s, g, c, n, mean, rstd): with `save` the GLU output, the convolution output, the LayerNorm output and the
+    row statistics the backward needs, else five Nones.  `time_tile`: 0 (the library's choice), 8 or 16 frames per workgroup."""
+    _cc(u, "convmod_causal.u"); _cc(w, "convmod_causal.w"); _cc(gamma, "convmod_causal.gamma"); _cc(beta, "convmod_causal.beta")
+    if act not in CAUSAL_ACTS:
+        raise DynError(f"convmod_causal: act={act!r} is not built ({sorted(CAUSAL_ACTS)})")
+    if u.dim() != 3 or u.shape[2] % 2 or w.dim() != 2 or w.shape[0] != u.shape[2] // 2 or gamma.numel() != w.shape[0] or beta.numel() != w.shape[0]:
+        raise DynError("convmod_causal: u must be [B, T, 2C], w [C, KW], gamma and beta [C]")
+    B, T, C2 = u.shape
+    C = C2 // 2
+    s = torch.empty(B, T, C, device=u.device, dtype=F32)
+    g = c = n = mean = rstd = None
+    if save:
+        g, c, n = (torch.empty(B, T, C, device=u.device, dtype=F32) for _ in range(3))
+        mean, rstd = (torch.empty(B * T, device=u.device, dtype=F32) for _ in range(2))
+    check(_L().dyn_convmod_causal_fwd(u.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), s.data_ptr(), _opt(g, "g"), _opt(c, "c"),
+                                      _opt(n, "n"), _opt(mean, "mean"), _opt(rstd, "rstd"), B, T, C, w.shape[1], CAUSAL_ACTS[act], eps,
+                                      int(time_tile), _stream()), "dyn_convmod_causal_fwd")
+    return s, g, c, n, mean, rstd
+
+
+def dwconv1d_causal_dgrad(dy, w, out=None, beta=0.0):
+    """dx [B, T, C] = beta * dx + the input gradient of the left-padded depthwise convolution (w [C, KW]) from dy [B, T, C]."""
+    _cc(dy, "dwconv1d_causal_dgrad.dy"); _cc(w, "dwconv1d_causal_dgrad.w")
+    B, T, C = dy.shape
+    if w.shape[0] != C:
+        raise DynError("dwconv1d_causal_dgrad: w must be [C, KW]")
+    out = torch.empty_like(dy) if out is None else _cc(out, "dwconv1d_causal_dgrad.out")
+    if out.shape != dy.shape or out.data_ptr() == dy.data_ptr():
+        raise DynError("dwconv1d_causal_dgrad: out must have the shape of dy and not alias it")
+    check(_L().dyn_dwconv1d_causal_dgrad(dy.data_ptr(), w.data_ptr(), out.data_ptr(), B, T, C, w.shape[1], beta, _stream()),
+          "dyn_dwconv1d_causal_dgrad")
+    return out
+
+
+def dwconv1d_causal_wgrad(x, dy, dw, beta=1.0):
+    """dw [C, KW] = beta * dw + the weight gradient of the left-padded depthwise convolution of x [B, T, C] from dy [B, T, C]."""
+    _cc(x, "dwconv1d_causal_wgrad.x"); _cc(dy, "dwconv1d_causal_wgrad.dy"); _cc(dw, "dwconv1d_causal_wgrad.dw")
+    B, T, C = x.shape
+    if dy.shape != x.shape or dw.dim() != 2 or dw.shape[0] != C:
+        raise DynError("dwconv1d_causal_wgrad: dy must have the shape of x, dw must be [C, KW]")
+    ws = workspace(x.device)
+    check(_L().dyn_dwconv1d_causal_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), beta, B, T, C, dw.shape[1], ws.data_ptr(), ws.numel(),
+                                         _stream()), "dyn_dwconv1d_causal_wgrad")
+    return dw
+
+
+def narrow_layernorm(x, gamma, beta, eps=1e-5, out=None):
+    """LayerNorm over the last axis of x [..., C] for a narrow row (C % 4 == 0, C <= 256; ops.layernorm needs C % 256 == 0): (y, mean, rstd)."""
+    _cc(x, "narrow_layernorm.x"); _cc(gamma, "narrow_layernorm.gamma")
+    C = x.shape[-1]
+    if gamma.numel() != C or (beta is not None and beta.numel() != C):
+        raise DynError("narrow_layernorm: gamma / beta must have C elements")
+    rows = x.numel() // C
+    out = torch.empty_like(x) if out is None else _cc(out, "narrow_layernorm.out")
+    mean = torch.empty(rows, device=x.device, dtype=F32)
+    rstd = torch.empty(rows, device=x.device, dtype=F32)
+    check(_L().dyn_narrow_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), _opt(beta, "beta"), out.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                        rows, C, eps, _stream()), "dyn_narrow_layernorm_fwd")
+    return out, mean, rstd
+
+
+def narrow_layernorm_bwd(x, gamma, mean, rstd, dy, dgamma, dbeta, dx=None, wgrad_beta=1.0):
+    """Backward of narrow_layernorm: dgamma / dbeta = wgrad_beta * old + their sums over the rows (None: not computed), dx written when given
+    (None: the input is data).  Returns dx."""
+    _cc(x, "narrow_layernorm_bwd.x"); _cc(gamma, "narrow_layernorm_bwd.gamma"); _cc(dy, "narrow_layernorm_bwd.dy")
+    _c(mean, "narrow_layernorm_bwd.mean"); _c(rstd, "narrow_layernorm_bwd.rstd")
+    C = x.shape[-1]
+    rows = x.numel() // C
+    if dy.shape != x.shape or mean.numel() != rows or rstd.numel() != rows or gamma.numel() != C:
+        raise DynError("narrow_layernorm_bwd: dy / mean / rstd / gamma do not match x")
+    for t, n in ((dgamma, "dgamma"), (dbeta, "dbeta")):
+        if t is not None and _cc(t, "narrow_layernorm_bwd." + n).numel() != C:
+            raise DynError(f"narrow_layernorm_bwd: {n} must have C elements")
+    if dx is not None and _cc(dx, "narrow_layernorm_bwd.dx").shape != x.shape:
+        raise DynError("narrow_layernorm_bwd: dx must have the shape of x")
+    ws = workspace(x.device)
+    check(_L().dyn_narrow_layernorm_bwd(x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dy.data_ptr(), _opt(dx, "dx"),
+                                        _opt(dgamma, "dgamma"), _opt(dbeta, "dbeta"), wgrad_beta, rows, C, ws.data_ptr(), ws.numel(), _stream()),
+          "dyn_narrow_layernorm_bwd")
+    return dx
+
+
+FBANK_MEL_FLOOR = 1.192092955078125e-07     # SeamlessM4TFeatureExtractor: float32 epsilon, as Kaldi
+
+
+def fbank_finish(mel, valid=None, mel_floor=FBANK_MEL_FLOOR, eps=1e-7):
+    """mel [B, F, M] filter-bank energies -> [B, F // 2, 2M], per sample: log(max(mel, floor)), per-bin (mean, unbiased variance) normalisation
+    over the first `valid` frames (device int32 scalar; None: all), two frames stacked per row; rows past valid // 2 are zeros."""
+    _c(mel, "fbank_finish.mel")
+    if mel.dim() != 3 or mel.shape[1] < 2:
+        raise DynError("fbank_finish: mel must be [B, F, M] with at least two frames (the unbiased variance of one frame is undefined)")
+    B, F, M = mel.shape
+    out = torch.empty(B, F // 2, 2 * M, device=mel.device, dtype=F32)
+    check(_L().dyn_fbank_finish(mel.data_ptr(), out.data_ptr(), B, F, M, mel_floor, eps, _valid_ptr(valid, "fbank_finish"), _stream()),
+          "dyn_fbank_finish")
+    return out
+
+
+def relkey_embed_grad(dc2p, q, dE, scale, beta=1.0):
+    """The gradient of Wav2Vec2-BERT's shared distance embedding E [P, D] (`self_attn.distance_embedding.weight`, one table for all heads):
+        dE[p, :] = beta * dE[p, :] + scale * sum_{b, h, i} dC2P[b, h, i, P - 1 - p] * q[b, h, i, :]
+    dc2p [B, nh, T, ldp] is ops.disentangled_bwd's first output over the REVERSED table (column r belongs to E[P - 1 - r]), q an _attn.View
+    of the queries.  Four launches whatever B * nh is: one strided batched GEMM leaves every (b, h)'s [P, D] product as a partial row, the
+    fixed-order reducer sums them (bit-reproducible: two calls give equal bits), the rows are reversed by a copy and accumulated into dE."""
+    _cc(dc2p, "relkey_embed_grad.dc2p"); _cc(dE, "relkey_embed_grad.dE")
+    if dc2p.dim() != 4 or dE.dim() != 2:
+        raise DynError("relkey_embed_grad: dc2p must be [B, nh, T, ldp], dE [P, D]")
+    B, nh, T, ldp = dc2p.shape
+    P, D = dE.shape
+    if P > ldp or D != q.sh:
+        raise DynError(f"relkey_embed_grad: dE [{P}, {D}] does not fit dc2p's {ldp} columns / the head dimension {q.sh}")
+    part = torch.empty(B * nh, P, D, device=dE.device, dtype=F32)
+    gemm(dc2p, q.t, part, trans_a=True, M=P, N=D, K=T, lda=ldp, ldb=q.ld, ldc=D, nb1=B, nb2=nh, sa=(nh * T * ldp, T * ldp), sb=(q.sb, q.sh),
+         sc=(nh * P * D, P * D), b_off=q.off, alpha=scale)
+    rev = torch.empty(P, D, device=dE.device, dtype=F32)
+    reduce_partials(part, rev, beta=0.0)
+    return axpby(rev.flip(0), dE, 1.0, beta)

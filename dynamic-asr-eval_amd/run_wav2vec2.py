@@ -10,7 +10,7 @@ Like both reference drivers it processes the FIRST recording only (they `break` 
 `AutoModelForCTC.from_pretrained("facebook/wav2vec2-base-960h")` and the corpora cannot be fetched offline, so the harness builds
 the base architecture (HF `Wav2Vec2Config()` defaults: 7 conv layers of 512 channels, positional conv k=128 g=16, 12 x 768, vocab 32)
 or the one a `config.json` names (`--config`, or `-c DIR` = a local HF model directory; the layer-norm / stable-LN layout of
-large-960h-lv60-self included, and by `model_type` WavLM, Wav2Vec2-Conformer, Data2Vec-Audio, HuBERT, SEW and SEW-D: load_pretrained_model) with
+large-960h-lv60-self included, and by `model_type` WavLM, Wav2Vec2-Conformer, Data2Vec-Audio, HuBERT, SEW, SEW-D and Wav2Vec2-BERT: load_pretrained_model) with
 seeded weights, or loads a local HF state_dict (`-c file.pt` / `DIR/pytorch_model.bin`, torch.load(weights_only=True)), and evaluates a synthetic
 TEDLIUM-shape talk (`--seconds`, utterances of 2-15 s).  An MMS directory (`adapter_attn_dim` in its config.json) runs with its
 per-layer adapters; `--target-lang LANG` loads `DIR/adapter.LANG.safetensors` (or `.bin`) over the base weights and `DIR/vocab.json` as the tokenizer,
@@ -25,7 +25,7 @@ import torch
 from . import wav2vec2_lib as lib
 from .datasets import fetch_utterances_from_lines, synthetic_text, synthetic_waveform
 from .decoding import GreedyCTCDecoder
-from . import data2vec_audio_model, hubert_model, sew_d_model, sew_model, wav2vec2_conformer_model, wavlm_model
+from . import data2vec_audio_model, hubert_model, sew_d_model, sew_model, wav2vec2_bert_model, wav2vec2_conformer_model, wavlm_model
 from .wav2vec2_model import Wav2Vec2ForCTC, config_from_json, make_config, param_spec
 from .wer import basic_normalize as normalize, word_error_rate_detail
 
@@ -170,7 +170,8 @@ def load_pretrained_model(args, device):
     base-960h architecture or at `--config PATH.json`; without a checkpoint: seeded weights at that architecture.  A config.json whose
     `model_type` is "wavlm" builds WavLMForCTC (wavlm_model.py), "wav2vec2-conformer" Wav2Vec2ConformerForCTC (wav2vec2_conformer_model.py),
     "data2vec-audio" Data2VecAudioForCTC (data2vec_audio_model.py), "hubert" HubertForCTC (hubert_model.py), "sew" SEWForCTC
-    (sew_model.py), "sew-d" SEWDForCTC (sew_d_model.py), under `-c DIR` and under `--config` alike; anything else Wav2Vec2ForCTC."""
+    (sew_model.py), "sew-d" SEWDForCTC (sew_d_model.py), "wav2vec2-bert" Wav2Vec2BertForCTC (wav2vec2_bert_model.py: it reads the waveform
+    through the filter-bank front end on the device), under `-c DIR` and under `--config` alike; anything else Wav2Vec2ForCTC."""
     cfg_path, ckpt = getattr(args, 'config', '') or '', args.checkpoint
     if ckpt and os.path.isdir(ckpt):
         cfg_path, ckpt = cfg_path or os.path.join(ckpt, 'config.json'), os.path.join(ckpt, 'pytorch_model.bin')
@@ -196,6 +197,8 @@ def load_pretrained_model(args, device):
         model = sew_model.SEWForCTC(sew_model.config_from_json(cfg_path), device=device)
     elif kind == 'sew-d':
         model = sew_d_model.SEWDForCTC(sew_d_model.config_from_json(cfg_path), device=device)
+    elif kind == 'wav2vec2-bert':
+        model = wav2vec2_bert_model.Wav2Vec2BertForCTC(wav2vec2_bert_model.config_from_json(cfg_path), device=device)
     elif lang:
         model = Wav2Vec2ForCTC(cfg, device=device)
     else:

@@ -97,18 +97,24 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
 
     def __init__(self, config=None, device="cuda:0"):
         super().__init__(config, device)
-        c, pf = self.cfg, self._prefix
+        c = self.cfg
         assert self.packed_qkv                                 # H % 256 == 0: the q | k | v slots are one [3H, H] matrix
         self.relative = c["position_embeddings_type"] == "relative"
+        self._layer_eps = LAYER_EPS                            # the per-layer LayerNorms' eps; a model of the family may carry config.layer_norm_eps here
         self._act, self._act_bwd = ACTS[c["hidden_act"]]
+        self.buffers_ = self._make_buffers()                   # BatchNorm1d's buffers: not parameters, not in the flat vector
+        self._tables = {}                                      # frame count -> pe [2T - 1, H] (relative) | (cos, sin) [T, D / 2] (rotary)
+
+    def _make_buffers(self):
+        """{name: tensor} of the conv modules' batch-norm buffers; a model of the family whose conv module has none returns {}."""
+        c, pf, out = self.cfg, self._prefix, {}
         H = c["hidden_size"]
-        self.buffers_ = {}                                     # BatchNorm1d's buffers: not parameters, not in the flat vector
         for l in range(c["num_hidden_layers"]):
             p = f"{pf}encoder.layers.{l}.conv_module.batch_norm."
-            self.buffers_[p + "running_mean"] = torch.zeros(H, device=self.device, dtype=torch.float32)
-            self.buffers_[p + "running_var"] = torch.ones(H, device=self.device, dtype=torch.float32)
-            self.buffers_[p + "num_batches_tracked"] = torch.zeros((), device=self.device, dtype=torch.int64)
-        self._tables = {}                                      # frame count -> pe [2T - 1, H] (relative) | (cos, sin) [T, D / 2] (rotary)
+            out[p + "running_mean"] = torch.zeros(H, device=self.device, dtype=torch.float32)
+            out[p + "running_var"] = torch.ones(H, device=self.device, dtype=torch.float32)
+            out[p + "num_batches_tracked"] = torch.zeros((), device=self.device, dtype=torch.int64)
+        return out
 
     # ------------------------------------------------------------------ state dict
     def _to_hf(self, name, t):
@@ -180,7 +186,7 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
     def _ffn_fwd(self, x, p, which, save):
         """x + 0.5 ffn(LN(x)); returns (result, saved)."""
         P = self.P
-        n, m, s = ops.layernorm(x, P[f"{p}{which}_layer_norm.weight"], P[f"{p}{which}_layer_norm.bias"], LAYER_EPS)
+        n, m, s = ops.layernorm(x, P[f"{p}{which}_layer_norm.weight"], P[f"{p}{which}_layer_norm.bias"], self._layer_eps)
         u = ops.linear(n, P[f"{p}{which}.intermediate_dense.weight"], P[f"{p}{which}.intermediate_dense.bias"])
         a = self._act(u)
         f = ops.linear(a, P[f"{p}{which}.output_dense.weight"], P[f"{p}{which}.output_dense.bias"])
@@ -210,7 +216,7 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         D = H // nh
         scale = D ** -0.5
         p = f"{pf}encoder.layers.{l}."
-        n, m, s = ops.layernorm(x, P[p + "self_attn_layer_norm.weight"], P[p + "self_attn_layer_norm.bias"], LAYER_EPS)
+        n, m, s = ops.layernorm(x, P[p + "self_attn_layer_norm.weight"], P[p + "self_attn_layer_norm.bias"], self._layer_eps)
         Wqkv, bqkv = self.Pqkv[l]
         qkv = torch.empty(B, T, 3 * H, device=x.device, dtype=torch.float32)
         S = torch.empty(B, nh, T, T, device=x.device, dtype=torch.float32)
@@ -242,7 +248,7 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         ops.linear(O, P[p + "self_attn.linear_out.weight"], P[p + "self_attn.linear_out.bias"], out=r, beta=1.0)
         return r, (x, m, s, n, qkv, S, O) + extra
 
-    def _attn_bwd(self, dr, kept, pos, l, nb, T, tab):
+    def _attn_bwd(self, dr, kept, pos, l, nb, T, tab, vT=None):
         c, P, G, pf = self.cfg, self.P, self.G, self._prefix
         H, nh = c["hidden_size"], c["num_attention_heads"]
         D = H // nh
@@ -301,7 +307,7 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         """x + conv_module(x)."""
         P = self.P
         p = f"{self._prefix}encoder.layers.{l}.conv_module."
-        n, m, s = ops.layernorm(x, P[p + "layer_norm.weight"], P[p + "layer_norm.bias"], LAYER_EPS)
+        n, m, s = ops.layernorm(x, P[p + "layer_norm.weight"], P[p + "layer_norm.bias"], self._layer_eps)
         g = ops.linear(n, P[p + "pointwise_conv1.weight"])
         gl = ops.glu(g)
         if vT is not None:
@@ -333,14 +339,13 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         ops.layernorm_bwd(x, P[p + "layer_norm.weight"], m, s, dn, dx, G[p + "layer_norm.weight"], G[p + "layer_norm.bias"], dx_beta=1.0, dx_in=dr)
         return dx
 
-    def _encode(self, h, ctx, vT, dims, v0):
+    def _layers_fwd(self, x, ctx, vT, tab):
+        """The conformer layers on x [B, T, H]; fills ctx["layers"] when a context is kept.  Shared with a model of the family whose encoder
+        ends differently (wav2vec2_bert_model.py)."""
         c, P, pf = self.cfg, self.P, self._prefix
         save = ctx is not None
-        T = dims[2]
-        tab = self.position_table(T)
         if save:
             ctx["layers"] = []
-        x = h
         for l in range(c["num_hidden_layers"]):
             p = f"{pf}encoder.layers.{l}."
             r1, k1 = self._ffn_fwd(x, p, "ffn1", save)
@@ -348,9 +353,16 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
             pos = k2[9] if self.relative else None              # [2T - 1, H]: not batch-indexed, kept apart from what an n_active backward cuts
             r3, k3 = self._conv_fwd(r2, l, vT, save)
             r4, k4 = self._ffn_fwd(r3, p, "ffn2", save)
-            x, m, s = ops.layernorm(r4, P[p + "final_layer_norm.weight"], P[p + "final_layer_norm.bias"], LAYER_EPS)
+            x, m, s = ops.layernorm(r4, P[p + "final_layer_norm.weight"], P[p + "final_layer_norm.bias"], self._layer_eps)
             if save:
                 ctx["layers"].append(((k1, k2[:9], k3, k4, (r4, m, s)), pos))
+        return x
+
+    def _encode(self, h, ctx, vT, dims, v0):
+        c, P, pf = self.cfg, self.P, self._prefix
+        save = ctx is not None
+        T = dims[2]
+        x = self._layers_fwd(h, ctx, vT, self.position_table(T))
         hN, mean, rstd = ops.layernorm(x, P[pf + "encoder.layer_norm.weight"], P[pf + "encoder.layer_norm.bias"], c["layer_norm_eps"])
         logits = ops.linear(hN, P["lm_head.weight"], P["lm_head.bias"])
         if save:
@@ -362,16 +374,9 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         return SimpleNamespace(logits=logits, frames=T)
 
     # ------------------------------------------------------------------ backward
-    def _backward_encoder(self, ctx, grad_logits, nb, cut):
-        v0, vT = ctx["valid"]
+    def _layers_bwd(self, ctx, dx, nb, T, tab, vT, cut):
+        """Backward of _layers_fwd from dx [nb, T, H], the gradient of its output: returns the gradient of its input."""
         c, P, G, pf = self.cfg, self.P, self.G, self._prefix
-        T = ctx["dims"][2]
-        tab = self.position_table(T)
-        dh = self._lin_bwd(grad_logits.contiguous(), cut(ctx["head"]), "lm_head.weight", "lm_head.bias")
-        x, mean, rstd = cut(ctx["final"])
-        dx = torch.empty_like(dh)
-        ops.layernorm_bwd(x, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dx, G[pf + "encoder.layer_norm.weight"],
-                          G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
         for l in reversed(range(c["num_hidden_layers"])):
             p = f"{pf}encoder.layers.{l}."
             kept, pos = ctx["layers"][l]
@@ -381,7 +386,18 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
                               G[p + "final_layer_norm.bias"], dx_beta=0.0)
             dr3 = self._ffn_bwd(dr4, k4, p, "ffn2")
             dr2 = self._conv_bwd(dr3, k3, l, vT)
-            dr1 = self._attn_bwd(dr2, k2, pos, l, nb, T, tab)
+            dr1 = self._attn_bwd(dr2, k2, pos, l, nb, T, tab, vT)
             dx = self._ffn_bwd(dr1, k1, p, "ffn1")
             ctx["layers"][l] = None
         return dx
+
+    def _backward_encoder(self, ctx, grad_logits, nb, cut):
+        v0, vT = ctx["valid"]
+        P, G, pf = self.P, self.G, self._prefix
+        T = ctx["dims"][2]
+        dh = self._lin_bwd(grad_logits.contiguous(), cut(ctx["head"]), "lm_head.weight", "lm_head.bias")
+        x, mean, rstd = cut(ctx["final"])
+        dx = torch.empty_like(dh)
+        ops.layernorm_bwd(x, P[pf + "encoder.layer_norm.weight"], mean, rstd, dh, dx, G[pf + "encoder.layer_norm.weight"],
+                          G[pf + "encoder.layer_norm.bias"], dx_beta=0.0)
+        return self._layers_bwd(ctx, dx, nb, T, self.position_table(T), vT, cut)

@@ -191,16 +191,17 @@ class Wav2Vec2ForCTC(FlatModel):
     _make_config = staticmethod(make_config)
     _param_spec = staticmethod(param_spec)
     _norm_weight_suffixes = ("adapter_layer.norm.weight",)       # run_wav2vec2.init_synthetic starts these around 1 too
+    _conv_extractor = True       # False: a model without the waveform conv stack (wav2vec2_bert_model.py); cfg's conv_kernel / conv_stride are then frame arithmetic only
 
     def __init__(self, config=None, device="cuda:0"):
         self.cfg = self._make_config(config)
         c, pf = self.cfg, self._prefix
         H = c["hidden_size"]
-        assert H % 256 == 0 and c["conv_dim"][-1] % 256 == 0, "LayerNorm kernels need C % 256 == 0"
+        assert H % 256 == 0 and (not self._conv_extractor or c["conv_dim"][-1] % 256 == 0), "LayerNorm kernels need C % 256 == 0"
         self.layer_extractor = c["feat_extract_norm"] == "layer"
         self.stable_ln = c["do_stable_layer_norm"]
         self.adapter_dim = adapter_dim(c)
-        if self.layer_extractor and any(d % 256 and d not in (64, 128) for d in c["conv_dim"]):
+        if self._conv_extractor and self.layer_extractor and any(d % 256 and d not in (64, 128) for d in c["conv_dim"]):
             raise ops.DynError(f"feat_extract_norm=\"layer\" needs every conv_dim to be 64, 128 or a multiple of 256 (got {c['conv_dim']})")
         spec = self._param_spec(c, pf)
         super().__init__([(n, shape) for n, shape, _ in spec], device)

@@ -836,6 +836,50 @@ int dyn_beam_search(const float* log_probs, int64_t frames, int64_t ld, int32_t 
                     int32_t width, float alpha, float beta, float blank_penalty, float repetition_penalty, float top_am_threshold,
                     float prune_less_than, int32_t use_prune, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Wav2Vec2-BERT (`model_type: "wav2vec2-bert"`, transformers Wav2Vec2BertForCTC; what `AutoModelForCTC.from_pretrained` builds for a
+ * w2v-BERT 2.0 fine-tune).  fp32, deterministic, no float atomics.
+ *   dyn_convmod_causal_fwd     Wav2Vec2BertConvolutionModule.forward between its two pointwise convolutions: `self.glu`, `F.pad(x,
+ *                              (kernel_size - 1, 0))`, `self.depthwise_conv`, `self.depthwise_layer_norm`, `self.activation` in one
+ *                              launch.  u [B, T, 2C] -> s [B, T, C] = act(LN_C(sum_j w[c, j] * GLU(u)[t - (KW - 1) + j, c])), zeros left
+ *                              of frame 0; w [C, KW]; act 0 = SiLU, 1 = erf GELU.  Optional outputs (null: not written) for the
+ *                              backward: g the GLU output, c the convolution output, n the LayerNorm output [B, T, C], mean / rstd
+ *                              [B * T] (centred two-pass variance).  time_tile: 0 = dyn_convmod_causal_time_tile(B, T), or 8 / 16 frames
+ *                              per workgroup (tests, tuning).  KW = 31, C in {256, 512, 768, 1024}: anything else DYN_E_UNSUPPORTED.
+ *   dyn_dwconv1d_causal_dgrad  the autograd of that padded depthwise convolution w.r.t. its input:
+ *                              dx[b,t,c] = dx_beta * dx[b,t,c] + sum_j w[c,j] * dy[b, t + (KW - 1) - j, c] (rows >= T are zeros).
+ *   dyn_dwconv1d_causal_wgrad  ... w.r.t. its weight: dw[c,j] = beta * dw[c,j] + sum_{b,t} dy[b,t,c] * x[b, t - (KW - 1) + j, c], partial
+ *                              sums per time tile in `workspace`, combined in tile order (bit-reproducible, deferrable).
+ *   dyn_narrow_layernorm_fwd   Wav2Vec2BertFeatureProjection.forward `self.layer_norm(hidden_states)` over C = 160 stacked filter-bank
+ *                              channels: LayerNorm of rows x C for C % 4 == 0, C <= 256 (one wave per row; the other LayerNorm
+ *                              entries need C % 256 == 0).  y, mean [rows], rstd [rows]; beta may be null.
+ *   dyn_narrow_layernorm_bwd   its autograd: dgamma / dbeta = wgrad_beta * old + column sums (partial rows per workgroup in `workspace`,
+ *                              added in workgroup order; either may be null), dx [rows, C] optional (null: the input is data).
+ *   dyn_fbank_finish           the tail of SeamlessM4TFeatureExtractor.__call__ after the mel projection (`np.maximum(mel_floor, ..)`,
+ *                              log, `(x - x.mean(0)) / sqrt(x.var(0, ddof=1) + 1e-7)`, the reshape to [frames // 2, 2 * bins]):
+ *                              mel [B, F, M] -> out [B, F / 2, 2M], per sample.  valid_frames (device int32 scalar, may be null = F; read when the kernel
+ *                              runs): the statistics cover the first `valid` frames, rows >= valid / 2 of out are written as zeros.
+ * Null pointers, sizes out of range -> DYN_E_ARG, a C / KW that is not built -> DYN_E_UNSUPPORTED, a short workspace -> DYN_E_WORKSPACE, all
+ * before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t dyn_convmod_causal_time_tile(int64_t B, int64_t T);
+int dyn_convmod_causal_fwd(const float* u, const float* w, const float* gamma, const float* beta, float* s, float* g, float* c, float* n,
+                           float* mean, float* rstd, int64_t B, int64_t T, int64_t C, int64_t KW, int32_t act, float eps, int64_t time_tile,
+                           void* stream);
+int dyn_dwconv1d_causal_dgrad(const float* dy, const float* w, float* dx, int64_t B, int64_t T, int64_t C, int64_t KW, float dx_beta,
+                              void* stream);
+int64_t dyn_dwconv1d_causal_wgrad_workspace_bytes(int64_t B, int64_t T, int64_t C, int64_t KW);
+int dyn_dwconv1d_causal_wgrad(const float* x, const float* dy, float* dw, float beta, int64_t B, int64_t T, int64_t C, int64_t KW,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int dyn_narrow_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int64_t rows,
+                             int64_t C, float eps, void* stream);
+int64_t dyn_narrow_layernorm_bwd_workspace_bytes(int64_t rows, int64_t C);
+int dyn_narrow_layernorm_bwd(const float* x, const float* gamma, const float* mean, const float* rstd, const float* dy, float* dx,
+                             float* dgamma, float* dbeta, float wgrad_beta, int64_t rows, int64_t C, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int dyn_fbank_finish(const float* mel, float* out, int64_t B, int64_t F, int64_t M, float mel_floor, float eps, const int32_t* valid_frames,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
