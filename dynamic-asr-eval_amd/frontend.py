@@ -5,7 +5,8 @@ un-vendored `lcasr.utils.audio_tools.processing_chain`, e.g. lcasr/earnings22/ru
 Constants DEFINED here (the upstream implementation is absent; parity unpinned, the oracle oracle/logmel_ref.py restates
 the same definition with torch.stft): n_fft 512, Hann(400, periodic) centred in the frame, hop 160, center=True with
 reflect padding, power spectrum, 80 HTK-mel triangular filters over 0-8000 Hz (torchaudio `melscale_fbanks` rule,
-norm=None), log(mel + 1e-6), then per-bin (mean, unbiased std) normalisation over the recording.
+norm=None), log(mel + 1e-6), then per-bin (mean, unbiased std) normalisation over the recording (the std from a second, centred pass:
+a bin at the floor log(1e-6) with a spread of 1e-3 keeps its std; a bin of zero variance comes out as zeros).
 The STFT is one fp32-MFMA GEMM over overlapping rows of the padded signal (lda = hop); see csrc/logmel.hip."""
 import math
 

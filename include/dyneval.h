@@ -282,7 +282,9 @@ int dyn_specaug_mask_args(float* x, int64_t F, int64_t T, const int32_t* start_h
  * reflect-padded signal with lda = hop < K (overlapping rows) and a window-folded DFT basis; these are the passes
  * around it:  reflect pad -> [GEMM: re|im] -> power -> [GEMM: mel] -> log + per-bin (mean, std) -> normalise + transpose.
  *   dyn_stft_power     reim [T, 2*KP] (re | im) -> power [T, KP]
- *   dyn_logmel_finish  mel [T, F] (overwritten by log(mel + eps)) -> out [F, T], optionally per-bin normalised over T */
+ *   dyn_logmel_finish  mel [T, F] (overwritten by log(mel + eps)) -> out [F, T], optionally per-bin normalised over T: the mean, then the
+ *                      centred sum of squares in a second pass (never E[x^2] - mean^2), fixed summation order; a bin of zero variance,
+ *                      and T == 1, give zeros.  F <= 256; workspace 8-byte aligned, dyn_logmel_finish_workspace_bytes(T, F) bytes. */
 int dyn_reflect_pad(const float* x, float* out, int64_t n, int64_t pad, void* stream);
 int dyn_stft_power(const float* reim, float* power, int64_t T, int64_t KP, void* stream);
 int64_t dyn_logmel_finish_workspace_bytes(int64_t T, int64_t F);

@@ -2,8 +2,9 @@
 operation's definition (no call into the torch op it mirrors).  tests/test_kernel_refs_cpu.py checks every one of them against torch's own
 op and autograd in float64 to 1e-12, so a wrong reference cannot hide a wrong kernel; tests/test_kernel_parity_f64_gpu.py compares the HIP
 kernels with them (the row softmax family: tests/test_row_kernels_gpu.py, on the device; the conformer's own convolutions, dtype- and
-device-agnostic: tests/test_conv_kernels_gpu.py).  Also here: the inputs both files share, the tolerance rule, and a CPU replay of the
-summation order the column norm used before its statistics were made stable (E[x^2] - mean^2 from fp32 running sums)."""
+device-agnostic: tests/test_conv_kernels_gpu.py; the log-mel front end and the window augmentations: tests/test_frontend_kernels_gpu.py).
+Also here: the inputs both files share, the tolerance rule, and CPU replays of the summation orders the column norm and the log-mel
+normalisation used before their statistics were made stable (E[x^2] - mean^2 from fp32 running sums)."""
 import math
 
 import numpy as np
@@ -664,3 +665,180 @@ def convmod_group_ref(u, w, bias, gamma, beta, layernorm, eps):
     per = [convmod_ref(u[b:b + 1], w[b % R], None if bias is None else bias[b % R], gamma[b % R], None if beta is None else beta[b % R],
                        layernorm, eps) for b in range(u.shape[0])]
     return tuple(None if per[0][i] is None else torch.cat([p[i] for p in per]) for i in range(6))
+
+
+# ----------------------------------------------------------------------------------------------------------- log-mel front end, window augmentations
+# csrc/logmel.hip and csrc/augment.hip from the definitions (tests/test_frontend_kernels_gpu.py), and a CPU replay of the summation order
+# dyn_logmel_finish had before its per-bin statistics were centred.
+LOGMEL_EPS = 1e-6
+LOGMEL_NORM_T = (2, 101, 801, 6001, 60001)
+LOGMEL_CLASSES = ((-13.8, 1e-3), (-13.8, 1e-2), (-10.0, 0.05), (-9.0, 0.3), (-5.0, 2.0), (4.0, 1.0))      # (mu, sd) of log(mel + eps)
+LOGMEL_ZERO_COLUMN = 79                          # this column of logmel_class_inputs is all zeros (an empty band)
+
+
+def reflect_pad_ref(x, pad):
+    """out[i] = x[|i - pad|] folded back at n - 1: torch.stft's center=True, pad_mode='reflect' (needs pad < n)."""
+    n = x.numel()
+    j = (torch.arange(n + 2 * pad) - pad).abs()
+    return x[torch.where(j >= n, 2 * (n - 1) - j, j)]
+
+
+def stft_power_ref(reim, KP):
+    """reim [T, 2 KP] (re | im) -> re^2 + im^2 [T, KP]."""
+    r = d(reim)
+    return r[:, :KP] ** 2 + r[:, KP:2 * KP] ** 2
+
+
+def centred_stats(x):
+    """Mean and centred sum of squares over the last axis, two passes.  The mean is taken about the first element (x0 + mean(x - x0)),
+    so a constant row has mean x0 and a centred sum of squares of 0, exactly."""
+    x0 = x[..., :1]
+    mean = x0 + (x - x0).sum(-1, keepdim=True) / x.shape[-1]
+    return mean, ((x - mean) ** 2).sum(-1, keepdim=True)
+
+
+def logmel_finish_ref(mel32, eps, normalize):
+    """mel [T, F] fp32 -> log(double(mel) + double(float32(eps))) as [F, T]; `normalize`: per bin (x - mean) / unbiased std over T.  A bin
+    whose centred variance is exactly 0, and T == 1, give zeros (dyn_logmel_finish's deliberate behaviour; the formula gives nan)."""
+    x = torch.log(d(mel32) + float(np.float32(eps))).t().contiguous()
+    if not normalize:
+        return x
+    T = x.shape[1]
+    mean, m2 = centred_stats(x)
+    var = m2 / max(T - 1, 1)
+    return torch.where(var > 0, (x - mean) / torch.sqrt(torch.where(var > 0, var, torch.ones_like(var))), torch.zeros_like(x))
+
+
+def rownorm_ref(x):
+    """x [R, T]: (x - mean) / unbiased std per row, two passes."""
+    x = d(x)
+    mean, m2 = centred_stats(x)
+    return (x - mean) / torch.sqrt(m2 / (x.shape[-1] - 1))
+
+
+def moments_ref(x):
+    """(sum, mean, unbiased std) of every element, as Python floats; the std of one element is 0."""
+    x = d(x).reshape(-1)
+    n = x.numel()
+    mean, m2 = centred_stats(x)
+    return x.sum().item(), mean.item(), math.sqrt(m2.item() / (n - 1)) if n > 1 else 0.0
+
+
+def cutout_winner(shape, rects):
+    """[F, T] int64: the index of the LAST rectangle (y0, y1, x0, x1) covering each cell, -1 where none does."""
+    F_, T = shape
+    f, t = torch.arange(F_)[:, None], torch.arange(T)[None, :]
+    win = torch.full((F_, T), -1, dtype=torch.long)
+    for k, (y0, y1, x0, x1) in enumerate(rects):
+        win = torch.where((f >= y0) & (f < y1) & (t >= x0) & (t < x1), torch.full_like(win, k), win)
+    return win
+
+
+def cutout_ref(x, rects, mode, value=0.0):
+    """x [F, T]; mode 0: zero, 1: every rectangle's own mean (all means taken from x before any fill), 2: `value`; later rectangles
+    overwrite earlier ones.  Returns (out float64, winner [F, T], means [n_rects] float64 — 0 for an empty rectangle)."""
+    x = d(x)
+    win = cutout_winner(tuple(x.shape), rects)
+    means = torch.zeros(len(rects), dtype=F64)
+    for k, (y0, y1, x0, x1) in enumerate(rects):
+        if y1 > y0 and x1 > x0:
+            means[k] = x[y0:y1, x0:x1].sum() / ((y1 - y0) * (x1 - x0))
+    fill = means if mode == 1 else torch.full((len(rects),), float(value) if mode == 2 else 0.0, dtype=F64)
+    out = x.clone()
+    if len(rects):
+        out = torch.where(win >= 0, fill[win.clamp(min=0)], x)
+    return out, win, means
+
+
+def gather_frames_ref(x, index, along_time):
+    """y[f, t] = x[f, index[t]] (along_time) or x[index[f], t]."""
+    return x[:, index.long()] if along_time else x[index.long()]
+
+
+def logmel_class_inputs(T, F_=80, seed=0):
+    """mel [T, F] fp32 whose column f has log(mel + eps) ~ mu + sd * randn with (mu, sd) = LOGMEL_CLASSES[f % 6]: mel = exp(mu + sd z) - eps,
+    clamped at 0.  Column LOGMEL_ZERO_COLUMN is all zeros.  The two (-13.8, .) classes sit at log(1e-6): a bin whose band is empty."""
+    z = torch.randn(T, F_, generator=gen(7000 + seed + T), dtype=F64)
+    mu = torch.tensor([LOGMEL_CLASSES[f % len(LOGMEL_CLASSES)][0] for f in range(F_)], dtype=F64)
+    sd = torch.tensor([LOGMEL_CLASSES[f % len(LOGMEL_CLASSES)][1] for f in range(F_)], dtype=F64)
+    mel = (torch.exp(mu + sd * z) - LOGMEL_EPS).clamp(min=0.0)
+    mel[:, LOGMEL_ZERO_COLUMN] = 0.0
+    return mel.float().contiguous()
+
+
+def logmel_torch_fp32(mel32, eps, normalize):
+    """torch's fp32 CPU chain of the same op: log, then mean and std (torch's own two-pass) per bin.  [F, T] fp32."""
+    x = torch.log(mel32 + torch.tensor(eps, dtype=torch.float32)).t().contiguous()
+    return (x - x.mean(-1, keepdim=True)) / x.std(-1, keepdim=True) if normalize else x
+
+
+def logmel_log_unit_err(out, ref64, std64):
+    """max |out - ref| * std_f: the error of a normalised [F, T] output in log-mel units (tests/test_frontend_gpu.py's metric)."""
+    return ((d(out) - ref64).abs() * std64).max().item()
+
+
+def unit_stats_err(out, cols):
+    """(max |mean|, max |std - 1|) over the rows `cols` of a normalised [F, T] output, mean and unbiased std taken in float64."""
+    o = d(out)[cols]
+    return o.mean(-1).abs().max().item(), (o.std(-1) - 1).abs().max().item()
+
+
+def normalise_fp32(x32):
+    """torch's fp32 CPU (x - mean) / std over the last axis (torch's own two-pass mean and unbiased std); a constant row, where torch gives
+    nan, is set to 0 (the kernels' zeros there are pinned separately)."""
+    x32 = x32.detach().cpu().float()
+    t32 = (x32 - x32.mean(-1, keepdim=True)) / x32.std(-1, keepdim=True)
+    return torch.where(torch.isfinite(t32), t32, torch.zeros_like(t32))
+
+
+def logmel_norm_bounds(mel32, eps=LOGMEL_EPS):
+    """The bounds dyn_logmel_finish's normalised output of mel [T, F] is held to: torch's fp32 chain (fp32 log, mean, std) measured against
+    logmel_finish_ref.  Returns a dict: `ref` [F, T] float64, `std` [F, 1] float64 (per-bin unbiased std of the float64 log-mel), `live`
+    (the bins of non-zero variance) and the (bound, torch's error) pairs `out` (|out - ref| * std: log-mel units, floor 2e-6), `mean` and
+    `unit_std` (per-bin mean 0 and std 1 of the output, floors 1e-5)."""
+    lm = logmel_finish_ref(mel32, eps, False)
+    std = torch.sqrt(centred_stats(lm)[1] / max(lm.shape[1] - 1, 1))
+    ref = logmel_finish_ref(mel32, eps, True)
+    live = [f for f in range(lm.shape[0]) if std[f, 0] > 0]
+    t32 = normalise_fp32(logmel_torch_fp32(mel32, eps, False))
+    e_m, e_s = unit_stats_err(t32, live)
+    return dict(ref=ref, std=std, live=live, out=measured_tol(t32 * std, ref * std, 2e-6), mean=(4.0 * e_m + 1e-5, e_m),
+                unit_std=(4.0 * e_s + 1e-5, e_s))
+
+
+def logmel_uncentred_replay(logvals32):
+    """The per-bin statistics dyn_logmel_finish formed BEFORE they were centred, replayed on the CPU from the fp32 log values [T, F]:
+    per 256-row block 256 // F row lanes (3 for F = 80; lane l takes rows l, l + lanes, ...) of fp32 running (sum, sum of squares), the lanes
+    added in order; the block partials added by 16 lanes of stride 16 in fp32, the lanes added in order; then mean = s / T and
+    var = (q - s * mean) / (T - 1) in double.  (The device contracts q += v * v into an fma, numpy does not: half an ulp per step, far below
+    the cancellation this shows.)  Returns (mean [F], var [F]) float64; the kernel replaced var <= 0 by 1."""
+    x = logvals32.detach().cpu().numpy().astype(np.float32)
+    T, F_ = x.shape
+    lanes = 256 // F_
+    nb = -(-T // 256)
+    per = -(-256 // lanes)                        # rows a lane visits in a full block
+    pad = np.zeros((nb, per * lanes, F_), np.float32)       # zero rows add nothing to either sum, as the rows past T the kernel skips
+    pad.reshape(nb, per * lanes * F_)[:, :256 * F_] = np.pad(x, ((0, nb * 256 - T), (0, 0))).reshape(nb, 256 * F_)
+    pad = pad.reshape(nb, per, lanes, F_)
+    s = np.zeros((nb, lanes, F_), np.float32)
+    q = np.zeros((nb, lanes, F_), np.float32)
+    for i in range(per):
+        v = pad[:, i]
+        s = (s + v).astype(np.float32)
+        q = (q + (v * v).astype(np.float32)).astype(np.float32)
+    bs, bq = np.zeros((nb, F_), np.float32), np.zeros((nb, F_), np.float32)
+    for k in range(lanes):
+        bs = (bs + s[:, k]).astype(np.float32)
+        bq = (bq + q[:, k]).astype(np.float32)
+    ls, lq = np.zeros((16, F_), np.float32), np.zeros((16, F_), np.float32)
+    for b in range(nb):
+        ls[b % 16] = (ls[b % 16] + bs[b]).astype(np.float32)
+        lq[b % 16] = (lq[b % 16] + bq[b]).astype(np.float32)
+    ts, tq = np.zeros(F_, np.float32), np.zeros(F_, np.float32)
+    for k in range(16):
+        ts = (ts + ls[k]).astype(np.float32)
+        tq = (tq + lq[k]).astype(np.float32)
+    sd_, qd = ts.astype(np.float64), tq.astype(np.float64)
+    mean = sd_ / T
+    var = (qd - sd_ * mean) / (T - 1) if T > 1 else np.ones(F_)
+    return torch.from_numpy(mean), torch.from_numpy(var)

@@ -1,6 +1,7 @@
 """tests/kernel_refs.py against torch's own ops and autograd in float64, to 1e-12 relative: the float64 restatements the GPU parity tests
 compare the HIP kernels with must themselves be right.  Also pins that the column-norm parity test discriminates: the summation order
-the kernel had before its statistics were made stable misses that test's bound on the offset inputs, torch's fp32 result meets it."""
+the kernel had before its statistics were made stable misses that test's bound on the offset inputs, torch's fp32 result meets it; and the
+same for the normalised log-mel test (tests/test_frontend_kernels_gpu.py) on bins at the floor log(1e-6)."""
 import os
 import sys
 
@@ -413,3 +414,112 @@ def test_convmod_ref_is_glu_conv_norm_silu(B, T, C, layernorm):
         for b in range(B):
             one = K.convmod_ref(u[b:b + 1], wR[b % R], bR[b % R], gR[b % R], tR[b % R] if layernorm else None, layernorm, eps)
             assert torch.equal(got[0][b], one[0][0]) and torch.equal(got[5][b * T:(b + 1) * T], one[5])
+
+
+# ----------------------------------------------------------------------------------------------------------- log-mel front end, window augmentations
+@pytest.mark.parametrize("n,pad", [(2, 1), (5, 0), (7, 6), (300, 256), (1000, 256)])
+def test_reflect_pad_ref_is_reflect_padding(n, pad):
+    x = _r(n, seed=80)
+    assert torch.equal(K.reflect_pad_ref(x, pad), F.pad(x[None, None], (pad, pad), mode="reflect")[0, 0] if pad else x)
+
+
+def test_stft_power_ref_is_the_squared_modulus():
+    T, KP = 9, 12
+    reim = _r(T, 2 * KP, seed=81)
+    _same(K.stft_power_ref(reim, KP), torch.complex(reim[:, :KP], reim[:, KP:]).abs() ** 2, "power")
+    assert K.stft_power_ref(reim.float(), KP).dtype == F64
+
+
+@pytest.mark.parametrize("T,Fq", [(2, 3), (300, 80), (1001, 7)])
+def test_logmel_finish_ref_is_log_then_mean_and_unbiased_std(T, Fq):
+    mel = torch.exp(_r(T, Fq, seed=82) * 2 - 5).float()
+    eps32 = torch.tensor(1e-6, dtype=torch.float32).double()
+    lm = torch.log(mel.double() + eps32).t()
+    _same(K.logmel_finish_ref(mel, 1e-6, False), lm, "log-mel")
+    _same(K.logmel_finish_ref(mel, 1e-6, True), (lm - lm.mean(-1, keepdim=True)) / lm.std(-1, keepdim=True), "normalised log-mel")
+
+
+def test_logmel_finish_ref_pins_zero_variance_and_one_frame_to_zeros():
+    mel = torch.exp(_r(50, 4, seed=83)).float()
+    mel[:, 1] = 0.0                                                    # an empty band: every frame is log(eps)
+    mel[:, 3] = 0.37
+    out = K.logmel_finish_ref(mel, 1e-6, True)
+    assert torch.equal(out[1], torch.zeros(50, dtype=F64)) and torch.equal(out[3], torch.zeros(50, dtype=F64))
+    assert torch.isfinite(out).all() and out[0].abs().max() > 0.5
+    assert torch.equal(K.logmel_finish_ref(mel[:1], 1e-6, True), torch.zeros(4, 1, dtype=F64))
+    assert torch.equal(K.logmel_finish_ref(mel[:1], 1e-6, False), torch.log(mel[:1].double() + float(torch.tensor(1e-6, dtype=torch.float32))).t())
+
+
+def test_rownorm_and_moments_refs_are_mean_and_std():
+    x = _r(3, 1025, seed=84) * 0.7 + torch.tensor([[0.0], [21.0], [700.0]], dtype=F64)
+    _same(K.rownorm_ref(x), (x - x.mean(-1, keepdim=True)) / x.std(-1, keepdim=True), "rownorm", 2.0 ** -52 * 1000 * 700)
+    _same(K.rownorm_ref(x[:1]), (x[:1] - x[:1].mean(-1, keepdim=True)) / x[:1].std(-1, keepdim=True), "rownorm, centred row")
+    for n in (2, 255, 2049):
+        v = _r(n, seed=85) + 0.3
+        s, mean, std = K.moments_ref(v)
+        assert abs(s - v.sum().item()) <= 1e-12 * n and abs(mean - v.mean().item()) <= 1e-12 and abs(std - v.std().item()) <= 1e-12
+    assert K.moments_ref(torch.tensor([2.5])) == (2.5, 2.5, 0.0)
+
+
+CUTOUT_RECTS = [(1, 3, 2, 6), (2, 4, 4, 7), (0, 1, 0, 7), (4, 5, 0, 1), (3, 3, 1, 5), (0, 5, 6, 6), (2, 5, 5, 7)]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_cutout_ref_is_sequential_slice_assignment(mode):
+    x = _r(5, 7, seed=86)
+    want = x.clone()
+    means = [x[y0:y1, x0:x1].mean() if (y1 > y0 and x1 > x0) else torch.tensor(0.0, dtype=F64) for y0, y1, x0, x1 in CUTOUT_RECTS]
+    for k, (y0, y1, x0, x1) in enumerate(CUTOUT_RECTS):
+        want[y0:y1, x0:x1] = (0.0, means[k], 1.25)[mode]
+    out, win, m = K.cutout_ref(x, CUTOUT_RECTS, mode, 1.25)
+    _same(out, want, f"cutout mode {mode}")
+    _same(m, torch.stack(means), "rectangle means")
+    assert torch.equal(out[win < 0], x[win < 0]) and (win < 0).any() and win[2, 5] == 6 and win[2, 4] == 1 and win[1, 2] == 0
+    out, win, m = K.cutout_ref(x, [], mode, 1.25)
+    assert torch.equal(out, x) and (win == -1).all() and m.numel() == 0
+    whole, _, _ = K.cutout_ref(x, [(0, 5, 0, 7)], 1, 0.0)
+    _same(whole, torch.full_like(x, x.mean().item()), "whole window")
+
+
+def test_gather_frames_ref_is_index_select():
+    x = _r(4, 9, seed=87)
+    pt, pf = torch.randperm(9, generator=K.gen(88)).int(), torch.randperm(4, generator=K.gen(89)).int()
+    assert torch.equal(K.gather_frames_ref(x, pt, 1), torch.index_select(x, 1, pt.long()))
+    assert torch.equal(K.gather_frames_ref(x, pf, 0), torch.index_select(x, 0, pf.long()))
+
+
+def test_logmel_class_inputs_have_their_classes():
+    mel = K.logmel_class_inputs(6001)
+    lm = K.logmel_finish_ref(mel, K.LOGMEL_EPS, False)
+    assert mel.dtype == torch.float32 and (mel >= 0).all() and (mel[:, K.LOGMEL_ZERO_COLUMN] == 0).all()
+    for f in range(12):
+        mu, sd = K.LOGMEL_CLASSES[f % 6]
+        # the (-13.8, 1e-2) class reaches the floor log(1e-6) = -13.8155 at -1.55 sd, where the clamp at mel = 0 cuts its lower tail
+        assert abs(lm[f].mean().item() - mu) < 0.1 * sd and abs(lm[f].std().item() / sd - 1) < 0.1, (f, lm[f].mean().item(), lm[f].std().item())
+
+
+@pytest.mark.parametrize("T", K.LOGMEL_NORM_T)
+def test_uncentred_logmel_statistics_miss_the_normalised_bound_on_near_floor_bins(T):
+    """The bounds of tests/test_frontend_kernels_gpu.py::test_logmel_finish_normalised (the output within 4 x torch's fp32 error + 2e-6 in
+    log-mel units; per-bin mean 0 and std 1 of the output within 4 x torch's + 1e-5) on that test's inputs: var = (q - s * mean) / (T - 1)
+    from fp32 running sums misses them on the bins at log(1e-6) at every T, torch's fp32 two-pass chain meets them."""
+    mel = K.logmel_class_inputs(T)
+    x32 = K.logmel_torch_fp32(mel, K.LOGMEL_EPS, False)                                  # [F, T] fp32 log values
+    bd = K.logmel_norm_bounds(mel)
+    ref, std64, live = bd["ref"], bd["std"], bd["live"]
+    (tol, e32), (tol_m, e_m), (tol_s, e_s) = bd["out"], bd["mean"], bd["unit_std"]
+    assert live == [f for f in range(80) if f != K.LOGMEL_ZERO_COLUMN]
+    assert e32 <= tol and e_m <= tol_m and e_s <= tol_s
+    assert torch.equal(ref, K.logmel_finish_ref(mel, K.LOGMEL_EPS, True)) and torch.equal(ref[K.LOGMEL_ZERO_COLUMN], torch.zeros(T, dtype=F64))
+    # the kernel as it was: fp32 logs (its own in-place result), the replayed statistics, var <= 0 replaced by 1, the quotient in double
+    mean, var = K.logmel_uncentred_replay(x32.t().contiguous())
+    var = torch.where(var > 0, var, torch.ones_like(var))
+    old = ((x32.double() - mean[:, None]) / torch.sqrt(var)[:, None]).float()
+    near_floor = [f for f in live if K.LOGMEL_CLASSES[f % 6][0] == -13.8]
+    got = K.logmel_log_unit_err(old[near_floor], ref[near_floor], std64[near_floor])
+    got_s = K.unit_stats_err(old, near_floor)[1]
+    print(f"T={T}: replay {got:.2e} log units, |std - 1| {got_s:.2e} | torch fp32 {e32:.2e}, mean {e_m:.2e}, std {e_s:.2e} | bounds {tol:.2e} {tol_m:.2e} {tol_s:.2e}")
+    assert got > tol and got_s > tol_s, (T, got, tol, got_s, tol_s)
+    for sd in (1e-3, 1e-2):                                            # each of the two near-floor classes on its own
+        cols = [f for f in near_floor if K.LOGMEL_CLASSES[f % 6][1] == sd]
+        assert K.logmel_log_unit_err(old[cols], ref[cols], std64[cols]) > tol, (T, sd)
