@@ -17,6 +17,12 @@ __device__ __forceinline__ float silu_grad(float x) {
     return s * (1.f + x * (1.f - s));
 }
 
+// The activation in front of a 3x3 stride-2 depthwise stage, fused into its loads: SiLU (the project's conformer) or ReLU (Parakeet's
+// dw_striding subsampling).  A compile-time parameter: the SiLU instances are the code as it was.
+constexpr int ACT_SILU = 0, ACT_RELU = 1;
+template <int ACT> __device__ __forceinline__ float act_in(float x) { return ACT == ACT_RELU ? fmaxf(x, 0.f) : silu_f(x); }
+template <int ACT> __device__ __forceinline__ float act_in_grad(float x) { return ACT == ACT_RELU ? (x > 0.f ? 1.f : 0.f) : silu_grad(x); }
+
 constexpr int TT = 32;  // time steps per workgroup tile
 
 // y[b,t,c] = bias[c] + sum_j w[c,j] * x[b, t + j - P, c],  P = (KW-1)/2.   FLIP => dgrad (w index reversed).
@@ -196,7 +202,8 @@ __global__ __launch_bounds__(256) void conv2d_first_wgrad_kernel(const float* __
 }
 
 // ---- subsampling: depthwise 3x3 stride 2 pad 1 over (T, F), input activation SiLU fused into the load ----
-//   u[b,to,fo,c] = bias[c] + sum_{dt,df} w[c,dt,df] * silu(z[b, 2to+dt-1, 2fo+df-1, c])
+//   u[b,to,fo,c] = bias[c] + sum_{dt,df} w[c,dt,df] * act(z[b, 2to+dt-1, 2fo+df-1, c])
+template <int ACT>
 __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                                const float* __restrict__ bias, float* __restrict__ u,
                                                                int64_t T, int F, int64_t To, int Fo, int C) {
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_kernel(const float* __res
             for (int df = 0; df < 3; ++df) {
                 const int f = 2 * fo + df - 1;
                 if (f < 0 || f >= F) continue;
-                acc += wk[dt * 3 + df] * silu_f(zb[(t * F + f) * C]);
+                acc += wk[dt * 3 + df] * act_in<ACT>(zb[(t * F + f) * C]);
             }
         }
         ub[(int64_t)fo * C] = acc;
@@ -232,6 +239,12 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_kernel(const float* __res
 // element is loaded (and SiLU'd) once per output row instead of up to 3 times.  Accumulation order per output is the same
 // (dt major, df minor) as the scalar kernels, so results are bit-identical to them.
 __device__ __forceinline__ float4 silu4(float4 v) { return make_float4(silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w)); }
+template <int ACT> __device__ __forceinline__ float4 act_in4(float4 v) {
+    return make_float4(act_in<ACT>(v.x), act_in<ACT>(v.y), act_in<ACT>(v.z), act_in<ACT>(v.w));
+}
+template <int ACT> __device__ __forceinline__ float4 act_in_grad4(float4 v) {
+    return make_float4(act_in_grad<ACT>(v.x), act_in_grad<ACT>(v.y), act_in_grad<ACT>(v.z), act_in_grad<ACT>(v.w));
+}
 __device__ __forceinline__ void fma4(float4& a, const float4& w, const float4& v) {
     a.x += w.x * v.x; a.y += w.y * v.y; a.z += w.z * v.z; a.w += w.w * v.w;
 }
@@ -240,6 +253,7 @@ __device__ __forceinline__ void load_w4(const float* __restrict__ w, int c0, flo
     for (int j = 0; j < 9; ++j) wk[j] = make_float4(w[(c0 + 0) * 9 + j], w[(c0 + 1) * 9 + j], w[(c0 + 2) * 9 + j], w[(c0 + 3) * 9 + j]);
 }
 
+template <int ACT>
 __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_v4_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                                   const float* __restrict__ bias, float* __restrict__ u,
                                                                   int64_t T, int F, int64_t To, int Fo, int C, int64_t rows) {
@@ -267,8 +281,8 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_v4_kernel(const float* __
             float4 c0v[3], c1v[3];
 #pragma unroll
             for (int dt = 0; dt < 3; ++dt) {
-                c0v[dt] = ok[dt] ? silu4(*reinterpret_cast<const float4*>(zr[dt] + (int64_t)f0 * C)) : zero;
-                c1v[dt] = (ok[dt] && f1 < F) ? silu4(*reinterpret_cast<const float4*>(zr[dt] + (int64_t)f1 * C)) : zero;
+                c0v[dt] = ok[dt] ? act_in4<ACT>(*reinterpret_cast<const float4*>(zr[dt] + (int64_t)f0 * C)) : zero;
+                c1v[dt] = (ok[dt] && f1 < F) ? act_in4<ACT>(*reinterpret_cast<const float4*>(zr[dt] + (int64_t)f1 * C)) : zero;
             }
             float4 acc = bv;
 #pragma unroll
@@ -328,6 +342,7 @@ __global__ __launch_bounds__(256) void conv2d_first_fwd_v4_kernel(const float* _
 __device__ __forceinline__ float4 silu_grad4(float4 v) { return make_float4(silu_grad(v.x), silu_grad(v.y), silu_grad(v.z), silu_grad(v.w)); }
 
 // dz row (b, t): every input element gathers the 1, 2 or 4 outputs it fed (parity of t and f decides which taps exist).
+template <int ACT>
 __global__ __launch_bounds__(256) void dwconv2d_s2_dgrad_v4_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                                     const float* __restrict__ du, float* __restrict__ dz,
                                                                     int64_t T, int F, int64_t To, int Fo, int C, int64_t rows) {
@@ -358,7 +373,7 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_dgrad_v4_kernel(const float* 
                     fma4(acc, wk[dt * 3 + df], *reinterpret_cast<const float4*>(gb + (to * Fo + fo) * C));
                 }
             }
-            const float4 sg = silu_grad4(*reinterpret_cast<const float4*>(zr + (int64_t)f * C));
+            const float4 sg = act_in_grad4<ACT>(*reinterpret_cast<const float4*>(zr + (int64_t)f * C));
             *reinterpret_cast<float4*>(dr + (int64_t)f * C) = make_float4(acc.x * sg.x, acc.y * sg.y, acc.z * sg.z, acc.w * sg.w);
         }
     }
@@ -366,7 +381,7 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_dgrad_v4_kernel(const float* 
 
 // weight gradient partials: one wave per tile of `per` output rows, sliding 3-column window like the forward; the four
 // waves of a workgroup are summed in wave order through LDS, so one partial row per WORKGROUP reaches the reducer.
-template <bool FIRST>   // FIRST: the 1-channel first conv (input x [B, T, F], no activation); else depthwise with SiLU(z)
+template <bool FIRST, int ACT = ACT_SILU>   // FIRST: the 1-channel first conv (input x [B, T, F], no activation); else depthwise with act(z)
 __global__ __launch_bounds__(256) void conv2d_s2_wgrad_v4_kernel(const float* __restrict__ in, const float* __restrict__ g_out,
                                                                   float* __restrict__ partial_w, float* __restrict__ partial_b,
                                                                   int64_t T, int F, int64_t To, int Fo, int C, int64_t per,
@@ -406,8 +421,8 @@ __global__ __launch_bounds__(256) void conv2d_s2_wgrad_v4_kernel(const float* __
                         if (ok[dt]) { const float v = ir[dt][f0]; a0 = make_float4(v, v, v, v); }
                         if (ok[dt] && f1 < F) { const float v = ir[dt][f1]; a1 = make_float4(v, v, v, v); }
                     } else {
-                        if (ok[dt]) a0 = silu4(*reinterpret_cast<const float4*>(ir[dt] + (int64_t)f0 * C));
-                        if (ok[dt] && f1 < F) a1 = silu4(*reinterpret_cast<const float4*>(ir[dt] + (int64_t)f1 * C));
+                        if (ok[dt]) a0 = act_in4<ACT>(*reinterpret_cast<const float4*>(ir[dt] + (int64_t)f0 * C));
+                        if (ok[dt] && f1 < F) a1 = act_in4<ACT>(*reinterpret_cast<const float4*>(ir[dt] + (int64_t)f1 * C));
                     }
                     fma4(acc[dt * 3 + 0], g, prev[dt]);
                     fma4(acc[dt * 3 + 1], g, a0);
@@ -650,7 +665,8 @@ __global__ __launch_bounds__(256) void sub12_bwd_kernel(const float* __restrict_
     }
 }
 
-// dz[b,t,f,c] = silu'(z) * sum_{(to,dt),(fo,df): 2to+dt-1=t, 2fo+df-1=f} w[c,dt,df] * du[b,to,fo,c]
+// dz[b,t,f,c] = act'(z) * sum_{(to,dt),(fo,df): 2to+dt-1=t, 2fo+df-1=f} w[c,dt,df] * du[b,to,fo,c]
+template <int ACT>
 __global__ __launch_bounds__(256) void dwconv2d_s2_dgrad_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                                  const float* __restrict__ du, float* __restrict__ dz,
                                                                  int64_t T, int F, int64_t To, int Fo, int C) {
@@ -679,10 +695,11 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_dgrad_kernel(const float* __r
             }
         }
         const int64_t idx = ((b * T + t) * F + f) * C + c;
-        dz[idx] = acc * silu_grad(z[idx]);
+        dz[idx] = acc * act_in_grad<ACT>(z[idx]);
     }
 }
 
+template <int ACT>
 __global__ __launch_bounds__(256) void dwconv2d_s2_wgrad_kernel(const float* __restrict__ z, const float* __restrict__ du,
                                                                  float* __restrict__ partial_w, float* __restrict__ partial_b,
                                                                  int64_t T, int F, int64_t To, int Fo, int C,
@@ -710,7 +727,7 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_wgrad_kernel(const float* __r
                 for (int df = 0; df < 3; ++df) {
                     const int f = 2 * fo + df - 1;
                     if (f < 0 || f >= F) continue;
-                    acc[dt * 3 + df] += g * silu_f(zb[(t * F + f) * C]);
+                    acc[dt * 3 + df] += g * act_in<ACT>(zb[(t * F + f) * C]);
                 }
             }
         }
@@ -943,63 +960,112 @@ extern "C" int dyn_sub12_bwd(const float* x, const float* du2, const float* w1, 
     return dyn::check_launch("dyn_sub12_bwd");
 }
 
-extern "C" int dyn_dwconv2d_s2_fwd(const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T,
-                                   int64_t F, int64_t C, void* stream) {
-    DYN_REQUIRE(z && w && bias && u && B >= 0 && T > 0 && F > 0 && C > 0, DYN_E_ARG, "dyn_dwconv2d_s2_fwd: bad arguments");
+namespace {
+
+int check_act(const char* who, int32_t act) {
+    DYN_REQUIRE(act == ACT_SILU || act == ACT_RELU, DYN_E_UNSUPPORTED, "%s: act=%d is not built (0 SiLU, 1 ReLU)", who, (int)act);
+    return DYN_OK;
+}
+
+template <int ACT>
+int dwconv2d_s2_fwd_impl(const char* who, const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T, int64_t F,
+                         int64_t C, void* stream) {
+    DYN_REQUIRE(z && w && bias && u && B >= 0 && T > 0 && F > 0 && C > 0, DYN_E_ARG, "%s: bad arguments", who);
     if (B == 0) return DYN_OK;
     const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1;
     if (C % 4 == 0 && (((uintptr_t)z | (uintptr_t)u | (uintptr_t)bias) & 15) == 0) {
         const int64_t rows = B * To;
-        hipLaunchKernelGGL(dwconv2d_s2_fwd_v4_kernel, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, w, bias, u,
+        hipLaunchKernelGGL(dwconv2d_s2_fwd_v4_kernel<ACT>, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, w, bias, u,
                            T, (int)F, To, (int)Fo, (int)C, rows);
-        return dyn::check_launch("dyn_dwconv2d_s2_fwd");
+        return dyn::check_launch(who);
     }
     dim3 grid((unsigned)To, (unsigned)dyn::cdiv(C, 256), (unsigned)B);
-    hipLaunchKernelGGL(dwconv2d_s2_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, z, w, bias, u, T, (int)F, To, (int)Fo, (int)C);
-    return dyn::check_launch("dyn_dwconv2d_s2_fwd");
+    hipLaunchKernelGGL(dwconv2d_s2_fwd_kernel<ACT>, grid, dim3(256), 0, (hipStream_t)stream, z, w, bias, u, T, (int)F, To, (int)Fo, (int)C);
+    return dyn::check_launch(who);
 }
 
-extern "C" int dyn_dwconv2d_s2_dgrad(const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T,
-                                     int64_t F, int64_t C, void* stream) {
-    DYN_REQUIRE(z && w && du && dz && B >= 0 && T > 0 && F > 0 && C > 0, DYN_E_ARG, "dyn_dwconv2d_s2_dgrad: bad arguments");
+template <int ACT>
+int dwconv2d_s2_dgrad_impl(const char* who, const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T, int64_t F,
+                           int64_t C, void* stream) {
+    DYN_REQUIRE(z && w && du && dz && B >= 0 && T > 0 && F > 0 && C > 0, DYN_E_ARG, "%s: bad arguments", who);
     if (B == 0) return DYN_OK;
     const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1;
     if (C % 4 == 0 && ((((uintptr_t)z) | ((uintptr_t)du) | ((uintptr_t)dz)) & 15) == 0) {
         const int64_t rows = B * T;
-        hipLaunchKernelGGL(dwconv2d_s2_dgrad_v4_kernel, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, w, du, dz,
+        hipLaunchKernelGGL(dwconv2d_s2_dgrad_v4_kernel<ACT>, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, w, du, dz,
                            T, (int)F, To, (int)Fo, (int)C, rows);
-        return dyn::check_launch("dyn_dwconv2d_s2_dgrad");
+        return dyn::check_launch(who);
     }
     dim3 grid((unsigned)T, (unsigned)dyn::cdiv(C, 256), (unsigned)B);
-    hipLaunchKernelGGL(dwconv2d_s2_dgrad_kernel, grid, dim3(256), 0, (hipStream_t)stream, z, w, du, dz, T, (int)F, To, (int)Fo, (int)C);
-    return dyn::check_launch("dyn_dwconv2d_s2_dgrad");
+    hipLaunchKernelGGL(dwconv2d_s2_dgrad_kernel<ACT>, grid, dim3(256), 0, (hipStream_t)stream, z, w, du, dz, T, (int)F, To, (int)Fo, (int)C);
+    return dyn::check_launch(who);
 }
 
-extern "C" int dyn_dwconv2d_s2_wgrad(const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B,
-                                     int64_t T, int64_t F, int64_t C, void* workspace, int64_t workspace_bytes, void* stream) {
-    DYN_REQUIRE(z && du && dw && dbias && B >= 0 && T > 0 && F > 0 && C > 0, DYN_E_ARG, "dyn_dwconv2d_s2_wgrad: bad arguments");
+template <int ACT>
+int dwconv2d_s2_wgrad_impl(const char* who, const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B, int64_t T,
+                           int64_t F, int64_t C, void* workspace, int64_t workspace_bytes, void* stream) {
+    DYN_REQUIRE(z && du && dw && dbias && B >= 0 && T > 0 && F > 0 && C > 0, DYN_E_ARG, "%s: bad arguments", who);
     if (B == 0) return DYN_OK;
     const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1;
     int64_t per;
     const int64_t chunks = wgrad_tiles2d(To, &per), tiles = chunks * B;
-    DYN_REQUIRE(workspace && workspace_bytes >= tiles * C * 10 * (int64_t)sizeof(float), DYN_E_WORKSPACE,
-                "dyn_dwconv2d_s2_wgrad: workspace too small");
+    DYN_REQUIRE(workspace && workspace_bytes >= tiles * C * 10 * (int64_t)sizeof(float), DYN_E_WORKSPACE, "%s: workspace too small", who);
     const bool v4 = C % 4 == 0 && ((((uintptr_t)z) | ((uintptr_t)du)) & 15) == 0;
     float* pw = v4 ? dyn::partials_alloc(workspace, tiles * C * 10 * (int64_t)sizeof(float)) : (float*)workspace;
     float* pb = pw + tiles * C * 9;
     hipStream_t st = (hipStream_t)stream;
     if (v4) {
-        hipLaunchKernelGGL((conv2d_s2_wgrad_v4_kernel<false>), dim3((unsigned)dyn::cdiv(tiles, 4)), dim3(256), 0, st, z, du, pw, pb, T, (int)F,
-                           To, (int)Fo, (int)C, per, chunks, tiles);
+        hipLaunchKernelGGL((conv2d_s2_wgrad_v4_kernel<false, ACT>), dim3((unsigned)dyn::cdiv(tiles, 4)), dim3(256), 0, st, z, du, pw, pb, T,
+                           (int)F, To, (int)Fo, (int)C, per, chunks, tiles);
         dyn::reduce_taps_or_defer(pw, dw, dyn::cdiv(tiles, 4), C * 9, beta, (int)C, st);
         dyn::reduce_or_defer(pb, dbias, dyn::cdiv(tiles, 4), C, beta, st);
-        return dyn::check_launch("dyn_dwconv2d_s2_wgrad");
+        return dyn::check_launch(who);
     } else {
         dim3 grid((unsigned)chunks, (unsigned)dyn::cdiv(C, 256), (unsigned)B);
-        hipLaunchKernelGGL(dwconv2d_s2_wgrad_kernel, grid, dim3(256), 0, st, z, du, pw, pb, T, (int)F, To, (int)Fo, (int)C, per);
+        hipLaunchKernelGGL(dwconv2d_s2_wgrad_kernel<ACT>, grid, dim3(256), 0, st, z, du, pw, pb, T, (int)F, To, (int)Fo, (int)C, per);
     }
     dyn::ordered_before_launch(st);
     dyn::launch_reduce_partials(pw, dw, tiles, C * 9, beta, st);
     dyn::launch_reduce_partials(pb, dbias, tiles, C, beta, st);
-    return dyn::check_launch("dyn_dwconv2d_s2_wgrad");
+    return dyn::check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int dyn_dwconv2d_s2_fwd(const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T,
+                                   int64_t F, int64_t C, void* stream) {
+    return dwconv2d_s2_fwd_impl<ACT_SILU>("dyn_dwconv2d_s2_fwd", z, w, bias, u, B, T, F, C, stream);
+}
+
+extern "C" int dyn_dwconv2d_s2_dgrad(const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T,
+                                     int64_t F, int64_t C, void* stream) {
+    return dwconv2d_s2_dgrad_impl<ACT_SILU>("dyn_dwconv2d_s2_dgrad", z, w, du, dz, B, T, F, C, stream);
+}
+
+extern "C" int dyn_dwconv2d_s2_wgrad(const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B,
+                                     int64_t T, int64_t F, int64_t C, void* workspace, int64_t workspace_bytes, void* stream) {
+    return dwconv2d_s2_wgrad_impl<ACT_SILU>("dyn_dwconv2d_s2_wgrad", z, du, dw, dbias, beta, B, T, F, C, workspace, workspace_bytes, stream);
+}
+
+// The same three stages with the input activation chosen by the caller: act 0 = SiLU (the entries above), 1 = ReLU.
+extern "C" int dyn_dwconv2d_s2_fwd_act(const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T, int64_t F,
+                                       int64_t C, int32_t act, void* stream) {
+    if (int rc = check_act("dyn_dwconv2d_s2_fwd_act", act)) return rc;
+    return act == ACT_RELU ? dwconv2d_s2_fwd_impl<ACT_RELU>("dyn_dwconv2d_s2_fwd_act", z, w, bias, u, B, T, F, C, stream)
+                           : dwconv2d_s2_fwd_impl<ACT_SILU>("dyn_dwconv2d_s2_fwd_act", z, w, bias, u, B, T, F, C, stream);
+}
+
+extern "C" int dyn_dwconv2d_s2_dgrad_act(const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T, int64_t F,
+                                         int64_t C, int32_t act, void* stream) {
+    if (int rc = check_act("dyn_dwconv2d_s2_dgrad_act", act)) return rc;
+    return act == ACT_RELU ? dwconv2d_s2_dgrad_impl<ACT_RELU>("dyn_dwconv2d_s2_dgrad_act", z, w, du, dz, B, T, F, C, stream)
+                           : dwconv2d_s2_dgrad_impl<ACT_SILU>("dyn_dwconv2d_s2_dgrad_act", z, w, du, dz, B, T, F, C, stream);
+}
+
+extern "C" int dyn_dwconv2d_s2_wgrad_act(const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B, int64_t T,
+                                         int64_t F, int64_t C, int32_t act, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (int rc = check_act("dyn_dwconv2d_s2_wgrad_act", act)) return rc;
+    return act == ACT_RELU
+               ? dwconv2d_s2_wgrad_impl<ACT_RELU>("dyn_dwconv2d_s2_wgrad_act", z, du, dw, dbias, beta, B, T, F, C, workspace, workspace_bytes, stream)
+               : dwconv2d_s2_wgrad_impl<ACT_SILU>("dyn_dwconv2d_s2_wgrad_act", z, du, dw, dbias, beta, B, T, F, C, workspace, workspace_bytes, stream);
 }

@@ -1,0 +1,206 @@
+// The core of Parakeet's (FastConformer) convolution module (transformers modeling_parakeet.py, ParakeetEncoderConvolutionModule.forward):
+//     glu -> depthwise_conv (KW taps, zero SAME padding, optional bias) -> BatchNorm1d in eval mode (running statistics) -> activation
+// between the two pointwise convolutions (GEMMs).  KW = 9, C in {256, 512, 768, 1024}, channels-last, fp32.
+//
+//   dyn_convmod_bn_fwd       u [B, T, 2C] -> s [B, T, C] = act((conv - mean_c) * rsqrt(var_c + eps) * weight_c + bias_c),
+//                            conv[b, t, c] = cbias_c + sum_j w[c, j] * GLU(u)[b, t - (KW - 1) / 2 + j, c], in ONE launch.
+//     Thread = channel.  A thread loads its channel's TT + KW - 1 GLU values ONCE into registers
+//     (statically indexed) and forms its TT outputs from them.  BatchNorm with fixed statistics is per channel: no row reduction, so no
+//     LDS stage and no barrier.  A GLU value is computed (TT + KW - 1) / TT = 1.5 times at TT = 16.
+//   dyn_convmod_bn_bwd_act   dc = ds * act'(bn) * weight * rstd and the three column sums (dweight, dbias, dcbias) as per-workgroup
+//                            partial rows, rows visited in a fixed order, combined by the fixed-order reducer (reduce.h; deferrable).
+//   dyn_glu_dwconv1d_dgrad   du = GLU'(u) * sum_j w[c, j] * dc[t + (KW - 1) / 2 - j]: the register window of the forward over dc, the GLU
+//                            backward applied to the sum before it is stored; no dgl tensor exists.
+// `valid` (device int32 scalar, may be null): GLU rows t >= *valid read as zeros (what SAME padding holds there in the unpadded run) and
+// rows >= *valid of every output are exact zeros / left out of the sums.  No float atomics: every result is bit-reproducible.
+#include "common.h"
+#include "reduce.h"
+
+namespace {
+
+constexpr int KW9 = 9;
+constexpr int TT = 16;        // frames per workgroup of the forward and the dgrad
+constexpr int ACT_SILU = 0;
+
+__device__ __forceinline__ float silu_f(float x) { return x * dyn::sigmoidf_(x); }
+__device__ __forceinline__ float silu_grad(float x) {
+    const float s = dyn::sigmoidf_(x);
+    return s * (1.f + x * (1.f - s));
+}
+
+// grid (ceil(T / TT), C / 256, B); 256 threads, thread = channel.
+template <int KW>
+__global__ __launch_bounds__(256) void convmod_bn_fwd_kernel(const float* __restrict__ u, const float* __restrict__ w,
+                                                              const float* __restrict__ cbias, const float* __restrict__ mean,
+                                                              const float* __restrict__ var, const float* __restrict__ weight,
+                                                              const float* __restrict__ bias, float* __restrict__ s,
+                                                              float* __restrict__ gl_out, float* __restrict__ c_out,
+                                                              const int32_t* __restrict__ valid, int64_t T, int C, float eps) {
+    constexpr int HALF = (KW - 1) / 2, NG = TT + KW - 1;
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    const int64_t b = blockIdx.z, t0 = (int64_t)blockIdx.x * TT;
+    const int64_t vr = dyn::valid_rows(valid, T);
+    float wk[KW], g[NG];
+#pragma unroll
+    for (int j = 0; j < KW; ++j) wk[j] = w[(int64_t)c * KW + j];
+    const float cb = cbias ? cbias[c] : 0.f, mu = mean[c], rs = rsqrtf(var[c] + eps), gw = weight[c], sh = bias[c];
+    const float* ub = u + b * T * 2 * C + c;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        const int64_t t = t0 - HALF + i;
+        g[i] = (t >= 0 && t < vr) ? ub[t * 2 * C] * dyn::sigmoidf_(ub[t * 2 * C + C]) : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < TT; ++k) {
+        const int64_t t = t0 + k;
+        if (t >= T) break;
+        const int64_t o = (b * T + t) * C + c;
+        float cv = 0.f, sv = 0.f;
+        if (t < vr) {
+            cv = cb;
+#pragma unroll
+            for (int j = 0; j < KW; ++j) cv += wk[j] * g[k + j];
+            sv = silu_f((cv - mu) * rs * gw + sh);
+        }
+        s[o] = sv;
+        if (gl_out) gl_out[o] = g[k + HALF];            // rows >= valid hold zeros in the window already
+        if (c_out) c_out[o] = cv;
+    }
+}
+
+// grid (nb, C / 256); thread = channel; workgroup x takes rows x, x + nb, ... of the B * T rows in that order.
+__global__ __launch_bounds__(256) void convmod_bn_bwd_act_kernel(const float* __restrict__ c_in, const float* __restrict__ mean,
+                                                                  const float* __restrict__ var, const float* __restrict__ weight,
+                                                                  const float* __restrict__ bias, const float* ds, float* dc,
+                                                                  float* __restrict__ pw, float* __restrict__ pb,
+                                                                  float* __restrict__ pc, const int32_t* __restrict__ valid, int64_t rows,
+                                                                  int64_t T, int C, float eps) {
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    const int64_t vr = dyn::valid_rows(valid, T);
+    const float mu = mean[c], rs = rsqrtf(var[c] + eps), gw = weight[c], sh = bias[c];
+    float aw = 0.f, ab = 0.f, ac = 0.f;
+    for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+        float o = 0.f;
+        if (r % T < vr) {
+            const float xh = (c_in[r * C + c] - mu) * rs;
+            const float da = ds[r * C + c] * silu_grad(xh * gw + sh);
+            o = da * gw * rs;
+            aw += da * xh;
+            ab += da;
+            ac += o;
+        }
+        dc[r * C + c] = o;
+    }
+    const int64_t p = (int64_t)blockIdx.x * C + c;
+    if (pw) pw[p] = aw;
+    if (pb) pb[p] = ab;
+    if (pc) pc[p] = ac;
+}
+
+// grid (ceil(T / TT), C / 256, B); 256 threads, thread = channel.
+template <int KW>
+__global__ __launch_bounds__(256) void glu_dwconv1d_dgrad_kernel(const float* __restrict__ u, const float* __restrict__ w,
+                                                                  const float* __restrict__ dc, float* __restrict__ du,
+                                                                  const int32_t* __restrict__ valid, int64_t T, int C) {
+    constexpr int HALF = (KW - 1) / 2, NG = TT + KW - 1;
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    const int64_t b = blockIdx.z, t0 = (int64_t)blockIdx.x * TT;
+    const int64_t vr = dyn::valid_rows(valid, T);
+    float wk[KW], g[NG];
+#pragma unroll
+    for (int j = 0; j < KW; ++j) wk[j] = w[(int64_t)c * KW + (KW - 1 - j)];      // flipped: dgl[t] = sum_i wk[i] * dc[t - HALF + i]
+    const float* gb = dc + b * T * C + c;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        const int64_t t = t0 - HALF + i;
+        g[i] = (t >= 0 && t < T) ? gb[t * C] : 0.f;
+    }
+    const float* ub = u + b * T * 2 * C + c;
+    float* ob = du + b * T * 2 * C + c;
+#pragma unroll
+    for (int k = 0; k < TT; ++k) {
+        const int64_t t = t0 + k;
+        if (t >= T) break;
+        float da = 0.f, db = 0.f;
+        if (t < vr) {
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < KW; ++i) acc += wk[i] * g[k + i];
+            const float a = ub[t * 2 * C], sg = dyn::sigmoidf_(ub[t * 2 * C + C]);
+            da = acc * sg;
+            db = acc * a * sg * (1.f - sg);
+        }
+        ob[t * 2 * C] = da;
+        ob[t * 2 * C + C] = db;
+    }
+}
+
+inline int bwd_blocks(int64_t rows) { return (int)(rows < 1 ? 1 : rows > 512 ? 512 : rows); }
+
+int check_dims(const char* who, int64_t B, int64_t T, int64_t C, int64_t KW) {
+    DYN_REQUIRE(B >= 0 && T >= 0 && B < 65536 && B * T < (1ll << 31), DYN_E_ARG, "%s: bad sizes B=%lld T=%lld", who, (long long)B, (long long)T);
+    DYN_REQUIRE(KW == KW9, DYN_E_UNSUPPORTED, "%s: kernel width %lld is not built (9)", who, (long long)KW);
+    DYN_REQUIRE(C == 256 || C == 512 || C == 768 || C == 1024, DYN_E_UNSUPPORTED, "%s: C=%lld is not built (256, 512, 768, 1024)", who,
+                (long long)C);
+    return DYN_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t dyn_convmod_bn_time_tile(void) { return TT; }
+
+extern "C" int dyn_convmod_bn_fwd(const float* u, const float* w, const float* cbias, const float* mean, const float* var, const float* weight,
+                                  const float* bias, float* s, float* gl, float* c, const int32_t* valid, int64_t B, int64_t T, int64_t C,
+                                  int64_t KW, int32_t act, float eps, void* stream) {
+    DYN_REQUIRE(u && w && mean && var && weight && bias && s, DYN_E_ARG, "dyn_convmod_bn_fwd: null pointer");
+    if (int rc = check_dims("dyn_convmod_bn_fwd", B, T, C, KW)) return rc;
+    DYN_REQUIRE(act == ACT_SILU, DYN_E_UNSUPPORTED, "dyn_convmod_bn_fwd: act=%d is not built (0 SiLU)", (int)act);
+    if (B == 0 || T == 0) return DYN_OK;
+    const dim3 grid((unsigned)dyn::cdiv(T, TT), (unsigned)(C / 256), (unsigned)B);
+    hipLaunchKernelGGL((convmod_bn_fwd_kernel<KW9>), grid, dim3(256), 0, (hipStream_t)stream, u, w, cbias, mean, var, weight, bias, s, gl, c,
+                       valid, T, (int)C, eps);
+    return dyn::check_launch("dyn_convmod_bn_fwd");
+}
+
+extern "C" int64_t dyn_convmod_bn_bwd_act_workspace_bytes(int64_t B, int64_t T, int64_t C) {
+    return (int64_t)3 * bwd_blocks(B * T) * C * (int64_t)sizeof(float);
+}
+
+extern "C" int dyn_convmod_bn_bwd_act(const float* c, const float* mean, const float* var, const float* weight, const float* bias,
+                                      const float* ds, float* dc, float* dweight, float* dbias, float* dcbias, float wgrad_beta,
+                                      const int32_t* valid, int64_t B, int64_t T, int64_t C, int32_t act, float eps, void* workspace,
+                                      int64_t workspace_bytes, void* stream) {
+    DYN_REQUIRE(c && mean && var && weight && bias && ds && dc, DYN_E_ARG, "dyn_convmod_bn_bwd_act: null pointer");
+    if (int rc = check_dims("dyn_convmod_bn_bwd_act", B, T, C, KW9)) return rc;
+    DYN_REQUIRE(act == ACT_SILU, DYN_E_UNSUPPORTED, "dyn_convmod_bn_bwd_act: act=%d is not built (0 SiLU)", (int)act);
+    const int64_t bytes = dyn_convmod_bn_bwd_act_workspace_bytes(B, T, C);
+    DYN_REQUIRE(workspace && workspace_bytes >= bytes, DYN_E_WORKSPACE, "dyn_convmod_bn_bwd_act: workspace too small (%lld bytes needed)",
+                (long long)bytes);
+    if (B == 0 || T == 0) return DYN_OK;
+    const int64_t rows = B * T;
+    const int nb = bwd_blocks(rows);
+    hipStream_t st = (hipStream_t)stream;
+    float* pw = dyn::partials_alloc(workspace, bytes);
+    float* pb = pw + (int64_t)nb * C;
+    float* pc = pb + (int64_t)nb * C;
+    hipLaunchKernelGGL(convmod_bn_bwd_act_kernel, dim3((unsigned)nb, (unsigned)(C / 256)), dim3(256), 0, st, c, mean, var, weight, bias, ds, dc,
+                       dweight ? pw : nullptr, dbias ? pb : nullptr, dcbias ? pc : nullptr, valid, rows, T, (int)C, eps);
+    if (dweight && dbias) dyn::reduce_pair_or_defer(pw, dweight, pb, dbias, (int64_t)nb, C, wgrad_beta, st);
+    else {
+        if (dweight) dyn::reduce_or_defer(pw, dweight, (int64_t)nb, C, wgrad_beta, st);
+        if (dbias) dyn::reduce_or_defer(pb, dbias, (int64_t)nb, C, wgrad_beta, st);
+    }
+    if (dcbias) dyn::reduce_or_defer(pc, dcbias, (int64_t)nb, C, wgrad_beta, st);
+    return dyn::check_launch("dyn_convmod_bn_bwd_act");
+}
+
+extern "C" int dyn_glu_dwconv1d_dgrad(const float* u, const float* w, const float* dc, float* du, const int32_t* valid, int64_t B, int64_t T,
+                                      int64_t C, int64_t KW, void* stream) {
+    DYN_REQUIRE(u && w && dc && du, DYN_E_ARG, "dyn_glu_dwconv1d_dgrad: null pointer");
+    if (int rc = check_dims("dyn_glu_dwconv1d_dgrad", B, T, C, KW)) return rc;
+    DYN_REQUIRE(du != u && du != dc, DYN_E_ARG, "dyn_glu_dwconv1d_dgrad: du must not alias u or dc");
+    if (B == 0 || T == 0) return DYN_OK;
+    const dim3 grid((unsigned)dyn::cdiv(T, TT), (unsigned)(C / 256), (unsigned)B);
+    hipLaunchKernelGGL((glu_dwconv1d_dgrad_kernel<KW9>), grid, dim3(256), 0, (hipStream_t)stream, u, w, dc, du, valid, T, (int)C);
+    return dyn::check_launch("dyn_glu_dwconv1d_dgrad");
+}

@@ -1,5 +1,5 @@
 // HBM-bound elementwise pieces of the encoder forward/backward (16-B vector accesses, grid-stride):
-// SiLU / ReLU(not used) / GLU, residual axpy, column sums for bias gradients, and the deterministic
+// SiLU / ReLU (Parakeet's subsampling) / GLU, residual axpy, column sums for bias gradients, and the deterministic
 // partial-sum reducer shared by every weight-gradient reduction.
 // Reference call sites: the activation / residual / bias ops inside model(audio_signal=...) and
 // loss.backward() (reference lcasr/lib.py:550,579); SpecAugment frequency masks (lib.py:541).
@@ -224,6 +224,48 @@ extern "C" int dyn_silu_bwd(const float* x, const float* dy, float* dx, int64_t 
     if (n == 0) return DYN_OK;
     hipLaunchKernelGGL(silu_bwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, (hipStream_t)stream, x, dy, dx, n);
     return dyn::check_launch("dyn_silu_bwd");
+}
+
+namespace {
+// y = max(x, 0)   (y may alias x)
+__global__ void relu_fwd_kernel(const float* x, float* y, int64_t n) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
+        float4 v = reinterpret_cast<const float4*>(x)[i];
+        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+        reinterpret_cast<float4*>(y)[i] = v;
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) y[i] = fmaxf(x[i], 0.f);
+}
+
+// dx = x > 0 ? dy : 0   (dx may alias dy; at exactly 0 no gradient, as torch)
+__global__ void relu_bwd_kernel(const float* __restrict__ x, const float* dy, float* dx, int64_t n) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
+        const float4 v = reinterpret_cast<const float4*>(x)[i];
+        float4 g = reinterpret_cast<const float4*>(dy)[i];
+        g.x = v.x > 0.f ? g.x : 0.f; g.y = v.y > 0.f ? g.y : 0.f; g.z = v.z > 0.f ? g.z : 0.f; g.w = v.w > 0.f ? g.w : 0.f;
+        reinterpret_cast<float4*>(dx)[i] = g;
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB)
+        dx[i] = x[i] > 0.f ? dy[i] : 0.f;
+}
+}  // namespace
+
+extern "C" int dyn_relu_fwd(const float* x, float* y, int64_t n, void* stream) {
+    DYN_REQUIRE(n >= 0 && (n == 0 || (x && y)), DYN_E_ARG, "dyn_relu_fwd: bad arguments");
+    DYN_REQUIRE(((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0, DYN_E_ARG, "dyn_relu_fwd: operands must be 16-byte aligned");
+    if (n == 0) return DYN_OK;
+    hipLaunchKernelGGL(relu_fwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, (hipStream_t)stream, x, y, n);
+    return dyn::check_launch("dyn_relu_fwd");
+}
+
+extern "C" int dyn_relu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream) {
+    DYN_REQUIRE(n >= 0 && (n == 0 || (x && dy && dx)), DYN_E_ARG, "dyn_relu_bwd: bad arguments");
+    DYN_REQUIRE(((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx)) & 15) == 0, DYN_E_ARG, "dyn_relu_bwd: operands must be 16-byte aligned");
+    if (n == 0) return DYN_OK;
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 4 + 1)), dim3(TPB), 0, (hipStream_t)stream, x, dy, dx, n);
+    return dyn::check_launch("dyn_relu_bwd");
 }
 
 extern "C" int dyn_glu_fwd(const float* u, float* y, int64_t rows, int64_t C, void* stream) {

@@ -1,0 +1,166 @@
+"""Drop-in mirror of the reference's third dynamic-eval library (reference nvidia_ctc/lib.py: NVIDIA's conformer-CTC models) on the HIP
+path: the chunked `dynamic_eval_ctc_loss` / `dynamic_eval` (:35-193) and `apply_args` (:206-221).
+
+Same call signature; `model` is this package's ParakeetForCTC (parakeet_model.py), the FastConformer-CTC architecture as transformers
+restates it, so no NeMo is needed.  The loop follows wav2vec2_lib.dynamic_eval_ctc_loss statement for statement; what differs, as in the
+reference:
+  * `spec` [1, n_mels, T] is a spectrogram, computed outside the loop (nvidia_ctc/lib.py:20-28), cut into windows along T (:116-125); every
+    copy is transposed to [T, n_mels] on the device, the layout transformers' model takes;
+  * SpecAugment (augment.SpecAugment, `spec_augment_config`) on the first `num_negatives` copies, one draw per copy in index order from the
+    host torch RNG (`args.spec_augment_generator`, a torch.Generator, when given).  The reference's SpecAugment comes from an un-vendored
+    package: the draw rule is augment.py's (parity unpinned, as for the other loops);
+  * Adam (optim.Adam: one fused launch over the flat vector);
+  * `pre_encode` and the decoder do not adapt (:81-86): `encoder.subsampling.` and `ctc_head.` are in `model.frozen` for the duration of the
+    call (`pos_enc` has no parameters), so their backward is not run at all;
+  * the conv modules' BatchNorm reads its running statistics (:89-102): the model is the eval-mode model;
+  * blank = `tokenizer.vocab_size`, greedy pseudo-labels from the clean last copy, `CTCLoss(reduction="sum") / (N * B)`, probability-space
+    stitching with a downsampling factor of 8 (:165-187); parameters and the `frozen` set are restored on exit (:189-191).
+The tokenizer is NeMo's surface: `vocab_size` (an attribute), `ids_to_text`, `text_to_ids`; SyntheticTokenizer is the stand-in for seeded
+weights."""
+import random
+
+import torch
+
+from . import ops
+from ._loop import Stitcher, window_fill_value
+from .augment import SpecAugment
+from .decoding import GreedyCTCDecoder
+from .optim import MADGRAD, Adam  # noqa: F401
+from .parakeet_model import FROZEN_IN_THE_LOOP
+
+try:
+    from tqdm import tqdm
+except Exception:  # pragma: no cover
+    def tqdm(x, **_):
+        return x
+
+SPEC_AUGMENT_CONFIG = {'n_time_masks': 3, 'n_freq_masks': 3, 'freq_mask_param': 40, 'time_mask_param': -1, 'min_p': 0.05, 'zero_masking': False}
+
+
+class SyntheticTokenizer:
+    """Stand-in for a NeMo tokenizer with seeded weights: token i <-> the word "w<i>", so ids_to_text -> text_to_ids is an exact identity and
+    the pseudo-label text hop of the reference is preserved.  `vocab_size` does not count the CTC blank (the model has vocab_size + 1 classes)."""
+
+    def __init__(self, vocab_size):
+        self.vocab_size = int(vocab_size)
+
+    def ids_to_text(self, ids):
+        return " ".join(f"w{int(i)}" for i in ids)
+
+    def text_to_ids(self, text):
+        return [int(w[1:]) for w in text.split() if len(w) > 1 and w[0] == "w" and w[1:].isdigit() and int(w[1:]) < self.vocab_size]
+
+
+class SentencePieceAdapter:
+    """reference nvidia_ctc/lib.py:196-204."""
+
+    def __init__(self, tokenizer):
+        self.tokenizer = tokenizer
+
+    def decode(self, ids):
+        return self.tokenizer.ids_to_text(ids)
+
+    def encode(self, text):
+        return self.tokenizer.text_to_ids(text)
+
+
+def disable_dropout(model):
+    """reference nvidia_ctc/lib.py:30-33 — the model has no dropout modules (eval-mode forward)."""
+    return model
+
+
+def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=Adam, num_negatives=4, lr_args={'lr': 1e-8},
+                          spec_augment_config=SPEC_AUGMENT_CONFIG, return_device=False):
+    """reference nvidia_ctc/lib.py:35-193: spectrogram windows, SpecAugment on the first copies, Adam, stitching of exp(log_p[-1])."""
+    device = model.device
+    spec = spec.to(device=device, dtype=torch.float32)                                           # [1, F, T]
+    if spec.dim() != 3 or spec.shape[0] != 1:
+        raise ops.DynError(f"spec must be [1, n_mels, T], got {tuple(spec.shape)}")
+    Fq, spec_n = spec.shape[1], spec.shape[-1]
+    downsampling_factor = 8
+    model = disable_dropout(model)
+    original = model.flat_params.clone()                                                         # lib.py:63-64
+    was_frozen = model.frozen
+    model.frozen = set(was_frozen) | set(FROZEN_IN_THE_LOOP)                                     # lib.py:81-86
+    try:
+        blank = tokenizer.vocab_size                                                             # lib.py:66,71
+        decoder = GreedyCTCDecoder(tokenizer=SentencePieceAdapter(tokenizer), blank_id=blank, device=device)
+        augmentation = SpecAugment(**spec_augment_config)
+        generator = args.__dict__.get('spec_augment_generator', None)
+        optimizer = optim(model.parameters(), **lr_args)                                         # lib.py:105
+        if seq_len > spec_n:
+            seq_len, overlap = spec_n, 0
+        assert overlap / downsampling_factor == overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
+        stitch = Stitcher.for_recording(spec_n, seq_len, tokenizer.vocab_size + 1, device)       # lib.py:113
+        last_ulen, kill_next, training_data = None, False, {}
+        for i in range(0, spec_n, seq_len - overlap):                                            # lib.py:116-125
+            chunk = spec[:, :, i:i + seq_len]
+            u_len = chunk.shape[-1]
+            if kill_next:
+                break
+            elif last_ulen is not None and u_len < last_ulen:
+                kill_next = True
+            last_ulen = u_len
+            training_data[i] = chunk
+        outputs = {}
+        B = num_negatives + 1
+        for epoch in range(args.__dict__.get('epochs', 1)):
+            outputs = {}
+            keys = list(training_data.keys())
+            keys = random.sample(keys, len(keys)) if args.__dict__.get('shuffle', False) else keys
+            for i in (tqdm(keys) if use_tqdm else keys):
+                chunk = training_data[i][0]                                                      # [F, u_len], a view of the recording
+                u_len = chunk.shape[-1]
+                feats = torch.empty(B, u_len, Fq, device=device, dtype=torch.float32)
+                copy = torch.empty(Fq, u_len, device=device, dtype=torch.float32)
+                for j in range(B):                                                               # lib.py:135-137: the last copy stays clean
+                    if j < num_negatives:
+                        copy.copy_(chunk)
+                        masks = augmentation.draw(Fq, u_len, generator)
+                        if masks[0][0] or masks[1][0]:
+                            augmentation.apply(copy, masks, window_fill_value(copy, augmentation.zero_masking))
+                        ops.transpose_ft(copy, out=feats[j])
+                    else:
+                        ops.transpose_ft(chunk, out=feats[j])
+                with torch.enable_grad():
+                    out = model(input_features=feats)                                            # lib.py:141
+                log_p = ops.log_softmax(out.logits)
+                N = out.frames
+                ids = tokenizer.text_to_ids(decoder(log_p[-1, :N]))                              # lib.py:144-146
+                S = len(ids)
+                targets = torch.tensor([ids if S else [0]] * num_negatives, dtype=torch.int32, device=device)
+                aug = log_p[:num_negatives].contiguous()
+                nb = aug.shape[0]
+                ilen = torch.full((nb,), N, dtype=torch.int32, device=device); tlen = torch.full((nb,), S, dtype=torch.int32, device=device)
+                _, _, g_lp = ops.ctc_loss(aug, targets, ilen, tlen, blank, reduction="sum", grad_scale=1.0 / (N * nb))   # lib.py:149-152
+                optimizer.zero_grad()
+                model.backward(ops.log_softmax_bwd(aug, g_lp), n_active=num_negatives)           # lib.py:155-156
+                optimizer.step()                                                                 # lib.py:160
+                outputs[i] = (log_p[-1, :N], u_len)                                              # lib.py:165-170
+        for i in sorted(outputs):                                                                # lib.py:174-187
+            stitch.add(i, *outputs[i], overlap)
+        logits = stitch.finalize()
+    finally:
+        model.flat_params.copy_(original)                                                        # lib.py:189-191
+        model.frozen = was_frozen
+    return logits if return_device else logits.cpu().numpy()
+
+
+dynamic_eval = dynamic_eval_ctc_loss
+
+
+def apply_args(parser, argv=None):
+    """reference nvidia_ctc/lib.py:206-221 (same flags).  The reference falls back to `paths.checkpoints.nvidia_ctc` when -c is empty; no
+    paths.yaml exists offline, so an empty -c stays empty (seeded weights)."""
+    parser.add_argument('-c', '--checkpoint', type=str, default='', help='path to checkpoint')
+    parser.add_argument('-split', '--split', type=str, default='test', help='test or dev split')
+    parser.add_argument('-seq', '--seq_len', type=int, default=2048)
+    parser.add_argument('-overlap', '--overlap', type=int, default=0)
+    parser.add_argument('-nv', '--not_verbose', action='store_true', help='verbose')
+    parser.add_argument('-log', '--log', type=str, default='')
+    parser.add_argument('-shuffle', '--shuffle', action='store_true', help='shuffle')
+    parser.add_argument('-epochs', '--epochs', type=int, default=1, help='epochs')
+    parser.add_argument('-dfa', '--disable_flash_attention', action='store_true', help='disable flash attention')
+    args = parser.parse_args(argv)
+    args.verbose = not args.not_verbose
+    return args

@@ -1854,3 +1854,136 @@ def relkey_embed_grad(dc2p, q, dE, scale, beta=1.0):
     rev = torch.empty(P, D, device=dE.device, dtype=F32)
     reduce_partials(part, rev, beta=0.0)
     return axpby(rev.flip(0), dE, 1.0, beta)
+
+
+# ----------------------------------------------------------------------------------------------- Parakeet (FastConformer)
+CONVMOD_BN_ACTS = {"silu": 0, "swish": 0}
+SUBSAMPLING_ACTS = {"silu": 0, "relu": 1}
+
+
+def convmod_bn_time_tile():
+    """Frames per workgroup of the conv-module kernels below (tests place their edges around it)."""
+    return int(_L().dyn_convmod_bn_time_tile())
+
+
+def _bn_operands(what, C, mean, var, weight, bias):
+    for n, t in (("mean", mean), ("var", var), ("weight", weight), ("bias", bias)):
+        _cc(t, f"{what}.{n}")
+        if t.numel() != C:
+            raise DynError(f"{what}: {n} must have C = {C} elements")
+
+
+def convmod_bn(u, w, cbias, mean, var, weight, bias, act="silu", eps=1e-5, valid=None, save=False):
+    """Parakeet's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = act(BatchNorm_eval(cbias + depthwise conv(GLU(u)))), w [C, 9],
+    zero SAME padding; cbias None: no convolution bias.  `valid` (device int32 scalar): GLU rows past it read as zeros, output rows past it are
+    zeros.  Returns (s, gl, c): with `save` the masked GLU output and the convolution output the backward needs, else two Nones."""
+    _cc(u, "convmod_bn.u"); _cc(w, "convmod_bn.w")
+    if act not in CONVMOD_BN_ACTS:
+        raise DynError(f"convmod_bn: act={act!r} is not built ({sorted(CONVMOD_BN_ACTS)})")
+    if u.dim() != 3 or u.shape[2] % 2 or w.dim() != 2 or w.shape[0] != u.shape[2] // 2:
+        raise DynError("convmod_bn: u must be [B, T, 2C], w [C, KW]")
+    B, T, C2 = u.shape
+    C = C2 // 2
+    _bn_operands("convmod_bn", C, mean, var, weight, bias)
+    if cbias is not None and cbias.numel() != C:
+        raise DynError(f"convmod_bn: cbias must have C = {C} elements")
+    s = torch.empty(B, T, C, device=u.device, dtype=F32)
+    gl = c = None
+    if save:
+        gl, c = (torch.empty(B, T, C, device=u.device, dtype=F32) for _ in range(2))
+    check(_L().dyn_convmod_bn_fwd(u.data_ptr(), w.data_ptr(), _opt(cbias, "cbias"), mean.data_ptr(), var.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                                  s.data_ptr(), _opt(gl, "gl"), _opt(c, "c"), _valid_ptr(valid, "convmod_bn"), B, T, C, w.shape[1],
+                                  CONVMOD_BN_ACTS[act], eps, _stream()), "dyn_convmod_bn_fwd")
+    return s, gl, c
+
+
+def convmod_bn_bwd_act(c, mean, var, weight, bias, ds, dweight, dbias, dcbias, act="silu", eps=1e-5, valid=None, out=None, wgrad_beta=1.0):
+    """Backward of convmod_bn's activation and BatchNorm: returns dc [B, T, C] = ds * act'(bn) * weight * rstd (`out` may be ds), and
+    accumulates dweight / dbias / dcbias = wgrad_beta * old + their column sums (None: frozen, not computed).  Rows past `valid`: dc = 0, left
+    out of the sums."""
+    _cc(c, "convmod_bn_bwd_act.c"); _cc(ds, "convmod_bn_bwd_act.ds")
+    if act not in CONVMOD_BN_ACTS:
+        raise DynError(f"convmod_bn_bwd_act: act={act!r} is not built ({sorted(CONVMOD_BN_ACTS)})")
+    if c.dim() != 3 or ds.shape != c.shape:
+        raise DynError("convmod_bn_bwd_act: c and ds must be [B, T, C]")
+    B, T, C = c.shape
+    _bn_operands("convmod_bn_bwd_act", C, mean, var, weight, bias)
+    for n, t in (("dweight", dweight), ("dbias", dbias), ("dcbias", dcbias)):
+        if t is not None and _cc(t, f"convmod_bn_bwd_act.{n}").numel() != C:
+            raise DynError(f"convmod_bn_bwd_act: {n} must have C = {C} elements")
+    out = torch.empty_like(ds) if out is None else _cc(out, "convmod_bn_bwd_act.out")
+    if out.shape != ds.shape:
+        raise DynError("convmod_bn_bwd_act: out must have the shape of ds")
+    ws = workspace(c.device)
+    check(_L().dyn_convmod_bn_bwd_act(c.data_ptr(), mean.data_ptr(), var.data_ptr(), weight.data_ptr(), bias.data_ptr(), ds.data_ptr(),
+                                      out.data_ptr(), _opt(dweight, "dweight"), _opt(dbias, "dbias"), _opt(dcbias, "dcbias"), wgrad_beta,
+                                      _valid_ptr(valid, "convmod_bn_bwd_act"), B, T, C, CONVMOD_BN_ACTS[act], eps, ws.data_ptr(), ws.numel(),
+                                      _stream()), "dyn_convmod_bn_bwd_act")
+    return out
+
+
+def glu_dwconv1d_dgrad(u, w, dc, valid=None, out=None):
+    """du [B, T, 2C] = GLU'(u) * (the input gradient of the SAME-padded depthwise convolution w [C, 9] from dc [B, T, C]) in one pass; rows past
+    `valid` are zeros."""
+    _cc(u, "glu_dwconv1d_dgrad.u"); _cc(w, "glu_dwconv1d_dgrad.w"); _cc(dc, "glu_dwconv1d_dgrad.dc")
+    if u.dim() != 3 or dc.dim() != 3 or u.shape[:2] != dc.shape[:2] or u.shape[2] != 2 * dc.shape[2] or w.dim() != 2 or w.shape[0] != dc.shape[2]:
+        raise DynError("glu_dwconv1d_dgrad: u must be [B, T, 2C], dc [B, T, C], w [C, KW]")
+    B, T, C = dc.shape
+    out = torch.empty_like(u) if out is None else _cc(out, "glu_dwconv1d_dgrad.out")
+    if out.shape != u.shape or out.data_ptr() in (u.data_ptr(), dc.data_ptr()):
+        raise DynError("glu_dwconv1d_dgrad: out must have the shape of u and alias neither u nor dc")
+    check(_L().dyn_glu_dwconv1d_dgrad(u.data_ptr(), w.data_ptr(), dc.data_ptr(), out.data_ptr(), _valid_ptr(valid, "glu_dwconv1d_dgrad"), B, T, C,
+                                      w.shape[1], _stream()), "dyn_glu_dwconv1d_dgrad")
+    return out
+
+
+def _sub_act(act, what):
+    if act not in SUBSAMPLING_ACTS:
+        raise DynError(f"{what}: act={act!r} is not built ({sorted(SUBSAMPLING_ACTS)})")
+    return SUBSAMPLING_ACTS[act]
+
+
+def dwconv2d_s2_act(z, w, bias, act, out=None):
+    """u = bias + dw3x3_s2(act(z)), act "silu" (ops.dwconv2d_s2) or "relu"; z [B, T, F, C] -> [B, To, Fo, C]; w [C, 3, 3]."""
+    a = _sub_act(act, "dwconv2d_s2_act")
+    _cc(z, "dwconv2d_s2_act.z"); _cc(w, "dwconv2d_s2_act.w"); _cc(bias, "dwconv2d_s2_act.bias")
+    B, T, F, C = z.shape
+    if out is None:
+        out = torch.empty(B, out_len(T), out_len(F), C, device=z.device, dtype=F32)
+    check(_L().dyn_dwconv2d_s2_fwd_act(z.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, T, F, C, a, _stream()),
+          "dyn_dwconv2d_s2_fwd_act")
+    return out
+
+
+def dwconv2d_s2_dgrad_act(z, w, du, act, out=None):
+    a = _sub_act(act, "dwconv2d_s2_dgrad_act")
+    _cc(z, "dwconv2d_s2_dgrad_act.z"); _cc(du, "dwconv2d_s2_dgrad_act.du"); _cc(w, "dwconv2d_s2_dgrad_act.w")
+    B, T, F, C = z.shape
+    out = torch.empty_like(z) if out is None else _cc(out, "dwconv2d_s2_dgrad_act.out")
+    check(_L().dyn_dwconv2d_s2_dgrad_act(z.data_ptr(), w.data_ptr(), du.data_ptr(), out.data_ptr(), B, T, F, C, a, _stream()),
+          "dyn_dwconv2d_s2_dgrad_act")
+    return out
+
+
+def dwconv2d_s2_wgrad_act(z, du, dw, dbias, act, beta=1.0):
+    a = _sub_act(act, "dwconv2d_s2_wgrad_act")
+    _cc(z, "dwconv2d_s2_wgrad_act.z"); _cc(du, "dwconv2d_s2_wgrad_act.du"); _cc(dw, "dwconv2d_s2_wgrad_act.dw"); _cc(dbias, "dwconv2d_s2_wgrad_act.dbias")
+    B, T, F, C = z.shape
+    ws = workspace(z.device)
+    check(_L().dyn_dwconv2d_s2_wgrad_act(z.data_ptr(), du.data_ptr(), dw.data_ptr(), dbias.data_ptr(), beta, B, T, F, C, a, ws.data_ptr(),
+                                         ws.numel(), _stream()), "dyn_dwconv2d_s2_wgrad_act")
+
+
+def relu(x, out=None):
+    _cc(x, "relu.x")
+    out = torch.empty_like(x) if out is None else _cc(out, "relu.out")
+    check(_L().dyn_relu_fwd(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "dyn_relu_fwd")
+    return out
+
+
+def relu_bwd(x, dy, out=None):
+    """dx = dy where x > 0, else 0 (x: the activation's INPUT, or its output: the masks agree); out may be dy."""
+    _cc(x, "relu_bwd.x"); _cc(dy, "relu_bwd.dy")
+    out = torch.empty_like(dy) if out is None else _cc(out, "relu_bwd.out")
+    check(_L().dyn_relu_bwd(x.data_ptr(), dy.data_ptr(), out.data_ptr(), x.numel(), _stream()), "dyn_relu_bwd")
+    return out

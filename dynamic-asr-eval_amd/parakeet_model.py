@@ -1,0 +1,386 @@
+"""ParakeetForCTC on MI355X: the FastConformer encoder + CTC head of the `nvidia/parakeet-ctc-*` checkpoints (`model_type: "parakeet_ctc"`,
+transformers modeling_parakeet.py), the model family of the reference's third loop (nvidia_ctc/lib.py: NVIDIA's conformer-CTC models), as
+`AutoModelForCTC` builds it in plain torch.  Eval mode, no attention mask: what the reference loop runs (it sets `layer.conv.eval()`, zeroes
+every dropout and reads the batch norm's running statistics, nvidia_ctc/lib.py:89-102).
+
+A subclass of Wav2Vec2ConformerForCTC: the two half-step FFNs, Transformer-XL attention with per-head `bias_u` / `bias_v` and a bias-free
+position projection (csrc/relshift.hip), the five attention products (_attn.py), the layer loop, flat parameters and the backward's deferred
+reductions are the parent's, found under the parent's names through an alias table (LAYER_NAMES, as sew_d_model.py does).  What differs:
+  * input: `input_features` [B, T, num_mel_bins] log-mel frames, as transformers takes them; no waveform front end (the reference computes
+    its spectrogram outside the loop, nvidia_ctc/lib.py:20-28).
+  * subsampling (ParakeetEncoderSubsamplingConv2D, x8 `dw_striding`): Conv2d(1 -> C, 3, s2) -> ReLU -> 2 x [depthwise Conv2d(C, 3, s2) -> 1x1
+    -> ReLU] -> flatten -> Linear(C F / 8 -> H).  The stage structure of the project's own conformer (csrc/conv.hip) with ReLU fused into
+    the depthwise loads (ops.dwconv2d_s2_*_act) and ops.relu in front of the flatten; the unfused stages (the reference freezes this part,
+    and its windows are 2048 frames).  The channels-last kernels flatten as (F, C), transformers as (C, F): the linear's weight lives in the
+    kernels' order in the flat vector, its columns are permuted in state_dict() / load_state_dict() / grads_hf() (SUBLIN).
+  * `scale_input`: the hidden states are multiplied by sqrt(hidden_size) after the subsampling linear, bias included.
+  * position table: ParakeetEncoderRelPositionalEncoding.forward restated on the host in its own dtypes and operation order
+    (position_table); ops.relative_position_table forms the angles differently and is not used.  Cached per frame count.
+  * optional biases: `attention_bias` (q / k / v / o projections and both FFNs) and `convolution_bias` (the conv module's three convs) may
+    each be false; the biases are then null pointers and absent from the state dict.
+  * conv module: LN -> pointwise_conv1 -> [GLU -> depthwise conv (9 taps, SAME, optional bias) -> BatchNorm1d (eval) -> SiLU] ->
+    pointwise_conv2, the bracket one launch forward and two backward (csrc/convmod_bn.hip: ops.convmod_bn, convmod_bn_bwd_act,
+    glu_dwconv1d_dgrad) + the existing ops.dwconv1d_wgrad.  A backward keeps u, gl and c of the bracket instead of g, gl, dw, bn.
+  * no `encoder.layer_norm`; the head is `ctc_head`, a k = 1 Conv1d = a linear.
+  * the batch-norm buffers live outside the flat vector (`buffers_`), as in the parent.
+
+Not built, refused by name before any launch: `subsampling_factor` != 8, `subsampling_conv_kernel_size` != 3, `subsampling_conv_stride` != 2,
+`subsampling_conv_channels` not a multiple of 4, `num_mel_bins` not a multiple of 8, `hidden_size` outside 256 / 512 / 768 / 1024,
+`conv_kernel_size` != 9, `hidden_act` != "silu", `num_key_value_heads` != `num_attention_heads`, a `head_dim` other than hidden_size / heads,
+an `attention_mask` argument.  Bucketed hipGraph replay, lockstep groups, ParakeetForRNNT / ForTDT are out of scope.  No hub checkpoint is on
+the machine: transformers' ParakeetForCTC on the CPU with the same (random) state dict is the oracle in the tests."""
+import math
+from types import SimpleNamespace
+
+import torch
+
+from . import ops
+from . import wav2vec2_conformer_model as WC
+from . import wav2vec2_model as W2
+
+ENCODER_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "hidden_act", "attention_bias",
+                "convolution_bias", "conv_kernel_size", "subsampling_factor", "subsampling_conv_channels", "num_mel_bins",
+                "subsampling_conv_kernel_size", "subsampling_conv_stride", "max_position_embeddings", "scale_input", "num_key_value_heads",
+                "head_dim")
+DEFAULT_CONFIG = dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=8, intermediate_size=4096, hidden_act="silu",
+                      attention_bias=True, convolution_bias=True, conv_kernel_size=9, subsampling_factor=8, subsampling_conv_channels=256,
+                      num_mel_bins=80, subsampling_conv_kernel_size=3, subsampling_conv_stride=2, max_position_embeddings=5000,
+                      scale_input=True, num_key_value_heads=None, head_dim=None, vocab_size=1025, pad_token_id=1024, layer_norm_eps=1e-5)
+WIDTHS = (256, 512, 768, 1024)         # instances of dyn_convmod_bn_* (and of the LayerNorm kernels)
+CONV_KERNEL = 9
+BN_EPS = 1e-5                          # nn.BatchNorm1d's default; the per-layer LayerNorms have torch's default too (WC.LAYER_EPS)
+# the parent's name of a layer's parameter group -> transformers' (ParakeetEncoderBlock)
+LAYER_NAMES = (("ffn1_layer_norm", "norm_feed_forward1"), ("ffn1.intermediate_dense", "feed_forward1.linear1"),
+               ("ffn1.output_dense", "feed_forward1.linear2"), ("self_attn_layer_norm", "norm_self_att"),
+               ("self_attn.linear_out", "self_attn.o_proj"), ("self_attn.linear_pos", "self_attn.relative_k_proj"),
+               ("ffn2_layer_norm", "norm_feed_forward2"), ("ffn2.intermediate_dense", "feed_forward2.linear1"),
+               ("ffn2.output_dense", "feed_forward2.linear2"), ("final_layer_norm", "norm_out"))
+SUB = "encoder.subsampling."
+FROZEN_IN_THE_LOOP = (SUB, "ctc_head.")          # nvidia_ctc/lib.py:81-86: pre_encode and the decoder do not adapt
+
+
+def _flatten(cfg):
+    """A ParakeetCTCConfig (or its dict, `encoder_config` nested; or a flat dict) -> one flat dict of the keys this module reads."""
+    if cfg is None:
+        return {}
+    get = (lambda o, k: o.get(k, None)) if isinstance(cfg, dict) else (lambda o, k: getattr(o, k, None))
+    enc = get(cfg, "encoder_config")
+    out = {}
+    for src in (cfg, enc):
+        if src is None:
+            continue
+        g = (lambda k, s=src: s.get(k, None)) if isinstance(src, dict) else (lambda k, s=src: getattr(s, k, None))
+        for k in ENCODER_KEYS + ("vocab_size", "pad_token_id"):
+            if src is not cfg and k in ("vocab_size", "pad_token_id"):
+                continue
+            v = g(k)
+            if v is not None:
+                out[k] = v
+    return out
+
+
+def make_config(cfg=None):
+    """transformers' ParakeetCTCConfig / ParakeetEncoderConfig keys with their defaults; what this forward does not build is refused by name."""
+    out = W2.make_config(_flatten(cfg), DEFAULT_CONFIG)
+    out["do_stable_layer_norm"] = False
+    out["position_embeddings_type"] = "relative"             # the parent's switch: Transformer-XL scores
+    out["conv_kernel"], out["conv_stride"], out["conv_dim"] = (), (), ()     # no waveform conv stack (_conv_extractor = False)
+    if out["subsampling_factor"] != 8:
+        raise ops.DynError(f"subsampling_factor={out['subsampling_factor']} is not built (8: three stride-2 stages)")
+    if out["subsampling_conv_kernel_size"] != 3:
+        raise ops.DynError(f"subsampling_conv_kernel_size={out['subsampling_conv_kernel_size']} is not built (3)")
+    if out["subsampling_conv_stride"] != 2:
+        raise ops.DynError(f"subsampling_conv_stride={out['subsampling_conv_stride']} is not built (2)")
+    C, F = out["subsampling_conv_channels"], out["num_mel_bins"]
+    if not (isinstance(C, int) and C > 0 and C % 4 == 0):
+        raise ops.DynError(f"subsampling_conv_channels={C!r} is not built: the channels-last conv kernels take a positive multiple of 4")
+    if not (isinstance(F, int) and F > 0 and F % 8 == 0):
+        raise ops.DynError(f"num_mel_bins={F!r} is not built: a positive multiple of 8 (transformers' num_mel_bins // 8 columns per channel "
+                           "are the conv stages' only then)")
+    H, nh = out["hidden_size"], out["num_attention_heads"]
+    if H not in WIDTHS:
+        raise ops.DynError(f"hidden_size={H} is not built: one of {WIDTHS}")
+    k = out["conv_kernel_size"] = int(out["conv_kernel_size"])
+    if k != CONV_KERNEL:
+        raise ops.DynError(f"conv_kernel_size={k} is not built ({CONV_KERNEL})")
+    if out["hidden_act"] != "silu":
+        raise ops.DynError(f"hidden_act={out['hidden_act']!r} is not built (\"silu\")")
+    if H % nh:
+        raise ops.DynError(f"hidden_size={H} is not a multiple of num_attention_heads={nh}")
+    kv = out["num_key_value_heads"]
+    if kv is not None and kv != nh:
+        raise ops.DynError(f"num_key_value_heads={kv} is not built: it must equal num_attention_heads={nh}")
+    hd = out["head_dim"]
+    if hd is not None and hd != H // nh:
+        raise ops.DynError(f"head_dim={hd} is not built: it must equal hidden_size / num_attention_heads = {H // nh}")
+    out["num_key_value_heads"], out["head_dim"] = nh, H // nh
+    out["attention_bias"], out["convolution_bias"], out["scale_input"] = (bool(out[k]) for k in ("attention_bias", "convolution_bias", "scale_input"))
+    return out
+
+
+def config_from_json(path):
+    """An HF `config.json` of a parakeet_ctc checkpoint -> make_config."""
+    import json
+    with open(path) as f:
+        src = json.load(f)
+    if not isinstance(src, dict):
+        raise ops.DynError(f"{path}: expected a JSON object")
+    return make_config(src)
+
+
+def frames(T):
+    """Encoder frames of T feature frames: three 3-wide, stride-2, pad-1 stages (transformers' _get_subsampling_output_length)."""
+    for _ in range(3):
+        T = ops.out_len(T)
+    return T
+
+
+def position_table(T, H):
+    """ParakeetEncoderRelPositionalEncoding.forward for T frames of width H on the host, in its dtypes and operation order: [2T - 1, H]
+    float32, positions T - 1 .. -(T - 1), sin / cos interleaved."""
+    if not isinstance(T, int) or T < 1:
+        raise ops.DynError(f"position_table: T={T!r} must be a positive integer")
+    inv_freq = 1.0 / (10000.0 ** (torch.arange(0, H, 2, dtype=torch.float) / H))
+    position_ids = torch.arange(T - 1, -T, -1)
+    freqs = (inv_freq[None, :, None].float() @ position_ids[None, None, :].float()).transpose(1, 2)
+    pe = torch.stack([freqs.sin(), freqs.cos()], dim=-1)
+    return pe.reshape(*pe.shape[:-2], -1)[0].contiguous()
+
+
+def sublin_to_hf(t, C, F3):
+    """The subsampling linear's weight (or gradient) from the kernels' column order (f, c) to transformers' (c, f)."""
+    return t.reshape(t.shape[0], F3, C).permute(0, 2, 1).reshape(t.shape[0], C * F3).contiguous()
+
+
+def sublin_from_hf(t, C, F3):
+    return t.reshape(t.shape[0], C, F3).permute(0, 2, 1).reshape(t.shape[0], F3 * C).contiguous()
+
+
+def param_spec(c, pf=""):
+    """[(name, shape, kind)] in transformers' names.  kind "pw": a k = 1 Conv1d kernel kept as [C_out, C_in]; "dw": a depthwise kernel kept
+    without its singleton input-channel axis ([C, k] / [C, 3, 3]); "pw2": a 1x1 Conv2d kernel kept as [C, C] (all reshapes); "sublin": the
+    subsampling linear, columns in the kernels' (f, c) order."""
+    H, I, k, nh = c["hidden_size"], c["intermediate_size"], c["conv_kernel_size"], c["num_attention_heads"]
+    C, F3 = c["subsampling_conv_channels"], c["num_mel_bins"] // 8
+    ab, cb = c["attention_bias"], c["convolution_bias"]
+    lin = lambda p, n, m, b=True, kind=None: [(p + ".weight", (n, m), kind)] + ([(p + ".bias", (n,), None)] if b else [])           # noqa: E731
+    ln = lambda p: [(p + ".weight", (H,), None), (p + ".bias", (H,), None)]                                                            # noqa: E731
+    s = pf + SUB
+    spec = [(s + "layers.0.weight", (C, 3, 3), "dw"), (s + "layers.0.bias", (C,), None)]
+    for i in (2, 5):
+        spec += [(s + f"layers.{i}.weight", (C, 3, 3), "dw"), (s + f"layers.{i}.bias", (C,), None)]
+        spec += lin(s + f"layers.{i + 1}", C, C, kind="pw2")
+    spec += lin(s + "linear", H, C * F3, kind="sublin")
+    for l in range(c["num_hidden_layers"]):
+        p = f"{pf}encoder.layers.{l}."
+        spec += ln(p + "norm_feed_forward1") + lin(p + "feed_forward1.linear1", I, H, ab) + lin(p + "feed_forward1.linear2", H, I, ab)
+        spec += ln(p + "norm_self_att")
+        spec += [(p + f"self_attn.{n}_proj.weight", (H, H), None) for n in "qkv"]                  # q | k | v side by side
+        spec += [(p + f"self_attn.{n}_proj.bias", (H,), None) for n in "qkv"] if ab else []
+        spec += lin(p + "self_attn.o_proj", H, H, ab)
+        spec += [(p + "self_attn.relative_k_proj.weight", (H, H), None), (p + "self_attn.bias_u", (nh, H // nh), None),
+                 (p + "self_attn.bias_v", (nh, H // nh), None)]
+        spec += ln(p + "norm_conv") + lin(p + "conv.pointwise_conv1", 2 * H, H, cb, "pw")
+        spec += [(p + "conv.depthwise_conv.weight", (H, k), "dw")] + ([(p + "conv.depthwise_conv.bias", (H,), None)] if cb else [])
+        spec += ln(p + "conv.norm") + lin(p + "conv.pointwise_conv2", H, H, cb, "pw")
+        spec += ln(p + "norm_feed_forward2") + lin(p + "feed_forward2.linear1", I, H, ab) + lin(p + "feed_forward2.linear2", H, I, ab)
+        spec += ln(p + "norm_out")
+    return spec + [(pf + "ctc_head.weight", (c["vocab_size"], H), "pw"), (pf + "ctc_head.bias", (c["vocab_size"],), None)]
+
+
+def buffer_spec(c, pf=""):
+    """[(name, shape, dtype)] of the batch norms' buffers, in transformers' names."""
+    out = []
+    for l in range(c["num_hidden_layers"]):
+        p = f"{pf}encoder.layers.{l}.conv.norm."
+        out += [(p + "running_mean", (c["hidden_size"],), torch.float32), (p + "running_var", (c["hidden_size"],), torch.float32),
+                (p + "num_batches_tracked", (), torch.int64)]
+    return out
+
+
+class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
+    _input = "input_features"
+    _prefix = ""
+    _qkv_fmt = "self_attn.{}_proj"
+    _make_config = staticmethod(make_config)
+    _param_spec = staticmethod(param_spec)
+    _norm_weight_suffixes = ("norm_feed_forward1.weight", "norm_feed_forward2.weight", "norm_self_att.weight", "norm_conv.weight", "norm_out.weight",
+                             "conv.norm.weight")               # run_wav2vec2.init_synthetic starts these around 1
+    _conv_extractor = False                                    # log-mel features, no waveform conv stack
+
+    def __init__(self, config=None, device="cuda:0"):
+        super().__init__(config, device)
+        c = self.cfg
+        self._alias = {}
+        for l in range(c["num_hidden_layers"]):                # the parent's layer code finds every parameter under the name it uses;
+            p = f"encoder.layers.{l}."                         # a bias this configuration does not have is None there (a null pointer)
+            for theirs, ours in LAYER_NAMES:
+                for leaf in ("weight", "bias"):
+                    a, b = f"{p}{theirs}.{leaf}", f"{p}{ours}.{leaf}"
+                    if theirs == "self_attn.linear_pos" and leaf == "bias":
+                        continue
+                    self.P[a], self.G[a] = self.P.get(b), self.G.get(b)
+                    self._alias[a] = b
+            for theirs, ours in (("self_attn.pos_bias_u", "self_attn.bias_u"), ("self_attn.pos_bias_v", "self_attn.bias_v")):
+                self.P[p + theirs], self.G[p + theirs] = self.P[p + ours], self.G[p + ours]
+                self._alias[p + theirs] = p + ours
+        self.n_mels, self.C, self.F3 = c["num_mel_bins"], c["subsampling_conv_channels"], c["num_mel_bins"] // 8
+        self.input_scale = math.sqrt(c["hidden_size"]) if c["scale_input"] else 1.0
+
+    def trainable(self, name):
+        return super().trainable(getattr(self, "_alias", {}).get(name, name))
+
+    def __call__(self, x=None, **kw):
+        return self.forward(kw.get(self._input, x), attention_mask=kw.get("attention_mask"))
+
+    def _make_buffers(self):
+        return {n: (torch.ones if n.endswith("running_var") else torch.zeros)(shape, device=self.device, dtype=dt)
+                for n, shape, dt in buffer_spec(self.cfg)}
+
+    def _bn(self, l):
+        p = f"encoder.layers.{l}.conv.norm."
+        return self.buffers_[p + "running_mean"], self.buffers_[p + "running_var"]
+
+    def _below_frozen(self):
+        """True when nothing of the subsampling adapts: its backward is then not run at all."""
+        return not any(self.trainable(n) for n, _ in self.spec if n.startswith(SUB))
+
+    # ------------------------------------------------------------------ state dict
+    def _to_hf(self, name, t):
+        kind = self._kind[name]
+        if kind == "pw2":
+            return t.reshape(*t.shape, 1, 1)
+        if kind == "sublin":
+            return sublin_to_hf(t, self.C, self.F3)
+        return super()._to_hf(name, t)                         # "pw" / "dw": the parent's reshapes
+
+    def load_state_dict(self, sd, strict=True):
+        n = SUB + "linear.weight"
+        if n in sd:
+            if tuple(sd[n].shape) != (self.cfg["hidden_size"], self.C * self.F3):
+                raise ops.DynError(f"{n}: shape {tuple(sd[n].shape)} in the state dict does not fit this configuration's "
+                                   f"{(self.cfg['hidden_size'], self.C * self.F3)}")
+            sd = dict(sd)
+            sd[n] = sublin_from_hf(sd[n].to(torch.float32), self.C, self.F3)
+        return super().load_state_dict(sd, strict)
+
+    # ------------------------------------------------------------------ position table
+    def position_table(self, T):
+        """pe [2T - 1, H] of T encoder frames on the device; built on the host the first time T is seen, never inside a capture."""
+        t = self._tables.get(T)
+        if t is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise ops.DynError(f"the position table of {T} frames has to exist before its launch sequence is captured")
+            t = self._tables[T] = position_table(T, self.cfg["hidden_size"]).to(self.device)
+        return t
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, input_features, attention_mask=None):
+        """input_features [B, T, num_mel_bins] float32 on the device -> SimpleNamespace(logits [B, T', V], frames = T'), T' = frames(T).
+        Every row is valid: `attention_mask` is refused."""
+        if attention_mask is not None:
+            raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (the reference loop passes whole windows)")
+        x = input_features
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.n_mels
+                and x.shape[1] >= 1):
+            raise ops.DynError(f"input_features must be a float32 CUDA tensor [B, T, {self.n_mels}]")
+        B, T, _ = x.shape
+        T3 = frames(T)
+        self.position_table(T3)
+        with ops.use_workspace(self._scratch()):
+            self._vl, self._ctx_static = None, False
+            ctx = {"conv": []} if torch.is_grad_enabled() else None
+            h, kept = self._subsample(x.contiguous())
+            if ctx is not None:
+                ctx["sub"] = kept
+            return self._encode(h, ctx, None, (B, T, T3), None)
+
+    def _subsample(self, x):
+        """x [B, T, F] -> (h [B, T', H], what _subsample_bwd needs, batch-major)."""
+        P, s = self.P, SUB
+        z1 = ops.conv2d_first(x, P[s + "layers.0.weight"], P[s + "layers.0.bias"])                       # [B, T1, F1, C], pre-activation
+        u2 = ops.dwconv2d_s2_act(z1, P[s + "layers.2.weight"], P[s + "layers.2.bias"], "relu")
+        z2 = ops.linear(u2, P[s + "layers.3.weight"], P[s + "layers.3.bias"])
+        u3 = ops.dwconv2d_s2_act(z2, P[s + "layers.5.weight"], P[s + "layers.5.bias"], "relu")
+        z3 = ops.linear(u3, P[s + "layers.6.weight"], P[s + "layers.6.bias"])
+        a3 = ops.relu(z3)
+        B, T3, F3, C = a3.shape
+        h = ops.linear(a3.view(B, T3, F3 * C), P[s + "linear.weight"], P[s + "linear.bias"])
+        if self.input_scale != 1.0:                           # (W a + b) * sqrt(H), one rounding, as transformers multiplies the linear's output
+            raw, h = h, h.clone()
+            ops.axpby(raw, h, 0.0, self.input_scale)
+        return h, (x, z1, u2, z2, u3, z3, a3)
+
+    def _subsample_bwd(self, kept, dh):
+        """Accumulates the subsampling's gradients from dh = dL/dh [nb, T', H]; the features are data, so nothing is returned."""
+        P, G, s = self.P, self.G, SUB
+        x, z1, u2, z2, u3, z3, a3 = kept
+        B, T3, F3, C = a3.shape
+        if self.input_scale != 1.0:
+            d = dh.clone()
+            ops.axpby(dh, d, 0.0, self.input_scale)
+            dh = d
+        da3 = self._lin_bwd(dh, a3.view(B, T3, F3 * C), s + "linear.weight", s + "linear.bias")
+        dz3 = ops.relu_bwd(z3, da3.view(z3.shape), out=da3.view(z3.shape))
+        du3 = self._lin_bwd(dz3, u3, s + "layers.6.weight", s + "layers.6.bias")
+        ops.dwconv2d_s2_wgrad_act(z2, du3, G[s + "layers.5.weight"], G[s + "layers.5.bias"], "relu", beta=1.0)
+        dz2 = ops.dwconv2d_s2_dgrad_act(z2, P[s + "layers.5.weight"], du3, "relu")
+        du2 = self._lin_bwd(dz2, u2, s + "layers.3.weight", s + "layers.3.bias")
+        ops.dwconv2d_s2_wgrad_act(z1, du2, G[s + "layers.2.weight"], G[s + "layers.2.bias"], "relu", beta=1.0)
+        dz1 = ops.dwconv2d_s2_dgrad_act(z1, P[s + "layers.2.weight"], du2, "relu")
+        ops.conv2d_first_wgrad(x, dz1, G[s + "layers.0.weight"], G[s + "layers.0.bias"], beta=1.0)
+
+    def _conv_fwd(self, x, l, vT, save):
+        """x + conv_module(x)."""
+        P = self.P
+        p = f"encoder.layers.{l}."
+        n, m, s = ops.layernorm(x, P[p + "norm_conv.weight"], P[p + "norm_conv.bias"], self._layer_eps)
+        u = ops.linear(n, P[p + "conv.pointwise_conv1.weight"], P.get(p + "conv.pointwise_conv1.bias"))
+        mean, var = self._bn(l)
+        w, cb = P[p + "conv.depthwise_conv.weight"], P.get(p + "conv.depthwise_conv.bias")
+        a, gl, cv = ops.convmod_bn(u, w, cb, mean, var, P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], "silu", BN_EPS, valid=vT, save=save)
+        r = x.clone() if save else x
+        ops.linear(a, P[p + "conv.pointwise_conv2.weight"], P.get(p + "conv.pointwise_conv2.bias"), out=r, beta=1.0)
+        return r, (x, m, s, n, u, gl, cv, a)
+
+    def _conv_bwd(self, dr, kept, l, vT):
+        P, G = self.P, self.G
+        p = f"encoder.layers.{l}."
+        x, m, s, n, u, gl, cv, a = kept
+        cbn = p + "conv.depthwise_conv.bias"
+        has_cb = cbn in P
+        b1, b2 = (p + f"conv.pointwise_conv{i}.bias" if has_cb else None for i in (1, 2))
+        da = self._lin_bwd(dr, a, p + "conv.pointwise_conv2.weight", b2)
+        mean, var = self._bn(l)
+        w = P[p + "conv.depthwise_conv.weight"]
+        dc = ops.convmod_bn_bwd_act(cv, mean, var, P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], da, self._g(p + "conv.norm.weight"),
+                                    self._g(p + "conv.norm.bias"), self._g(cbn) if has_cb else None, "silu", BN_EPS, valid=vT, out=da)
+        ops.dwconv1d_wgrad(gl, dc, G[p + "conv.depthwise_conv.weight"], None, beta=1.0)
+        du = ops.glu_dwconv1d_dgrad(u, w, dc, valid=vT)
+        dn = self._lin_bwd(du, n, p + "conv.pointwise_conv1.weight", b1)
+        dx = torch.empty_like(dr)
+        ops.layernorm_bwd(x, P[p + "norm_conv.weight"], m, s, dn, dx, G[p + "norm_conv.weight"], G[p + "norm_conv.bias"], dx_beta=1.0, dx_in=dr)
+        return dx
+
+    def _encode(self, h, ctx, vT, dims, v0):
+        P = self.P
+        T = dims[2]
+        x = self._layers_fwd(h, ctx, vT, self.position_table(T))
+        logits = ops.linear(x, P["ctc_head.weight"], P["ctc_head.bias"])
+        if ctx is not None:
+            ctx["head"] = x
+            ctx["dims"] = dims
+            ctx["valid"] = (v0, vT)
+        self._ctx = ctx
+        return SimpleNamespace(logits=logits, frames=T)
+
+    # ------------------------------------------------------------------ backward
+    def _backward_encoder(self, ctx, grad_logits, nb, cut):
+        """ctc_head, the layers and the subsampling; returns None: nothing lies below the subsampling (the features are data)."""
+        v0, vT = ctx["valid"]
+        T = ctx["dims"][2]
+        dx = self._lin_bwd(grad_logits.contiguous(), cut(ctx["head"]), "ctc_head.weight", "ctc_head.bias")
+        dh = self._layers_bwd(ctx, dx, nb, T, self.position_table(T), vT, cut)
+        if not self._below_frozen():
+            self._subsample_bwd(cut(ctx["sub"]), dh)
+        return None

@@ -22,6 +22,7 @@ import time
 
 import torch
 
+from . import ops
 from . import wav2vec2_lib as lib
 from .datasets import fetch_utterances_from_lines, synthetic_text, synthetic_waveform
 from .decoding import GreedyCTCDecoder
@@ -176,6 +177,9 @@ def load_pretrained_model(args, device):
     if ckpt and os.path.isdir(ckpt):
         cfg_path, ckpt = cfg_path or os.path.join(ckpt, 'config.json'), os.path.join(ckpt, 'pytorch_model.bin')
     kind = model_type(cfg_path) if cfg_path else ''         # what AutoModelForCTC dispatches on
+    if kind == 'parakeet_ctc':
+        raise ops.DynError(f'{cfg_path}: model_type "parakeet_ctc" takes log-mel features [B, T, num_mel_bins], not waveforms: build '
+                           'parakeet_model.ParakeetForCTC and drive it with nvidia_ctc_lib.dynamic_eval (the reference\'s nvidia_ctc/lib.py)')
     lang, adapter_sd, tokenizer = getattr(args, 'target_lang', '') or '', None, None
     if lang:
         if kind not in ('', 'wav2vec2') or not (args.checkpoint and os.path.isdir(args.checkpoint)):

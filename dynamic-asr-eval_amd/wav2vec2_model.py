@@ -214,8 +214,12 @@ class Wav2Vec2ForCTC(FlatModel):
             for l in range(c["num_hidden_layers"]):
                 q, v = self._qv_names(l)
                 ow = slots[f"{q}.weight"][0]
-                ob = slots[f"{q}.bias"][0]
                 assert slots[f"{v}.weight"][0] == ow + 2 * H * H
+                if f"{q}.bias" not in slots:                     # a model of the family whose projections may have no bias (parakeet_model.py)
+                    self.Pqkv.append((self.flat_params[ow:ow + 3 * H * H].view(3 * H, H), None))
+                    self.Gqkv.append((self.flat_grads[ow:ow + 3 * H * H].view(3 * H, H), None))
+                    continue
+                ob = slots[f"{q}.bias"][0]
                 assert slots[f"{v}.bias"][0] == ob + 2 * H
                 self.Pqkv.append((self.flat_params[ow:ow + 3 * H * H].view(3 * H, H), self.flat_params[ob:ob + 3 * H]))
                 self.Gqkv.append((self.flat_grads[ow:ow + 3 * H * H].view(3 * H, H), self.flat_grads[ob:ob + 3 * H]))

@@ -882,6 +882,52 @@ int dyn_narrow_layernorm_bwd(const float* x, const float* gamma, const float* me
 int dyn_fbank_finish(const float* mel, float* out, int64_t B, int64_t F, int64_t M, float mel_floor, float eps, const int32_t* valid_frames,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Parakeet (`model_type: "parakeet_ctc"`, transformers ParakeetForCTC: the FastConformer encoder of the nvidia/parakeet-ctc checkpoints,
+ * the model family of the reference's nvidia_ctc/lib.py).  fp32, deterministic, no float atomics.
+ *   dyn_convmod_bn_fwd        ParakeetEncoderConvolutionModule.forward between its two pointwise convolutions: `glu`, `depthwise_conv`,
+ *                             `norm` (BatchNorm1d in eval mode: running statistics), `activation` in one launch.
+ *                             u [B, T, 2C] -> s [B, T, C] = act((conv - mean_c) * rsqrt(var_c + eps) * weight_c + bias_c),
+ *                             conv[b,t,c] = cbias_c + sum_j w[c,j] * GLU(u)[b, t - (KW - 1) / 2 + j, c], zero SAME padding; w [C, KW];
+ *                             cbias [C] may be null (convolution_bias = false); mean / var / weight / bias [C]; act 0 = SiLU.
+ *                             valid (device int32 scalar, may be null = T; read when the kernel runs): GLU rows t >= *valid read as
+ *                             zeros.  Optional outputs (null: not written) for the backward: gl the masked GLU output, c the
+ *                             convolution output before BatchNorm, [B, T, C].  Rows >= *valid of s, gl and c are exact zeros.
+ *                             dyn_convmod_bn_time_tile() is the number of frames one workgroup takes (tests).
+ *   dyn_convmod_bn_bwd_act    from c, the BatchNorm constants and ds [B, T, C]: dc = ds * act'(bn) * weight * rstd (dc may be ds), and
+ *                             dweight = wgrad_beta * old + sum ds * act' * xhat, dbias = .. + sum ds * act', dcbias = .. + sum dc over
+ *                             the rows; each of the three may be null (frozen: not computed, nothing written).  Partial rows per
+ *                             workgroup in `workspace`, combined in workgroup order (bit-reproducible, deferrable).  Rows >= *valid
+ *                             give dc = 0 and are left out of the sums.
+ *   dyn_glu_dwconv1d_dgrad    du [B, T, 2C] = GLU'(u) * sum_j w[c,j] * dc[b, t + (KW - 1) / 2 - j, c] (rows of dc outside [0, T) are
+ *                             zeros): the depthwise data gradient and the GLU backward in one pass, no dgl tensor.  Rows >= *valid of
+ *                             du are exact zeros.  du must not alias u or dc.
+ *   The depthwise weight gradient is dyn_dwconv1d_wgrad(gl, dc, ..).
+ *   dyn_dwconv2d_s2_*_act     dyn_dwconv2d_s2_fwd / _dgrad / _wgrad with the activation fused into the loads chosen by the caller:
+ *                             act 0 = SiLU (those entries, bit for bit), 1 = ReLU (Parakeet's dw_striding subsampling; ReLU'(0) = 0).
+ *   dyn_relu_fwd / _bwd       y = max(x, 0); dx = x > 0 ? dy : 0 (in place allowed), n elements, 16-byte aligned.
+ * KW = 9, C in {256, 512, 768, 1024}, act as listed: anything else DYN_E_UNSUPPORTED.  Null pointers, sizes out of range -> DYN_E_ARG, a
+ * short workspace -> DYN_E_WORKSPACE, all before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t dyn_convmod_bn_time_tile(void);
+int dyn_convmod_bn_fwd(const float* u, const float* w, const float* cbias, const float* mean, const float* var, const float* weight,
+                       const float* bias, float* s, float* gl, float* c, const int32_t* valid, int64_t B, int64_t T, int64_t C, int64_t KW,
+                       int32_t act, float eps, void* stream);
+int64_t dyn_convmod_bn_bwd_act_workspace_bytes(int64_t B, int64_t T, int64_t C);
+int dyn_convmod_bn_bwd_act(const float* c, const float* mean, const float* var, const float* weight, const float* bias, const float* ds,
+                           float* dc, float* dweight, float* dbias, float* dcbias, float wgrad_beta, const int32_t* valid, int64_t B,
+                           int64_t T, int64_t C, int32_t act, float eps, void* workspace, int64_t workspace_bytes, void* stream);
+int dyn_glu_dwconv1d_dgrad(const float* u, const float* w, const float* dc, float* du, const int32_t* valid, int64_t B, int64_t T, int64_t C,
+                           int64_t KW, void* stream);
+int dyn_dwconv2d_s2_fwd_act(const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T, int64_t F, int64_t C,
+                            int32_t act, void* stream);
+int dyn_dwconv2d_s2_dgrad_act(const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T, int64_t F, int64_t C,
+                              int32_t act, void* stream);
+int dyn_dwconv2d_s2_wgrad_act(const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B, int64_t T, int64_t F,
+                              int64_t C, int32_t act, void* workspace, int64_t workspace_bytes, void* stream);
+int dyn_relu_fwd(const float* x, float* y, int64_t n, void* stream);
+int dyn_relu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
