@@ -1,5 +1,6 @@
 // Convolutions of the conformer encoder, channels-last so every access is coalesced along C:
-//   * depthwise Conv1d (kernel KW <= 31, 'same' zero padding) of the conformer conv module, fwd / dgrad / wgrad;
+//   * depthwise Conv1d (odd kernel KW <= 31, 'same' zero padding) of the conformer conv module, fwd / dgrad / wgrad; the wgrad also at
+//     KW = 32 (15 | 16 padding, csrc/convmod_bn.hip's 32-tap core);
 //   * the dw_striding x8 subsampling front-end: first 3x3 stride-2 conv (1 -> C channels, direct) and the
 //     3x3 stride-2 depthwise convs with the preceding SiLU fused into the load (pointwise 1x1 convs are GEMMs).
 // These are HBM-bound (a few FLOPs per byte): each thread owns one channel and slides over time so every
@@ -66,12 +67,12 @@ __global__ __launch_bounds__(256) void dwconv1d_kernel(const float* __restrict__
     }
 }
 
-// partial[(tile), j, c] = sum_{t in tile} dy[b,t,c] * x[b, t + j - P, c];   partial_b[(tile), c] = sum dy
+// partial[(tile), j, c] = sum_{t in tile} dy[b,t,c] * x[b, t + j - P, c], j = 0 .. KW - 1;   partial_b[(tile), c] = sum dy
 template <int KW>
 __global__ __launch_bounds__(256) void dwconv1d_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                               float* __restrict__ partial_w, float* __restrict__ partial_b,
                                                               int64_t T, int C, int64_t t_per_block) {
-    constexpr int P = (KW - 1) / 2;
+    constexpr int P = (KW - 1) / 2, PR = KW - 1 - P;      // frames left / right of t; an even KW (32) pads as torch's "same": 15 | 16
     const int c = blockIdx.y * 256 + threadIdx.x;
     if (c >= C) return;
     const int64_t b = blockIdx.z;
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void dwconv1d_wgrad_kernel(const float* __rest
     for (int64_t t = t0; t < t1; ++t) {
 #pragma unroll
         for (int j = 0; j < KW - 1; ++j) win[j] = win[j + 1];
-        const int64_t tn = t + P;
+        const int64_t tn = t + PR;
         win[KW - 1] = tn < T ? xb[tn * C] : 0.f;
         const float g = gb[t * C];
         accb += g;
@@ -831,6 +832,7 @@ static int dwconv1d_wgrad_impl(const float* x, const float* dy, float* dw, float
     switch (KW) {
         case 3: GO(3); break; case 5: GO(5); break; case 7: GO(7); break; case 9: GO(9); break;
         case 15: GO(15); break; case 31: GO(31); break;
+        case 32: GO(32); break;      // the forward-direction correlation is right at an even width (P | PR above); the flipped entries are not built there
         default: dyn::set_error("dwconv1d_wgrad: unsupported kernel width %lld", (long long)KW); return DYN_E_UNSUPPORTED;
     }
 #undef GO

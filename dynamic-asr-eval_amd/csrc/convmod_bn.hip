@@ -1,16 +1,21 @@
 // The core of Parakeet's (FastConformer) convolution module (transformers modeling_parakeet.py, ParakeetEncoderConvolutionModule.forward):
 //     glu -> depthwise_conv (KW taps, zero SAME padding, optional bias) -> BatchNorm1d in eval mode (running statistics) -> activation
-// between the two pointwise convolutions (GEMMs).  KW = 9, C in {256, 512, 768, 1024}, channels-last, fp32.
+// between the two pointwise convolutions (GEMMs).  KW = 9 (Parakeet) or 32 (LASR / MedASR), C in {256, 512, 768, 1024}, channels-last, fp32.
+// An even KW pads as torch's padding="same" does: HL = (KW - 1) / 2 frames on the left, HR = KW - 1 - HL on the right (15 | 16 at 32 taps);
+// the data gradient's halo is the mirror image (HR left, HL right).  The two are separate compile-time quantities in every kernel below.
 //
 //   dyn_convmod_bn_fwd       u [B, T, 2C] -> s [B, T, C] = act((conv - mean_c) * rsqrt(var_c + eps) * weight_c + bias_c),
-//                            conv[b, t, c] = cbias_c + sum_j w[c, j] * GLU(u)[b, t - (KW - 1) / 2 + j, c], in ONE launch.
+//                            conv[b, t, c] = cbias_c + sum_j w[c, j] * GLU(u)[b, t - HL + j, c], in ONE launch.
 //     Thread = channel.  A thread loads its channel's TT + KW - 1 GLU values ONCE into registers
 //     (statically indexed) and forms its TT outputs from them.  BatchNorm with fixed statistics is per channel: no row reduction, so no
-//     LDS stage and no barrier.  A GLU value is computed (TT + KW - 1) / TT = 1.5 times at TT = 16.
+//     LDS stage and no barrier.  A GLU value is computed (TT + KW - 1) / TT = 1.5 times at 9 taps (TT = 16), 1.97 times at 32 taps
+//     (TT = 32: a 63-float window, 116 VGPRs, 4 waves per SIMD, no scratch).  The other tiling tried at 32 taps, the tile's GLU rows formed
+//     once into LDS (63 KB, 2 waves per SIMD) and a thread sliding over its column, gave equal bits and was 16 % / 38 % slower at
+//     [5, 509, 512] / [5, 2048, 512] (the LASR section): not kept.
 //   dyn_convmod_bn_bwd_act   dc = ds * act'(bn) * weight * rstd and the three column sums (dweight, dbias, dcbias) as per-workgroup
 //                            partial rows, rows visited in a fixed order, combined by the fixed-order reducer (reduce.h; deferrable).
-//   dyn_glu_dwconv1d_dgrad   du = GLU'(u) * sum_j w[c, j] * dc[t + (KW - 1) / 2 - j]: the register window of the forward over dc, the GLU
-//                            backward applied to the sum before it is stored; no dgl tensor exists.
+//   dyn_glu_dwconv1d_dgrad   du = GLU'(u) * sum_j w[c, j] * dc[t + HL - j]: the register window of the forward over dc (it starts HR frames
+//                            to the left), the GLU backward applied to the sum before it is stored; no dgl tensor exists.
 // `valid` (device int32 scalar, may be null): GLU rows t >= *valid read as zeros (what SAME padding holds there in the unpadded run) and
 // rows >= *valid of every output are exact zeros / left out of the sums.  No float atomics: every result is bit-reproducible.
 #include "common.h"
@@ -18,8 +23,9 @@
 
 namespace {
 
-constexpr int KW9 = 9;
-constexpr int TT = 16;        // frames per workgroup of the forward and the dgrad
+constexpr int KW9 = 9, KW32 = 32;
+constexpr int TT9 = 16;       // frames per workgroup of the 9-tap forward and dgrad
+constexpr int TT32 = 32;      // ... of the 32-tap ones
 constexpr int ACT_SILU = 0;
 
 __device__ __forceinline__ float silu_f(float x) { return x * dyn::sigmoidf_(x); }
@@ -29,14 +35,14 @@ __device__ __forceinline__ float silu_grad(float x) {
 }
 
 // grid (ceil(T / TT), C / 256, B); 256 threads, thread = channel.
-template <int KW>
+template <int KW, int TT>
 __global__ __launch_bounds__(256) void convmod_bn_fwd_kernel(const float* __restrict__ u, const float* __restrict__ w,
                                                               const float* __restrict__ cbias, const float* __restrict__ mean,
                                                               const float* __restrict__ var, const float* __restrict__ weight,
                                                               const float* __restrict__ bias, float* __restrict__ s,
                                                               float* __restrict__ gl_out, float* __restrict__ c_out,
                                                               const int32_t* __restrict__ valid, int64_t T, int C, float eps) {
-    constexpr int HALF = (KW - 1) / 2, NG = TT + KW - 1;
+    constexpr int HL = (KW - 1) / 2, HR = KW - 1 - HL, NG = TT + HL + HR;      // frames read left / right of the tile
     const int c = blockIdx.y * 256 + threadIdx.x;
     const int64_t b = blockIdx.z, t0 = (int64_t)blockIdx.x * TT;
     const int64_t vr = dyn::valid_rows(valid, T);
@@ -47,7 +53,7 @@ __global__ __launch_bounds__(256) void convmod_bn_fwd_kernel(const float* __rest
     const float* ub = u + b * T * 2 * C + c;
 #pragma unroll
     for (int i = 0; i < NG; ++i) {
-        const int64_t t = t0 - HALF + i;
+        const int64_t t = t0 - HL + i;
         g[i] = (t >= 0 && t < vr) ? ub[t * 2 * C] * dyn::sigmoidf_(ub[t * 2 * C + C]) : 0.f;
     }
 #pragma unroll
@@ -63,7 +69,7 @@ __global__ __launch_bounds__(256) void convmod_bn_fwd_kernel(const float* __rest
             sv = silu_f((cv - mu) * rs * gw + sh);
         }
         s[o] = sv;
-        if (gl_out) gl_out[o] = g[k + HALF];            // rows >= valid hold zeros in the window already
+        if (gl_out) gl_out[o] = g[k + HL];              // rows >= valid hold zeros in the window already
         if (c_out) c_out[o] = cv;
     }
 }
@@ -98,21 +104,22 @@ __global__ __launch_bounds__(256) void convmod_bn_bwd_act_kernel(const float* __
 }
 
 // grid (ceil(T / TT), C / 256, B); 256 threads, thread = channel.
-template <int KW>
+template <int KW, int TT>
 __global__ __launch_bounds__(256) void glu_dwconv1d_dgrad_kernel(const float* __restrict__ u, const float* __restrict__ w,
                                                                   const float* __restrict__ dc, float* __restrict__ du,
                                                                   const int32_t* __restrict__ valid, int64_t T, int C) {
-    constexpr int HALF = (KW - 1) / 2, NG = TT + KW - 1;
+    constexpr int HL = (KW - 1) / 2, HR = KW - 1 - HL;      // the forward's halos
+    constexpr int DL = HR, DR = HL, NG = TT + DL + DR;      // the data gradient's: dc[t + HL - j], j = 0 .. KW - 1, reaches HR back and HL ahead
     const int c = blockIdx.y * 256 + threadIdx.x;
     const int64_t b = blockIdx.z, t0 = (int64_t)blockIdx.x * TT;
     const int64_t vr = dyn::valid_rows(valid, T);
     float wk[KW], g[NG];
 #pragma unroll
-    for (int j = 0; j < KW; ++j) wk[j] = w[(int64_t)c * KW + (KW - 1 - j)];      // flipped: dgl[t] = sum_i wk[i] * dc[t - HALF + i]
+    for (int j = 0; j < KW; ++j) wk[j] = w[(int64_t)c * KW + (KW - 1 - j)];      // flipped: dgl[t] = sum_i wk[i] * dc[t - DL + i]
     const float* gb = dc + b * T * C + c;
 #pragma unroll
     for (int i = 0; i < NG; ++i) {
-        const int64_t t = t0 - HALF + i;
+        const int64_t t = t0 - DL + i;
         g[i] = (t >= 0 && t < T) ? gb[t * C] : 0.f;
     }
     const float* ub = u + b * T * 2 * C + c;
@@ -139,7 +146,7 @@ inline int bwd_blocks(int64_t rows) { return (int)(rows < 1 ? 1 : rows > 512 ? 5
 
 int check_dims(const char* who, int64_t B, int64_t T, int64_t C, int64_t KW) {
     DYN_REQUIRE(B >= 0 && T >= 0 && B < 65536 && B * T < (1ll << 31), DYN_E_ARG, "%s: bad sizes B=%lld T=%lld", who, (long long)B, (long long)T);
-    DYN_REQUIRE(KW == KW9, DYN_E_UNSUPPORTED, "%s: kernel width %lld is not built (9)", who, (long long)KW);
+    DYN_REQUIRE(KW == KW9 || KW == KW32, DYN_E_UNSUPPORTED, "%s: kernel width %lld is not built (9, 32)", who, (long long)KW);
     DYN_REQUIRE(C == 256 || C == 512 || C == 768 || C == 1024, DYN_E_UNSUPPORTED, "%s: C=%lld is not built (256, 512, 768, 1024)", who,
                 (long long)C);
     return DYN_OK;
@@ -147,7 +154,9 @@ int check_dims(const char* who, int64_t B, int64_t T, int64_t C, int64_t KW) {
 
 }  // namespace
 
-extern "C" int64_t dyn_convmod_bn_time_tile(void) { return TT; }
+extern "C" int64_t dyn_convmod_bn_time_tile(void) { return TT9; }
+
+extern "C" int64_t dyn_convmod_bn_time_tile_kw(int64_t KW) { return KW == KW9 ? TT9 : KW == KW32 ? TT32 : 0; }
 
 extern "C" int dyn_convmod_bn_fwd(const float* u, const float* w, const float* cbias, const float* mean, const float* var, const float* weight,
                                   const float* bias, float* s, float* gl, float* c, const int32_t* valid, int64_t B, int64_t T, int64_t C,
@@ -156,9 +165,11 @@ extern "C" int dyn_convmod_bn_fwd(const float* u, const float* w, const float* c
     if (int rc = check_dims("dyn_convmod_bn_fwd", B, T, C, KW)) return rc;
     DYN_REQUIRE(act == ACT_SILU, DYN_E_UNSUPPORTED, "dyn_convmod_bn_fwd: act=%d is not built (0 SiLU)", (int)act);
     if (B == 0 || T == 0) return DYN_OK;
-    const dim3 grid((unsigned)dyn::cdiv(T, TT), (unsigned)(C / 256), (unsigned)B);
-    hipLaunchKernelGGL((convmod_bn_fwd_kernel<KW9>), grid, dim3(256), 0, (hipStream_t)stream, u, w, cbias, mean, var, weight, bias, s, gl, c,
-                       valid, T, (int)C, eps);
+    const dim3 grid((unsigned)dyn::cdiv(T, KW == KW9 ? TT9 : TT32), (unsigned)(C / 256), (unsigned)B);
+#define GO(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, (hipStream_t)stream, u, w, cbias, mean, var, weight, bias, s, gl, c, valid, T, (int)C, eps)
+    if (KW == KW9) GO((convmod_bn_fwd_kernel<KW9, TT9>));
+    else GO((convmod_bn_fwd_kernel<KW32, TT32>));
+#undef GO
     return dyn::check_launch("dyn_convmod_bn_fwd");
 }
 
@@ -200,7 +211,10 @@ extern "C" int dyn_glu_dwconv1d_dgrad(const float* u, const float* w, const floa
     if (int rc = check_dims("dyn_glu_dwconv1d_dgrad", B, T, C, KW)) return rc;
     DYN_REQUIRE(du != u && du != dc, DYN_E_ARG, "dyn_glu_dwconv1d_dgrad: du must not alias u or dc");
     if (B == 0 || T == 0) return DYN_OK;
-    const dim3 grid((unsigned)dyn::cdiv(T, TT), (unsigned)(C / 256), (unsigned)B);
-    hipLaunchKernelGGL((glu_dwconv1d_dgrad_kernel<KW9>), grid, dim3(256), 0, (hipStream_t)stream, u, w, dc, du, valid, T, (int)C);
+    const dim3 grid((unsigned)dyn::cdiv(T, KW == KW9 ? TT9 : TT32), (unsigned)(C / 256), (unsigned)B);
+#define GO(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, (hipStream_t)stream, u, w, dc, du, valid, T, (int)C)
+    if (KW == KW9) GO((glu_dwconv1d_dgrad_kernel<KW9, TT9>));
+    else GO((glu_dwconv1d_dgrad_kernel<KW32, TT32>));
+#undef GO
     return dyn::check_launch("dyn_glu_dwconv1d_dgrad");
 }

@@ -2,7 +2,8 @@
 path: the chunked `dynamic_eval_ctc_loss` / `dynamic_eval` (:35-193) and `apply_args` (:206-221).
 
 Same call signature; `model` is this package's ParakeetForCTC (parakeet_model.py), the FastConformer-CTC architecture as transformers
-restates it, so no NeMo is needed.  The loop follows wav2vec2_lib.dynamic_eval_ctc_loss statement for statement; what differs, as in the
+restates it, so no NeMo is needed, or a model of its family that says what the loop has to know about it (lasr_model.LasrForCTC: the
+attributes `downsampling_factor` and `frozen_in_the_loop`, read by loop_constants below).  The loop follows wav2vec2_lib.dynamic_eval_ctc_loss statement for statement; what differs, as in the
 reference:
   * `spec` [1, n_mels, T] is a spectrogram, computed outside the loop (nvidia_ctc/lib.py:20-28), cut into windows along T (:116-125); every
     copy is transposed to [T, n_mels] on the device, the layout transformers' model takes;
@@ -10,11 +11,12 @@ reference:
     host torch RNG (`args.spec_augment_generator`, a torch.Generator, when given).  The reference's SpecAugment comes from an un-vendored
     package: the draw rule is augment.py's (parity unpinned, as for the other loops);
   * Adam (optim.Adam: one fused launch over the flat vector);
-  * `pre_encode` and the decoder do not adapt (:81-86): `encoder.subsampling.` and `ctc_head.` are in `model.frozen` for the duration of the
-    call (`pos_enc` has no parameters), so their backward is not run at all;
+  * `pre_encode` and the decoder do not adapt (:81-86): the model's `frozen_in_the_loop` prefixes (Parakeet: `encoder.subsampling.` and
+    `ctc_head.`) are in `model.frozen` for the duration of the call (`pos_enc` has no parameters), so their backward is not run at all;
   * the conv modules' BatchNorm reads its running statistics (:89-102): the model is the eval-mode model;
   * blank = `tokenizer.vocab_size`, greedy pseudo-labels from the clean last copy, `CTCLoss(reduction="sum") / (N * B)`, probability-space
-    stitching with a downsampling factor of 8 (:165-187); parameters and the `frozen` set are restored on exit (:189-191).
+    stitching by the window's own ratio of input to output frames (:165-187; the model's `downsampling_factor`, 8 for Parakeet, is what the
+    overlap must be a multiple of, :110); parameters and the `frozen` set are restored on exit (:189-191).
 The tokenizer is NeMo's surface: `vocab_size` (an attribute), `ids_to_text`, `text_to_ids`; SyntheticTokenizer is the stand-in for seeded
 weights."""
 import random
@@ -26,7 +28,6 @@ from ._loop import Stitcher, window_fill_value
 from .augment import SpecAugment
 from .decoding import GreedyCTCDecoder
 from .optim import MADGRAD, Adam  # noqa: F401
-from .parakeet_model import FROZEN_IN_THE_LOOP
 
 try:
     from tqdm import tqdm
@@ -64,24 +65,42 @@ class SentencePieceAdapter:
         return self.tokenizer.text_to_ids(text)
 
 
+DOWNSAMPLING_FACTOR = 8                                      # nvidia_ctc/lib.py:60, and
+FROZEN_IN_THE_LOOP = ("encoder.subsampling.", "ctc_head.")   # :81-86 for the FastConformer the reference drives: the defaults below
+
+
+def loop_constants(model):
+    """(downsampling factor, parameter-name prefixes frozen for the duration of the loop) of `model` (an instance or its class): its
+    `downsampling_factor` / `frozen_in_the_loop` attributes, or the reference's own constants for a model that does not say."""
+    factor = int(getattr(model, "downsampling_factor", DOWNSAMPLING_FACTOR))
+    frozen = tuple(getattr(model, "frozen_in_the_loop", FROZEN_IN_THE_LOOP))
+    if factor < 1 or not all(isinstance(p, str) and p for p in frozen):
+        raise ops.DynError(f"{type(model).__name__}: downsampling_factor={factor!r} / frozen_in_the_loop={frozen!r} are not a positive integer and "
+                           "non-empty parameter-name prefixes")
+    return factor, frozen
+
+
 def disable_dropout(model):
     """reference nvidia_ctc/lib.py:30-33 — the model has no dropout modules (eval-mode forward)."""
     return model
 
 
 def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=Adam, num_negatives=4, lr_args={'lr': 1e-8},
-                          spec_augment_config=SPEC_AUGMENT_CONFIG, return_device=False):
-    """reference nvidia_ctc/lib.py:35-193: spectrogram windows, SpecAugment on the first copies, Adam, stitching of exp(log_p[-1])."""
+                          spec_augment_config=SPEC_AUGMENT_CONFIG, return_device=False, downsampling_factor=None, frozen_prefixes=None):
+    """reference nvidia_ctc/lib.py:35-193: spectrogram windows, SpecAugment on the first copies, Adam, stitching of exp(log_p[-1]).
+    `downsampling_factor` / `frozen_prefixes`: given, they take the place of what loop_constants reads from the model."""
     device = model.device
     spec = spec.to(device=device, dtype=torch.float32)                                           # [1, F, T]
     if spec.dim() != 3 or spec.shape[0] != 1:
         raise ops.DynError(f"spec must be [1, n_mels, T], got {tuple(spec.shape)}")
     Fq, spec_n = spec.shape[1], spec.shape[-1]
-    downsampling_factor = 8
+    factor, frozen = loop_constants(model)
+    downsampling_factor = factor if downsampling_factor is None else int(downsampling_factor)
+    frozen = frozen if frozen_prefixes is None else tuple(frozen_prefixes)
     model = disable_dropout(model)
     original = model.flat_params.clone()                                                         # lib.py:63-64
     was_frozen = model.frozen
-    model.frozen = set(was_frozen) | set(FROZEN_IN_THE_LOOP)                                     # lib.py:81-86
+    model.frozen = set(was_frozen) | set(frozen)                                     # lib.py:81-86
     try:
         blank = tokenizer.vocab_size                                                             # lib.py:66,71
         decoder = GreedyCTCDecoder(tokenizer=SentencePieceAdapter(tokenizer), blank_id=blank, device=device)

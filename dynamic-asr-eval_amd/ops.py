@@ -886,9 +886,17 @@ def conv2d_first_dgrad(dz, w, T, F):
 
 
 # ----------------------------------------------------------------------------------------------- convolutions
+def _odd_width(who, w):
+    """The plain depthwise kernels pad (KW - 1) / 2 frames on both sides, and their data gradient is the flipped forward: both are right at
+    an odd width only.  (The 32-tap conv module goes through convmod_bn / glu_dwconv1d_dgrad, which carry the two halos apart.)"""
+    if w.shape[-1] % 2 == 0:
+        raise DynError(f"{who}: an even kernel width ({w.shape[-1]}) is not built: SAME padding is asymmetric there")
+
+
 def dwconv1d(x, w, bias, out=None):
     """x [B, T, C] channels-last, w [C, KW]."""
     _cc(x, "dwconv1d.x"); _cc(w, "dwconv1d.w")
+    _odd_width("dwconv1d", w)
     B, T, C = x.shape
     out = torch.empty_like(x) if out is None else _cc(out, "dwconv1d.out")
     check(_L().dyn_dwconv1d_fwd(x.data_ptr(), w.data_ptr(), _opt(bias, "bias"), out.data_ptr(), B, T, C, w.shape[1], _stream()),
@@ -898,6 +906,7 @@ def dwconv1d(x, w, bias, out=None):
 
 def dwconv1d_dgrad(dy, w, out=None, beta=0.0):
     _cc(dy, "dwconv1d_dgrad.dy")
+    _odd_width("dwconv1d_dgrad", w)
     B, T, C = dy.shape
     out = torch.empty_like(dy) if out is None else _cc(out, "dwconv1d_dgrad.out")
     if _is_group(w):
@@ -1861,9 +1870,17 @@ CONVMOD_BN_ACTS = {"silu": 0, "swish": 0}
 SUBSAMPLING_ACTS = {"silu": 0, "relu": 1}
 
 
-def convmod_bn_time_tile():
-    """Frames per workgroup of the conv-module kernels below (tests place their edges around it)."""
-    return int(_L().dyn_convmod_bn_time_tile())
+CONVMOD_BN_WIDTHS = (9, 32)        # instances of dyn_convmod_bn_fwd / dyn_glu_dwconv1d_dgrad
+
+
+def convmod_bn_time_tile(kw=None):
+    """Frames per workgroup of the conv-module kernels below (tests place their edges around it): of the 9-tap instances, or of `kw` taps."""
+    if kw is None:
+        return int(_L().dyn_convmod_bn_time_tile())
+    tt = int(_L().dyn_convmod_bn_time_tile_kw(int(kw)))
+    if tt <= 0:
+        raise DynError(f"convmod_bn_time_tile: kernel width {kw} is not built {CONVMOD_BN_WIDTHS}")
+    return tt
 
 
 def _bn_operands(what, C, mean, var, weight, bias):
@@ -1874,8 +1891,8 @@ def _bn_operands(what, C, mean, var, weight, bias):
 
 
 def convmod_bn(u, w, cbias, mean, var, weight, bias, act="silu", eps=1e-5, valid=None, save=False):
-    """Parakeet's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = act(BatchNorm_eval(cbias + depthwise conv(GLU(u)))), w [C, 9],
-    zero SAME padding; cbias None: no convolution bias.  `valid` (device int32 scalar): GLU rows past it read as zeros, output rows past it are
+    """Parakeet's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = act(BatchNorm_eval(cbias + depthwise conv(GLU(u)))), w [C, 9]
+    or [C, 32] (LASR; 15 frames of padding left, 16 right, as torch's padding="same"), zero SAME padding; cbias None: no convolution bias.  `valid` (device int32 scalar): GLU rows past it read as zeros, output rows past it are
     zeros.  Returns (s, gl, c): with `save` the masked GLU output and the convolution output the backward needs, else two Nones."""
     _cc(u, "convmod_bn.u"); _cc(w, "convmod_bn.w")
     if act not in CONVMOD_BN_ACTS:
@@ -1923,7 +1940,7 @@ def convmod_bn_bwd_act(c, mean, var, weight, bias, ds, dweight, dbias, dcbias, a
 
 
 def glu_dwconv1d_dgrad(u, w, dc, valid=None, out=None):
-    """du [B, T, 2C] = GLU'(u) * (the input gradient of the SAME-padded depthwise convolution w [C, 9] from dc [B, T, C]) in one pass; rows past
+    """du [B, T, 2C] = GLU'(u) * (the input gradient of the SAME-padded depthwise convolution w [C, 9] or [C, 32] from dc [B, T, C]) in one pass; rows past
     `valid` are zeros."""
     _cc(u, "glu_dwconv1d_dgrad.u"); _cc(w, "glu_dwconv1d_dgrad.w"); _cc(dc, "glu_dwconv1d_dgrad.dc")
     if u.dim() != 3 or dc.dim() != 3 or u.shape[:2] != dc.shape[:2] or u.shape[2] != 2 * dc.shape[2] or w.dim() != 2 or w.shape[0] != dc.shape[2]:

@@ -59,8 +59,9 @@ SUB = "encoder.subsampling."
 FROZEN_IN_THE_LOOP = (SUB, "ctc_head.")          # nvidia_ctc/lib.py:81-86: pre_encode and the decoder do not adapt
 
 
-def _flatten(cfg):
-    """A ParakeetCTCConfig (or its dict, `encoder_config` nested; or a flat dict) -> one flat dict of the keys this module reads."""
+def _flatten(cfg, keys=ENCODER_KEYS):
+    """A ParakeetCTCConfig (or its dict, `encoder_config` nested; or a flat dict) -> one flat dict of the keys this module reads (`keys`: the
+    encoder keys of another model of the family, lasr_model.py)."""
     if cfg is None:
         return {}
     get = (lambda o, k: o.get(k, None)) if isinstance(cfg, dict) else (lambda o, k: getattr(o, k, None))
@@ -70,7 +71,7 @@ def _flatten(cfg):
         if src is None:
             continue
         g = (lambda k, s=src: s.get(k, None)) if isinstance(src, dict) else (lambda k, s=src: getattr(s, k, None))
-        for k in ENCODER_KEYS + ("vocab_size", "pad_token_id"):
+        for k in tuple(keys) + ("vocab_size", "pad_token_id"):
             if src is not cfg and k in ("vocab_size", "pad_token_id"):
                 continue
             v = g(k)
@@ -207,6 +208,11 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
     _norm_weight_suffixes = ("norm_feed_forward1.weight", "norm_feed_forward2.weight", "norm_self_att.weight", "norm_conv.weight", "norm_out.weight",
                              "conv.norm.weight")               # run_wav2vec2.init_synthetic starts these around 1
     _conv_extractor = False                                    # log-mel features, no waveform conv stack
+    # what a model of the family (lasr_model.py) replaces: the alias tables, and what nvidia_ctc_lib.dynamic_eval reads from its model
+    _layer_names = LAYER_NAMES
+    _head_bias_names = (("self_attn.pos_bias_u", "self_attn.bias_u"), ("self_attn.pos_bias_v", "self_attn.bias_v"))
+    downsampling_factor = 8                                    # nvidia_ctc/lib.py:110: the overlap must be a multiple of it
+    frozen_in_the_loop = FROZEN_IN_THE_LOOP
 
     def __init__(self, config=None, device="cuda:0"):
         super().__init__(config, device)
@@ -214,18 +220,18 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
         self._alias = {}
         for l in range(c["num_hidden_layers"]):                # the parent's layer code finds every parameter under the name it uses;
             p = f"encoder.layers.{l}."                         # a bias this configuration does not have is None there (a null pointer)
-            for theirs, ours in LAYER_NAMES:
+            for theirs, ours in self._layer_names:
                 for leaf in ("weight", "bias"):
                     a, b = f"{p}{theirs}.{leaf}", f"{p}{ours}.{leaf}"
                     if theirs == "self_attn.linear_pos" and leaf == "bias":
                         continue
                     self.P[a], self.G[a] = self.P.get(b), self.G.get(b)
                     self._alias[a] = b
-            for theirs, ours in (("self_attn.pos_bias_u", "self_attn.bias_u"), ("self_attn.pos_bias_v", "self_attn.bias_v")):
+            for theirs, ours in self._head_bias_names:
                 self.P[p + theirs], self.G[p + theirs] = self.P[p + ours], self.G[p + ours]
                 self._alias[p + theirs] = p + ours
         self.n_mels, self.C, self.F3 = c["num_mel_bins"], c["subsampling_conv_channels"], c["num_mel_bins"] // 8
-        self.input_scale = math.sqrt(c["hidden_size"]) if c["scale_input"] else 1.0
+        self.input_scale = math.sqrt(c["hidden_size"]) if c.get("scale_input", False) else 1.0
 
     def trainable(self, name):
         return super().trainable(getattr(self, "_alias", {}).get(name, name))

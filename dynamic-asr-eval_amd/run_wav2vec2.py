@@ -180,6 +180,9 @@ def load_pretrained_model(args, device):
     if kind == 'parakeet_ctc':
         raise ops.DynError(f'{cfg_path}: model_type "parakeet_ctc" takes log-mel features [B, T, num_mel_bins], not waveforms: build '
                            'parakeet_model.ParakeetForCTC and drive it with nvidia_ctc_lib.dynamic_eval (the reference\'s nvidia_ctc/lib.py)')
+    if kind == 'lasr_ctc':
+        raise ops.DynError(f'{cfg_path}: model_type "lasr_ctc" takes log-mel features [B, T, num_mel_bins], not waveforms: build '
+                           'lasr_model.LasrForCTC and drive it with nvidia_ctc_lib.dynamic_eval (the reference\'s nvidia_ctc/lib.py)')
     lang, adapter_sd, tokenizer = getattr(args, 'target_lang', '') or '', None, None
     if lang:
         if kind not in ('', 'wav2vec2') or not (args.checkpoint and os.path.isdir(args.checkpoint)):

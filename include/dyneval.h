@@ -889,27 +889,33 @@ int dyn_fbank_finish(const float* mel, float* out, int64_t B, int64_t F, int64_t
  *                             `norm` (BatchNorm1d in eval mode: running statistics), `activation` in one launch.
  *                             u [B, T, 2C] -> s [B, T, C] = act((conv - mean_c) * rsqrt(var_c + eps) * weight_c + bias_c),
  *                             conv[b,t,c] = cbias_c + sum_j w[c,j] * GLU(u)[b, t - (KW - 1) / 2 + j, c], zero SAME padding; w [C, KW];
+ *                             an even KW pads as torch's padding="same": (KW - 1) / 2 = 15 frames left, 16 right at KW = 32;
  *                             cbias [C] may be null (convolution_bias = false); mean / var / weight / bias [C]; act 0 = SiLU.
  *                             valid (device int32 scalar, may be null = T; read when the kernel runs): GLU rows t >= *valid read as
  *                             zeros.  Optional outputs (null: not written) for the backward: gl the masked GLU output, c the
  *                             convolution output before BatchNorm, [B, T, C].  Rows >= *valid of s, gl and c are exact zeros.
- *                             dyn_convmod_bn_time_tile() is the number of frames one workgroup takes (tests).
+ *                             dyn_convmod_bn_time_tile() is the number of frames one workgroup takes at 9 taps,
+ *                             dyn_convmod_bn_time_tile_kw(KW) at KW taps (0: KW is not built) (tests).
  *   dyn_convmod_bn_bwd_act    from c, the BatchNorm constants and ds [B, T, C]: dc = ds * act'(bn) * weight * rstd (dc may be ds), and
  *                             dweight = wgrad_beta * old + sum ds * act' * xhat, dbias = .. + sum ds * act', dcbias = .. + sum dc over
  *                             the rows; each of the three may be null (frozen: not computed, nothing written).  Partial rows per
  *                             workgroup in `workspace`, combined in workgroup order (bit-reproducible, deferrable).  Rows >= *valid
  *                             give dc = 0 and are left out of the sums.
  *   dyn_glu_dwconv1d_dgrad    du [B, T, 2C] = GLU'(u) * sum_j w[c,j] * dc[b, t + (KW - 1) / 2 - j, c] (rows of dc outside [0, T) are
- *                             zeros): the depthwise data gradient and the GLU backward in one pass, no dgl tensor.  Rows >= *valid of
- *                             du are exact zeros.  du must not alias u or dc.
- *   The depthwise weight gradient is dyn_dwconv1d_wgrad(gl, dc, ..).
+ *                             zeros): the depthwise data gradient and the GLU backward in one pass, no dgl tensor.  Its halo mirrors
+ *                             the forward's: 16 frames back and 15 ahead at KW = 32.  Rows >= *valid of du are exact zeros.  du must
+ *                             not alias u or dc.
+ *   The depthwise weight gradient is dyn_dwconv1d_wgrad(gl, dc, ..), built at KW = 32 too (dw[c,j] = sum_t dc[t] * gl[t + j - 15]); the plain
+ *   depthwise entries dyn_dwconv1d_fwd / _dgrad / _dgrad_g stay refused at even widths.
  *   dyn_dwconv2d_s2_*_act     dyn_dwconv2d_s2_fwd / _dgrad / _wgrad with the activation fused into the loads chosen by the caller:
  *                             act 0 = SiLU (those entries, bit for bit), 1 = ReLU (Parakeet's dw_striding subsampling; ReLU'(0) = 0).
  *   dyn_relu_fwd / _bwd       y = max(x, 0); dx = x > 0 ? dy : 0 (in place allowed), n elements, 16-byte aligned.
- * KW = 9, C in {256, 512, 768, 1024}, act as listed: anything else DYN_E_UNSUPPORTED.  Null pointers, sizes out of range -> DYN_E_ARG, a
+ * KW = 9 (Parakeet) or 32 (LASR: `model_type: "lasr_ctc"`, transformers LasrForCTC, google/medasr), C in {256, 512, 768, 1024}, act as
+ * listed: anything else DYN_E_UNSUPPORTED.  Null pointers, sizes out of range -> DYN_E_ARG, a
  * short workspace -> DYN_E_WORKSPACE, all before any launch.
  * ------------------------------------------------------------------------------------------------ */
 int64_t dyn_convmod_bn_time_tile(void);
+int64_t dyn_convmod_bn_time_tile_kw(int64_t KW);
 int dyn_convmod_bn_fwd(const float* u, const float* w, const float* cbias, const float* mean, const float* var, const float* weight,
                        const float* bias, float* s, float* gl, float* c, const int32_t* valid, int64_t B, int64_t T, int64_t C, int64_t KW,
                        int32_t act, float eps, void* stream);
