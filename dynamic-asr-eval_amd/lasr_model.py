@@ -1,6 +1,8 @@
 """LasrForCTC on MI355X: the conformer encoder + CTC head of google/medasr (`model_type: "lasr_ctc"`, transformers modeling_lasr.py), the
 second model family of the reference's third loop (nvidia_ctc/lib.py driven through nvidia_ctc_lib.dynamic_eval), as `AutoModelForCTC`
-builds it in plain torch.  Eval mode, no attention mask: what the loop runs.
+builds it in plain torch.  No attention mask; the conv modules' norm reads its running statistics by default (eval mode).  The reference loop
+itself replaces that norm by a training-mode BatchRenorm1d (nvidia_ctc/lib.py:74,89-102): ParakeetForCTC.batch_renorm_training(), inherited
+here at 32 taps, runs it; eval mode remains the default until a maintainer flips it.
 
 transformers derives LasrForCTC from ParakeetForCTC, and so does this module: flat parameters, the batch-norm buffers outside the flat
 vector, the alias table that lets Wav2Vec2ConformerForCTC's layer loop find every parameter under the name it uses (LAYER_NAMES), the
@@ -353,25 +355,22 @@ class LasrForCTC(PM.ParakeetForCTC):
         p = f"encoder.layers.{l}."
         n, m, s = ops.layernorm(x, P[p + "norm_conv.weight"], None, self._layer_eps)
         u = ops.linear(n, P[p + "conv.pointwise_conv1.weight"], P.get(p + "conv.pointwise_conv1.bias"))
-        mean, var = self._bn(l)
         w, cb = P[p + "conv.depthwise_conv.weight"], P.get(p + "conv.depthwise_conv.bias")
-        a, gl, cv = ops.convmod_bn(u, w, cb, mean, var, P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], "silu", BN_EPS, valid=vT, save=save)
+        a, gl, cv, st = self._convmod(l, u, w, cb, p, vT, save)
         r = self._weighted_out(x, a, p + "conv.pointwise_conv2.weight", p + "conv.pointwise_conv2.bias", self.conv_weights, save)
-        return r, (x, m, s, n, u, gl, cv, a)
+        return r, (x, m, s, n, u, gl, cv, a, st)
 
     def _conv_bwd(self, dr, kept, l, vT):
         P, G = self.P, self.G
         p = f"encoder.layers.{l}."
-        x, m, s, n, u, gl, cv, a = kept
+        x, m, s, n, u, gl, cv, a, st = kept
         cbn = p + "conv.depthwise_conv.bias"
         has_cb = cbn in P
         b1, b2 = (p + f"conv.pointwise_conv{i}.bias" if has_cb else None for i in (1, 2))
         d = self._branch_grad(dr, self.conv_weights[1])
         da = self._lin_bwd(d, a, p + "conv.pointwise_conv2.weight", b2)
-        mean, var = self._bn(l)
         w = P[p + "conv.depthwise_conv.weight"]
-        dc = ops.convmod_bn_bwd_act(cv, mean, var, P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], da, self._g(p + "conv.norm.weight"),
-                                    self._g(p + "conv.norm.bias"), self._g(cbn) if has_cb else None, "silu", BN_EPS, valid=vT, out=da)
+        dc = self._convmod_bwd(l, cv, st, da, p, cbn, has_cb, vT)
         ops.dwconv1d_wgrad(gl, dc, G[p + "conv.depthwise_conv.weight"], None, beta=1.0)
         du = ops.glu_dwconv1d_dgrad(u, w, dc, valid=vT)
         dn = self._lin_bwd(du, n, p + "conv.pointwise_conv1.weight", b1)

@@ -13,12 +13,20 @@ reference:
   * Adam (optim.Adam: one fused launch over the flat vector);
   * `pre_encode` and the decoder do not adapt (:81-86): the model's `frozen_in_the_loop` prefixes (Parakeet: `encoder.subsampling.` and
     `ctc_head.`) are in `model.frozen` for the duration of the call (`pos_enc` has no parameters), so their backward is not run at all;
-  * the conv modules' BatchNorm reads its running statistics (:89-102): the model is the eval-mode model;
+  * the conv modules' norm.  The reference calls `model.train()` (:74), puts `layer.conv` and its batch norm into eval mode (:92-93) and then
+    REPLACES that batch norm by a fresh BatchRenorm1d(momentum=0.001, eps=1e-5) (:94-102), which is in training mode: at every step it
+    normalises with the statistics of the batch (augmented copies and the clean one), corrects them towards the running statistics by the
+    detached r / d (num_batches_tracked = 1000000 saturates the clamps at 3 / 5, :97; running_std = sqrt(running_var), :101), moves the
+    running statistics, and the gradient flows through the batch mean and deviation into every row.  `batch_renorm=True` (or
+    `args.batch_renorm`) runs exactly that (model.batch_renorm_training(), csrc/convmod_brn.hip; BatchRenorm1d is un-vendored: the
+    `batchrenorm` package form, parity unpinned against upstream `lcasr`).  The DEFAULT is still the eval-mode norm reading its running
+    statistics, until a maintainer flips it;
   * blank = `tokenizer.vocab_size`, greedy pseudo-labels from the clean last copy, `CTCLoss(reduction="sum") / (N * B)`, probability-space
     stitching by the window's own ratio of input to output frames (:165-187; the model's `downsampling_factor`, 8 for Parakeet, is what the
     overlap must be a multiple of, :110); parameters and the `frozen` set are restored on exit (:189-191).
 The tokenizer is NeMo's surface: `vocab_size` (an attribute), `ids_to_text`, `text_to_ids`; SyntheticTokenizer is the stand-in for seeded
 weights."""
+import contextlib
 import random
 
 import torch
@@ -65,6 +73,7 @@ class SentencePieceAdapter:
         return self.tokenizer.text_to_ids(text)
 
 
+BATCH_RENORM = dict(momentum=0.001, eps=1e-5, num_batches_tracked=1000000)      # nvidia_ctc/lib.py:94-97
 DOWNSAMPLING_FACTOR = 8                                      # nvidia_ctc/lib.py:60, and
 FROZEN_IN_THE_LOOP = ("encoder.subsampling.", "ctc_head.")   # :81-86 for the FastConformer the reference drives: the defaults below
 
@@ -86,9 +95,16 @@ def disable_dropout(model):
 
 
 def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, use_tqdm=True, optim=Adam, num_negatives=4, lr_args={'lr': 1e-8},
-                          spec_augment_config=SPEC_AUGMENT_CONFIG, return_device=False, downsampling_factor=None, frozen_prefixes=None):
+                          spec_augment_config=SPEC_AUGMENT_CONFIG, return_device=False, downsampling_factor=None, frozen_prefixes=None,
+                          batch_renorm=None):
     """reference nvidia_ctc/lib.py:35-193: spectrogram windows, SpecAugment on the first copies, Adam, stitching of exp(log_p[-1]).
-    `downsampling_factor` / `frozen_prefixes`: given, they take the place of what loop_constants reads from the model."""
+    `downsampling_factor` / `frozen_prefixes`: given, they take the place of what loop_constants reads from the model.
+    `batch_renorm` (None: `args.batch_renorm`, False when absent): True runs the loop inside model.batch_renorm_training() with the
+    reference's constants (:94-102) and hands the backward a gradient for all B rows, zeros for the clean copy, since the training-mode
+    norm carries it into every row.  The state (running statistics, counters) is dropped on exit, so the model's buffers are restored
+    trivially: they are never written."""
+    if batch_renorm is None:
+        batch_renorm = bool(args.__dict__.get('batch_renorm', False))
     device = model.device
     spec = spec.to(device=device, dtype=torch.float32)                                           # [1, F, T]
     if spec.dim() != 3 or spec.shape[0] != 1:
@@ -101,7 +117,10 @@ def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, use_tq
     original = model.flat_params.clone()                                                         # lib.py:63-64
     was_frozen = model.frozen
     model.frozen = set(was_frozen) | set(frozen)                                     # lib.py:81-86
+    mode = contextlib.ExitStack()
     try:
+        if batch_renorm:
+            mode.enter_context(model.batch_renorm_training(**BATCH_RENORM))                      # lib.py:74,89-102
         blank = tokenizer.vocab_size                                                             # lib.py:66,71
         decoder = GreedyCTCDecoder(tokenizer=SentencePieceAdapter(tokenizer), blank_id=blank, device=device)
         augmentation = SpecAugment(**spec_augment_config)
@@ -153,13 +172,19 @@ def dynamic_eval_ctc_loss(args, model, spec, seq_len, overlap, tokenizer, use_tq
                 ilen = torch.full((nb,), N, dtype=torch.int32, device=device); tlen = torch.full((nb,), S, dtype=torch.int32, device=device)
                 _, _, g_lp = ops.ctc_loss(aug, targets, ilen, tlen, blank, reduction="sum", grad_scale=1.0 / (N * nb))   # lib.py:149-152
                 optimizer.zero_grad()
-                model.backward(ops.log_softmax_bwd(aug, g_lp), n_active=num_negatives)           # lib.py:155-156
+                if batch_renorm:                                                                 # every row takes part in the batch statistics
+                    g_all = torch.zeros_like(log_p)
+                    g_all[:num_negatives].copy_(g_lp)
+                    model.backward(ops.log_softmax_bwd(log_p, g_all), n_active=B)
+                else:
+                    model.backward(ops.log_softmax_bwd(aug, g_lp), n_active=num_negatives)       # lib.py:155-156
                 optimizer.step()                                                                 # lib.py:160
                 outputs[i] = (log_p[-1, :N], u_len)                                              # lib.py:165-170
         for i in sorted(outputs):                                                                # lib.py:174-187
             stitch.add(i, *outputs[i], overlap)
         logits = stitch.finalize()
     finally:
+        mode.close()
         model.flat_params.copy_(original)                                                        # lib.py:189-191
         model.frozen = was_frozen
     return logits if return_device else logits.cpu().numpy()

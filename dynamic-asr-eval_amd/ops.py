@@ -1954,6 +1954,69 @@ def glu_dwconv1d_dgrad(u, w, dc, valid=None, out=None):
     return out
 
 
+def batch_renorm_clamps(num_batches_tracked):
+    """(rmax, dmax) of BatchRenorm1d's schedule at `num_batches_tracked` (the value BEFORE the forward's increment): host arithmetic,
+    rmax = clamp(2 / 35000 * n + 25 / 35, 1, 3), dmax = clamp(5 / 20000 * n - 25 / 20, 0, 5).  (1, 0) at 0: plain training-mode batch norm;
+    (3, 5) from 40000 / 25000 on, so at the reference's 1000000 (nvidia_ctc/lib.py:97)."""
+    n = float(num_batches_tracked)
+    return min(max(2.0 / 35000.0 * n + 25.0 / 35.0, 1.0), 3.0), min(max(5.0 / 20000.0 * n - 25.0 / 20.0, 0.0), 5.0)
+
+
+def convmod_brn_stats_rows():
+    return int(_L().dyn_convmod_brn_stats_rows())
+
+
+def convmod_brn(u, w, cbias, running_mean, running_std, weight, bias, rmax, dmax, momentum, act="silu", eps=1e-5, valid=None):
+    """The conv-module core with BatchRenorm1d in TRAINING mode (reference nvidia_ctc/lib.py:74,89-102; the `batchrenorm` package form, parity
+    unpinned against upstream `lcasr`): u [B, T, 2C] -> s = act(weight * ((x - mu) / sig * r + d) + bias), x = cbias + depthwise conv(GLU(u)),
+    mu / sig = std + eps the statistics of the batch's B * valid rows, r / d the clamped (rmax, dmax) corrections towards running_mean /
+    running_std, which then move IN PLACE by `momentum` (0: untouched).  Returns (s, gl, c, stats): gl, c as convmod_bn's, stats [7, C] =
+    mu, 1 / sig, r, d, scale, shift, 1 / std for convmod_brn_bwd.  A channel of zero batch variance is outside the contract."""
+    _cc(u, "convmod_brn.u"); _cc(w, "convmod_brn.w")
+    if act not in CONVMOD_BN_ACTS:
+        raise DynError(f"convmod_brn: act={act!r} is not built ({sorted(CONVMOD_BN_ACTS)})")
+    if u.dim() != 3 or u.shape[2] % 2 or w.dim() != 2 or w.shape[0] != u.shape[2] // 2:
+        raise DynError("convmod_brn: u must be [B, T, 2C], w [C, KW]")
+    B, T, C2 = u.shape
+    C = C2 // 2
+    _bn_operands("convmod_brn", C, running_mean, running_std, weight, bias)
+    if cbias is not None and cbias.numel() != C:
+        raise DynError(f"convmod_brn: cbias must have C = {C} elements")
+    s, gl, c = (torch.empty(B, T, C, device=u.device, dtype=F32) for _ in range(3))
+    stats = torch.empty(convmod_brn_stats_rows(), C, device=u.device, dtype=F32)
+    ws = workspace(u.device)
+    check(_L().dyn_convmod_brn_fwd(u.data_ptr(), w.data_ptr(), _opt(cbias, "cbias"), running_mean.data_ptr(), running_std.data_ptr(),
+                                   weight.data_ptr(), bias.data_ptr(), s.data_ptr(), gl.data_ptr(), c.data_ptr(), stats.data_ptr(),
+                                   _valid_ptr(valid, "convmod_brn"), B, T, C, w.shape[1], CONVMOD_BN_ACTS[act], eps, rmax, dmax, momentum,
+                                   ws.data_ptr(), ws.numel(), _stream()), "dyn_convmod_brn_fwd")
+    return s, gl, c, stats
+
+
+def convmod_brn_bwd(c, stats, ds, dweight, dbias, dcbias, act="silu", valid=None, out=None, wgrad_beta=1.0):
+    """Backward of convmod_brn's activation and training-mode BatchRenorm1d through the batch mean and deviation (r, d constants): returns dc
+    [B, T, C] (`out` may be ds) and writes dweight / dbias = wgrad_beta * old + their sums (None: frozen).  dcbias = wgrad_beta * old: the
+    convolution bias cancels in x - mu.  The gradient reaches every row of the batch.  Rows past `valid`: dc = 0, left out of the sums."""
+    _cc(c, "convmod_brn_bwd.c"); _cc(ds, "convmod_brn_bwd.ds"); _cc(stats, "convmod_brn_bwd.stats")
+    if act not in CONVMOD_BN_ACTS:
+        raise DynError(f"convmod_brn_bwd: act={act!r} is not built ({sorted(CONVMOD_BN_ACTS)})")
+    if c.dim() != 3 or ds.shape != c.shape:
+        raise DynError("convmod_brn_bwd: c and ds must be [B, T, C]")
+    B, T, C = c.shape
+    if stats.dim() != 2 or tuple(stats.shape) != (convmod_brn_stats_rows(), C):
+        raise DynError(f"convmod_brn_bwd: stats must be convmod_brn's [{convmod_brn_stats_rows()}, C = {C}]")
+    for n, t in (("dweight", dweight), ("dbias", dbias), ("dcbias", dcbias)):
+        if t is not None and _cc(t, f"convmod_brn_bwd.{n}").numel() != C:
+            raise DynError(f"convmod_brn_bwd: {n} must have C = {C} elements")
+    out = torch.empty_like(ds) if out is None else _cc(out, "convmod_brn_bwd.out")
+    if out.shape != ds.shape:
+        raise DynError("convmod_brn_bwd: out must have the shape of ds")
+    ws = workspace(c.device)
+    check(_L().dyn_convmod_brn_bwd(c.data_ptr(), stats.data_ptr(), ds.data_ptr(), out.data_ptr(), _opt(dweight, "dweight"), _opt(dbias, "dbias"),
+                                   _opt(dcbias, "dcbias"), wgrad_beta, _valid_ptr(valid, "convmod_brn_bwd"), B, T, C, CONVMOD_BN_ACTS[act],
+                                   ws.data_ptr(), ws.numel(), _stream()), "dyn_convmod_brn_bwd")
+    return out
+
+
 def _sub_act(act, what):
     if act not in SUBSAMPLING_ACTS:
         raise DynError(f"{what}: act={act!r} is not built ({sorted(SUBSAMPLING_ACTS)})")

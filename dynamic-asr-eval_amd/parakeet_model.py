@@ -1,7 +1,9 @@
 """ParakeetForCTC on MI355X: the FastConformer encoder + CTC head of the `nvidia/parakeet-ctc-*` checkpoints (`model_type: "parakeet_ctc"`,
 transformers modeling_parakeet.py), the model family of the reference's third loop (nvidia_ctc/lib.py: NVIDIA's conformer-CTC models), as
-`AutoModelForCTC` builds it in plain torch.  Eval mode, no attention mask: what the reference loop runs (it sets `layer.conv.eval()`, zeroes
-every dropout and reads the batch norm's running statistics, nvidia_ctc/lib.py:89-102).
+`AutoModelForCTC` builds it in plain torch.  No attention mask, dropout zero.  The conv modules' norm by default reads its running statistics
+(the eval-mode model).  That is NOT what the reference loop runs: it calls `model.train()` (nvidia_ctc/lib.py:74), puts `layer.conv` and its
+batch norm into eval mode (:92-93) and then replaces that batch norm by a fresh, hence training-mode, BatchRenorm1d (:94-102).
+`batch_renorm_training()` runs that norm (csrc/convmod_brn.hip); eval mode remains the default until a maintainer flips it.
 
 A subclass of Wav2Vec2ConformerForCTC: the two half-step FFNs, Transformer-XL attention with per-head `bias_u` / `bias_v` and a bias-free
 position projection (csrc/relshift.hip), the five attention products (_attn.py), the layer loop, flat parameters and the backward's deferred
@@ -29,6 +31,7 @@ Not built, refused by name before any launch: `subsampling_factor` != 8, `subsam
 `conv_kernel_size` != 9, `hidden_act` != "silu", `num_key_value_heads` != `num_attention_heads`, a `head_dim` other than hidden_size / heads,
 an `attention_mask` argument.  Bucketed hipGraph replay, lockstep groups, ParakeetForRNNT / ForTDT are out of scope.  No hub checkpoint is on
 the machine: transformers' ParakeetForCTC on the CPU with the same (random) state dict is the oracle in the tests."""
+import contextlib
 import math
 from types import SimpleNamespace
 
@@ -232,6 +235,7 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
                 self._alias[p + theirs] = p + ours
         self.n_mels, self.C, self.F3 = c["num_mel_bins"], c["subsampling_conv_channels"], c["num_mel_bins"] // 8
         self.input_scale = math.sqrt(c["hidden_size"]) if c.get("scale_input", False) else 1.0
+        self._brn, self._ctx_brn = None, False             # batch_renorm_training()'s state; whether the last forward ran inside it
 
     def trainable(self, name):
         return super().trainable(getattr(self, "_alias", {}).get(name, name))
@@ -250,6 +254,65 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
     def _below_frozen(self):
         """True when nothing of the subsampling adapts: its backward is then not run at all."""
         return not any(self.trainable(n) for n, _ in self.spec if n.startswith(SUB))
+
+    # ------------------------------------------------------------------ training-mode BatchRenorm (the reference loop's conv-module norm)
+    @contextlib.contextmanager
+    def batch_renorm_training(self, momentum=0.001, eps=1e-5, num_batches_tracked=1_000_000):
+        """Inside this context the conv modules' norm is what reference nvidia_ctc/lib.py:74,89-102 leaves in the model: a BatchRenorm1d in
+        TRAINING mode (the `batchrenorm` package form; parity unpinned against upstream `lcasr`) with the reference's constants as defaults.
+        On entry every layer's `running_mean` and `sqrt(running_var)` (no eps under the root, :101) are copied into loop-local device
+        tensors; the returned state exposes them as lists over the layers (`running_mean`, `running_std`) next to `num_batches_tracked` (a
+        list too: one counter per replaced module, as in the reference), `momentum` and `eps`.  Every forward, grad mode or not, normalises
+        with the statistics of its batch (all rows, the clean copy included), corrects them by the detached r / d clamped at
+        ops.batch_renorm_clamps(num_batches_tracked), moves the state's running statistics and advances the counters.  The gradient flows
+        through the batch mean and deviation and so reaches every row: backward(n_active < B) is refused.
+        Deviation from the reference: it leaves its replaced modules in the model and never restores anything; here the state is dropped
+        on exit, and the model's own buffers and its eval-mode path are untouched throughout."""
+        if self._brn is not None:
+            raise ops.DynError("batch_renorm_training() is already active on this model")
+        if not (0.0 <= float(momentum) <= 1.0 and float(eps) >= 0.0 and int(num_batches_tracked) >= 0):
+            raise ops.DynError(f"batch_renorm_training: momentum={momentum!r} must lie in [0, 1], eps={eps!r} and "
+                               f"num_batches_tracked={num_batches_tracked!r} must not be negative")
+        L = self.cfg["num_hidden_layers"]
+        stats = [self._bn(l) for l in range(L)]
+        state = SimpleNamespace(momentum=float(momentum), eps=float(eps), num_batches_tracked=[int(num_batches_tracked)] * L,
+                                running_mean=[m.clone() for m, _ in stats], running_std=[v.sqrt() for _, v in stats])
+        self._brn = state
+        try:
+            yield state
+        finally:
+            self._brn = None
+
+    def _convmod(self, l, u, w, cb, p, vT, save):
+        """The bracket between the two pointwise convolutions in the model's mode: (a, gl, cv, stats); stats is None in eval mode."""
+        P = self.P
+        self._ctx_brn = self._brn is not None
+        if self._brn is None:
+            mean, var = self._bn(l)
+            return ops.convmod_bn(u, w, cb, mean, var, P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], "silu", BN_EPS, valid=vT, save=save) + (None,)
+        st = self._brn
+        rmax, dmax = ops.batch_renorm_clamps(st.num_batches_tracked[l])
+        out = ops.convmod_brn(u, w, cb, st.running_mean[l], st.running_std[l], P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], rmax, dmax,
+                              st.momentum, "silu", st.eps, valid=vT)
+        st.num_batches_tracked[l] += 1
+        return out
+
+    def _convmod_bwd(self, l, cv, stats, da, p, cbn, has_cb, vT):
+        """dc of the bracket's norm and activation (over da), the norm's affine gradients accumulated."""
+        P = self.P
+        gw, gb, gc = self._g(p + "conv.norm.weight"), self._g(p + "conv.norm.bias"), self._g(cbn) if has_cb else None
+        if stats is None:
+            mean, var = self._bn(l)
+            return ops.convmod_bn_bwd_act(cv, mean, var, P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], da, gw, gb, gc, "silu", BN_EPS,
+                                          valid=vT, out=da)
+        return ops.convmod_brn_bwd(cv, stats, da, gw, gb, gc, "silu", valid=vT, out=da)
+
+    def backward(self, grad_logits, n_active=None):
+        if self._ctx_brn and isinstance(self._ctx, dict) and n_active is not None and int(n_active) < self._ctx["dims"][0]:
+            raise ops.DynError(f"backward(n_active={int(n_active)}) of a batch of {self._ctx['dims'][0]} after a forward under batch_renorm_training(): "
+                               "the gradient flows through the batch statistics and reaches every row; pass a gradient for all rows "
+                               "(zeros where the loss has none)")
+        return super().backward(grad_logits, n_active)
 
     # ------------------------------------------------------------------ state dict
     def _to_hf(self, name, t):
@@ -342,25 +405,22 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
         p = f"encoder.layers.{l}."
         n, m, s = ops.layernorm(x, P[p + "norm_conv.weight"], P[p + "norm_conv.bias"], self._layer_eps)
         u = ops.linear(n, P[p + "conv.pointwise_conv1.weight"], P.get(p + "conv.pointwise_conv1.bias"))
-        mean, var = self._bn(l)
         w, cb = P[p + "conv.depthwise_conv.weight"], P.get(p + "conv.depthwise_conv.bias")
-        a, gl, cv = ops.convmod_bn(u, w, cb, mean, var, P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], "silu", BN_EPS, valid=vT, save=save)
+        a, gl, cv, st = self._convmod(l, u, w, cb, p, vT, save)
         r = x.clone() if save else x
         ops.linear(a, P[p + "conv.pointwise_conv2.weight"], P.get(p + "conv.pointwise_conv2.bias"), out=r, beta=1.0)
-        return r, (x, m, s, n, u, gl, cv, a)
+        return r, (x, m, s, n, u, gl, cv, a, st)
 
     def _conv_bwd(self, dr, kept, l, vT):
         P, G = self.P, self.G
         p = f"encoder.layers.{l}."
-        x, m, s, n, u, gl, cv, a = kept
+        x, m, s, n, u, gl, cv, a, st = kept
         cbn = p + "conv.depthwise_conv.bias"
         has_cb = cbn in P
         b1, b2 = (p + f"conv.pointwise_conv{i}.bias" if has_cb else None for i in (1, 2))
         da = self._lin_bwd(dr, a, p + "conv.pointwise_conv2.weight", b2)
-        mean, var = self._bn(l)
         w = P[p + "conv.depthwise_conv.weight"]
-        dc = ops.convmod_bn_bwd_act(cv, mean, var, P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], da, self._g(p + "conv.norm.weight"),
-                                    self._g(p + "conv.norm.bias"), self._g(cbn) if has_cb else None, "silu", BN_EPS, valid=vT, out=da)
+        dc = self._convmod_bwd(l, cv, st, da, p, cbn, has_cb, vT)
         ops.dwconv1d_wgrad(gl, dc, G[p + "conv.depthwise_conv.weight"], None, beta=1.0)
         du = ops.glu_dwconv1d_dgrad(u, w, dc, valid=vT)
         dn = self._lin_bwd(du, n, p + "conv.pointwise_conv1.weight", b1)

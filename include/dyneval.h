@@ -934,6 +934,47 @@ int dyn_dwconv2d_s2_wgrad_act(const float* z, const float* du, float* dw, float*
 int dyn_relu_fwd(const float* x, float* y, int64_t n, void* stream);
 int dyn_relu_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The conv-module core with the norm the reference's third loop runs (reference nvidia_ctc/lib.py:74,89-102): `model.train()`, the conv
+ * module and its batch norm put into eval mode, and that batch norm then REPLACED by a fresh BatchRenorm1d(momentum = 0.001, eps = 1e-5),
+ * which is in training mode (num_batches_tracked = 1000000 saturates its clamps at rmax = 3, dmax = 5; running_std = sqrt(running_var)).
+ * BatchRenorm1d is the `batchrenorm` package form; parity unpinned against upstream `lcasr`.  Per channel over the n = B * *valid valid
+ * rows of x = the depthwise convolution's output:
+ *     mu = mean(x), std = sqrt(mean((x - mu)^2)) (biased), sig = std + eps (eps joins the deviation, not the variance),
+ *     r = clamp(sig / running_std, 1 / rmax, rmax), d = clamp((mu - running_mean) / running_std, -dmax, dmax)   (both constants of the backward)
+ *     s = act(weight * ((x - mu) / sig * r + d) + bias);
+ *     running_mean += momentum * (mu - running_mean), running_std += momentum * (sig - running_std)   (in place; momentum = 0: untouched).
+ * rmax / dmax come from the caller (the schedule over num_batches_tracked is host arithmetic).  fp32, no float atomics, centred
+ * statistics (no E[x^2] - E[x]^2), every result bit-reproducible.  A channel whose batch variance is exactly zero is OUTSIDE the contract
+ * (the backward divides by std).
+ *   dyn_convmod_brn_fwd     u [B, T, 2C], w [C, KW], cbias [C] or null -> s, gl, c [B, T, C] (all three written; rows >= *valid exact zeros)
+ *                           and stats [dyn_convmod_brn_stats_rows() = 7][C]: mu, 1 / sig, r, d, scale = weight * r / sig,
+ *                           shift = weight * d + bias, 1 / std (what the backward reads).  Three launches: the GLU + depthwise forward of
+ *                           dyn_convmod_bn_fwd leaving one centred partial (count, mean, sum of squared deviations) per time tile and
+ *                           channel in `workspace`; one thread per channel combining them in tile order (pairwise update, count 0 skipped);
+ *                           the apply.  s, c, stats 16-byte aligned.
+ *   dyn_convmod_brn_bwd     from c, stats and ds [B, T, C]: dc = scale * (g - mean(g) - (x - mu) / std * mean(g * x0)), g = ds * act'(y),
+ *                           x0 = (x - mu) / sig (dc may be ds); dbias = wgrad_beta * old + sum g, dweight = wgrad_beta * old +
+ *                           r * sum(g * x0) + d * sum g (null: frozen, not written); dcbias = wgrad_beta * old: the convolution bias
+ *                           cancels in x - mu, its gradient is identically zero and no sum is launched for it.  Three launches (g and the
+ *                           per-workgroup partial rows in dyn_convmod_bn_bwd_act's fixed row order; one thread per channel adding them in
+ *                           workgroup order; dc in place).  The two sums are needed before dc, so this reduction is never deferred.
+ *                           The gradient reaches every row of the batch.  c, dc, stats, workspace 16-byte aligned.
+ *   The depthwise weight gradient and the data gradient stay dyn_dwconv1d_wgrad(gl, dc) and dyn_glu_dwconv1d_dgrad.
+ * KW in {9, 32}, C in {256, 512, 768, 1024}, act 0 = SiLU: anything else DYN_E_UNSUPPORTED.  Null pointers, rmax < 1, dmax < 0, momentum
+ * outside [0, 1], B * T < 2 -> DYN_E_ARG; a short workspace -> DYN_E_WORKSPACE; all before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t dyn_convmod_brn_stats_rows(void);
+int64_t dyn_convmod_brn_fwd_workspace_bytes(int64_t B, int64_t T, int64_t C, int64_t KW);
+int dyn_convmod_brn_fwd(const float* u, const float* w, const float* cbias, float* running_mean, float* running_std, const float* weight,
+                        const float* bias, float* s, float* gl, float* c, float* stats, const int32_t* valid, int64_t B, int64_t T,
+                        int64_t C, int64_t KW, int32_t act, float eps, float rmax, float dmax, float momentum, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+int64_t dyn_convmod_brn_bwd_workspace_bytes(int64_t B, int64_t T, int64_t C);
+int dyn_convmod_brn_bwd(const float* c, const float* stats, const float* ds, float* dc, float* dweight, float* dbias, float* dcbias,
+                        float wgrad_beta, const int32_t* valid, int64_t B, int64_t T, int64_t C, int32_t act, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
