@@ -2,7 +2,8 @@
 operation's definition (no call into the torch op it mirrors).  tests/test_kernel_refs_cpu.py checks every one of them against torch's own
 op and autograd in float64 to 1e-12, so a wrong reference cannot hide a wrong kernel; tests/test_kernel_parity_f64_gpu.py compares the HIP
 kernels with them (the row softmax family: tests/test_row_kernels_gpu.py, on the device; the conformer's own convolutions, dtype- and
-device-agnostic: tests/test_conv_kernels_gpu.py; the log-mel front end and the window augmentations: tests/test_frontend_kernels_gpu.py).
+device-agnostic: tests/test_conv_kernels_gpu.py; the log-mel front end and the window augmentations: tests/test_frontend_kernels_gpu.py;
+the fused streaming attention: tests/test_attention_kernels_gpu.py).
 Also here: the inputs both files share, the tolerance rule, and CPU replays of the summation orders the column norm and the log-mel
 normalisation used before their statistics were made stable (E[x^2] - mean^2 from fp32 running sums)."""
 import math
@@ -842,3 +843,139 @@ def logmel_uncentred_replay(logvals32):
     mean = sd_ / T
     var = (qd - sd_ * mean) / (T - 1) if T > 1 else np.ones(F_)
     return torch.from_numpy(mean), torch.from_numpy(var)
+
+
+# ----------------------------------------------------------------------------------------------------------- fused streaming attention
+# csrc/attention.hip from the definitions (tests/test_attention_kernels_gpu.py): q, k, v [B, H, T, D], one softmax row per query.  The
+# references return float64 on the CPU; attention_torch_fp32 is torch's own fp32 evaluation of the same expression (measured_tol).  Also
+# here: the view of a strided [B, T, .] buffer as [B, H, T, D], and the generators of the cases whose construction carries an assertion.
+ATTN_D = 128
+
+
+def heads_view(flat, offset, B, T, H, row_stride, batch_stride, D=ATTN_D):
+    """The [B, H, T, D] view of a flat buffer in the layout the C-ABI addresses: element (b, h, t, d) at
+    offset + b * batch_stride + t * row_stride + h * D + d (floats).  Writes through the view land in the buffer."""
+    return torch.as_strided(flat, (B, H, T, D), (batch_stride, D, row_stride, 1), offset)
+
+
+def attention_ref(q, k, v, scale):
+    """out = softmax(scale * q k^T) v and lse = log sum_j exp(scale * q k_j), the row maximum taken out first.  Returns (out, lse [B, H, T])."""
+    q, k, v = d(q), d(k), d(v)
+    s = (q @ k.transpose(-1, -2)) * scale
+    m = s.max(-1, keepdim=True).values
+    e = torch.exp(s - m)
+    l = e.sum(-1, keepdim=True)
+    return (e / l) @ v, (m + torch.log(l)).squeeze(-1)
+
+
+def attention_bwd_ref(q, k, v, out, dout, scale):
+    """P = exp(s - lse), delta = sum_d dO o O (from the `out` it is handed, as the kernel does), dS = P o (dO V^T - delta),
+    dQ = scale dS K, dK = scale dS^T Q, dV = P^T dO.  Returns (dq, dk, dv, delta [B, H, T])."""
+    q, k, v, out, dout = d(q), d(k), d(v), d(out), d(dout)
+    s = (q @ k.transpose(-1, -2)) * scale
+    m = s.max(-1, keepdim=True).values
+    lse = m + torch.log(torch.exp(s - m).sum(-1, keepdim=True))
+    p = torch.exp(s - lse)
+    delta = (dout * out).sum(-1, keepdim=True)
+    ds = p * (dout @ v.transpose(-1, -2) - delta)
+    return scale * (ds @ k), scale * (ds.transpose(-1, -2) @ q), p.transpose(-1, -2) @ dout, delta.squeeze(-1)
+
+
+def attention_cancellation_bound(q, k, v, out, dout, scale):
+    """What dQ and dK may be off by where the exact gradient vanishes.  The backward forms dS = P o (dP - delta) from two separately
+    rounded fp32 sums of D products, dP_ij = sum_d dO_id V_jd and delta_i = sum_d dO_id O_id (that is its interface: delta is an output,
+    taken from `out`).  Where a row attends to one key alone (T = 1 always: P = 1, O = V, dP = delta and dQ = dK = 0 identically) torch's
+    softmax backward returns exactly 0 and 2e-5 * max|grad| is no bound at all, while the two sums, accumulated in different orders, differ
+    by their rounding.  An fp32 sum of D signed terms accumulated in any order: every addition rounds by at most u = 2^-24 of a partial sum,
+    partial sums of random sign grow like sqrt(n) * rms term, so the errors add up (in quadrature) to about u * D * rms / sqrt(2), which is
+    0.5 to 0.9 u * sum_d |term| — the rigorous worst case is D u sum |term| (Higham, Accuracy and Stability, (3.5)), 128 times more and
+    never seen.  Allowing 2 u sum |term| per sum (the largest of many elements, not the rms):
+        E_ij = 2 u (sum_d |dO_id V_jd| + sum_d |dO_id O_id|),  |err dQ_i| <= scale sum_j P_ij E_ij |K_j|,  |err dK_j| <= scale sum_i P_ij E_ij |Q_i|.
+    Returns (bound on dQ, bound on dK) as floats: the largest element of each.  Used for T = 1 only; every other shape keeps the
+    floor relative to its gradient."""
+    q, k, v, out, dout = d(q), d(k), d(v), d(out), d(dout)
+    s = (q @ k.transpose(-1, -2)) * scale
+    e = torch.exp(s - s.max(-1, keepdim=True).values)
+    p = e / e.sum(-1, keepdim=True)
+    pe = p * (2.0 * 2.0 ** -24 * (dout.abs() @ v.abs().transpose(-1, -2) + (dout.abs() * out.abs()).sum(-1, keepdim=True)))
+    return (scale * (pe @ k.abs())).max().item(), (scale * (pe.transpose(-1, -2) @ q.abs())).max().item()
+
+
+def attention_torch_fp32(q, k, v, scale, dout=None):
+    """torch's fp32 CPU evaluation: softmax / logsumexp of (q k^T) * scale, and with `dout` fp32 autograd of it.
+    Returns (out, lse) or (out, lse, dq, dk, dv)."""
+    q, k, v = (t.detach().cpu().float().clone().requires_grad_(dout is not None) for t in (q, k, v))
+    s = (q @ k.transpose(-1, -2)) * scale
+    out = torch.softmax(s, -1) @ v
+    lse = torch.logsumexp(s, -1).detach()
+    if dout is None:
+        return out, lse
+    out.backward(dout.detach().cpu().float())
+    return out.detach(), lse, q.grad, k.grad, v.grad
+
+
+def attention_inputs(B, H, T, seed, kind="plain", step=0.5, scale=1.0 / math.sqrt(ATTN_D)):
+    """q, k, v, dout [B, H, T, D] fp32, O(1) and seeded.  `kind`: "plain"; "peaky": q rows * 8 (one key takes most of a row, as after
+    rotary and training); "rising" / "falling": dimension 0 of q is the constant 1 / scale and dimension 0 of k a ramp of `step` per key,
+    so every score carries + step * j (rising: the running maximum rises on every key tile) or - step * j (falling: it never rises after
+    the first tile) on top of the O(1) rest."""
+    g = gen(9000 + seed + 7 * T)
+    q, k, v, dout = (torch.randn(B, H, T, ATTN_D, generator=g) for _ in range(4))
+    if kind == "peaky":
+        q = q * 8
+    elif kind in ("rising", "falling"):
+        q[..., 0] = 1.0 / scale
+        k[..., 0] = torch.arange(T, dtype=torch.float32) * (step if kind == "rising" else -step)
+    else:
+        assert kind == "plain", kind
+    return q.contiguous(), k.contiguous(), v.contiguous(), dout.contiguous()
+
+
+ATTN_ROUTING_SEED = 11
+ATTN_ROUTING_GAIN = 400.0
+ATTN_ROUTING_GAP = 120.0
+
+
+def attention_routing_inputs(B, H, T, seed=ATTN_ROUTING_SEED):
+    """Exact routing: k rows of unit length, q_i = 400 k_pi(i) for a seeded permutation pi per (b, h), scale = 1.  Query i's score with key
+    pi(i) is 400 |k|^2 and every other one 400 cos, so far below that its exp is exactly 0 in fp32 (exp(-104) is below the smallest
+    denormal): the output row i is the row pi(i) of v, bit for bit, and lse the winning score.  Asserts, in float64, that the gap between
+    the best and the second-best score of every row exceeds ATTN_ROUTING_GAP and that the best is pi's.
+    Returns (q, k, v, pi [B, H, T] int64, winning score [B, H, T] float64)."""
+    g = gen(9500 + seed + T)
+    k = torch.randn(B, H, T, ATTN_D, generator=g, dtype=F64)
+    k = (k / torch.sqrt((k * k).sum(-1, keepdim=True))).float()
+    v = torch.randn(B, H, T, ATTN_D, generator=g)
+    pi = torch.stack([torch.randperm(T, generator=g) for _ in range(B * H)]).view(B, H, T)
+    q = (ATTN_ROUTING_GAIN * torch.gather(k, 2, pi[..., None].expand(B, H, T, ATTN_D))).contiguous()
+    s = d(q) @ d(k).transpose(-1, -2)
+    top = s.topk(min(2, T), -1)
+    assert torch.equal(top.indices[..., 0], pi), "the best key of every query is pi's"
+    if T > 1:
+        gap = (top.values[..., 0] - top.values[..., 1]).min().item()
+        assert gap > ATTN_ROUTING_GAP, f"score gap {gap} at T = {T}, seed {seed}"
+    return q, k.contiguous(), v.contiguous(), pi, top.values[..., 0]
+
+
+ATTN_UNDERFLOW_STEP = 1.0
+ATTN_UNDERFLOW_GAP = 110.0
+
+
+def attention_underflow_inputs(B, H, T=256, seed=3, nsplit=2):
+    """The rising ramp of attention_inputs, steep enough (1 per key) that the log-sum-exp of the first of `nsplit` key splits is more than
+    ATTN_UNDERFLOW_GAP below the second's for every query: the first split's merge weight exp(lse_0 - lse_1) underflows to 0.  Asserts that
+    gap in float64 (splits are whole 32-key tiles, ceil(tiles / nsplit) each, as in the kernel).  Returns (q, k, v, dout)."""
+    scale = 1.0 / math.sqrt(ATTN_D)
+    q, k, v, dout = attention_inputs(B, H, T, seed, "rising", ATTN_UNDERFLOW_STEP, scale)
+    per = -(-(-(-T // 32)) // nsplit) * 32
+    s = (d(q) @ d(k).transpose(-1, -2)) * scale
+    lse = [torch.log(torch.exp(part - s.max(-1, keepdim=True).values).sum(-1)) for part in (s[..., :per], s[..., per:2 * per])]
+    gap = (lse[1] - lse[0]).min().item()
+    assert gap > ATTN_UNDERFLOW_GAP, f"lse gap {gap}"
+    return q, k, v, dout
+
+
+def attention_split_fits(T, nsplit):
+    """The host guard of dyn_attention_fwd_split: 1 <= nsplit <= 8 and the last split still has a key tile."""
+    tiles = -(-T // 32)
+    return 1 <= nsplit <= 8 and (nsplit == 1 or (nsplit - 1) * -(-tiles // nsplit) < tiles)

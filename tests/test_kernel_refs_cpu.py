@@ -2,6 +2,7 @@
 compare the HIP kernels with must themselves be right.  Also pins that the column-norm parity test discriminates: the summation order
 the kernel had before its statistics were made stable misses that test's bound on the offset inputs, torch's fp32 result meets it; and the
 same for the normalised log-mel test (tests/test_frontend_kernels_gpu.py) on bins at the floor log(1e-6)."""
+import math
 import os
 import sys
 
@@ -523,3 +524,97 @@ def test_uncentred_logmel_statistics_miss_the_normalised_bound_on_near_floor_bin
     for sd in (1e-3, 1e-2):                                            # each of the two near-floor classes on its own
         cols = [f for f in near_floor if K.LOGMEL_CLASSES[f % 6][1] == sd]
         assert K.logmel_log_unit_err(old[cols], ref[cols], std64[cols]) > tol, (T, sd)
+
+
+# ----------------------------------------------------------------------------------------------------------- fused streaming attention
+ATTN_KINDS = [("plain", 0.5), ("peaky", 0.5), ("rising", 0.5), ("falling", 0.5), ("rising", K.ATTN_UNDERFLOW_STEP)]
+
+
+@pytest.mark.parametrize("kind,step", ATTN_KINDS, ids=[f"{k}-{s:g}" for k, s in ATTN_KINDS])
+@pytest.mark.parametrize("B,H,T,scale", [(2, 2, 1, 0.3), (1, 3, 5, 1.0), (2, 2, 33, 128 ** -0.5), (1, 2, 130, 128 ** -0.5), (1, 1, 40, 0.0)])
+def test_attention_refs_are_softmax_logsumexp_and_their_autograd(B, H, T, scale, kind, step):
+    q, k, v, dout = (t.double() for t in K.attention_inputs(B, H, T, 1, kind, step, scale if scale else 1.0))
+    qr, kr, vr = (t.clone().requires_grad_() for t in (q, k, v))
+    s = (qr @ kr.transpose(-1, -2)) * scale
+    want = torch.softmax(s, -1) @ vr
+    want.backward(dout)
+    out, lse = K.attention_ref(q, k, v, scale)
+    _same(out, want.detach(), "out"); _same(lse, torch.logsumexp(s.detach(), -1), "lse")
+    dq, dk, dv, delta = K.attention_bwd_ref(q, k, v, out, dout, scale)
+    _same(dq, qr.grad, "dq"); _same(dk, kr.grad, "dk"); _same(dv, vr.grad, "dv")
+    _same(delta, (dout * want.detach()).sum(-1), "delta")
+    if scale == 0.0:                                                # the uniform row: the column mean of v, log T, and no gradient through s
+        _same(out, v.mean(2, keepdim=True).expand_as(v), "column mean"); _same(lse, torch.full_like(lse, math.log(T)), "log T")
+        assert not dq.any() and not dk.any()
+    # delta comes from the `out` handed in, not from a forward of its own
+    other = out + 1.0
+    assert torch.equal(K.attention_bwd_ref(q, k, v, other, dout, scale)[3], (dout * other).sum(-1))
+
+
+def test_attention_torch_fp32_is_fp32_and_close():
+    q, k, v, dout = K.attention_inputs(2, 2, 65, 2)
+    res = K.attention_torch_fp32(q, k, v, 128 ** -0.5, dout)
+    out, lse = K.attention_ref(q, k, v, 128 ** -0.5)
+    want = (out, lse) + K.attention_bwd_ref(q, k, v, out, dout, 128 ** -0.5)[:3]
+    assert all(r.dtype == torch.float32 and not r.requires_grad for r in res)
+    assert all(K.max_err(r, w) < 1e-5 for r, w in zip(res, want)) and not q.requires_grad
+    assert all(torch.equal(a, b) for a, b in zip(res[:2], K.attention_torch_fp32(q, k, v, 128 ** -0.5)))
+
+
+def test_attention_cancellation_bound_covers_an_fp32_replay_at_one_key():
+    """T = 1: the gradient through the scores is identically 0, torch's fp32 autograd returns exactly 0, and an fp32 replay of the kernel's
+    formulation (dP from one sum, delta from another) does not — by less than the derived bound, which is itself far below the gradients'
+    own size at any other T (O(1))."""
+    scale = 128 ** -0.5
+    q, k, v, dout = K.attention_inputs(2, 2, 1, 1)
+    res = K.attention_torch_fp32(q, k, v, scale, dout)
+    assert not res[2].any() and not res[3].any() and torch.equal(res[0], v)
+    dp = (dout.double() @ v.double().transpose(-1, -2)).float()                        # two roundings of the same number ...
+    delta = torch.stack([(dout[..., i::4] * v[..., i::4]).sum(-1, keepdim=True) for i in range(4)]).sum(0)      # ... summed in another order
+    ds = dp - delta
+    assert ds.any()
+    bq, bk = K.attention_cancellation_bound(q, k, v, v, dout, scale)
+    eq, ek = (scale * ds * k).abs().max().item(), (scale * ds * q).abs().max().item()
+    print(f"T=1 replay: dq {eq:.2e} (bound {bq:.2e}), dk {ek:.2e} (bound {bk:.2e})")
+    assert 0 < eq <= bq < 2e-5 and 0 < ek <= bk < 2e-5
+
+
+def test_heads_view_addresses_what_the_c_abi_addresses():
+    B, T, H, D, W = 2, 5, 3, K.ATTN_D, 3 * 3 * K.ATTN_D + 8
+    bs = T * W + 12
+    flat = torch.arange(4 + B * bs, dtype=torch.float32)
+    for which in range(3):
+        view = K.heads_view(flat, 4 + which * H * D, B, T, H, W, bs)
+        assert view.shape == (B, H, T, D)
+        for b, h, t, dd in ((0, 0, 0, 0), (1, 2, 4, 127), (1, 0, 3, 5), (0, 1, 2, 64)):
+            assert view[b, h, t, dd].item() == 4 + which * H * D + b * bs + t * W + h * D + dd
+    K.heads_view(flat, 4, B, T, H, W, bs)[1, 2, 4, 127] = -1.0                   # a write through the view lands in the buffer
+    assert flat[4 + bs + 4 * W + 2 * D + 127].item() == -1.0
+    packed = torch.randn(B, T, 3 * H * D, generator=K.gen(5))
+    x = packed.view(B, T, 3, H, D)
+    for which in range(3):
+        assert torch.equal(K.heads_view(packed.view(-1), which * H * D, B, T, H, 3 * H * D, T * 3 * H * D), x[:, :, which].transpose(1, 2))
+
+
+@pytest.mark.parametrize("T", [96, 300])
+def test_attention_routing_inputs_keep_their_score_gap(T):
+    """The generator's own assertions (best key = pi's, gap > 120, in float64) hold for the committed seed; every other key's weight
+    exp(s - s_best) is exactly 0 in fp32 and the float64 output is the permuted v to its last bit but rounding."""
+    q, k, v, pi, win = K.attention_routing_inputs(2, 2, T)
+    s = q.double() @ k.double().transpose(-1, -2)
+    w = torch.exp((s - win[..., None]).float())
+    assert int((w != 0).sum()) == 2 * 2 * T and float(win.min()) > 399.0
+    out, lse = K.attention_ref(q, k, v, 1.0)
+    want = torch.gather(v, 2, pi[..., None].expand_as(v))
+    _same(out, want.double(), "out"); _same(lse, win, "lse")
+    assert [n for n in range(1, 9) if K.attention_split_fits(T, n)] == ([1, 2, 3] if T == 96 else [1, 2, 3, 4, 5])
+
+
+def test_attention_underflow_inputs_keep_their_lse_gap():
+    """The generator asserts the gap > 110 between the two splits' log-sum-exps; the first split's merge weight is then 0 in fp32."""
+    q, k, v, _ = K.attention_underflow_inputs(2, 2)
+    s = (q.double() @ k.double().transpose(-1, -2)) * 128 ** -0.5
+    gap = torch.logsumexp(s[..., 128:], -1) - torch.logsumexp(s[..., :128], -1)
+    assert float(gap.min()) > K.ATTN_UNDERFLOW_GAP and not torch.exp(-gap.float()).any()
+    assert K.attention_split_fits(1024, 7) and K.attention_split_fits(1024, 8) and not K.attention_split_fits(100, 8)
+    assert not K.attention_split_fits(256, 9) and not K.attention_split_fits(256, 0)
