@@ -2067,3 +2067,193 @@ def relu_bwd(x, dy, out=None):
     out = torch.empty_like(dy) if out is None else _cc(out, "relu_bwd.out")
     check(_L().dyn_relu_bwd(x.data_ptr(), dy.data_ptr(), out.data_ptr(), x.numel(), _stream()), "dyn_relu_bwd")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- transducer head (csrc/transducer.hip)
+JOINT_ACTS = {"relu": 0}
+TDT_REDUCTIONS = {"sum": 0, "mean_batch": 1, "mean": 2, "mean_volume": 3, "none": 4}
+TDT_MAX_DURATIONS = 8
+TDT_WORKSPACE_BUDGET = 512 << 20      # bytes of lattice state a dyn_tdt_loss call may ask for; the joint is not chunked over t
+
+
+def _joint_act(act, what):
+    if act not in JOINT_ACTS:
+        raise DynError(f"{what}: hidden_act={act!r} is not built ({sorted(JOINT_ACTS)})")
+    return JOINT_ACTS[act]
+
+
+def check_durations(durations, what="durations"):
+    """The duration list of a TDT head as a tuple of ints: 1 .. 8 values, non-negative, strictly ascending, at least one positive."""
+    d = tuple(int(v) for v in durations)
+    if not 1 <= len(d) <= TDT_MAX_DURATIONS:
+        raise DynError(f"{what}: {len(d)} durations are not built (1 .. {TDT_MAX_DURATIONS})")
+    if any(v < 0 for v in d):
+        raise DynError(f"{what}: negative durations {d} are not built")
+    if any(b <= a for a, b in zip(d, d[1:])):
+        raise DynError(f"{what}: unsorted durations {d} are not built (strictly ascending)")
+    if d[-1] == 0:
+        raise DynError(f"{what}: durations {d} hold no positive value: no arc advances the frame")
+    return d
+
+
+def _durations_arg(durations):
+    d = check_durations(durations)
+    return (ctypes.c_int32 * len(d))(*d), len(d)
+
+
+def lstm_cell(xg, hg, c_prev=None, save=False, out=None):
+    """gates = xg + hg [Bd, 4 Hd] (i | f | g | o) -> (c, h, gate activations or None); `out` = (c, h, gates or None) to write into."""
+    _cc(xg, "lstm_cell.xg"); _cc(hg, "lstm_cell.hg")
+    Bd, H4 = xg.shape
+    if H4 % 4 or hg.shape != xg.shape or (c_prev is not None and tuple(c_prev.shape) != (Bd, H4 // 4)):
+        raise DynError(f"lstm_cell: xg {tuple(xg.shape)}, hg {tuple(hg.shape)}, c_prev {None if c_prev is None else tuple(c_prev.shape)}")
+    Hd = H4 // 4
+    if out is None:
+        c = torch.empty(Bd, Hd, device=xg.device, dtype=F32)
+        h = torch.empty(Bd, Hd, device=xg.device, dtype=F32)
+        gates = torch.empty(Bd, H4, device=xg.device, dtype=F32) if save else None
+    else:
+        c, h, gates = out
+        _cc(c, "lstm_cell.c"); _cc(h, "lstm_cell.h")
+        if tuple(c.shape) != (Bd, Hd) or tuple(h.shape) != (Bd, Hd) or (gates is not None and tuple(gates.shape) != (Bd, H4)):
+            raise DynError("lstm_cell: out shapes do not fit")
+    check(_L().dyn_lstm_cell_fwd(xg.data_ptr(), hg.data_ptr(), _opt(c_prev, "lstm_cell.c_prev"), c.data_ptr(), h.data_ptr(),
+                                 _opt(gates, "lstm_cell.gates"), Bd, Hd, _stream()), "dyn_lstm_cell_fwd")
+    return c, h, gates
+
+
+def lstm_cell_bwd(dh, dc_next, gates, c_prev, c, dgates=None):
+    """-> (dgates [Bd, 4 Hd] pre-activation gradients, dc_prev [Bd, Hd]); dc_next / c_prev None = zeros."""
+    _cc(dh, "lstm_cell_bwd.dh"); _cc(gates, "lstm_cell_bwd.gates"); _cc(c, "lstm_cell_bwd.c")
+    Bd, Hd = c.shape
+    if tuple(gates.shape) != (Bd, 4 * Hd) or dh.shape != c.shape:
+        raise DynError(f"lstm_cell_bwd: dh {tuple(dh.shape)}, gates {tuple(gates.shape)}, c {tuple(c.shape)}")
+    dgates = torch.empty_like(gates) if dgates is None else _cc(dgates, "lstm_cell_bwd.dgates")
+    if tuple(dgates.shape) != (Bd, 4 * Hd):
+        raise DynError(f"lstm_cell_bwd: dgates {tuple(dgates.shape)}")
+    dc_prev = torch.empty_like(c)
+    check(_L().dyn_lstm_cell_bwd(dh.data_ptr(), _opt(dc_next, "lstm_cell_bwd.dc_next"), gates.data_ptr(), _opt(c_prev, "lstm_cell_bwd.c_prev"),
+                                 c.data_ptr(), dgates.data_ptr(), dc_prev.data_ptr(), Bd, Hd, _stream()), "dyn_lstm_cell_bwd")
+    return dgates, dc_prev
+
+
+def _joint_p(p, B, Hd, what):
+    """p [Bp, U1, Hd] (Bp = B, or 1: shared) as any view whose last axis is contiguous -> (shared, stride_b, stride_u)."""
+    _chk(p, what + ".p")
+    if p.dim() != 3 or p.shape[2] != Hd or p.shape[0] not in (1, B) or p.stride(2) != 1 or p.data_ptr() % 16:
+        raise DynError(f"{what}: p {tuple(p.shape)} must be [{B} or 1, U + 1, {Hd}] with a contiguous, 16-byte aligned last axis")
+    shared = p.shape[0] == 1 and B > 1
+    return shared, 0 if p.shape[0] == 1 else p.stride(0), p.stride(1)
+
+
+def joint(e, p, act="relu"):
+    """z [B, T, U1, Hd] = act(e[b, t] + p[b, u]); e [B, T, Hd], p [B or 1, U1, Hd] (one row set shared by the batch)."""
+    a = _joint_act(act, "joint")
+    _cc(e, "joint.e")
+    B, T, Hd = e.shape
+    _, sb, su = _joint_p(p, B, Hd, "joint")
+    U1 = p.shape[1]
+    z = torch.empty(B, T, U1, Hd, device=e.device, dtype=F32)
+    check(_L().dyn_joint_fwd(e.data_ptr(), p.data_ptr(), z.data_ptr(), B, T, U1, Hd, sb, su, a, _stream()), "dyn_joint_fwd")
+    return z
+
+
+def joint_bwd(dz, z, dp_like, act="relu", want_de=True, want_dp=True, time_major=False):
+    """(de [B, T, Hd] or None, dp in the shape of `dp_like` ([B or 1, U1, Hd]: 1 sums over the batch too) or None); `time_major`: dp is
+    written as [U1, B or 1, Hd] (the layout the LSTM backward walks)."""
+    a = _joint_act(act, "joint_bwd")
+    _cc(dz, "joint_bwd.dz"); _cc(z, "joint_bwd.z")
+    B, T, U1, Hd = z.shape
+    if dz.shape != z.shape or tuple(dp_like.shape[1:]) != (U1, Hd) or dp_like.shape[0] not in (1, B):
+        raise DynError(f"joint_bwd: dz {tuple(dz.shape)}, z {tuple(z.shape)}, p {tuple(dp_like.shape)}")
+    shared = dp_like.shape[0] == 1 and B > 1
+    de = torch.empty(B, T, Hd, device=z.device, dtype=F32) if want_de else None
+    Bp = dp_like.shape[0]
+    dp = torch.empty((U1, Bp, Hd) if time_major else (Bp, U1, Hd), device=z.device, dtype=F32) if want_dp else None
+    sb, su = (Hd, Bp * Hd) if time_major else (U1 * Hd, Hd)
+    check(_L().dyn_joint_bwd(dz.data_ptr(), z.data_ptr(), 0 if de is None else de.data_ptr(), 0 if dp is None else dp.data_ptr(), B, T, U1, Hd,
+                             int(shared), sb, su, a, _stream()), "dyn_joint_bwd")
+    return de, dp
+
+
+def tdt_loss(logits, targets, logit_lengths, target_lengths, blank, durations, sigma=0.0, reduction="mean", grad_scale=1.0, want_grad=True,
+             out=None, budget=None):
+    """logits [B, T, U1, V1 + D] contiguous; targets int32 [B, S >= 1]; lengths int32 [B] (all on the device); `durations` a host list.
+    Returns (loss [1], nll [B], grad [B, T, U1, V1 + D] of grad_scale * loss or None) with transformers' tdt_loss semantics
+    (reduction "none": loss is the sum, the rows are nll).  `out` may be logits (the gradient written over them)."""
+    _c(logits, "tdt_loss.logits"); _c(targets, "tdt_loss.targets", I32)
+    _cc(logit_lengths, "tdt_loss.logit_lengths", I32); _cc(target_lengths, "tdt_loss.target_lengths", I32)
+    if reduction not in TDT_REDUCTIONS:
+        raise DynError(f"tdt_loss: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
+    dur, D = _durations_arg(durations)
+    if logits.dim() != 4 or logits.shape[3] <= D:
+        raise DynError(f"tdt_loss: logits {tuple(logits.shape)} must be [B, T, U + 1, V + 1 + {D}]")
+    B, T, U1, N = logits.shape
+    if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or logit_lengths.numel() != B or target_lengths.numel() != B:
+        raise DynError(f"tdt_loss: targets {tuple(targets.shape)} must be [B, S >= 1], the lengths [B]")
+    loss = torch.empty(1, device=logits.device, dtype=F32)
+    nll = torch.empty(B, device=logits.device, dtype=F32)
+    grad = None
+    if want_grad:
+        grad = torch.empty_like(logits) if out is None else _c(out, "tdt_loss.out")
+        if grad.shape != logits.shape:
+            raise DynError(f"tdt_loss: out {tuple(grad.shape)} != logits {tuple(logits.shape)}")
+    ws = workspace(logits.device)
+    check(_L().dyn_tdt_loss(logits.data_ptr(), B, T, U1, N - D, ctypes.cast(dur, ctypes.c_void_p), D, targets.data_ptr(), targets.shape[1],
+                            logit_lengths.data_ptr(), target_lengths.data_ptr(), blank, sigma, TDT_REDUCTIONS[reduction], grad_scale,
+                            loss.data_ptr(), nll.data_ptr(), 0 if grad is None else grad.data_ptr(), ws.data_ptr(), ws.numel(),
+                            TDT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_tdt_loss")
+    return loss, nll, grad
+
+
+def tdt_lattice(B, T, U1, D, device):
+    """What the last ops.tdt_loss call of this (device, stream) left in the workspace, as absolute values: (alpha [B, T, U1],
+    beta [B, T, U1] (written only when a gradient was asked for), lp [B, T, U1, 2 + D], lse [B, T, U1, 2]).  The kernels store every
+    anti-diagonal relative to an integer base; the bases are added back here in float64 (host arithmetic, for tests)."""
+    off = (ctypes.c_int64 * 8)()
+    check(_L().dyn_tdt_loss_workspace_layout(B, T, U1, D, ctypes.cast(off, ctypes.c_void_p)), "dyn_tdt_loss_workspace_layout")
+    ws = workspace(device)
+    cells = B * T * U1
+
+    def view(i, n, shape):
+        return ws[off[i]:off[i] + 4 * n].view(F32).view(shape)
+
+    diag = (torch.arange(T, device=ws.device)[:, None] + torch.arange(U1, device=ws.device)[None, :]).expand(B, T, U1)
+    alpha = view(2, cells, (B, T, U1)).double() + view(4, B * (T + U1), (B, T + U1)).double().gather(1, diag.reshape(B, -1)).view(B, T, U1)
+    beta = view(3, cells, (B, T, U1)).double() + view(5, B * (T + U1), (B, T + U1)).double().gather(1, diag.reshape(B, -1)).view(B, T, U1)
+    return alpha, beta, view(0, cells * (2 + D), (B, T, U1, 2 + D)), view(1, cells * 2, (B, T, U1, 2))
+
+
+class TdtGreedyState:
+    """Device state of a greedy TDT decode (dyn_tdt_greedy_steps): istate [6, B] = frame pointer, last token, emit flag, done flag, output
+    count, steps taken; the LSTM's h / c per layer, the cached projector output, the step's logits and the outputs."""
+
+    def __init__(self, B, Hd, layers, N, n_max, start_token, device):
+        z = lambda *s, dt=F32: torch.zeros(*s, device=device, dtype=dt)           # noqa: E731
+        self.istate = z(6, B, dt=I32)
+        self.istate[1] = int(start_token)
+        self.istate[2] = 1                       # the first step primes the prediction network on the start token
+        self.h, self.c, self.h_new = z(layers, B, Hd), z(layers, B, Hd), z(layers, B, Hd)
+        self.dec, self.logits = z(B, Hd), z(B, N)
+        self.tokens, self.frames = z(B, n_max, dt=I32), z(B, n_max, dt=I32)
+        self.n_max = int(n_max)
+
+
+def tdt_greedy_steps(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, durations, blank, max_steps, n_steps):
+    """n_steps greedy steps of every live row, queued from one call.  enc [B, T, Hd]; valid int32 [B]; lstm_ptrs int64 DEVICE tensor
+    [4 * layers] of data pointers (w_ih, w_hh, b_ih, b_hh per layer); head_w [V1 + D, Hd]."""
+    _cc(enc, "tdt_greedy.enc"); _cc(valid, "tdt_greedy.valid", I32); _cc(embed, "tdt_greedy.embed"); _cc(lstm_ptrs, "tdt_greedy.lstm_ptrs", torch.int64)
+    for t, n in ((proj_w, "proj_w"), (proj_b, "proj_b"), (head_w, "head_w"), (head_b, "head_b")):
+        _cc(t, "tdt_greedy." + n)
+    dur, D = _durations_arg(durations)
+    B, T, Hd = enc.shape
+    layers = state.h.shape[0]
+    V1 = head_w.shape[0] - D
+    if (tuple(state.h.shape) != (layers, B, Hd) or lstm_ptrs.numel() != 4 * layers or embed.shape != (V1, Hd) or head_w.shape[1] != Hd
+            or tuple(proj_w.shape) != (Hd, Hd) or tuple(state.logits.shape) != (B, V1 + D) or valid.numel() != B or not 0 <= blank < V1):
+        raise DynError("tdt_greedy_steps: shapes of the state, the weights and enc do not fit together")
+    check(_L().dyn_tdt_greedy_steps(enc.data_ptr(), valid.data_ptr(), embed.data_ptr(), lstm_ptrs.data_ptr(), proj_w.data_ptr(), proj_b.data_ptr(),
+                                    head_w.data_ptr(), head_b.data_ptr(), state.istate.data_ptr(), state.h.data_ptr(), state.c.data_ptr(),
+                                    state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(), state.tokens.data_ptr(),
+                                    state.frames.data_ptr(), B, T, Hd, layers, V1, ctypes.cast(dur, ctypes.c_void_p), D, blank, state.n_max,
+                                    int(max_steps), int(n_steps), _stream()), "dyn_tdt_greedy_steps")

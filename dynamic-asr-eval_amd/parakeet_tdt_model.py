@@ -1,0 +1,351 @@
+"""ParakeetForTDT on MI355X: the token-and-duration transducer of the `nvidia/parakeet-tdt-*` checkpoints (`model_type: "parakeet_tdt"`,
+transformers modeling_parakeet.py: ParakeetForTDT) as transformers builds it in plain torch.  The encoder is ParakeetForCTC's
+(parakeet_model.py), kernel for kernel, without the `ctc_head`; behind it:
+  * `encoder_projector`: Linear(H -> Hd) on the encoder's last hidden states (the existing GEMM).
+  * the prediction network (ParakeetRNNTDecoder): Embedding(V + 1, Hd) -> LSTM(Hd, Hd, layers, batch_first) from a zero state ->
+    Linear(Hd, Hd), teacher-forced over the U + 1 decoder inputs.  Per layer x W_ih^T + b_ih of ALL steps is one GEMM, h W_hh^T + b_hh one
+    small GEMM per step, the cell is ops.lstm_cell (csrc/transducer.hip, gate order i, f, g, o).  Activations are kept time-major
+    ([U + 1, B, .]): a step's rows are contiguous.  Backward: ops.lstm_cell_bwd per step, the recurrent data gradient through
+    ops.linear_dgrad accumulated into the step below, the four weight gradients one product each over all steps at the end.
+  * the joint (ParakeetTDTJointNetwork): z = relu(enc[:, :, None] + dec[:, None]) (ops.joint), head Linear(Hd -> V + 1 + D) over
+    [B, T', U + 1, Hd] by the existing GEMM (M = B T' (U + 1)).  The decoder rows may be ONE row set shared by the batch
+    (decoder_input_ids [1, U + 1]: the loop's copies carry identical labels); their gradient then sums over the batch as well.
+  * the loss: ops.tdt_loss (transformers.loss.loss_tdt.tdt_loss and its autograd: arc log-probs, lattice, gradient), the five reductions
+    of tdt_loss with default "mean", plus sigma.  The whole lattice is materialised; above ops.TDT_WORKSPACE_BUDGET it is refused by name.
+  * generate: the duration-aware greedy decode of ParakeetTDTGenerationMixin with all state on the device (ops.tdt_greedy_steps); the
+    host reads the done flags once per chunk of steps.  The frame pointer advances by durations[argmax] (transformers adds the argmax
+    INDEX, the same thing for the released checkpoints' durations 0 .. D - 1), by 1 for a blank with duration 0.
+
+Refused by name before any launch: `attention_mask`, a `hidden_act` of the joint other than "relu", more than 8 durations, negative or
+unsorted durations, `model_type: "parakeet_rnnt"` (ParakeetForRNNT: no duration head; its oracle loss needs torchaudio), and whatever
+parakeet_model.make_config refuses of the encoder.  Out of scope: beam / MAES decoding, ragged batches in the model (the loss kernel's
+per-row lengths are built), a waveform front end, hipGraph replay and lockstep groups, chunking the joint over t.  No hub checkpoint is
+on the machine: transformers' ParakeetForTDT on the CPU with the same (random) state dict is the oracle in the tests."""
+from types import SimpleNamespace
+
+import torch
+
+from . import ops
+from . import parakeet_model as PM
+from ._lib import check, load
+
+DEFAULT_HEAD = dict(vocab_size=8193, decoder_hidden_size=640, num_decoder_layers=2, hidden_act="relu", max_symbols_per_step=10, pad_token_id=2,
+                    blank_token_id=8192, durations=(0, 1, 2, 3, 4), decoder_start_token_id=None)
+DEC, JOINT, PROJ = "decoder.", "joint.", "encoder_projector."
+FROZEN_IN_THE_LOOP = (PM.SUB, DEC)          # nvidia_ctc/lib.py:81-86: pre_encode and NeMo's `decoder`, here the prediction network
+
+
+def make_config(cfg=None):
+    """transformers' ParakeetTDTConfig (the object, or the nested dict of a config.json; None: its defaults) -> the flat dict this module
+    reads: parakeet_model.make_config's encoder keys plus the head's.  The joint's `hidden_act` is kept as `joint_hidden_act` (the
+    encoder has a `hidden_act` of its own)."""
+    get = (lambda k: cfg.get(k)) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k, None))
+    head = dict(DEFAULT_HEAD)
+    if cfg is not None:
+        mt = get("model_type")
+        if mt == "parakeet_rnnt" or (mt is None and get("durations") is None and type(cfg).__name__ == "ParakeetRNNTConfig"):
+            raise ops.DynError("ParakeetForRNNT (model_type \"parakeet_rnnt\") is not built: this module is the TDT head (ParakeetForTDT)")
+        if mt is not None and mt != "parakeet_tdt":
+            raise ops.DynError(f"model_type={mt!r} is not a ParakeetForTDT configuration (\"parakeet_tdt\")")
+        for k in head:
+            v = get(k)
+            if v is not None:
+                head[k] = v
+    out = PM.make_config({"encoder_config": None if cfg is None else get("encoder_config"), "vocab_size": head["vocab_size"],
+                          "pad_token_id": head["pad_token_id"]})
+    if head["hidden_act"] not in ops.JOINT_ACTS:
+        raise ops.DynError(f"hidden_act={head['hidden_act']!r} of the joint is not built ({sorted(ops.JOINT_ACTS)})")
+    out["joint_hidden_act"] = head["hidden_act"]
+    out["durations"] = ops.check_durations(head["durations"])
+    Hd, L, V1 = (int(head[k]) for k in ("decoder_hidden_size", "num_decoder_layers", "vocab_size"))
+    if Hd < 4 or Hd % 4:
+        raise ops.DynError(f"decoder_hidden_size={Hd} is not built: a positive multiple of 4 (16-byte rows)")
+    if not 1 <= L <= 8:
+        raise ops.DynError(f"num_decoder_layers={L} is not built (1 .. 8)")
+    blank = int(head["blank_token_id"])
+    if not 0 <= blank < V1:
+        raise ops.DynError(f"blank_token_id={blank} lies outside the vocabulary of {V1}")
+    start = head["decoder_start_token_id"]
+    if start is not None and not 0 <= int(start) < V1:
+        raise ops.DynError(f"decoder_start_token_id={start} lies outside the vocabulary of {V1}")
+    out.update(decoder_hidden_size=Hd, num_decoder_layers=L, blank_token_id=blank, max_symbols_per_step=int(head["max_symbols_per_step"]),
+               decoder_start_token_id=None if start is None else int(start))
+    if out["max_symbols_per_step"] < 1:
+        raise ops.DynError(f"max_symbols_per_step={out['max_symbols_per_step']} must be positive")
+    return out
+
+
+def config_from_json(path):
+    """An HF `config.json` of a parakeet_tdt checkpoint -> make_config."""
+    import json
+    with open(path) as f:
+        src = json.load(f)
+    if not isinstance(src, dict):
+        raise ops.DynError(f"{path}: expected a JSON object")
+    return make_config(src)
+
+
+def param_spec(c, pf=""):
+    """transformers' state dict of ParakeetForTDT: the encoder's names (parakeet_model.param_spec without the ctc_head), then
+    encoder_projector, decoder.embedding, decoder.lstm.{weight,bias}_{ih,hh}_l{k}, decoder.decoder_projector, joint.head."""
+    H, Hd, V1, D = c["hidden_size"], c["decoder_hidden_size"], c["vocab_size"], len(c["durations"])
+    spec = [s for s in PM.param_spec(c, pf) if not s[0].startswith(pf + "ctc_head.")]
+    spec += [(pf + PROJ + "weight", (Hd, H), None), (pf + PROJ + "bias", (Hd,), None), (pf + DEC + "embedding.weight", (V1, Hd), None)]
+    for k in range(c["num_decoder_layers"]):
+        spec += [(pf + DEC + f"lstm.weight_ih_l{k}", (4 * Hd, Hd), None), (pf + DEC + f"lstm.weight_hh_l{k}", (4 * Hd, Hd), None),
+                 (pf + DEC + f"lstm.bias_ih_l{k}", (4 * Hd,), None), (pf + DEC + f"lstm.bias_hh_l{k}", (4 * Hd,), None)]
+    spec += [(pf + DEC + "decoder_projector.weight", (Hd, Hd), None), (pf + DEC + "decoder_projector.bias", (Hd,), None),
+             (pf + JOINT + "head.weight", (V1 + D, Hd), None), (pf + JOINT + "head.bias", (V1 + D,), None)]
+    return spec
+
+
+def _host_ids(t, what, vocab):
+    """An integer tensor (host or device) or nested list -> int64 host tensor [rows, n], every id inside the vocabulary."""
+    t = torch.as_tensor(t).detach().cpu()
+    if t.numel() == 0:
+        t = t.to(torch.int64)
+    if t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+        raise ops.DynError(f"{what} must be an integer tensor [rows, n], got {tuple(t.shape)} {t.dtype}")
+    t = t.long()
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= vocab):
+        raise ops.DynError(f"{what}: ids must lie in [0, {vocab})")
+    return t
+
+
+class ParakeetForTDT(PM.ParakeetForCTC):
+    _make_config = staticmethod(make_config)
+    _param_spec = staticmethod(param_spec)
+    frozen_in_the_loop = FROZEN_IN_THE_LOOP
+    greedy_chunk = 32                                    # greedy steps queued per host call; the done flags are read once per chunk
+
+    def __init__(self, config=None, device="cuda:0"):
+        super().__init__(config, device)
+        c = self.cfg
+        self.Hd, self.V1, self.D = c["decoder_hidden_size"], c["vocab_size"], len(c["durations"])
+        self.blank = c["blank_token_id"]
+        self.start_token = c["decoder_start_token_id"] if c["decoder_start_token_id"] is not None else self.blank
+        self._tdt = None
+        names = [DEC + f"lstm.{n}_l{k}" for k in range(c["num_decoder_layers"]) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        self._lstm_ptrs = torch.tensor([self.P[n].data_ptr() for n in names], dtype=torch.int64, device=self.device)
+
+    def __call__(self, x=None, **kw):
+        return self.forward(kw.pop(self._input, x), **kw)
+
+    def _decoder_frozen(self):
+        return not any(self.trainable(n) for n, _ in self.spec if n.startswith(DEC))
+
+    def _encoder_frozen(self):
+        return not any(self.trainable(n) for n, _ in self.spec if n.startswith(("encoder.", PROJ)))
+
+    # ------------------------------------------------------------------ encoder
+    def _encode(self, h, ctx, vT, dims, v0):
+        P = self.P
+        T = dims[2]
+        x = self._layers_fwd(h, ctx, vT, self.position_table(T))
+        enc = ops.linear(x, P[PROJ + "weight"], P[PROJ + "bias"])
+        if ctx is not None:
+            ctx["head"] = x
+            ctx["dims"] = dims
+            ctx["valid"] = (v0, vT)
+        self._ctx = ctx
+        return SimpleNamespace(enc=enc, frames=T)
+
+    def encode(self, input_features, attention_mask=None):
+        """input_features [B, T, num_mel_bins] -> the projected encoder states [B, T', Hd] (transformers' `pooler_output`).  In grad mode
+        the encoder's activations are kept for a later head() + backward()."""
+        self._tdt = None
+        return PM.ParakeetForCTC.forward(self, input_features, attention_mask).enc
+
+    # ------------------------------------------------------------------ prediction network
+    def _decoder_fwd(self, ids, save):
+        """ids int64 host [Bd, U1] -> (p [U1, Bd, Hd] time-major, what _decoder_bwd needs or None)."""
+        P, c, Hd = self.P, self.cfg, self.Hd
+        Bd, U1 = ids.shape
+        ids_tm = ids.t().contiguous().to(torch.int32).to(self.device).view(-1)                     # [U1 * Bd], step-major
+        x = torch.empty(U1, Bd, Hd, device=self.device, dtype=torch.float32)
+        check(load().dyn_embedding_fwd(ids_tm.data_ptr(), P[DEC + "embedding.weight"].data_ptr(), None, x.data_ptr(), U1 * Bd, Hd, self.V1, 1,
+                                       torch.cuda.current_stream().cuda_stream), "dyn_embedding_fwd")
+        kept = []
+        zeros = torch.zeros(Bd, Hd, device=self.device, dtype=torch.float32)
+        for k in range(c["num_decoder_layers"]):
+            w_ih, w_hh, b_ih, b_hh = (P[DEC + f"lstm.{n}_l{k}"] for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+            xg = ops.linear(x.view(U1 * Bd, Hd), w_ih, b_ih).view(U1, Bd, 4 * Hd)                  # every step's input half: one GEMM
+            h_all = torch.empty(U1, Bd, Hd, device=self.device, dtype=torch.float32)
+            c_all = torch.empty(U1, Bd, Hd, device=self.device, dtype=torch.float32)
+            g_all = torch.empty(U1, Bd, 4 * Hd, device=self.device, dtype=torch.float32) if save else None
+            for u in range(U1):
+                hg = ops.linear(h_all[u - 1] if u else zeros, w_hh, b_hh)
+                ops.lstm_cell(xg[u], hg, c_all[u - 1] if u else None, out=(c_all[u], h_all[u], g_all[u] if save else None))
+            if save:
+                kept.append((x, h_all, c_all, g_all))
+            x = h_all
+        p = ops.linear(x.view(U1 * Bd, Hd), P[DEC + "decoder_projector.weight"], P[DEC + "decoder_projector.bias"]).view(U1, Bd, Hd)
+        return p, ((ids_tm, kept) if save else None)
+
+    def _decoder_bwd(self, dp, saved):
+        """dp [U1, Bd, Hd] time-major: accumulates the prediction network's gradients."""
+        P, G, c, Hd = self.P, self.G, self.cfg, self.Hd
+        ids_tm, kept = saved
+        U1, Bd, _ = dp.shape
+        top = kept[-1][1]
+        d = self._lin_bwd(dp.view(U1 * Bd, Hd), top.view(U1 * Bd, Hd), DEC + "decoder_projector.weight", DEC + "decoder_projector.bias")
+        for k in reversed(range(c["num_decoder_layers"])):
+            x, h_all, c_all, g_all = kept[k]
+            names = [DEC + f"lstm.{n}_l{k}" for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+            w_ih, w_hh = P[names[0]], P[names[1]]
+            dh_all = d.view(U1, Bd, Hd)                      # the gradient from above; the recurrent gradient is added step by step
+            dg_all = torch.empty_like(g_all)
+            dc = None
+            for u in reversed(range(U1)):
+                _, dc = ops.lstm_cell_bwd(dh_all[u], dc, g_all[u], c_all[u - 1] if u else None, c_all[u], dgates=dg_all[u])
+                if u:
+                    ops.linear_dgrad(dg_all[u], w_hh, out=dh_all[u - 1], beta=1.0)
+            dg = dg_all.view(U1 * Bd, 4 * Hd)
+            if any(self.trainable(n) for n in names):
+                self._wgrad(dg, x.view(U1 * Bd, Hd), G[names[0]], G[names[2]])
+                if U1 > 1:                                   # h_{-1} = 0: step 0 adds nothing to the recurrent weight
+                    self._wgrad(dg_all[1:].view((U1 - 1) * Bd, 4 * Hd), h_all[:-1].view((U1 - 1) * Bd, Hd), G[names[1]], None)
+                ops.colsum(dg, G[names[3]], beta=1.0)
+            d = ops.linear_dgrad(dg, w_ih)
+        if self.trainable(DEC + "embedding.weight"):
+            check(load().dyn_embedding_bwd(ids_tm.data_ptr(), d.data_ptr(), G[DEC + "embedding.weight"].data_ptr(), U1 * Bd, Hd, self.V1, 1.0,
+                                           torch.cuda.current_stream().cuda_stream), "dyn_embedding_bwd")
+
+    # ------------------------------------------------------------------ joint, loss
+    def head(self, enc, decoder_input_ids, labels=None, reduction="mean", sigma=0.0, grad_scale=1.0, n_active=None, label_lengths=None):
+        """The prediction network, the joint and (with labels) the TDT loss on the first n_active rows of enc [B, T', Hd].
+        decoder_input_ids [n_active or 1, U + 1] (one row: shared by every copy); labels [same rows, U], padded with pad_token_id
+        (transformers counts `labels != pad_token_id`; `label_lengths`, one per label row, replaces that count: unpadded labels may
+        hold the pad id).
+        Returns SimpleNamespace(logits [n_active, T', U + 1, V + 1 + D], loss [1] or None, nll [n_active] or None).  In grad mode the
+        loss's gradient w.r.t. the logits, times grad_scale, is kept for backward()."""
+        c, P, Hd = self.cfg, self.P, self.Hd
+        B, T, _ = enc.shape
+        nb = B if n_active is None else int(n_active)
+        if not 1 <= nb <= B:
+            raise ops.DynError(f"n_active={n_active!r} must lie in 1 .. {B}")
+        ids = _host_ids(decoder_input_ids, "decoder_input_ids", self.V1)
+        if ids.shape[0] not in (1, nb) or ids.shape[1] < 1:
+            raise ops.DynError(f"decoder_input_ids {tuple(ids.shape)} must be [{nb} or 1, U + 1]")
+        U1 = ids.shape[1]
+        grad_mode = torch.is_grad_enabled() and self._ctx is not None
+        with ops.use_workspace(self._scratch()):
+            run_dec_bwd = grad_mode and not self._decoder_frozen()
+            p, dec_saved = self._decoder_fwd(ids, run_dec_bwd)
+            e = enc[:nb].contiguous()
+            z = ops.joint(e, p.transpose(0, 1), c["joint_hidden_act"])
+            logits = ops.linear(z, P[JOINT + "head.weight"], P[JOINT + "head.bias"])
+            loss = nll = dlogits = None
+            if labels is not None:
+                lab = _host_ids(labels, "labels", self.V1)
+                if lab.shape[0] != ids.shape[0] or lab.shape[1] != U1 - 1:
+                    raise ops.DynError(f"labels {tuple(lab.shape)} must be [{ids.shape[0]}, {U1 - 1}]: one label per decoder input after the start token")
+                if lab.shape[0] == 1 and nb > 1:
+                    lab = lab.expand(nb, -1)
+                if label_lengths is None:
+                    tlen = (lab != c["pad_token_id"]).sum(-1).to(torch.int32)
+                else:
+                    tlen = torch.as_tensor(list(label_lengths), dtype=torch.int32).reshape(-1)
+                    if tlen.numel() == 1 and nb > 1:
+                        tlen = tlen.expand(nb).contiguous()
+                    if tlen.numel() != nb or int(tlen.min()) < 0 or int(tlen.max()) > U1 - 1:
+                        raise ops.DynError(f"label_lengths {tlen.tolist()} must be {nb} (or 1) values in 0 .. {U1 - 1}")
+                tg = lab.to(torch.int32).contiguous() if U1 > 1 else torch.zeros(nb, 1, dtype=torch.int32)
+                loss, nll, dlogits = ops.tdt_loss(logits, tg.to(self.device), torch.full((nb,), T, dtype=torch.int32, device=self.device),
+                                                  tlen.to(self.device), self.blank, c["durations"], float(sigma), reduction, float(grad_scale),
+                                                  want_grad=grad_mode)
+        self._tdt = dict(z=z, p_rows=ids.shape[0], dec=dec_saved, rows=nb, dlogits=dlogits) if grad_mode else None
+        return SimpleNamespace(logits=logits, loss=loss, nll=nll, frames=T)
+
+    def forward(self, input_features, decoder_input_ids=None, labels=None, attention_mask=None, reduction="mean", sigma=0.0, grad_scale=1.0,
+                n_active=None, label_lengths=None):
+        """input_features [B, T, num_mel_bins] float32 on the device, decoder_input_ids [B or 1, U + 1] -> SimpleNamespace(logits
+        [B, T', U + 1, V + 1 + D], loss, nll, frames = T', enc [B, T', Hd]).  `attention_mask` is refused: every frame is valid."""
+        if attention_mask is not None:
+            raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (ragged batches are out of scope; "
+                               "the loss kernel's per-row lengths are reached through ops.tdt_loss)")
+        if decoder_input_ids is None:
+            raise ops.DynError("forward() needs decoder_input_ids [B or 1, U + 1] (start token + labels); generate() decodes without them")
+        enc = self.encode(input_features, attention_mask)
+        out = self.head(enc, decoder_input_ids, labels, reduction, sigma, grad_scale, n_active, label_lengths)
+        out.enc = enc
+        return out
+
+    # ------------------------------------------------------------------ backward
+    def backward(self, grad_logits=None, n_active=None):
+        """Accumulates every parameter's gradient into flat_grads: of grad_scale * loss of the last grad-mode forward with labels, or of
+        sum(grad_logits * logits) for a given grad_logits [n_active, T', U + 1, V + 1 + D].  The joint ran on the first n_active rows of
+        the forward; under batch_renorm_training() the encoder's backward still covers every row (zeros for the rest)."""
+        t = self._tdt
+        if t is None:
+            raise ops.DynError("backward() without a grad-mode forward through the joint")
+        if n_active is not None and int(n_active) != t["rows"]:
+            raise ops.DynError(f"backward(n_active={n_active}) after a forward whose joint ran on {t['rows']} rows")
+        g = t["dlogits"] if grad_logits is None else grad_logits
+        if g is None:
+            raise ops.DynError("backward() needs grad_logits: the last forward had no labels")
+        if tuple(g.shape) != tuple(t["z"].shape[:3]) + (self.V1 + self.D,):
+            raise ops.DynError(f"grad_logits {tuple(g.shape)} does not fit the joint logits")
+        t["g"] = g.contiguous()
+        B = self._ctx["dims"][0]
+        nb = B if self._ctx_brn else t["rows"]          # batch renorm: the gradient reaches every row through the batch statistics
+        # the parent's surface hands dL/dlogits [nb, ..] down to _backward_encoder; the joint's gradient waits in self._tdt instead
+        # (its rows may be fewer than the encoder's), the placeholder only carries nb
+        try:
+            super().backward(torch.empty(nb, 0, device=self.device), None if nb == B else nb)
+        finally:
+            self._tdt = None
+
+    def _backward_encoder(self, ctx, grad_logits, nb, cut):
+        t, P = self._tdt, self.P
+        v0, vT = ctx["valid"]
+        T = ctx["dims"][2]
+        z, g = t["z"], t["g"]
+        rows, U1, Hd = z.shape[0], z.shape[2], self.Hd
+        dz = self._lin_bwd(g.view(-1, g.shape[-1]), z.view(-1, Hd), JOINT + "head.weight", JOINT + "head.bias").view(z.shape)
+        need_dec, need_enc = t["dec"] is not None, not self._encoder_frozen()
+        if not (need_dec or need_enc):
+            return None
+        de, dp = ops.joint_bwd(dz, z, torch.empty(t["p_rows"], U1, Hd, device="meta"), self.cfg["joint_hidden_act"], want_de=need_enc,
+                               want_dp=need_dec, time_major=True)
+        if need_dec:
+            self._decoder_bwd(dp, t["dec"])
+        if not need_enc:
+            return None
+        if rows < nb:                                    # batch renorm: zero gradient rows for the copies the loss did not see
+            full = torch.zeros(nb, T, Hd, device=self.device, dtype=torch.float32)
+            full[:rows] = de
+            de = full
+        dx = self._lin_bwd(de, cut(ctx["head"]), PROJ + "weight", PROJ + "bias")
+        dh = self._layers_bwd(ctx, dx, nb, T, self.position_table(T), vT, cut)
+        if not self._below_frozen():
+            self._subsample_bwd(cut(ctx["sub"]), dh)
+        return None
+
+    # ------------------------------------------------------------------ greedy decode
+    def generate(self, input_features=None, enc=None):
+        """Greedy TDT decode of input_features [B, T, num_mel_bins] (or of projected encoder states `enc` [B, T', Hd]) ->
+        SimpleNamespace(tokens int32 [B, Nmax], frames int32 [B, Nmax] (the encoder frame at which each non-blank token was emitted),
+        count int32 [B], steps int32 [B]).  At most max_symbols_per_step * T' steps per row, transformers' derived max_length."""
+        c = self.cfg
+        with torch.no_grad():
+            if enc is None:
+                keep = self._ctx, self._tdt
+                enc = self.encode(input_features)
+                self._ctx, self._tdt = keep
+            enc = enc.detach().contiguous()
+            B, T, _ = enc.shape
+            cap = c["max_symbols_per_step"] * T
+            st = ops.TdtGreedyState(B, self.Hd, c["num_decoder_layers"], self.V1 + self.D, cap, self.start_token, self.device)
+            valid = torch.full((B,), T, dtype=torch.int32, device=self.device)
+            P = self.P
+            done = 0
+            while done < cap:
+                n = min(self.greedy_chunk, cap - done)
+                ops.tdt_greedy_steps(enc, valid, P[DEC + "embedding.weight"], self._lstm_ptrs, P[DEC + "decoder_projector.weight"],
+                                     P[DEC + "decoder_projector.bias"], P[JOINT + "head.weight"], P[JOINT + "head.bias"], st, c["durations"],
+                                     self.blank, cap, n)
+                done += n
+                if bool(st.istate[3].all()):             # the one host read of the chunk
+                    break
+        return SimpleNamespace(tokens=st.tokens, frames=st.frames, count=st.istate[4], steps=st.istate[5])

@@ -183,6 +183,9 @@ def load_pretrained_model(args, device):
     if kind == 'lasr_ctc':
         raise ops.DynError(f'{cfg_path}: model_type "lasr_ctc" takes log-mel features [B, T, num_mel_bins], not waveforms: build '
                            'lasr_model.LasrForCTC and drive it with nvidia_ctc_lib.dynamic_eval (the reference\'s nvidia_ctc/lib.py)')
+    if kind == 'parakeet_tdt':
+        raise ops.DynError(f'{cfg_path}: model_type "parakeet_tdt" is a transducer over log-mel features [B, T, num_mel_bins], not a CTC model '
+                           'over waveforms: build parakeet_tdt_model.ParakeetForTDT and drive it with parakeet_tdt_lib.dynamic_eval')
     lang, adapter_sd, tokenizer = getattr(args, 'target_lang', '') or '', None, None
     if lang:
         if kind not in ('', 'wav2vec2') or not (args.checkpoint and os.path.isdir(args.checkpoint)):

@@ -975,6 +975,65 @@ int dyn_convmod_brn_bwd(const float* c, const float* stats, const float* ds, flo
                         float wgrad_beta, const int32_t* valid, int64_t B, int64_t T, int64_t C, int32_t act, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The transducer head of ParakeetForTDT (`model_type: "parakeet_tdt"`, transformers modeling_parakeet.py / generation_parakeet.py /
+ * loss/loss_tdt.py; csrc/transducer.hip).  fp32, fixed-order sums, no float atomics, bit-reproducible.
+ *   dyn_lstm_cell_fwd     replaces the cell of torch.nn.LSTM (ParakeetRNNTDecoder.lstm): gates = xg + hg, both [Bd, 4 Hd] pre-activations in
+ *                         torch's order i | f | g | o (xg = x W_ih^T + b_ih for all steps from one GEMM, hg = h W_hh^T + b_hh per step);
+ *                         c = f * c_prev + i * g, h = o * tanh(c); `gates` (null: not saved) receives the four activations.  c_prev null = zeros.
+ *   dyn_lstm_cell_bwd     replaces its autograd: from dh, dc_next (null = zeros), the saved gates, c_prev (null = zeros) and c, the
+ *                         pre-activation gradients dgates [Bd, 4 Hd] and dc_prev.  The data and weight gradients are GEMMs of dgates.
+ *   dyn_joint_fwd         replaces ACT2FN[hidden_act](encoder[:, :, None] + decoder[:, None]) of ParakeetRNNTJointNetwork.forward:
+ *                         z[b, t, u, :] = relu(e[b, t, :] + p[b * p_stride_b + u * p_stride_u + :]); p_stride_b = 0 shares one p among the
+ *                         batch rows.  act 0 = relu, anything else DYN_E_UNSUPPORTED.  Hd and the strides multiples of 4, 16-byte aligned.
+ *   dyn_joint_bwd         replaces its autograd: de[b, t, :] = sum_u dz * [z > 0] (u ascending), dp[b, u, :] = sum_t the same (t ascending;
+ *                         shared_p: one set of rows, summed over b ascending, then t).  de or dp may be null.
+ *   dyn_tdt_loss          replaces transformers.loss.loss_tdt.tdt_loss and its autograd.  logits [B, T, U1, V1 + D] (V1 = vocabulary with the
+ *                         blank, U1 = longest target + 1), targets int32 [B, S], per-row logit_lengths / target_lengths (clamped into
+ *                         the tensor), `durations` a HOST array of 1 .. 8 strictly ascending non-negative values with at least one
+ *                         positive.  Arcs from (t, u): a blank arc of every duration d > 0 to (t + d, u), a label arc of every duration
+ *                         to (t + d, u + 1); the terminal sums the blank arcs with t + d == T_b at u == U_b; sigma is subtracted from the
+ *                         token log-probs.  Four launches: arc log-probs (one wave per logits row: the two log-sum-exps, blank, label and
+ *                         duration log-probs), alpha and beta over anti-diagonals (one workgroup per row and direction, a diagonal
+ *                         strided over its threads, one barrier per diagonal, each diagonal stored relative to an integer base so that
+ *                         the stored values stay O(1)), the reduction, and with `grad` the gradient of grad_scale * loss w.r.t. the
+ *                         logits from the arc posteriors (rows at t >= T_b or u > U_b exact zeros; grad may be logits).  An unreachable
+ *                         terminal gives nll = +inf and an all-zero gradient for that row.  reduction 0 sum, 1 mean_batch,
+ *                         2 mean (nll_b / U_b, then the batch mean), 3 mean_volume, 4 none (loss = the sum; the rows in nll_per_row).
+ *                         The whole lattice lives in `workspace`; workspace_budget_bytes > 0 refuses a larger one by name
+ *                         (DYN_E_WORKSPACE): chunking over t is not built.
+ *   dyn_tdt_loss_workspace_layout   byte offsets of lp, lse, alpha, beta, abase, bbase, ll, nll in the workspace (tests).
+ *   dyn_tdt_greedy_steps  replaces ParakeetTDTGenerationMixin's greedy loop, n_steps steps per call with all state on the device, in
+ *                         the manner of dyn_decoder_steps.  istate int32 [6, B]: frame pointer, last token, emit flag, done flag, output
+ *                         count, steps taken (the caller starts with last token = the start token and emit = 1: the first step then
+ *                         primes the prediction network).  A step: if emit, the LSTM layers (one wave per hidden unit over [x ; h]) and
+ *                         the projector on the last token; logits = head . relu(enc[frame] + dec); argmax over the V1 token and the D
+ *                         duration logits (lowest index on ties); the frame pointer advances by durations[argmax], by 1 for a blank
+ *                         with duration 0; a non-blank is appended to tokens / frames [B, n_max] and sets emit.  A row is done when
+ *                         its pointer reaches valid[b], after max_steps steps or n_max outputs; a done row launches no work.
+ *                         `lstm_ptrs`: DEVICE array of 4 * layers pointers (w_ih, w_hh, b_ih, b_hh per layer).
+ * Null pointers and sizes out of range -> DYN_E_ARG, all before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int dyn_lstm_cell_fwd(const float* xg, const float* hg, const float* c_prev, float* c, float* h, float* gates, int64_t Bd, int64_t Hd,
+                      void* stream);
+int dyn_lstm_cell_bwd(const float* dh, const float* dc_next, const float* gates, const float* c_prev, const float* c, float* dgates,
+                      float* dc_prev, int64_t Bd, int64_t Hd, void* stream);
+int dyn_joint_fwd(const float* e, const float* p, float* z, int64_t B, int64_t T, int64_t U1, int64_t Hd, int64_t p_stride_b,
+                  int64_t p_stride_u, int32_t act, void* stream);
+int dyn_joint_bwd(const float* dz, const float* z, float* de, float* dp, int64_t B, int64_t T, int64_t U1, int64_t Hd, int32_t shared_p,
+                  int64_t dp_stride_b, int64_t dp_stride_u, int32_t act, void* stream);
+int64_t dyn_tdt_loss_workspace_bytes(int64_t B, int64_t T, int64_t U1, int64_t D);
+int dyn_tdt_loss_workspace_layout(int64_t B, int64_t T, int64_t U1, int64_t D, int64_t* offsets8);
+int dyn_tdt_loss(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+                 const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank,
+                 float sigma, int32_t reduction, float grad_scale, float* loss, float* nll_per_row, float* grad, void* workspace,
+                 int64_t workspace_bytes, int64_t workspace_budget_bytes, void* stream);
+int dyn_tdt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs, const float* proj_w,
+                         const float* proj_b, const float* head_w, const float* head_b, int32_t* istate, float* h, float* c, float* h_new,
+                         float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd, int64_t layers,
+                         int64_t V1, const int32_t* durations, int64_t D, int32_t blank, int64_t n_max, int64_t max_steps,
+                         int32_t n_steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
