@@ -5,6 +5,10 @@
 //   * ACT2FN["relu"](encoder + decoder) and its autograd    dyn_joint_fwd / dyn_joint_bwd (the broadcast sum over [B, T, U + 1, Hd])
 //   * tdt_loss: log_softmax of the token and duration logits, the gather of the blank / label columns, the anti-diagonal lattice and,
 //     through autograd, its gradient                        dyn_tdt_loss (arc log-probs, alpha / beta, arc posteriors -> dlogits)
+//     The same three passes for a joint that is never whole: dyn_tdt_arcs_chunk (the arc log-probs of the frames [t0, t0 + Tc) into a
+//     caller-owned lattice state), dyn_tdt_lattice_run (alpha / beta and the reduction on that state), dyn_tdt_grad_chunk (dlogits of
+//     a chunk), and dyn_joint_bwd_chunk (de of a chunk's frames, dp accumulated over the chunks in launch order).  One set of
+//     kernels: the whole forms are the chunk forms at t0 = 0, Tc = T, so every output is bit-equal whatever the chunking.
 //   * ParakeetTDTGenerationMixin's greedy loop              dyn_tdt_greedy_steps (all state on the device, no host round trip per token)
 //
 // fp32 throughout, every sum in a fixed order, no float atomics; argument errors come back as codes before any launch.
@@ -98,24 +102,27 @@ __device__ __forceinline__ void acc_masked(float4& s, const float4 g, const floa
     s.x += zz.x > 0.f ? g.x : 0.f; s.y += zz.y > 0.f ? g.y : 0.f; s.z += zz.z > 0.f ? g.z : 0.f; s.w += zz.w > 0.f ? g.w : 0.f;
 }
 
-// de[b, t, :] = sum_u dz * [z > 0], u ascending
+// de[b, t, :] = sum_u dz * [z > 0], u ascending; de rows of one b are contiguous, batch rows de_sb4 float4 apart (T * H4: the whole
+// tensor; more: the frames [t0, t0 + T) of a longer one, the chunk form)
 __global__ __launch_bounds__(256) void joint_bwd_e_kernel(const float* __restrict__ dz, const float* __restrict__ z, float* __restrict__ de,
-                                                          int64_t BT, int64_t U1, int64_t H4) {
-    const int64_t n = BT * H4;
+                                                          int64_t B, int64_t T, int64_t U1, int64_t H4, int64_t de_sb4) {
+    const int64_t n = B * T * H4;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t h = idx % H4, bt = idx / H4;
+        const int64_t h = idx % H4, bt = idx / H4, b = bt / T, t = bt - b * T;
         float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int64_t u = 0; u < U1; ++u) {
             const int64_t o = (bt * U1 + u) * H4 + h;
             acc_masked(s, reinterpret_cast<const float4*>(dz)[o], reinterpret_cast<const float4*>(z)[o]);
         }
-        reinterpret_cast<float4*>(de)[idx] = s;
+        reinterpret_cast<float4*>(de)[b * de_sb4 + t * H4 + h] = s;
     }
 }
 
-// dp[b, u, :] = sum_t dz * [z > 0], t ascending; shared: one dp row set, summed over b (ascending, outer) as well
+// dp[b, u, :] = sum_t dz * [z > 0], t ascending; shared: one dp row set, summed over b (ascending, outer) as well.  accumulate: the
+// sum of these frames is added to what dp holds (the chunk form: one launch per chunk of frames, in stream order)
 __global__ __launch_bounds__(256) void joint_bwd_p_kernel(const float* __restrict__ dz, const float* __restrict__ z, float* __restrict__ dp,
-                                                          int64_t B, int64_t T, int64_t U1, int64_t H4, int shared, int64_t dp_sb, int64_t dp_su) {
+                                                          int64_t B, int64_t T, int64_t U1, int64_t H4, int shared, int64_t dp_sb, int64_t dp_su,
+                                                          int accumulate) {
     const int64_t Bo = shared ? 1 : B, n = Bo * U1 * H4;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
         const int64_t h = idx % H4, r = idx / H4, u = r % U1, bo = r / U1;
@@ -126,13 +133,19 @@ __global__ __launch_bounds__(256) void joint_bwd_p_kernel(const float* __restric
                 const int64_t o = ((b * T + t) * U1 + u) * H4 + h;
                 acc_masked(s, reinterpret_cast<const float4*>(dz)[o], reinterpret_cast<const float4*>(z)[o]);
             }
-        reinterpret_cast<float4*>(dp + bo * dp_sb + u * dp_su)[h] = s;
+        float4* out = reinterpret_cast<float4*>(dp + bo * dp_sb + u * dp_su) + h;
+        if (accumulate) {
+            const float4 was = *out;
+            s = make_float4(was.x + s.x, was.y + s.y, was.z + s.z, was.w + s.w);
+        }
+        *out = s;
     }
 }
 
 // ---- TDT arc log-probabilities ---------------------------------------------------------------------------------------------
 struct TdtDims {
-    int64_t B, T, U1;       // logits [B, T, U1, N]
+    int64_t B, T, U1;       // the lattice [B, T, U1]
+    int64_t t0, Tc;         // the row kernels' logits [B, Tc, U1, N] hold the frames [t0, t0 + Tc) (0, T: the whole lattice; a chunk may overhang T)
     int64_t V1, N;          // V1 = V + 1 token classes (the blank among them), N = V1 + D
     int64_t S;              // targets [B, S]
     int32_t blank;
@@ -145,15 +158,19 @@ __device__ __forceinline__ int row_U(const int32_t* tlen, int64_t b, const TdtDi
     return clampi(tlen[b], 0, (int)(d.U1 - 1 < d.S ? d.U1 - 1 : d.S));
 }
 
-// One wave per logits row: lp[row] = (blank, label, D durations) log-probs, lse[row] = (token lse, duration lse).
+// One wave per logits row (b, tc, u) of the frames [t0, t0 + Tc): lp[cell] = (blank, label, D durations) log-probs, lse[cell] = (token lse,
+// duration lse) of the lattice cell (b, t0 + tc, u).  Rows of a chunk past the lattice's last frame are skipped.
 __global__ __launch_bounds__(64 * WPB) void tdt_arcs_kernel(const float* __restrict__ logits, const int32_t* __restrict__ targets,
                                                             const int32_t* __restrict__ tlen, float* __restrict__ lp, float* __restrict__ lse,
                                                             TdtDims d) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t rows = d.B * d.T * d.U1;
+    const int64_t rows = d.B * d.Tc * d.U1;
     const int D = d.durs.n, C = 2 + D;
-    for (int64_t row = (int64_t)blockIdx.x * WPB + w; row < rows; row += (int64_t)gridDim.x * WPB) {
-        const float* x = logits + row * d.N;
+    for (int64_t crow = (int64_t)blockIdx.x * WPB + w; crow < rows; crow += (int64_t)gridDim.x * WPB) {
+        const int64_t u = crow % d.U1, b = crow / (d.U1 * d.Tc), t = d.t0 + (crow / d.U1) % d.Tc;
+        if (t >= d.T) continue;                                       // wave-uniform
+        const int64_t row = (b * d.T + t) * d.U1 + u;                 // the lattice cell
+        const float* x = logits + crow * d.N;
         float m = -INFINITY;
         for (int c = lane; c < d.V1; c += 64) m = fmaxf(m, x[c]);
         m = dyn::wave_max(m);
@@ -166,7 +183,6 @@ __global__ __launch_bounds__(64 * WPB) void tdt_arcs_kernel(const float* __restr
         const float dm = dyn::wave_max(dv);
         const float ds = dyn::wave_sum(lane < D ? expf(dv - dm) : 0.f);
         const float ld = dm + logf(ds);
-        const int64_t u = row % d.U1, b = row / (d.U1 * d.T);
         float* o = lp + row * C;
         if (lane == 0) {
             o[0] = x[d.blank] - lt - d.sigma;
@@ -375,6 +391,7 @@ __global__ void tdt_loss_reduce_kernel(const float* __restrict__ nll, const int3
 // One wave per logits row (b, t, u).  With the arc posteriors g_b[i] (blank arc of duration i), g_l[i] (label arc), Gb = sum g_b,
 // Gl = sum g_l: dtoken[v] = softmax_v * (Gb + Gl) - Gb [v = blank] - Gl [v = target], ddur[i] = softmax_i * (Gb + Gl) - g_b[i] - g_l[i],
 // times grad_scale * row weight.  Rows at t >= T_b or u > U_b, and every row of an unreachable lattice, are zeros.  grad may be logits.
+// logits / grad hold the frames [t0, t0 + Tc) ([B, Tc, U1, N]); lp, lse, alpha, beta are the whole lattice's.
 __global__ __launch_bounds__(64 * WPB) void tdt_grad_kernel(const float* logits, const int32_t* __restrict__ targets,
                                                             const int32_t* __restrict__ ilen, const int32_t* __restrict__ tlen,
                                                             const float* __restrict__ lp, const float* __restrict__ lse,
@@ -382,11 +399,12 @@ __global__ __launch_bounds__(64 * WPB) void tdt_grad_kernel(const float* logits,
                                                             const float* __restrict__ abase, const float* __restrict__ bbase,
                                                             const float* __restrict__ ll, float* grad, float grad_scale, int reduction, TdtDims d) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t rows = d.B * d.T * d.U1;
+    const int64_t rows = d.B * d.Tc * d.U1;
     const int D = d.durs.n, C = 2 + D, U1 = (int)d.U1;
     for (int64_t row = (int64_t)blockIdx.x * WPB + w; row < rows; row += (int64_t)gridDim.x * WPB) {
-        const int u = (int)(row % d.U1), t = (int)((row / d.U1) % d.T);
-        const int64_t b = row / (d.U1 * d.T);
+        const int u = (int)(row % d.U1);
+        const int64_t b = row / (d.U1 * d.Tc), tt = d.t0 + (row / d.U1) % d.Tc;      // a chunk's frame may lie past the lattice: zeros
+        const int t = (int)(tt < d.T ? tt : d.T);
         const int T = row_T(ilen, b, d), U = row_U(tlen, b, d);
         const float* x = logits + row * d.N;
         float* g = grad + row * d.N;
@@ -624,19 +642,41 @@ extern "C" int dyn_joint_fwd(const float* e, const float* p, float* z, int64_t B
     return dyn::check_launch("dyn_joint_fwd");
 }
 
-extern "C" int dyn_joint_bwd(const float* dz, const float* z, float* de, float* dp, int64_t B, int64_t T, int64_t U1, int64_t Hd,
-                             int32_t shared_p, int64_t dp_stride_b, int64_t dp_stride_u, int32_t act, void* stream) {
-    DYN_REQUIRE(act == 0, DYN_E_UNSUPPORTED, "dyn_joint_bwd: hidden_act %d is not built (0 = relu)", act);
-    DYN_REQUIRE(dz && z && (de || dp) && B > 0 && T > 0 && U1 > 0 && Hd > 0 && Hd % 4 == 0, DYN_E_ARG, "dyn_joint_bwd: bad arguments");
+namespace {
+
+// dyn_joint_bwd (de_stride_b = T * Hd, no accumulation) and dyn_joint_bwd_chunk: the same two launches
+int joint_bwd(const char* who, const float* dz, const float* z, float* de, float* dp, int64_t B, int64_t T, int64_t U1, int64_t Hd,
+              int32_t shared_p, int64_t de_stride_b, int64_t dp_stride_b, int64_t dp_stride_u, int32_t dp_accumulate, int32_t act, void* stream) {
+    DYN_REQUIRE(act == 0, DYN_E_UNSUPPORTED, "%s: hidden_act %d is not built (0 = relu)", who, act);
+    DYN_REQUIRE(dz && z && (de || dp) && B > 0 && T > 0 && U1 > 0 && Hd > 0 && Hd % 4 == 0, DYN_E_ARG, "%s: bad arguments", who);
+    DYN_REQUIRE(!de || (de_stride_b >= T * Hd && de_stride_b % 4 == 0), DYN_E_ARG,
+                "%s: de_stride_b must be a multiple of 4, at least the chunk's frames * Hd", who);
     DYN_REQUIRE(!dp || (dp_stride_b >= 0 && dp_stride_b % 4 == 0 && dp_stride_u >= Hd && dp_stride_u % 4 == 0), DYN_E_ARG,
-                "dyn_joint_bwd: dp strides must be multiples of 4, dp_stride_u >= Hd");
-    DYN_REQUIRE(!(((uintptr_t)dz | (uintptr_t)z | (uintptr_t)de | (uintptr_t)dp) & 15), DYN_E_ARG, "dyn_joint_bwd: pointers must be 16-byte aligned");
+                "%s: dp strides must be multiples of 4, dp_stride_u >= Hd", who);
+    DYN_REQUIRE(dp_accumulate == 0 || dp_accumulate == 1, DYN_E_ARG, "%s: dp_accumulate must be 0 or 1", who);
+    DYN_REQUIRE(!(((uintptr_t)dz | (uintptr_t)z | (uintptr_t)de | (uintptr_t)dp) & 15), DYN_E_ARG, "%s: pointers must be 16-byte aligned", who);
     hipStream_t st = (hipStream_t)stream;
-    if (de) hipLaunchKernelGGL(joint_bwd_e_kernel, dim3(grid_for(B * T * (Hd / 4), 256)), dim3(256), 0, st, dz, z, de, B * T, U1, Hd / 4);
+    if (de)
+        hipLaunchKernelGGL(joint_bwd_e_kernel, dim3(grid_for(B * T * (Hd / 4), 256)), dim3(256), 0, st, dz, z, de, B, T, U1, Hd / 4,
+                           de_stride_b / 4);
     if (dp)
         hipLaunchKernelGGL(joint_bwd_p_kernel, dim3(grid_for((shared_p ? 1 : B) * U1 * (Hd / 4), 256)), dim3(256), 0, st, dz, z, dp, B, T, U1,
-                           Hd / 4, (int)(shared_p != 0), dp_stride_b, dp_stride_u);
-    return dyn::check_launch("dyn_joint_bwd");
+                           Hd / 4, (int)(shared_p != 0), dp_stride_b, dp_stride_u, (int)dp_accumulate);
+    return dyn::check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int dyn_joint_bwd(const float* dz, const float* z, float* de, float* dp, int64_t B, int64_t T, int64_t U1, int64_t Hd,
+                             int32_t shared_p, int64_t dp_stride_b, int64_t dp_stride_u, int32_t act, void* stream) {
+    return joint_bwd("dyn_joint_bwd", dz, z, de, dp, B, T, U1, Hd, shared_p, T * Hd, dp_stride_b, dp_stride_u, 0, act, stream);
+}
+
+extern "C" int dyn_joint_bwd_chunk(const float* dz, const float* z, float* de, float* dp, int64_t B, int64_t Tc, int64_t U1, int64_t Hd,
+                                   int32_t shared_p, int64_t de_stride_b, int64_t dp_stride_b, int64_t dp_stride_u, int32_t dp_accumulate,
+                                   int32_t act, void* stream) {
+    return joint_bwd("dyn_joint_bwd_chunk", dz, z, de, dp, B, Tc, U1, Hd, shared_p, de_stride_b, dp_stride_b, dp_stride_u, dp_accumulate, act,
+                     stream);
 }
 
 extern "C" int64_t dyn_tdt_loss_workspace_bytes(int64_t B, int64_t T, int64_t U1, int64_t D) {
@@ -652,39 +692,127 @@ extern "C" int dyn_tdt_loss_workspace_layout(int64_t B, int64_t T, int64_t U1, i
     return DYN_OK;
 }
 
+namespace {
+
+// What every TDT entry does before its launches: sizes, the duration list, the lattice state carved out of `state` (refused by name over
+// the budget, `over` ends that message), the kernels' dimensions for the whole lattice (t0 = 0, Tc = T).
+int tdt_setup(const char* who, const char* over, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D, int64_t S,
+              int32_t blank, float sigma, void* state, int64_t state_bytes, int64_t budget_bytes, TdtDims& d, TdtWs& w) {
+    DYN_REQUIRE(B > 0 && T > 0 && U1 > 0 && V1 > 0 && S >= 1 && blank >= 0 && blank < V1, DYN_E_ARG, "%s: bad arguments", who);
+    DYN_REQUIRE(T + U1 < (1 << 24), DYN_E_UNSUPPORTED, "%s: %lld diagonals unsupported", who, (long long)(T + U1));
+    if (const int rc = check_durs(durations, D, d.durs, who)) return rc;
+    w = carve(state, B, T, U1, D);
+    DYN_REQUIRE(budget_bytes <= 0 || w.total <= budget_bytes, DYN_E_WORKSPACE,
+                "%s: the lattice of [%lld, %lld, %lld] needs %lld bytes, over the workspace budget of %lld (%s)", who, (long long)B, (long long)T,
+                (long long)U1, (long long)w.total, (long long)budget_bytes, over);
+    DYN_REQUIRE(state && state_bytes >= w.total, DYN_E_WORKSPACE, "%s: workspace %lld < %lld bytes", who, (long long)state_bytes,
+                (long long)w.total);
+    d.B = B; d.T = T; d.U1 = U1; d.t0 = 0; d.Tc = T; d.V1 = V1; d.N = V1 + D; d.S = S; d.blank = blank; d.sigma = sigma;
+    return DYN_OK;
+}
+
+// the frames [t0, t0 + Tc) of a chunk entry; the rows of one launch are counted in int64, the grid is capped (grid_for)
+int tdt_chunk(const char* who, int64_t t0, int64_t Tc, TdtDims& d) {
+    DYN_REQUIRE(t0 >= 0 && t0 < d.T && Tc > 0 && Tc < (1 << 24), DYN_E_ARG, "%s: the chunk [%lld, %lld + %lld) must start inside the %lld frames",
+                who, (long long)t0, (long long)t0, (long long)Tc, (long long)d.T);
+    d.t0 = t0; d.Tc = Tc;
+    return DYN_OK;
+}
+
+void launch_arcs(const float* logits, const int32_t* targets, const int32_t* tlen, const TdtWs& w, const TdtDims& d, hipStream_t st) {
+    hipLaunchKernelGGL(tdt_arcs_kernel, dim3(grid_for(d.B * d.Tc * d.U1, WPB)), dim3(64 * WPB), 0, st, logits, targets, tlen, w.lp, w.lse, d);
+}
+
+// alpha (and with `both` beta) over the anti-diagonals, the reduction, the per-row nll
+int launch_lattice(const char* who, const int32_t* ilen, const int32_t* tlen, int reduction, float* loss, float* nll_per_row, bool both,
+                   const TdtWs& w, const TdtDims& d, hipStream_t st) {
+    const int64_t diag = d.T < d.U1 ? d.T : d.U1;
+    int threads = (int)((diag + 63) / 64 * 64);
+    if (threads > LATTICE_T) threads = LATTICE_T;
+    hipLaunchKernelGGL(tdt_lattice_kernel, dim3((unsigned)d.B, both ? 2u : 1u), dim3(threads), 0, st, w.lp, ilen, tlen, w.alpha, w.beta, w.abase,
+                       w.bbase, w.ll, w.nll, d);
+    hipLaunchKernelGGL(tdt_loss_reduce_kernel, dim3(1), dim3(64), 0, st, w.nll, tlen, loss, d.B, reduction);
+    if (nll_per_row) {
+        hipError_t e = hipMemcpyAsync(nll_per_row, w.nll, d.B * sizeof(float), hipMemcpyDeviceToDevice, st);
+        DYN_REQUIRE(e == hipSuccess, DYN_E_LAUNCH, "%s: copy of the per-row nll failed", who);
+    }
+    return DYN_OK;
+}
+
+void launch_grad(const float* logits, const int32_t* targets, const int32_t* ilen, const int32_t* tlen, float* grad, float grad_scale,
+                 int reduction, const TdtWs& w, const TdtDims& d, hipStream_t st) {
+    hipLaunchKernelGGL(tdt_grad_kernel, dim3(grid_for(d.B * d.Tc * d.U1, WPB)), dim3(64 * WPB), 0, st, logits, targets, ilen, tlen, w.lp, w.lse,
+                       w.alpha, w.beta, w.abase, w.bbase, w.ll, grad, grad_scale, reduction, d);
+}
+
+const char* const OVER_STATE = "chunking the lattice state is not built: only the joint streams over frame chunks";
+
+}  // namespace
+
 extern "C" int dyn_tdt_loss(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
                             const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank,
                             float sigma, int32_t reduction, float grad_scale, float* loss, float* nll_per_row, float* grad,
                             void* workspace, int64_t workspace_bytes, int64_t workspace_budget_bytes, void* stream) {
-    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && loss && B > 0 && T > 0 && U1 > 0 && V1 > 0 && S >= 1 &&
-                    blank >= 0 && blank < V1 && reduction >= 0 && reduction <= 4, DYN_E_ARG, "dyn_tdt_loss: bad arguments");
-    DYN_REQUIRE(T + U1 < (1 << 24), DYN_E_UNSUPPORTED, "dyn_tdt_loss: %lld diagonals unsupported", (long long)(T + U1));
+    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && loss && reduction >= 0 && reduction <= 4, DYN_E_ARG,
+                "dyn_tdt_loss: bad arguments");
     TdtDims d;
-    if (const int rc = check_durs(durations, D, d.durs, "dyn_tdt_loss")) return rc;
-    TdtWs w = carve(workspace, B, T, U1, D);
-    DYN_REQUIRE(workspace_budget_bytes <= 0 || w.total <= workspace_budget_bytes, DYN_E_WORKSPACE,
-                "dyn_tdt_loss: the lattice of [%lld, %lld, %lld] needs %lld bytes, over the workspace budget of %lld (chunking over t is not built)",
-                (long long)B, (long long)T, (long long)U1, (long long)w.total, (long long)workspace_budget_bytes);
-    DYN_REQUIRE(workspace && workspace_bytes >= w.total, DYN_E_WORKSPACE, "dyn_tdt_loss: workspace %lld < %lld bytes",
-                (long long)workspace_bytes, (long long)w.total);
-    d.B = B; d.T = T; d.U1 = U1; d.V1 = V1; d.N = V1 + D; d.S = S; d.blank = blank; d.sigma = sigma;
+    TdtWs w;
+    if (const int rc = tdt_setup("dyn_tdt_loss", "chunking over t is not built", B, T, U1, V1, durations, D, S, blank, sigma, workspace,
+                                 workspace_bytes, workspace_budget_bytes, d, w))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t rows = B * T * U1;
-    hipLaunchKernelGGL(tdt_arcs_kernel, dim3(grid_for(rows, WPB)), dim3(64 * WPB), 0, st, logits, targets, target_lengths, w.lp, w.lse, d);
-    int64_t diag = T < U1 ? T : U1;
-    int threads = (int)((diag + 63) / 64 * 64);
-    if (threads > LATTICE_T) threads = LATTICE_T;
-    hipLaunchKernelGGL(tdt_lattice_kernel, dim3((unsigned)B, grad ? 2u : 1u), dim3(threads), 0, st, w.lp, logit_lengths, target_lengths,
-                       w.alpha, w.beta, w.abase, w.bbase, w.ll, w.nll, d);
-    hipLaunchKernelGGL(tdt_loss_reduce_kernel, dim3(1), dim3(64), 0, st, w.nll, target_lengths, loss, B, (int)reduction);
-    if (nll_per_row) {
-        hipError_t e = hipMemcpyAsync(nll_per_row, w.nll, B * sizeof(float), hipMemcpyDeviceToDevice, st);
-        DYN_REQUIRE(e == hipSuccess, DYN_E_LAUNCH, "dyn_tdt_loss: copy of the per-row nll failed");
-    }
-    if (grad)
-        hipLaunchKernelGGL(tdt_grad_kernel, dim3(grid_for(rows, WPB)), dim3(64 * WPB), 0, st, logits, targets, logit_lengths, target_lengths,
-                           w.lp, w.lse, w.alpha, w.beta, w.abase, w.bbase, w.ll, grad, grad_scale, (int)reduction, d);
+    launch_arcs(logits, targets, target_lengths, w, d, st);
+    if (const int rc = launch_lattice("dyn_tdt_loss", logit_lengths, target_lengths, (int)reduction, loss, nll_per_row, grad != nullptr, w, d, st))
+        return rc;
+    if (grad) launch_grad(logits, targets, logit_lengths, target_lengths, grad, grad_scale, (int)reduction, w, d, st);
     return dyn::check_launch("dyn_tdt_loss");
+}
+
+extern "C" int dyn_tdt_arcs_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+                                  const int32_t* targets, int64_t S, const int32_t* target_lengths, int32_t blank, float sigma, int64_t t0,
+                                  int64_t Tc, void* state, int64_t state_bytes, int64_t state_budget_bytes, void* stream) {
+    DYN_REQUIRE(logits && targets && target_lengths, DYN_E_ARG, "dyn_tdt_arcs_chunk: bad arguments");
+    TdtDims d;
+    TdtWs w;
+    if (const int rc = tdt_setup("dyn_tdt_arcs_chunk", OVER_STATE, B, T, U1, V1, durations, D, S, blank, sigma, state, state_bytes,
+                                 state_budget_bytes, d, w))
+        return rc;
+    if (const int rc = tdt_chunk("dyn_tdt_arcs_chunk", t0, Tc, d)) return rc;
+    launch_arcs(logits, targets, target_lengths, w, d, (hipStream_t)stream);
+    return dyn::check_launch("dyn_tdt_arcs_chunk");
+}
+
+extern "C" int dyn_tdt_lattice_run(int64_t B, int64_t T, int64_t U1, const int32_t* durations, int64_t D, int64_t S,
+                                   const int32_t* logit_lengths, const int32_t* target_lengths, int32_t reduction, float* loss,
+                                   float* nll_per_row, int32_t want_beta, void* state, int64_t state_bytes, int64_t state_budget_bytes,
+                                   void* stream) {
+    DYN_REQUIRE(logit_lengths && target_lengths && loss && reduction >= 0 && reduction <= 4, DYN_E_ARG, "dyn_tdt_lattice_run: bad arguments");
+    TdtDims d;
+    TdtWs w;
+    // the lattice reads neither the vocabulary nor the blank: one token class stands in for them
+    if (const int rc = tdt_setup("dyn_tdt_lattice_run", OVER_STATE, B, T, U1, 1, durations, D, S, 0, 0.f, state, state_bytes, state_budget_bytes,
+                                 d, w))
+        return rc;
+    if (const int rc = launch_lattice("dyn_tdt_lattice_run", logit_lengths, target_lengths, (int)reduction, loss, nll_per_row, want_beta != 0, w, d,
+                                      (hipStream_t)stream))
+        return rc;
+    return dyn::check_launch("dyn_tdt_lattice_run");
+}
+
+extern "C" int dyn_tdt_grad_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+                                  const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths,
+                                  int32_t blank, int32_t reduction, float grad_scale, int64_t t0, int64_t Tc, float* grad, const void* state,
+                                  int64_t state_bytes, void* stream) {
+    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && grad && reduction >= 0 && reduction <= 4, DYN_E_ARG,
+                "dyn_tdt_grad_chunk: bad arguments");
+    TdtDims d;
+    TdtWs w;
+    if (const int rc = tdt_setup("dyn_tdt_grad_chunk", OVER_STATE, B, T, U1, V1, durations, D, S, blank, 0.f, const_cast<void*>(state), state_bytes,
+                                 0, d, w))
+        return rc;
+    if (const int rc = tdt_chunk("dyn_tdt_grad_chunk", t0, Tc, d)) return rc;
+    launch_grad(logits, targets, logit_lengths, target_lengths, grad, grad_scale, (int)reduction, w, d, (hipStream_t)stream);
+    return dyn::check_launch("dyn_tdt_grad_chunk");
 }
 
 extern "C" int dyn_tdt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,

@@ -2073,7 +2073,11 @@ def relu_bwd(x, dy, out=None):
 JOINT_ACTS = {"relu": 0}
 TDT_REDUCTIONS = {"sum": 0, "mean_batch": 1, "mean": 2, "mean_volume": 3, "none": 4}
 TDT_MAX_DURATIONS = 8
-TDT_WORKSPACE_BUDGET = 512 << 20      # bytes of lattice state a dyn_tdt_loss call may ask for; the joint is not chunked over t
+TDT_WORKSPACE_BUDGET = 512 << 20      # bytes of lattice state (44 B per cell at D = 5) a TDT loss may ask for; the state is never chunked
+# Bytes of z + logits + dz a transducer head may hold at once before it streams the joint over frame chunks (parakeet_tdt_model.
+# plan_joint_chunk).  A memory policy, not a tuned figure: nothing was timed to pick it; it is large enough that every shape the tests
+# and the 16-frame windows of the loop use stays on the whole-joint path.
+TDT_JOINT_BUDGET = 8 << 30
 
 
 def _joint_act(act, what):
@@ -2146,14 +2150,16 @@ def _joint_p(p, B, Hd, what):
     return shared, 0 if p.shape[0] == 1 else p.stride(0), p.stride(1)
 
 
-def joint(e, p, act="relu"):
-    """z [B, T, U1, Hd] = act(e[b, t] + p[b, u]); e [B, T, Hd], p [B or 1, U1, Hd] (one row set shared by the batch)."""
+def joint(e, p, act="relu", out=None):
+    """z [B, T, U1, Hd] = act(e[b, t] + p[b, u]); e [B, T, Hd], p [B or 1, U1, Hd] (one row set shared by the batch); `out`: z to write."""
     a = _joint_act(act, "joint")
     _cc(e, "joint.e")
     B, T, Hd = e.shape
     _, sb, su = _joint_p(p, B, Hd, "joint")
     U1 = p.shape[1]
-    z = torch.empty(B, T, U1, Hd, device=e.device, dtype=F32)
+    z = torch.empty(B, T, U1, Hd, device=e.device, dtype=F32) if out is None else _cc(out, "joint.out")
+    if tuple(z.shape) != (B, T, U1, Hd):
+        raise DynError(f"joint: out {tuple(z.shape)} must be {(B, T, U1, Hd)}")
     check(_L().dyn_joint_fwd(e.data_ptr(), p.data_ptr(), z.data_ptr(), B, T, U1, Hd, sb, su, a, _stream()), "dyn_joint_fwd")
     return z
 
@@ -2206,13 +2212,116 @@ def tdt_loss(logits, targets, logit_lengths, target_lengths, blank, durations, s
     return loss, nll, grad
 
 
-def tdt_lattice(B, T, U1, D, device):
-    """What the last ops.tdt_loss call of this (device, stream) left in the workspace, as absolute values: (alpha [B, T, U1],
+def joint_bwd_chunk(dz, z, de, dp, t0, accumulate, act="relu", time_major=False):
+    """joint_bwd of the frames [t0, t0 + Tc): dz, z [B, Tc, U1, Hd].  de [B, T, Hd] (or None) receives its rows [:, t0:t0 + Tc], the same
+    bits as joint_bwd's; dp [B or 1, U1, Hd] (`time_major`: [U1, B or 1, Hd]; or None) the chunk's sum over its frames, written
+    (`accumulate` false) or added to what it holds: chunks in ascending order give one fixed summation order."""
+    a = _joint_act(act, "joint_bwd_chunk")
+    _cc(dz, "joint_bwd_chunk.dz"); _cc(z, "joint_bwd_chunk.z")
+    if z.dim() != 4 or dz.shape != z.shape or (de is None and dp is None):
+        raise DynError(f"joint_bwd_chunk: dz {tuple(dz.shape)}, z {tuple(z.shape)} must be [B, Tc, U + 1, Hd], with de or dp to write")
+    B, Tc, U1, Hd = z.shape
+    t0 = int(t0)
+    de_ptr = sde = 0
+    if de is not None:
+        _cc(de, "joint_bwd_chunk.de")
+        if de.dim() != 3 or de.shape[0] != B or de.shape[2] != Hd or not 0 <= t0 <= de.shape[1] - Tc:
+            raise DynError(f"joint_bwd_chunk: de {tuple(de.shape)} must be [{B}, T, {Hd}] with the frames [{t0}, {t0 + Tc}) inside T")
+        de_ptr, sde = de.data_ptr() + 4 * t0 * Hd, de.shape[1] * Hd
+    dp_ptr, shared, sb, su = 0, False, 0, Hd
+    if dp is not None:
+        _cc(dp, "joint_bwd_chunk.dp")
+        Bp = dp.shape[1] if time_major and dp.dim() == 3 else dp.shape[0]
+        if tuple(dp.shape) != ((U1, Bp, Hd) if time_major else (Bp, U1, Hd)) or Bp not in (1, B):
+            raise DynError(f"joint_bwd_chunk: dp {tuple(dp.shape)} does not fit z {tuple(z.shape)}")
+        shared = Bp == 1 and B > 1
+        sb, su = (Hd, Bp * Hd) if time_major else (U1 * Hd, Hd)
+        dp_ptr = dp.data_ptr()
+    check(_L().dyn_joint_bwd_chunk(dz.data_ptr(), z.data_ptr(), de_ptr, dp_ptr, B, Tc, U1, Hd, int(shared), sde, sb, su, int(bool(accumulate)),
+                                   a, _stream()), "dyn_joint_bwd_chunk")
+    return de, dp
+
+
+def tdt_state(B, T, U1, durations, device, budget=None):
+    """A caller-owned lattice state for tdt_arcs_chunk / tdt_lattice_run / tdt_grad_chunk (uint8, dyn_tdt_loss_workspace_layout's
+    layout; tdt_lattice(state=) reads it back).  Over `budget` (default TDT_WORKSPACE_BUDGET) it is refused by name before anything
+    is allocated: the joint streams over frame chunks, the lattice state does not."""
+    D = len(check_durations(durations))
+    need = _L().dyn_tdt_loss_workspace_bytes(B, T, U1, D)
+    budget = TDT_WORKSPACE_BUDGET if budget is None else int(budget)
+    if need < 0:
+        raise DynError(f"tdt_state: bad lattice [{B}, {T}, {U1}]")
+    if 0 < budget < need:
+        raise DynError(f"tdt_state: the lattice of [{B}, {T}, {U1}] needs {need} bytes of state, over the workspace budget of {budget} "
+                       "(chunking the lattice state is not built: only the joint streams over frame chunks)")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _tdt_chunk_args(who, logits, targets, target_lengths, T, durations, state):
+    _c(logits, who + ".logits"); _c(targets, who + ".targets", I32); _cc(target_lengths, who + ".target_lengths", I32)
+    _cc(state, who + ".state", torch.uint8)
+    dur, D = _durations_arg(durations)
+    if logits.dim() != 4 or logits.shape[3] <= D:
+        raise DynError(f"{who}: logits {tuple(logits.shape)} must be [B, Tc, U + 1, V + 1 + {D}]")
+    B = logits.shape[0]
+    if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or target_lengths.numel() != B or int(T) < 1:
+        raise DynError(f"{who}: targets {tuple(targets.shape)} must be [B, S >= 1], the lengths [B], T positive")
+    return dur, D
+
+
+def tdt_arcs_chunk(logits, t0, T, targets, target_lengths, blank, durations, state, sigma=0.0, budget=None):
+    """The arcs pass of tdt_loss on the frames [t0, t0 + Tc) of a lattice of T frames: logits [B, Tc, U1, V1 + D] (a chunk may overhang T,
+    those rows are not read) -> lp and lse of those cells in `state` (tdt_state).  Every frame has to be covered before tdt_lattice_run."""
+    dur, D = _tdt_chunk_args("tdt_arcs_chunk", logits, targets, target_lengths, T, durations, state)
+    B, Tc, U1, N = logits.shape
+    check(_L().dyn_tdt_arcs_chunk(logits.data_ptr(), B, int(T), U1, N - D, ctypes.cast(dur, ctypes.c_void_p), D, targets.data_ptr(),
+                                  targets.shape[1], target_lengths.data_ptr(), blank, sigma, int(t0), Tc, state.data_ptr(), state.numel(),
+                                  TDT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_tdt_arcs_chunk")
+
+
+def tdt_lattice_run(B, T, U1, S, logit_lengths, target_lengths, durations, state, reduction="mean", want_beta=True, budget=None):
+    """The lattice and the reduction of tdt_loss on a state the arcs pass filled -> (loss [1], nll [B]); beta (the gradient pass needs
+    it) only with want_beta.  S = the width of the targets tensor the arcs pass saw (it caps the target lengths)."""
+    _cc(logit_lengths, "tdt_lattice_run.logit_lengths", I32); _cc(target_lengths, "tdt_lattice_run.target_lengths", I32)
+    _cc(state, "tdt_lattice_run.state", torch.uint8)
+    if reduction not in TDT_REDUCTIONS:
+        raise DynError(f"tdt_lattice_run: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
+    if logit_lengths.numel() != B or target_lengths.numel() != B:
+        raise DynError(f"tdt_lattice_run: the lengths must be [{B}]")
+    dur, D = _durations_arg(durations)
+    loss = torch.empty(1, device=state.device, dtype=F32)
+    nll = torch.empty(B, device=state.device, dtype=F32)
+    check(_L().dyn_tdt_lattice_run(B, T, U1, ctypes.cast(dur, ctypes.c_void_p), D, int(S), logit_lengths.data_ptr(), target_lengths.data_ptr(),
+                                   TDT_REDUCTIONS[reduction], loss.data_ptr(), nll.data_ptr(), int(bool(want_beta)), state.data_ptr(),
+                                   state.numel(), TDT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_tdt_lattice_run")
+    return loss, nll
+
+
+def tdt_grad_chunk(logits, t0, T, targets, logit_lengths, target_lengths, blank, durations, state, reduction="mean", grad_scale=1.0, out=None):
+    """The gradient pass of tdt_loss on the frames [t0, t0 + Tc): the gradient of grad_scale * loss w.r.t. the chunk's logits
+    [B, Tc, U1, V1 + D], from a state tdt_lattice_run(want_beta=True) completed.  `out` may be the logits; rows past T are zeros."""
+    dur, D = _tdt_chunk_args("tdt_grad_chunk", logits, targets, target_lengths, T, durations, state)
+    _cc(logit_lengths, "tdt_grad_chunk.logit_lengths", I32)
+    if reduction not in TDT_REDUCTIONS:
+        raise DynError(f"tdt_grad_chunk: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
+    B, Tc, U1, N = logits.shape
+    grad = torch.empty_like(logits) if out is None else _c(out, "tdt_grad_chunk.out")
+    if grad.shape != logits.shape or logit_lengths.numel() != B:
+        raise DynError(f"tdt_grad_chunk: out {tuple(grad.shape)} != logits {tuple(logits.shape)}, or the lengths are not [{B}]")
+    check(_L().dyn_tdt_grad_chunk(logits.data_ptr(), B, int(T), U1, N - D, ctypes.cast(dur, ctypes.c_void_p), D, targets.data_ptr(),
+                                  targets.shape[1], logit_lengths.data_ptr(), target_lengths.data_ptr(), blank, TDT_REDUCTIONS[reduction],
+                                  grad_scale, int(t0), Tc, grad.data_ptr(), state.data_ptr(), state.numel(), _stream()), "dyn_tdt_grad_chunk")
+    return grad
+
+
+def tdt_lattice(B, T, U1, D, device, state=None):
+    """What the last ops.tdt_loss call of this (device, stream) left in the workspace (or what the chunk entries left in `state`), as
+    absolute values: (alpha [B, T, U1],
     beta [B, T, U1] (written only when a gradient was asked for), lp [B, T, U1, 2 + D], lse [B, T, U1, 2]).  The kernels store every
     anti-diagonal relative to an integer base; the bases are added back here in float64 (host arithmetic, for tests)."""
     off = (ctypes.c_int64 * 8)()
     check(_L().dyn_tdt_loss_workspace_layout(B, T, U1, D, ctypes.cast(off, ctypes.c_void_p)), "dyn_tdt_loss_workspace_layout")
-    ws = workspace(device)
+    ws = workspace(device) if state is None else state
     cells = B * T * U1
 
     def view(i, n, shape):

@@ -11,7 +11,17 @@ transformers modeling_parakeet.py: ParakeetForTDT) as transformers builds it in 
     [B, T', U + 1, Hd] by the existing GEMM (M = B T' (U + 1)).  The decoder rows may be ONE row set shared by the batch
     (decoder_input_ids [1, U + 1]: the loop's copies carry identical labels); their gradient then sums over the batch as well.
   * the loss: ops.tdt_loss (transformers.loss.loss_tdt.tdt_loss and its autograd: arc log-probs, lattice, gradient), the five reductions
-    of tdt_loss with default "mean", plus sigma.  The whole lattice is materialised; above ops.TDT_WORKSPACE_BUDGET it is refused by name.
+    of tdt_loss with default "mean", plus sigma.  The lattice STATE (arc log-probs, alpha, beta: 44 bytes per cell at D = 5) is always
+    whole; above ops.TDT_WORKSPACE_BUDGET it is refused by name.
+  * the joint over frame chunks: z, the logits and dz are 4 (2 Hd + V + 1 + D) bytes per lattice cell, 35 KB at the released head.  When
+    a loss is asked for and they do not fit `joint_budget` (ops.TDT_JOINT_BUDGET; plan_joint_chunk picks the frames per chunk, head's
+    `frames_per_chunk=` overrides it), nothing of the joint is kept.  Pass 1, per chunk of Tc frames: z_c, logits_c, their arc
+    log-probs into the state (ops.tdt_arcs_chunk), then both are dropped.  Pass 2: the lattice and the reduction on the state
+    (ops.tdt_lattice_run).  Pass 3, in backward(), chunks ascending: z_c and logits_c once more, the gradient over logits_c
+    (ops.tdt_grad_chunk), the head's weight and bias gradients accumulated, dz_c, de of the chunk's frames and dp added to the earlier
+    chunks' (ops.joint_bwd_chunk).  The same kernels as the whole path: loss and per-logit gradient are bit-equal, sums over frames (dp,
+    the head's gradients) differ by their order.  One more head GEMM per step; `logits` of the output is None, an explicit
+    `grad_logits` is refused.  What backward() needs (state, e, p) lives in tensors of the call, never in the shared scratch.
   * generate: the duration-aware greedy decode of ParakeetTDTGenerationMixin with all state on the device (ops.tdt_greedy_steps); the
     host reads the done flags once per chunk of steps.  The frame pointer advances by durations[argmax] (transformers adds the argmax
     INDEX, the same thing for the released checkpoints' durations 0 .. D - 1), by 1 for a blank with duration 0.
@@ -19,7 +29,8 @@ transformers modeling_parakeet.py: ParakeetForTDT) as transformers builds it in 
 Refused by name before any launch: `attention_mask`, a `hidden_act` of the joint other than "relu", more than 8 durations, negative or
 unsorted durations, `model_type: "parakeet_rnnt"` (ParakeetForRNNT: no duration head; its oracle loss needs torchaudio), and whatever
 parakeet_model.make_config refuses of the encoder.  Out of scope: beam / MAES decoding, ragged batches in the model (the loss kernel's
-per-row lengths are built), a waveform front end, hipGraph replay and lockstep groups, chunking the joint over t.  No hub checkpoint is
+per-row lengths are built), a waveform front end, hipGraph replay and lockstep groups, chunking the joint over u or the lattice state, a
+log-sum-exp in the GEMM's epilogue that never writes the logits.  No hub checkpoint is
 on the machine: transformers' ParakeetForTDT on the CPU with the same (random) state dict is the oracle in the tests."""
 from types import SimpleNamespace
 
@@ -99,6 +110,17 @@ def param_spec(c, pf=""):
     return spec
 
 
+def plan_joint_chunk(B, T, U1, Hd, N, budget):
+    """Pure host function: the frames per chunk of the joint.  One frame of z + logits + dz is B * U1 * (2 Hd + N) * 4 bytes; the result
+    is the largest Tc in 1 .. T whose chunk fits `budget` bytes (1 when not even one frame does: the head then runs frame by frame,
+    over the budget, rather than not at all).  Tc == T means the whole joint fits: unchunked."""
+    B, T, U1, Hd, N, budget = (int(v) for v in (B, T, U1, Hd, N, budget))
+    if min(B, T, U1, Hd, N) < 1:
+        raise ops.DynError(f"plan_joint_chunk: B, T, U1, Hd, N = {(B, T, U1, Hd, N)} must be positive")
+    frame = B * U1 * (2 * Hd + N) * 4
+    return max(1, min(T, budget // frame))
+
+
 def _host_ids(t, what, vocab):
     """An integer tensor (host or device) or nested list -> int64 host tensor [rows, n], every id inside the vocabulary."""
     t = torch.as_tensor(t).detach().cpu()
@@ -125,6 +147,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         self.blank = c["blank_token_id"]
         self.start_token = c["decoder_start_token_id"] if c["decoder_start_token_id"] is not None else self.blank
         self._tdt = None
+        self.joint_budget = ops.TDT_JOINT_BUDGET             # bytes of z + logits + dz held at once; above it the joint streams over frame chunks
         names = [DEC + f"lstm.{n}_l{k}" for k in range(c["num_decoder_layers"]) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
         self._lstm_ptrs = torch.tensor([self.P[n].data_ptr() for n in names], dtype=torch.int64, device=self.device)
 
@@ -212,13 +235,53 @@ class ParakeetForTDT(PM.ParakeetForCTC):
                                            torch.cuda.current_stream().cuda_stream), "dyn_embedding_bwd")
 
     # ------------------------------------------------------------------ joint, loss
-    def head(self, enc, decoder_input_ids, labels=None, reduction="mean", sigma=0.0, grad_scale=1.0, n_active=None, label_lengths=None):
+    def _joint_frames(self, nb, T, U1, frames_per_chunk):
+        """Frames per chunk of the joint for a loss on [nb, T, U1]: the override, or plan_joint_chunk under joint_budget.  T: unchunked."""
+        if frames_per_chunk is None:
+            return plan_joint_chunk(nb, T, U1, self.Hd, self.V1 + self.D, self.joint_budget)
+        if isinstance(frames_per_chunk, bool) or not isinstance(frames_per_chunk, int) or frames_per_chunk < 1:
+            raise ops.DynError(f"frames_per_chunk={frames_per_chunk!r} must be a positive integer")
+        return min(frames_per_chunk, T)
+
+    def _joint_chunk(self, e, p, t0, n, zbuf, lbuf):
+        """z and the logits of the frames [t0, t0 + n) into the front of the two chunk buffers: ([nb, n, U1, Hd], [nb, n, U1, V + 1 + D])."""
+        P, Hd = self.P, self.Hd
+        nb, U1, N = e.shape[0], p.shape[0], self.V1 + self.D
+        z = ops.joint(e[:, t0:t0 + n].contiguous(), p.transpose(0, 1), self.cfg["joint_hidden_act"], out=zbuf[:nb * n * U1 * Hd].view(nb, n, U1, Hd))
+        return z, ops.linear(z, P[JOINT + "head.weight"], P[JOINT + "head.bias"], out=lbuf[:nb * n * U1 * N].view(nb, n, U1, N))
+
+    def _chunk_buffers(self, nb, Tc, U1, dz):
+        n = nb * Tc * U1
+        new = lambda k: torch.empty(n * k, device=self.device, dtype=torch.float32)                # noqa: E731
+        return new(self.Hd), new(self.V1 + self.D), (new(self.Hd) if dz else None)
+
+    def _head_chunked(self, e, p, Tc, tg, ilen, tlen, reduction, sigma, want_beta):
+        """Passes 1 and 2 of the chunked loss: the arcs of every chunk of Tc frames into a lattice state this call owns (the joint of a
+        chunk is dropped as soon as its arcs are written), then the lattice -> (loss, nll, state)."""
+        c = self.cfg
+        nb, T, _ = e.shape
+        U1 = p.shape[0]
+        if reduction not in ops.TDT_REDUCTIONS:
+            raise ops.DynError(f"reduction={reduction!r} is not one of {sorted(ops.TDT_REDUCTIONS)}")
+        state = ops.tdt_state(nb, T, U1, c["durations"], self.device)                              # over TDT_WORKSPACE_BUDGET: refused by name
+        zbuf, lbuf, _ = self._chunk_buffers(nb, Tc, U1, False)
+        for t0 in range(0, T, Tc):
+            _, logits = self._joint_chunk(e, p, t0, min(Tc, T - t0), zbuf, lbuf)
+            ops.tdt_arcs_chunk(logits, t0, T, tg, tlen, self.blank, c["durations"], state, sigma)
+        loss, nll = ops.tdt_lattice_run(nb, T, U1, tg.shape[1], ilen, tlen, c["durations"], state, reduction, want_beta)
+        return loss, nll, state
+
+    def head(self, enc, decoder_input_ids, labels=None, reduction="mean", sigma=0.0, grad_scale=1.0, n_active=None, label_lengths=None,
+             frames_per_chunk=None):
         """The prediction network, the joint and (with labels) the TDT loss on the first n_active rows of enc [B, T', Hd].
         decoder_input_ids [n_active or 1, U + 1] (one row: shared by every copy); labels [same rows, U], padded with pad_token_id
         (transformers counts `labels != pad_token_id`; `label_lengths`, one per label row, replaces that count: unpadded labels may
         hold the pad id).
         Returns SimpleNamespace(logits [n_active, T', U + 1, V + 1 + D], loss [1] or None, nll [n_active] or None).  In grad mode the
-        loss's gradient w.r.t. the logits, times grad_scale, is kept for backward()."""
+        loss's gradient w.r.t. the logits, times grad_scale, is kept for backward().
+        With labels, when z + logits + dz of the whole joint do not fit `joint_budget` bytes (or `frames_per_chunk` < T' is given), the
+        joint streams over chunks of frames (module docstring): `logits` is then None, loss and nll are those of the whole-joint path,
+        and backward() recomputes the joint chunk by chunk."""
         c, P, Hd = self.cfg, self.P, self.Hd
         B, T, _ = enc.shape
         nb = B if n_active is None else int(n_active)
@@ -228,14 +291,17 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         if ids.shape[0] not in (1, nb) or ids.shape[1] < 1:
             raise ops.DynError(f"decoder_input_ids {tuple(ids.shape)} must be [{nb} or 1, U + 1]")
         U1 = ids.shape[1]
+        Tc = T if labels is None else self._joint_frames(nb, T, U1, frames_per_chunk)
         grad_mode = torch.is_grad_enabled() and self._ctx is not None
         with ops.use_workspace(self._scratch()):
             run_dec_bwd = grad_mode and not self._decoder_frozen()
             p, dec_saved = self._decoder_fwd(ids, run_dec_bwd)
             e = enc[:nb].contiguous()
-            z = ops.joint(e, p.transpose(0, 1), c["joint_hidden_act"])
-            logits = ops.linear(z, P[JOINT + "head.weight"], P[JOINT + "head.bias"])
-            loss = nll = dlogits = None
+            z = logits = None
+            if Tc >= T:
+                z = ops.joint(e, p.transpose(0, 1), c["joint_hidden_act"])
+                logits = ops.linear(z, P[JOINT + "head.weight"], P[JOINT + "head.bias"])
+            loss = nll = dlogits = chunked = None
             if labels is not None:
                 lab = _host_ids(labels, "labels", self.V1)
                 if lab.shape[0] != ids.shape[0] or lab.shape[1] != U1 - 1:
@@ -250,24 +316,30 @@ class ParakeetForTDT(PM.ParakeetForCTC):
                         tlen = tlen.expand(nb).contiguous()
                     if tlen.numel() != nb or int(tlen.min()) < 0 or int(tlen.max()) > U1 - 1:
                         raise ops.DynError(f"label_lengths {tlen.tolist()} must be {nb} (or 1) values in 0 .. {U1 - 1}")
-                tg = lab.to(torch.int32).contiguous() if U1 > 1 else torch.zeros(nb, 1, dtype=torch.int32)
-                loss, nll, dlogits = ops.tdt_loss(logits, tg.to(self.device), torch.full((nb,), T, dtype=torch.int32, device=self.device),
-                                                  tlen.to(self.device), self.blank, c["durations"], float(sigma), reduction, float(grad_scale),
-                                                  want_grad=grad_mode)
-        self._tdt = dict(z=z, p_rows=ids.shape[0], dec=dec_saved, rows=nb, dlogits=dlogits) if grad_mode else None
+                tg = (lab.to(torch.int32).contiguous() if U1 > 1 else torch.zeros(nb, 1, dtype=torch.int32)).to(self.device)
+                ilen, tlen = torch.full((nb,), T, dtype=torch.int32, device=self.device), tlen.to(self.device)
+                if Tc >= T:
+                    loss, nll, dlogits = ops.tdt_loss(logits, tg, ilen, tlen, self.blank, c["durations"], float(sigma), reduction, float(grad_scale),
+                                                      want_grad=grad_mode)
+                else:
+                    loss, nll, state = self._head_chunked(e, p, Tc, tg, ilen, tlen, reduction, float(sigma), grad_mode)
+                    # what the gradient pass needs, in tensors of this call's own: nothing of it lives in the shared scratch
+                    chunked = dict(frames=Tc, e=e, p=p, state=state, tg=tg, ilen=ilen, tlen=tlen, reduction=reduction, grad_scale=float(grad_scale))
+        self._tdt = dict(z=z, p_rows=ids.shape[0], dec=dec_saved, rows=nb, dlogits=dlogits, chunked=chunked) if grad_mode else None
         return SimpleNamespace(logits=logits, loss=loss, nll=nll, frames=T)
 
     def forward(self, input_features, decoder_input_ids=None, labels=None, attention_mask=None, reduction="mean", sigma=0.0, grad_scale=1.0,
-                n_active=None, label_lengths=None):
+                n_active=None, label_lengths=None, frames_per_chunk=None):
         """input_features [B, T, num_mel_bins] float32 on the device, decoder_input_ids [B or 1, U + 1] -> SimpleNamespace(logits
-        [B, T', U + 1, V + 1 + D], loss, nll, frames = T', enc [B, T', Hd]).  `attention_mask` is refused: every frame is valid."""
+        [B, T', U + 1, V + 1 + D] (None when the joint was chunked: head()), loss, nll, frames = T', enc [B, T', Hd]).  `attention_mask`
+        is refused: every frame is valid."""
         if attention_mask is not None:
             raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (ragged batches are out of scope; "
                                "the loss kernel's per-row lengths are reached through ops.tdt_loss)")
         if decoder_input_ids is None:
             raise ops.DynError("forward() needs decoder_input_ids [B or 1, U + 1] (start token + labels); generate() decodes without them")
         enc = self.encode(input_features, attention_mask)
-        out = self.head(enc, decoder_input_ids, labels, reduction, sigma, grad_scale, n_active, label_lengths)
+        out = self.head(enc, decoder_input_ids, labels, reduction, sigma, grad_scale, n_active, label_lengths, frames_per_chunk)
         out.enc = enc
         return out
 
@@ -281,12 +353,18 @@ class ParakeetForTDT(PM.ParakeetForCTC):
             raise ops.DynError("backward() without a grad-mode forward through the joint")
         if n_active is not None and int(n_active) != t["rows"]:
             raise ops.DynError(f"backward(n_active={n_active}) after a forward whose joint ran on {t['rows']} rows")
-        g = t["dlogits"] if grad_logits is None else grad_logits
-        if g is None:
-            raise ops.DynError("backward() needs grad_logits: the last forward had no labels")
-        if tuple(g.shape) != tuple(t["z"].shape[:3]) + (self.V1 + self.D,):
-            raise ops.DynError(f"grad_logits {tuple(g.shape)} does not fit the joint logits")
-        t["g"] = g.contiguous()
+        if t.get("chunked") is not None:
+            if grad_logits is not None:
+                raise ops.DynError("backward(grad_logits=...) after a chunked forward is not built: the joint streamed over chunks of "
+                                   f"{t['chunked']['frames']} frames and the logits were never whole; backward() without grad_logits takes the "
+                                   "loss's own gradient (or run the forward with a joint_budget / frames_per_chunk that keeps the joint whole)")
+        else:
+            g = t["dlogits"] if grad_logits is None else grad_logits
+            if g is None:
+                raise ops.DynError("backward() needs grad_logits: the last forward had no labels")
+            if tuple(g.shape) != tuple(t["z"].shape[:3]) + (self.V1 + self.D,):
+                raise ops.DynError(f"grad_logits {tuple(g.shape)} does not fit the joint logits")
+            t["g"] = g.contiguous()
         B = self._ctx["dims"][0]
         nb = B if self._ctx_brn else t["rows"]          # batch renorm: the gradient reaches every row through the batch statistics
         # the parent's surface hands dL/dlogits [nb, ..] down to _backward_encoder; the joint's gradient waits in self._tdt instead
@@ -296,18 +374,52 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         finally:
             self._tdt = None
 
+    def _joint_bwd_chunked(self, t, need_enc, need_dec):
+        """Pass 3 of the chunked loss, chunks in ascending order: the joint and the logits of a chunk once more, the loss's gradient written
+        over those logits, the head's weight and bias gradients accumulated at once (not through the deferred queue: the chunk buffers are
+        reused), dz, then de of the chunk's frames and dp added to the chunks before -> (de [rows, T', Hd] or None, dp time-major or None)."""
+        P, G, Hd, N = self.P, self.G, self.Hd, self.V1 + self.D
+        k = t["chunked"]
+        e, p, Tc = k["e"], k["p"], k["frames"]
+        rows, T, _ = e.shape
+        U1 = p.shape[0]
+        wn, bn = JOINT + "head.weight", JOINT + "head.bias"
+        head_grads, need_dz = self.trainable(wn) or self.trainable(bn), need_enc or need_dec
+        if not (head_grads or need_dz):
+            return None, None
+        zbuf, lbuf, dzbuf = self._chunk_buffers(rows, Tc, U1, need_dz)
+        de = torch.empty(rows, T, Hd, device=self.device, dtype=torch.float32) if need_enc else None
+        dp = torch.empty(U1, t["p_rows"], Hd, device=self.device, dtype=torch.float32) if need_dec else None
+        for t0 in range(0, T, Tc):
+            z, logits = self._joint_chunk(e, p, t0, min(Tc, T - t0), zbuf, lbuf)
+            g = ops.tdt_grad_chunk(logits, t0, T, k["tg"], k["ilen"], k["tlen"], self.blank, self.cfg["durations"], k["state"], k["reduction"],
+                                   k["grad_scale"], out=logits).view(-1, N)
+            if head_grads:                                   # as _lin_bwd: both sums unless both are frozen
+                ops.linear_wgrad(g, z.view(-1, Hd), G[wn], beta=1.0)
+                ops.colsum(g, G[bn], beta=1.0)
+            if need_dz:
+                dz = ops.linear_dgrad(g, P[wn], out=dzbuf[:z.numel()].view(-1, Hd)).view(z.shape)
+                ops.joint_bwd_chunk(dz, z, de, dp, t0, t0 > 0, self.cfg["joint_hidden_act"], time_major=True)
+        return de, dp
+
     def _backward_encoder(self, ctx, grad_logits, nb, cut):
         t, P = self._tdt, self.P
         v0, vT = ctx["valid"]
         T = ctx["dims"][2]
-        z, g = t["z"], t["g"]
-        rows, U1, Hd = z.shape[0], z.shape[2], self.Hd
-        dz = self._lin_bwd(g.view(-1, g.shape[-1]), z.view(-1, Hd), JOINT + "head.weight", JOINT + "head.bias").view(z.shape)
+        rows, Hd = t["rows"], self.Hd
         need_dec, need_enc = t["dec"] is not None, not self._encoder_frozen()
-        if not (need_dec or need_enc):
-            return None
-        de, dp = ops.joint_bwd(dz, z, torch.empty(t["p_rows"], U1, Hd, device="meta"), self.cfg["joint_hidden_act"], want_de=need_enc,
-                               want_dp=need_dec, time_major=True)
+        if t["chunked"] is not None:
+            de, dp = self._joint_bwd_chunked(t, need_enc, need_dec)
+            if not (need_dec or need_enc):
+                return None
+        else:
+            z, g = t["z"], t["g"]
+            U1 = z.shape[2]
+            dz = self._lin_bwd(g.view(-1, g.shape[-1]), z.view(-1, Hd), JOINT + "head.weight", JOINT + "head.bias").view(z.shape)
+            if not (need_dec or need_enc):
+                return None
+            de, dp = ops.joint_bwd(dz, z, torch.empty(t["p_rows"], U1, Hd, device="meta"), self.cfg["joint_hidden_act"], want_de=need_enc,
+                                   want_dp=need_dec, time_major=True)
         if need_dec:
             self._decoder_bwd(dp, t["dec"])
         if not need_enc:

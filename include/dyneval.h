@@ -1001,8 +1001,24 @@ int dyn_convmod_brn_bwd(const float* c, const float* stats, const float* ds, flo
  *                         terminal gives nll = +inf and an all-zero gradient for that row.  reduction 0 sum, 1 mean_batch,
  *                         2 mean (nll_b / U_b, then the batch mean), 3 mean_volume, 4 none (loss = the sum; the rows in nll_per_row).
  *                         The whole lattice lives in `workspace`; workspace_budget_bytes > 0 refuses a larger one by name
- *                         (DYN_E_WORKSPACE): chunking over t is not built.
+ *                         (DYN_E_WORKSPACE).  This entry wants the whole logits tensor; the three below stream it over frame chunks.
  *   dyn_tdt_loss_workspace_layout   byte offsets of lp, lse, alpha, beta, abase, bbase, ll, nll in the workspace (tests).
+ *   dyn_tdt_arcs_chunk / dyn_tdt_lattice_run / dyn_tdt_grad_chunk   dyn_tdt_loss in three passes, for a joint that is produced, consumed and
+ *                         dropped a few frames at a time (and produced once more for the gradient).  `state` is a caller-owned buffer of
+ *                         dyn_tdt_loss_workspace_bytes in dyn_tdt_loss_workspace_layout's layout; it must survive from the first arcs
+ *                         chunk to the last gradient chunk.  A chunk is logits [B, Tc, U1, V1 + D] of the frames [t0, t0 + Tc) of the
+ *                         lattice [B, T, U1] (0 <= t0 < T; it may overhang T: those rows are not read by the arcs pass and come out as
+ *                         zeros of the gradient pass).  dyn_tdt_arcs_chunk writes lp and lse of the chunk's cells (every frame of the
+ *                         lattice must be covered before the lattice runs); dyn_tdt_lattice_run is the alpha / beta launch (beta only
+ *                         with want_beta: the gradient needs it), the reduction into loss and the per-row nll; dyn_tdt_grad_chunk writes
+ *                         the chunk's gradient (grad may be its logits).  The same kernels as dyn_tdt_loss, a row's arithmetic depends on
+ *                         its own logits and on the lattice state alone: every output is bit-equal to dyn_tdt_loss's on the whole tensor,
+ *                         whatever the chunking.  state_budget_bytes > 0 refuses a larger lattice state by name (DYN_E_WORKSPACE):
+ *                         only the joint is chunked, not the state.
+ *   dyn_joint_bwd_chunk   dyn_joint_bwd on z / dz [B, Tc, U1, Hd] of a chunk of frames: de points at the chunk's first frame inside a
+ *                         longer [B, T, Hd] (batch rows de_stride_b floats apart) and receives the same bits as those rows of
+ *                         dyn_joint_bwd; with dp_accumulate = 1 the chunk's sum over its frames is ADDED to dp (0: written), so chunks
+ *                         launched in ascending order on one stream give a fixed summation order, without float atomics.
  *   dyn_tdt_greedy_steps  replaces ParakeetTDTGenerationMixin's greedy loop, n_steps steps per call with all state on the device, in
  *                         the manner of dyn_decoder_steps.  istate int32 [6, B]: frame pointer, last token, emit flag, done flag, output
  *                         count, steps taken (the caller starts with last token = the start token and emit = 1: the first step then
@@ -1028,6 +1044,18 @@ int dyn_tdt_loss(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t 
                  const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank,
                  float sigma, int32_t reduction, float grad_scale, float* loss, float* nll_per_row, float* grad, void* workspace,
                  int64_t workspace_bytes, int64_t workspace_budget_bytes, void* stream);
+int dyn_tdt_arcs_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+                       const int32_t* targets, int64_t S, const int32_t* target_lengths, int32_t blank, float sigma, int64_t t0, int64_t Tc,
+                       void* state, int64_t state_bytes, int64_t state_budget_bytes, void* stream);
+int dyn_tdt_lattice_run(int64_t B, int64_t T, int64_t U1, const int32_t* durations, int64_t D, int64_t S, const int32_t* logit_lengths,
+                        const int32_t* target_lengths, int32_t reduction, float* loss, float* nll_per_row, int32_t want_beta, void* state,
+                        int64_t state_bytes, int64_t state_budget_bytes, void* stream);
+int dyn_tdt_grad_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+                       const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank,
+                       int32_t reduction, float grad_scale, int64_t t0, int64_t Tc, float* grad, const void* state, int64_t state_bytes,
+                       void* stream);
+int dyn_joint_bwd_chunk(const float* dz, const float* z, float* de, float* dp, int64_t B, int64_t Tc, int64_t U1, int64_t Hd, int32_t shared_p,
+                        int64_t de_stride_b, int64_t dp_stride_b, int64_t dp_stride_u, int32_t dp_accumulate, int32_t act, void* stream);
 int dyn_tdt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs, const float* proj_w,
                          const float* proj_b, const float* head_w, const float* head_b, int32_t* istate, float* h, float* c, float* h_new,
                          float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd, int64_t layers,

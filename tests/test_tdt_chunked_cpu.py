@@ -1,0 +1,127 @@
+"""The host side of the joint streamed over frame chunks (parakeet_tdt_model.plan_joint_chunk, the chunk entries of csrc/transducer.hip,
+the refusals of ParakeetForTDT.backward and ops.tdt_state): what can be checked without a GPU."""
+import ctypes
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+
+def test_plan_joint_chunk():
+    """One frame of z + logits + dz is B * U1 * (2 Hd + N) * 4 bytes.  A budget of exactly k frames gives k, one byte less k - 1; below
+    one frame the plan is 1 (frame by frame, never 0); at or above the whole joint it is T: unchunked."""
+    from dynamic_asr_eval_amd import ops
+    from dynamic_asr_eval_amd.parakeet_tdt_model import plan_joint_chunk as plan
+    B, T, U1, Hd, N = 4, 1024, 221, 640, 8198
+    frame = B * U1 * (2 * Hd + N) * 4
+    assert frame == 4 * 221 * 9478 * 4
+    for k in (1, 2, 7, 100, T - 1):
+        assert plan(B, T, U1, Hd, N, k * frame) == k
+        assert plan(B, T, U1, Hd, N, k * frame + frame - 1) == k
+        assert plan(B, T, U1, Hd, N, k * frame - 1) == max(1, k - 1)
+    assert plan(B, T, U1, Hd, N, frame - 1) == 1 and plan(B, T, U1, Hd, N, 0) == 1 and plan(B, T, U1, Hd, N, 1) == 1
+    assert plan(B, T, U1, Hd, N, T * frame) == T and plan(B, T, U1, Hd, N, T * frame - 1) == T - 1
+    assert plan(B, T, U1, Hd, N, 10 * T * frame) == T and plan(B, T, U1, Hd, N, 1 << 62) == T
+    assert plan(1, 1, 1, 4, 2, 0) == 1
+    # the issue's 82 s window does not fit the default budget, every shape of the test suite and the loop's 16-frame windows do
+    assert plan(B, T, U1, Hd, N, ops.TDT_JOINT_BUDGET) == ops.TDT_JOINT_BUDGET // frame < T
+    assert plan(3, 9, 5, 64, 38, ops.TDT_JOINT_BUDGET) == 9 and plan(4, 128, 41, 640, 8198, ops.TDT_JOINT_BUDGET) == 128
+    assert ops.TDT_JOINT_BUDGET == 8 << 30
+    for bad in ((0, 9, 5, 64, 38), (3, 0, 5, 64, 38), (3, 9, 0, 64, 38), (3, 9, 5, 0, 38), (3, 9, 5, 64, 0)):
+        with pytest.raises(ops.DynError):
+            plan(*bad, 1 << 30)
+
+
+def test_chunk_entries_are_exported_and_refuse_before_any_launch():
+    """dyn_tdt_arcs_chunk, dyn_tdt_lattice_run, dyn_tdt_grad_chunk and dyn_joint_bwd_chunk are in include/dyneval.h and in the library;
+    argument errors come back as codes before any launch, so the dummy pointers are never dereferenced: DYN_E_ARG (-1) for null
+    pointers, bad sizes, bad duration lists and a chunk that starts outside the lattice, DYN_E_UNSUPPORTED (-4) for a joint activation
+    other than relu, DYN_E_WORKSPACE (-3) for a short state and, by name, for a lattice state over the budget."""
+    from dynamic_asr_eval_amd import _lib
+    names = ("dyn_tdt_arcs_chunk", "dyn_tdt_lattice_run", "dyn_tdt_grad_chunk", "dyn_joint_bwd_chunk")
+    assert set(names) <= set(_lib.exported_symbols())
+    lib = _lib.load()
+    for n in names:
+        assert hasattr(lib, n), n
+    p, big = 256, 1 << 40
+    dur = lambda *d: ctypes.cast((ctypes.c_int32 * len(d))(*d), ctypes.c_void_p)                 # noqa: E731
+    d5 = dur(0, 1, 2, 3, 4)
+    need = lib.dyn_tdt_loss_workspace_bytes(2, 9, 6, 5)
+    bad_durs = ((dur(0, 1, 2, 3, 4, 5, 6, 7, 8), 9), (dur(-1, 1), 2), (dur(0, 2, 1), 3), (dur(1, 1), 2), (dur(0), 1), (None, 2))
+
+    # logits, B, T, U1, V1, durations, D, targets, S, target_lengths, blank, sigma, t0, Tc, state, state_bytes, budget, stream
+    arcs = lambda d=d5, D=5, logits=p, B=2, blank=8, t0=0, Tc=4, st=p, sb=big, budget=0: (  # noqa: E731
+        logits, B, 9, 6, 9, d, D, p, 5, p, blank, 0.0, t0, Tc, st, sb, budget, None)
+    for d, D in bad_durs:
+        assert lib.dyn_tdt_arcs_chunk(*arcs(d, D)) == -1 and b"dyn_tdt_arcs_chunk" in lib.dyn_last_error()
+    assert lib.dyn_tdt_arcs_chunk(*arcs(logits=None)) == -1 and lib.dyn_tdt_arcs_chunk(*arcs(B=0)) == -1
+    assert lib.dyn_tdt_arcs_chunk(*arcs(blank=9)) == -1
+    for t0, Tc in ((-1, 4), (9, 4), (0, 0), (0, -2)):
+        assert lib.dyn_tdt_arcs_chunk(*arcs(t0=t0, Tc=Tc)) == -1 and b"chunk" in lib.dyn_last_error(), (t0, Tc)
+    assert lib.dyn_tdt_arcs_chunk(*arcs(sb=need - 1)) == -3 and lib.dyn_tdt_arcs_chunk(*arcs(st=None)) == -3
+    assert lib.dyn_tdt_arcs_chunk(*arcs(budget=need - 1)) == -3
+    assert b"budget" in lib.dyn_last_error() and b"lattice state" in lib.dyn_last_error() and b"dyn_tdt_arcs_chunk" in lib.dyn_last_error()
+
+    # B, T, U1, durations, D, S, logit_lengths, target_lengths, reduction, loss, nll, want_beta, state, state_bytes, budget, stream
+    lat = lambda d=d5, D=5, B=2, S=5, il=p, red=0, loss=p, st=p, sb=big, budget=0: (  # noqa: E731
+        B, 9, 6, d, D, S, il, p, red, loss, p, 1, st, sb, budget, None)
+    for d, D in bad_durs:
+        assert lib.dyn_tdt_lattice_run(*lat(d, D)) == -1 and b"dyn_tdt_lattice_run" in lib.dyn_last_error()
+    assert lib.dyn_tdt_lattice_run(*lat(il=None)) == -1 and lib.dyn_tdt_lattice_run(*lat(loss=None)) == -1
+    assert lib.dyn_tdt_lattice_run(*lat(B=0)) == -1 and lib.dyn_tdt_lattice_run(*lat(S=0)) == -1
+    assert lib.dyn_tdt_lattice_run(*lat(red=5)) == -1 and lib.dyn_tdt_lattice_run(*lat(red=-1)) == -1
+    assert lib.dyn_tdt_lattice_run(*lat(sb=need - 1)) == -3 and lib.dyn_tdt_lattice_run(*lat(st=None)) == -3
+    assert lib.dyn_tdt_lattice_run(*lat(budget=need - 1)) == -3 and b"budget" in lib.dyn_last_error() and b"lattice state" in lib.dyn_last_error()
+
+    # logits, B, T, U1, V1, durations, D, targets, S, logit_lengths, target_lengths, blank, reduction, grad_scale, t0, Tc, grad, state, bytes, stream
+    grad = lambda d=d5, D=5, B=2, blank=8, red=0, t0=0, Tc=4, g=p, st=p, sb=big: (  # noqa: E731
+        p, B, 9, 6, 9, d, D, p, 5, p, p, blank, red, 1.0, t0, Tc, g, st, sb, None)
+    for d, D in bad_durs:
+        assert lib.dyn_tdt_grad_chunk(*grad(d, D)) == -1 and b"dyn_tdt_grad_chunk" in lib.dyn_last_error()
+    assert lib.dyn_tdt_grad_chunk(*grad(g=None)) == -1 and lib.dyn_tdt_grad_chunk(*grad(B=0)) == -1
+    assert lib.dyn_tdt_grad_chunk(*grad(blank=-1)) == -1 and lib.dyn_tdt_grad_chunk(*grad(red=5)) == -1
+    for t0, Tc in ((-1, 4), (9, 1), (3, 0)):
+        assert lib.dyn_tdt_grad_chunk(*grad(t0=t0, Tc=Tc)) == -1 and b"chunk" in lib.dyn_last_error(), (t0, Tc)
+    assert lib.dyn_tdt_grad_chunk(*grad(sb=need - 1)) == -3 and lib.dyn_tdt_grad_chunk(*grad(st=None)) == -3
+
+    # dz, z, de, dp, B, Tc, U1, Hd, shared_p, de_stride_b, dp_stride_b, dp_stride_u, dp_accumulate, act, stream
+    jb = lambda dz=p, de=p, dp=p, Tc=2, Hd=64, sde=7 * 64, su=64, acc=1, act=0: (  # noqa: E731
+        dz, p, de, dp, 1, Tc, 3, Hd, 0, sde, 192, su, acc, act, None)
+    assert lib.dyn_joint_bwd_chunk(*jb(act=1)) == -4 and b"hidden_act" in lib.dyn_last_error()
+    assert lib.dyn_joint_bwd_chunk(*jb(dz=None)) == -1 and lib.dyn_joint_bwd_chunk(*jb(de=None, dp=None)) == -1
+    assert lib.dyn_joint_bwd_chunk(*jb(Tc=0)) == -1 and lib.dyn_joint_bwd_chunk(*jb(Hd=66, su=66)) == -1
+    assert lib.dyn_joint_bwd_chunk(*jb(sde=64)) == -1 and b"de_stride_b" in lib.dyn_last_error()          # fewer floats than the chunk's frames
+    assert lib.dyn_joint_bwd_chunk(*jb(sde=7 * 64 + 2)) == -1 and lib.dyn_joint_bwd_chunk(*jb(su=32)) == -1
+    assert lib.dyn_joint_bwd_chunk(*jb(acc=2)) == -1 and b"dp_accumulate" in lib.dyn_last_error()
+    assert lib.dyn_joint_bwd_chunk(*jb(de=p + 4)) == -1 and b"aligned" in lib.dyn_last_error()
+
+
+def test_grad_logits_after_a_chunked_forward_is_refused_by_name():
+    """backward(grad_logits=...) wants the gradient of logits that a chunked forward never held whole: refused on the host, by name,
+    before anything else of the model is touched (a bare namespace stands in for it)."""
+    from dynamic_asr_eval_amd import parakeet_tdt_model as TM
+    from dynamic_asr_eval_amd.ops import DynError
+    stub = SimpleNamespace(_tdt=dict(rows=2, chunked=dict(frames=4)))
+    with pytest.raises(DynError) as e:
+        TM.ParakeetForTDT.backward(stub, grad_logits=torch.zeros(2, 9, 5, 38))
+    assert "grad_logits" in str(e.value) and "chunked forward" in str(e.value) and "4 frames" in str(e.value)
+    with pytest.raises(DynError) as e:
+        TM.ParakeetForTDT.backward(stub, n_active=3)
+    assert "n_active" in str(e.value)
+    with pytest.raises(DynError) as e:
+        TM.ParakeetForTDT._joint_frames(SimpleNamespace(), 2, 9, 5, 0)
+    assert "frames_per_chunk" in str(e.value)
+    assert TM.ParakeetForTDT._joint_frames(SimpleNamespace(), 2, 9, 5, 12) == 9                  # at or above T': unchunked
+
+
+def test_lattice_state_over_the_budget_is_refused_by_name_on_the_host():
+    """Only the joint streams over chunks: a lattice state over ops.TDT_WORKSPACE_BUDGET stays a named refusal, before any allocation."""
+    from dynamic_asr_eval_amd import ops
+    with pytest.raises(ops.DynError) as e:
+        ops.tdt_state(4, 4096, 900, (0, 1, 2, 3, 4), "cuda:0")
+    assert "budget" in str(e.value) and "lattice state" in str(e.value)
+    with pytest.raises(ops.DynError) as e:
+        ops.tdt_state(2, 9, 6, (0, 1, 2, 3, 4), "cuda:0", budget=1000)
+    assert "budget" in str(e.value)
+    with pytest.raises(ops.DynError):
+        ops.tdt_state(2, 9, 6, (0, 2, 1), "cuda:0")
