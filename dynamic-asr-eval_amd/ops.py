@@ -2366,3 +2366,158 @@ def tdt_greedy_steps(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_
                                     state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(), state.tokens.data_ptr(),
                                     state.frames.data_ptr(), B, T, Hd, layers, V1, ctypes.cast(dur, ctypes.c_void_p), D, blank, state.n_max,
                                     int(max_steps), int(n_steps), _stream()), "dyn_tdt_greedy_steps")
+
+
+# ----------------------------------------------------------------------------------------------- RNN-T (ParakeetForRNNT; csrc/transducer.hip)
+RNNT_WORKSPACE_BUDGET = TDT_WORKSPACE_BUDGET      # bytes of lattice state (20 B per cell) an RNN-T loss may ask for; the state is never chunked
+
+
+def _rnnt_args(who, logits, targets, target_lengths, blank, T=1, state=None):
+    _c(logits, who + ".logits"); _c(targets, who + ".targets", I32); _cc(target_lengths, who + ".target_lengths", I32)
+    if state is not None:
+        _cc(state, who + ".state", torch.uint8)
+    if logits.dim() != 4:
+        raise DynError(f"{who}: logits {tuple(logits.shape)} must be [B, T, U + 1, V + 1] (an RNN-T joint has no duration columns)")
+    B = logits.shape[0]
+    if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or target_lengths.numel() != B or int(T) < 1:
+        raise DynError(f"{who}: targets {tuple(targets.shape)} must be [B, S >= 1], the lengths [B], T positive")
+    if not 0 <= int(blank) < logits.shape[3]:
+        raise DynError(f"{who}: blank={blank} lies outside the {logits.shape[3]} classes")
+
+
+def _rnnt_reduction(who, reduction):
+    if reduction not in TDT_REDUCTIONS:
+        raise DynError(f"{who}: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
+    return TDT_REDUCTIONS[reduction]
+
+
+def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank, reduction="mean_volume", grad_scale=1.0, want_grad=True, out=None,
+              budget=None):
+    """logits [B, T, U1, V1] contiguous; targets int32 [B, S >= 1]; lengths int32 [B] (all on the device).
+    Returns (loss [1], nll [B], grad [B, T, U1, V1] of grad_scale * loss or None) with transformers' rnnt_loss semantics: its five
+    reductions under ops.TDT_REDUCTIONS' codes, default "mean_volume" (reduction "none": loss is the sum, the rows are nll).  `out` may
+    be logits (the gradient written over them)."""
+    _rnnt_args("rnnt_loss", logits, targets, target_lengths, blank)
+    _cc(logit_lengths, "rnnt_loss.logit_lengths", I32)
+    red = _rnnt_reduction("rnnt_loss", reduction)
+    B, T, U1, V1 = logits.shape
+    if logit_lengths.numel() != B:
+        raise DynError(f"rnnt_loss: the lengths must be [{B}]")
+    loss = torch.empty(1, device=logits.device, dtype=F32)
+    nll = torch.empty(B, device=logits.device, dtype=F32)
+    grad = None
+    if want_grad:
+        grad = torch.empty_like(logits) if out is None else _c(out, "rnnt_loss.out")
+        if grad.shape != logits.shape:
+            raise DynError(f"rnnt_loss: out {tuple(grad.shape)} != logits {tuple(logits.shape)}")
+    ws = workspace(logits.device)
+    check(_L().dyn_rnnt_loss(logits.data_ptr(), B, T, U1, V1, targets.data_ptr(), targets.shape[1], logit_lengths.data_ptr(),
+                             target_lengths.data_ptr(), int(blank), red, grad_scale, loss.data_ptr(), nll.data_ptr(),
+                             0 if grad is None else grad.data_ptr(), ws.data_ptr(), ws.numel(),
+                             RNNT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_rnnt_loss")
+    return loss, nll, grad
+
+
+def rnnt_state(B, T, U1, device, budget=None):
+    """A caller-owned lattice state for rnnt_arcs_chunk / rnnt_lattice_run / rnnt_grad_chunk (uint8, dyn_rnnt_loss_workspace_layout's
+    layout; rnnt_lattice(state=) reads it back).  Over `budget` (default RNNT_WORKSPACE_BUDGET) it is refused by name before anything
+    is allocated: the joint streams over frame chunks, the lattice state does not."""
+    need = _L().dyn_rnnt_loss_workspace_bytes(B, T, U1)
+    budget = RNNT_WORKSPACE_BUDGET if budget is None else int(budget)
+    if need < 0:
+        raise DynError(f"rnnt_state: bad lattice [{B}, {T}, {U1}]")
+    if 0 < budget < need:
+        raise DynError(f"rnnt_state: the lattice of [{B}, {T}, {U1}] needs {need} bytes of state, over the workspace budget of {budget} "
+                       "(chunking the lattice state is not built: only the joint streams over frame chunks)")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def rnnt_arcs_chunk(logits, t0, T, targets, target_lengths, blank, state, budget=None):
+    """The arcs pass of rnnt_loss on the frames [t0, t0 + Tc) of a lattice of T frames: logits [B, Tc, U1, V1] (a chunk may overhang T,
+    those rows are not read) -> lp and lse of those cells in `state` (rnnt_state).  Every frame has to be covered before rnnt_lattice_run."""
+    _rnnt_args("rnnt_arcs_chunk", logits, targets, target_lengths, blank, T, state)
+    B, Tc, U1, V1 = logits.shape
+    check(_L().dyn_rnnt_arcs_chunk(logits.data_ptr(), B, int(T), U1, V1, targets.data_ptr(), targets.shape[1], target_lengths.data_ptr(),
+                                   int(blank), int(t0), Tc, state.data_ptr(), state.numel(),
+                                   RNNT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_rnnt_arcs_chunk")
+
+
+def rnnt_lattice_run(B, T, U1, S, logit_lengths, target_lengths, state, reduction="mean_volume", want_beta=True, budget=None):
+    """The lattice and the reduction of rnnt_loss on a state the arcs pass filled -> (loss [1], nll [B]); beta (the gradient pass needs
+    it) only with want_beta.  S = the width of the targets tensor the arcs pass saw (it caps the target lengths)."""
+    _cc(logit_lengths, "rnnt_lattice_run.logit_lengths", I32); _cc(target_lengths, "rnnt_lattice_run.target_lengths", I32)
+    _cc(state, "rnnt_lattice_run.state", torch.uint8)
+    red = _rnnt_reduction("rnnt_lattice_run", reduction)
+    if logit_lengths.numel() != B or target_lengths.numel() != B:
+        raise DynError(f"rnnt_lattice_run: the lengths must be [{B}]")
+    loss = torch.empty(1, device=state.device, dtype=F32)
+    nll = torch.empty(B, device=state.device, dtype=F32)
+    check(_L().dyn_rnnt_lattice_run(B, T, U1, int(S), logit_lengths.data_ptr(), target_lengths.data_ptr(), red, loss.data_ptr(), nll.data_ptr(),
+                                    int(bool(want_beta)), state.data_ptr(), state.numel(),
+                                    RNNT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_rnnt_lattice_run")
+    return loss, nll
+
+
+def rnnt_grad_chunk(logits, t0, T, targets, logit_lengths, target_lengths, blank, state, reduction="mean_volume", grad_scale=1.0, out=None):
+    """The gradient pass of rnnt_loss on the frames [t0, t0 + Tc): the gradient of grad_scale * loss w.r.t. the chunk's logits
+    [B, Tc, U1, V1], from a state rnnt_lattice_run(want_beta=True) completed.  `out` may be the logits; rows past T are zeros."""
+    _rnnt_args("rnnt_grad_chunk", logits, targets, target_lengths, blank, T, state)
+    _cc(logit_lengths, "rnnt_grad_chunk.logit_lengths", I32)
+    red = _rnnt_reduction("rnnt_grad_chunk", reduction)
+    B, Tc, U1, V1 = logits.shape
+    grad = torch.empty_like(logits) if out is None else _c(out, "rnnt_grad_chunk.out")
+    if grad.shape != logits.shape or logit_lengths.numel() != B:
+        raise DynError(f"rnnt_grad_chunk: out {tuple(grad.shape)} != logits {tuple(logits.shape)}, or the lengths are not [{B}]")
+    check(_L().dyn_rnnt_grad_chunk(logits.data_ptr(), B, int(T), U1, V1, targets.data_ptr(), targets.shape[1], logit_lengths.data_ptr(),
+                                   target_lengths.data_ptr(), int(blank), red, grad_scale, int(t0), Tc, grad.data_ptr(), state.data_ptr(),
+                                   state.numel(), _stream()), "dyn_rnnt_grad_chunk")
+    return grad
+
+
+def rnnt_lattice(B, T, U1, device, state=None):
+    """What the last ops.rnnt_loss call of this (device, stream) left in the workspace (or what the chunk entries left in `state`), as
+    absolute values: (alpha [B, T, U1], beta [B, T, U1] (written only when a gradient was asked for), lp [B, T, U1, 2], lse [B, T, U1]).
+    The integer bases of the anti-diagonals are added back here in float64 (host arithmetic, for tests)."""
+    off = (ctypes.c_int64 * 8)()
+    check(_L().dyn_rnnt_loss_workspace_layout(B, T, U1, ctypes.cast(off, ctypes.c_void_p)), "dyn_rnnt_loss_workspace_layout")
+    ws = workspace(device) if state is None else state
+    cells = B * T * U1
+
+    def view(i, n, shape):
+        return ws[off[i]:off[i] + 4 * n].view(F32).view(shape)
+
+    diag = (torch.arange(T, device=ws.device)[:, None] + torch.arange(U1, device=ws.device)[None, :]).expand(B, T, U1).reshape(B, -1)
+    alpha = view(2, cells, (B, T, U1)).double() + view(4, B * (T + U1), (B, T + U1)).double().gather(1, diag).view(B, T, U1)
+    beta = view(3, cells, (B, T, U1)).double() + view(5, B * (T + U1), (B, T + U1)).double().gather(1, diag).view(B, T, U1)
+    return alpha, beta, view(0, cells * 2, (B, T, U1, 2)), view(1, cells, (B, T, U1))
+
+
+class RnntGreedyState(TdtGreedyState):
+    """Device state of a greedy RNN-T decode (dyn_rnnt_greedy_steps): TdtGreedyState with one more int32 row of istate ([7, B]), the
+    symbols emitted at the current frame; the logits row is [B, V1]."""
+
+    def __init__(self, B, Hd, layers, V1, n_max, start_token, device):
+        super().__init__(B, Hd, layers, V1, n_max, start_token, device)
+        first = self.istate
+        self.istate = torch.zeros(7, B, device=device, dtype=I32)
+        self.istate[:6] = first
+
+
+def rnnt_greedy_steps(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, blank, max_symbols, max_steps, n_steps):
+    """n_steps greedy RNN-T steps of every live row, queued from one call.  enc [B, T, Hd]; valid int32 [B]; lstm_ptrs int64 DEVICE tensor
+    [4 * layers] of data pointers (w_ih, w_hh, b_ih, b_hh per layer); head_w [V1, Hd]; `max_symbols`: max_symbols_per_step."""
+    _cc(enc, "rnnt_greedy.enc"); _cc(valid, "rnnt_greedy.valid", I32); _cc(embed, "rnnt_greedy.embed"); _cc(lstm_ptrs, "rnnt_greedy.lstm_ptrs", torch.int64)
+    for t, n in ((proj_w, "proj_w"), (proj_b, "proj_b"), (head_w, "head_w"), (head_b, "head_b")):
+        _cc(t, "rnnt_greedy." + n)
+    B, T, Hd = enc.shape
+    layers = state.h.shape[0]
+    V1 = head_w.shape[0]
+    if (tuple(state.h.shape) != (layers, B, Hd) or lstm_ptrs.numel() != 4 * layers or embed.shape != (V1, Hd) or head_w.shape[1] != Hd
+            or tuple(proj_w.shape) != (Hd, Hd) or tuple(state.logits.shape) != (B, V1) or tuple(state.istate.shape) != (7, B)
+            or valid.numel() != B or head_b.numel() != V1 or not 0 <= blank < V1 or int(max_symbols) < 1):
+        raise DynError("rnnt_greedy_steps: shapes of the state (RnntGreedyState), the weights and enc do not fit together")
+    check(_L().dyn_rnnt_greedy_steps(enc.data_ptr(), valid.data_ptr(), embed.data_ptr(), lstm_ptrs.data_ptr(), proj_w.data_ptr(), proj_b.data_ptr(),
+                                     head_w.data_ptr(), head_b.data_ptr(), state.istate.data_ptr(), state.h.data_ptr(), state.c.data_ptr(),
+                                     state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(), state.tokens.data_ptr(),
+                                     state.frames.data_ptr(), B, T, Hd, layers, V1, int(blank), int(max_symbols), state.n_max, int(max_steps),
+                                     int(n_steps), _stream()), "dyn_rnnt_greedy_steps")

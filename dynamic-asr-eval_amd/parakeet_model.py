@@ -29,8 +29,8 @@ reductions are the parent's, found under the parent's names through an alias tab
 Not built, refused by name before any launch: `subsampling_factor` != 8, `subsampling_conv_kernel_size` != 3, `subsampling_conv_stride` != 2,
 `subsampling_conv_channels` not a multiple of 4, `num_mel_bins` not a multiple of 8, `hidden_size` outside 256 / 512 / 768 / 1024,
 `conv_kernel_size` != 9, `hidden_act` != "silu", `num_key_value_heads` != `num_attention_heads`, a `head_dim` other than hidden_size / heads,
-an `attention_mask` argument.  Bucketed hipGraph replay, lockstep groups, ParakeetForRNNT are out of scope (ParakeetForTDT: since built,
-parakeet_tdt_model.py).  No hub checkpoint is on
+an `attention_mask` argument.  Bucketed hipGraph replay and lockstep groups are out of scope (ParakeetForTDT and ParakeetForRNNT: since built,
+parakeet_tdt_model.py, parakeet_rnnt_model.py).  No hub checkpoint is on
 the machine: transformers' ParakeetForCTC on the CPU with the same (random) state dict is the oracle in the tests."""
 import contextlib
 import math

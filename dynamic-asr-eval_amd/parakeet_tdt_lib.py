@@ -1,4 +1,7 @@
-"""Dynamic evaluation of a token-and-duration transducer (parakeet_tdt_model.ParakeetForTDT) on transducer pseudo-labels.
+"""Dynamic evaluation of a transducer on transducer pseudo-labels: the token-and-duration one (parakeet_tdt_model.ParakeetForTDT) or the
+plain RNN-T (parakeet_rnnt_model.ParakeetForRNNT, a subclass).  The loop reaches the model only through encode / generate / head /
+backward and reads nothing of the head's own (no `durations`): with a ParakeetForRNNT "the TDT loss" below is ops.rnnt_loss and "the
+greedy TDT decode" the RNN-T stepping rule.  `dynamic_eval_transducer_loss` is the head-neutral name of `dynamic_eval_tdt_loss`.
 
 The reference has NO transducer loop: this one is DEFINED HERE, on the pattern of its third loop (reference nvidia_ctc/lib.py:35-193) as
 nvidia_ctc_lib.dynamic_eval_ctc_loss mirrors it, with the same signature, flags and `apply_args`.  Line by line against that loop:
@@ -159,4 +162,4 @@ def dynamic_eval_tdt_loss(args, model, spec, seq_len, overlap, tokenizer, use_tq
     return ids, frames, tokenizer.ids_to_text(ids)
 
 
-dynamic_eval = dynamic_eval_tdt_loss
+dynamic_eval = dynamic_eval_transducer_loss = dynamic_eval_tdt_loss

@@ -27,7 +27,7 @@ transformers modeling_parakeet.py: ParakeetForTDT) as transformers builds it in 
     INDEX, the same thing for the released checkpoints' durations 0 .. D - 1), by 1 for a blank with duration 0.
 
 Refused by name before any launch: `attention_mask`, a `hidden_act` of the joint other than "relu", more than 8 durations, negative or
-unsorted durations, `model_type: "parakeet_rnnt"` (ParakeetForRNNT: no duration head; its oracle loss needs torchaudio), and whatever
+unsorted durations, `model_type: "parakeet_rnnt"` (ParakeetForRNNT: no duration head; parakeet_rnnt_model builds it on this class), and whatever
 parakeet_model.make_config refuses of the encoder.  Out of scope: beam / MAES decoding, ragged batches in the model (the loss kernel's
 per-row lengths are built), a waveform front end, hipGraph replay and lockstep groups, chunking the joint over u or the lattice state, a
 log-sum-exp in the GEMM's epilogue that never writes the logits.  No hub checkpoint is
@@ -50,14 +50,27 @@ def make_config(cfg=None):
     """transformers' ParakeetTDTConfig (the object, or the nested dict of a config.json; None: its defaults) -> the flat dict this module
     reads: parakeet_model.make_config's encoder keys plus the head's.  The joint's `hidden_act` is kept as `joint_hidden_act` (the
     encoder has a `hidden_act` of its own)."""
-    get = (lambda k: cfg.get(k)) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k, None))
-    head = dict(DEFAULT_HEAD)
+    get = _getter(cfg)
     if cfg is not None:
         mt = get("model_type")
         if mt == "parakeet_rnnt" or (mt is None and get("durations") is None and type(cfg).__name__ == "ParakeetRNNTConfig"):
-            raise ops.DynError("ParakeetForRNNT (model_type \"parakeet_rnnt\") is not built: this module is the TDT head (ParakeetForTDT)")
+            raise ops.DynError("ParakeetForRNNT (model_type \"parakeet_rnnt\") is not built by this module, the TDT head (ParakeetForTDT): "
+                               "parakeet_rnnt_model.ParakeetForRNNT builds it")
         if mt is not None and mt != "parakeet_tdt":
             raise ops.DynError(f"model_type={mt!r} is not a ParakeetForTDT configuration (\"parakeet_tdt\")")
+    return head_config(cfg, DEFAULT_HEAD)
+
+
+def _getter(cfg):
+    return (lambda k: cfg.get(k)) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k, None))
+
+
+def head_config(cfg, defaults):
+    """make_config behind the model_type check, for both transducer heads: `defaults` holds the head's keys (with `durations`: TDT;
+    without: RNN-T, `durations` of the result is then empty and the joint head is [V + 1, Hd])."""
+    get = _getter(cfg)
+    head = dict(defaults)
+    if cfg is not None:
         for k in head:
             v = get(k)
             if v is not None:
@@ -67,7 +80,7 @@ def make_config(cfg=None):
     if head["hidden_act"] not in ops.JOINT_ACTS:
         raise ops.DynError(f"hidden_act={head['hidden_act']!r} of the joint is not built ({sorted(ops.JOINT_ACTS)})")
     out["joint_hidden_act"] = head["hidden_act"]
-    out["durations"] = ops.check_durations(head["durations"])
+    out["durations"] = ops.check_durations(head["durations"]) if "durations" in head else ()
     Hd, L, V1 = (int(head[k]) for k in ("decoder_hidden_size", "num_decoder_layers", "vocab_size"))
     if Hd < 4 or Hd % 4:
         raise ops.DynError(f"decoder_hidden_size={Hd} is not built: a positive multiple of 4 (16-byte rows)")
@@ -139,6 +152,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
     _param_spec = staticmethod(param_spec)
     frozen_in_the_loop = FROZEN_IN_THE_LOOP
     greedy_chunk = 32                                    # greedy steps queued per host call; the done flags are read once per chunk
+    default_reduction = "mean"                           # tdt_loss's
 
     def __init__(self, config=None, device="cuda:0"):
         super().__init__(config, device)
@@ -159,6 +173,37 @@ class ParakeetForTDT(PM.ParakeetForCTC):
 
     def _encoder_frozen(self):
         return not any(self.trainable(n) for n, _ in self.spec if n.startswith(("encoder.", PROJ)))
+
+    # ------------------------------------------------------------------ what differs between the transducer heads (ParakeetForRNNT overrides)
+    def _label_lengths(self, lab):
+        """transformers' ParakeetForTDT.forward counts `labels != pad_token_id`."""
+        return (lab != self.cfg["pad_token_id"]).sum(-1).to(torch.int32)
+
+    def _loss_whole(self, logits, tg, ilen, tlen, sigma, reduction, grad_scale, want_grad):
+        return ops.tdt_loss(logits, tg, ilen, tlen, self.blank, self.cfg["durations"], sigma, reduction, grad_scale, want_grad=want_grad)
+
+    def _loss_state(self, nb, T, U1, reduction, sigma):
+        if reduction not in ops.TDT_REDUCTIONS:
+            raise ops.DynError(f"reduction={reduction!r} is not one of {sorted(ops.TDT_REDUCTIONS)}")
+        return ops.tdt_state(nb, T, U1, self.cfg["durations"], self.device)                       # over TDT_WORKSPACE_BUDGET: refused by name
+
+    def _loss_arcs_chunk(self, logits, t0, T, tg, tlen, state, sigma):
+        ops.tdt_arcs_chunk(logits, t0, T, tg, tlen, self.blank, self.cfg["durations"], state, sigma)
+
+    def _loss_lattice_run(self, nb, T, U1, S, ilen, tlen, state, reduction, want_beta):
+        return ops.tdt_lattice_run(nb, T, U1, S, ilen, tlen, self.cfg["durations"], state, reduction, want_beta)
+
+    def _loss_grad_chunk(self, logits, t0, T, tg, ilen, tlen, state, reduction, grad_scale):
+        return ops.tdt_grad_chunk(logits, t0, T, tg, ilen, tlen, self.blank, self.cfg["durations"], state, reduction, grad_scale, out=logits)
+
+    def _greedy_state(self, B, cap):
+        return ops.TdtGreedyState(B, self.Hd, self.cfg["num_decoder_layers"], self.V1 + self.D, cap, self.start_token, self.device)
+
+    def _greedy_steps(self, enc, valid, st, cap, n):
+        P = self.P
+        ops.tdt_greedy_steps(enc, valid, P[DEC + "embedding.weight"], self._lstm_ptrs, P[DEC + "decoder_projector.weight"],
+                             P[DEC + "decoder_projector.bias"], P[JOINT + "head.weight"], P[JOINT + "head.bias"], st, self.cfg["durations"],
+                             self.blank, cap, n)
 
     # ------------------------------------------------------------------ encoder
     def _encode(self, h, ctx, vT, dims, v0):
@@ -258,20 +303,17 @@ class ParakeetForTDT(PM.ParakeetForCTC):
     def _head_chunked(self, e, p, Tc, tg, ilen, tlen, reduction, sigma, want_beta):
         """Passes 1 and 2 of the chunked loss: the arcs of every chunk of Tc frames into a lattice state this call owns (the joint of a
         chunk is dropped as soon as its arcs are written), then the lattice -> (loss, nll, state)."""
-        c = self.cfg
         nb, T, _ = e.shape
         U1 = p.shape[0]
-        if reduction not in ops.TDT_REDUCTIONS:
-            raise ops.DynError(f"reduction={reduction!r} is not one of {sorted(ops.TDT_REDUCTIONS)}")
-        state = ops.tdt_state(nb, T, U1, c["durations"], self.device)                              # over TDT_WORKSPACE_BUDGET: refused by name
+        state = self._loss_state(nb, T, U1, reduction, sigma)
         zbuf, lbuf, _ = self._chunk_buffers(nb, Tc, U1, False)
         for t0 in range(0, T, Tc):
             _, logits = self._joint_chunk(e, p, t0, min(Tc, T - t0), zbuf, lbuf)
-            ops.tdt_arcs_chunk(logits, t0, T, tg, tlen, self.blank, c["durations"], state, sigma)
-        loss, nll = ops.tdt_lattice_run(nb, T, U1, tg.shape[1], ilen, tlen, c["durations"], state, reduction, want_beta)
+            self._loss_arcs_chunk(logits, t0, T, tg, tlen, state, sigma)
+        loss, nll = self._loss_lattice_run(nb, T, U1, tg.shape[1], ilen, tlen, state, reduction, want_beta)
         return loss, nll, state
 
-    def head(self, enc, decoder_input_ids, labels=None, reduction="mean", sigma=0.0, grad_scale=1.0, n_active=None, label_lengths=None,
+    def head(self, enc, decoder_input_ids, labels=None, reduction=None, sigma=0.0, grad_scale=1.0, n_active=None, label_lengths=None,
              frames_per_chunk=None):
         """The prediction network, the joint and (with labels) the TDT loss on the first n_active rows of enc [B, T', Hd].
         decoder_input_ids [n_active or 1, U + 1] (one row: shared by every copy); labels [same rows, U], padded with pad_token_id
@@ -283,6 +325,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         joint streams over chunks of frames (module docstring): `logits` is then None, loss and nll are those of the whole-joint path,
         and backward() recomputes the joint chunk by chunk."""
         c, P, Hd = self.cfg, self.P, self.Hd
+        reduction = self.default_reduction if reduction is None else reduction
         B, T, _ = enc.shape
         nb = B if n_active is None else int(n_active)
         if not 1 <= nb <= B:
@@ -309,7 +352,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
                 if lab.shape[0] == 1 and nb > 1:
                     lab = lab.expand(nb, -1)
                 if label_lengths is None:
-                    tlen = (lab != c["pad_token_id"]).sum(-1).to(torch.int32)
+                    tlen = self._label_lengths(lab)
                 else:
                     tlen = torch.as_tensor(list(label_lengths), dtype=torch.int32).reshape(-1)
                     if tlen.numel() == 1 and nb > 1:
@@ -319,8 +362,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
                 tg = (lab.to(torch.int32).contiguous() if U1 > 1 else torch.zeros(nb, 1, dtype=torch.int32)).to(self.device)
                 ilen, tlen = torch.full((nb,), T, dtype=torch.int32, device=self.device), tlen.to(self.device)
                 if Tc >= T:
-                    loss, nll, dlogits = ops.tdt_loss(logits, tg, ilen, tlen, self.blank, c["durations"], float(sigma), reduction, float(grad_scale),
-                                                      want_grad=grad_mode)
+                    loss, nll, dlogits = self._loss_whole(logits, tg, ilen, tlen, float(sigma), reduction, float(grad_scale), grad_mode)
                 else:
                     loss, nll, state = self._head_chunked(e, p, Tc, tg, ilen, tlen, reduction, float(sigma), grad_mode)
                     # what the gradient pass needs, in tensors of this call's own: nothing of it lives in the shared scratch
@@ -328,7 +370,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         self._tdt = dict(z=z, p_rows=ids.shape[0], dec=dec_saved, rows=nb, dlogits=dlogits, chunked=chunked) if grad_mode else None
         return SimpleNamespace(logits=logits, loss=loss, nll=nll, frames=T)
 
-    def forward(self, input_features, decoder_input_ids=None, labels=None, attention_mask=None, reduction="mean", sigma=0.0, grad_scale=1.0,
+    def forward(self, input_features, decoder_input_ids=None, labels=None, attention_mask=None, reduction=None, sigma=0.0, grad_scale=1.0,
                 n_active=None, label_lengths=None, frames_per_chunk=None):
         """input_features [B, T, num_mel_bins] float32 on the device, decoder_input_ids [B or 1, U + 1] -> SimpleNamespace(logits
         [B, T', U + 1, V + 1 + D] (None when the joint was chunked: head()), loss, nll, frames = T', enc [B, T', Hd]).  `attention_mask`
@@ -392,8 +434,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         dp = torch.empty(U1, t["p_rows"], Hd, device=self.device, dtype=torch.float32) if need_dec else None
         for t0 in range(0, T, Tc):
             z, logits = self._joint_chunk(e, p, t0, min(Tc, T - t0), zbuf, lbuf)
-            g = ops.tdt_grad_chunk(logits, t0, T, k["tg"], k["ilen"], k["tlen"], self.blank, self.cfg["durations"], k["state"], k["reduction"],
-                                   k["grad_scale"], out=logits).view(-1, N)
+            g = self._loss_grad_chunk(logits, t0, T, k["tg"], k["ilen"], k["tlen"], k["state"], k["reduction"], k["grad_scale"]).view(-1, N)
             if head_grads:                                   # as _lin_bwd: both sums unless both are frozen
                 ops.linear_wgrad(g, z.view(-1, Hd), G[wn], beta=1.0)
                 ops.colsum(g, G[bn], beta=1.0)
@@ -448,15 +489,12 @@ class ParakeetForTDT(PM.ParakeetForCTC):
             enc = enc.detach().contiguous()
             B, T, _ = enc.shape
             cap = c["max_symbols_per_step"] * T
-            st = ops.TdtGreedyState(B, self.Hd, c["num_decoder_layers"], self.V1 + self.D, cap, self.start_token, self.device)
+            st = self._greedy_state(B, cap)
             valid = torch.full((B,), T, dtype=torch.int32, device=self.device)
-            P = self.P
             done = 0
             while done < cap:
                 n = min(self.greedy_chunk, cap - done)
-                ops.tdt_greedy_steps(enc, valid, P[DEC + "embedding.weight"], self._lstm_ptrs, P[DEC + "decoder_projector.weight"],
-                                     P[DEC + "decoder_projector.bias"], P[JOINT + "head.weight"], P[JOINT + "head.bias"], st, c["durations"],
-                                     self.blank, cap, n)
+                self._greedy_steps(enc, valid, st, cap, n)
                 done += n
                 if bool(st.istate[3].all()):             # the one host read of the chunk
                     break

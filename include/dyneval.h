@@ -1028,6 +1028,25 @@ int dyn_convmod_brn_bwd(const float* c, const float* stats, const float* ds, flo
  *                         with duration 0; a non-blank is appended to tokens / frames [B, n_max] and sets emit.  A row is done when
  *                         its pointer reaches valid[b], after max_steps steps or n_max outputs; a done row launches no work.
  *                         `lstm_ptrs`: DEVICE array of 4 * layers pointers (w_ih, w_hh, b_ih, b_hh per layer).
+ *   dyn_rnnt_loss         replaces transformers.loss.loss_rnnt.rnnt_loss (loss/loss_rnnt.py:23-90, a wrapper around
+ *                         torchaudio.functional.rnnt_loss) and its autograd, the head of ParakeetForRNNT (`model_type: "parakeet_rnnt"`,
+ *                         modeling_parakeet.py:922-1032).  logits [B, T, U1, V1]: no duration columns.  Arcs from (t, u): a blank arc to
+ *                         (t + 1, u), a label arc to (t, u + 1); the terminal is alpha(T_b - 1, U_b) + lp_blank(T_b - 1, U_b).  The same four
+ *                         launches, integer bases, (integer, fraction) log-likelihood, reductions (0 sum, 1 mean_batch, 2 mean,
+ *                         3 mean_volume, 4 none), length clamping, zeros outside [:T_b, :U_b + 1] and workspace budget as dyn_tdt_loss;
+ *                         20 bytes of state per cell (lp 8, lse 4, alpha 4, beta 4).  A row with T_b == 0 has no terminal: nll = +inf, zero
+ *                         gradient; so has a row whose lattice -inf logits cut.
+ *   dyn_rnnt_loss_workspace_bytes / _layout   the state's size and the byte offsets of lp [.., 2], lse [.., 1], alpha, beta, abase, bbase,
+ *                         ll, nll in it (tests).
+ *   dyn_rnnt_arcs_chunk / dyn_rnnt_lattice_run / dyn_rnnt_grad_chunk   dyn_rnnt_loss in three passes against a caller-owned state, as the
+ *                         three dyn_tdt_* chunk entries: the whole form is the chunk form at t0 = 0, Tc = T, every output bit-equal
+ *                         whatever the chunking.
+ *   dyn_rnnt_greedy_steps replaces ParakeetRNNTGenerationMixin's greedy loop (generation_parakeet.py:141-163,
+ *                         _update_model_kwargs_for_generation).  dyn_tdt_greedy_steps's LSTM, projector and joint launches with N = V1;
+ *                         istate int32 [7, B]: its six rows plus the symbols emitted at the current frame.  argmax over the row (lowest
+ *                         index on ties); a blank advances the frame by one and resets the counter; a non-blank is emitted, feeds the
+ *                         prediction network and increments it; when it reaches max_symbols the frame advances anyway and the counter
+ *                         resets, the forced step's token still emitted and fed.  Done as in dyn_tdt_greedy_steps.
  * Null pointers and sizes out of range -> DYN_E_ARG, all before any launch.
  * ------------------------------------------------------------------------------------------------ */
 int dyn_lstm_cell_fwd(const float* xg, const float* hg, const float* c_prev, float* c, float* h, float* gates, int64_t Bd, int64_t Hd,
@@ -1061,6 +1080,24 @@ int dyn_tdt_greedy_steps(const float* enc, const int32_t* valid, const float* em
                          float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd, int64_t layers,
                          int64_t V1, const int32_t* durations, int64_t D, int32_t blank, int64_t n_max, int64_t max_steps,
                          int32_t n_steps, void* stream);
+int64_t dyn_rnnt_loss_workspace_bytes(int64_t B, int64_t T, int64_t U1);
+int dyn_rnnt_loss_workspace_layout(int64_t B, int64_t T, int64_t U1, int64_t* offsets8);
+int dyn_rnnt_loss(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* targets, int64_t S,
+                  const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank, int32_t reduction, float grad_scale, float* loss,
+                  float* nll_per_row, float* grad, void* workspace, int64_t workspace_bytes, int64_t workspace_budget_bytes, void* stream);
+int dyn_rnnt_arcs_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* targets, int64_t S,
+                        const int32_t* target_lengths, int32_t blank, int64_t t0, int64_t Tc, void* state, int64_t state_bytes,
+                        int64_t state_budget_bytes, void* stream);
+int dyn_rnnt_lattice_run(int64_t B, int64_t T, int64_t U1, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths,
+                         int32_t reduction, float* loss, float* nll_per_row, int32_t want_beta, void* state, int64_t state_bytes,
+                         int64_t state_budget_bytes, void* stream);
+int dyn_rnnt_grad_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* targets, int64_t S,
+                        const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank, int32_t reduction, float grad_scale,
+                        int64_t t0, int64_t Tc, float* grad, const void* state, int64_t state_bytes, void* stream);
+int dyn_rnnt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs, const float* proj_w,
+                          const float* proj_b, const float* head_w, const float* head_b, int32_t* istate, float* h, float* c, float* h_new,
+                          float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd, int64_t layers,
+                          int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max, int64_t max_steps, int32_t n_steps, void* stream);
 
 #ifdef __cplusplus
 }
