@@ -183,6 +183,7 @@ class LasrForCTC(PM.ParakeetForCTC):
     _head_bias_names = ()
     downsampling_factor = 4                                    # two stride-2 stages
     frozen_in_the_loop = FROZEN_IN_THE_LOOP
+    frames = staticmethod(frames)
 
     def __init__(self, config=None, device="cuda:0"):
         super().__init__(config, device)

@@ -2521,3 +2521,165 @@ def rnnt_greedy_steps(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head
                                      state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(), state.tokens.data_ptr(),
                                      state.frames.data_ptr(), B, T, Hd, layers, V1, int(blank), int(max_symbols), state.n_max, int(max_steps),
                                      int(n_steps), _stream()), "dyn_rnnt_greedy_steps")
+
+
+# ----------------------------------------------------------------------------------------------- NemotronAsrStreamingForRNNT
+def chunked_band(T, left_context, lookahead):
+    """Pure host function: the geometry of transformers' chunked_limited_mask_function(left_context, lookahead) over T frames.
+    cs = lookahead + 1 frames per chunk, lc = left_context // cs left chunks (-1: unlimited, left_context < 0); query i sees the keys
+    [max(0, i // cs - lc) * cs, min(T, (i // cs + 1) * cs)).  j - i then lies in [-dlo, dhi]: W = dlo + dhi + 1 relative positions,
+    the rows r0 .. r0 + W of the [2T - 1, H] position table (row T - 1 is distance 0), lc * cs + 2 cs - 1 of them once T - 1 reaches
+    both ends.  Returns SimpleNamespace(cs, lc, dlo, dhi, W, r0)."""
+    from types import SimpleNamespace
+    for name, v in (("T", T), ("left_context", left_context), ("lookahead", lookahead)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise DynError(f"chunked_band: {name}={v!r} must be an integer")
+    if T < 1 or lookahead < 0:
+        raise DynError(f"chunked_band: T={T} must be positive and lookahead={lookahead} must not be negative")
+    cs = lookahead + 1
+    lc = left_context // cs if left_context >= 0 else -1
+    dlo = T - 1 if lc < 0 else min(lc * cs + cs - 1, T - 1)
+    dhi = min(cs - 1, T - 1)
+    return SimpleNamespace(cs=cs, lc=lc, dlo=dlo, dhi=dhi, W=dlo + dhi + 1, r0=T - 1 - dlo)
+
+
+def _band_dims(who, S, BD, band):
+    if S.dim() != 4 or S.shape[2] != S.shape[3]:
+        raise DynError(f"{who}: scores must be [B, heads, T, T], got {tuple(S.shape)}")
+    M, T = S.shape[0] * S.shape[1], S.shape[-1]
+    if BD is not None and (BD.dim() != 4 or tuple(BD.shape[:3]) != tuple(S.shape[:3]) or BD.shape[3] < band.W):
+        raise DynError(f"{who}: the band buffer must be [B, heads, T, ld >= {band.W}], got {tuple(BD.shape)}")
+    return M, T
+
+
+def softmax_relshift_band(S, BD, band, out=None):
+    """softmax over the keys the chunked mask leaves row i of S [B, nh, T, T] + BD[b, h, i, j - i + band.dlo] (BD [B, nh, T, ld >= band.W]:
+    the band product, both scaled already), exact zeros in every other column.  `band`: chunked_band(T, ...).  `out` may be S."""
+    _cc(S, "softmax_relshift_band.S"); _c(BD, "softmax_relshift_band.BD")
+    M, T = _band_dims("softmax_relshift_band", S, BD, band)
+    out = torch.empty_like(S) if out is None else _cc(out, "softmax_relshift_band.out")
+    check(_L().dyn_softmax_relshift_band_fwd(S.data_ptr(), out.data_ptr(), BD.data_ptr(), M, T, BD.shape[3], band.cs, band.lc, _stream()),
+          "dyn_softmax_relshift_band_fwd")
+    return out
+
+
+def relshift_band_bwd(dS, band, out=None, ld_bd=None):
+    """dBD [B, nh, T, ld_bd (band.W)] from dS [B, nh, T, T]: dS of every row's key range in the band's columns, zeros written everywhere
+    else (`out` may be stale scratch)."""
+    _cc(dS, "relshift_band_bwd.dS")
+    ld = band.W if ld_bd is None else int(ld_bd)
+    if out is None:
+        out = torch.empty(*dS.shape[:3], ld, device=dS.device, dtype=F32)
+    M, T = _band_dims("relshift_band_bwd", dS, _c(out, "relshift_band_bwd.out"), band)
+    check(_L().dyn_relshift_band_bwd(dS.data_ptr(), out.data_ptr(), M, T, out.shape[3], band.cs, band.lc, _stream()), "dyn_relshift_band_bwd")
+    return out
+
+
+def causal_out_len(n):
+    """Output length of a 3-wide, stride-2 convolution padded (2, 1): NemotronAsrStreamingEncoderCausalConv2D."""
+    return n // 2 + 1
+
+
+def conv2d_first_causal(x, w, bias):
+    """x [B, T, F] -> z [B, T // 2 + 1, F // 2 + 1, C], the causal stem (padding (2, 1) on both axes); w [C, 3, 3]."""
+    _c(x, "conv2d_first_causal.x"); _cc(w, "conv2d_first_causal.w"); _cc(bias, "conv2d_first_causal.bias")
+    B, T, F = x.shape
+    C = w.shape[0]
+    out = torch.empty(B, causal_out_len(T), causal_out_len(F), C, device=x.device, dtype=F32)
+    check(_L().dyn_conv2d_first_causal_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, T, F, C, _stream()),
+          "dyn_conv2d_first_causal_fwd")
+    return out
+
+
+def conv2d_first_causal_wgrad(x, dz, dw, dbias, beta=1.0):
+    _c(x, "conv2d_first_causal_wgrad.x"); _cc(dz, "conv2d_first_causal_wgrad.dz"); _cc(dw, "conv2d_first_causal_wgrad.dw")
+    _cc(dbias, "conv2d_first_causal_wgrad.dbias")
+    B, T, F = x.shape
+    C = dw.shape[0]
+    if tuple(dz.shape) != (B, causal_out_len(T), causal_out_len(F), C):
+        raise DynError("conv2d_first_causal_wgrad: dz must be [B, T // 2 + 1, F // 2 + 1, C]")
+    ws = workspace(x.device)
+    check(_L().dyn_conv2d_first_causal_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), dbias.data_ptr(), beta, B, T, F, C, ws.data_ptr(),
+                                             ws.numel(), _stream()), "dyn_conv2d_first_causal_wgrad")
+
+
+def dwconv2d_s2_causal_act(z, w, bias, act):
+    """u = bias + causal dw3x3_s2(act(z)), act "relu"; z [B, T, F, C] -> [B, T // 2 + 1, F // 2 + 1, C]; w [C, 3, 3]."""
+    a = _sub_act(act, "dwconv2d_s2_causal_act")
+    _cc(z, "dwconv2d_s2_causal_act.z"); _cc(w, "dwconv2d_s2_causal_act.w"); _cc(bias, "dwconv2d_s2_causal_act.bias")
+    B, T, F, C = z.shape
+    out = torch.empty(B, causal_out_len(T), causal_out_len(F), C, device=z.device, dtype=F32)
+    check(_L().dyn_dwconv2d_s2_causal_fwd_act(z.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, T, F, C, a, _stream()),
+          "dyn_dwconv2d_s2_causal_fwd_act")
+    return out
+
+
+def dwconv2d_s2_causal_dgrad_act(z, w, du, act):
+    a = _sub_act(act, "dwconv2d_s2_causal_dgrad_act")
+    _cc(z, "dwconv2d_s2_causal_dgrad_act.z"); _cc(du, "dwconv2d_s2_causal_dgrad_act.du"); _cc(w, "dwconv2d_s2_causal_dgrad_act.w")
+    B, T, F, C = z.shape
+    if tuple(du.shape) != (B, causal_out_len(T), causal_out_len(F), C):
+        raise DynError("dwconv2d_s2_causal_dgrad_act: du must be [B, T // 2 + 1, F // 2 + 1, C]")
+    out = torch.empty_like(z)
+    check(_L().dyn_dwconv2d_s2_causal_dgrad_act(z.data_ptr(), w.data_ptr(), du.data_ptr(), out.data_ptr(), B, T, F, C, a, _stream()),
+          "dyn_dwconv2d_s2_causal_dgrad_act")
+    return out
+
+
+def dwconv2d_s2_causal_wgrad_act(z, du, dw, dbias, act, beta=1.0):
+    a = _sub_act(act, "dwconv2d_s2_causal_wgrad_act")
+    _cc(z, "dwconv2d_s2_causal_wgrad_act.z"); _cc(du, "dwconv2d_s2_causal_wgrad_act.du"); _cc(dw, "dwconv2d_s2_causal_wgrad_act.dw")
+    _cc(dbias, "dwconv2d_s2_causal_wgrad_act.dbias")
+    B, T, F, C = z.shape
+    if tuple(du.shape) != (B, causal_out_len(T), causal_out_len(F), C):
+        raise DynError("dwconv2d_s2_causal_wgrad_act: du must be [B, T // 2 + 1, F // 2 + 1, C]")
+    ws = workspace(z.device)
+    check(_L().dyn_dwconv2d_s2_causal_wgrad_act(z.data_ptr(), du.data_ptr(), dw.data_ptr(), dbias.data_ptr(), beta, B, T, F, C, a, ws.data_ptr(),
+                                                ws.numel(), _stream()), "dyn_dwconv2d_s2_causal_wgrad_act")
+
+
+def convmod_causal_k9(u, w, cbias, gamma, beta, eps=1e-5, save=False):
+    """NemotronAsrStreaming's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = silu(LayerNorm_C(cbias + causal depthwise
+    conv(GLU(u)))), w [C, 9], cbias [C] or None, zeros left of frame 0.  Returns (s, g, c, n, mean, rstd) as convmod_causal."""
+    _cc(u, "convmod_causal_k9.u"); _cc(w, "convmod_causal_k9.w"); _cc(gamma, "convmod_causal_k9.gamma"); _cc(beta, "convmod_causal_k9.beta")
+    if u.dim() != 3 or u.shape[2] % 2 or w.dim() != 2 or w.shape[0] != u.shape[2] // 2 or gamma.numel() != w.shape[0] or beta.numel() != w.shape[0]:
+        raise DynError("convmod_causal_k9: u must be [B, T, 2C], w [C, KW], gamma and beta [C]")
+    B, T, C2 = u.shape
+    C = C2 // 2
+    if cbias is not None and _cc(cbias, "convmod_causal_k9.cbias").numel() != C:
+        raise DynError("convmod_causal_k9: cbias must be [C]")
+    s = torch.empty(B, T, C, device=u.device, dtype=F32)
+    g = c = n = mean = rstd = None
+    if save:
+        g, c, n = (torch.empty(B, T, C, device=u.device, dtype=F32) for _ in range(3))
+        mean, rstd = (torch.empty(B * T, device=u.device, dtype=F32) for _ in range(2))
+    check(_L().dyn_convmod_causal_k9_fwd(u.data_ptr(), w.data_ptr(), _opt(cbias, "cbias"), gamma.data_ptr(), beta.data_ptr(), s.data_ptr(),
+                                         _opt(g, "g"), _opt(c, "c"), _opt(n, "n"), _opt(mean, "mean"), _opt(rstd, "rstd"), B, T, C, w.shape[1],
+                                         eps, _stream()), "dyn_convmod_causal_k9_fwd")
+    return s, g, c, n, mean, rstd
+
+
+def dwconv1d_causal_k9_dgrad(dy, w, out=None, beta=0.0):
+    """dwconv1d_causal_dgrad at 9 taps."""
+    _cc(dy, "dwconv1d_causal_k9_dgrad.dy"); _cc(w, "dwconv1d_causal_k9_dgrad.w")
+    B, T, C = dy.shape
+    if w.shape[0] != C:
+        raise DynError("dwconv1d_causal_k9_dgrad: w must be [C, KW]")
+    out = torch.empty_like(dy) if out is None else _cc(out, "dwconv1d_causal_k9_dgrad.out")
+    if out.shape != dy.shape or out.data_ptr() == dy.data_ptr():
+        raise DynError("dwconv1d_causal_k9_dgrad: out must have the shape of dy and not alias it")
+    check(_L().dyn_dwconv1d_causal_k9_dgrad(dy.data_ptr(), w.data_ptr(), out.data_ptr(), B, T, C, w.shape[1], beta, _stream()),
+          "dyn_dwconv1d_causal_k9_dgrad")
+    return out
+
+
+def dwconv1d_causal_k9_wgrad(x, dy, dw, beta=1.0):
+    """dwconv1d_causal_wgrad at 9 taps."""
+    _cc(x, "dwconv1d_causal_k9_wgrad.x"); _cc(dy, "dwconv1d_causal_k9_wgrad.dy"); _cc(dw, "dwconv1d_causal_k9_wgrad.dw")
+    B, T, C = x.shape
+    if dy.shape != x.shape or dw.dim() != 2 or dw.shape[0] != C:
+        raise DynError("dwconv1d_causal_k9_wgrad: dy must have the shape of x, dw must be [C, KW]")
+    ws = workspace(x.device)
+    check(_L().dyn_dwconv1d_causal_k9_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), beta, B, T, C, dw.shape[1], ws.data_ptr(), ws.numel(),
+                                            _stream()), "dyn_dwconv1d_causal_k9_wgrad")
+    return dw

@@ -84,9 +84,10 @@ def _flatten(cfg, keys=ENCODER_KEYS):
     return out
 
 
-def make_config(cfg=None):
-    """transformers' ParakeetCTCConfig / ParakeetEncoderConfig keys with their defaults; what this forward does not build is refused by name."""
-    out = W2.make_config(_flatten(cfg), DEFAULT_CONFIG)
+def make_config(cfg=None, defaults=DEFAULT_CONFIG, keys=ENCODER_KEYS, mel_multiple=8):
+    """transformers' ParakeetCTCConfig / ParakeetEncoderConfig keys with their defaults; what this forward does not build is refused by name.
+    `defaults`, `keys`, `mel_multiple`: a model of the family with more encoder keys and another subsampling (nemotron_asr_streaming_model.py)."""
+    out = W2.make_config(_flatten(cfg, keys), defaults)
     out["do_stable_layer_norm"] = False
     out["position_embeddings_type"] = "relative"             # the parent's switch: Transformer-XL scores
     out["conv_kernel"], out["conv_stride"], out["conv_dim"] = (), (), ()     # no waveform conv stack (_conv_extractor = False)
@@ -99,9 +100,9 @@ def make_config(cfg=None):
     C, F = out["subsampling_conv_channels"], out["num_mel_bins"]
     if not (isinstance(C, int) and C > 0 and C % 4 == 0):
         raise ops.DynError(f"subsampling_conv_channels={C!r} is not built: the channels-last conv kernels take a positive multiple of 4")
-    if not (isinstance(F, int) and F > 0 and F % 8 == 0):
-        raise ops.DynError(f"num_mel_bins={F!r} is not built: a positive multiple of 8 (transformers' num_mel_bins // 8 columns per channel "
-                           "are the conv stages' only then)")
+    if not (isinstance(F, int) and F > 0 and F % mel_multiple == 0):
+        raise ops.DynError(f"num_mel_bins={F!r} is not built: a positive multiple of {mel_multiple} (transformers' num_mel_bins // 8 columns "
+                           "per channel are the conv stages' only then)")
     H, nh = out["hidden_size"], out["num_attention_heads"]
     if H not in WIDTHS:
         raise ops.DynError(f"hidden_size={H} is not built: one of {WIDTHS}")
@@ -217,6 +218,7 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
     _head_bias_names = (("self_attn.pos_bias_u", "self_attn.bias_u"), ("self_attn.pos_bias_v", "self_attn.bias_v"))
     downsampling_factor = 8                                    # nvidia_ctc/lib.py:110: the overlap must be a multiple of it
     frozen_in_the_loop = FROZEN_IN_THE_LOOP
+    frames = staticmethod(frames)                              # encoder frames of T feature frames; a model with another subsampling replaces it
 
     def __init__(self, config=None, device="cuda:0"):
         super().__init__(config, device)
@@ -355,7 +357,7 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
                 and x.shape[1] >= 1):
             raise ops.DynError(f"input_features must be a float32 CUDA tensor [B, T, {self.n_mels}]")
         B, T, _ = x.shape
-        T3 = frames(T)
+        T3 = self.frames(T)
         self.position_table(T3)
         with ops.use_workspace(self._scratch()):
             self._vl, self._ctx_static = None, False

@@ -65,9 +65,10 @@ def _getter(cfg):
     return (lambda k: cfg.get(k)) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k, None))
 
 
-def head_config(cfg, defaults):
+def head_config(cfg, defaults, encoder=PM.make_config):
     """make_config behind the model_type check, for both transducer heads: `defaults` holds the head's keys (with `durations`: TDT;
-    without: RNN-T, `durations` of the result is then empty and the joint head is [V + 1, Hd])."""
+    without: RNN-T, `durations` of the result is then empty and the joint head is [V + 1, Hd]).  `encoder`: the configuration reader of
+    the encoder (a model of the family with another encoder, nemotron_asr_streaming_model.py)."""
     get = _getter(cfg)
     head = dict(defaults)
     if cfg is not None:
@@ -75,8 +76,8 @@ def head_config(cfg, defaults):
             v = get(k)
             if v is not None:
                 head[k] = v
-    out = PM.make_config({"encoder_config": None if cfg is None else get("encoder_config"), "vocab_size": head["vocab_size"],
-                          "pad_token_id": head["pad_token_id"]})
+    out = encoder({"encoder_config": None if cfg is None else get("encoder_config"), "vocab_size": head["vocab_size"],
+                   "pad_token_id": head["pad_token_id"]})
     if head["hidden_act"] not in ops.JOINT_ACTS:
         raise ops.DynError(f"hidden_act={head['hidden_act']!r} of the joint is not built ({sorted(ops.JOINT_ACTS)})")
     out["joint_hidden_act"] = head["hidden_act"]

@@ -190,6 +190,10 @@ def load_pretrained_model(args, device):
         raise ops.DynError(f'{cfg_path}: model_type "parakeet_rnnt" is a transducer over log-mel features [B, T, num_mel_bins], not a CTC model '
                            'over waveforms: build parakeet_rnnt_model.ParakeetForRNNT and drive it with '
                            'parakeet_tdt_lib.dynamic_eval_transducer_loss')
+    if kind == 'nemotron_asr_streaming':
+        raise ops.DynError(f'{cfg_path}: model_type "nemotron_asr_streaming" is a transducer over log-mel features [B, T, num_mel_bins], not a '
+                           'CTC model over waveforms: build nemotron_asr_streaming_model.NemotronAsrStreamingForRNNT and drive it with '
+                           'parakeet_tdt_lib.dynamic_eval_transducer_loss')
     lang, adapter_sd, tokenizer = getattr(args, 'target_lang', '') or '', None, None
     if lang:
         if kind not in ('', 'wav2vec2') or not (args.checkpoint and os.path.isdir(args.checkpoint)):

@@ -1099,6 +1099,63 @@ int dyn_rnnt_greedy_steps(const float* enc, const int32_t* valid, const float* e
                           float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd, int64_t layers,
                           int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max, int64_t max_steps, int32_t n_steps, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * NemotronAsrStreamingForRNNT (`model_type: "nemotron_asr_streaming"`, transformers modeling_nemotron_asr_streaming.py): the encoder's
+ * three differences from Parakeet's.  fp32, deterministic, no float atomics.
+ *
+ * Chunked limited-context attention (chunked_limited_mask_function, :870-883, applied by NemotronAsrStreamingEncoder.forward :981-988 and
+ * NemotronAsrStreamingEncoderAttention.forward :619-628: `_rel_shift`, `masked_fill_(attention_mask.logical_not(), -inf)`, the softmax
+ * of eager_attention_forward).  cs = lookahead + 1 frames per chunk, lc left chunks (lc < 0: unlimited); query i sees key j iff
+ * 0 <= i / cs - j / cs <= lc, the contiguous range [j0, j1) = [max(0, i / cs - lc) * cs, min(T, (i / cs + 1) * cs)).  With
+ * dlo = min(lc * cs + cs - 1, T - 1) and dhi = min(cs - 1, T - 1), j - i lies in [-dlo, dhi]: W = dlo + dhi + 1 relative positions.
+ * bd is the BAND product (q + v) P_h[T - 1 - dlo .. T - 1 + dhi]^T [M, T, ld_bd >= W], already scaled; relative position -dlo is column 0.
+ *   dyn_softmax_relshift_band_fwd  y[m,i,j] = softmax over [j0, j1) of x[m,i,j] + bd[m, i, j - i + dlo]; 0 WRITTEN in every other column
+ *                                  of the row.  y may be x (not bd).  One pass, nothing copied for the shift.  T <= 16384.
+ *   dyn_relshift_band_bwd          dBD[m,i,k] = dS[m, i, k - dlo + i] where that key lies in [j0, j1), 0 WRITTEN in every other column of
+ *                                  the ld_bd-float row: the buffer may be uninitialised scratch.
+ * cs >= T is one chunk and lc >= T every chunk (both are clamped).  Null pointer, T < 1, cs < 1, ld_bd < W, T beyond the row limit
+ * -> DYN_E_ARG before any launch.
+ *
+ * Causal x8 subsampling (NemotronAsrStreamingEncoderCausalConv2D.forward :305-316: padding (kernel - 1, stride - 1) = (2, 1) on both
+ * axes; NemotronAsrStreamingEncoderSubsamplingConv2D.forward :718-729).  To = T / 2 + 1, Fo = F / 2 + 1, output (to, fo) reads the inputs
+ * (2 to + dt - 2, 2 fo + df - 2).  Channels-last, w [C, 3, 3], C % 4 == 0, any T >= 1 and F >= 1.
+ *   dyn_conv2d_first_causal_fwd / _wgrad   `conv_in`: x [B, T, F] -> z [B, To, Fo, C] (pre-activation); dw [C, 9] and dbias [C] as
+ *                                          beta * old + the sums, per-tile partials in `workspace` combined in tile order (deferrable).
+ *   dyn_dwconv2d_s2_causal_fwd_act / _dgrad_act / _wgrad_act   `layers.{i}.depthwise_conv` with `act_fn` of its input fused into the
+ *                                          loads, the contracts of dyn_dwconv2d_s2_*_act: u = bias + dw3x3(act(z)), dz = act'(z) * ...;
+ *                                          act 1 = ReLU (0, SiLU, has no caller and is DYN_E_UNSUPPORTED).
+ *
+ * Conv-module core (NemotronAsrStreamingEncoderConvolutionModule.forward :454-469: `glu`, the left-padded `depthwise_conv` with its
+ * optional bias, `self.norm` = LayerNorm(C), `self.activation` = SiLU) at KW = 9, C in {256, 512, 768, 1024}.
+ *   dyn_convmod_causal_k9_fwd      u [B, T, 2C] -> s [B, T, C] in one launch; cbias may be null; optional outputs g, c, n [B, T, C] and
+ *                                  mean / rstd [B * T] as dyn_convmod_causal_fwd.
+ *   dyn_dwconv1d_causal_k9_dgrad / _wgrad   the contracts of dyn_dwconv1d_causal_dgrad / _wgrad at 9 taps (the bias gradient is dyn_colsum
+ *                                  of dy).
+ * A C / KW / act that is not built -> DYN_E_UNSUPPORTED, a short workspace -> DYN_E_WORKSPACE, all before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int dyn_softmax_relshift_band_fwd(const float* x, float* y, const float* bd, int64_t M, int64_t T, int64_t ld_bd, int64_t cs, int64_t lc,
+                                  void* stream);
+int dyn_relshift_band_bwd(const float* dS, float* dBD, int64_t M, int64_t T, int64_t ld_bd, int64_t cs, int64_t lc, void* stream);
+int dyn_conv2d_first_causal_fwd(const float* x, const float* w, const float* bias, float* z, int64_t B, int64_t T, int64_t F, int64_t C,
+                                void* stream);
+int64_t dyn_conv2d_causal_wgrad_workspace_bytes(int64_t B, int64_t T, int64_t C);
+int dyn_conv2d_first_causal_wgrad(const float* x, const float* dz, float* dw, float* dbias, float beta, int64_t B, int64_t T, int64_t F,
+                                  int64_t C, void* workspace, int64_t workspace_bytes, void* stream);
+int dyn_dwconv2d_s2_causal_fwd_act(const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T, int64_t F, int64_t C,
+                                   int32_t act, void* stream);
+int dyn_dwconv2d_s2_causal_dgrad_act(const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T, int64_t F, int64_t C,
+                                     int32_t act, void* stream);
+int dyn_dwconv2d_s2_causal_wgrad_act(const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B, int64_t T, int64_t F,
+                                     int64_t C, int32_t act, void* workspace, int64_t workspace_bytes, void* stream);
+int dyn_convmod_causal_k9_fwd(const float* u, const float* w, const float* cbias, const float* gamma, const float* beta, float* s, float* g,
+                              float* c, float* n, float* mean, float* rstd, int64_t B, int64_t T, int64_t C, int64_t KW, float eps,
+                              void* stream);
+int dyn_dwconv1d_causal_k9_dgrad(const float* dy, const float* w, float* dx, int64_t B, int64_t T, int64_t C, int64_t KW, float dx_beta,
+                                 void* stream);
+int64_t dyn_dwconv1d_causal_k9_wgrad_workspace_bytes(int64_t B, int64_t T, int64_t C, int64_t KW);
+int dyn_dwconv1d_causal_k9_wgrad(const float* x, const float* dy, float* dw, float beta, int64_t B, int64_t T, int64_t C, int64_t KW,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
