@@ -78,6 +78,11 @@ __device__ __forceinline__ int64_t valid_rows(const int32_t* valid, int64_t T) {
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+__device__ __forceinline__ float silu_f(float x) { return x * sigmoidf_(x); }
+__device__ __forceinline__ float silu_grad(float x) {
+    const float s = sigmoidf_(x);
+    return s * (1.f + x * (1.f - s));
+}
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

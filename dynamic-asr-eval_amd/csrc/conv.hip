@@ -1,6 +1,6 @@
 // Convolutions of the conformer encoder, channels-last so every access is coalesced along C:
 //   * depthwise Conv1d (odd kernel KW <= 31, 'same' zero padding) of the conformer conv module, fwd / dgrad / wgrad; the wgrad also at
-//     KW = 32 (15 | 16 padding, csrc/convmod_bn.hip's 32-tap core);
+//     KW = 32 (15 | 16 padding, csrc/convmod_bn.hip's 32-tap core).  The kernels are the sliding window of dwconv_window.h;
 //   * the dw_striding x8 subsampling front-end: first 3x3 stride-2 conv (1 -> C channels, direct) and the
 //     3x3 stride-2 depthwise convs with the preceding SiLU fused into the load (pointwise 1x1 convs are GEMMs).
 // These are HBM-bound (a few FLOPs per byte): each thread owns one channel and slides over time so every
@@ -8,15 +8,13 @@
 // Reference call sites: upstream SCConformerXL conv module / subsampling reached through
 // model(audio_signal=...) (reference lcasr/lib.py:164,550; earnings_finetune/lcasr160rb1.yaml:10-15).
 #include "common.h"
+#include "dwconv_window.h"
 #include "reduce.h"
 
 namespace {
 
-__device__ __forceinline__ float silu_f(float x) { return x * dyn::sigmoidf_(x); }
-__device__ __forceinline__ float silu_grad(float x) {
-    const float s = dyn::sigmoidf_(x);
-    return s * (1.f + x * (1.f - s));
-}
+using dyn::silu_f;
+using dyn::silu_grad;
 
 // The activation in front of a 3x3 stride-2 depthwise stage, fused into its loads: SiLU (the project's conformer) or ReLU (Parakeet's
 // dw_striding subsampling).  A compile-time parameter: the SiLU instances are the code as it was.
@@ -24,86 +22,9 @@ constexpr int ACT_SILU = 0, ACT_RELU = 1;
 template <int ACT> __device__ __forceinline__ float act_in(float x) { return ACT == ACT_RELU ? fmaxf(x, 0.f) : silu_f(x); }
 template <int ACT> __device__ __forceinline__ float act_in_grad(float x) { return ACT == ACT_RELU ? (x > 0.f ? 1.f : 0.f) : silu_grad(x); }
 
-constexpr int TT = 32;  // time steps per workgroup tile
-
-// y[b,t,c] = bias[c] + sum_j w[c,j] * x[b, t + j - P, c],  P = (KW-1)/2.   FLIP => dgrad (w index reversed).
-template <int KW, bool FLIP>
-__global__ __launch_bounds__(256) void dwconv1d_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                        const float* __restrict__ bias, float* __restrict__ y, int64_t T,
-                                                        int C, float beta, int ngroups, int64_t pstride) {
-    constexpr int P = (KW - 1) / 2;
-    const int c = blockIdx.y * 256 + threadIdx.x;
-    if (c >= C) return;
-    const int64_t b = blockIdx.z;
-    {   // lockstep group: sample b convolves with the filters of replica b % ngroups (ngroups = 1: plain launch)
-        const int64_t poff = (int64_t)(blockIdx.z % ngroups) * pstride;
-        w += poff;
-        if (bias) bias += poff;
-    }
-    const int64_t t0 = (int64_t)blockIdx.x * TT;
-    float wk[KW];
-#pragma unroll
-    for (int j = 0; j < KW; ++j) wk[j] = w[(int64_t)c * KW + (FLIP ? KW - 1 - j : j)];
-    const float bv = bias ? bias[c] : 0.f;
-    const float* xb = x + b * T * C + c;
-    float* yb = y + b * T * C + c;
-    float win[KW];
-#pragma unroll
-    for (int j = 0; j < KW - 1; ++j) {
-        const int64_t t = t0 + j - P;
-        win[j + 1] = (t >= 0 && t < T) ? xb[t * C] : 0.f;
-    }
-    for (int k = 0; k < TT; ++k) {
-        const int64_t t = t0 + k;
-        if (t >= T) break;
-#pragma unroll
-        for (int j = 0; j < KW - 1; ++j) win[j] = win[j + 1];
-        const int64_t tn = t + P;
-        win[KW - 1] = tn < T ? xb[tn * C] : 0.f;
-        float acc = bv;
-#pragma unroll
-        for (int j = 0; j < KW; ++j) acc += wk[j] * win[j];
-        yb[t * C] = beta != 0.f ? acc + beta * yb[t * C] : acc;
-    }
-}
-
-// partial[(tile), j, c] = sum_{t in tile} dy[b,t,c] * x[b, t + j - P, c], j = 0 .. KW - 1;   partial_b[(tile), c] = sum dy
-template <int KW>
-__global__ __launch_bounds__(256) void dwconv1d_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                              float* __restrict__ partial_w, float* __restrict__ partial_b,
-                                                              int64_t T, int C, int64_t t_per_block) {
-    constexpr int P = (KW - 1) / 2, PR = KW - 1 - P;      // frames left / right of t; an even KW (32) pads as torch's "same": 15 | 16
-    const int c = blockIdx.y * 256 + threadIdx.x;
-    if (c >= C) return;
-    const int64_t b = blockIdx.z;
-    const int64_t t0 = (int64_t)blockIdx.x * t_per_block;
-    const int64_t t1 = (t0 + t_per_block < T) ? t0 + t_per_block : T;
-    const float* xb = x + b * T * C + c;
-    const float* gb = dy + b * T * C + c;
-    float acc[KW], win[KW];
-    float accb = 0.f;
-#pragma unroll
-    for (int j = 0; j < KW; ++j) acc[j] = 0.f;
-#pragma unroll
-    for (int j = 0; j < KW - 1; ++j) {
-        const int64_t t = t0 + j - P;
-        win[j + 1] = (t >= 0 && t < T) ? xb[t * C] : 0.f;
-    }
-    for (int64_t t = t0; t < t1; ++t) {
-#pragma unroll
-        for (int j = 0; j < KW - 1; ++j) win[j] = win[j + 1];
-        const int64_t tn = t + PR;
-        win[KW - 1] = tn < T ? xb[tn * C] : 0.f;
-        const float g = gb[t * C];
-        accb += g;
-#pragma unroll
-        for (int j = 0; j < KW; ++j) acc[j] += g * win[j];
-    }
-    const int64_t tile = (int64_t)blockIdx.z * gridDim.x + blockIdx.x;
-#pragma unroll
-    for (int j = 0; j < KW; ++j) partial_w[(tile * C + c) * KW + j] = acc[j];
-    partial_b[tile * C + c] = accb;
-}
+// The depthwise Conv1d kernels are dwconv_window.h's sliding window with 'same' padding: P = (KW - 1) / 2 frames left of t and
+// PR = KW - 1 - P right of it (an even KW, 32, pads as torch's "same": 15 | 16).
+constexpr int same_left(int KW) { return (KW - 1) / 2; }
 
 // ---- subsampling: first conv, 1 input channel, 3x3, stride 2, pad 1:  x [B, T, F] -> z [B, To, Fo, C] ----
 __global__ __launch_bounds__(256) void conv2d_first_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -742,8 +663,8 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_wgrad_kernel(const float* __r
 template <bool FLIP>
 int launch_dw1d(const float* x, const float* w, const float* bias, float* y, int64_t B, int64_t T, int64_t C, int64_t KW,
                 float beta, hipStream_t st, int ngroups = 1, int64_t pstride = 0) {
-    dim3 grid((unsigned)dyn::cdiv(T, TT), (unsigned)dyn::cdiv(C, 256), (unsigned)B), blk(256);
-#define GO(K) hipLaunchKernelGGL((dwconv1d_kernel<K, FLIP>), grid, blk, 0, st, x, w, bias, y, T, (int)C, beta, ngroups, pstride)
+    dim3 grid((unsigned)dyn::cdiv(T, dyn::DW_TT), (unsigned)dyn::cdiv(C, 256), (unsigned)B), blk(256);
+#define GO(K) hipLaunchKernelGGL((dwconv1d_kernel<K, same_left(K), FLIP>), grid, blk, 0, st, x, w, bias, y, T, (int)C, beta, ngroups, pstride)
     switch (KW) {
         case 3: GO(3); break; case 5: GO(5); break; case 7: GO(7); break; case 9: GO(9); break;
         case 15: GO(15); break; case 31: GO(31); break;
@@ -751,17 +672,6 @@ int launch_dw1d(const float* x, const float* w, const float* bias, float* y, int
     }
 #undef GO
     return dyn::check_launch("dyn_dwconv1d");
-}
-
-// Rows (time steps) per wgrad workgroup: short serial chains and thousands of workgroups; the partial sums are
-// combined afterwards by the fixed-order 2-D reducer (reduce.h).
-inline int64_t wgrad_tiles(int64_t B, int64_t T, int64_t* per_block) {
-    int64_t chunks = dyn::cdiv(T, 8);
-    if (chunks > 2048) chunks = 2048;
-    if (chunks < 1) chunks = 1;
-    *per_block = dyn::cdiv(T > 0 ? T : 1, chunks);
-    chunks = dyn::cdiv(T > 0 ? T : 1, *per_block);
-    return chunks;
 }
 
 // 2-D subsampling weight gradients: one wave per tile, enough tiles (up to 4096 per sample) to fill the chip at B = 1.
@@ -798,7 +708,7 @@ extern "C" int dyn_dwconv1d_dgrad_g(const float* dy, const float* w, float* dx, 
 
 extern "C" int64_t dyn_dwconv1d_wgrad_workspace_bytes(int64_t B, int64_t T, int64_t C, int64_t KW) {
     int64_t per;
-    const int64_t tiles = wgrad_tiles(B, T, &per) * B;
+    const int64_t tiles = dyn::wgrad_tiles(T, &per) * B;
     return tiles * C * (KW + 1) * (int64_t)sizeof(float);
 }
 
@@ -821,14 +731,14 @@ static int dwconv1d_wgrad_impl(const float* x, const float* dy, float* dw, float
     DYN_REQUIRE(x && dy && dw && B >= 0 && T >= 0 && C > 0, DYN_E_ARG, "dyn_dwconv1d_wgrad: bad arguments");
     if (B == 0 || T == 0) return DYN_OK;
     int64_t per;
-    const int64_t chunks = wgrad_tiles(B, T, &per), tiles = chunks * B;
+    const int64_t chunks = dyn::wgrad_tiles(T, &per), tiles = chunks * B;
     DYN_REQUIRE(workspace && workspace_bytes >= tiles * C * (KW + 1) * (int64_t)sizeof(float), DYN_E_WORKSPACE,
                 "dyn_dwconv1d_wgrad: workspace too small");
     float* pw = dyn::partials_alloc(workspace, tiles * C * (KW + 1) * (int64_t)sizeof(float));   // the workspace, or the open deferral context's arena
     float* pb = pw + tiles * C * KW;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)chunks, (unsigned)dyn::cdiv(C, 256), (unsigned)B), blk(256);
-#define GO(K) hipLaunchKernelGGL((dwconv1d_wgrad_kernel<K>), grid, blk, 0, st, x, dy, pw, pb, T, (int)C, per)
+#define GO(K) hipLaunchKernelGGL((dwconv1d_wgrad_kernel<K, same_left(K), true>), grid, blk, 0, st, x, dy, pw, pb, T, (int)C, per)
     switch (KW) {
         case 3: GO(3); break; case 5: GO(5); break; case 7: GO(7); break; case 9: GO(9); break;
         case 15: GO(15); break; case 31: GO(31); break;

@@ -19,6 +19,7 @@
 // `valid` (device int32 scalar, may be null): GLU rows t >= *valid read as zeros (what SAME padding holds there in the unpadded run) and
 // rows >= *valid of every output are exact zeros / left out of the sums.  No float atomics: every result is bit-reproducible.
 #include "common.h"
+#include "dwconv_window.h"
 #include "reduce.h"
 
 namespace {
@@ -28,11 +29,8 @@ constexpr int TT9 = 16;       // frames per workgroup of the 9-tap forward and d
 constexpr int TT32 = 32;      // ... of the 32-tap ones
 constexpr int ACT_SILU = 0;
 
-__device__ __forceinline__ float silu_f(float x) { return x * dyn::sigmoidf_(x); }
-__device__ __forceinline__ float silu_grad(float x) {
-    const float s = dyn::sigmoidf_(x);
-    return s * (1.f + x * (1.f - s));
-}
+using dyn::silu_f;
+using dyn::silu_grad;
 
 // grid (ceil(T / TT), C / 256, B); 256 threads, thread = channel.
 template <int KW, int TT>
@@ -47,15 +45,8 @@ __global__ __launch_bounds__(256) void convmod_bn_fwd_kernel(const float* __rest
     const int64_t b = blockIdx.z, t0 = (int64_t)blockIdx.x * TT;
     const int64_t vr = dyn::valid_rows(valid, T);
     float wk[KW], g[NG];
-#pragma unroll
-    for (int j = 0; j < KW; ++j) wk[j] = w[(int64_t)c * KW + j];
-    const float cb = cbias ? cbias[c] : 0.f, mu = mean[c], rs = rsqrtf(var[c] + eps), gw = weight[c], sh = bias[c];
-    const float* ub = u + b * T * 2 * C + c;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        const int64_t t = t0 - HL + i;
-        g[i] = (t >= 0 && t < vr) ? ub[t * 2 * C] * dyn::sigmoidf_(ub[t * 2 * C + C]) : 0.f;
-    }
+    const float cb = dyn::load_glu_window(w, cbias, u + b * T * 2 * C + c, c, C, t0 - HL, vr, wk, g);
+    const float mu = mean[c], rs = rsqrtf(var[c] + eps), gw = weight[c], sh = bias[c];
 #pragma unroll
     for (int k = 0; k < TT; ++k) {
         const int64_t t = t0 + k;
@@ -145,10 +136,8 @@ __global__ __launch_bounds__(256) void glu_dwconv1d_dgrad_kernel(const float* __
 inline int bwd_blocks(int64_t rows) { return (int)(rows < 1 ? 1 : rows > 512 ? 512 : rows); }
 
 int check_dims(const char* who, int64_t B, int64_t T, int64_t C, int64_t KW) {
-    DYN_REQUIRE(B >= 0 && T >= 0 && B < 65536 && B * T < (1ll << 31), DYN_E_ARG, "%s: bad sizes B=%lld T=%lld", who, (long long)B, (long long)T);
+    if (int rc = dyn::check_convmod_dims(who, B, T, C)) return rc;
     DYN_REQUIRE(KW == KW9 || KW == KW32, DYN_E_UNSUPPORTED, "%s: kernel width %lld is not built (9, 32)", who, (long long)KW);
-    DYN_REQUIRE(C == 256 || C == 512 || C == 768 || C == 1024, DYN_E_UNSUPPORTED, "%s: C=%lld is not built (256, 512, 768, 1024)", who,
-                (long long)C);
     return DYN_OK;
 }
 

@@ -23,6 +23,7 @@
 // No float atomics, no E[x^2] - E[x]^2: every result is bit-reproducible.  A channel whose batch variance is exactly zero is outside the
 // contract (xt = (x - mu) / std is 0 / 0 there).
 #include "common.h"
+#include "dwconv_window.h"
 
 namespace {
 
@@ -33,11 +34,8 @@ constexpr int FIN_BATCH = 16;           // partials a finalise thread has in fli
 constexpr int STATS_ROWS = 7;          // mu, 1 / sig, r, d, scale = weight * r / sig, shift = weight * d + bias, 1 / std
 enum { S_MU = 0, S_ISIG, S_R, S_D, S_SCALE, S_SHIFT, S_ISTD };
 
-__device__ __forceinline__ float silu_f(float x) { return x * dyn::sigmoidf_(x); }
-__device__ __forceinline__ float silu_grad(float x) {
-    const float s = dyn::sigmoidf_(x);
-    return s * (1.f + x * (1.f - s));
-}
+using dyn::silu_f;
+using dyn::silu_grad;
 
 // grid (ceil(T / TT), C / 256, B); 256 threads, thread = channel.  part [B * tiles][3][C]: count, mean, M2 of the tile.
 template <int KW, int TT>
@@ -50,15 +48,7 @@ __global__ __launch_bounds__(256) void convmod_brn_conv_kernel(const float* __re
     const int64_t b = blockIdx.z, t0 = (int64_t)blockIdx.x * TT;
     const int64_t vr = dyn::valid_rows(valid, T);
     float wk[KW], g[NG];
-#pragma unroll
-    for (int j = 0; j < KW; ++j) wk[j] = w[(int64_t)c * KW + j];
-    const float cb = cbias ? cbias[c] : 0.f;
-    const float* ub = u + b * T * 2 * C + c;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        const int64_t t = t0 - HL + i;
-        g[i] = (t >= 0 && t < vr) ? ub[t * 2 * C] * dyn::sigmoidf_(ub[t * 2 * C + C]) : 0.f;
-    }
+    const float cb = dyn::load_glu_window(w, cbias, u + b * T * 2 * C + c, c, C, t0 - HL, vr, wk, g);
     float cnt = 0.f, mean = 0.f, m2 = 0.f;
 #pragma unroll
     for (int k = 0; k < TT; ++k) {
@@ -229,11 +219,9 @@ inline unsigned flat_blocks(int64_t n4) { return (unsigned)(n4 < 256 ? 1 : dyn::
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int check_dims(const char* who, int64_t B, int64_t T, int64_t C, int64_t KW) {
-    DYN_REQUIRE(B >= 0 && T >= 0 && B < 65536 && B * T < (1ll << 31), DYN_E_ARG, "%s: bad sizes B=%lld T=%lld", who, (long long)B, (long long)T);
+    if (int rc = dyn::check_convmod_dims(who, B, T, C)) return rc;
     DYN_REQUIRE(B * T >= 2, DYN_E_ARG, "%s: B * T = %lld rows: a batch statistic needs at least 2", who, (long long)(B * T));
     DYN_REQUIRE(KW == KW9 || KW == KW32, DYN_E_UNSUPPORTED, "%s: kernel width %lld is not built (9, 32)", who, (long long)KW);
-    DYN_REQUIRE(C == 256 || C == 512 || C == 768 || C == 1024, DYN_E_UNSUPPORTED, "%s: C=%lld is not built (256, 512, 768, 1024)", who,
-                (long long)C);
     return DYN_OK;
 }
 

@@ -17,11 +17,8 @@ inline unsigned grid_for(int64_t n_vec) {
     return (unsigned)g;
 }
 
-__device__ __forceinline__ float silu_f(float x) { return x * dyn::sigmoidf_(x); }
-__device__ __forceinline__ float silu_grad(float x) {
-    const float s = dyn::sigmoidf_(x);
-    return s * (1.f + x * (1.f - s));
-}
+using dyn::silu_f;
+using dyn::silu_grad;
 
 __global__ void silu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n) {
     const int64_t n4 = n >> 2;

@@ -17,7 +17,7 @@ loss follows ParakeetForRNNT.  The encoder differs in three places:
     the backward writes dS into the band's layout (ops.relshift_band_bwd): d(q + v) is a K = W product and the position table's gradient
     only has its W band rows.  The score and context GEMMs stay dense over [T', T'].
   * conv module: the depthwise conv is causal (left padding 8) with an optional bias and `conv.norm` is a LayerNorm(H), no batch-norm
-    buffers: GLU, conv, bias, LayerNorm and SiLU are one launch (csrc/convmod_causal_k9.hip: ops.convmod_causal_k9); backward by the
+    buffers: GLU, conv, bias, LayerNorm and SiLU are one launch (csrc/convmod_causal.hip: ops.convmod_causal_k9); backward by the
     existing SiLU' and LayerNorm kernels, the causal depthwise dgrad / wgrad at 9 taps and ops.colsum for the bias.
   * x8 subsampling (`encoder.subsampling.`: conv_in, layers.{0,1}.depthwise_conv / pointwise_conv, linear): every 3x3 stride-2 conv pads
     (2, 1) on both axes, one stage maps n -> n // 2 + 1, so the widths are odd (80 -> 41 -> 21 -> 11) and `num_mel_bins` need not be a
@@ -294,35 +294,15 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
         return dx
 
     # ------------------------------------------------------------------ conv module
+    def _causal_conv_spec(self, l):
+        p = f"encoder.layers.{l}."
+        names = tuple(p + n for n in ("norm_conv", "conv.pointwise_conv1", "conv.depthwise_conv", "conv.norm", "conv.pointwise_conv2"))
+        core = lambda u, w, cb, gamma, beta, save: ops.convmod_causal_k9(u, w, cb, gamma, beta, self._layer_eps, save=save)
+        return names, core, ops.silu_bwd, ops.dwconv1d_causal_k9_wgrad, ops.dwconv1d_causal_k9_dgrad
+
     def _conv_fwd(self, x, l, vT, save):
         """x + conv_module(x)."""
-        P = self.P
-        p = f"encoder.layers.{l}."
-        n, m, s = ops.layernorm(x, P[p + "norm_conv.weight"], P[p + "norm_conv.bias"], self._layer_eps)
-        u = ops.linear(n, P[p + "conv.pointwise_conv1.weight"], P.get(p + "conv.pointwise_conv1.bias"))
-        a, g, cv, nn, mean, rstd = ops.convmod_causal_k9(u, P[p + "conv.depthwise_conv.weight"], P.get(p + "conv.depthwise_conv.bias"),
-                                                         P[p + "conv.norm.weight"], P[p + "conv.norm.bias"], self._layer_eps, save=save)
-        r = x.clone() if save else x
-        ops.linear(a, P[p + "conv.pointwise_conv2.weight"], P.get(p + "conv.pointwise_conv2.bias"), out=r, beta=1.0)
-        return r, (x, m, s, n, u, g, cv, nn, mean, rstd, a)
+        return self._causal_conv_fwd(x, l, save)
 
     def _conv_bwd(self, dr, kept, l, vT):
-        P, G = self.P, self.G
-        p = f"encoder.layers.{l}."
-        x, m, s, n, u, g, cv, nn, mean, rstd, a = kept
-        cbn = p + "conv.depthwise_conv.bias"
-        has_cb = cbn in P
-        b1, b2 = (p + f"conv.pointwise_conv{i}.bias" if has_cb else None for i in (1, 2))
-        da = self._lin_bwd(dr, a, p + "conv.pointwise_conv2.weight", b2)
-        dnn = ops.silu_bwd(nn, da, out=da)
-        dcv = torch.empty_like(dnn)
-        ops.layernorm_bwd(cv, P[p + "conv.norm.weight"], mean, rstd, dnn, dcv, G[p + "conv.norm.weight"], G[p + "conv.norm.bias"], dx_beta=0.0)
-        ops.dwconv1d_causal_k9_wgrad(g, dcv, G[p + "conv.depthwise_conv.weight"], beta=1.0)
-        if has_cb:
-            ops.colsum(dcv.view(-1, dcv.shape[-1]), G[cbn], beta=1.0)
-        dg = ops.dwconv1d_causal_k9_dgrad(dcv, P[p + "conv.depthwise_conv.weight"])
-        du = ops.glu_bwd(u, dg)
-        dn = self._lin_bwd(du, n, p + "conv.pointwise_conv1.weight", b1)
-        dx = torch.empty_like(dr)
-        ops.layernorm_bwd(x, P[p + "norm_conv.weight"], m, s, dn, dx, G[p + "norm_conv.weight"], G[p + "norm_conv.bias"], dx_beta=1.0, dx_in=dr)
-        return dx
+        return self._causal_conv_bwd(dr, kept, l)

@@ -1744,52 +1744,66 @@ def attn_adapter_bwd(x, gamma, beta, w1, w2, mean, rstd, a, dy, dgamma, dbeta, d
 CAUSAL_ACTS = {"swish": 0, "silu": 0, "gelu": 1}
 
 
-def convmod_causal(u, w, gamma, beta, act="swish", eps=1e-5, save=False, time_tile=0):
-    """Wav2Vec2-BERT's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = act(LayerNorm_C(causal depthwise conv(GLU(u)))), w [C, 31],
-    zeros left of frame 0.  Returns (s, g, c, n, mean, rstd): with `save` the GLU output, the convolution output, the LayerNorm output and the
-    row statistics the backward needs, else five Nones.  `time_tile`: 0 (the library's choice), 8 or 16 frames per workgroup."""
-    _cc(u, "convmod_causal.u"); _cc(w, "convmod_causal.w"); _cc(gamma, "convmod_causal.gamma"); _cc(beta, "convmod_causal.beta")
-    if act not in CAUSAL_ACTS:
-        raise DynError(f"convmod_causal: act={act!r} is not built ({sorted(CAUSAL_ACTS)})")
+def _convmod_causal(name, u, w, cbias, gamma, beta, act, eps, save, launch):
+    """The checks and buffers of convmod_causal / convmod_causal_k9; `launch(s, g, c, n, mean, rstd, B, T, C)` calls the entry."""
+    _cc(u, name + ".u"); _cc(w, name + ".w"); _cc(gamma, name + ".gamma"); _cc(beta, name + ".beta")
+    if act is not None and act not in CAUSAL_ACTS:
+        raise DynError(f"{name}: act={act!r} is not built ({sorted(CAUSAL_ACTS)})")
     if u.dim() != 3 or u.shape[2] % 2 or w.dim() != 2 or w.shape[0] != u.shape[2] // 2 or gamma.numel() != w.shape[0] or beta.numel() != w.shape[0]:
-        raise DynError("convmod_causal: u must be [B, T, 2C], w [C, KW], gamma and beta [C]")
+        raise DynError(f"{name}: u must be [B, T, 2C], w [C, KW], gamma and beta [C]")
     B, T, C2 = u.shape
     C = C2 // 2
+    if cbias is not None and _cc(cbias, name + ".cbias").numel() != C:
+        raise DynError(f"{name}: cbias must be [C]")
     s = torch.empty(B, T, C, device=u.device, dtype=F32)
     g = c = n = mean = rstd = None
     if save:
         g, c, n = (torch.empty(B, T, C, device=u.device, dtype=F32) for _ in range(3))
         mean, rstd = (torch.empty(B * T, device=u.device, dtype=F32) for _ in range(2))
-    check(_L().dyn_convmod_causal_fwd(u.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), s.data_ptr(), _opt(g, "g"), _opt(c, "c"),
-                                      _opt(n, "n"), _opt(mean, "mean"), _opt(rstd, "rstd"), B, T, C, w.shape[1], CAUSAL_ACTS[act], eps,
-                                      int(time_tile), _stream()), "dyn_convmod_causal_fwd")
+    outs = (s.data_ptr(), _opt(g, "g"), _opt(c, "c"), _opt(n, "n"), _opt(mean, "mean"), _opt(rstd, "rstd"))
+    check(launch(outs, B, T, C), f"dyn_{name}_fwd")
     return s, g, c, n, mean, rstd
+
+
+def _dwconv1d_causal_dgrad(name, dy, w, out, beta):
+    _cc(dy, name + ".dy"); _cc(w, name + ".w")
+    B, T, C = dy.shape
+    if w.shape[0] != C:
+        raise DynError(f"{name}: w must be [C, KW]")
+    out = torch.empty_like(dy) if out is None else _cc(out, name + ".out")
+    if out.shape != dy.shape or out.data_ptr() == dy.data_ptr():
+        raise DynError(f"{name}: out must have the shape of dy and not alias it")
+    check(getattr(_L(), "dyn_" + name)(dy.data_ptr(), w.data_ptr(), out.data_ptr(), B, T, C, w.shape[1], beta, _stream()), "dyn_" + name)
+    return out
+
+
+def _dwconv1d_causal_wgrad(name, x, dy, dw, beta):
+    _cc(x, name + ".x"); _cc(dy, name + ".dy"); _cc(dw, name + ".dw")
+    B, T, C = x.shape
+    if dy.shape != x.shape or dw.dim() != 2 or dw.shape[0] != C:
+        raise DynError(f"{name}: dy must have the shape of x, dw must be [C, KW]")
+    ws = workspace(x.device)
+    check(getattr(_L(), "dyn_" + name)(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), beta, B, T, C, dw.shape[1], ws.data_ptr(), ws.numel(), _stream()),
+          "dyn_" + name)
+    return dw
+
+
+def convmod_causal(u, w, gamma, beta, act="swish", eps=1e-5, save=False, time_tile=0):
+    """Wav2Vec2-BERT's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = act(LayerNorm_C(causal depthwise conv(GLU(u)))), w [C, 31],
+    zeros left of frame 0.  Returns (s, g, c, n, mean, rstd): with `save` the GLU output, the convolution output, the LayerNorm output and the
+    row statistics the backward needs, else five Nones.  `time_tile`: 0 (the library's choice), 8 or 16 frames per workgroup."""
+    return _convmod_causal("convmod_causal", u, w, None, gamma, beta, act, eps, save, lambda outs, B, T, C: _L().dyn_convmod_causal_fwd(
+        u.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), *outs, B, T, C, w.shape[1], CAUSAL_ACTS[act], eps, int(time_tile), _stream()))
 
 
 def dwconv1d_causal_dgrad(dy, w, out=None, beta=0.0):
     """dx [B, T, C] = beta * dx + the input gradient of the left-padded depthwise convolution (w [C, KW]) from dy [B, T, C]."""
-    _cc(dy, "dwconv1d_causal_dgrad.dy"); _cc(w, "dwconv1d_causal_dgrad.w")
-    B, T, C = dy.shape
-    if w.shape[0] != C:
-        raise DynError("dwconv1d_causal_dgrad: w must be [C, KW]")
-    out = torch.empty_like(dy) if out is None else _cc(out, "dwconv1d_causal_dgrad.out")
-    if out.shape != dy.shape or out.data_ptr() == dy.data_ptr():
-        raise DynError("dwconv1d_causal_dgrad: out must have the shape of dy and not alias it")
-    check(_L().dyn_dwconv1d_causal_dgrad(dy.data_ptr(), w.data_ptr(), out.data_ptr(), B, T, C, w.shape[1], beta, _stream()),
-          "dyn_dwconv1d_causal_dgrad")
-    return out
+    return _dwconv1d_causal_dgrad("dwconv1d_causal_dgrad", dy, w, out, beta)
 
 
 def dwconv1d_causal_wgrad(x, dy, dw, beta=1.0):
     """dw [C, KW] = beta * dw + the weight gradient of the left-padded depthwise convolution of x [B, T, C] from dy [B, T, C]."""
-    _cc(x, "dwconv1d_causal_wgrad.x"); _cc(dy, "dwconv1d_causal_wgrad.dy"); _cc(dw, "dwconv1d_causal_wgrad.dw")
-    B, T, C = x.shape
-    if dy.shape != x.shape or dw.dim() != 2 or dw.shape[0] != C:
-        raise DynError("dwconv1d_causal_wgrad: dy must have the shape of x, dw must be [C, KW]")
-    ws = workspace(x.device)
-    check(_L().dyn_dwconv1d_causal_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), beta, B, T, C, dw.shape[1], ws.data_ptr(), ws.numel(),
-                                         _stream()), "dyn_dwconv1d_causal_wgrad")
-    return dw
+    return _dwconv1d_causal_wgrad("dwconv1d_causal_wgrad", x, dy, dw, beta)
 
 
 def narrow_layernorm(x, gamma, beta, eps=1e-5, out=None):
@@ -2641,45 +2655,15 @@ def dwconv2d_s2_causal_wgrad_act(z, du, dw, dbias, act, beta=1.0):
 def convmod_causal_k9(u, w, cbias, gamma, beta, eps=1e-5, save=False):
     """NemotronAsrStreaming's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = silu(LayerNorm_C(cbias + causal depthwise
     conv(GLU(u)))), w [C, 9], cbias [C] or None, zeros left of frame 0.  Returns (s, g, c, n, mean, rstd) as convmod_causal."""
-    _cc(u, "convmod_causal_k9.u"); _cc(w, "convmod_causal_k9.w"); _cc(gamma, "convmod_causal_k9.gamma"); _cc(beta, "convmod_causal_k9.beta")
-    if u.dim() != 3 or u.shape[2] % 2 or w.dim() != 2 or w.shape[0] != u.shape[2] // 2 or gamma.numel() != w.shape[0] or beta.numel() != w.shape[0]:
-        raise DynError("convmod_causal_k9: u must be [B, T, 2C], w [C, KW], gamma and beta [C]")
-    B, T, C2 = u.shape
-    C = C2 // 2
-    if cbias is not None and _cc(cbias, "convmod_causal_k9.cbias").numel() != C:
-        raise DynError("convmod_causal_k9: cbias must be [C]")
-    s = torch.empty(B, T, C, device=u.device, dtype=F32)
-    g = c = n = mean = rstd = None
-    if save:
-        g, c, n = (torch.empty(B, T, C, device=u.device, dtype=F32) for _ in range(3))
-        mean, rstd = (torch.empty(B * T, device=u.device, dtype=F32) for _ in range(2))
-    check(_L().dyn_convmod_causal_k9_fwd(u.data_ptr(), w.data_ptr(), _opt(cbias, "cbias"), gamma.data_ptr(), beta.data_ptr(), s.data_ptr(),
-                                         _opt(g, "g"), _opt(c, "c"), _opt(n, "n"), _opt(mean, "mean"), _opt(rstd, "rstd"), B, T, C, w.shape[1],
-                                         eps, _stream()), "dyn_convmod_causal_k9_fwd")
-    return s, g, c, n, mean, rstd
+    return _convmod_causal("convmod_causal_k9", u, w, cbias, gamma, beta, None, eps, save, lambda outs, B, T, C: _L().dyn_convmod_causal_k9_fwd(
+        u.data_ptr(), w.data_ptr(), _opt(cbias, "cbias"), gamma.data_ptr(), beta.data_ptr(), *outs, B, T, C, w.shape[1], eps, _stream()))
 
 
 def dwconv1d_causal_k9_dgrad(dy, w, out=None, beta=0.0):
     """dwconv1d_causal_dgrad at 9 taps."""
-    _cc(dy, "dwconv1d_causal_k9_dgrad.dy"); _cc(w, "dwconv1d_causal_k9_dgrad.w")
-    B, T, C = dy.shape
-    if w.shape[0] != C:
-        raise DynError("dwconv1d_causal_k9_dgrad: w must be [C, KW]")
-    out = torch.empty_like(dy) if out is None else _cc(out, "dwconv1d_causal_k9_dgrad.out")
-    if out.shape != dy.shape or out.data_ptr() == dy.data_ptr():
-        raise DynError("dwconv1d_causal_k9_dgrad: out must have the shape of dy and not alias it")
-    check(_L().dyn_dwconv1d_causal_k9_dgrad(dy.data_ptr(), w.data_ptr(), out.data_ptr(), B, T, C, w.shape[1], beta, _stream()),
-          "dyn_dwconv1d_causal_k9_dgrad")
-    return out
+    return _dwconv1d_causal_dgrad("dwconv1d_causal_k9_dgrad", dy, w, out, beta)
 
 
 def dwconv1d_causal_k9_wgrad(x, dy, dw, beta=1.0):
     """dwconv1d_causal_wgrad at 9 taps."""
-    _cc(x, "dwconv1d_causal_k9_wgrad.x"); _cc(dy, "dwconv1d_causal_k9_wgrad.dy"); _cc(dw, "dwconv1d_causal_k9_wgrad.dw")
-    B, T, C = x.shape
-    if dy.shape != x.shape or dw.dim() != 2 or dw.shape[0] != C:
-        raise DynError("dwconv1d_causal_k9_wgrad: dy must have the shape of x, dw must be [C, KW]")
-    ws = workspace(x.device)
-    check(_L().dyn_dwconv1d_causal_k9_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), beta, B, T, C, dw.shape[1], ws.data_ptr(), ws.numel(),
-                                            _stream()), "dyn_dwconv1d_causal_k9_wgrad")
-    return dw
+    return _dwconv1d_causal_wgrad("dwconv1d_causal_k9_wgrad", x, dy, dw, beta)

@@ -287,34 +287,18 @@ class Wav2Vec2BertForCTC(WC.Wav2Vec2ConformerForCTC):
                           G[p + "self_attn_layer_norm.bias"], dx_beta=1.0, dx_in=dr)
         return dx
 
+    def _causal_conv_spec(self, l):
+        p = f"{self._prefix}encoder.layers.{l}.conv_module."
+        names = tuple(p + n for n in ("layer_norm", "pointwise_conv1", "depthwise_conv", "depthwise_layer_norm", "pointwise_conv2"))
+        core = lambda u, w, cb, gamma, beta, save: ops.convmod_causal(u, w, gamma, beta, self._act_name, self._layer_eps, save=save)
+        return names, core, self._act_bwd, ops.dwconv1d_causal_wgrad, ops.dwconv1d_causal_dgrad
+
     def _conv_fwd(self, x, l, vT, save):
         """x + conv_module(x).  No row masking under a length bucket: the convolution is causal (see the module docstring)."""
-        P = self.P
-        p = f"{self._prefix}encoder.layers.{l}.conv_module."
-        n, m, s = ops.layernorm(x, P[p + "layer_norm.weight"], P[p + "layer_norm.bias"], self._layer_eps)
-        u = ops.linear(n, P[p + "pointwise_conv1.weight"])
-        a, g, cv, nn, mean, rstd = ops.convmod_causal(u, P[p + "depthwise_conv.weight"], P[p + "depthwise_layer_norm.weight"],
-                                                      P[p + "depthwise_layer_norm.bias"], self._act_name, self._layer_eps, save=save)
-        r = x.clone() if save else x
-        ops.linear(a, P[p + "pointwise_conv2.weight"], None, out=r, beta=1.0)
-        return r, (x, m, s, n, u, g, cv, nn, mean, rstd, a)
+        return self._causal_conv_fwd(x, l, save)
 
     def _conv_bwd(self, dr, kept, l, vT):
-        P, G = self.P, self.G
-        p = f"{self._prefix}encoder.layers.{l}.conv_module."
-        x, m, s, n, u, g, cv, nn, mean, rstd, a = kept
-        da = self._lin_bwd(dr, a, p + "pointwise_conv2.weight", None)
-        dnn = self._act_bwd(nn, da, out=da)
-        dcv = torch.empty_like(dnn)
-        ops.layernorm_bwd(cv, P[p + "depthwise_layer_norm.weight"], mean, rstd, dnn, dcv, G[p + "depthwise_layer_norm.weight"],
-                          G[p + "depthwise_layer_norm.bias"], dx_beta=0.0)
-        ops.dwconv1d_causal_wgrad(g, dcv, G[p + "depthwise_conv.weight"], beta=1.0)
-        dg = ops.dwconv1d_causal_dgrad(dcv, P[p + "depthwise_conv.weight"])
-        du = ops.glu_bwd(u, dg)
-        dn = self._lin_bwd(du, n, p + "pointwise_conv1.weight", None)
-        dx = torch.empty_like(dr)
-        ops.layernorm_bwd(x, P[p + "layer_norm.weight"], m, s, dn, dx, G[p + "layer_norm.weight"], G[p + "layer_norm.bias"], dx_beta=1.0, dx_in=dr)
-        return dx
+        return self._causal_conv_bwd(dr, kept, l)
 
     def _encode(self, h, ctx, vT, dims, v0):
         P = self.P

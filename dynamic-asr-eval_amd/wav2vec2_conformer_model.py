@@ -339,6 +339,41 @@ class Wav2Vec2ConformerForCTC(W2.Wav2Vec2ForCTC):
         ops.layernorm_bwd(x, P[p + "layer_norm.weight"], m, s, dn, dx, G[p + "layer_norm.weight"], G[p + "layer_norm.bias"], dx_beta=1.0, dx_in=dr)
         return dx
 
+    # The conv module of the family's causal members (Wav2Vec2-BERT, Nemotron streaming): LayerNorm -> pointwise conv -> [GLU -> causal
+    # depthwise conv -> LayerNorm -> activation in one launch] -> pointwise conv, added to x.  A class says what is its own in
+    # _causal_conv_spec(l): the parameter names (without .weight / .bias; the three convolutions' biases are used where they exist) of
+    # (layer_norm, pointwise_conv1, depthwise_conv, depthwise_layer_norm, pointwise_conv2), then core(u, w, cbias, gamma, beta, save), the
+    # activation's backward and the depthwise wgrad and dgrad ops.
+    def _causal_conv_fwd(self, x, l, save):
+        P = self.P
+        (ln, pw1, dw, dln, pw2), core = self._causal_conv_spec(l)[:2]
+        n, m, s = ops.layernorm(x, P[ln + ".weight"], P[ln + ".bias"], self._layer_eps)
+        u = ops.linear(n, P[pw1 + ".weight"], P.get(pw1 + ".bias"))
+        a, g, cv, nn, mean, rstd = core(u, P[dw + ".weight"], P.get(dw + ".bias"), P[dln + ".weight"], P[dln + ".bias"], save)
+        r = x.clone() if save else x
+        ops.linear(a, P[pw2 + ".weight"], P.get(pw2 + ".bias"), out=r, beta=1.0)
+        return r, (x, m, s, n, u, g, cv, nn, mean, rstd, a)
+
+    def _causal_conv_bwd(self, dr, kept, l):
+        P, G = self.P, self.G
+        (ln, pw1, dw, dln, pw2), _, act_bwd, wgrad, dgrad = self._causal_conv_spec(l)
+        x, m, s, n, u, g, cv, nn, mean, rstd, a = kept
+        has_cb = dw + ".bias" in P
+        b1, b2 = (pw + ".bias" if has_cb else None for pw in (pw1, pw2))
+        da = self._lin_bwd(dr, a, pw2 + ".weight", b2)
+        dnn = act_bwd(nn, da, out=da)
+        dcv = torch.empty_like(dnn)
+        ops.layernorm_bwd(cv, P[dln + ".weight"], mean, rstd, dnn, dcv, G[dln + ".weight"], G[dln + ".bias"], dx_beta=0.0)
+        wgrad(g, dcv, G[dw + ".weight"], beta=1.0)
+        if has_cb:
+            ops.colsum(dcv.view(-1, dcv.shape[-1]), G[dw + ".bias"], beta=1.0)
+        dg = dgrad(dcv, P[dw + ".weight"])
+        du = ops.glu_bwd(u, dg)
+        dn = self._lin_bwd(du, n, pw1 + ".weight", b1)
+        dx = torch.empty_like(dr)
+        ops.layernorm_bwd(x, P[ln + ".weight"], m, s, dn, dx, G[ln + ".weight"], G[ln + ".bias"], dx_beta=1.0, dx_in=dr)
+        return dx
+
     def _layers_fwd(self, x, ctx, vT, tab):
         """The conformer layers on x [B, T, H]; fills ctx["layers"] when a context is kept.  Shared with a model of the family whose encoder
         ends differently (wav2vec2_bert_model.py)."""
