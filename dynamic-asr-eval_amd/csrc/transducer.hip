@@ -1065,7 +1065,8 @@ __global__ __launch_bounds__(64 * WPB) void rnnt_grad_kernel(const float* logits
 // frame and resets the per-frame symbol counter; a non-blank is emitted and counted, and when the counter reaches max_symbols the frame
 // advances anyway and the counter resets (the forced step's token is still emitted and fed to the prediction network).
 enum { S_SYMBOLS = 6 };
-__global__ __launch_bounds__(256) void rnnt_greedy_pick_kernel(const GreedyArgs a, int max_symbols) {
+// `frame_base`: added to the frame RECORDED with an emitted token (0 offline; the absolute frame of a streamed chunk's frame 0).
+__global__ __launch_bounds__(256) void rnnt_greedy_pick_kernel(const GreedyArgs a, int max_symbols, int frame_base) {
     __shared__ float rv[4];
     __shared__ int ri[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1096,7 +1097,7 @@ __global__ __launch_bounds__(256) void rnnt_greedy_pick_kernel(const GreedyArgs 
     int count = ist(a, S_COUNT)[b];
     if (!is_blank && count < a.n_max) {
         a.tokens[(int64_t)b * a.n_max + count] = tok;
-        a.frames[(int64_t)b * a.n_max + count] = frame;
+        a.frames[(int64_t)b * a.n_max + count] = frame + frame_base;
         ++count;
     }
     const int steps = ist(a, S_STEPS)[b] + 1;
@@ -1107,6 +1108,18 @@ __global__ __launch_bounds__(256) void rnnt_greedy_pick_kernel(const GreedyArgs 
     ist(a, S_FRAME)[b] = frame + adv;
     ist(a, S_SYMBOLS)[b] = adv ? 0 : symbols;
     if (frame + adv >= a.valid[b] || steps >= a.max_steps || count >= a.n_max) ist(a, S_DONE)[b] = 1;
+}
+
+// A streamed decode moves on to the next chunk of encoder frames: the frame pointer back to 0, the done flags, the per-frame symbol
+// counter and the chunk's output count and step count cleared.  h / c, the cached projector output, the last token and the emit flag stay.
+__global__ void rnnt_greedy_rebase_kernel(const GreedyArgs a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    ist(a, S_FRAME)[b] = 0;
+    ist(a, S_DONE)[b] = 0;
+    ist(a, S_COUNT)[b] = 0;
+    ist(a, S_STEPS)[b] = 0;
+    ist(a, S_SYMBOLS)[b] = 0;
 }
 
 // What every RNN-T entry does before its launches (tdt_setup without the durations)
@@ -1230,16 +1243,20 @@ extern "C" int dyn_rnnt_grad_chunk(const float* logits, int64_t B, int64_t T, in
     return dyn::check_launch("dyn_rnnt_grad_chunk");
 }
 
-extern "C" int dyn_rnnt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
-                                     const float* proj_w, const float* proj_b, const float* head_w, const float* head_b, int32_t* istate,
-                                     float* h, float* c, float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B,
-                                     int64_t T, int64_t Hd, int64_t layers, int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max,
-                                     int64_t max_steps, int32_t n_steps, void* stream) {
+namespace {
+
+int rnnt_greedy_launch(const char* who, const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
+                       const float* proj_w, const float* proj_b, const float* head_w, const float* head_b, int32_t* istate, float* h, float* c,
+                       float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd,
+                       int64_t layers, int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max, int64_t max_steps, int32_t n_steps,
+                       int64_t frame_base, bool rebase, void* stream) {
     DYN_REQUIRE(enc && valid && embed && lstm_ptrs && proj_w && proj_b && head_w && head_b && istate && h && c && h_new && dec && logits &&
-                    tokens && frames, DYN_E_ARG, "dyn_rnnt_greedy_steps: null pointer");
+                    tokens && frames, DYN_E_ARG, "%s: null pointer", who);
     DYN_REQUIRE(B > 0 && B <= 65535 && T > 0 && Hd > 0 && layers > 0 && layers <= 8 && V1 > 0 && V1 < (1 << 30) && blank >= 0 && blank < V1 &&
                     max_symbols > 0 && n_max > 0 && max_steps > 0 && n_steps >= 0 && T < (1 << 30) && n_max < (1 << 30), DYN_E_ARG,
-                "dyn_rnnt_greedy_steps: bad sizes");
+                "%s: bad sizes", who);
+    DYN_REQUIRE(frame_base >= 0 && frame_base + T < (1ll << 31), DYN_E_ARG, "%s: frame_base=%lld leaves the int32 frames", who,
+                (long long)frame_base);
     GreedyArgs a;
     a.durs.n = 0;
     for (int i = 0; i < MAX_DUR; ++i) a.durs.d[i] = 0;
@@ -1251,11 +1268,35 @@ extern "C" int dyn_rnnt_greedy_steps(const float* enc, const int32_t* valid, con
     const int ms = (int)(max_symbols < (1 << 30) ? max_symbols : (1 << 30));
     hipStream_t st = (hipStream_t)stream;
     const dim3 blk(256), gh((unsigned)dyn::cdiv(Hd, 4), (unsigned)B), gn((unsigned)dyn::cdiv(V1, 4), (unsigned)B);
+    if (rebase) hipLaunchKernelGGL(rnnt_greedy_rebase_kernel, dim3((unsigned)dyn::cdiv(B, 256)), blk, 0, st, a);
     for (int s = 0; s < n_steps; ++s) {
         for (int l = 0; l < layers; ++l) hipLaunchKernelGGL(greedy_lstm_kernel, gh, blk, 0, st, a, l);
         hipLaunchKernelGGL(greedy_proj_kernel, gh, blk, 0, st, a);
         hipLaunchKernelGGL(greedy_joint_kernel, gn, blk, 0, st, a);
-        hipLaunchKernelGGL(rnnt_greedy_pick_kernel, dim3((unsigned)B), blk, 0, st, a, ms);
+        hipLaunchKernelGGL(rnnt_greedy_pick_kernel, dim3((unsigned)B), blk, 0, st, a, ms, (int)frame_base);
     }
-    return dyn::check_launch("dyn_rnnt_greedy_steps");
+    return dyn::check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int dyn_rnnt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
+                                     const float* proj_w, const float* proj_b, const float* head_w, const float* head_b, int32_t* istate,
+                                     float* h, float* c, float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B,
+                                     int64_t T, int64_t Hd, int64_t layers, int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max,
+                                     int64_t max_steps, int32_t n_steps, void* stream) {
+    return rnnt_greedy_launch("dyn_rnnt_greedy_steps", enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, istate, h, c, h_new, dec,
+                              logits, tokens, frames, B, T, Hd, layers, V1, blank, max_symbols, n_max, max_steps, n_steps, 0, false, stream);
+}
+
+extern "C" int dyn_rnnt_greedy_steps_chunk(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
+                                           const float* proj_w, const float* proj_b, const float* head_w, const float* head_b,
+                                           int32_t* istate, float* h, float* c, float* h_new, float* dec, float* logits, int32_t* tokens,
+                                           int32_t* frames, int64_t B, int64_t T, int64_t Hd, int64_t layers, int64_t V1, int32_t blank,
+                                           int64_t max_symbols, int64_t n_max, int64_t max_steps, int32_t n_steps, int64_t frame_base,
+                                           int32_t rebase, void* stream) {
+    DYN_REQUIRE(rebase == 0 || rebase == 1, DYN_E_ARG, "dyn_rnnt_greedy_steps_chunk: rebase=%d (0 or 1)", (int)rebase);
+    return rnnt_greedy_launch("dyn_rnnt_greedy_steps_chunk", enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, istate, h, c, h_new,
+                              dec, logits, tokens, frames, B, T, Hd, layers, V1, blank, max_symbols, n_max, max_steps, n_steps, frame_base,
+                              rebase != 0, stream);
 }

@@ -26,12 +26,18 @@ loss follows ParakeetForRNNT.  The encoder differs in three places:
 `num_lookahead_tokens=` of forward / encode / generate picks the lookahead of that call (None: `default_num_lookahead_tokens`); head() and
 backward() take it too and refuse a value that differs from the encode whose activations they continue.
 
-Refused by name before any launch: `attention_mask`; `use_cache`, `past_key_values`, `padding_cache` (the streaming caches);
+Streaming is a separate interface: `model.stream(batch_size, num_lookahead_tokens=None, graph=False)` returns a session that owns the K/V
+rings, the conv states, the subsampling carries and the greedy decoder's state on the device (encode_chunk / push / reset), and
+`generate_streaming()` drives one over a whole stream (nemotron_asr_streaming_stream.py, csrc/stream.hip); a stream is not bounded by
+`max_position_embeddings`.
+Refused by name before any launch: `attention_mask`; `use_cache`, `past_key_values`, `padding_cache` in the offline calls (the streaming caches
+belong to a session);
 `subsampling_factor` != 8, subsampling kernel != 3, stride != 2, `conv_kernel_size` != 9, `hidden_act` != "silu", a joint activation
 other than relu, `hidden_size` outside 256 / 512 / 768 / 1024; a negative or non-integer lookahead, `sliding_window` = 0, T' >
 `max_position_embeddings`; the `model_type` of any Parakeet head; `sigma`; batch_renorm_training() (there is no batch norm); and what
 the parents refuse of the head.
-Out of scope: the streaming caches and chunk-by-chunk encode; ragged batches; a waveform front end; hipGraph replay and lockstep groups;
+Out of scope: gradients through a streaming session; ragged batches and rows that join or leave a session; a waveform front end; hipGraph
+replay of the offline calls and lockstep groups; the decode inside the captured streaming step;
 skipping fully masked tiles in the score and context GEMMs (the band is exploited in the position product and the softmax only);
 `Nemotron3_5AsrForRNNT`.  No hub checkpoint is on the machine: transformers' class on the CPU with the same random state dict is the
 oracle in the tests."""
@@ -124,6 +130,7 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
         self.F3 = frames(self.cfg["num_mel_bins"])             # the frequency columns the subsampling linear reads per channel
         self._lookahead = self.cfg["default_num_lookahead_tokens"]     # of the encode in flight
         self._ctx_lookahead = None                             # of the encode whose activations self._ctx holds
+        self._after_stream = False                             # a streaming session ran since the last encode(): backward() is refused
 
     def _make_buffers(self):
         return {}                                              # conv.norm is a LayerNorm: no running statistics
@@ -135,8 +142,8 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
     def _refuse_caches(self, kw):
         for k in CACHES:
             if kw.pop(k, None) not in (None, False):
-                raise ops.DynError(f"{k} is not built: the streaming caches and chunk-by-chunk encode are out of scope (the offline forward "
-                                   "under the chunked limited-context mask is)")
+                raise ops.DynError(f"{k} is not built here: this call is the offline forward under the chunked limited-context mask; the "
+                                   "streaming caches live in a session, model.stream(batch_size) (encode_chunk / push), or generate_streaming()")
         if kw:
             raise TypeError(f"unexpected arguments {sorted(kw)}")
 
@@ -149,7 +156,8 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
         """ParakeetForTDT.encode under the chunked mask of `num_lookahead_tokens` (None: the configuration's default)."""
         self._refuse_caches(caches)
         c = self.cfg
-        self._lookahead = c["default_num_lookahead_tokens"] if num_lookahead_tokens is None else check_lookahead(num_lookahead_tokens)
+        self._after_stream = False
+        self._lookahead =c["default_num_lookahead_tokens"] if num_lookahead_tokens is None else check_lookahead(num_lookahead_tokens)
         if isinstance(input_features, torch.Tensor) and input_features.dim() == 3 and self.frames(input_features.shape[1]) > c["max_position_embeddings"]:
             raise ops.DynError(f"{self.frames(input_features.shape[1])} encoder frames exceed max_position_embeddings={c['max_position_embeddings']}")
         enc = super().encode(input_features, attention_mask)
@@ -175,8 +183,24 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
         return super().head(enc, decoder_input_ids, labels, reduction, sigma, grad_scale, n_active, label_lengths, frames_per_chunk)
 
     def backward(self, grad_logits=None, n_active=None, num_lookahead_tokens=None):
+        if self._after_stream:
+            raise ops.DynError("backward() after a streaming push / encode_chunk is not built: a session runs under no_grad and keeps no "
+                               "activations (gradients through a stream are out of scope); run encode() / forward() first")
         self._same_lookahead("backward", num_lookahead_tokens)
         return super().backward(grad_logits, n_active)
+
+    # ------------------------------------------------------------------ streaming (nemotron_asr_streaming_stream.py)
+    def stream(self, batch_size, num_lookahead_tokens=None, graph=False):
+        """A cache-aware streaming session of `batch_size` streams: StreamSession (first_chunk_frames, chunk_frames, encode_chunk(feats),
+        push(feats), frames_seen, reset()).  graph=True replays the steady-state encoder step as one captured hipGraph."""
+        from .nemotron_asr_streaming_stream import StreamSession
+        return StreamSession(self, batch_size, num_lookahead_tokens, graph)
+
+    def generate_streaming(self, input_features, num_lookahead_tokens=None, graph=False):
+        """generate() chunk by chunk through a session: input_features [B, T, F] with T = first_chunk_frames + k * chunk_frames, or an
+        iterable of chunks -> the same fields, concatenated over the chunks."""
+        from .nemotron_asr_streaming_stream import generate_streaming
+        return generate_streaming(self, input_features, num_lookahead_tokens, graph)
 
     def generate(self, input_features=None, enc=None, num_lookahead_tokens=None):
         """ParakeetForTDT.generate; the encoder pass of `input_features` runs under the mask of `num_lookahead_tokens`."""

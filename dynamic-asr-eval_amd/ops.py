@@ -2667,3 +2667,140 @@ def dwconv1d_causal_k9_dgrad(dy, w, out=None, beta=0.0):
 def dwconv1d_causal_k9_wgrad(x, dy, dw, beta=1.0):
     """dwconv1d_causal_wgrad at 9 taps."""
     return _dwconv1d_causal_wgrad("dwconv1d_causal_k9_wgrad", x, dy, dw, beta)
+
+
+# ----------------------------------------------------------------------------------------------- NemotronAsrStreamingForRNNT, streaming
+def stream_geometry(sliding_window, lookahead):
+    """Pure host function: the geometry of a cache-aware stream.  cs = lookahead + 1 encoder frames per chunk, lc = (sliding_window - 1) //
+    cs visible cached chunks, the ring's lc + 1 slots, NK = (lc + 1) cs keys at most, W = NK + cs - 1 distances (lc cs + cs - 1 down to
+    -(cs - 1)), and the feature frames of the first and of every later chunk (transformers' _required_stream_chunk_frames)."""
+    from types import SimpleNamespace
+    for name, v in (("sliding_window", sliding_window), ("lookahead", lookahead)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise DynError(f"stream_geometry: {name}={v!r} must be an integer")
+    if sliding_window < 1 or lookahead < 0:
+        raise DynError(f"stream_geometry: sliding_window={sliding_window} must be positive (a negative one leaves the left context, and so "
+                       f"the cache, without a bound) and lookahead={lookahead} must not be negative")
+    cs = lookahead + 1
+    lc = (sliding_window - 1) // cs
+    NK = (lc + 1) * cs
+    return SimpleNamespace(cs=cs, lc=lc, slots=lc + 1, NK=NK, W=NK + cs - 1, dlo=NK - 1, first_frames=1 + 8 * lookahead, frames=8 * cs)
+
+
+def stream_stage_len(n, first):
+    """Output rows of a streamed 3-wide stride-2 stage on n input rows: one carried row to the left (two zero rows on the first chunk),
+    nothing to the right (NemotronAsrStreamingEncoderCausalConv2D.output_length(streaming=True))."""
+    return (n + (2 if first else 1) - 3) // 2 + 1
+
+
+def stream_position_rows(geo, H):
+    """[W, H] float32 on the host: the sinusoid rows of the distances geo.dlo .. -(geo.cs - 1), NemotronAsrStreamingEncoderRelPositionalEncoding's
+    arithmetic (the rows ops.chunked_band names of a long enough offline table)."""
+    inv_freq = 1.0 / (10000.0 ** (torch.arange(0, H, 2, dtype=torch.float) / H))
+    position_ids = torch.arange(geo.dlo, -geo.cs, -1)
+    freqs = (inv_freq[None, :, None].float() @ position_ids[None, None, :].float()).transpose(1, 2)
+    pe = torch.stack([freqs.sin(), freqs.cos()], dim=-1)
+    return pe.reshape(*pe.shape[:-2], -1)[0].contiguous()
+
+
+def _counter(counter, who):
+    _c(counter, who + ".counter", I32)
+    if counter.numel() < 1:
+        raise DynError(f"{who}: the counter must hold one int32")
+    return counter
+
+
+def stream_advance(counter):
+    """counter[0] += 1 on the device: the last launch of a streaming step."""
+    check(_L().dyn_stream_advance(_counter(counter, "stream_advance").data_ptr(), _stream()), "dyn_stream_advance")
+
+
+def stream_attn(qkv, bias_u, bias_v, pos, k_cache, v_cache, counter, nh, lc, scale=None, out=None):
+    """The attention core of one layer and chunk: qkv [B, cs, 3H] -> context [B, cs, H]; pos [W, H]; k_cache / v_cache [B, lc + 1, cs, H]
+    rings, the chunk's k / v stored into slot counter % (lc + 1)."""
+    _cc(qkv, "stream_attn.qkv"); _cc(bias_u, "stream_attn.bias_u"); _cc(bias_v, "stream_attn.bias_v"); _cc(pos, "stream_attn.pos")
+    _cc(k_cache, "stream_attn.k_cache"); _cc(v_cache, "stream_attn.v_cache"); _counter(counter, "stream_attn")
+    if qkv.dim() != 3 or qkv.shape[2] % 3:
+        raise DynError(f"stream_attn: qkv {tuple(qkv.shape)} must be [B, cs, 3H]")
+    B, cs, H3 = qkv.shape
+    H = H3 // 3
+    if H % nh:
+        raise DynError(f"stream_attn: H={H} is not a multiple of {nh} heads")
+    W = (lc + 1) * cs + cs - 1
+    if (tuple(pos.shape) != (W, H) or tuple(k_cache.shape) != (B, lc + 1, cs, H) or tuple(v_cache.shape) != (B, lc + 1, cs, H)
+            or bias_u.numel() != H or bias_v.numel() != H):
+        raise DynError(f"stream_attn: pos must be [{W}, {H}], the caches [{B}, {lc + 1}, {cs}, {H}], the head biases [{H}]")
+    out = torch.empty(B, cs, H, device=qkv.device, dtype=F32) if out is None else _cc(out, "stream_attn.out")
+    if tuple(out.shape) != (B, cs, H):
+        raise DynError(f"stream_attn: out must be [{B}, {cs}, {H}]")
+    D = H // nh
+    check(_L().dyn_stream_attn(qkv.data_ptr(), bias_u.data_ptr(), bias_v.data_ptr(), pos.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                               counter.data_ptr(), out.data_ptr(), B, cs, lc, nh, D, D ** -0.5 if scale is None else scale, _stream()),
+          "dyn_stream_attn")
+    return out
+
+
+def stream_convmod_k9(u, w, cbias, gamma, beta, state, counter, eps=1e-5):
+    """convmod_causal_k9 on a chunk u [B, T, 2C] with the carried GLU frames state [2, B, 8, C] (half counter & 1 read, the other written)."""
+    _cc(u, "stream_convmod_k9.u"); _cc(w, "stream_convmod_k9.w"); _cc(gamma, "stream_convmod_k9.gamma"); _cc(beta, "stream_convmod_k9.beta")
+    _cc(state, "stream_convmod_k9.state"); _counter(counter, "stream_convmod_k9")
+    B, T, C2 = u.shape
+    C = C2 // 2
+    if tuple(w.shape) != (C, 9) or tuple(state.shape) != (2, B, 8, C) or gamma.numel() != C or beta.numel() != C:
+        raise DynError(f"stream_convmod_k9: w must be [{C}, 9], the state [2, {B}, 8, {C}], gamma and beta [{C}]")
+    s = torch.empty(B, T, C, device=u.device, dtype=F32)
+    check(_L().dyn_stream_convmod_k9(u.data_ptr(), w.data_ptr(), _opt(cbias, "cbias"), gamma.data_ptr(), beta.data_ptr(), state.data_ptr(),
+                                     counter.data_ptr(), s.data_ptr(), B, T, C, w.shape[1], eps, _stream()), "dyn_stream_convmod_k9")
+    return s
+
+
+def stream_conv2d_first(x, w, bias, carry, counter, first):
+    """The causal stem on a chunk x [B, T, F] -> z [B, stream_stage_len(T, first), F // 2 + 1, C]; carry [2, B, F]."""
+    _c(x, "stream_conv2d_first.x"); _cc(w, "stream_conv2d_first.w"); _cc(bias, "stream_conv2d_first.bias"); _c(carry, "stream_conv2d_first.carry")
+    _counter(counter, "stream_conv2d_first")
+    B, T, F = x.shape
+    C = w.shape[0]
+    if tuple(carry.shape) != (2, B, F):
+        raise DynError(f"stream_conv2d_first: the carry must be [2, {B}, {F}]")
+    out = torch.empty(B, stream_stage_len(T, first), causal_out_len(F), C, device=x.device, dtype=F32)
+    check(_L().dyn_stream_conv2d_first(x.data_ptr(), w.data_ptr(), bias.data_ptr(), carry.data_ptr(), counter.data_ptr(), out.data_ptr(), B, T, F,
+                                       C, int(bool(first)), _stream()), "dyn_stream_conv2d_first")
+    return out
+
+
+def stream_dwconv2d_s2_act(z, w, bias, carry, counter, act, first):
+    """The ReLU-fused causal depthwise stage on a chunk z [B, T, F, C] -> [B, stream_stage_len(T, first), F // 2 + 1, C]; carry [2, B, F, C]
+    (rows before the ReLU)."""
+    a = _sub_act(act, "stream_dwconv2d_s2_act")
+    _cc(z, "stream_dwconv2d_s2_act.z"); _cc(w, "stream_dwconv2d_s2_act.w"); _cc(bias, "stream_dwconv2d_s2_act.bias")
+    _cc(carry, "stream_dwconv2d_s2_act.carry"); _counter(counter, "stream_dwconv2d_s2_act")
+    B, T, F, C = z.shape
+    if tuple(carry.shape) != (2, B, F, C):
+        raise DynError(f"stream_dwconv2d_s2_act: the carry must be [2, {B}, {F}, {C}]")
+    out = torch.empty(B, stream_stage_len(T, first), causal_out_len(F), C, device=z.device, dtype=F32)
+    check(_L().dyn_stream_dwconv2d_s2_act(z.data_ptr(), w.data_ptr(), bias.data_ptr(), carry.data_ptr(), counter.data_ptr(), out.data_ptr(), B, T,
+                                          F, C, a, int(bool(first)), _stream()), "dyn_stream_dwconv2d_s2_act")
+    return out
+
+
+def rnnt_greedy_steps_chunk(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, blank, max_symbols, max_steps, n_steps,
+                            frame_base, rebase):
+    """rnnt_greedy_steps on the frames enc [B, cs, Hd] of one streamed chunk; `rebase`: first move the state on to this chunk (frame pointer 0,
+    done flags, per-frame counter, output and step counts cleared; h / c, the projector cache, the last token and the emit flag kept).
+    Frames are recorded as frame_base + the frame inside the chunk."""
+    _cc(enc, "rnnt_greedy.enc"); _cc(valid, "rnnt_greedy.valid", I32); _cc(embed, "rnnt_greedy.embed"); _cc(lstm_ptrs, "rnnt_greedy.lstm_ptrs", torch.int64)
+    for t, n in ((proj_w, "proj_w"), (proj_b, "proj_b"), (head_w, "head_w"), (head_b, "head_b")):
+        _cc(t, "rnnt_greedy." + n)
+    B, T, Hd = enc.shape
+    layers = state.h.shape[0]
+    V1 = head_w.shape[0]
+    if (tuple(state.h.shape) != (layers, B, Hd) or lstm_ptrs.numel() != 4 * layers or embed.shape != (V1, Hd) or head_w.shape[1] != Hd
+            or tuple(proj_w.shape) != (Hd, Hd) or tuple(state.logits.shape) != (B, V1) or tuple(state.istate.shape) != (7, B)
+            or valid.numel() != B or head_b.numel() != V1 or not 0 <= blank < V1 or int(max_symbols) < 1):
+        raise DynError("rnnt_greedy_steps_chunk: shapes of the state (RnntGreedyState), the weights and enc do not fit together")
+    check(_L().dyn_rnnt_greedy_steps_chunk(enc.data_ptr(), valid.data_ptr(), embed.data_ptr(), lstm_ptrs.data_ptr(), proj_w.data_ptr(),
+                                           proj_b.data_ptr(), head_w.data_ptr(), head_b.data_ptr(), state.istate.data_ptr(), state.h.data_ptr(),
+                                           state.c.data_ptr(), state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(),
+                                           state.tokens.data_ptr(), state.frames.data_ptr(), B, T, Hd, layers, V1, int(blank), int(max_symbols),
+                                           state.n_max, int(max_steps), int(n_steps), int(frame_base), int(bool(rebase)), _stream()),
+          "dyn_rnnt_greedy_steps_chunk")

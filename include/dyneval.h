@@ -1156,6 +1156,51 @@ int64_t dyn_dwconv1d_causal_k9_wgrad_workspace_bytes(int64_t B, int64_t T, int64
 int dyn_dwconv1d_causal_k9_wgrad(const float* x, const float* dy, float* dw, float beta, int64_t B, int64_t T, int64_t C, int64_t KW,
                                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * NemotronAsrStreamingForRNNT, cache-aware streaming (transformers modeling_nemotron_asr_streaming.py with `use_cache=True`, and
+ * generation_nemotron_asr_streaming.py): one STEP takes cs = lookahead + 1 encoder frames of B streams.  `counter` is a device int32:
+ * counter[0] = the chunks consumed so far.  Every kernel reads the ring slot, the warm-up count and the state half from it, so a step's
+ * launches have the same arguments every time (csrc/stream.hip).  lc = (sliding_window - 1) / cs cached chunks are visible.
+ *   dyn_stream_advance        counter[0] += 1: the last launch of a step.
+ *   dyn_stream_attn           replaces, for one layer and chunk, `past_key_values.update` (DynamicSlidingWindowLayer), the two head
+ *                             biases, `relative_k_proj`'s product with the query, `_rel_shift`, the chunked mask, eager_attention_forward
+ *                             (NemotronAsrStreamingEncoderAttention.forward :599-642).  qkv [B, cs, 3H] packed q | k | v, bias_u / bias_v
+ *                             [H], pos [W, H] = relative_k_proj of the W = lc cs + 2 cs - 1 sinusoid rows of the distances
+ *                             lc cs + cs - 1 .. -(cs - 1) (the same on every step), k_cache / v_cache [B, lc + 1, cs, H] rings (the chunk
+ *                             of step s in slot s % (lc + 1)), out [B, cs, H].  Every query sees the min(s, lc) cs cached frames and the
+ *                             whole chunk: softmax(((q + u) K^T + (q + v) P[distance]^T) scale) V, the chunk's k / v stored.  One workgroup
+ *                             per (head, stream); dyn_stream_attn_lds_bytes of LDS (-1: bad sizes), over a CU's 160 KiB ->
+ *                             DYN_E_UNSUPPORTED.  D % 4 == 0.  lc = 0: no cached keys.
+ *   dyn_stream_convmod_k9     dyn_convmod_causal_k9_fwd with the padding cache of NemotronAsrStreamingEncoderCausalConv1dCacheLayer.update
+ *                             (:81-104, both branches of `shortfall`): state [2, B, 8, C] GLU frames, half counter & 1 read (the 8 frames
+ *                             left of the chunk), the last 8 frames of state + chunk written to the other half.  u [B, T, 2C] -> s [B, T, C].
+ *   dyn_stream_conv2d_first / dyn_stream_dwconv2d_s2_act   dyn_conv2d_first_causal_fwd / dyn_dwconv2d_s2_causal_fwd_act under
+ *                             NemotronAsrStreamingEncoderCausalConv2dCacheLayer.update (:125-149): carry [2, B, F] / [2, B, F, C] holds the
+ *                             last input row of the previous chunk (before the ReLU), no padding on the right in time;
+ *                             `first` = 1 puts two zero rows in its place (`left_pad_init`).  To = (T + left - 3) / 2 + 1 with left = 1
+ *                             (first: 2), Fo = F / 2 + 1.  The new carry is written to the other half in the same launch.
+ *   dyn_rnnt_greedy_steps_chunk   dyn_rnnt_greedy_steps on the frames of one streamed chunk: `rebase` = 1 first points the frame pointer at
+ *                             frame 0, clears the done flags, the per-frame symbol counter and the chunk's output and step counts and
+ *                             keeps h / c, the projector cache, the last token and the emit flag; emitted frames are recorded as
+ *                             frame_base + the frame inside the chunk.
+ * Null pointers and sizes out of range -> DYN_E_ARG, a width that is not built -> DYN_E_UNSUPPORTED, all before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int dyn_stream_advance(int32_t* counter, void* stream);
+int64_t dyn_stream_attn_lds_bytes(int64_t cs, int64_t lc, int64_t D);
+int dyn_stream_attn(const float* qkv, const float* bias_u, const float* bias_v, const float* pos, float* k_cache, float* v_cache,
+                    const int32_t* counter, float* out, int64_t B, int64_t cs, int64_t lc, int64_t nh, int64_t D, float scale, void* stream);
+int dyn_stream_convmod_k9(const float* u, const float* w, const float* cbias, const float* gamma, const float* beta, float* state,
+                          const int32_t* counter, float* s, int64_t B, int64_t T, int64_t C, int64_t KW, float eps, void* stream);
+int dyn_stream_conv2d_first(const float* x, const float* w, const float* bias, float* carry, const int32_t* counter, float* z, int64_t B,
+                            int64_t T, int64_t F, int64_t C, int32_t first, void* stream);
+int dyn_stream_dwconv2d_s2_act(const float* z, const float* w, const float* bias, float* carry, const int32_t* counter, float* u, int64_t B,
+                               int64_t T, int64_t F, int64_t C, int32_t act, int32_t first, void* stream);
+int dyn_rnnt_greedy_steps_chunk(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs, const float* proj_w,
+                                const float* proj_b, const float* head_w, const float* head_b, int32_t* istate, float* h, float* c,
+                                float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd,
+                                int64_t layers, int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max, int64_t max_steps,
+                                int32_t n_steps, int64_t frame_base, int32_t rebase, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
