@@ -34,12 +34,12 @@ Refused by name before any launch: `attention_mask`; `use_cache`, `past_key_valu
 belong to a session);
 `subsampling_factor` != 8, subsampling kernel != 3, stride != 2, `conv_kernel_size` != 9, `hidden_act` != "silu", a joint activation
 other than relu, `hidden_size` outside 256 / 512 / 768 / 1024; a negative or non-integer lookahead, `sliding_window` = 0, T' >
-`max_position_embeddings`; the `model_type` of any Parakeet head; `sigma`; batch_renorm_training() (there is no batch norm); and what
+`max_position_embeddings`; the `model_type` of any Parakeet head and "nemotron3_5_asr" (the multilingual sibling with a language-prompt
+projector: nemotron3_5_asr_model.py builds it on this class); `sigma`; batch_renorm_training() (there is no batch norm); and what
 the parents refuse of the head.
 Out of scope: gradients through a streaming session; ragged batches and rows that join or leave a session; a waveform front end; hipGraph
 replay of the offline calls and lockstep groups; the decode inside the captured streaming step;
-skipping fully masked tiles in the score and context GEMMs (the band is exploited in the position product and the softmax only);
-`Nemotron3_5AsrForRNNT`.  No hub checkpoint is on the machine: transformers' class on the CPU with the same random state dict is the
+skipping fully masked tiles in the score and context GEMMs (the band is exploited in the position product and the softmax only).  No hub checkpoint is on the machine: transformers' class on the CPU with the same random state dict is the
 oracle in the tests."""
 import torch
 
@@ -84,6 +84,9 @@ def make_config(cfg=None):
         if mt in PARAKEET_TYPES or get("durations") is not None:
             raise ops.DynError(f"model_type={mt!r} is a Parakeet configuration, not built by this module (NemotronAsrStreamingForRNNT): "
                                "parakeet_model / parakeet_tdt_model / parakeet_rnnt_model build those")
+        if mt == "nemotron3_5_asr":
+            raise ops.DynError("model_type=\"nemotron3_5_asr\" (Nemotron3_5AsrForRNNT: this encoder and head with a language-prompt projector "
+                               "in between) is not built by this module: nemotron3_5_asr_model.Nemotron3_5AsrForRNNT builds it")
         if mt is not None and mt != "nemotron_asr_streaming":
             raise ops.DynError(f"model_type={mt!r} is not a NemotronAsrStreamingForRNNT configuration (\"nemotron_asr_streaming\")")
     return TM.head_config(cfg, DEFAULT_HEAD, encoder_config)

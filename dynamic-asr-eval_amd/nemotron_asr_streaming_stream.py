@@ -163,9 +163,14 @@ class StreamSession:
             ops.linear(a, P[pw2 + ".weight"], P.get(pw2 + ".bias"), out=x, beta=1.0)
             x, _ = m._ffn_fwd(x, p, "ffn2", False)
             x, _, _ = ops.layernorm(x, P[p + "final_layer_norm.weight"], P[p + "final_layer_norm.bias"], m._layer_eps)
-        enc = ops.linear(x, P[TM.PROJ + "weight"], P[TM.PROJ + "bias"])
+        enc = self._project(x)
         ops.stream_advance(cnt)
         return enc
+
+    def _project(self, x):
+        """The chunk's last hidden states -> the projected states: the model's _project_enc (a session with state of its own between the
+        encoder and the projector overrides this)."""
+        return self.model._project_enc(x, False)[0]
 
     def _encode(self, feats, attention_mask=None):
         """The step of one chunk -> enc [B, cs, Hd]; under graph=True the captured step's own output buffer (valid until the next chunk)."""
@@ -226,20 +231,21 @@ def split_chunks(session, input_features):
     return [input_features[:, :a]] + [input_features[:, s:s + b] for s in range(a, T, b)]
 
 
-def generate_streaming(model, input_features, num_lookahead_tokens=None, graph=False):
+def generate_streaming(model, input_features, num_lookahead_tokens=None, graph=False, **session_kw):
     """The greedy decode of a whole stream, chunk by chunk: `input_features` [B, T, F] (T = first_chunk_frames + k * chunk_frames) or an
-    iterable of chunks -> generate()'s fields, concatenated over the chunks (frames are absolute encoder frames)."""
+    iterable of chunks -> generate()'s fields, concatenated over the chunks (frames are absolute encoder frames).  `session_kw`: what
+    the model's stream() takes beyond these (nemotron3_5_asr_model.py: prompt_ids)."""
     chunks = input_features
     if isinstance(input_features, torch.Tensor):
         if input_features.dim() != 3:
             raise ops.DynError("generate_streaming: input_features must be [B, T, num_mel_bins] or an iterable of chunks")
-        session = model.stream(input_features.shape[0], num_lookahead_tokens, graph)
+        session = model.stream(input_features.shape[0], num_lookahead_tokens, graph, **session_kw)
         chunks = split_chunks(session, input_features)
     else:
         chunks = list(chunks)
         if not chunks or not isinstance(chunks[0], torch.Tensor) or chunks[0].dim() != 3:
             raise ops.DynError("generate_streaming: input_features must be [B, T, num_mel_bins] or an iterable of chunks [B, frames, num_mel_bins]")
-        session = model.stream(chunks[0].shape[0], num_lookahead_tokens, graph)
+        session = model.stream(chunks[0].shape[0], num_lookahead_tokens, graph, **session_kw)
     outs = [session.push(ch) for ch in chunks]
     session.close()
     B, n_max, dev = session.B, session.cap, model.device

@@ -2804,3 +2804,86 @@ def rnnt_greedy_steps_chunk(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w
                                            state.tokens.data_ptr(), state.frames.data_ptr(), B, T, Hd, layers, V1, int(blank), int(max_symbols),
                                            state.n_max, int(max_steps), int(n_steps), int(frame_base), int(bool(rebase)), _stream()),
           "dyn_rnnt_greedy_steps_chunk")
+
+
+# ----------------------------------------------------------------------------------------------- Nemotron3_5AsrForRNNT, language-prompt fusion
+def host_prompt_ids(prompt_ids, B, num_prompts, default, what="prompt_ids"):
+    """Pure host function: None (`default` for every row), one int (broadcast), or an integer tensor / list [B] -> a list of B ints, every
+    one inside [0, num_prompts).  A wrong length, a non-integer or an id outside the table is a DynError before any launch."""
+    p = default if prompt_ids is None else prompt_ids
+    if isinstance(p, bool):
+        raise DynError(f"{what}={p!r} must be an integer, or an integer tensor or list [{B}]")
+    if isinstance(p, int):
+        ids = [p] * B
+    else:
+        t = torch.as_tensor(p).detach().cpu()
+        if t.dim() != 1 or t.dtype not in (torch.int32, torch.int64) or t.numel() != B:
+            raise DynError(f"{what} must be one integer or an integer tensor or list [{B}], one language per row; got {tuple(t.shape)} {t.dtype}")
+        ids = [int(v) for v in t.tolist()]
+    if any(not 0 <= v < num_prompts for v in ids):
+        raise DynError(f"{what}={ids}: every id must lie in [0, {num_prompts}) (num_prompts)")
+    return ids
+
+
+def _prompt_ids(ids, B, who):
+    _c(ids, who + ".prompt_ids", I32)
+    if ids.dim() != 1 or ids.numel() != B:
+        raise DynError(f"{who}: prompt_ids must be int32 [{B}]")
+    return ids
+
+
+def prompt_bias_gather(b1, w1p, prompt_ids, out=None):
+    """pb [B, I] = b1 [I] + the column p_b of w1p [I, Np] for every batch row: the language prompt as a per-row bias of linear_1.
+    prompt_ids int32 [B] on the device, read when the kernel runs (validated by the caller: host_prompt_ids; the kernel clamps)."""
+    _cc(b1, "prompt_bias_gather.b1"); _cc(w1p, "prompt_bias_gather.w1p")
+    I = b1.numel()
+    if w1p.dim() != 2 or w1p.shape[0] != I or I % 4:
+        raise DynError(f"prompt_bias_gather: w1p {tuple(w1p.shape)} must be [I, num_prompts] with I = {I} a multiple of 4")
+    B = prompt_ids.numel()
+    _prompt_ids(prompt_ids, B, "prompt_bias_gather")
+    out = torch.empty(B, I, device=b1.device, dtype=F32) if out is None else _cc(out, "prompt_bias_gather.out")
+    if tuple(out.shape) != (B, I):
+        raise DynError(f"prompt_bias_gather: out must be [{B}, {I}]")
+    check(_L().dyn_prompt_bias_gather(b1.data_ptr(), w1p.data_ptr(), prompt_ids.data_ptr(), out.data_ptr(), B, I, w1p.shape[1], _stream()),
+          "dyn_prompt_bias_gather")
+    return out
+
+
+def prompt_relu(z, pb, out=None):
+    """a [B, T, I] = max(z + pb[:, None, :], 0) in one pass; out may be z."""
+    _cc(z, "prompt_relu.z"); _cc(pb, "prompt_relu.pb")
+    if z.dim() != 3 or tuple(pb.shape) != (z.shape[0], z.shape[2]):
+        raise DynError(f"prompt_relu: z {tuple(z.shape)} must be [B, T, I] and pb {tuple(pb.shape)} [B, I]")
+    out = torch.empty_like(z) if out is None else _cc(out, "prompt_relu.out")
+    if out.shape != z.shape:
+        raise DynError("prompt_relu: out must have z's shape")
+    B, T, I = z.shape
+    check(_L().dyn_prompt_relu_fwd(z.data_ptr(), pb.data_ptr(), out.data_ptr(), B, T, I, _stream()), "dyn_prompt_relu_fwd")
+    return out
+
+
+def prompt_relu_bwd(a, da, prompt_ids, db1, dw1p, beta=1.0, out=None):
+    """Backward of prompt_relu and of the gather in one pass over (a, da) [B, T, I]: returns dz = da where a > 0, else 0 (out may be da);
+    db1 [I] = beta * db1 + the column sums of dz; dw1p [I, Np] column p = beta * old + the sums of the batch rows whose prompt is p, b
+    ascending (a column no row used: exactly beta * old).  db1 / dw1p None: frozen, that sum is skipped."""
+    _cc(a, "prompt_relu_bwd.a"); _cc(da, "prompt_relu_bwd.da")
+    if a.dim() != 3 or da.shape != a.shape:
+        raise DynError(f"prompt_relu_bwd: a {tuple(a.shape)} and da {tuple(da.shape)} must both be [B, T, I]")
+    B, T, I = a.shape
+    out = torch.empty_like(da) if out is None else _cc(out, "prompt_relu_bwd.out")
+    if out.shape != a.shape:
+        raise DynError("prompt_relu_bwd: out must have a's shape")
+    Np, ids_ptr, ws_ptr, ws_bytes = 1, 0, 0, 0
+    if db1 is not None or dw1p is not None:
+        ids_ptr = _prompt_ids(prompt_ids, B, "prompt_relu_bwd").data_ptr()
+        if db1 is not None and _cc(db1, "prompt_relu_bwd.db1").numel() != I:
+            raise DynError(f"prompt_relu_bwd: db1 must be [{I}]")
+        if dw1p is not None:
+            if _cc(dw1p, "prompt_relu_bwd.dw1p").dim() != 2 or dw1p.shape[0] != I:
+                raise DynError(f"prompt_relu_bwd: dw1p {tuple(dw1p.shape)} must be [{I}, num_prompts]")
+            Np = dw1p.shape[1]
+        ws = workspace(a.device)
+        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    check(_L().dyn_prompt_relu_bwd(a.data_ptr(), da.data_ptr(), out.data_ptr(), ids_ptr, _opt(db1, "db1"), _opt(dw1p, "dw1p"), beta, B, T, I, Np,
+                                   ws_ptr, ws_bytes, _stream()), "dyn_prompt_relu_bwd")
+    return out

@@ -207,13 +207,24 @@ class ParakeetForTDT(PM.ParakeetForCTC):
                              self.blank, cap, n)
 
     # ------------------------------------------------------------------ encoder
+    def _project_enc(self, x, save):
+        """The encoder's last hidden states x [B, T', H] -> (the projected states [B, T', Hd], what _project_enc_bwd needs besides x, or
+        None): `encoder_projector`.  A model with more between the encoder and the projector (nemotron3_5_asr_model.py) overrides the
+        pair; a streaming session calls it too.  (Not `_project`: that is the feature projection of the waveform models this family
+        inherits from.)"""
+        return ops.linear(x, self.P[PROJ + "weight"], self.P[PROJ + "bias"]), None
+
+    def _project_enc_bwd(self, de, ctx, cut):
+        """Backward of _project_enc from de [nb, T', Hd]: accumulates its parameters' gradients, returns dL/dx [nb, T', H]."""
+        return self._lin_bwd(de, cut(ctx["head"]), PROJ + "weight", PROJ + "bias")
+
     def _encode(self, h, ctx, vT, dims, v0):
-        P = self.P
         T = dims[2]
         x = self._layers_fwd(h, ctx, vT, self.position_table(T))
-        enc = ops.linear(x, P[PROJ + "weight"], P[PROJ + "bias"])
+        enc, kept = self._project_enc(x, ctx is not None)
         if ctx is not None:
             ctx["head"] = x
+            ctx["project"] = kept
             ctx["dims"] = dims
             ctx["valid"] = (v0, vT)
         self._ctx = ctx
@@ -470,7 +481,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
             full = torch.zeros(nb, T, Hd, device=self.device, dtype=torch.float32)
             full[:rows] = de
             de = full
-        dx = self._lin_bwd(de, cut(ctx["head"]), PROJ + "weight", PROJ + "bias")
+        dx = self._project_enc_bwd(de, ctx, cut)
         dh = self._layers_bwd(ctx, dx, nb, T, self.position_table(T), vT, cut)
         if not self._below_frozen():
             self._subsample_bwd(cut(ctx["sub"]), dh)

@@ -194,6 +194,10 @@ def load_pretrained_model(args, device):
         raise ops.DynError(f'{cfg_path}: model_type "nemotron_asr_streaming" is a transducer over log-mel features [B, T, num_mel_bins], not a '
                            'CTC model over waveforms: build nemotron_asr_streaming_model.NemotronAsrStreamingForRNNT and drive it with '
                            'parakeet_tdt_lib.dynamic_eval_transducer_loss')
+    if kind == 'nemotron3_5_asr':
+        raise ops.DynError(f'{cfg_path}: model_type "nemotron3_5_asr" is a transducer over log-mel features [B, T, num_mel_bins], not a '
+                           'CTC model over waveforms: build nemotron3_5_asr_model.Nemotron3_5AsrForRNNT (prompt_ids= or default_prompt_id '
+                           'choose the language) and drive it with parakeet_tdt_lib.dynamic_eval_transducer_loss')
     lang, adapter_sd, tokenizer = getattr(args, 'target_lang', '') or '', None, None
     if lang:
         if kind not in ('', 'wav2vec2') or not (args.checkpoint and os.path.isdir(args.checkpoint)):

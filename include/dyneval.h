@@ -1201,6 +1201,34 @@ int dyn_rnnt_greedy_steps_chunk(const float* enc, const int32_t* valid, const fl
                                 int64_t layers, int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max, int64_t max_steps,
                                 int32_t n_steps, int64_t frame_base, int32_t rebase, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Nemotron3_5AsrForRNNT, language-prompt fusion (transformers modeling_nemotron3_5_asr.py, Nemotron3_5AsrForRNNT.get_audio_features:
+ * `one_hot`, `expand`, `torch.cat`, Nemotron3_5AsrPromptProjector.forward's `linear_1` and `act`) and its autograd, csrc/prompt_fuse.hip.
+ * linear_1(cat([h, onehot(p_b)])) = h W1[:, :H]^T + (b1 + W1[:, H + p_b]): the K = H product stays on dyn_gemm_f32 (z [B, T, I], no
+ * bias), the prompt is a per-batch-row bias.  w1p [I, Np] is the prompt block W1[:, H:] kept contiguous; prompt_ids int32 [B] in DEVICE
+ * memory, read when the kernels run.  The caller validates the ids against [0, Np); no kernel reads outside the table for any id: the
+ * gather CLAMPS an id into [0, Np - 1], the backward only compares ids with column numbers (an id outside the table adds to db1 alone).
+ *   dyn_prompt_bias_gather   pb[b, j] = b1[j] + w1p[j, p_b], pb [B, I].
+ *   dyn_prompt_relu_fwd      a[b, t, j] = max(z[b, t, j] + pb[b, j], 0) in one pass (a may be z): replaces the concat copy, the bias add
+ *                            and dyn_relu_fwd.  ReLU'(0) = 0 as dyn_relu_bwd.
+ *   dyn_prompt_relu_bwd      one pass over (a, da): dz = a > 0 ? da : 0 (dz may be da), per-(b, row tile) partial column sums in
+ *                            `workspace` (tiles of dyn_prompt_relu_bwd_row_tile(T) rows, summed in row order); then s[b, :] = the tiles
+ *                            of b in tile order, db1[j] = beta * db1[j] + sum_b s[b, j] (b ascending) and, for every p in 0 .. Np - 1,
+ *                            dw1p[j, p] = beta * dw1p[j, p] + sum over the b with p_b = p of s[b, j] (b ascending).  A column of a
+ *                            prompt no row used is exactly beta * old: zeros at beta = 0, untouched at beta = 1.  No float atomics,
+ *                            bit-reproducible; not deferrable (the segment sum is not dyn_reduce_defer's column sum).  db1 / dw1p may be
+ *                            null (frozen); with both null only dz is written and ids and workspace are not needed.  Replaces
+ *                            dyn_relu_bwd, dyn_colsum and a weight-gradient GEMM over a [rows, Np] one-hot.
+ * fp32, 16-byte aligned operands, I % 4 == 0, 1 <= B <= 65535, else DYN_E_ARG; a short workspace -> DYN_E_WORKSPACE; all before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int dyn_prompt_bias_gather(const float* b1, const float* w1p, const int32_t* prompt_ids, float* pb, int64_t B, int64_t I, int64_t Np,
+                           void* stream);
+int dyn_prompt_relu_fwd(const float* z, const float* pb, float* a, int64_t B, int64_t T, int64_t I, void* stream);
+int64_t dyn_prompt_relu_bwd_row_tile(int64_t T);
+int64_t dyn_prompt_relu_bwd_workspace_bytes(int64_t B, int64_t T, int64_t I);
+int dyn_prompt_relu_bwd(const float* a, const float* da, float* dz, const int32_t* prompt_ids, float* db1, float* dw1p, float beta, int64_t B,
+                        int64_t T, int64_t I, int64_t Np, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
