@@ -179,6 +179,7 @@ class EncDecSCConformerXL(SCConformerXL):
             enc = encoder_states if encoder_states is not None else self.forward(audio_signal)
             h = enc["hidden"][0]
             limit = max_tokens if max_tokens is not None else max(1, min(self.dec["dec_max_positions"] - 1, h.shape[0] // 2))
+            limit = min(int(limit), self.dec["dec_max_positions"] - 1)       # position t reads pos_table[t]: never past the table
             dc, P = self.dec, self.P
             dd, L = dc["dec_d_model"], dc["dec_layers"]
             if sample:

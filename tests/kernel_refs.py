@@ -3,7 +3,8 @@ operation's definition (no call into the torch op it mirrors).  tests/test_kerne
 op and autograd in float64 to 1e-12, so a wrong reference cannot hide a wrong kernel; tests/test_kernel_parity_f64_gpu.py compares the HIP
 kernels with them (the row softmax family: tests/test_row_kernels_gpu.py, on the device; the conformer's own convolutions, dtype- and
 device-agnostic: tests/test_conv_kernels_gpu.py; the log-mel front end and the window augmentations: tests/test_frontend_kernels_gpu.py;
-the fused streaming attention: tests/test_attention_kernels_gpu.py).
+the fused streaming attention: tests/test_attention_kernels_gpu.py; the one-token decoder steps, dtype-agnostic:
+tests/test_decoder_step_kernels_gpu.py, held to oracle/enc_dec_ref.py's decoder instead of a torch op).
 Also here: the inputs both files share, the tolerance rule, and CPU replays of the summation orders the column norm and the log-mel
 normalisation used before their statistics were made stable (E[x^2] - mean^2 from fp32 running sums)."""
 import math
@@ -979,3 +980,130 @@ def attention_split_fits(T, nsplit):
     """The host guard of dyn_attention_fwd_split: 1 <= nsplit <= 8 and the last split still has a key tile."""
     tiles = -(-T // 32)
     return 1 <= nsplit <= 8 and (nsplit == 1 or (nsplit - 1) * -(-tiles // nsplit) < tiles)
+
+
+# ----------------------------------------------------------------------------------------------------------- one-token decoder
+# csrc/decoder_step.hip (dyn_decoder_steps, dyn_decoder_steps_batch) from the definition of a pre-LN decoder layer
+# (tests/test_decoder_step_kernels_gpu.py).  Dtype-agnostic: the result has the dtype of `params`, so the same function on fp32 copies is the
+# "torch fp32" column of measured_tol.  The projected encoder keys | values are an INPUT: the key count is the caller's choice and no
+# encoder is needed.  tests/test_kernel_refs_cpu.py holds it to oracle.enc_dec_ref.Decoder in float64.
+# The 16 parameters of a layer in the pointer order of dyn_decoder_desc.layer_ptrs (slot 16 is the cache, slot 17 the projected kv).
+DECODER_LAYER_PARAMS = ("self.norm.weight", "self.norm.bias", "self.qkv.weight", "self.qkv.bias", "self.out.weight", "self.out.bias",
+                        "cross.norm.weight", "cross.norm.bias", "cross.q.weight", "cross.q.bias", "cross.out.weight", "cross.out.bias",
+                        "ff.norm.weight", "ff.norm.bias", "ff.w1.weight", "ff.w2.weight")
+DECODER_EPS = 1e-5
+
+
+def decoder_positions(n, d_model):
+    """The sinusoidal position rows [n, d_model]: sin in the even columns, cos in the odd ones, float64 rounded to fp32 once."""
+    pos = torch.arange(n, dtype=F64)[:, None]
+    inv = torch.exp(torch.arange(0, d_model, 2, dtype=F64) * (-math.log(10000.0) / d_model))
+    tab = torch.zeros(n, d_model, dtype=F64)
+    tab[:, 0::2] = torch.sin(pos * inv)
+    tab[:, 1::2] = torch.cos(pos * inv)
+    return tab.float()
+
+
+def decoder_params(d_model, d_ff, vocab, layers, max_positions, seed=0):
+    """fp32 CPU weights of one decoder, drawn as oracle.enc_dec_ref.EncDecRef draws them: matrices uniform / sqrt(fan_in) (embedding and
+    head times 3), norm weights 1 +- 0.05, biases +- 0.05.  Keys are the decoder's state-dict names, plus "pos" (the position table)."""
+    g = gen(31000 + seed)
+
+    def mat(o, i, gain=1.0):
+        return (torch.rand(o, i, generator=g) * 2 - 1) / math.sqrt(i) * gain
+
+    def vec(n, centre=0.0):
+        return centre + 0.1 * (torch.rand(n, generator=g) - 0.5)
+
+    shapes = {"self.qkv.weight": (3 * d_model, d_model), "self.out.weight": (d_model, d_model), "cross.q.weight": (d_model, d_model),
+              "cross.out.weight": (d_model, d_model), "ff.w1.weight": (d_ff, d_model), "ff.w2.weight": (d_model, d_ff)}
+    p = {"embed.weight": mat(vocab, d_model, 3.0), "pos": decoder_positions(max_positions, d_model)}
+    for l in range(layers):
+        for nm in DECODER_LAYER_PARAMS:
+            if nm in shapes:
+                p[f"layers.{l}.{nm}"] = mat(*shapes[nm])
+            elif nm.endswith("norm.weight"):
+                p[f"layers.{l}.{nm}"] = vec(d_model, 1.0)
+            elif nm.endswith("norm.bias"):
+                p[f"layers.{l}.{nm}"] = vec(d_model)
+            else:
+                p[f"layers.{l}.{nm}"] = vec(shapes[nm.replace("bias", "weight")][0])
+    p["norm_out.weight"], p["norm_out.bias"] = vec(d_model, 1.0), vec(d_model)
+    p["head.weight"], p["head.bias"] = mat(vocab, d_model, 3.0), vec(vocab)
+    return p
+
+
+def decoder_kv(layers, n_enc, d_model, seed=0, gain=1.0):
+    """Projected encoder keys | values [n_enc, 2 * d_model] per layer, fp32: N(0, 1) * gain."""
+    g = gen(32000 + seed + 13 * n_enc)
+    return [torch.randn(n_enc, 2 * d_model, generator=g) * gain for _ in range(layers)]
+
+
+def _decoder_norm(x, w, b, eps):
+    n = x.shape[-1]
+    mean = x.sum(-1, keepdim=True) / n
+    var = ((x - mean) ** 2).sum(-1, keepdim=True) / n
+    return (x - mean) / torch.sqrt(var + eps) * w + b
+
+
+def _decoder_attend(q, k, v, heads, causal):
+    """softmax(q k^T / sqrt(hd)) v per head, rows of q against rows of k / v; `causal`: query i sees keys 0 .. i.  [S, d] -> [S, d]."""
+    S, dd = q.shape
+    hd = dd // heads
+    q, k, v = (t.reshape(t.shape[0], heads, hd).permute(1, 0, 2) for t in (q, k, v))
+    s = (q @ k.transpose(-1, -2)) / math.sqrt(hd)
+    if causal:
+        i = torch.arange(S)
+        s = s.masked_fill(i[None, :] > i[:, None], float("-inf"))
+    e = torch.exp(s - s.max(-1, keepdim=True).values)
+    p = e / e.sum(-1, keepdim=True)
+    return (p @ v).permute(1, 0, 2).reshape(S, dd)
+
+
+def decoder_split_maxima(q, k, heads, nsplit=4):
+    """Score maxima [heads, nsplit] of ONE query row q [d] against keys k [n, d], the keys cut into `nsplit` chunks of ceil(n / nsplit) as
+    dec_attn_kernel cuts them (an empty chunk: -inf).  float64."""
+    q, k = d(q), d(k)
+    n, dd = k.shape
+    hd = dd // heads
+    s = torch.einsum("hc,nhc->hn", q.view(heads, hd), k.view(n, heads, hd)) / math.sqrt(hd)
+    chunk = -(-n // nsplit)
+    out = torch.full((heads, nsplit), float("-inf"), dtype=F64)
+    for u in range(nsplit):
+        if u * chunk < n:
+            out[:, u] = s[:, u * chunk:(u + 1) * chunk].max(-1).values
+    return out
+
+
+def decoder_steps_ref(params, tokens, kv_per_layer, heads, eps, cross_q=None):
+    """Positions 0 .. S - 1 of the decoder on the token ids `tokens` [S], all at once (the causal mask is the prefix each one-token step
+    sees): x = embed[token] + pos; per layer x += out(selfattn(LN x)), x += out(crossattn(q(LN x), kv)), x += w2 SiLU(w1 LN x);
+    logits = head(LN x).  `kv_per_layer`: the already-projected encoder keys | values [n_enc, 2 * d_model] of every layer.
+    `cross_q`: a list that receives every layer's cross-attention queries [S, d_model] (for assertions on a case's scores).
+    Returns (logits [S, V], [per layer: the packed q | k | v rows [S, 3 * d_model], what the kernel leaves in its cache])."""
+    P = params
+    tok = torch.as_tensor(tokens, dtype=torch.long)
+    S = tok.numel()
+    x = P["embed.weight"][tok] + P["pos"][:S]
+    dd = x.shape[1]
+    rows = []
+    for l, kv in enumerate(kv_per_layer):
+        L = lambda nm: P[f"layers.{l}.{nm}"]                                   # noqa: E731
+        qkv = _decoder_norm(x, L("self.norm.weight"), L("self.norm.bias"), eps) @ L("self.qkv.weight").T + L("self.qkv.bias")
+        rows.append(qkv)
+        o = _decoder_attend(qkv[:, :dd], qkv[:, dd:2 * dd], qkv[:, 2 * dd:], heads, True)
+        x = x + o @ L("self.out.weight").T + L("self.out.bias")
+        q2 = _decoder_norm(x, L("cross.norm.weight"), L("cross.norm.bias"), eps) @ L("cross.q.weight").T + L("cross.q.bias")
+        if cross_q is not None:
+            cross_q.append(q2)
+        o = _decoder_attend(q2, kv[:, :dd], kv[:, dd:], heads, False)
+        x = x + o @ L("cross.out.weight").T + L("cross.out.bias")
+        a = _decoder_norm(x, L("ff.norm.weight"), L("ff.norm.bias"), eps) @ L("ff.w1.weight").T
+        x = x + silu_expr(a) @ L("ff.w2.weight").T
+    return _decoder_norm(x, P["norm_out.weight"], P["norm_out.bias"], eps) @ P["head.weight"].T + P["head.bias"], rows
+
+
+def decoder_tol(torch_fp32, ref64):
+    """measured_tol with the floor the project asserts for these logits and cache rows (2e-5 absolute at O(1) values,
+    test_one_token_decoder_kernels_match_the_tile_kernel_path), taken relative to the largest wanted value once that exceeds 1."""
+    return measured_tol(torch_fp32, ref64, 2e-5 * max(1.0, ref64.abs().max().item()))

@@ -216,6 +216,28 @@ def test_one_token_decoder_kernels_match_the_tile_kernel_path(cuda, dec):
         _lib.check(_lib.load().dyn_decoder_steps(ctypes.byref(desc), 0, 1, 1, 0.0, 0, 0, 0), "dyn_decoder_steps")
 
 
+@pytest.mark.parametrize("fused", [True, False])
+def test_generate_clamps_max_tokens_to_the_position_table(cuda, fused):
+    """`generate(max_tokens=20)` on a decoder of 8 positions decodes positions 0 .. 6 only, as generate_batch does: at most 7 tokens, and
+    the tokens of `generate(max_tokens=7)`, on the one-token kernels and on the tile-kernel path.  Greedy and three sampled decodes at a
+    temperature that rarely draws eos; at least one of them runs to the cap, where the unclamped limit would have shown."""
+    from dynamic_asr_eval_amd.enc_dec import EncDecSCConformerXL
+    from dynamic_asr_eval_amd.synthetic_weights import init_synthetic
+    hip = EncDecSCConformerXL(dict(CFG, dec_max_positions=8), vocab_size=VOCAB + 3, device=cuda)
+    init_synthetic(hip, seed=21, blank_bias=1.0)
+    assert hip.fused_decode and hip.pos_table.shape[0] == 8
+    hip.fused_decode = fused
+    x = torch.randn(1, 80, 640, generator=torch.Generator().manual_seed(9)).to(cuda)
+    enc = hip.forward(x)
+    longest = 0
+    for kw in [dict()] + [dict(sample=True, temperature=4.0, seed=s) for s in (1, 2, 3)]:
+        got = hip.generate(x, encoder_states=enc, max_tokens=20, **kw)["text_sequence"]
+        want = hip.generate(x, encoder_states=enc, max_tokens=7, **kw)["text_sequence"]
+        assert len(got) <= 7 and got == want, (kw, got, want)
+        longest = max(longest, len(got))
+    assert longest == 7, "fixture: no decode reached the cap"
+
+
 def test_decoder_dropout_forward_and_every_gradient(cuda):
     """The three decoder dropout knobs (`dropout_emb`, `dropout_post_ff` -> ff_out_dropout, `dropout_attn` -> layer[0].fn.dropout_p;
     reference lcasr/lib.py:1511-1525,1636-1637) in training mode: loss and every gradient vs autograd with the same masks; in eval

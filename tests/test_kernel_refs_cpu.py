@@ -618,3 +618,86 @@ def test_attention_underflow_inputs_keep_their_lse_gap():
     assert float(gap.min()) > K.ATTN_UNDERFLOW_GAP and not torch.exp(-gap.float()).any()
     assert K.attention_split_fits(1024, 7) and K.attention_split_fits(1024, 8) and not K.attention_split_fits(100, 8)
     assert not K.attention_split_fits(256, 9) and not K.attention_split_fits(256, 0)
+
+
+# ----------------------------------------------------------------------------------------------------------- one-token decoder
+def _oracle_decoder(heads, layers=2, d_model=256, mult=2, vocab=67, d_enc=48, n_enc=11, seed=0):
+    """oracle.enc_dec_ref.Decoder in float64 carrying kernel_refs.decoder_params' weights; returns (decoder, params, mem)."""
+    ROOT = os.path.dirname(HERE)
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from oracle.enc_dec_ref import Decoder
+    dc = dict(dec_d_model=d_model, dec_layers=layers, dec_heads=heads, dec_ff_mult=mult, dec_max_positions=16)
+    dec = Decoder(dc, d_enc, vocab).double()
+    params = {k: v.double() for k, v in K.decoder_params(d_model, d_model * mult, vocab, layers, 16, seed).items()}
+    g = K.gen(40 + seed)
+    with torch.no_grad():
+        for name, p in dec.named_parameters():
+            if name in params:
+                p.copy_(params[name])
+            else:
+                assert name.endswith(("cross.kv.weight", "cross.kv.bias")), name
+                p.copy_(torch.randn(p.shape, generator=g, dtype=F64) / math.sqrt(p.shape[-1]))
+    assert torch.equal(dec.pos.double(), params["pos"]), "the position table is the oracle's"
+    return dec, params, torch.randn(n_enc, d_enc, generator=g, dtype=F64)
+
+
+@pytest.mark.parametrize("heads", [1, 4, 64])
+def test_decoder_steps_ref_is_the_oracle_decoder(heads):
+    """decoder_steps_ref on kv = layer.cross.kv(mem) against oracle.enc_dec_ref.Decoder(...).double() on mem: the logits of every position
+    to 1e-12, and the packed q | k | v rows are the oracle's own qkv projection of each layer's input."""
+    dec, params, mem = _oracle_decoder(heads)
+    tokens = torch.randint(0, 67, (9,), generator=K.gen(5))
+    with torch.no_grad():
+        want = dec(tokens, mem)
+        kv = [l.cross.kv(mem) for l in dec.layers]
+        x = dec.embed.weight[tokens] + dec.pos[:9]
+        want_rows = []
+        for l in dec.layers:
+            want_rows.append(l.self.qkv(l.self.norm(x)))
+            x = l.ff(l.cross(l.self(x), mem))
+    cross_q = []
+    logits, rows = K.decoder_steps_ref(params, tokens, kv, heads, K.DECODER_EPS, cross_q=cross_q)
+    assert logits.dtype == F64 and logits.shape == (9, 67) and len(rows) == len(cross_q) == 2
+    _same(logits, want, "logits")
+    for got, w in zip(rows, want_rows):
+        _same(got, w, "cache rows")
+    # a prefix is what the one-token step sees: position t of a longer run does not depend on the tokens after it
+    short, short_rows = K.decoder_steps_ref(params, tokens[:4], kv, heads, K.DECODER_EPS)
+    _same(short, logits[:4], "prefix logits"); _same(short_rows[1], rows[1][:4], "prefix rows")
+
+
+def test_decoder_steps_ref_in_fp32_is_fp32_and_close():
+    """The same function on fp32 copies returns fp32 (the "torch fp32" column) within 1e-4 of float64; decoder_tol is 4 x that plus
+    2e-5 * max(1, max|want|)."""
+    _, params, mem = _oracle_decoder(4)
+    kv = K.decoder_kv(2, 37, 256)
+    tokens = [3, 66, 0, 17, 17, 41]
+    want, want_rows = K.decoder_steps_ref(params, tokens, [t.double() for t in kv], 4, K.DECODER_EPS)
+    got, got_rows = K.decoder_steps_ref({k: v.float() for k, v in params.items()}, tokens, kv, 4, K.DECODER_EPS)
+    assert got.dtype == torch.float32 and got_rows[0].dtype == torch.float32
+    e32 = K.max_err(got, want)
+    assert 0.0 < e32 < 1e-4 and K.max_err(got_rows[1], want_rows[1]) < 1e-4
+    tol, e = K.decoder_tol(got, want)
+    assert e == e32 and tol == 4.0 * e32 + 2e-5 * max(1.0, want.abs().max().item())
+
+
+def test_decoder_params_are_drawn_as_the_oracle_draws_them():
+    p = K.decoder_params(256, 512, 67, 1, 9, seed=2)
+    assert set(k.split(".", 2)[2] for k in p if k.startswith("layers.0.")) == set(K.DECODER_LAYER_PARAMS) and len(K.DECODER_LAYER_PARAMS) == 16
+    assert p["pos"].shape == (9, 256) and p["layers.0.ff.w1.weight"].shape == (512, 256) and p["layers.0.ff.w2.weight"].shape == (256, 512)
+    assert p["layers.0.self.qkv.weight"].abs().max() <= 1 / 16 and p["embed.weight"].abs().max() <= 3 / 16 and p["head.weight"].abs().max() > 1 / 16
+    for k, v in p.items():
+        if k.endswith("norm.weight") or k == "norm_out.weight":
+            assert (v - 1).abs().max() <= 0.05
+        elif v.dim() == 1:
+            assert v.abs().max() <= 0.05
+
+
+def test_decoder_split_maxima_cut_the_keys_as_the_kernel_does():
+    k = torch.zeros(5, 8)
+    k[:, 0] = torch.tensor([1.0, 2.0, 3.0, 4.0, 5.0])
+    q = torch.zeros(8)
+    q[0] = 2.0
+    m = K.decoder_split_maxima(q, k, 2)                      # chunk = 2: keys {0, 1}, {2, 3}, {4}, {}
+    assert m[0].tolist() == [2.0, 4.0, 5.0, float("-inf")] and m[1].tolist() == [0.0, 0.0, 0.0, float("-inf")]
