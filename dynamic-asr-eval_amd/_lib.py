@@ -62,6 +62,24 @@ class DecoderBatchDesc(ctypes.Structure):
 DEC_PTRS_PER_LAYER = 18
 
 
+class Seq2SeqDesc(ctypes.Structure):
+    """Mirror of dyn_seq2seq_desc (include/dyneval.h)."""
+    _fields_ = [
+        ("d_model", ctypes.c_int32), ("heads", ctypes.c_int32), ("d_ff", ctypes.c_int32), ("vocab", ctypes.c_int32),
+        ("layers", ctypes.c_int32), ("n_enc", ctypes.c_int32), ("max_positions", ctypes.c_int32), ("rows", ctypes.c_int32),
+        ("pad_id", ctypes.c_int32), ("eos_id", ctypes.c_int32), ("eps", ctypes.c_float), ("reserved_", ctypes.c_float),
+        ("embed", ctypes.c_void_p), ("pos_emb", ctypes.c_void_p), ("emb_ln_w", ctypes.c_void_p), ("emb_ln_b", ctypes.c_void_p),
+        ("norm_w", ctypes.c_void_p), ("norm_b", ctypes.c_void_p), ("head_w", ctypes.c_void_p), ("head_b", ctypes.c_void_p),
+        ("layer_ptrs", ctypes.POINTER(ctypes.c_void_p)),
+        ("tokens", ctypes.c_void_p), ("finished", ctypes.c_void_p), ("logits", ctypes.c_void_p), ("scratch", ctypes.c_void_p),
+        ("scratch_floats", ctypes.c_int64), ("token_stride", ctypes.c_int64), ("cache_stride", ctypes.c_int64),
+        ("cross_stride", ctypes.c_int64),
+    ]
+
+
+S2S_PTRS_PER_LAYER = 20
+
+
 def load():
     """Load the shared library once; raise loudly when it has not been built."""
     global _lib
@@ -124,7 +142,8 @@ def prototypes():
             if "*" in a:
                 argtypes.append(ctypes.POINTER(GemmDesc) if "dyn_gemm_desc" in a else
                                 ctypes.POINTER(DecoderDesc) if "dyn_decoder_desc" in a else
-                                ctypes.POINTER(DecoderBatchDesc) if "dyn_decoder_batch_desc" in a else ctypes.c_void_p)
+                                ctypes.POINTER(DecoderBatchDesc) if "dyn_decoder_batch_desc" in a else
+                                ctypes.POINTER(Seq2SeqDesc) if "dyn_seq2seq_desc" in a else ctypes.c_void_p)
             else:
                 argtypes.append(_CTYPES[a.replace("const ", "").split()[0]])
         protos[name] = (restype, argtypes)

@@ -198,6 +198,10 @@ def load_pretrained_model(args, device):
         raise ops.DynError(f'{cfg_path}: model_type "nemotron3_5_asr" is a transducer over log-mel features [B, T, num_mel_bins], not a '
                            'CTC model over waveforms: build nemotron3_5_asr_model.Nemotron3_5AsrForRNNT (prompt_ids= or default_prompt_id '
                            'choose the language) and drive it with parakeet_tdt_lib.dynamic_eval_transducer_loss')
+    if kind == 'cohere_asr':
+        raise ops.DynError(f'{cfg_path}: model_type "cohere_asr" is an attention encoder-decoder over log-mel features [B, T, num_mel_bins], not a '
+                           'CTC model over waveforms: build cohere_asr_model.CohereAsrForConditionalGeneration and drive it with '
+                           'cohere_asr_lib.dynamic_eval_seq2seq_loss')
     lang, adapter_sd, tokenizer = getattr(args, 'target_lang', '') or '', None, None
     if lang:
         if kind not in ('', 'wav2vec2') or not (args.checkpoint and os.path.isdir(args.checkpoint)):

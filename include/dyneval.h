@@ -441,6 +441,55 @@ int64_t dyn_decoder_row_scratch_floats(int64_t d_model, int64_t d_ff, int64_t he
 int dyn_decoder_steps_batch(const dyn_decoder_batch_desc* d, int32_t t0, int32_t n_steps, int32_t sample, float inv_temperature,
                             uint64_t seed, uint64_t step0, void* stream);
 
+/* The cached greedy decode of CohereAsrForConditionalGeneration.generate(do_sample=False) (transformers modeling_cohere_asr.py:
+ * CohereAsrDecoder.forward with past_key_values, CohereAsrDecoderLayer.forward, CohereAsrSelfAttention / CohereAsrCrossAttention,
+ * CohereAsrDecoderMLP, `proj_out`, and GenerationMixin's greedy loop: argmax, eos bookkeeping, pad fill) for `rows` (1 .. 8) sequences,
+ * one position per step for all of them, n_steps positions t0 .. t0 + n_steps - 1 per call, 10 * layers + 2 launches per position.
+ * Per position t and live row r: x = embedding_layernorm(embed[tokens[r][t]] + pos_emb[t]); per layer the pre-LN blocks
+ *   x += o(self-attention of q | k | v(input_layernorm(x)) over cache rows 0 .. t; row t is written here),
+ *   x += o(cross-attention of q(post_attention_layernorm(x)) over the row's n_enc precomputed keys | values),
+ *   x += fc2(relu(fc1(final_layernorm(x))));
+ * logits[r] = head(norm(x)); tokens[r][t + 1] = the first maximum.  A row that picks eos_id is marked in `finished`; a finished row
+ * (on entry or marked here) runs no work, writes no cache row and receives pad_id in every later slot.  For t + 1 < n_forced slot
+ * t + 1 already holds the forced prompt: it is left alone and the head is not run.
+ * Every row-times-matrix kernel reads each weight element once per position and applies it to all rows held in registers, K split over
+ * the four waves of a workgroup and merged in wave order (no atomics); row r's numbers do not depend on `rows` or on its neighbours.
+ * Row r lives at tokens + r * token_stride, layer cache + r * cache_stride, cross_kv + r * cross_stride, logits + r * vocab,
+ * scratch + r * dyn_seq2seq_row_scratch_floats(d_model, d_ff, heads).
+ * layer_ptrs: HOST array of layers * DYN_S2S_PTRS_PER_LAYER device pointers (16-byte aligned), per layer in this order:
+ *   input_layernorm.weight, .bias, self q | k | v weight [3d, d], bias [3d], self o_proj.weight [d, d], .bias,
+ *   post_attention_layernorm.weight, .bias, cross q_proj.weight [d, d], .bias, cross o_proj.weight [d, d], .bias,
+ *   final_layernorm.weight, .bias, fc1.weight [d_ff, d], .bias, fc2.weight [d, d_ff], .bias,
+ *   cache [>= t0 + n_steps rows, 3d] of row 0 (read / written), cross_kv [n_enc, 2d] of row 0 (keys | values).
+ * Limits: d_model and d_ff multiples of 256 up to 4096, head dim a power of two in 4 .. 256, t0 + n_steps <= max_positions, keys per
+ * attention <= 49152, token_stride > t0 + n_steps, cache_stride >= (t0 + n_steps) * 3 d, cross_stride >= n_enc * 2 d (both multiples
+ * of 4), scratch_floats >= rows * the per-row count.  DYN_E_ARG / DYN_E_UNSUPPORTED / DYN_E_WORKSPACE, nothing launched. */
+#define DYN_S2S_PTRS_PER_LAYER 20
+typedef struct {
+    int32_t d_model, heads, d_ff, vocab, layers, n_enc, max_positions, rows;
+    int32_t pad_id, eos_id;
+    float eps, reserved_;
+    const float* embed;        /* [vocab, d] */
+    const float* pos_emb;      /* [max_positions, d] */
+    const float* emb_ln_w;     /* embedding_layernorm */
+    const float* emb_ln_b;
+    const float* norm_w;       /* the final norm */
+    const float* norm_b;
+    const float* head_w;       /* proj_out [vocab, d] */
+    const float* head_b;
+    const void* const* layer_ptrs;
+    int32_t* tokens;           /* device; row r: >= t0 + n_steps + 1 entries, slot t0 (and the forced prompt) valid on entry */
+    int32_t* finished;         /* device [rows] */
+    float* logits;             /* device [rows, vocab]: the logits of the last position whose head ran */
+    float* scratch;
+    int64_t scratch_floats;
+    int64_t token_stride;      /* int32 entries between the token buffers of consecutive rows */
+    int64_t cache_stride;      /* floats between the self-attention caches of consecutive rows (every layer) */
+    int64_t cross_stride;      /* floats between the cross-attention keys | values of consecutive rows (every layer) */
+} dyn_seq2seq_desc;
+int64_t dyn_seq2seq_row_scratch_floats(int64_t d_model, int64_t d_ff, int64_t heads);
+int dyn_seq2seq_steps(const dyn_seq2seq_desc* d, int32_t t0, int32_t n_steps, int32_t n_forced, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * CTC.  dyn_ctc_greedy replaces GreedyCTCDecoder on a CPU copy of the posteriors (reference lcasr/lib.py:498,
  * 559,565; run_dynamic_eval_full.py:53,100): argmax over classes (first maximum), collapse repeats, drop `blank`.
