@@ -24,7 +24,8 @@ multiple of 256 or above 4096, tie_word_embeddings, attention_bias false, `atten
 num_beams > 1, and whatever parakeet_model.make_config refuses of the encoder.  That last includes the released encoder's
 hidden_size 1280: the package's FastConformer is built at 256 / 512 / 768 / 1024, so the released checkpoint itself does not load yet;
 the decoder and the step are built and measured at the released decoder size.  Out of scope: the waveform front end, sampling, beam search, ragged encoder
-lengths, hipGraph replay, lockstep groups, bf16.  No hub checkpoint is on the machine: transformers' CohereAsrForConditionalGeneration on
+lengths (since built: `input_lengths=` on encode / forward / generate, lengths[b] keys in row b's cross-attention; DESIGN.md, "Ragged
+batches"), hipGraph replay, lockstep groups, bf16.  No hub checkpoint is on the machine: transformers' CohereAsrForConditionalGeneration on
 the CPU with the same (random) state dict is the oracle in the tests."""
 import ctypes
 import math
@@ -255,23 +256,29 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
         self._ctx = ctx
         return SimpleNamespace(x=x, frames=T)
 
-    def encode(self, input_features):
-        """input_features [B, T, num_mel_bins] -> the encoder's last hidden states [B, T', H_enc].  In grad mode its activations are kept."""
+    def encode(self, input_features, input_lengths=None):
+        """input_features [B, T, num_mel_bins] -> the encoder's last hidden states [B, T', H_enc].  In grad mode its activations are kept.
+        `input_lengths` (ParakeetForCTC.forward): the valid frames per row of a ragged batch; head() and generate() given this call's
+        result find the rows' encoder frame counts themselves (else `enc_lengths=`): row b's cross-attention sees lengths[b] keys."""
         self._dec = None
-        return PM.ParakeetForCTC.forward(self, input_features, None).x
+        out = PM.ParakeetForCTC.forward(self, input_features, None, *(() if input_lengths is None else (input_lengths,)))
+        self._remember_lengths(out.x, out)
+        return out.x
 
     # ------------------------------------------------------------------ decoder, teacher-forced
     def _kv_view(self, kv, j):
         """Keys (j = 0) or values (j = 1) of a packed cross projection [B, T', 2d]."""
         return _attn.View(kv, j * self.d, 2 * self.d, kv.shape[-2] * 2 * self.d, self.hd)
 
-    def _attend(self, q, k, v, B, Tq, Tk, causal):
-        """softmax(q k^T / sqrt(hd)) v per head on Views -> (O [B, Tq, d], the probabilities [B, nh, Tq, Tk])."""
+    def _attend(self, q, k, v, B, Tq, Tk, causal, klens=None):
+        """softmax(q k^T / sqrt(hd)) v per head on Views -> (O [B, Tq, d], the probabilities [B, nh, Tq, Tk]).  `klens` (int32 [B] on the
+        device): row b has klens[b] keys, probability 0 past them (so the backward needs no mask: dS = P * (..) is 0 there, and with it
+        the padded keys' dk and dv)."""
         Pm = torch.empty(B, self.nh, Tq, Tk, device=self.device, dtype=torch.float32)
         _attn.scores(q, k, Pm, 1.0 / math.sqrt(self.hd))
         if causal:
             check(load().dyn_causal_mask(Pm.data_ptr(), B * self.nh, Tq, torch.cuda.current_stream().cuda_stream), "dyn_causal_mask")
-        ops.softmax(Pm, out=Pm)
+        ops.softmax(Pm, out=Pm, lens=klens)
         O = torch.empty(B, Tq, self.d, device=self.device, dtype=torch.float32)
         _attn.context(Pm, v, _attn.plain(O, self.hd))
         return O, Pm
@@ -293,8 +300,8 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
         x, m, r = ops.layernorm(e, P[DEC + "embedding_layernorm.weight"], P[DEC + "embedding_layernorm.bias"], LN_EPS)
         return x, (ids, e, m, r)
 
-    def _decoder_fwd(self, ids, mem, save):
-        """ids int64 host [B, S], mem [B, T', d] -> (logits [B, S, V], the saved activations or None)."""
+    def _decoder_fwd(self, ids, mem, save, klens=None):
+        """ids int64 host [B, S], mem [B, T', d] -> (logits [B, S, V], the saved activations or None); `klens`: the rows' valid frames of mem."""
         P, d, hd = self.P, self.d, self.hd
         B, S = ids.shape
         Tk = mem.shape[1]
@@ -311,7 +318,7 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
             n2, m2, r2 = ops.layernorm(x1, P[p + "post_attention_layernorm.weight"], P[p + "post_attention_layernorm.bias"], LN_EPS)
             q2 = ops.linear(n2, P[p + "encoder_attn.q_proj.weight"], P[p + "encoder_attn.q_proj.bias"])
             kv = ops.linear(mem, Wkv, bkv)
-            o2, P2 = self._attend(_attn.plain(q2, hd), self._kv_view(kv, 0), self._kv_view(kv, 1), B, S, Tk, False)
+            o2, P2 = self._attend(_attn.plain(q2, hd), self._kv_view(kv, 0), self._kv_view(kv, 1), B, S, Tk, False, klens)
             x2 = ops.linear(o2, P[p + "encoder_attn.o_proj.weight"], P[p + "encoder_attn.o_proj.bias"], beta=1.0, residual=x1)
             n3, m3, r3 = ops.layernorm(x2, P[p + "final_layernorm.weight"], P[p + "final_layernorm.bias"], LN_EPS)
             u = ops.linear(n3, P[p + "mlp.fc1.weight"], P[p + "mlp.fc1.bias"])
@@ -407,20 +414,24 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
             raise ops.DynError(f"{what}: ids must lie in [0, {self.V})" + (" or be -100" if allow_ignore else ""))
         return t.expand(rows, -1).contiguous()
 
-    def forward(self, input_features, decoder_input_ids=None, labels=None, n_active=None, attention_mask=None, decoder_attention_mask=None):
-        """The teacher-forced pass: input_features [B, T, num_mel_bins] float32 on the device, decoder_input_ids [n or 1, S] (one row: shared
+    def forward(self, input_features, decoder_input_ids=None, labels=None, n_active=None, attention_mask=None, decoder_attention_mask=None,
+                input_lengths=None):
+        """The teacher-forced pass (`input_lengths`: encode()): input_features [B, T, num_mel_bins] float32 on the device, decoder_input_ids [n or 1, S] (one row: shared
         by the batch), labels [same rows, S] with -100 for positions outside the loss; n = n_active (default B): the decoder runs on the
         first n rows.  `labels` without `decoder_input_ids` means shift_tokens_right(labels, pad, decoder_start).  Returns
         SimpleNamespace(logits [n, S, V], loss [1] or None, encoder_last_hidden_state [B, T', H_enc], frames = T').  In grad mode the
         loss's gradient is kept for backward()."""
         if attention_mask is not None or decoder_attention_mask is not None:
             raise ops.DynError("attention_mask / decoder_attention_mask are not built: every frame and every decoder position is taken as valid "
-                               "(ragged batches are out of scope)")
+                               "(a ragged batch passes input_lengths)")
         if decoder_input_ids is None and labels is None:
             raise ops.DynError("forward() needs decoder_input_ids [B or 1, S] or labels; generate() decodes without them")
-        return self.head(self.encode(input_features), decoder_input_ids, labels, n_active)
+        out = self.head(self.encode(input_features, input_lengths), decoder_input_ids, labels, n_active)
+        if input_lengths is not None:
+            out.lengths, out.lengths_device = self._enc_lengths[1:]
+        return out
 
-    def head(self, x, decoder_input_ids=None, labels=None, n_active=None):
+    def head(self, x, decoder_input_ids=None, labels=None, n_active=None, enc_lengths=None):
         """forward() behind the encoder: `decoder.proj`, the decoder and the loss on the first n_active rows of the encoder states x
         [B, T', H_enc] of the last encode() (the loop encodes all copies once, decodes the clean one and scores the others)."""
         if decoder_input_ids is None and labels is None:
@@ -439,10 +450,11 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
             raise ops.DynError(f"{S} decoder positions exceed max_position_embeddings={self.cfg['dec_max_positions']}")
         grad_mode = torch.is_grad_enabled() and self._ctx is not None
         P = self.P
+        klens = self._lengths_of(x, enc_lengths, nb)
         with ops.use_workspace(self._scratch()):
             xe = x[:nb].contiguous()
             mem = ops.linear(xe, P[DEC + "proj.weight"], P[DEC + "proj.bias"])
-            logits, saved = self._decoder_fwd(ids, mem, grad_mode)
+            logits, saved = self._decoder_fwd(ids, mem, grad_mode, klens)
             loss = dlogits = None
             if lab is not None:
                 count = int((lab != -100).sum())
@@ -499,9 +511,13 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
             full = torch.zeros(nb, T, dx.shape[-1], device=self.device, dtype=torch.float32)
             full[:rows] = dx
             dx = full
+        lens = ctx.get("lens")
+        if lens is not None:                             # a ragged batch: no gradient enters at a padded frame (decoder.proj's bias rows)
+            vT, lens = vT.cut(nb), lens[:, :nb]
+            dx = ops.mask_rows_lens(dx.contiguous(), lens[3])
         dh = self._layers_bwd(ctx, dx, nb, T, self.position_table(T), vT, cut)
         if not self._below_frozen():
-            self._subsample_bwd(cut(ctx["sub"]), dh)
+            self._subsample_bwd(cut(ctx["sub"]), dh, *(() if lens is None else (lens,)))
         return None
 
     # ------------------------------------------------------------------ greedy decode
@@ -532,10 +548,12 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
         return d, ptrs
 
     def generate(self, input_features=None, decoder_input_ids=None, max_new_tokens=64, encoder_hidden_states=None, do_sample=False, num_beams=1,
-                 attention_mask=None, decoder_attention_mask=None):
+                 attention_mask=None, decoder_attention_mask=None, input_lengths=None, enc_lengths=None):
         """Greedy decode of input_features [B, T, num_mel_bins] (or of encoder states `encoder_hidden_states` [B, T', H_enc]) -> int64 host
         tensor [B, P + n] as transformers' generate(do_sample=False): `decoder_input_ids` [B or 1, P] is the whole forced prompt, start
-        token included (None: the start token alone); a row that emitted eos is pad afterwards; cut at the longest row."""
+        token included (None: the start token alone); a row that emitted eos is pad afterwards; cut at the longest row.  A ragged batch:
+        `input_lengths` with input_features, `enc_lengths` with encoder_hidden_states; row b's step attends to its own encoder frames
+        (dyn_seq2seq_steps_len), so it emits what it emits decoded alone."""
         if do_sample or (num_beams is not None and int(num_beams) > 1):
             raise ops.DynError("do_sample / num_beams > 1 are not built: generate() is the greedy decode")
         if attention_mask is not None or decoder_attention_mask is not None:
@@ -546,10 +564,14 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
         with torch.no_grad():
             if encoder_hidden_states is None:
                 keep = self._ctx, self._dec
-                x = self.encode(input_features)
+                x = self.encode(input_features, input_lengths)
                 self._ctx, self._dec = keep
             else:
+                if input_lengths is not None:
+                    raise ops.DynError("generate(encoder_hidden_states=..., input_lengths=...): input_lengths counts feature frames; pass "
+                                       "enc_lengths with encoder states")
                 x = encoder_hidden_states
+            klens = self._lengths_of(x, enc_lengths, x.shape[0])
             x = x.detach().contiguous()
             B, Tk, _ = x.shape
             prompt = host_prompt(decoder_input_ids, B, self.start_token, self.V)
@@ -577,7 +599,10 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
                     t = 0
                     while t < cap:
                         n = min(self.greedy_chunk, cap - t)
-                        check(load().dyn_seq2seq_steps(ctypes.byref(desc), t, n, Pn, st), "dyn_seq2seq_steps")
+                        if klens is None:
+                            check(load().dyn_seq2seq_steps(ctypes.byref(desc), t, n, Pn, st), "dyn_seq2seq_steps")
+                        else:
+                            check(load().dyn_seq2seq_steps_len(ctypes.byref(desc), klens[r0:r0 + R].data_ptr(), t, n, Pn, st), "dyn_seq2seq_steps_len")
                         t += n
                         if t >= Pn and bool(finished.all()):             # the one host read of the chunk
                             break

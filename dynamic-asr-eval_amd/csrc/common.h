@@ -77,6 +77,9 @@ __device__ __forceinline__ int64_t valid_rows(const int32_t* valid, int64_t T) {
     return v < 0 ? 0 : (v < T ? v : T);
 }
 
+// The same for entry `i` of a count array (one count per batch entry of a ragged batch; i = 0: the scalar).
+__device__ __forceinline__ int64_t valid_rows(const int32_t* valid, int64_t i, int64_t T) { return valid_rows(valid ? valid + i : nullptr, T); }
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 __device__ __forceinline__ float silu_f(float x) { return x * sigmoidf_(x); }
 __device__ __forceinline__ float silu_grad(float x) {

@@ -175,15 +175,26 @@ __device__ __forceinline__ void load_w4(const float* __restrict__ w, int c0, flo
     for (int j = 0; j < 9; ++j) wk[j] = make_float4(w[(c0 + 0) * 9 + j], w[(c0 + 1) * 9 + j], w[(c0 + 2) * 9 + j], w[(c0 + 3) * 9 + j]);
 }
 
-template <int ACT>
+// LENS (a ragged batch, one frame count per batch entry): input rows t >= lens_in[b] read as zeros whatever they hold (the masked
+// activation of the stage before, its pointwise bias rows included) and output rows to >= lens_out[b] are written as zeros: the row masks
+// transformers applies after every Conv2d of the subsampling, folded into the stage that reads / writes the rows anyway.  The instances
+// without LENS are the code as it was.
+template <int ACT, bool LENS = false>
 __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_v4_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                                   const float* __restrict__ bias, float* __restrict__ u,
-                                                                  int64_t T, int F, int64_t To, int Fo, int C, int64_t rows) {
+                                                                  int64_t T, int F, int64_t To, int Fo, int C, int64_t rows,
+                                                                  const int32_t* __restrict__ lens_in = nullptr,
+                                                                  const int32_t* __restrict__ lens_out = nullptr) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * 4 + wv;     // (b, to) flattened
     if (row >= rows) return;
     const int64_t b = row / To, to = row % To;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int64_t Tin = LENS ? dyn::valid_rows(lens_in, b, T) : T;
+    if (LENS && to >= dyn::valid_rows(lens_out, b, To)) {
+        for (int64_t i = lane * 4; i < (int64_t)Fo * C; i += 256) *reinterpret_cast<float4*>(u + row * Fo * C + i) = zero;
+        return;
+    }
     for (int c0 = lane * 4; c0 < C; c0 += 256) {
         float4 wk[9];
         load_w4(w, c0, wk);
@@ -193,7 +204,7 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_v4_kernel(const float* __
 #pragma unroll
         for (int dt = 0; dt < 3; ++dt) {
             const int64_t t = 2 * to + dt - 1;
-            ok[dt] = t >= 0 && t < T;
+            ok[dt] = t >= 0 && t < Tin;
             zr[dt] = z + ((b * T + (ok[dt] ? t : 0)) * F) * C + c0;
         }
         float4 prev[3] = {zero, zero, zero};      // column 2*fo - 1 (f = -1 for fo = 0: padding)
@@ -220,13 +231,18 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_fwd_v4_kernel(const float* __
     }
 }
 
+// LENS: feature frames t >= lens[b] read as zeros whatever the caller left there (every output row is written; the stage that reads
+// them masks the rows past its own input length).
+template <bool LENS = false>
 __global__ __launch_bounds__(256) void conv2d_first_fwd_v4_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                    const float* __restrict__ bias, float* __restrict__ z,
-                                                                   int64_t T, int F, int64_t To, int Fo, int C, int64_t rows) {
+                                                                   int64_t T, int F, int64_t To, int Fo, int C, int64_t rows,
+                                                                   const int32_t* __restrict__ lens = nullptr) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * 4 + wv;
     if (row >= rows) return;
     const int64_t b = row / To, to = row % To;
+    const int64_t Tin = LENS ? dyn::valid_rows(lens, b, T) : T;
     for (int c0 = lane * 4; c0 < C; c0 += 256) {
         float4 wk[9];
         load_w4(w, c0, wk);
@@ -236,7 +252,7 @@ __global__ __launch_bounds__(256) void conv2d_first_fwd_v4_kernel(const float* _
 #pragma unroll
         for (int dt = 0; dt < 3; ++dt) {
             const int64_t t = 2 * to + dt - 1;
-            ok[dt] = t >= 0 && t < T;
+            ok[dt] = t >= 0 && t < Tin;
             xr[dt] = x + (b * T + (ok[dt] ? t : 0)) * F;
         }
         float prev[3] = {0.f, 0.f, 0.f};
@@ -264,20 +280,29 @@ __global__ __launch_bounds__(256) void conv2d_first_fwd_v4_kernel(const float* _
 __device__ __forceinline__ float4 silu_grad4(float4 v) { return make_float4(silu_grad(v.x), silu_grad(v.y), silu_grad(v.z), silu_grad(v.w)); }
 
 // dz row (b, t): every input element gathers the 1, 2 or 4 outputs it fed (parity of t and f decides which taps exist).
-template <int ACT>
+// LENS: dz rows t >= lens_in[b] are written as zeros (the forward read them as zeros) and du rows to >= lens_out[b] are not read (the
+// forward wrote zeros there, whatever the 1x1 conv behind it did with them).
+template <int ACT, bool LENS = false>
 __global__ __launch_bounds__(256) void dwconv2d_s2_dgrad_v4_kernel(const float* __restrict__ z, const float* __restrict__ w,
                                                                     const float* __restrict__ du, float* __restrict__ dz,
-                                                                    int64_t T, int F, int64_t To, int Fo, int C, int64_t rows) {
+                                                                    int64_t T, int F, int64_t To_, int Fo, int C, int64_t rows,
+                                                                    const int32_t* __restrict__ lens_in = nullptr,
+                                                                    const int32_t* __restrict__ lens_out = nullptr) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * 4 + wv;     // (b, t) flattened
     if (row >= rows) return;
     const int64_t b = row / T, t = row % T;
+    const int64_t To = LENS ? dyn::valid_rows(lens_out, b, To_) : To_;      // the output rows that carry a gradient
+    if (LENS && t >= dyn::valid_rows(lens_in, b, T)) {
+        for (int64_t i = lane * 4; i < (int64_t)F * C; i += 256) *reinterpret_cast<float4*>(dz + row * F * C + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
     for (int c0 = lane * 4; c0 < C; c0 += 256) {
         float4 wk[9];
         load_w4(w, c0, wk);
         const float* zr = z + (row * F) * C + c0;
         float* dr = dz + (row * F) * C + c0;
-        const float* gb = du + (b * To * Fo) * C + c0;
+        const float* gb = du + (b * To_ * Fo) * C + c0;
         for (int f = 0; f < F; ++f) {
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -303,11 +328,13 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_dgrad_v4_kernel(const float* 
 
 // weight gradient partials: one wave per tile of `per` output rows, sliding 3-column window like the forward; the four
 // waves of a workgroup are summed in wave order through LDS, so one partial row per WORKGROUP reaches the reducer.
-template <bool FIRST, int ACT = ACT_SILU>   // FIRST: the 1-channel first conv (input x [B, T, F], no activation); else depthwise with act(z)
+// LENS: input rows t >= lens_in[b] read as zeros, as the forward read them (g_out is zero past the output length already: the row mask
+// behind the stage, or the dgrad of the stage after it, wrote zeros there).
+template <bool FIRST, int ACT = ACT_SILU, bool LENS = false>   // FIRST: the 1-channel first conv (input x [B, T, F], no activation); else depthwise with act(z)
 __global__ __launch_bounds__(256) void conv2d_s2_wgrad_v4_kernel(const float* __restrict__ in, const float* __restrict__ g_out,
                                                                   float* __restrict__ partial_w, float* __restrict__ partial_b,
                                                                   int64_t T, int F, int64_t To, int Fo, int C, int64_t per,
-                                                                  int64_t chunks, int64_t tiles) {
+                                                                  int64_t chunks, int64_t tiles, const int32_t* __restrict__ lens_in = nullptr) {
     __shared__ float4 red[3][64][10];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t tile = (int64_t)blockIdx.x * 4 + wv;     // (b, chunk) flattened
@@ -315,6 +342,7 @@ __global__ __launch_bounds__(256) void conv2d_s2_wgrad_v4_kernel(const float* __
     const int64_t b = live ? tile / chunks : 0, to0 = live ? (tile % chunks) * per : 0;
     const int64_t to1 = live ? ((to0 + per < To) ? to0 + per : To) : 0;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int64_t Tin = LENS ? dyn::valid_rows(lens_in, b, T) : T;
     for (int cb = 0; cb < C; cb += 256) {
         const int c0 = cb + lane * 4;
         const bool cok = c0 < C;
@@ -327,7 +355,7 @@ __global__ __launch_bounds__(256) void conv2d_s2_wgrad_v4_kernel(const float* __
 #pragma unroll
             for (int dt = 0; dt < 3; ++dt) {
                 const int64_t t = 2 * to + dt - 1;
-                ok[dt] = t >= 0 && t < T;
+                ok[dt] = t >= 0 && t < Tin;
                 ir[dt] = FIRST ? in + (b * T + (ok[dt] ? t : 0)) * F : in + ((b * T + (ok[dt] ? t : 0)) * F) * C + c0;
             }
             const float* gr = g_out + ((b * To + to) * Fo) * C + c0;
@@ -767,8 +795,8 @@ extern "C" int dyn_conv2d_first_fwd(const float* x, const float* w, const float*
     const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1;
     if (C % 4 == 0 && (((uintptr_t)z | (uintptr_t)bias) & 15) == 0) {
         const int64_t rows = B * To;
-        hipLaunchKernelGGL(conv2d_first_fwd_v4_kernel, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, w, bias, z,
-                           T, (int)F, To, (int)Fo, (int)C, rows);
+        hipLaunchKernelGGL(conv2d_first_fwd_v4_kernel<false>, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, w, bias, z,
+                           T, (int)F, To, (int)Fo, (int)C, rows, (const int32_t*)nullptr);
         return dyn::check_launch("dyn_conv2d_first_fwd");
     }
     dim3 grid((unsigned)To, (unsigned)dyn::cdiv(C, 256), (unsigned)B);
@@ -794,9 +822,19 @@ extern "C" int64_t dyn_conv2d_wgrad_workspace_bytes(int64_t B, int64_t To, int64
     return tiles * C * 10 * (int64_t)sizeof(float);
 }
 
+static int conv2d_first_wgrad_impl(const float* x, const float* dz, float* dw, float* dbias, float beta, int64_t B, int64_t T, int64_t F,
+                                   int64_t C, const int32_t* lens, void* workspace, int64_t workspace_bytes, void* stream);
+
 extern "C" int dyn_conv2d_first_wgrad(const float* x, const float* dz, float* dw, float* dbias, float beta, int64_t B,
                                       int64_t T, int64_t F, int64_t C, void* workspace, int64_t workspace_bytes, void* stream) {
+    return conv2d_first_wgrad_impl(x, dz, dw, dbias, beta, B, T, F, C, nullptr, workspace, workspace_bytes, stream);
+}
+
+static int conv2d_first_wgrad_impl(const float* x, const float* dz, float* dw, float* dbias, float beta, int64_t B, int64_t T, int64_t F,
+                                   int64_t C, const int32_t* lens, void* workspace, int64_t workspace_bytes, void* stream) {
     DYN_REQUIRE(x && dz && dw && dbias && B >= 0 && T > 0 && F > 0 && C > 0, DYN_E_ARG, "dyn_conv2d_first_wgrad: bad arguments");
+    DYN_REQUIRE(!lens || (C % 4 == 0 && (((uintptr_t)dz) & 15) == 0), DYN_E_UNSUPPORTED,
+                "dyn_conv2d_first_wgrad_lens: needs C %% 4 == 0 and a 16-byte aligned dz (C=%lld)", (long long)C);
     if (B == 0) return DYN_OK;
     const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1;
     int64_t per;
@@ -807,8 +845,12 @@ extern "C" int dyn_conv2d_first_wgrad(const float* x, const float* dz, float* dw
     float* pb = pw + tiles * C * 9;
     hipStream_t st = (hipStream_t)stream;
     if (C % 4 == 0 && (((uintptr_t)dz) & 15) == 0) {
-        hipLaunchKernelGGL((conv2d_s2_wgrad_v4_kernel<true>), dim3((unsigned)dyn::cdiv(tiles, 4)), dim3(256), 0, st, x, dz, pw, pb, T, (int)F,
-                           To, (int)Fo, (int)C, per, chunks, tiles);
+        if (lens)
+            hipLaunchKernelGGL((conv2d_s2_wgrad_v4_kernel<true, ACT_SILU, true>), dim3((unsigned)dyn::cdiv(tiles, 4)), dim3(256), 0, st, x, dz, pw,
+                               pb, T, (int)F, To, (int)Fo, (int)C, per, chunks, tiles, lens);
+        else
+            hipLaunchKernelGGL((conv2d_s2_wgrad_v4_kernel<true, ACT_SILU, false>), dim3((unsigned)dyn::cdiv(tiles, 4)), dim3(256), 0, st, x, dz, pw,
+                               pb, T, (int)F, To, (int)Fo, (int)C, per, chunks, tiles, (const int32_t*)nullptr);
         dyn::ordered_before_launch(st);
         dyn::launch_reduce_partials_taps(pw, dw, dyn::cdiv(tiles, 4), C * 9, beta, (int)C, st);
         dyn::launch_reduce_partials(pb, dbias, dyn::cdiv(tiles, 4), C, beta, st);
@@ -887,8 +929,8 @@ int dwconv2d_s2_fwd_impl(const char* who, const float* z, const float* w, const 
     const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1;
     if (C % 4 == 0 && (((uintptr_t)z | (uintptr_t)u | (uintptr_t)bias) & 15) == 0) {
         const int64_t rows = B * To;
-        hipLaunchKernelGGL(dwconv2d_s2_fwd_v4_kernel<ACT>, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, w, bias, u,
-                           T, (int)F, To, (int)Fo, (int)C, rows);
+        hipLaunchKernelGGL((dwconv2d_s2_fwd_v4_kernel<ACT, false>), dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, w,
+                           bias, u, T, (int)F, To, (int)Fo, (int)C, rows, (const int32_t*)nullptr, (const int32_t*)nullptr);
         return dyn::check_launch(who);
     }
     dim3 grid((unsigned)To, (unsigned)dyn::cdiv(C, 256), (unsigned)B);
@@ -904,8 +946,8 @@ int dwconv2d_s2_dgrad_impl(const char* who, const float* z, const float* w, cons
     const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1;
     if (C % 4 == 0 && ((((uintptr_t)z) | ((uintptr_t)du) | ((uintptr_t)dz)) & 15) == 0) {
         const int64_t rows = B * T;
-        hipLaunchKernelGGL(dwconv2d_s2_dgrad_v4_kernel<ACT>, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, w, du, dz,
-                           T, (int)F, To, (int)Fo, (int)C, rows);
+        hipLaunchKernelGGL((dwconv2d_s2_dgrad_v4_kernel<ACT, false>), dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, z, w,
+                           du, dz, T, (int)F, To, (int)Fo, (int)C, rows, (const int32_t*)nullptr, (const int32_t*)nullptr);
         return dyn::check_launch(who);
     }
     dim3 grid((unsigned)T, (unsigned)dyn::cdiv(C, 256), (unsigned)B);
@@ -915,8 +957,10 @@ int dwconv2d_s2_dgrad_impl(const char* who, const float* z, const float* w, cons
 
 template <int ACT>
 int dwconv2d_s2_wgrad_impl(const char* who, const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B, int64_t T,
-                           int64_t F, int64_t C, void* workspace, int64_t workspace_bytes, void* stream) {
+                           int64_t F, int64_t C, void* workspace, int64_t workspace_bytes, void* stream, const int32_t* lens_in = nullptr) {
     DYN_REQUIRE(z && du && dw && dbias && B >= 0 && T > 0 && F > 0 && C > 0, DYN_E_ARG, "%s: bad arguments", who);
+    DYN_REQUIRE(!lens_in || (C % 4 == 0 && ((((uintptr_t)z) | ((uintptr_t)du)) & 15) == 0), DYN_E_UNSUPPORTED,
+                "%s: needs C %% 4 == 0 and 16-byte aligned operands (C=%lld)", who, (long long)C);
     if (B == 0) return DYN_OK;
     const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1;
     int64_t per;
@@ -927,8 +971,12 @@ int dwconv2d_s2_wgrad_impl(const char* who, const float* z, const float* du, flo
     float* pb = pw + tiles * C * 9;
     hipStream_t st = (hipStream_t)stream;
     if (v4) {
-        hipLaunchKernelGGL((conv2d_s2_wgrad_v4_kernel<false, ACT>), dim3((unsigned)dyn::cdiv(tiles, 4)), dim3(256), 0, st, z, du, pw, pb, T,
-                           (int)F, To, (int)Fo, (int)C, per, chunks, tiles);
+        if (lens_in)
+            hipLaunchKernelGGL((conv2d_s2_wgrad_v4_kernel<false, ACT, true>), dim3((unsigned)dyn::cdiv(tiles, 4)), dim3(256), 0, st, z, du, pw, pb,
+                               T, (int)F, To, (int)Fo, (int)C, per, chunks, tiles, lens_in);
+        else
+            hipLaunchKernelGGL((conv2d_s2_wgrad_v4_kernel<false, ACT, false>), dim3((unsigned)dyn::cdiv(tiles, 4)), dim3(256), 0, st, z, du, pw, pb,
+                               T, (int)F, To, (int)Fo, (int)C, per, chunks, tiles, (const int32_t*)nullptr);
         dyn::reduce_taps_or_defer(pw, dw, dyn::cdiv(tiles, 4), C * 9, beta, (int)C, st);
         dyn::reduce_or_defer(pb, dbias, dyn::cdiv(tiles, 4), C, beta, st);
         return dyn::check_launch(who);
@@ -980,4 +1028,100 @@ extern "C" int dyn_dwconv2d_s2_wgrad_act(const float* z, const float* du, float*
     return act == ACT_RELU
                ? dwconv2d_s2_wgrad_impl<ACT_RELU>("dyn_dwconv2d_s2_wgrad_act", z, du, dw, dbias, beta, B, T, F, C, workspace, workspace_bytes, stream)
                : dwconv2d_s2_wgrad_impl<ACT_SILU>("dyn_dwconv2d_s2_wgrad_act", z, du, dw, dbias, beta, B, T, F, C, workspace, workspace_bytes, stream);
+}
+
+// ---- ragged batches: one frame count per batch entry (include/dyneval.h) ----
+namespace {
+
+// x [B, T, W] in place: rows t >= lens[b] := 0.  One workgroup per row, grid (T, B).
+__global__ __launch_bounds__(256) void mask_rows_lens_kernel(float* __restrict__ x, int64_t T, int64_t W, const int32_t* __restrict__ lens) {
+    const int64_t t = blockIdx.x, b = blockIdx.y;
+    if (t < dyn::valid_rows(lens, b, T)) return;
+    float* r = x + (b * T + t) * W;
+    for (int64_t i = threadIdx.x; i < W; i += 256) r[i] = 0.f;
+}
+
+int check_lens_stage(const char* who, int64_t B, int64_t T, int64_t F, int64_t C, const void* a, const void* b, const void* c) {
+    DYN_REQUIRE(B >= 0 && T > 0 && F > 0 && C > 0 && B * T < (1ll << 31), DYN_E_ARG, "%s: bad sizes B=%lld T=%lld F=%lld C=%lld", who,
+                (long long)B, (long long)T, (long long)F, (long long)C);
+    DYN_REQUIRE(C % 4 == 0 && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0, DYN_E_UNSUPPORTED,
+                "%s: needs C %% 4 == 0 and 16-byte aligned operands (C=%lld)", who, (long long)C);
+    return DYN_OK;
+}
+
+template <int ACT>
+void launch_fwd_lens(const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T, int64_t F, int64_t C,
+                     const int32_t* lens_in, const int32_t* lens_out, hipStream_t st) {
+    const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1, rows = B * To;
+    hipLaunchKernelGGL((dwconv2d_s2_fwd_v4_kernel<ACT, true>), dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, st, z, w, bias, u, T, (int)F, To,
+                       (int)Fo, (int)C, rows, lens_in, lens_out);
+}
+
+template <int ACT>
+void launch_dgrad_lens(const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T, int64_t F, int64_t C,
+                       const int32_t* lens_in, const int32_t* lens_out, hipStream_t st) {
+    const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1, rows = B * T;
+    hipLaunchKernelGGL((dwconv2d_s2_dgrad_v4_kernel<ACT, true>), dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, st, z, w, du, dz, T, (int)F,
+                       To, (int)Fo, (int)C, rows, lens_in, lens_out);
+}
+
+}  // namespace
+
+extern "C" int dyn_conv2d_first_fwd_lens(const float* x, const float* w, const float* bias, float* z, int64_t B, int64_t T, int64_t F,
+                                         int64_t C, const int32_t* lens, void* stream) {
+    DYN_REQUIRE(x && w && bias && z && lens, DYN_E_ARG, "dyn_conv2d_first_fwd_lens: null pointer");
+    if (int rc = check_lens_stage("dyn_conv2d_first_fwd_lens", B, T, F, C, z, bias, nullptr)) return rc;
+    if (B == 0) return DYN_OK;
+    const int64_t To = (T - 1) / 2 + 1, Fo = (F - 1) / 2 + 1, rows = B * To;
+    hipLaunchKernelGGL(conv2d_first_fwd_v4_kernel<true>, dim3((unsigned)dyn::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, w, bias, z, T,
+                       (int)F, To, (int)Fo, (int)C, rows, lens);
+    return dyn::check_launch("dyn_conv2d_first_fwd_lens");
+}
+
+extern "C" int dyn_dwconv2d_s2_fwd_act_lens(const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T, int64_t F,
+                                            int64_t C, int32_t act, const int32_t* lens_in, const int32_t* lens_out, void* stream) {
+    DYN_REQUIRE(z && w && bias && u && lens_in && lens_out, DYN_E_ARG, "dyn_dwconv2d_s2_fwd_act_lens: null pointer");
+    if (int rc = check_act("dyn_dwconv2d_s2_fwd_act_lens", act)) return rc;
+    if (int rc = check_lens_stage("dyn_dwconv2d_s2_fwd_act_lens", B, T, F, C, z, u, bias)) return rc;
+    if (B == 0) return DYN_OK;
+    if (act == ACT_RELU) launch_fwd_lens<ACT_RELU>(z, w, bias, u, B, T, F, C, lens_in, lens_out, (hipStream_t)stream);
+    else launch_fwd_lens<ACT_SILU>(z, w, bias, u, B, T, F, C, lens_in, lens_out, (hipStream_t)stream);
+    return dyn::check_launch("dyn_dwconv2d_s2_fwd_act_lens");
+}
+
+extern "C" int dyn_dwconv2d_s2_dgrad_act_lens(const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T, int64_t F,
+                                              int64_t C, int32_t act, const int32_t* lens_in, const int32_t* lens_out, void* stream) {
+    DYN_REQUIRE(z && w && du && dz && lens_in && lens_out, DYN_E_ARG, "dyn_dwconv2d_s2_dgrad_act_lens: null pointer");
+    if (int rc = check_act("dyn_dwconv2d_s2_dgrad_act_lens", act)) return rc;
+    if (int rc = check_lens_stage("dyn_dwconv2d_s2_dgrad_act_lens", B, T, F, C, z, du, dz)) return rc;
+    if (B == 0) return DYN_OK;
+    if (act == ACT_RELU) launch_dgrad_lens<ACT_RELU>(z, w, du, dz, B, T, F, C, lens_in, lens_out, (hipStream_t)stream);
+    else launch_dgrad_lens<ACT_SILU>(z, w, du, dz, B, T, F, C, lens_in, lens_out, (hipStream_t)stream);
+    return dyn::check_launch("dyn_dwconv2d_s2_dgrad_act_lens");
+}
+
+extern "C" int dyn_mask_rows_lens(float* x, int64_t B, int64_t T, int64_t W, const int32_t* lens, void* stream) {
+    DYN_REQUIRE(x && lens, DYN_E_ARG, "dyn_mask_rows_lens: null pointer");
+    DYN_REQUIRE(B >= 0 && B < 65536 && T > 0 && T < (1ll << 31) && W > 0, DYN_E_ARG, "dyn_mask_rows_lens: bad sizes B=%lld T=%lld W=%lld",
+                (long long)B, (long long)T, (long long)W);
+    if (B == 0) return DYN_OK;
+    hipLaunchKernelGGL(mask_rows_lens_kernel, dim3((unsigned)T, (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, T, W, lens);
+    return dyn::check_launch("dyn_mask_rows_lens");
+}
+
+extern "C" int dyn_conv2d_first_wgrad_lens(const float* x, const float* dz, float* dw, float* dbias, float beta, int64_t B, int64_t T,
+                                           int64_t F, int64_t C, const int32_t* lens, void* workspace, int64_t workspace_bytes, void* stream) {
+    DYN_REQUIRE(lens, DYN_E_ARG, "dyn_conv2d_first_wgrad_lens: null pointer");
+    return conv2d_first_wgrad_impl(x, dz, dw, dbias, beta, B, T, F, C, lens, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dyn_dwconv2d_s2_wgrad_act_lens(const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B, int64_t T,
+                                              int64_t F, int64_t C, int32_t act, const int32_t* lens_in, void* workspace,
+                                              int64_t workspace_bytes, void* stream) {
+    DYN_REQUIRE(lens_in, DYN_E_ARG, "dyn_dwconv2d_s2_wgrad_act_lens: null pointer");
+    if (int rc = check_act("dyn_dwconv2d_s2_wgrad_act_lens", act)) return rc;
+    return act == ACT_RELU ? dwconv2d_s2_wgrad_impl<ACT_RELU>("dyn_dwconv2d_s2_wgrad_act_lens", z, du, dw, dbias, beta, B, T, F, C, workspace,
+                                                              workspace_bytes, stream, lens_in)
+                           : dwconv2d_s2_wgrad_impl<ACT_SILU>("dyn_dwconv2d_s2_wgrad_act_lens", z, du, dw, dbias, beta, B, T, F, C, workspace,
+                                                              workspace_bytes, stream, lens_in);
 }

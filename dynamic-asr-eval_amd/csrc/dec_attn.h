@@ -25,6 +25,9 @@ struct AttnArgs {
     // rows of a batched step (blockIdx.z): floats between rows of q / k and v / parts; a finished row does nothing
     int64_t s_q, s_kv, s_parts;
     const int32_t* finished;
+    // a ragged batch (null: every row has n_keys): row z attends to its first row_keys[z] keys, clamped into [1, n_keys]; the launch's
+    // LDS stays sized by n_keys.  Row z's splits are those of a launch with n_keys = row_keys[z]: the same chunks, the same bits.
+    const int32_t* row_keys;
 };
 
 // One query; workgroup (h, s) takes the s-th quarter of the keys of head h.  LDS: the split's scores, then 256 partial sums.
@@ -35,9 +38,11 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(const AttnArgs a) {
     const int hd = a.hd;
     const int64_t z = blockIdx.z;
     if (a.finished && a.finished[z] != 0) return;
-    const int chunk = (a.n_keys + NSPLIT - 1) / NSPLIT;
+    int n_keys = a.n_keys;
+    if (a.row_keys) n_keys = max(1, min(a.row_keys[z], n_keys));
+    const int chunk = (n_keys + NSPLIT - 1) / NSPLIT;
     const int j_lo = blockIdx.y * chunk;
-    const int n = min(chunk, a.n_keys - j_lo);       // keys of this split (<= 0: none)
+    const int n = min(chunk, n_keys - j_lo);         // keys of this split (<= 0: none)
     float* out = a.parts + z * a.s_parts + ((int64_t)h * NSPLIT + blockIdx.y) * (hd + 4);
     if (n <= 0) {
         if (tid < hd) out[tid] = 0.f;

@@ -18,12 +18,16 @@ constexpr int HB_MAX_CHUNKS = 512;
 
 // One workgroup per row, as softmax_fwd_kernel (nothing is shared between rows here, so a row block would only serialise them): the row of
 // x and the row's window of bd are read once into registers (ITEMS values per thread, coalesced stride-256 accesses), the result is written once.
-template <int ITEMS>
+// LENS (a ragged batch): `valid` holds one key count per batch entry and rows_per_len = nh * T rows share one; the instances without it
+// are the code as it was (the per-row division costs 2 - 8 VGPRs in the row loop, so it is not in them).
+template <int ITEMS, bool LENS = false>
 __global__ __launch_bounds__(TPB) void softmax_relshift_fwd_kernel(const float* x, float* y, const float* __restrict__ bd, int64_t rows, int T,
-                                                                    int64_t ld_bd, const int32_t* __restrict__ valid) {   // y may alias x
+                                                                    int64_t ld_bd, const int32_t* __restrict__ valid,
+                                                                    int64_t rows_per_len) {   // y may alias x
     __shared__ float red[16];
-    const int Lv = dyn::valid_len(valid, T);
+    const int Lv0 = dyn::valid_len(valid, T);
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int Lv = LENS ? dyn::valid_len_of_row(valid, row, rows_per_len, T) : Lv0;
         const int i = (int)(row % T);                          // query position inside its (batch, head)
         const float* xr = x + row * T;
         const float* br = bd + row * ld_bd + (T - 1 - i);      // the row's window: columns T-1-i .. 2T-2-i, inside [0, 2T-1)
@@ -111,9 +115,28 @@ extern "C" int dyn_softmax_relshift_fwd_len(const float* x, float* y, const floa
     const dim3 grid((unsigned)(rows < 65535 * 4 ? rows : 65535 * 4)), blk(TPB);
     hipStream_t st = (hipStream_t)stream;
     if (int rc = dyn::dispatch_items<dyn::MAX_ROW_FWD>("dyn_softmax_relshift_fwd_len", T, [&](auto I) {
-            hipLaunchKernelGGL((softmax_relshift_fwd_kernel<decltype(I)::value>), grid, blk, 0, st, x, y, bd, rows, (int)T, ld_bd, valid_cols);
+            hipLaunchKernelGGL((softmax_relshift_fwd_kernel<decltype(I)::value, false>), grid, blk, 0, st, x, y, bd, rows, (int)T, ld_bd, valid_cols,
+                               (int64_t)0);
         })) return rc;
     return dyn::check_launch("dyn_softmax_relshift_fwd_len");
+}
+
+// The ragged batch: x [B, nh, T, T], row m of the B * nh * T rows has lens[m / (nh * T)] keys (clamped into [1, T] by the kernel).
+extern "C" int dyn_softmax_relshift_fwd_lens(const float* x, float* y, const float* bd, int64_t B, int64_t nh, int64_t T, int64_t ld_bd,
+                                             const int32_t* lens, void* stream) {
+    DYN_REQUIRE(x && y && bd && lens, DYN_E_ARG, "dyn_softmax_relshift_fwd_lens: null pointer");
+    DYN_REQUIRE(B >= 0 && nh >= 1 && B * nh < (1ll << 31), DYN_E_ARG, "dyn_softmax_relshift_fwd_lens: bad sizes B=%lld nh=%lld", (long long)B,
+                (long long)nh);
+    if (int rc = check_scores("dyn_softmax_relshift_fwd_lens", B * nh, T, ld_bd)) return rc;
+    DYN_REQUIRE((const void*)y != (const void*)bd, DYN_E_ARG, "dyn_softmax_relshift_fwd_lens: the output may alias the scores, not BD");
+    if (B == 0) return DYN_OK;
+    const int64_t rows = B * nh * T;
+    const dim3 grid((unsigned)(rows < 65535 * 4 ? rows : 65535 * 4)), blk(TPB);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = dyn::dispatch_items<dyn::MAX_ROW_FWD>("dyn_softmax_relshift_fwd_lens", T, [&](auto I) {
+            hipLaunchKernelGGL((softmax_relshift_fwd_kernel<decltype(I)::value, true>), grid, blk, 0, st, x, y, bd, rows, (int)T, ld_bd, lens, nh * T);
+        })) return rc;
+    return dyn::check_launch("dyn_softmax_relshift_fwd_lens");
 }
 
 extern "C" int dyn_relshift_bwd(const float* dS, float* dBD, int64_t M, int64_t T, int64_t ld_bd, void* stream) {

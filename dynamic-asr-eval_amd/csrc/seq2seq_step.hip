@@ -289,8 +289,22 @@ extern "C" int64_t dyn_seq2seq_row_scratch_floats(int64_t d_model, int64_t d_ff,
     return row_scratch(d_model, d_ff, heads);
 }
 
+static int seq2seq_steps_impl(const char* who, const dyn_seq2seq_desc* d, const int32_t* enc_lens, int32_t t0, int32_t n_steps, int32_t n_forced,
+                              void* stream);
+
 extern "C" int dyn_seq2seq_steps(const dyn_seq2seq_desc* d, int32_t t0, int32_t n_steps, int32_t n_forced, void* stream) {
-    const char* who = "dyn_seq2seq_steps";
+    return seq2seq_steps_impl("dyn_seq2seq_steps", d, nullptr, t0, n_steps, n_forced, stream);
+}
+
+// The ragged batch: row r's cross-attention sees its first enc_lens[r] (device int32 [rows], clamped into [1, n_enc]) encoder keys.
+extern "C" int dyn_seq2seq_steps_len(const dyn_seq2seq_desc* d, const int32_t* enc_lens, int32_t t0, int32_t n_steps, int32_t n_forced,
+                                     void* stream) {
+    DYN_REQUIRE(enc_lens, DYN_E_ARG, "dyn_seq2seq_steps_len: null enc_lens");
+    return seq2seq_steps_impl("dyn_seq2seq_steps_len", d, enc_lens, t0, n_steps, n_forced, stream);
+}
+
+static int seq2seq_steps_impl(const char* who, const dyn_seq2seq_desc* d, const int32_t* enc_lens, int32_t t0, int32_t n_steps, int32_t n_forced,
+                              void* stream) {
     DYN_REQUIRE(d, DYN_E_ARG, "%s: null descriptor", who);
     DYN_REQUIRE(d->embed && d->pos_emb && d->emb_ln_w && d->emb_ln_b && d->norm_w && d->norm_b && d->head_w && d->head_b && d->layer_ptrs &&
                     d->tokens && d->finished && d->logits && d->scratch, DYN_E_ARG, "%s: null pointer in the descriptor", who);
@@ -358,7 +372,7 @@ extern "C" int dyn_seq2seq_steps(const dyn_seq2seq_desc* d, int32_t t0, int32_t 
             a = base(F(8), F(9), q2, S, dd);
             a.gamma = F(6); a.beta = F(7);
             launch<LNORM>(a, dd, st);
-            AttnArgs c{q2, ckv, ckv + dd, parts, d->n_enc, 2 * dd, hd, scale, S, d->cross_stride, S, d->finished};
+            AttnArgs c{q2, ckv, ckv + dd, parts, d->n_enc, 2 * dd, hd, scale, S, d->cross_stride, S, d->finished, enc_lens};
             hipLaunchKernelGGL(dec_attn_kernel, dim3(H, NSPLIT, R), dim3(256), (size_t)(dyn::cdiv(d->n_enc, NSPLIT) + 256) * sizeof(float), st, c);
             a = base(F(10), F(11), x, S, dd);
             a.parts = parts; a.hd = hd; a.res = x;

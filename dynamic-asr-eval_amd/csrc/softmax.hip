@@ -10,12 +10,16 @@ namespace {
 
 constexpr int TPB = dyn::ROW_TPB;
 
-template <int ITEMS, bool LOG>
+// LENS (a ragged batch): `valid` holds one key count per batch entry, rows_per_len rows share one (relshift.hip's per-row form); the
+// instances without it are the code as it was.
+template <int ITEMS, bool LOG, bool LENS = false>
 __global__ __launch_bounds__(TPB) void softmax_fwd_kernel(const float* x, float* y, int64_t rows, int L, int64_t ldx,
-                                                           int64_t ldy, const int32_t* __restrict__ valid) {  // y may alias x (in-place attention softmax)
+                                                           int64_t ldy, const int32_t* __restrict__ valid,
+                                                           int64_t rows_per_len = 0) {  // y may alias x (in-place attention softmax)
     __shared__ float red[8];
-    const int Lv = dyn::valid_len(valid, L);
+    const int Lv0 = dyn::valid_len(LENS ? nullptr : valid, L);
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int Lv = LENS ? dyn::valid_len_of_row(valid, row, rows_per_len, L) : Lv0;
         const float* xr = x + row * ldx;
         dyn::softmax_row<ITEMS, LOG>([xr](int c) { return xr[c]; }, y + row * ldy, L, Lv, red);
     }
@@ -85,7 +89,8 @@ dim3 row_grid(int64_t rows) { return dim3((unsigned)(rows < 65535 * 4 ? rows : 6
 template <bool LOG>
 int launch_fwd(const float* x, float* y, int64_t rows, int64_t L, int64_t ldx, int64_t ldy, hipStream_t st, const int32_t* valid = nullptr) {
     if (int rc = dyn::dispatch_items<dyn::MAX_ROW_FWD>("softmax", L, [&](auto I) {
-            hipLaunchKernelGGL((softmax_fwd_kernel<decltype(I)::value, LOG>), row_grid(rows), dim3(TPB), 0, st, x, y, rows, (int)L, ldx, ldy, valid);
+            hipLaunchKernelGGL((softmax_fwd_kernel<decltype(I)::value, LOG, false>), row_grid(rows), dim3(TPB), 0, st, x, y, rows, (int)L, ldx, ldy, valid,
+                               (int64_t)0);
         })) return rc;
     return dyn::check_launch("dyn_softmax_fwd");
 }
@@ -112,6 +117,20 @@ extern "C" int dyn_softmax_fwd_len(const float* x, float* y, int64_t rows, int64
     DYN_REQUIRE(x && y && valid_cols && rows >= 0 && L > 0 && ldx >= L && ldy >= L, DYN_E_ARG, "dyn_softmax_fwd_len: bad arguments");
     if (rows == 0) return DYN_OK;
     return launch_fwd<false>(x, y, rows, L, ldx, ldy, (hipStream_t)stream, valid_cols);
+}
+// The ragged batch: x [B, rows_per, L], every row of batch entry b has lens[b] keys (clamped into [1, L]); as dyn_softmax_relshift_fwd_lens.
+extern "C" int dyn_softmax_fwd_lens(const float* x, float* y, int64_t B, int64_t rows_per, int64_t L, int64_t ldx, int64_t ldy,
+                                    const int32_t* lens, void* stream) {
+    DYN_REQUIRE(x && y && lens && B >= 0 && rows_per >= 1 && L > 0 && ldx >= L && ldy >= L && B * rows_per < (1ll << 40), DYN_E_ARG,
+                "dyn_softmax_fwd_lens: bad arguments");
+    if (B == 0) return DYN_OK;
+    const int64_t rows = B * rows_per;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = dyn::dispatch_items<dyn::MAX_ROW_FWD>("dyn_softmax_fwd_lens", L, [&](auto I) {
+            hipLaunchKernelGGL((softmax_fwd_kernel<decltype(I)::value, false, true>), row_grid(rows), dim3(TPB), 0, st, x, y, rows, (int)L, ldx, ldy,
+                               lens, rows_per);
+        })) return rc;
+    return dyn::check_launch("dyn_softmax_fwd_lens");
 }
 extern "C" int dyn_softmax_bwd(const float* y, const float* dy, float* dx, int64_t rows, int64_t L, int64_t ld, float scale,
                                void* stream) {

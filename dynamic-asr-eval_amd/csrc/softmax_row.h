@@ -19,6 +19,11 @@ __device__ __forceinline__ int valid_len(const int32_t* __restrict__ valid, int 
     return Lv;
 }
 
+// The valid length of `row` when `valid` holds one count per batch entry and rows_per_len consecutive rows share one (a ragged batch).
+__device__ __forceinline__ int valid_len_of_row(const int32_t* __restrict__ valid, int64_t row, int64_t rows_per_len, int L) {
+    return valid_len(valid + row / rows_per_len, L);
+}
+
 // yr[0 .. L) = softmax (LOG: log-softmax) of load(0 .. Lv); columns in [Lv, L) are outside the max and the sum and written as 0 (-inf for
 // LOG).  The row is read ONCE into registers, max and sum are wavefront + LDS reductions (`red`: the block_max / block_sum scratch), the
 // result is written once.  The values of the first Lv columns are bit for bit those of a row of length Lv (same per-thread items, same

@@ -207,9 +207,12 @@ class LasrForCTC(PM.ParakeetForCTC):
         return t
 
     # ------------------------------------------------------------------ forward
-    def forward(self, input_features, attention_mask=None):
+    _ragged = False
+
+    def forward(self, input_features, attention_mask=None, input_lengths=None):
         """input_features [B, T, num_mel_bins] float32 on the device, T >= 13 -> SimpleNamespace(logits [B, T', V], frames = T'),
-        T' = frames(T).  Every row is valid: `attention_mask` is refused."""
+        T' = frames(T).  Every row is valid: `attention_mask` and `input_lengths` are refused."""
+        PM.refuse_input_lengths("LasrForCTC", input_lengths)
         if attention_mask is not None:
             raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (the reference loop passes whole windows)")
         x = input_features

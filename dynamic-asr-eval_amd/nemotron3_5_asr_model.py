@@ -186,8 +186,9 @@ class Nemotron3_5AsrForRNNT(NM.NemotronAsrStreamingForRNNT):
             if ids != self._ctx_prompts:
                 raise ops.DynError(f"{who}(prompt_ids={ids}) continues an encode that ran with prompt_ids={self._ctx_prompts}")
 
-    def encode(self, input_features, attention_mask=None, num_lookahead_tokens=None, prompt_ids=None, **caches):
+    def encode(self, input_features, attention_mask=None, num_lookahead_tokens=None, prompt_ids=None, input_lengths=None, **caches):
         """The parent's encode with the language of every row (`prompt_ids`: module docstring) fused in front of `encoder_projector`."""
+        NM.PM.refuse_input_lengths(type(self).__name__, input_lengths)
         self._refuse_caches(caches)
         x = input_features
         if isinstance(x, torch.Tensor) and x.dim() == 3 and x.shape[0] >= 1:      # anything else: the parent refuses it
@@ -198,8 +199,10 @@ class Nemotron3_5AsrForRNNT(NM.NemotronAsrStreamingForRNNT):
         return enc
 
     def forward(self, input_features, decoder_input_ids=None, labels=None, attention_mask=None, reduction=None, sigma=0.0, grad_scale=1.0,
-                n_active=None, label_lengths=None, frames_per_chunk=None, num_lookahead_tokens=None, prompt_ids=None, **caches):
+                n_active=None, label_lengths=None, frames_per_chunk=None, num_lookahead_tokens=None, prompt_ids=None, input_lengths=None,
+                **caches):
         """The parent's forward with `prompt_ids`."""
+        NM.PM.refuse_input_lengths(type(self).__name__, input_lengths)
         self._refuse_caches(caches)
         if attention_mask is not None:
             raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (ragged batches are out of scope)")
@@ -220,9 +223,10 @@ class Nemotron3_5AsrForRNNT(NM.NemotronAsrStreamingForRNNT):
         self._same_prompts("backward", prompt_ids)
         return super().backward(grad_logits, n_active, num_lookahead_tokens)
 
-    def generate(self, input_features=None, enc=None, num_lookahead_tokens=None, prompt_ids=None):
+    def generate(self, input_features=None, enc=None, num_lookahead_tokens=None, prompt_ids=None, input_lengths=None):
         """The parent's generate; the encoder pass of `input_features` runs with the languages `prompt_ids`.  Projected states `enc` are
         already fused: `prompt_ids` next to them is refused."""
+        NM.PM.refuse_input_lengths(type(self).__name__, input_lengths)
         if enc is None:
             with torch.no_grad():
                 keep = self._ctx, self._tdt, self._ctx_lookahead, self._ctx_prompts

@@ -155,8 +155,11 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
             raise ops.DynError(f"{who}(num_lookahead_tokens={num_lookahead_tokens}) continues an encode that ran with "
                                f"num_lookahead_tokens={self._ctx_lookahead}")
 
-    def encode(self, input_features, attention_mask=None, num_lookahead_tokens=None, **caches):
+    _ragged = False                                            # the chunked attention mask and the causal subsampling know one length
+
+    def encode(self, input_features, attention_mask=None, num_lookahead_tokens=None, input_lengths=None, **caches):
         """ParakeetForTDT.encode under the chunked mask of `num_lookahead_tokens` (None: the configuration's default)."""
+        PM.refuse_input_lengths(type(self).__name__, input_lengths)
         self._refuse_caches(caches)
         c = self.cfg
         self._after_stream = False
@@ -168,8 +171,9 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
         return enc
 
     def forward(self, input_features, decoder_input_ids=None, labels=None, attention_mask=None, reduction=None, sigma=0.0, grad_scale=1.0,
-                n_active=None, label_lengths=None, frames_per_chunk=None, num_lookahead_tokens=None, **caches):
+                n_active=None, label_lengths=None, frames_per_chunk=None, num_lookahead_tokens=None, input_lengths=None, **caches):
         """ParakeetForTDT.forward with `num_lookahead_tokens`."""
+        PM.refuse_input_lengths(type(self).__name__, input_lengths)
         self._refuse_caches(caches)
         if attention_mask is not None:
             raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (ragged batches are out of scope)")
@@ -205,8 +209,9 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
         from .nemotron_asr_streaming_stream import generate_streaming
         return generate_streaming(self, input_features, num_lookahead_tokens, graph)
 
-    def generate(self, input_features=None, enc=None, num_lookahead_tokens=None):
+    def generate(self, input_features=None, enc=None, num_lookahead_tokens=None, input_lengths=None):
         """ParakeetForTDT.generate; the encoder pass of `input_features` runs under the mask of `num_lookahead_tokens`."""
+        PM.refuse_input_lengths(type(self).__name__, input_lengths)
         if enc is None:
             with torch.no_grad():
                 keep = self._ctx, self._tdt, self._ctx_lookahead

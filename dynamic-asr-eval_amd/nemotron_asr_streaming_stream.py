@@ -172,8 +172,10 @@ class StreamSession:
         encoder and the projector overrides this)."""
         return self.model._project_enc(x, False)[0]
 
-    def _encode(self, feats, attention_mask=None):
+    def _encode(self, feats, attention_mask=None, input_lengths=None):
         """The step of one chunk -> enc [B, cs, Hd]; under graph=True the captured step's own output buffer (valid until the next chunk)."""
+        if input_lengths is not None:
+            raise ops.DynError("input_lengths is not built for a streaming session: every frame of a chunk is taken as valid")
         first = self._check_chunk(feats, attention_mask)
         m = self.model
         m._ctx = m._tdt = m._ctx_lookahead = None
@@ -194,17 +196,17 @@ class StreamSession:
         return enc
 
     # ------------------------------------------------------------------ the public calls
-    def encode_chunk(self, feats, attention_mask=None):
+    def encode_chunk(self, feats, attention_mask=None, input_lengths=None):
         """feats [B, first_chunk_frames | chunk_frames, num_mel_bins] -> the projected encoder states [B, cs, Hd] of the chunk."""
-        enc = self._encode(feats, attention_mask)
+        enc = self._encode(feats, attention_mask, input_lengths)
         return enc.clone() if enc is self._static_out else enc
 
-    def push(self, feats, attention_mask=None):
+    def push(self, feats, attention_mask=None, input_lengths=None):
         """encode_chunk + the greedy RNN-T decode of the chunk's cs frames, the decoder's state carried over from the chunk before ->
         SimpleNamespace(enc [B, cs, Hd], tokens int32 [B, max_symbols_per_step * cs], frames (absolute encoder frames), count int32 [B],
         steps int32 [B]), all of this chunk."""
         base = self.frames_seen
-        enc = self._encode(feats, attention_mask)
+        enc = self._encode(feats, attention_mask, input_lengths)
         m, st, P = self.model, self.greedy, self.model.P
         DEC, JOINT = TM.DEC, TM.JOINT
         with torch.no_grad():

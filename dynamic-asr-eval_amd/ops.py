@@ -657,11 +657,20 @@ def _rows_L(x):
     return x.numel() // L, L
 
 
-def softmax(x, out=None, valid=None):
-    """Row softmax; `valid` (device int32 scalar): columns >= valid are masked keys (probability 0)."""
+def softmax(x, out=None, valid=None, lens=None):
+    """Row softmax; `valid` (device int32 scalar): columns >= valid are masked keys (probability 0); `lens` (int32 CUDA [B], x [B, ..., L]):
+    lens[b] keys in every row of batch entry b."""
     _cc(x, "softmax.x")
     rows, L = _rows_L(x)
     out = torch.empty_like(x) if out is None else _cc(out, "softmax.out")
+    valid, lens = _split_valid(valid, lens)
+    if lens is not None:
+        if x.dim() < 3:
+            raise DynError("softmax: lens needs x as [B, ..., L]")
+        B = x.shape[0]
+        check(_L().dyn_softmax_fwd_lens(x.data_ptr(), out.data_ptr(), B, rows // max(B, 1), L, L, L, _lens_ptr(lens, B, "softmax", valid), _stream()),
+              "dyn_softmax_fwd_lens")
+        return out
     if valid is not None:
         check(_L().dyn_softmax_fwd_len(x.data_ptr(), out.data_ptr(), rows, L, L, L, _valid_ptr(valid, "softmax"), _stream()), "dyn_softmax_fwd_len")
         return out
@@ -795,14 +804,21 @@ def _relshift_dims(who, S, ld_bd):
     return S.shape[0] * S.shape[1], T, ld
 
 
-def softmax_relshift(S, BD, out=None, valid=None, ld_bd=None):
+def softmax_relshift(S, BD, out=None, valid=None, ld_bd=None, lens=None):
     """softmax over the keys of S [B, nh, T, T] + BD[b, h, i, T - 1 - i + j] (BD [B, nh, T, ld_bd >= 2T - 1], both scaled already: the
-    Transformer-XL shift read in place); `valid` as in softmax().  `out` may be S."""
+    Transformer-XL shift read in place); `valid` as in softmax(), or `lens` (int32 CUDA [B]): lens[b] keys in batch entry b.  `out` may be S."""
+    valid, lens = _split_valid(valid, lens)
     _cc(S, "softmax_relshift.S"); _c(BD, "softmax_relshift.BD")
     M, T, ld = _relshift_dims("softmax_relshift", S, ld_bd)
     if BD.numel() != M * T * ld:
         raise DynError(f"softmax_relshift: BD holds {BD.numel()} floats, {M} x {T} x {ld} expected")
     out = torch.empty_like(S) if out is None else _cc(out, "softmax_relshift.out")
+    if lens is not None:
+        if S.dim() != 4:
+            raise DynError("softmax_relshift: lens needs S as [B, nh, T, T]")
+        check(_L().dyn_softmax_relshift_fwd_lens(S.data_ptr(), out.data_ptr(), BD.data_ptr(), S.shape[0], S.shape[1], T, ld,
+                                                 _lens_ptr(lens, S.shape[0], "softmax_relshift", valid), _stream()), "dyn_softmax_relshift_fwd_lens")
+        return out
     check(_L().dyn_softmax_relshift_fwd_len(S.data_ptr(), out.data_ptr(), BD.data_ptr(), M, T, ld, _valid_ptr(valid, "softmax_relshift"),
                                             _stream()), "dyn_softmax_relshift_fwd_len")
     return out
@@ -966,23 +982,33 @@ def out_len(n):
     return (n - 1) // 2 + 1
 
 
-def conv2d_first(x, w, bias, out=None):
-    """x [B, T, F] -> z [B, To, Fo, C]; w [C, 3, 3]."""
+def conv2d_first(x, w, bias, out=None, lens=None):
+    """x [B, T, F] -> z [B, To, Fo, C]; w [C, 3, 3].  `lens` (int32 CUDA [B]): frames t >= lens[b] of x read as zeros."""
     _cc(x, "conv2d_first.x"); _cc(w, "conv2d_first.w"); _cc(bias, "conv2d_first.bias")
     B, T, F = x.shape
     C = w.shape[0]
     if out is None:
         out = torch.empty(B, out_len(T), out_len(F), C, device=x.device, dtype=F32)
+    if lens is not None:
+        check(_L().dyn_conv2d_first_fwd_lens(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, T, F, C,
+                                             _lens_ptr(lens, B, "conv2d_first"), _stream()), "dyn_conv2d_first_fwd_lens")
+        return out
     check(_L().dyn_conv2d_first_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, T, F, C, _stream()),
           "dyn_conv2d_first_fwd")
     return out
 
 
-def conv2d_first_wgrad(x, dz, dw, dbias, beta=1.0):
+def conv2d_first_wgrad(x, dz, dw, dbias, beta=1.0, lens=None):
+    """dw [C, 3, 3], dbias [C] = beta * old + the gradients of conv2d_first.  `lens` (int32 CUDA [B]): frames t >= lens[b] of x read as zeros."""
     _cc(x, "conv2d_first_wgrad.x"); _cc(dz, "conv2d_first_wgrad.dz")
     B, T, F = x.shape
     C = dw.shape[0]
     ws = workspace(x.device)
+    if lens is not None:
+        check(_L().dyn_conv2d_first_wgrad_lens(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), dbias.data_ptr(), beta, B, T, F, C,
+                                               _lens_ptr(lens, B, "conv2d_first_wgrad"), ws.data_ptr(), ws.numel(), _stream()),
+              "dyn_conv2d_first_wgrad_lens")
+        return
     check(_L().dyn_conv2d_first_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr(), dbias.data_ptr(), beta, B, T, F, C,
                                       ws.data_ptr(), ws.numel(), _stream()), "dyn_conv2d_first_wgrad")
 
@@ -1327,6 +1353,44 @@ def _valid_ptr(valid, what):
     if not (isinstance(valid, torch.Tensor) and valid.is_cuda and valid.dtype == torch.int32 and valid.numel() == 1):
         raise DynError(f"{what}: the valid-length operand must be a one-element int32 CUDA tensor")
     return valid.data_ptr()
+
+
+class RowLens:
+    """The `valid` argument of a ragged batch: frame counts per batch entry (`lens`, int32 CUDA [B]) where a length bucket has one device
+    scalar.  The layer code hands `valid` through unchanged; the wrappers that take `valid` route a RowLens to their `_lens` entry."""
+
+    def __init__(self, lens):
+        self.lens = lens
+
+    def cut(self, nb):
+        return RowLens(self.lens[:nb])
+
+
+def _split_valid(valid, lens):
+    return (None, valid.lens) if isinstance(valid, RowLens) and lens is None else (valid, lens)
+
+
+def _lens_ptr(lens, B, what, valid=None):
+    """`lens`: the frame counts of a ragged batch, one per batch entry: an int32 CUDA tensor [B] the kernel reads (and clamps) when it runs.
+    It takes the place of the scalar `valid`; both together are refused."""
+    if valid is not None:
+        raise DynError(f"{what}: pass `valid` (one count for the batch) or `lens` (one per batch entry), not both")
+    if not (isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32 and lens.dim() == 1 and lens.is_contiguous()):
+        raise DynError(f"{what}: lens must be a contiguous int32 CUDA tensor [B]")
+    if lens.numel() != B:
+        raise DynError(f"{what}: lens holds {lens.numel()} counts for a batch of {B}")
+    return lens.data_ptr()
+
+
+def mask_rows_lens(x, lens):
+    """x [B, T, ...] in place: rows t >= lens[b] (int32 CUDA [B]) of batch entry b := 0."""
+    _cc(x, "mask_rows_lens.x")
+    if x.dim() < 3:
+        raise DynError("mask_rows_lens: x must be [B, T, ...]")
+    B, T = x.shape[:2]
+    check(_L().dyn_mask_rows_lens(x.data_ptr(), B, T, x.numel() // max(B * T, 1), _lens_ptr(lens, B, "mask_rows_lens"), _stream()),
+          "dyn_mask_rows_lens")
+    return x
 
 
 def colnorm(x, gamma, beta, eps=1e-5, valid=None):
@@ -1904,10 +1968,12 @@ def _bn_operands(what, C, mean, var, weight, bias):
             raise DynError(f"{what}: {n} must have C = {C} elements")
 
 
-def convmod_bn(u, w, cbias, mean, var, weight, bias, act="silu", eps=1e-5, valid=None, save=False):
+def convmod_bn(u, w, cbias, mean, var, weight, bias, act="silu", eps=1e-5, valid=None, save=False, lens=None):
     """Parakeet's conv-module core in one launch: u [B, T, 2C] -> s [B, T, C] = act(BatchNorm_eval(cbias + depthwise conv(GLU(u)))), w [C, 9]
     or [C, 32] (LASR; 15 frames of padding left, 16 right, as torch's padding="same"), zero SAME padding; cbias None: no convolution bias.  `valid` (device int32 scalar): GLU rows past it read as zeros, output rows past it are
-    zeros.  Returns (s, gl, c): with `save` the masked GLU output and the convolution output the backward needs, else two Nones."""
+    zeros; `lens` (int32 CUDA [B]) in its place: the same with lens[b] for batch entry b.  Returns (s, gl, c): with `save` the masked GLU
+    output and the convolution output the backward needs, else two Nones."""
+    valid, lens = _split_valid(valid, lens)
     _cc(u, "convmod_bn.u"); _cc(w, "convmod_bn.w")
     if act not in CONVMOD_BN_ACTS:
         raise DynError(f"convmod_bn: act={act!r} is not built ({sorted(CONVMOD_BN_ACTS)})")
@@ -1922,16 +1988,20 @@ def convmod_bn(u, w, cbias, mean, var, weight, bias, act="silu", eps=1e-5, valid
     gl = c = None
     if save:
         gl, c = (torch.empty(B, T, C, device=u.device, dtype=F32) for _ in range(2))
-    check(_L().dyn_convmod_bn_fwd(u.data_ptr(), w.data_ptr(), _opt(cbias, "cbias"), mean.data_ptr(), var.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                  s.data_ptr(), _opt(gl, "gl"), _opt(c, "c"), _valid_ptr(valid, "convmod_bn"), B, T, C, w.shape[1],
-                                  CONVMOD_BN_ACTS[act], eps, _stream()), "dyn_convmod_bn_fwd")
+    fn, vp = (_L().dyn_convmod_bn_fwd, _valid_ptr(valid, "convmod_bn")) if lens is None else \
+        (_L().dyn_convmod_bn_fwd_lens, _lens_ptr(lens, B, "convmod_bn", valid))
+    check(fn(u.data_ptr(), w.data_ptr(), _opt(cbias, "cbias"), mean.data_ptr(), var.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+             s.data_ptr(), _opt(gl, "gl"), _opt(c, "c"), vp, B, T, C, w.shape[1], CONVMOD_BN_ACTS[act], eps, _stream()),
+          "dyn_convmod_bn_fwd" if lens is None else "dyn_convmod_bn_fwd_lens")
     return s, gl, c
 
 
-def convmod_bn_bwd_act(c, mean, var, weight, bias, ds, dweight, dbias, dcbias, act="silu", eps=1e-5, valid=None, out=None, wgrad_beta=1.0):
+def convmod_bn_bwd_act(c, mean, var, weight, bias, ds, dweight, dbias, dcbias, act="silu", eps=1e-5, valid=None, out=None, wgrad_beta=1.0,
+                       lens=None):
     """Backward of convmod_bn's activation and BatchNorm: returns dc [B, T, C] = ds * act'(bn) * weight * rstd (`out` may be ds), and
-    accumulates dweight / dbias / dcbias = wgrad_beta * old + their column sums (None: frozen, not computed).  Rows past `valid`: dc = 0, left
-    out of the sums."""
+    accumulates dweight / dbias / dcbias = wgrad_beta * old + their column sums (None: frozen, not computed).  Rows past `valid` (or past
+    lens[b], `lens` int32 CUDA [B]): dc = 0, left out of the sums."""
+    valid, lens = _split_valid(valid, lens)
     _cc(c, "convmod_bn_bwd_act.c"); _cc(ds, "convmod_bn_bwd_act.ds")
     if act not in CONVMOD_BN_ACTS:
         raise DynError(f"convmod_bn_bwd_act: act={act!r} is not built ({sorted(CONVMOD_BN_ACTS)})")
@@ -1946,16 +2016,18 @@ def convmod_bn_bwd_act(c, mean, var, weight, bias, ds, dweight, dbias, dcbias, a
     if out.shape != ds.shape:
         raise DynError("convmod_bn_bwd_act: out must have the shape of ds")
     ws = workspace(c.device)
-    check(_L().dyn_convmod_bn_bwd_act(c.data_ptr(), mean.data_ptr(), var.data_ptr(), weight.data_ptr(), bias.data_ptr(), ds.data_ptr(),
-                                      out.data_ptr(), _opt(dweight, "dweight"), _opt(dbias, "dbias"), _opt(dcbias, "dcbias"), wgrad_beta,
-                                      _valid_ptr(valid, "convmod_bn_bwd_act"), B, T, C, CONVMOD_BN_ACTS[act], eps, ws.data_ptr(), ws.numel(),
-                                      _stream()), "dyn_convmod_bn_bwd_act")
+    fn, vp = (_L().dyn_convmod_bn_bwd_act, _valid_ptr(valid, "convmod_bn_bwd_act")) if lens is None else \
+        (_L().dyn_convmod_bn_bwd_act_lens, _lens_ptr(lens, B, "convmod_bn_bwd_act", valid))
+    check(fn(c.data_ptr(), mean.data_ptr(), var.data_ptr(), weight.data_ptr(), bias.data_ptr(), ds.data_ptr(), out.data_ptr(),
+             _opt(dweight, "dweight"), _opt(dbias, "dbias"), _opt(dcbias, "dcbias"), wgrad_beta, vp, B, T, C, CONVMOD_BN_ACTS[act], eps,
+             ws.data_ptr(), ws.numel(), _stream()), "dyn_convmod_bn_bwd_act" if lens is None else "dyn_convmod_bn_bwd_act_lens")
     return out
 
 
-def glu_dwconv1d_dgrad(u, w, dc, valid=None, out=None):
+def glu_dwconv1d_dgrad(u, w, dc, valid=None, out=None, lens=None):
     """du [B, T, 2C] = GLU'(u) * (the input gradient of the SAME-padded depthwise convolution w [C, 9] or [C, 32] from dc [B, T, C]) in one pass; rows past
-    `valid` are zeros."""
+    `valid` (or past lens[b], `lens` int32 CUDA [B]) are zeros."""
+    valid, lens = _split_valid(valid, lens)
     _cc(u, "glu_dwconv1d_dgrad.u"); _cc(w, "glu_dwconv1d_dgrad.w"); _cc(dc, "glu_dwconv1d_dgrad.dc")
     if u.dim() != 3 or dc.dim() != 3 or u.shape[:2] != dc.shape[:2] or u.shape[2] != 2 * dc.shape[2] or w.dim() != 2 or w.shape[0] != dc.shape[2]:
         raise DynError("glu_dwconv1d_dgrad: u must be [B, T, 2C], dc [B, T, C], w [C, KW]")
@@ -1963,8 +2035,10 @@ def glu_dwconv1d_dgrad(u, w, dc, valid=None, out=None):
     out = torch.empty_like(u) if out is None else _cc(out, "glu_dwconv1d_dgrad.out")
     if out.shape != u.shape or out.data_ptr() in (u.data_ptr(), dc.data_ptr()):
         raise DynError("glu_dwconv1d_dgrad: out must have the shape of u and alias neither u nor dc")
-    check(_L().dyn_glu_dwconv1d_dgrad(u.data_ptr(), w.data_ptr(), dc.data_ptr(), out.data_ptr(), _valid_ptr(valid, "glu_dwconv1d_dgrad"), B, T, C,
-                                      w.shape[1], _stream()), "dyn_glu_dwconv1d_dgrad")
+    fn, vp = (_L().dyn_glu_dwconv1d_dgrad, _valid_ptr(valid, "glu_dwconv1d_dgrad")) if lens is None else \
+        (_L().dyn_glu_dwconv1d_dgrad_lens, _lens_ptr(lens, B, "glu_dwconv1d_dgrad", valid))
+    check(fn(u.data_ptr(), w.data_ptr(), dc.data_ptr(), out.data_ptr(), vp, B, T, C, w.shape[1], _stream()),
+          "dyn_glu_dwconv1d_dgrad" if lens is None else "dyn_glu_dwconv1d_dgrad_lens")
     return out
 
 
@@ -2037,33 +2111,58 @@ def _sub_act(act, what):
     return SUBSAMPLING_ACTS[act]
 
 
-def dwconv2d_s2_act(z, w, bias, act, out=None):
-    """u = bias + dw3x3_s2(act(z)), act "silu" (ops.dwconv2d_s2) or "relu"; z [B, T, F, C] -> [B, To, Fo, C]; w [C, 3, 3]."""
+def _stage_lens(what, B, lens_in, lens_out):
+    if (lens_in is None) != (lens_out is None):
+        raise DynError(f"{what}: lens_in and lens_out go together")
+    return None if lens_in is None else (_lens_ptr(lens_in, B, what + ".lens_in"), _lens_ptr(lens_out, B, what + ".lens_out"))
+
+
+def dwconv2d_s2_act(z, w, bias, act, out=None, lens_in=None, lens_out=None):
+    """u = bias + dw3x3_s2(act(z)), act "silu" (ops.dwconv2d_s2) or "relu"; z [B, T, F, C] -> [B, To, Fo, C]; w [C, 3, 3].  `lens_in` /
+    `lens_out` (int32 CUDA [B], together): rows t >= lens_in[b] of z read as zeros, rows to >= lens_out[b] of u are written as zeros."""
     a = _sub_act(act, "dwconv2d_s2_act")
     _cc(z, "dwconv2d_s2_act.z"); _cc(w, "dwconv2d_s2_act.w"); _cc(bias, "dwconv2d_s2_act.bias")
     B, T, F, C = z.shape
     if out is None:
         out = torch.empty(B, out_len(T), out_len(F), C, device=z.device, dtype=F32)
+    ll = _stage_lens("dwconv2d_s2_act", B, lens_in, lens_out)
+    if ll is not None:
+        check(_L().dyn_dwconv2d_s2_fwd_act_lens(z.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, T, F, C, a, ll[0], ll[1], _stream()),
+              "dyn_dwconv2d_s2_fwd_act_lens")
+        return out
     check(_L().dyn_dwconv2d_s2_fwd_act(z.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, T, F, C, a, _stream()),
           "dyn_dwconv2d_s2_fwd_act")
     return out
 
 
-def dwconv2d_s2_dgrad_act(z, w, du, act, out=None):
+def dwconv2d_s2_dgrad_act(z, w, du, act, out=None, lens_in=None, lens_out=None):
+    """dz of dwconv2d_s2_act from du.  `lens_in` / `lens_out`: rows t >= lens_in[b] of dz are zeros, rows to >= lens_out[b] of du are not read."""
     a = _sub_act(act, "dwconv2d_s2_dgrad_act")
     _cc(z, "dwconv2d_s2_dgrad_act.z"); _cc(du, "dwconv2d_s2_dgrad_act.du"); _cc(w, "dwconv2d_s2_dgrad_act.w")
     B, T, F, C = z.shape
     out = torch.empty_like(z) if out is None else _cc(out, "dwconv2d_s2_dgrad_act.out")
+    ll = _stage_lens("dwconv2d_s2_dgrad_act", B, lens_in, lens_out)
+    if ll is not None:
+        check(_L().dyn_dwconv2d_s2_dgrad_act_lens(z.data_ptr(), w.data_ptr(), du.data_ptr(), out.data_ptr(), B, T, F, C, a, ll[0], ll[1],
+                                                  _stream()), "dyn_dwconv2d_s2_dgrad_act_lens")
+        return out
     check(_L().dyn_dwconv2d_s2_dgrad_act(z.data_ptr(), w.data_ptr(), du.data_ptr(), out.data_ptr(), B, T, F, C, a, _stream()),
           "dyn_dwconv2d_s2_dgrad_act")
     return out
 
 
-def dwconv2d_s2_wgrad_act(z, du, dw, dbias, act, beta=1.0):
+def dwconv2d_s2_wgrad_act(z, du, dw, dbias, act, beta=1.0, lens_in=None):
+    """dw, dbias = beta * old + the gradients of dwconv2d_s2_act.  `lens_in` (int32 CUDA [B]): rows t >= lens_in[b] of z read as zeros (du is
+    zero past the output length already)."""
     a = _sub_act(act, "dwconv2d_s2_wgrad_act")
     _cc(z, "dwconv2d_s2_wgrad_act.z"); _cc(du, "dwconv2d_s2_wgrad_act.du"); _cc(dw, "dwconv2d_s2_wgrad_act.dw"); _cc(dbias, "dwconv2d_s2_wgrad_act.dbias")
     B, T, F, C = z.shape
     ws = workspace(z.device)
+    if lens_in is not None:
+        check(_L().dyn_dwconv2d_s2_wgrad_act_lens(z.data_ptr(), du.data_ptr(), dw.data_ptr(), dbias.data_ptr(), beta, B, T, F, C, a,
+                                                  _lens_ptr(lens_in, B, "dwconv2d_s2_wgrad_act"), ws.data_ptr(), ws.numel(), _stream()),
+              "dyn_dwconv2d_s2_wgrad_act_lens")
+        return
     check(_L().dyn_dwconv2d_s2_wgrad_act(z.data_ptr(), du.data_ptr(), dw.data_ptr(), dbias.data_ptr(), beta, B, T, F, C, a, ws.data_ptr(),
                                          ws.numel(), _stream()), "dyn_dwconv2d_s2_wgrad_act")
 

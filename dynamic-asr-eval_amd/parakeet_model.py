@@ -25,6 +25,11 @@ reductions are the parent's, found under the parent's names through an alias tab
     glu_dwconv1d_dgrad) + the existing ops.dwconv1d_wgrad.  A backward keeps u, gl and c of the bracket instead of g, gl, dw, bn.
   * no `encoder.layer_norm`; the head is `ctc_head`, a k = 1 Conv1d = a linear.
   * the batch-norm buffers live outside the flat vector (`buffers_`), as in the parent.
+  * ragged batches: `input_lengths=` (the valid feature frames per row) on forward / generate.  The counts behind each stride-2 stage
+    (output_lengths) go to the device once; the first conv reads the frames past a row's length as zeros, the depthwise stages read and
+    write their rows past it as zeros, the relative-position softmax takes the row's own key count, the conv module zeroes the GLU rows
+    past it, backward() zeroes the incoming gradient there (the `_lens` entries of csrc/conv.hip, relshift.hip, convmod_bn.hip).  Valid
+    frames equal the row run alone; DESIGN.md, "Ragged batches".
 
 Not built, refused by name before any launch: `subsampling_factor` != 8, `subsampling_conv_kernel_size` != 3, `subsampling_conv_stride` != 2,
 `subsampling_conv_channels` not a multiple of 4, `num_mel_bins` not a multiple of 8, `hidden_size` outside 256 / 512 / 768 / 1024,
@@ -34,6 +39,7 @@ parakeet_tdt_model.py, parakeet_rnnt_model.py).  No hub checkpoint is on
 the machine: transformers' ParakeetForCTC on the CPU with the same (random) state dict is the oracle in the tests."""
 import contextlib
 import math
+import weakref
 from types import SimpleNamespace
 
 import torch
@@ -141,6 +147,58 @@ def frames(T):
     return T
 
 
+def output_lengths(lens):
+    """Valid feature frames per row -> [(frames into stage 1), after stage 1, after stage 2, after stage 3]: four lists, each stride-2 stage
+    maps L -> (L - 1) // 2 + 1 (transformers' _get_subsampling_output_length); the last is the encoder's valid frames per row."""
+    out = [[int(n) for n in lens]]
+    for _ in range(3):
+        out.append([ops.out_len(n) for n in out[-1]])
+    return out
+
+
+def lengths_from_mask(mask):
+    """The feature extractor's `attention_mask` [B, T] (nonzero = valid frame) -> the list of valid frames per row.  A mask that is not a
+    prefix (a valid frame behind an invalid one) or has an empty row is refused: `input_lengths` can only say how many leading frames count."""
+    if not (isinstance(mask, torch.Tensor) and mask.dim() == 2 and mask.shape[1] >= 1 and not mask.is_floating_point() and not mask.is_complex()):
+        raise ops.DynError("lengths_from_mask: the mask must be an integer or bool tensor [B, T]")
+    m = (mask != 0).cpu()
+    lens = m.sum(1)
+    if not bool((m == (torch.arange(m.shape[1])[None, :] < lens[:, None])).all()):
+        raise ops.DynError("lengths_from_mask: the mask is not a prefix mask (a valid frame follows an invalid one); input_lengths cannot express it")
+    if int(lens.min()) < 1:
+        raise ops.DynError("lengths_from_mask: a row of the mask has no valid frame")
+    return [int(n) for n in lens]
+
+
+def check_input_lengths(input_lengths, B, T):
+    """`input_lengths` (a sequence of ints, or an integer tensor [B] on the host or the device: one host copy) -> a list of B ints in 1 .. T."""
+    v = input_lengths
+    if isinstance(v, torch.Tensor):
+        if v.is_floating_point() or v.is_complex() or v.dtype == torch.bool:
+            raise ops.DynError(f"input_lengths must hold integers, not {v.dtype}")
+        if v.dim() != 1:
+            raise ops.DynError(f"input_lengths must be one count per row [B], not a tensor of shape {tuple(v.shape)}")
+        v = v.tolist()
+    elif isinstance(v, (list, tuple)):
+        if not all(isinstance(n, int) and not isinstance(n, bool) for n in v):
+            raise ops.DynError("input_lengths must hold integers")
+        v = list(v)
+    else:
+        raise ops.DynError("input_lengths must be a sequence of ints or an integer tensor [B]")
+    if len(v) != B:
+        raise ops.DynError(f"input_lengths holds {len(v)} counts for a batch of {B} rows")
+    if not all(1 <= n <= T for n in v):
+        raise ops.DynError(f"input_lengths={v} must lie in 1 .. T = {T}, the frames of input_features")
+    return v
+
+
+def refuse_input_lengths(who, input_lengths):
+    """A model of the family without per-row frame counts refuses them by name."""
+    if input_lengths is not None:
+        raise ops.DynError(f"input_lengths is not built for {who}: per-row frame counts exist for ParakeetForCTC, ParakeetForTDT and "
+                           "ParakeetForRNNT; run every utterance at its own length")
+
+
 def position_table(T, H):
     """ParakeetEncoderRelPositionalEncoding.forward for T frames of width H on the host, in its dtypes and operation order: [2T - 1, H]
     float32, positions T - 1 .. -(T - 1), sin / cos interleaved."""
@@ -244,7 +302,8 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
         return super().trainable(getattr(self, "_alias", {}).get(name, name))
 
     def __call__(self, x=None, **kw):
-        return self.forward(kw.get(self._input, x), attention_mask=kw.get("attention_mask"))
+        more = {"input_lengths": kw["input_lengths"]} if kw.get("input_lengths") is not None else {}
+        return self.forward(kw.get(self._input, x), attention_mask=kw.get("attention_mask"), **more)
 
     def _make_buffers(self):
         return {n: (torch.ones if n.endswith("running_var") else torch.zeros)(shape, device=self.device, dtype=dt)
@@ -347,34 +406,93 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
         return t
 
     # ------------------------------------------------------------------ forward
-    def forward(self, input_features, attention_mask=None):
+    _ragged = True                                             # a model of the family without per-row frame counts says so (refused by name)
+    _enc_lengths = None      # (weak reference to enc, host list, int32 [B] on the device) of the last encode() of a ragged batch
+
+    def _remember_lengths(self, enc, out):
+        """encode() of a model whose head runs in a later call: keeps the rows' encoder frame counts next to a weak reference to `enc`."""
+        self._enc_lengths = (weakref.ref(enc), out.lengths, out.lengths_device) if hasattr(out, "lengths") else None
+
+    def _lengths_of(self, enc, enc_lengths, rows):
+        """The valid encoder frames of the first `rows` rows of enc as int32 on the device, or None (every frame): `enc_lengths` (a
+        sequence of ints or an integer tensor [B], 1 .. T'), else what the encode() that returned this very tensor knows.  Another
+        tensor of that shape while a ragged encode is remembered (a clone, a detached or contiguous copy) is refused: it would silently
+        run at full lengths."""
+        if enc_lengths is None:
+            k = self._enc_lengths
+            if k is None:
+                return None
+            if k[0]() is enc:
+                return k[2][:rows]
+            if k[0]() is not None and tuple(k[0]().shape) == tuple(enc.shape):
+                raise ops.DynError("the last encode() ran a ragged batch (input_lengths) and these encoder states are another tensor of the "
+                                   "same shape: pass enc_lengths (the result's `lengths`) with it")
+            return None
+        host = check_input_lengths(enc_lengths, enc.shape[0], enc.shape[1])
+        return torch.tensor(host + [0] * (-len(host) % 4), dtype=torch.int32).to(self.device, non_blocking=True)[:rows]
+
+    def forward(self, input_features, attention_mask=None, input_lengths=None):
         """input_features [B, T, num_mel_bins] float32 on the device -> SimpleNamespace(logits [B, T', V], frames = T'), T' = frames(T).
-        Every row is valid: `attention_mask` is refused."""
+        `attention_mask` is refused.  `input_lengths` (None: every frame of every row is valid; else check_input_lengths): the valid
+        frames per row of a ragged batch.  Frames >= input_lengths[b] of input_features are never read as data (they count as zeros,
+        what the extractor's `input_features *= mask` leaves there), the result gains `lengths` (the valid encoder frames per row,
+        output_lengths(..)[3], a host list) and `lengths_device` (the same, int32 [B] on the device): logits at frames < lengths[b] are
+        those of the row run alone at its own length, the frames past it are finite and carry no meaning."""
         if attention_mask is not None:
-            raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (the reference loop passes whole windows)")
+            raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (the reference loop passes whole "
+                               "windows); a ragged batch passes input_lengths (parakeet_model.lengths_from_mask turns a prefix mask into them)")
         x = input_features
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.n_mels
                 and x.shape[1] >= 1):
             raise ops.DynError(f"input_features must be a float32 CUDA tensor [B, T, {self.n_mels}]")
         B, T, _ = x.shape
         T3 = self.frames(T)
+        host = lens = None
+        if input_lengths is not None:
+            host, lens = self._stage_lengths(input_lengths, B, T)
         self.position_table(T3)
         with ops.use_workspace(self._scratch()):
             self._vl, self._ctx_static = None, False
             ctx = {"conv": []} if torch.is_grad_enabled() else None
-            h, kept = self._subsample(x.contiguous())
+            h, kept = self._subsample(x.contiguous()) if lens is None else self._subsample(x.contiguous(), lens)
             if ctx is not None:
                 ctx["sub"] = kept
-            return self._encode(h, ctx, None, (B, T, T3), None)
+                ctx["lens"] = lens
+            out = self._encode(h, ctx, None if lens is None else ops.RowLens(lens[3]), (B, T, T3), None)
+        if lens is not None:
+            out.lengths, out.lengths_device = host[3], lens[3]
+        return out
 
-    def _subsample(self, x):
-        """x [B, T, F] -> (h [B, T', H], what _subsample_bwd needs, batch-major)."""
+    def _stage_lengths(self, input_lengths, B, T):
+        """(output_lengths as host lists, the same as one int32 tensor [4, B] (a view) on the device: one small copy, no synchronisation) of a ragged
+        batch; what is not built with per-row frame counts is refused by name here, before any launch."""
+        if not self._ragged:
+            refuse_input_lengths(type(self).__name__, input_lengths)
+        if self._brn is not None:
+            raise ops.DynError("input_lengths inside batch_renorm_training() is not built: the batch statistics would have to leave out every "
+                               "row's padded frames")
+        if torch.cuda.is_current_stream_capturing():
+            raise ops.DynError("input_lengths under hipGraph capture is not built: the frame counts are checked and copied on the host")
+        host = output_lengths(check_input_lengths(input_lengths, B, T))
+        rows = torch.zeros(4, (B + 3) // 4 * 4, dtype=torch.int32)          # every stage's counts start 16-byte aligned (the loss kernels ask for it)
+        rows[:, :B] = torch.tensor(host, dtype=torch.int32)
+        return host, rows.to(self.device, non_blocking=True)[:, :B]
+
+    def _subsample(self, x, lens=None):
+        """x [B, T, F] -> (h [B, T', H], what _subsample_bwd needs, batch-major).  `lens` (int32 [4, B], _stage_lengths): transformers zeroes
+        the rows past a row's length after every Conv2d.  Here the two depthwise stages read their input rows past it as zeros and write
+        their output rows past it as zeros (that covers the first conv's output, both large intermediates and the first pointwise conv's
+        bias rows without a pass over them), the first conv reads the feature frames past it as zeros, and the small z3 behind the last
+        pointwise conv gets ops.mask_rows_lens."""
         P, s = self.P, SUB
-        z1 = ops.conv2d_first(x, P[s + "layers.0.weight"], P[s + "layers.0.bias"])                       # [B, T1, F1, C], pre-activation
-        u2 = ops.dwconv2d_s2_act(z1, P[s + "layers.2.weight"], P[s + "layers.2.bias"], "relu")
+        l0, l1, l2, l3 = (None,) * 4 if lens is None else lens                                       # None: the entries without counts
+        z1 = ops.conv2d_first(x, P[s + "layers.0.weight"], P[s + "layers.0.bias"], lens=l0)             # [B, T1, F1, C], pre-activation
+        u2 = ops.dwconv2d_s2_act(z1, P[s + "layers.2.weight"], P[s + "layers.2.bias"], "relu", lens_in=l1, lens_out=l2)
         z2 = ops.linear(u2, P[s + "layers.3.weight"], P[s + "layers.3.bias"])
-        u3 = ops.dwconv2d_s2_act(z2, P[s + "layers.5.weight"], P[s + "layers.5.bias"], "relu")
+        u3 = ops.dwconv2d_s2_act(z2, P[s + "layers.5.weight"], P[s + "layers.5.bias"], "relu", lens_in=l2, lens_out=l3)
         z3 = ops.linear(u3, P[s + "layers.6.weight"], P[s + "layers.6.bias"])
+        if lens is not None:
+            ops.mask_rows_lens(z3, l3)
         a3 = ops.relu(z3)
         B, T3, F3, C = a3.shape
         h = ops.linear(a3.view(B, T3, F3 * C), P[s + "linear.weight"], P[s + "linear.bias"])
@@ -383,8 +501,10 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
             ops.axpby(raw, h, 0.0, self.input_scale)
         return h, (x, z1, u2, z2, u3, z3, a3)
 
-    def _subsample_bwd(self, kept, dh):
-        """Accumulates the subsampling's gradients from dh = dL/dh [nb, T', H]; the features are data, so nothing is returned."""
+    def _subsample_bwd(self, kept, dh, lens=None):
+        """Accumulates the subsampling's gradients from dh = dL/dh [nb, T', H]; the features are data, so nothing is returned.  `lens`
+        (int32 [4, nb]): the forward's row masks run backwards: dz3 is zeroed past a row's length, each depthwise dgrad writes zeros past
+        its input length and reads no du past its output length, the weight gradients read their input rows past the length as zeros."""
         P, G, s = self.P, self.G, SUB
         x, z1, u2, z2, u3, z3, a3 = kept
         B, T3, F3, C = a3.shape
@@ -394,13 +514,16 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
             dh = d
         da3 = self._lin_bwd(dh, a3.view(B, T3, F3 * C), s + "linear.weight", s + "linear.bias")
         dz3 = ops.relu_bwd(z3, da3.view(z3.shape), out=da3.view(z3.shape))
+        l0, l1, l2, l3 = (None,) * 4 if lens is None else lens
+        if lens is not None:
+            ops.mask_rows_lens(dz3, l3)
         du3 = self._lin_bwd(dz3, u3, s + "layers.6.weight", s + "layers.6.bias")
-        ops.dwconv2d_s2_wgrad_act(z2, du3, G[s + "layers.5.weight"], G[s + "layers.5.bias"], "relu", beta=1.0)
-        dz2 = ops.dwconv2d_s2_dgrad_act(z2, P[s + "layers.5.weight"], du3, "relu")
+        ops.dwconv2d_s2_wgrad_act(z2, du3, G[s + "layers.5.weight"], G[s + "layers.5.bias"], "relu", beta=1.0, lens_in=l2)
+        dz2 = ops.dwconv2d_s2_dgrad_act(z2, P[s + "layers.5.weight"], du3, "relu", lens_in=l2, lens_out=l3)
         du2 = self._lin_bwd(dz2, u2, s + "layers.3.weight", s + "layers.3.bias")
-        ops.dwconv2d_s2_wgrad_act(z1, du2, G[s + "layers.2.weight"], G[s + "layers.2.bias"], "relu", beta=1.0)
-        dz1 = ops.dwconv2d_s2_dgrad_act(z1, P[s + "layers.2.weight"], du2, "relu")
-        ops.conv2d_first_wgrad(x, dz1, G[s + "layers.0.weight"], G[s + "layers.0.bias"], beta=1.0)
+        ops.dwconv2d_s2_wgrad_act(z1, du2, G[s + "layers.2.weight"], G[s + "layers.2.bias"], "relu", beta=1.0, lens_in=l1)
+        dz1 = ops.dwconv2d_s2_dgrad_act(z1, P[s + "layers.2.weight"], du2, "relu", lens_in=l1, lens_out=l2)
+        ops.conv2d_first_wgrad(x, dz1, G[s + "layers.0.weight"], G[s + "layers.0.bias"], beta=1.0, lens=l0)
 
     def _conv_fwd(self, x, l, vT, save):
         """x + conv_module(x)."""
@@ -448,8 +571,23 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
         """ctc_head, the layers and the subsampling; returns None: nothing lies below the subsampling (the features are data)."""
         v0, vT = ctx["valid"]
         T = ctx["dims"][2]
+        lens = ctx.get("lens")
+        if lens is not None:                                   # a ragged batch: no gradient enters at a padded frame, whatever the caller's loss left there
+            vT, lens = vT.cut(nb), lens[:, :nb]
+            grad_logits = ops.mask_rows_lens(grad_logits.contiguous().clone(), lens[3])
         dx = self._lin_bwd(grad_logits.contiguous(), cut(ctx["head"]), "ctc_head.weight", "ctc_head.bias")
         dh = self._layers_bwd(ctx, dx, nb, T, self.position_table(T), vT, cut)
         if not self._below_frozen():
-            self._subsample_bwd(cut(ctx["sub"]), dh)
+            self._subsample_bwd(cut(ctx["sub"]), dh, *(() if lens is None else (lens,)))
         return None
+
+    def generate(self, input_features, input_lengths=None):
+        """Greedy CTC ids as transformers' ParakeetForCTC.generate returns them: the argmax of every frame's logits [B, T'] (int64, blanks
+        and repeats kept), `pad_token_id` at the frames past a row's length of a ragged batch."""
+        with torch.no_grad():
+            out = self.forward(input_features, input_lengths=input_lengths)
+        B, T3, V = out.logits.shape
+        ids = ops.argmax_rows(out.logits.view(B * T3, V))[0].view(B, T3).to(torch.int64)
+        if input_lengths is not None:
+            ids.masked_fill_(torch.arange(T3, device=ids.device)[None, :] >= out.lengths_device[:, None], self.cfg["pad_token_id"])
+        return ids

@@ -230,11 +230,15 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         self._ctx = ctx
         return SimpleNamespace(enc=enc, frames=T)
 
-    def encode(self, input_features, attention_mask=None):
+    def encode(self, input_features, attention_mask=None, input_lengths=None):
         """input_features [B, T, num_mel_bins] -> the projected encoder states [B, T', Hd] (transformers' `pooler_output`).  In grad mode
-        the encoder's activations are kept for a later head() + backward()."""
+        the encoder's activations are kept for a later head() + backward().  `input_lengths` (ParakeetForCTC.forward): the valid
+        frames per row of a ragged batch; head() and generate() given this call's result find the rows' encoder frame counts
+        (`enc_lengths`) themselves."""
         self._tdt = None
-        return PM.ParakeetForCTC.forward(self, input_features, attention_mask).enc
+        out = PM.ParakeetForCTC.forward(self, input_features, attention_mask, *(() if input_lengths is None else (input_lengths,)))
+        self._remember_lengths(out.enc, out)
+        return out.enc
 
     # ------------------------------------------------------------------ prediction network
     def _decoder_fwd(self, ids, save):
@@ -326,11 +330,12 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         return loss, nll, state
 
     def head(self, enc, decoder_input_ids, labels=None, reduction=None, sigma=0.0, grad_scale=1.0, n_active=None, label_lengths=None,
-             frames_per_chunk=None):
+             frames_per_chunk=None, enc_lengths=None):
         """The prediction network, the joint and (with labels) the TDT loss on the first n_active rows of enc [B, T', Hd].
         decoder_input_ids [n_active or 1, U + 1] (one row: shared by every copy); labels [same rows, U], padded with pad_token_id
         (transformers counts `labels != pad_token_id`; `label_lengths`, one per label row, replaces that count: unpadded labels may
-        hold the pad id).
+        hold the pad id).  `enc_lengths` (_lengths_of): the valid frames per row of enc, the loss's logit lengths; the logits past them
+        carry no meaning.
         Returns SimpleNamespace(logits [n_active, T', U + 1, V + 1 + D], loss [1] or None, nll [n_active] or None).  In grad mode the
         loss's gradient w.r.t. the logits, times grad_scale, is kept for backward().
         With labels, when z + logits + dz of the whole joint do not fit `joint_budget` bytes (or `frames_per_chunk` < T' is given), the
@@ -346,6 +351,7 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         if ids.shape[0] not in (1, nb) or ids.shape[1] < 1:
             raise ops.DynError(f"decoder_input_ids {tuple(ids.shape)} must be [{nb} or 1, U + 1]")
         U1 = ids.shape[1]
+        rows_T = self._lengths_of(enc, enc_lengths, nb)
         Tc = T if labels is None else self._joint_frames(nb, T, U1, frames_per_chunk)
         grad_mode = torch.is_grad_enabled() and self._ctx is not None
         with ops.use_workspace(self._scratch()):
@@ -372,7 +378,8 @@ class ParakeetForTDT(PM.ParakeetForCTC):
                     if tlen.numel() != nb or int(tlen.min()) < 0 or int(tlen.max()) > U1 - 1:
                         raise ops.DynError(f"label_lengths {tlen.tolist()} must be {nb} (or 1) values in 0 .. {U1 - 1}")
                 tg = (lab.to(torch.int32).contiguous() if U1 > 1 else torch.zeros(nb, 1, dtype=torch.int32)).to(self.device)
-                ilen, tlen = torch.full((nb,), T, dtype=torch.int32, device=self.device), tlen.to(self.device)
+                ilen = torch.full((nb,), T, dtype=torch.int32, device=self.device) if rows_T is None else rows_T
+                tlen = tlen.to(self.device)
                 if Tc >= T:
                     loss, nll, dlogits = self._loss_whole(logits, tg, ilen, tlen, float(sigma), reduction, float(grad_scale), grad_mode)
                 else:
@@ -383,18 +390,21 @@ class ParakeetForTDT(PM.ParakeetForCTC):
         return SimpleNamespace(logits=logits, loss=loss, nll=nll, frames=T)
 
     def forward(self, input_features, decoder_input_ids=None, labels=None, attention_mask=None, reduction=None, sigma=0.0, grad_scale=1.0,
-                n_active=None, label_lengths=None, frames_per_chunk=None):
+                n_active=None, label_lengths=None, frames_per_chunk=None, input_lengths=None):
         """input_features [B, T, num_mel_bins] float32 on the device, decoder_input_ids [B or 1, U + 1] -> SimpleNamespace(logits
         [B, T', U + 1, V + 1 + D] (None when the joint was chunked: head()), loss, nll, frames = T', enc [B, T', Hd]).  `attention_mask`
-        is refused: every frame is valid."""
+        is refused.  `input_lengths` (ParakeetForCTC.forward): the valid frames per row of a ragged batch; the rows' encoder frame counts
+        become the loss's logit lengths and the result's `lengths` (host list) / `lengths_device`."""
         if attention_mask is not None:
-            raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid (ragged batches are out of scope; "
-                               "the loss kernel's per-row lengths are reached through ops.tdt_loss)")
+            raise ops.DynError("attention_mask is not built: every frame of input_features is taken as valid; a ragged batch passes "
+                               "input_lengths (parakeet_model.lengths_from_mask turns a prefix mask into them)")
         if decoder_input_ids is None:
             raise ops.DynError("forward() needs decoder_input_ids [B or 1, U + 1] (start token + labels); generate() decodes without them")
-        enc = self.encode(input_features, attention_mask)
+        enc = self.encode(input_features, attention_mask, *(() if input_lengths is None else (input_lengths,)))
         out = self.head(enc, decoder_input_ids, labels, reduction, sigma, grad_scale, n_active, label_lengths, frames_per_chunk)
         out.enc = enc
+        if input_lengths is not None:
+            out.lengths, out.lengths_device = self._enc_lengths[1:]
         return out
 
     # ------------------------------------------------------------------ backward
@@ -481,28 +491,36 @@ class ParakeetForTDT(PM.ParakeetForCTC):
             full = torch.zeros(nb, T, Hd, device=self.device, dtype=torch.float32)
             full[:rows] = de
             de = full
+        lens = ctx.get("lens")
+        if lens is not None:                             # a ragged batch: no gradient enters at a padded frame, whatever the joint left there
+            vT, lens = vT.cut(nb), lens[:, :nb]
+            de = ops.mask_rows_lens(de.contiguous(), lens[3])
         dx = self._project_enc_bwd(de, ctx, cut)
         dh = self._layers_bwd(ctx, dx, nb, T, self.position_table(T), vT, cut)
         if not self._below_frozen():
-            self._subsample_bwd(cut(ctx["sub"]), dh)
+            self._subsample_bwd(cut(ctx["sub"]), dh, *(() if lens is None else (lens,)))
         return None
 
     # ------------------------------------------------------------------ greedy decode
-    def generate(self, input_features=None, enc=None):
+    def generate(self, input_features=None, enc=None, input_lengths=None, enc_lengths=None):
         """Greedy TDT decode of input_features [B, T, num_mel_bins] (or of projected encoder states `enc` [B, T', Hd]) ->
         SimpleNamespace(tokens int32 [B, Nmax], frames int32 [B, Nmax] (the encoder frame at which each non-blank token was emitted),
-        count int32 [B], steps int32 [B]).  At most max_symbols_per_step * T' steps per row, transformers' derived max_length."""
+        count int32 [B], steps int32 [B]).  At most max_symbols_per_step * T' steps per row, transformers' derived max_length.
+        A ragged batch: `input_lengths` with input_features, `enc_lengths` (_lengths_of) with enc; every row decodes its own frames."""
         c = self.cfg
         with torch.no_grad():
             if enc is None:
                 keep = self._ctx, self._tdt
-                enc = self.encode(input_features)
+                enc = self.encode(input_features, None, *(() if input_lengths is None else (input_lengths,)))
                 self._ctx, self._tdt = keep
+            elif input_lengths is not None:
+                raise ops.DynError("generate(enc=..., input_lengths=...): input_lengths counts feature frames; pass enc_lengths with enc")
+            rows_T = self._lengths_of(enc, enc_lengths, enc.shape[0])
             enc = enc.detach().contiguous()
             B, T, _ = enc.shape
             cap = c["max_symbols_per_step"] * T
             st = self._greedy_state(B, cap)
-            valid = torch.full((B,), T, dtype=torch.int32, device=self.device)
+            valid = torch.full((B,), T, dtype=torch.int32, device=self.device) if rows_T is None else rows_T
             done = 0
             while done < cap:
                 n = min(self.greedy_chunk, cap - done)

@@ -1278,6 +1278,64 @@ int64_t dyn_prompt_relu_bwd_workspace_bytes(int64_t B, int64_t T, int64_t I);
 int dyn_prompt_relu_bwd(const float* a, const float* da, float* dz, const int32_t* prompt_ids, float* db1, float* dw1p, float beta, int64_t B,
                         int64_t T, int64_t I, int64_t Np, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ragged batches of the FastConformer encoder (transformers modeling_parakeet.py with an `attention_mask`): one frame count per batch
+ * entry, `lens` int32 [B] on the device, read when the kernel runs and clamped there as the scalar `valid` of the entries beside them
+ * (the softmax into [1, T], the others into [0, T]).  The entries above keep their signatures and their bits.
+ *   dyn_conv2d_first_fwd_lens      dyn_conv2d_first_fwd with feature frames t >= lens[b] read as zeros whatever they hold (the extractor's
+ *                                  `input_features *= mask`; ParakeetEncoderSubsamplingConv2D.forward reads frame L of an odd length L
+ *                                  before it masks anything).  Every row of z is written.
+ *   dyn_dwconv2d_s2_fwd_act_lens   dyn_dwconv2d_s2_fwd_act with input rows t >= lens_in[b] read as zeros and output rows to >= lens_out[b]
+ *                                  written as zeros: `hidden_states *= channel_mask[:, None, :, None]` after the Conv2d in front of this
+ *                                  stage (its rows past the length, the pointwise conv's bias rows included) and after this one
+ *                                  (ParakeetEncoderSubsamplingConv2D.forward, "mask the hidden states"), with no pass of their own.
+ *   dyn_dwconv2d_s2_dgrad_act_lens its data gradient: dz rows t >= lens_in[b] are zeros, du rows to >= lens_out[b] are not read.
+ *   dyn_dwconv2d_s2_wgrad_act_lens / dyn_conv2d_first_wgrad_lens
+ *                                  the weight gradients with input rows t >= lens_in[b] (feature frames t >= lens[b]) read as zeros, as
+ *                                  the forward read them; the output gradient is zero past the output length already.
+ *   dyn_mask_rows_lens             x [B, T, W] in place, rows t >= lens[b] := 0 (the same mask behind the last 1x1 Conv2d, a small tensor).
+ *   dyn_convmod_bn_fwd_lens / dyn_convmod_bn_bwd_act_lens / dyn_glu_dwconv1d_dgrad_lens
+ *                                  the three conv-module entries with lens[b] in the place of *valid: GLU rows t >= lens[b] read as zeros
+ *                                  (ParakeetEncoderConvolutionModule.forward, `hidden_states.masked_fill(all_masked_rows, 0.0)`), rows
+ *                                  past it of every output exact zeros and left out of the three column sums.  The kernels are the scalar
+ *                                  entries': they read valid[b * vstride], vstride 0 there and 1 here.
+ *   dyn_softmax_relshift_fwd_lens  dyn_softmax_relshift_fwd_len on x [B, nh, T, T] with lens[b] keys in every row of batch entry b
+ *                                  (ParakeetEncoder.forward's `attention_mask & attention_mask.transpose(1, 2)` for a valid query): columns
+ *                                  >= lens[b] are outside max and sum and get probability 0.  A padded query row is a softmax over the
+ *                                  row's valid keys: finite, without meaning.
+ *   dyn_softmax_fwd_lens           dyn_softmax_fwd_len on x [B, rows_per, L] with lens[b] keys in every row of batch entry b: the teacher-forced
+ *                                  cross-attention of CohereAsr (transformers' `encoder_attention_mask` on the scores [B, nh, S, T']); the
+ *                                  per-row count is relshift's (softmax_row.h).
+ *   dyn_seq2seq_steps_len          dyn_seq2seq_steps with enc_lens[r] (device int32 [rows], clamped into [1, n_enc]) encoder keys in row r's
+ *                                  cross-attention; the descriptor keeps its layout, n_enc is the batch's maximum (strides, LDS).  Row r is
+ *                                  bit-equal to the same row stepped alone with n_enc = enc_lens[r] at the same cross_stride.
+ * The stage entries need C % 4 == 0 and 16-byte aligned tensors (DYN_E_UNSUPPORTED otherwise); a null `lens` is DYN_E_ARG.
+ * ------------------------------------------------------------------------------------------------ */
+int dyn_conv2d_first_fwd_lens(const float* x, const float* w, const float* bias, float* z, int64_t B, int64_t T, int64_t F, int64_t C,
+                              const int32_t* lens, void* stream);
+int dyn_dwconv2d_s2_fwd_act_lens(const float* z, const float* w, const float* bias, float* u, int64_t B, int64_t T, int64_t F, int64_t C,
+                                 int32_t act, const int32_t* lens_in, const int32_t* lens_out, void* stream);
+int dyn_dwconv2d_s2_dgrad_act_lens(const float* z, const float* w, const float* du, float* dz, int64_t B, int64_t T, int64_t F, int64_t C,
+                                   int32_t act, const int32_t* lens_in, const int32_t* lens_out, void* stream);
+int dyn_dwconv2d_s2_wgrad_act_lens(const float* z, const float* du, float* dw, float* dbias, float beta, int64_t B, int64_t T, int64_t F,
+                                   int64_t C, int32_t act, const int32_t* lens_in, void* workspace, int64_t workspace_bytes, void* stream);
+int dyn_conv2d_first_wgrad_lens(const float* x, const float* dz, float* dw, float* dbias, float beta, int64_t B, int64_t T, int64_t F,
+                                int64_t C, const int32_t* lens, void* workspace, int64_t workspace_bytes, void* stream);
+int dyn_mask_rows_lens(float* x, int64_t B, int64_t T, int64_t W, const int32_t* lens, void* stream);
+int dyn_convmod_bn_fwd_lens(const float* u, const float* w, const float* cbias, const float* mean, const float* var, const float* weight,
+                            const float* bias, float* s, float* gl, float* c, const int32_t* lens, int64_t B, int64_t T, int64_t C,
+                            int64_t KW, int32_t act, float eps, void* stream);
+int dyn_convmod_bn_bwd_act_lens(const float* c, const float* mean, const float* var, const float* weight, const float* bias, const float* ds,
+                                float* dc, float* dweight, float* dbias, float* dcbias, float wgrad_beta, const int32_t* lens, int64_t B,
+                                int64_t T, int64_t C, int32_t act, float eps, void* workspace, int64_t workspace_bytes, void* stream);
+int dyn_glu_dwconv1d_dgrad_lens(const float* u, const float* w, const float* dc, float* du, const int32_t* lens, int64_t B, int64_t T,
+                                int64_t C, int64_t KW, void* stream);
+int dyn_softmax_relshift_fwd_lens(const float* x, float* y, const float* bd, int64_t B, int64_t nh, int64_t T, int64_t ld_bd,
+                                  const int32_t* lens, void* stream);
+int dyn_softmax_fwd_lens(const float* x, float* y, int64_t B, int64_t rows_per, int64_t L, int64_t ldx, int64_t ldy, const int32_t* lens,
+                         void* stream);
+int dyn_seq2seq_steps_len(const dyn_seq2seq_desc* d, const int32_t* enc_lens, int32_t t0, int32_t n_steps, int32_t n_forced, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
