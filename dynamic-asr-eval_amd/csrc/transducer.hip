@@ -10,6 +10,9 @@
 //     a chunk), and dyn_joint_bwd_chunk (de of a chunk's frames, dp accumulated over the chunks in launch order).  One set of
 //     kernels: the whole forms are the chunk forms at t0 = 0, Tc = T, so every output is bit-equal whatever the chunking.
 //   * ParakeetTDTGenerationMixin's greedy loop              dyn_tdt_greedy_steps (all state on the device, no host round trip per token)
+// and the plain RNN-T head of ParakeetForRNNT and the Nemotron models (dyn_rnnt_*): the same code without the duration head.  One
+// LatticeDims / state layout / host path; the arcs and gradient kernels are templates on DUR (a duration head or none), the only
+// compile-time switch; the lattice and the greedy pick keep one kernel per head (see the RNN-T section below).
 //
 // fp32 throughout, every sum in a fixed order, no float atomics; argument errors come back as codes before any launch.
 //
@@ -142,8 +145,9 @@ __global__ __launch_bounds__(256) void joint_bwd_p_kernel(const float* __restric
     }
 }
 
-// ---- TDT arc log-probabilities ---------------------------------------------------------------------------------------------
-struct TdtDims {
+// ---- arc log-probabilities -------------------------------------------------------------------------------------------------
+// One set of dimensions for both transducer heads.  durs.n == 0: a plain RNN-T lattice (ParakeetForRNNT), N == V1, sigma unused.
+struct LatticeDims {
     int64_t B, T, U1;       // the lattice [B, T, U1]
     int64_t t0, Tc;         // the row kernels' logits [B, Tc, U1, N] hold the frames [t0, t0 + Tc) (0, T: the whole lattice; a chunk may overhang T)
     int64_t V1, N;          // V1 = V + 1 token classes (the blank among them), N = V1 + D
@@ -153,19 +157,25 @@ struct TdtDims {
     Durs durs;
 };
 
-__device__ __forceinline__ int row_T(const int32_t* ilen, int64_t b, const TdtDims& d) { return clampi(ilen[b], 0, (int)d.T); }
-__device__ __forceinline__ int row_U(const int32_t* tlen, int64_t b, const TdtDims& d) {
+__device__ __forceinline__ int row_T(const int32_t* ilen, int64_t b, const LatticeDims& d) { return clampi(ilen[b], 0, (int)d.T); }
+__device__ __forceinline__ int row_U(const int32_t* tlen, int64_t b, const LatticeDims& d) {
     return clampi(tlen[b], 0, (int)(d.U1 - 1 < d.S ? d.U1 - 1 : d.S));
 }
+__device__ __forceinline__ int target_of(const int32_t* targets, int64_t b, int u, const LatticeDims& d) {
+    const int k = targets[b * d.S + u];
+    return k < 0 ? 0 : (k >= d.V1 ? (int)d.V1 - 1 : k);               // ids are validated on the host; never read outside the row
+}
 
-// One wave per logits row (b, tc, u) of the frames [t0, t0 + Tc): lp[cell] = (blank, label, D durations) log-probs, lse[cell] = (token lse,
-// duration lse) of the lattice cell (b, t0 + tc, u).  Rows of a chunk past the lattice's last frame are skipped.
-__global__ __launch_bounds__(64 * WPB) void tdt_arcs_kernel(const float* __restrict__ logits, const int32_t* __restrict__ targets,
-                                                            const int32_t* __restrict__ tlen, float* __restrict__ lp, float* __restrict__ lse,
-                                                            TdtDims d) {
+// One wave per logits row (b, tc, u) of the frames [t0, t0 + Tc): lp[cell] = (blank, label) log-probs (label -inf at u >= U_b),
+// lse[cell] = the token log-sum-exp of the lattice cell (b, t0 + tc, u).  DUR (a duration head, TDT): the D duration log-probs behind
+// lp's two, the duration log-sum-exp behind lse's one, sigma taken off the token log-probs.  Rows of a chunk past the lattice's last
+// frame are skipped.
+template <bool DUR>
+__global__ __launch_bounds__(64 * WPB) void arcs_kernel(const float* __restrict__ logits, const int32_t* __restrict__ targets,
+                                                        const int32_t* __restrict__ tlen, float* __restrict__ lp, float* __restrict__ lse,
+                                                        LatticeDims d) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t rows = d.B * d.Tc * d.U1;
-    const int D = d.durs.n, C = 2 + D;
     for (int64_t crow = (int64_t)blockIdx.x * WPB + w; crow < rows; crow += (int64_t)gridDim.x * WPB) {
         const int64_t u = crow % d.U1, b = crow / (d.U1 * d.Tc), t = d.t0 + (crow / d.U1) % d.Tc;
         if (t >= d.T) continue;                                       // wave-uniform
@@ -178,42 +188,44 @@ __global__ __launch_bounds__(64 * WPB) void tdt_arcs_kernel(const float* __restr
         for (int c = lane; c < d.V1; c += 64) s += expf(x[c] - m);
         s = dyn::wave_sum(s);
         const float lt = m + logf(s);
-        // durations: D <= 8 values, one lane each
-        const float dv = lane < D ? x[d.V1 + lane] : -INFINITY;
-        const float dm = dyn::wave_max(dv);
-        const float ds = dyn::wave_sum(lane < D ? expf(dv - dm) : 0.f);
-        const float ld = dm + logf(ds);
-        float* o = lp + row * C;
-        if (lane == 0) {
-            o[0] = x[d.blank] - lt - d.sigma;
-            float lab = -INFINITY;
-            if (u < row_U(tlen, b, d)) {
-                int k = targets[b * d.S + u];
-                k = k < 0 ? 0 : (k >= d.V1 ? (int)d.V1 - 1 : k);      // ids are validated on the host; never read outside the row
-                lab = x[k] - lt - d.sigma;
+        if constexpr (DUR) {
+            // durations: D <= 8 values, one lane each
+            const int D = d.durs.n;
+            const float dv = lane < D ? x[d.V1 + lane] : -INFINITY;
+            const float dm = dyn::wave_max(dv);
+            const float ds = dyn::wave_sum(lane < D ? expf(dv - dm) : 0.f);
+            const float ld = dm + logf(ds);
+            float* o = lp + row * (2 + D);
+            if (lane == 0) {
+                o[0] = x[d.blank] - lt - d.sigma;
+                o[1] = u < row_U(tlen, b, d) ? x[target_of(targets, b, (int)u, d)] - lt - d.sigma : -INFINITY;
+                lse[2 * row] = lt;
+                lse[2 * row + 1] = ld;
             }
-            o[1] = lab;
-            lse[2 * row] = lt;
-            lse[2 * row + 1] = ld;
+            if (lane < D) o[2 + lane] = dv - ld;
+        } else if (lane == 0) {
+            lp[2 * row] = x[d.blank] - lt;
+            lp[2 * row + 1] = u < row_U(tlen, b, d) ? x[target_of(targets, b, (int)u, d)] - lt : -INFINITY;
+            lse[row] = lt;
         }
-        if (lane < D) o[2 + lane] = dv - ld;
     }
 }
 
-// ---- TDT lattice -----------------------------------------------------------------------------------------------------------
-// Workspace per row b: alpha, beta [T, U1] (stored relative to the bases), abase, bbase [T + U1] (floats holding integers),
-// ll [2] = (integer part, fraction) of the row's log-likelihood, -inf fraction when the terminal is unreachable.
-struct TdtWs { float* lp; float* lse; float* alpha; float* beta; float* abase; float* bbase; float* ll; float* nll; int64_t total; };
+// ---- lattice ---------------------------------------------------------------------------------------------------------------
+// State per row b: lp [T, U1, 2 + D], lse [T, U1, 2] (D == 0: [T, U1]), alpha, beta [T, U1] (stored relative to the bases), abase, bbase
+// [T + U1] (floats holding integers), ll [2] = (integer part, fraction) of the row's log-likelihood, -inf fraction when the terminal is
+// unreachable, nll.  Per cell 20 bytes without a duration head, 44 at D = 5.
+struct LatticeWs { float* lp; float* lse; float* alpha; float* beta; float* abase; float* bbase; float* ll; float* nll; int64_t total; };
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
-TdtWs carve(void* ws, int64_t B, int64_t T, int64_t U1, int64_t D) {
-    TdtWs w;
+LatticeWs carve(void* ws, int64_t B, int64_t T, int64_t U1, int64_t D) {
+    LatticeWs w;
     char* p = (char*)ws;
     int64_t off = 0;
     const int64_t cells = B * T * U1;
     w.lp = (float*)(p + off); off += align_up(cells * (2 + D) * 4, 256);
-    w.lse = (float*)(p + off); off += align_up(cells * 2 * 4, 256);
+    w.lse = (float*)(p + off); off += align_up(cells * (D > 0 ? 2 : 1) * 4, 256);
     w.alpha = (float*)(p + off); off += align_up(cells * 4, 256);
     w.beta = (float*)(p + off); off += align_up(cells * 4, 256);
     w.abase = (float*)(p + off); off += align_up(B * (T + U1) * 4, 256);
@@ -247,7 +259,7 @@ __device__ __forceinline__ float lse_of(const float* c, int k) {
 
 __global__ __launch_bounds__(LATTICE_T) void tdt_lattice_kernel(const float* __restrict__ lp, const int32_t* __restrict__ ilen,
                                                            const int32_t* __restrict__ tlen, float* alpha, float* beta, float* abase,
-                                                           float* bbase, float* ll_out, float* __restrict__ nll, TdtDims d) {
+                                                           float* bbase, float* ll_out, float* __restrict__ nll, LatticeDims d) {
     __shared__ float wmax[2][16];       // LATTICE_T / 64 wave maxima per diagonal, double-buffered
     const int64_t b = blockIdx.x;
     const int U1 = (int)d.U1, D = d.durs.n, C = 2 + D;
@@ -365,6 +377,110 @@ __global__ __launch_bounds__(LATTICE_T) void tdt_lattice_kernel(const float* __r
     }
 }
 
+// ==== RNN-T (ParakeetForRNNT, `model_type: "parakeet_rnnt"`) =================================================================
+// The plain transducer lattice of transformers.loss.loss_rnnt.rnnt_loss (a wrapper around torchaudio.functional.rnnt_loss): no
+// duration head (durs.n == 0, N == V1), from (t, u) a blank arc to (t + 1, u) and a label arc to (t, u + 1), the terminal
+// alpha(T - 1, U) + lp_blank(T - 1, U).  Every arc advances the anti-diagonal by exactly one, so a diagonal reads only the one before it
+// and the base difference it needs is the rint() it has just taken: the integer-base scheme of the TDT lattice above with one source
+// diagonal, its offset kept in a register where tdt_lattice_kernel reads up to 2 * D bases from memory.  That is why this lattice has a
+// body of its own; everything around it (dimensions, state layout, arcs and gradient kernels, reduction, host path, the greedy LSTM /
+// projector / joint kernels) is the TDT head's code at D = 0.
+
+// log(exp(a) + exp(b)), -inf when both are
+__device__ __forceinline__ float lse2(float a, float b) {
+    const float c[2] = {a, b};
+    return lse_of(c, 2);
+}
+
+__global__ __launch_bounds__(LATTICE_T) void rnnt_lattice_kernel(const float* __restrict__ lp, const int32_t* __restrict__ ilen,
+                                                                 const int32_t* __restrict__ tlen, float* alpha, float* beta, float* abase,
+                                                                 float* bbase, float* ll_out, float* __restrict__ nll, LatticeDims d) {
+    __shared__ float wmax[2][16];
+    const int64_t b = blockIdx.x;
+    const int U1 = (int)d.U1;
+    const int T = row_T(ilen, b, d), U = row_U(tlen, b, d);
+    const float* lpb = lp + b * d.T * d.U1 * 2;
+    const int ND = T > 0 ? T + U : 0;           // diagonals 0 .. T + U - 1; T_b == 0: no cell, no terminal
+    if (blockIdx.y == 0) {
+        float* al = alpha + b * d.T * d.U1;
+        float* bs = abase + b * (d.T + d.U1);
+        float base = 0.f;
+        for (int n = 0; n < ND; ++n) {
+            float off = 0.f;                    // base of diagonal n - 1 minus this one's
+            if (n > 0) {
+                const float mx = read_max(wmax, n - 1);
+                if (mx > -INFINITY) off = -rintf(mx);
+            }
+            base -= off;
+            if (threadIdx.x == 0) bs[n] = base;
+            float tmax = -INFINITY;
+            const int u_lo = n - T + 1 > 0 ? n - T + 1 : 0, u_hi = n < U ? n : U;
+            for (int u = u_lo + (int)threadIdx.x; u <= u_hi; u += blockDim.x) {
+                const int t = n - u;
+                float v = 0.f;
+                if (n > 0) {
+                    float cb = -INFINITY, cl = -INFINITY;
+                    if (t > 0) {
+                        const int64_t s = (int64_t)(t - 1) * U1 + u;
+                        cb = al[s] + off + lpb[2 * s];
+                    }
+                    if (u > 0) {
+                        const int64_t s = (int64_t)t * U1 + u - 1;
+                        cl = al[s] + off + lpb[2 * s + 1];
+                    }
+                    v = lse2(cb, cl);
+                }
+                al[(int64_t)t * U1 + u] = v;
+                tmax = fmaxf(tmax, v);
+            }
+            publish_max(tmax, wmax, n);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            float lf = -INFINITY;
+            if (T > 0) {
+                const int64_t s = (int64_t)(T - 1) * U1 + U;
+                lf = al[s] + lpb[2 * s];
+            }
+            ll_out[2 * b] = base;
+            ll_out[2 * b + 1] = lf;
+            nll[b] = lf > -INFINITY ? -(base + lf) : INFINITY;
+        }
+    } else {
+        float* be = beta + b * d.T * d.U1;
+        float* bs = bbase + b * (d.T + d.U1);
+        float base = 0.f;
+        for (int n = ND - 1; n >= 0; --n) {
+            float off = 0.f;                    // base of diagonal n + 1 minus this one's
+            if (n < ND - 1) {
+                const float mx = read_max(wmax, n + 1);
+                if (mx > -INFINITY) off = -rintf(mx);
+            }
+            base -= off;
+            if (threadIdx.x == 0) bs[n] = base;
+            float tmax = -INFINITY;
+            const int u_lo = n - T + 1 > 0 ? n - T + 1 : 0, u_hi = n < U ? n : U;
+            for (int u = u_lo + (int)threadIdx.x; u <= u_hi; u += blockDim.x) {
+                const int t = n - u;
+                const int64_t s = (int64_t)t * U1 + u;
+                float v;
+                if (t == T - 1 && u == U) {
+                    v = lpb[2 * s];                                   // the terminal, absolute 0 behind it (base is 0 here)
+                } else {
+                    float cb = -INFINITY, cl = -INFINITY;
+                    if (t + 1 < T) cb = lpb[2 * s] + be[s + U1] + off;
+                    if (u < U) cl = lpb[2 * s + 1] + be[s + 1] + off;
+                    v = lse2(cb, cl);
+                }
+                be[s] = v;
+                tmax = fmaxf(tmax, v);
+            }
+            publish_max(tmax, wmax, n);
+            __syncthreads();
+        }
+    }
+}
+
 // d loss / d nll_b of the reduction (tdt_loss's five; "none" as "sum")
 __device__ __forceinline__ float row_weight(int reduction, const int32_t* tlen, int64_t B, int64_t b) {
     if (reduction == 1) return 1.f / (float)B;                                   // mean_batch
@@ -387,20 +503,22 @@ __global__ void tdt_loss_reduce_kernel(const float* __restrict__ nll, const int3
     *loss = reduction == 1 || reduction == 2 ? s / (float)B : (reduction == 3 ? s / vol : s);
 }
 
-// ---- TDT gradient ----------------------------------------------------------------------------------------------------------
+// ---- gradient --------------------------------------------------------------------------------------------------------------
 // One wave per logits row (b, t, u).  With the arc posteriors g_b[i] (blank arc of duration i), g_l[i] (label arc), Gb = sum g_b,
 // Gl = sum g_l: dtoken[v] = softmax_v * (Gb + Gl) - Gb [v = blank] - Gl [v = target], ddur[i] = softmax_i * (Gb + Gl) - g_b[i] - g_l[i],
 // times grad_scale * row weight.  Rows at t >= T_b or u > U_b, and every row of an unreachable lattice, are zeros.  grad may be logits.
 // logits / grad hold the frames [t0, t0 + Tc) ([B, Tc, U1, N]); lp, lse, alpha, beta are the whole lattice's.
-__global__ __launch_bounds__(64 * WPB) void tdt_grad_kernel(const float* logits, const int32_t* __restrict__ targets,
-                                                            const int32_t* __restrict__ ilen, const int32_t* __restrict__ tlen,
-                                                            const float* __restrict__ lp, const float* __restrict__ lse,
-                                                            const float* __restrict__ alpha, const float* __restrict__ beta,
-                                                            const float* __restrict__ abase, const float* __restrict__ bbase,
-                                                            const float* __restrict__ ll, float* grad, float grad_scale, int reduction, TdtDims d) {
+// DUR: lane i < D holds the posteriors of duration i, summed in a fixed order.  Without a duration head there is one blank arc
+// (to (t + 1, u); beta = 0 behind the terminal cell (T - 1, U)) and one label arc (to (t, u + 1)): Gb and Gl themselves, wave-uniform.
+template <bool DUR>
+__global__ __launch_bounds__(64 * WPB) void grad_kernel(const float* logits, const int32_t* __restrict__ targets,
+                                                        const int32_t* __restrict__ ilen, const int32_t* __restrict__ tlen,
+                                                        const float* __restrict__ lp, const float* __restrict__ lse,
+                                                        const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                        const float* __restrict__ abase, const float* __restrict__ bbase,
+                                                        const float* __restrict__ ll, float* grad, float grad_scale, int reduction, LatticeDims d) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t rows = d.B * d.Tc * d.U1;
-    const int D = d.durs.n, C = 2 + D, U1 = (int)d.U1;
     for (int64_t row = (int64_t)blockIdx.x * WPB + w; row < rows; row += (int64_t)gridDim.x * WPB) {
         const int u = (int)(row % d.U1);
         const int64_t b = row / (d.U1 * d.Tc), tt = d.t0 + (row / d.U1) % d.Tc;      // a chunk's frame may lie past the lattice: zeros
@@ -413,50 +531,64 @@ __global__ __launch_bounds__(64 * WPB) void tdt_grad_kernel(const float* logits,
             for (int c = lane; c < d.N; c += 64) g[c] = 0.f;
             continue;
         }
-        const int ND = T + U, n = t + u;
+        const int n = t + u;
         const int64_t cell = (b * d.T + t) * d.U1 + u;
-        const float* be = beta + b * d.T * d.U1;
         const float* ab = abase + b * (d.T + d.U1);
         const float* bb = bbase + b * (d.T + d.U1);
         const float a = alpha[cell], abn = ab[n];
-        const float* lpc = lp + cell * C;
-        const float lb = lpc[0], llab = lpc[1];
-        // lane i < D holds the posteriors of duration i (uniform control flow: every lane evaluates its own duration or nothing)
-        float gb = 0.f, gl = 0.f;
-        if (lane < D && a > -INFINITY) {
-            const int dur = d.durs.d[lane], tn = t + dur;
-            const float ld = lpc[2 + lane];
-            if (dur > 0) {
+        float gb = 0.f, gl = 0.f;        // DUR: this lane's duration; else the row's two arcs, every lane the same
+        float Gb = 0.f, Gl = 0.f;
+        if constexpr (DUR) {
+            const int D = d.durs.n, U1 = (int)d.U1, ND = T + U;
+            const float* be = beta + b * d.T * d.U1;
+            const float* lpc = lp + cell * (2 + D);
+            const float lb = lpc[0], llab = lpc[1];
+            // uniform control flow: every lane evaluates its own duration or nothing
+            if (lane < D && a > -INFINITY) {
+                const int dur = d.durs.d[lane], tn = t + dur;
+                const float ld = lpc[2 + lane];
+                if (dur > 0) {
+                    float e = -INFINITY;
+                    if (tn == T && u == U) e = a + lb + ld + ((abn - li) - lf);
+                    else if (tn < T) e = a + lb + ld + be[(int64_t)tn * U1 + u] + ((abn + bb[n + dur] - li) - lf);
+                    gb = e > -INFINITY ? expf(e) : 0.f;
+                }
+                if (u < U && tn < T && n + dur + 1 < ND) {
+                    const float e = a + llab + ld + be[(int64_t)tn * U1 + u + 1] + ((abn + bb[n + dur + 1] - li) - lf);
+                    gl = e > -INFINITY ? expf(e) : 0.f;
+                }
+            }
+            for (int i = 0; i < D; ++i) {        // fixed order: duration 0, 1, ..
+                Gb += __shfl(gb, i, 64);
+                Gl += __shfl(gl, i, 64);
+            }
+        } else {
+            if (a > -INFINITY) {
+                const float lb = lp[2 * cell], llab = lp[2 * cell + 1];
                 float e = -INFINITY;
-                if (tn == T && u == U) e = a + lb + ld + ((abn - li) - lf);
-                else if (tn < T) e = a + lb + ld + be[(int64_t)tn * U1 + u] + ((abn + bb[n + dur] - li) - lf);
+                if (t == T - 1 && u == U) e = a + lb + ((abn - li) - lf);
+                else if (t + 1 < T) e = a + lb + beta[cell + d.U1] + ((abn + bb[n + 1] - li) - lf);
                 gb = e > -INFINITY ? expf(e) : 0.f;
+                if (u < U) {
+                    e = a + llab + beta[cell + 1] + ((abn + bb[n + 1] - li) - lf);
+                    gl = e > -INFINITY ? expf(e) : 0.f;
+                }
             }
-            if (u < U && tn < T && n + dur + 1 < ND) {
-                const float e = a + llab + ld + be[(int64_t)tn * U1 + u + 1] + ((abn + bb[n + dur + 1] - li) - lf);
-                gl = e > -INFINITY ? expf(e) : 0.f;
-            }
-        }
-        float Gb = 0.f, Gl = 0.f;        // fixed order: duration 0, 1, ..
-        for (int i = 0; i < D; ++i) {
-            Gb += __shfl(gb, i, 64);
-            Gl += __shfl(gl, i, 64);
+            Gb = gb;
+            Gl = gl;
         }
         const float G = Gb + Gl;
         const float sc = grad_scale * row_weight(reduction, tlen, d.B, b);
-        const float lt = lse[2 * cell], ldn = lse[2 * cell + 1];
-        int tgt = -1;
-        if (u < U) {
-            tgt = targets[b * d.S + u];
-            tgt = tgt < 0 ? 0 : (tgt >= d.V1 ? (int)d.V1 - 1 : tgt);
-        }
+        const float lt = lse[DUR ? 2 * cell : cell];
+        const int tgt = u < U ? target_of(targets, b, u, d) : -1;
         for (int c = lane; c < d.V1; c += 64) {
             float v = expf(x[c] - lt) * G;
             if (c == d.blank) v -= Gb;
             if (c == tgt) v -= Gl;
             g[c] = v * sc;
         }
-        if (lane < D) g[d.V1 + lane] = (expf(x[d.V1 + lane] - ldn) * G - (gb + gl)) * sc;
+        if constexpr (DUR)
+            if (lane < d.durs.n) g[d.V1 + lane] = (expf(x[d.V1 + lane] - lse[2 * cell + 1]) * G - (gb + gl)) * sc;
     }
 }
 
@@ -468,7 +600,7 @@ struct GreedyArgs {
     const float* const* lstm;    // device array [4 * L]: w_ih, w_hh, b_ih, b_hh per layer
     const float* proj_w; const float* proj_b;     // [Hd, Hd], [Hd]
     const float* head_w; const float* head_b;     // [N, Hd], [N]
-    int32_t* istate;             // [6, B]: frame, last token, emit flag, done flag, count, steps
+    int32_t* istate;             // [6, B]: frame, last token, emit flag, done flag, count, steps; RNN-T [7, B]: the symbols of the frame
     float* h; float* c; float* h_new;             // [L, B, Hd] each
     float* dec;                  // [B, Hd] cached projector output
     float* logits;               // [B, N]
@@ -478,7 +610,7 @@ struct GreedyArgs {
 };
 
 __device__ __forceinline__ int32_t* ist(const GreedyArgs& a, int which) { return a.istate + (int64_t)which * a.B; }
-enum { S_FRAME = 0, S_TOKEN = 1, S_EMIT = 2, S_DONE = 3, S_COUNT = 4, S_STEPS = 5 };
+enum { S_FRAME = 0, S_TOKEN = 1, S_EMIT = 2, S_DONE = 3, S_COUNT = 4, S_STEPS = 5, S_SYMBOLS = 6 };
 
 __device__ __forceinline__ float wave_dot(const float* __restrict__ w, const float* __restrict__ x, int K, int lane) {
     float s = 0.f;
@@ -547,17 +679,15 @@ __global__ __launch_bounds__(256) void greedy_joint_kernel(const GreedyArgs a) {
     if (lane == 0) a.logits[(int64_t)b * a.N + n] = s + a.head_b[n];
 }
 
-// argmax over the token and the duration logits (first maximum wins), then the step's bookkeeping: one workgroup per row
-__global__ __launch_bounds__(256) void greedy_pick_kernel(const GreedyArgs a) {
+// The argmax of a workgroup of 256 over the V1 token logits x (first maximum wins; no finite maximum: the blank).  One barrier; the
+// result is thread 0's alone.
+__device__ __forceinline__ int token_argmax(const float* x, int V1, int blank) {
     __shared__ float rv[4];
     __shared__ int ri[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int b = blockIdx.x;
-    if (ist(a, S_DONE)[b]) return;                 // uniform: the flag is written after the barrier below
-    const float* x = a.logits + (int64_t)b * a.N;
     float bv = -INFINITY;
     int bi = 0x7fffffff;
-    for (int c = threadIdx.x; c < a.V1; c += blockDim.x)
+    for (int c = threadIdx.x; c < V1; c += blockDim.x)
         if (better(x[c], c, bv, bi)) { bv = x[c]; bi = c; }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -567,10 +697,19 @@ __global__ __launch_bounds__(256) void greedy_pick_kernel(const GreedyArgs a) {
     }
     if (lane == 0) { rv[w] = bv; ri[w] = bi; }
     __syncthreads();
-    if (threadIdx.x != 0) return;
+    if (threadIdx.x != 0) return blank;
     for (int i = 1; i < 4; ++i)
         if (better(rv[i], ri[i], bv, bi)) { bv = rv[i]; bi = ri[i]; }
-    const int tok = bi == 0x7fffffff ? a.blank : bi;
+    return bi == 0x7fffffff ? blank : bi;
+}
+
+// argmax over the token and the duration logits (first maximum wins), then the step's bookkeeping: one workgroup per row
+__global__ __launch_bounds__(256) void greedy_pick_kernel(const GreedyArgs a) {
+    const int b = blockIdx.x;
+    if (ist(a, S_DONE)[b]) return;                 // uniform: the flag is written after the barrier of token_argmax
+    const float* x = a.logits + (int64_t)b * a.N;
+    const int tok = token_argmax(x, a.V1, a.blank);
+    if (threadIdx.x != 0) return;
     int di = 0;
     float dv = x[a.V1];
     for (int i = 1; i < a.durs.n; ++i)
@@ -592,6 +731,48 @@ __global__ __launch_bounds__(256) void greedy_pick_kernel(const GreedyArgs a) {
     ist(a, S_TOKEN)[b] = tok;
     ist(a, S_FRAME)[b] = frame + adv;
     if (frame + adv >= a.valid[b] || steps >= a.max_steps || count >= a.n_max) ist(a, S_DONE)[b] = 1;
+}
+
+// argmax over the row (first maximum wins), then ParakeetRNNTGenerationMixin._update_model_kwargs_for_generation: a blank advances the
+// frame and resets the per-frame symbol counter; a non-blank is emitted and counted, and when the counter reaches max_symbols the frame
+// advances anyway and the counter resets (the forced step's token is still emitted and fed to the prediction network).
+// `frame_base`: added to the frame RECORDED with an emitted token (0 offline; the absolute frame of a streamed chunk's frame 0).
+__global__ __launch_bounds__(256) void rnnt_greedy_pick_kernel(const GreedyArgs a, int max_symbols, int frame_base) {
+    const int b = blockIdx.x;
+    if (ist(a, S_DONE)[b]) return;                 // uniform: the flag is written after the barrier of token_argmax
+    const int tok = token_argmax(a.logits + (int64_t)b * a.N, a.V1, a.blank);
+    if (threadIdx.x != 0) return;
+    const bool is_blank = tok == a.blank;
+    const int frame = ist(a, S_FRAME)[b];
+    const int symbols = is_blank ? 0 : ist(a, S_SYMBOLS)[b] + 1;
+    const bool forced = symbols >= max_symbols;
+    const int adv = is_blank || forced ? 1 : 0;
+    int count = ist(a, S_COUNT)[b];
+    if (!is_blank && count < a.n_max) {
+        a.tokens[(int64_t)b * a.n_max + count] = tok;
+        a.frames[(int64_t)b * a.n_max + count] = frame + frame_base;
+        ++count;
+    }
+    const int steps = ist(a, S_STEPS)[b] + 1;
+    ist(a, S_COUNT)[b] = count;
+    ist(a, S_STEPS)[b] = steps;
+    ist(a, S_EMIT)[b] = is_blank ? 0 : 1;
+    ist(a, S_TOKEN)[b] = tok;
+    ist(a, S_FRAME)[b] = frame + adv;
+    ist(a, S_SYMBOLS)[b] = adv ? 0 : symbols;
+    if (frame + adv >= a.valid[b] || steps >= a.max_steps || count >= a.n_max) ist(a, S_DONE)[b] = 1;
+}
+
+// A streamed decode moves on to the next chunk of encoder frames: the frame pointer back to 0, the done flags, the per-frame symbol
+// counter and the chunk's output count and step count cleared.  h / c, the cached projector output, the last token and the emit flag stay.
+__global__ void rnnt_greedy_rebase_kernel(const GreedyArgs a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    ist(a, S_FRAME)[b] = 0;
+    ist(a, S_DONE)[b] = 0;
+    ist(a, S_COUNT)[b] = 0;
+    ist(a, S_STEPS)[b] = 0;
+    ist(a, S_SYMBOLS)[b] = 0;
 }
 
 int check_durs(const int32_t* durations, int64_t D, Durs& out, const char* who) {
@@ -679,58 +860,52 @@ extern "C" int dyn_joint_bwd_chunk(const float* dz, const float* z, float* de, f
                      stream);
 }
 
-extern "C" int64_t dyn_tdt_loss_workspace_bytes(int64_t B, int64_t T, int64_t U1, int64_t D) {
-    if (B <= 0 || T <= 0 || U1 <= 0 || D <= 0) return -1;
-    return carve(nullptr, B, T, U1, D).total;
-}
-
-extern "C" int dyn_tdt_loss_workspace_layout(int64_t B, int64_t T, int64_t U1, int64_t D, int64_t* offsets8) {
-    DYN_REQUIRE(offsets8 && B > 0 && T > 0 && U1 > 0 && D > 0 && D <= MAX_DUR, DYN_E_ARG, "dyn_tdt_loss_workspace_layout: bad arguments");
-    const TdtWs w = carve(nullptr, B, T, U1, D);
-    const float* ps[8] = {w.lp, w.lse, w.alpha, w.beta, w.abase, w.bbase, w.ll, w.nll};
-    for (int i = 0; i < 8; ++i) offsets8[i] = (const char*)ps[i] - (const char*)nullptr;
-    return DYN_OK;
-}
-
+// ---- the loss entries: one host path, `tdt` false = no duration head (durations null, D = 0, sigma unused) ------------------------
 namespace {
 
-// What every TDT entry does before its launches: sizes, the duration list, the lattice state carved out of `state` (refused by name over
+const char* const OVER_STATE = "chunking the lattice state is not built: only the joint streams over frame chunks";
+
+// What every loss entry does before its launches: sizes, the duration list, the lattice state carved out of `state` (refused by name over
 // the budget, `over` ends that message), the kernels' dimensions for the whole lattice (t0 = 0, Tc = T).
-int tdt_setup(const char* who, const char* over, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D, int64_t S,
-              int32_t blank, float sigma, void* state, int64_t state_bytes, int64_t budget_bytes, TdtDims& d, TdtWs& w) {
+int setup(const char* who, const char* over, bool tdt, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+          int64_t S, int32_t blank, float sigma, void* state, int64_t state_bytes, int64_t budget_bytes, LatticeDims& d, LatticeWs& w) {
     DYN_REQUIRE(B > 0 && T > 0 && U1 > 0 && V1 > 0 && S >= 1 && blank >= 0 && blank < V1, DYN_E_ARG, "%s: bad arguments", who);
-    DYN_REQUIRE(T + U1 < (1 << 24), DYN_E_UNSUPPORTED, "%s: %lld diagonals unsupported", who, (long long)(T + U1));
-    if (const int rc = check_durs(durations, D, d.durs, who)) return rc;
-    w = carve(state, B, T, U1, D);
+    DYN_REQUIRE(V1 < (1 << 30) && U1 < (1 << 24) && T + U1 < (1 << 24), DYN_E_UNSUPPORTED, "%s: %lld diagonals / %lld classes unsupported", who,
+                (long long)(T + U1), (long long)V1);
+    d.durs = Durs{};
+    if (tdt)
+        if (const int rc = check_durs(durations, D, d.durs, who)) return rc;
+    w = carve(state, B, T, U1, d.durs.n);
     DYN_REQUIRE(budget_bytes <= 0 || w.total <= budget_bytes, DYN_E_WORKSPACE,
                 "%s: the lattice of [%lld, %lld, %lld] needs %lld bytes, over the workspace budget of %lld (%s)", who, (long long)B, (long long)T,
                 (long long)U1, (long long)w.total, (long long)budget_bytes, over);
     DYN_REQUIRE(state && state_bytes >= w.total, DYN_E_WORKSPACE, "%s: workspace %lld < %lld bytes", who, (long long)state_bytes,
                 (long long)w.total);
-    d.B = B; d.T = T; d.U1 = U1; d.t0 = 0; d.Tc = T; d.V1 = V1; d.N = V1 + D; d.S = S; d.blank = blank; d.sigma = sigma;
+    d.B = B; d.T = T; d.U1 = U1; d.t0 = 0; d.Tc = T; d.V1 = V1; d.N = V1 + d.durs.n; d.S = S; d.blank = blank; d.sigma = sigma;
     return DYN_OK;
 }
 
 // the frames [t0, t0 + Tc) of a chunk entry; the rows of one launch are counted in int64, the grid is capped (grid_for)
-int tdt_chunk(const char* who, int64_t t0, int64_t Tc, TdtDims& d) {
+int chunk(const char* who, int64_t t0, int64_t Tc, LatticeDims& d) {
     DYN_REQUIRE(t0 >= 0 && t0 < d.T && Tc > 0 && Tc < (1 << 24), DYN_E_ARG, "%s: the chunk [%lld, %lld + %lld) must start inside the %lld frames",
                 who, (long long)t0, (long long)t0, (long long)Tc, (long long)d.T);
     d.t0 = t0; d.Tc = Tc;
     return DYN_OK;
 }
 
-void launch_arcs(const float* logits, const int32_t* targets, const int32_t* tlen, const TdtWs& w, const TdtDims& d, hipStream_t st) {
-    hipLaunchKernelGGL(tdt_arcs_kernel, dim3(grid_for(d.B * d.Tc * d.U1, WPB)), dim3(64 * WPB), 0, st, logits, targets, tlen, w.lp, w.lse, d);
+void launch_arcs(const float* logits, const int32_t* targets, const int32_t* tlen, const LatticeWs& w, const LatticeDims& d, hipStream_t st) {
+    hipLaunchKernelGGL(d.durs.n ? arcs_kernel<true> : arcs_kernel<false>, dim3(grid_for(d.B * d.Tc * d.U1, WPB)), dim3(64 * WPB), 0, st, logits,
+                       targets, tlen, w.lp, w.lse, d);
 }
 
 // alpha (and with `both` beta) over the anti-diagonals, the reduction, the per-row nll
 int launch_lattice(const char* who, const int32_t* ilen, const int32_t* tlen, int reduction, float* loss, float* nll_per_row, bool both,
-                   const TdtWs& w, const TdtDims& d, hipStream_t st) {
+                   const LatticeWs& w, const LatticeDims& d, hipStream_t st) {
     const int64_t diag = d.T < d.U1 ? d.T : d.U1;
     int threads = (int)((diag + 63) / 64 * 64);
     if (threads > LATTICE_T) threads = LATTICE_T;
-    hipLaunchKernelGGL(tdt_lattice_kernel, dim3((unsigned)d.B, both ? 2u : 1u), dim3(threads), 0, st, w.lp, ilen, tlen, w.alpha, w.beta, w.abase,
-                       w.bbase, w.ll, w.nll, d);
+    hipLaunchKernelGGL(d.durs.n ? tdt_lattice_kernel : rnnt_lattice_kernel, dim3((unsigned)d.B, both ? 2u : 1u), dim3(threads), 0, st, w.lp, ilen,
+                       tlen, w.alpha, w.beta, w.abase, w.bbase, w.ll, w.nll, d);
     hipLaunchKernelGGL(tdt_loss_reduce_kernel, dim3(1), dim3(64), 0, st, w.nll, tlen, loss, d.B, reduction);
     if (nll_per_row) {
         hipError_t e = hipMemcpyAsync(nll_per_row, w.nll, d.B * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -740,516 +915,170 @@ int launch_lattice(const char* who, const int32_t* ilen, const int32_t* tlen, in
 }
 
 void launch_grad(const float* logits, const int32_t* targets, const int32_t* ilen, const int32_t* tlen, float* grad, float grad_scale,
-                 int reduction, const TdtWs& w, const TdtDims& d, hipStream_t st) {
-    hipLaunchKernelGGL(tdt_grad_kernel, dim3(grid_for(d.B * d.Tc * d.U1, WPB)), dim3(64 * WPB), 0, st, logits, targets, ilen, tlen, w.lp, w.lse,
-                       w.alpha, w.beta, w.abase, w.bbase, w.ll, grad, grad_scale, reduction, d);
+                 int reduction, const LatticeWs& w, const LatticeDims& d, hipStream_t st) {
+    hipLaunchKernelGGL(d.durs.n ? grad_kernel<true> : grad_kernel<false>, dim3(grid_for(d.B * d.Tc * d.U1, WPB)), dim3(64 * WPB), 0, st, logits,
+                       targets, ilen, tlen, w.lp, w.lse, w.alpha, w.beta, w.abase, w.bbase, w.ll, grad, grad_scale, reduction, d);
 }
 
-const char* const OVER_STATE = "chunking the lattice state is not built: only the joint streams over frame chunks";
+int loss(const char* who, const char* over, bool tdt, const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1,
+         const int32_t* durations, int64_t D, const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths,
+         int32_t blank, float sigma, int32_t reduction, float grad_scale, float* loss_out, float* nll_per_row, float* grad, void* workspace,
+         int64_t workspace_bytes, int64_t workspace_budget_bytes, void* stream) {
+    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && loss_out && reduction >= 0 && reduction <= 4, DYN_E_ARG,
+                "%s: bad arguments", who);
+    LatticeDims d;
+    LatticeWs w;
+    if (const int rc = setup(who, over, tdt, B, T, U1, V1, durations, D, S, blank, sigma, workspace, workspace_bytes, workspace_budget_bytes, d, w))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    launch_arcs(logits, targets, target_lengths, w, d, st);
+    if (const int rc = launch_lattice(who, logit_lengths, target_lengths, (int)reduction, loss_out, nll_per_row, grad != nullptr, w, d, st)) return rc;
+    if (grad) launch_grad(logits, targets, logit_lengths, target_lengths, grad, grad_scale, (int)reduction, w, d, st);
+    return dyn::check_launch(who);
+}
+
+int arcs_chunk(const char* who, bool tdt, const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+               const int32_t* targets, int64_t S, const int32_t* target_lengths, int32_t blank, float sigma, int64_t t0, int64_t Tc, void* state,
+               int64_t state_bytes, int64_t state_budget_bytes, void* stream) {
+    DYN_REQUIRE(logits && targets && target_lengths, DYN_E_ARG, "%s: bad arguments", who);
+    LatticeDims d;
+    LatticeWs w;
+    if (const int rc = setup(who, OVER_STATE, tdt, B, T, U1, V1, durations, D, S, blank, sigma, state, state_bytes, state_budget_bytes, d, w))
+        return rc;
+    if (const int rc = chunk(who, t0, Tc, d)) return rc;
+    launch_arcs(logits, targets, target_lengths, w, d, (hipStream_t)stream);
+    return dyn::check_launch(who);
+}
+
+int lattice_run(const char* who, bool tdt, int64_t B, int64_t T, int64_t U1, const int32_t* durations, int64_t D, int64_t S,
+                const int32_t* logit_lengths, const int32_t* target_lengths, int32_t reduction, float* loss_out, float* nll_per_row,
+                int32_t want_beta, void* state, int64_t state_bytes, int64_t state_budget_bytes, void* stream) {
+    DYN_REQUIRE(logit_lengths && target_lengths && loss_out && reduction >= 0 && reduction <= 4, DYN_E_ARG, "%s: bad arguments", who);
+    LatticeDims d;
+    LatticeWs w;
+    // the lattice reads neither the vocabulary nor the blank: one token class stands in for them
+    if (const int rc = setup(who, OVER_STATE, tdt, B, T, U1, 1, durations, D, S, 0, 0.f, state, state_bytes, state_budget_bytes, d, w)) return rc;
+    if (const int rc = launch_lattice(who, logit_lengths, target_lengths, (int)reduction, loss_out, nll_per_row, want_beta != 0, w, d,
+                                      (hipStream_t)stream))
+        return rc;
+    return dyn::check_launch(who);
+}
+
+int grad_chunk(const char* who, bool tdt, const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+               const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank, int32_t reduction,
+               float grad_scale, int64_t t0, int64_t Tc, float* grad, const void* state, int64_t state_bytes, void* stream) {
+    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && grad && reduction >= 0 && reduction <= 4, DYN_E_ARG, "%s: bad arguments",
+                who);
+    LatticeDims d;
+    LatticeWs w;
+    if (const int rc = setup(who, OVER_STATE, tdt, B, T, U1, V1, durations, D, S, blank, 0.f, const_cast<void*>(state), state_bytes, 0, d, w))
+        return rc;
+    if (const int rc = chunk(who, t0, Tc, d)) return rc;
+    launch_grad(logits, targets, logit_lengths, target_lengths, grad, grad_scale, (int)reduction, w, d, (hipStream_t)stream);
+    return dyn::check_launch(who);
+}
+
+void layout(int64_t B, int64_t T, int64_t U1, int64_t D, int64_t* offsets8) {
+    const LatticeWs w = carve(nullptr, B, T, U1, D);
+    const float* ps[8] = {w.lp, w.lse, w.alpha, w.beta, w.abase, w.bbase, w.ll, w.nll};
+    for (int i = 0; i < 8; ++i) offsets8[i] = (const char*)ps[i] - (const char*)nullptr;
+}
 
 }  // namespace
+
+extern "C" int64_t dyn_tdt_loss_workspace_bytes(int64_t B, int64_t T, int64_t U1, int64_t D) {
+    if (B <= 0 || T <= 0 || U1 <= 0 || D <= 0) return -1;
+    return carve(nullptr, B, T, U1, D).total;
+}
+
+extern "C" int64_t dyn_rnnt_loss_workspace_bytes(int64_t B, int64_t T, int64_t U1) {
+    if (B <= 0 || T <= 0 || U1 <= 0) return -1;
+    return carve(nullptr, B, T, U1, 0).total;
+}
+
+extern "C" int dyn_tdt_loss_workspace_layout(int64_t B, int64_t T, int64_t U1, int64_t D, int64_t* offsets8) {
+    DYN_REQUIRE(offsets8 && B > 0 && T > 0 && U1 > 0 && D > 0 && D <= MAX_DUR, DYN_E_ARG, "dyn_tdt_loss_workspace_layout: bad arguments");
+    layout(B, T, U1, D, offsets8);
+    return DYN_OK;
+}
+
+extern "C" int dyn_rnnt_loss_workspace_layout(int64_t B, int64_t T, int64_t U1, int64_t* offsets8) {
+    DYN_REQUIRE(offsets8 && B > 0 && T > 0 && U1 > 0, DYN_E_ARG, "dyn_rnnt_loss_workspace_layout: bad arguments");
+    layout(B, T, U1, 0, offsets8);
+    return DYN_OK;
+}
 
 extern "C" int dyn_tdt_loss(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
                             const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank,
                             float sigma, int32_t reduction, float grad_scale, float* loss, float* nll_per_row, float* grad,
                             void* workspace, int64_t workspace_bytes, int64_t workspace_budget_bytes, void* stream) {
-    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && loss && reduction >= 0 && reduction <= 4, DYN_E_ARG,
-                "dyn_tdt_loss: bad arguments");
-    TdtDims d;
-    TdtWs w;
-    if (const int rc = tdt_setup("dyn_tdt_loss", "chunking over t is not built", B, T, U1, V1, durations, D, S, blank, sigma, workspace,
-                                 workspace_bytes, workspace_budget_bytes, d, w))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    launch_arcs(logits, targets, target_lengths, w, d, st);
-    if (const int rc = launch_lattice("dyn_tdt_loss", logit_lengths, target_lengths, (int)reduction, loss, nll_per_row, grad != nullptr, w, d, st))
-        return rc;
-    if (grad) launch_grad(logits, targets, logit_lengths, target_lengths, grad, grad_scale, (int)reduction, w, d, st);
-    return dyn::check_launch("dyn_tdt_loss");
-}
-
-extern "C" int dyn_tdt_arcs_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
-                                  const int32_t* targets, int64_t S, const int32_t* target_lengths, int32_t blank, float sigma, int64_t t0,
-                                  int64_t Tc, void* state, int64_t state_bytes, int64_t state_budget_bytes, void* stream) {
-    DYN_REQUIRE(logits && targets && target_lengths, DYN_E_ARG, "dyn_tdt_arcs_chunk: bad arguments");
-    TdtDims d;
-    TdtWs w;
-    if (const int rc = tdt_setup("dyn_tdt_arcs_chunk", OVER_STATE, B, T, U1, V1, durations, D, S, blank, sigma, state, state_bytes,
-                                 state_budget_bytes, d, w))
-        return rc;
-    if (const int rc = tdt_chunk("dyn_tdt_arcs_chunk", t0, Tc, d)) return rc;
-    launch_arcs(logits, targets, target_lengths, w, d, (hipStream_t)stream);
-    return dyn::check_launch("dyn_tdt_arcs_chunk");
-}
-
-extern "C" int dyn_tdt_lattice_run(int64_t B, int64_t T, int64_t U1, const int32_t* durations, int64_t D, int64_t S,
-                                   const int32_t* logit_lengths, const int32_t* target_lengths, int32_t reduction, float* loss,
-                                   float* nll_per_row, int32_t want_beta, void* state, int64_t state_bytes, int64_t state_budget_bytes,
-                                   void* stream) {
-    DYN_REQUIRE(logit_lengths && target_lengths && loss && reduction >= 0 && reduction <= 4, DYN_E_ARG, "dyn_tdt_lattice_run: bad arguments");
-    TdtDims d;
-    TdtWs w;
-    // the lattice reads neither the vocabulary nor the blank: one token class stands in for them
-    if (const int rc = tdt_setup("dyn_tdt_lattice_run", OVER_STATE, B, T, U1, 1, durations, D, S, 0, 0.f, state, state_bytes, state_budget_bytes,
-                                 d, w))
-        return rc;
-    if (const int rc = launch_lattice("dyn_tdt_lattice_run", logit_lengths, target_lengths, (int)reduction, loss, nll_per_row, want_beta != 0, w, d,
-                                      (hipStream_t)stream))
-        return rc;
-    return dyn::check_launch("dyn_tdt_lattice_run");
-}
-
-extern "C" int dyn_tdt_grad_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
-                                  const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths,
-                                  int32_t blank, int32_t reduction, float grad_scale, int64_t t0, int64_t Tc, float* grad, const void* state,
-                                  int64_t state_bytes, void* stream) {
-    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && grad && reduction >= 0 && reduction <= 4, DYN_E_ARG,
-                "dyn_tdt_grad_chunk: bad arguments");
-    TdtDims d;
-    TdtWs w;
-    if (const int rc = tdt_setup("dyn_tdt_grad_chunk", OVER_STATE, B, T, U1, V1, durations, D, S, blank, 0.f, const_cast<void*>(state), state_bytes,
-                                 0, d, w))
-        return rc;
-    if (const int rc = tdt_chunk("dyn_tdt_grad_chunk", t0, Tc, d)) return rc;
-    launch_grad(logits, targets, logit_lengths, target_lengths, grad, grad_scale, (int)reduction, w, d, (hipStream_t)stream);
-    return dyn::check_launch("dyn_tdt_grad_chunk");
-}
-
-extern "C" int dyn_tdt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
-                                    const float* proj_w, const float* proj_b, const float* head_w, const float* head_b, int32_t* istate,
-                                    float* h, float* c, float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames,
-                                    int64_t B, int64_t T, int64_t Hd, int64_t layers, int64_t V1, const int32_t* durations, int64_t D,
-                                    int32_t blank, int64_t n_max, int64_t max_steps, int32_t n_steps, void* stream) {
-    DYN_REQUIRE(enc && valid && embed && lstm_ptrs && proj_w && proj_b && head_w && head_b && istate && h && c && h_new && dec && logits &&
-                    tokens && frames, DYN_E_ARG, "dyn_tdt_greedy_steps: null pointer");
-    DYN_REQUIRE(B > 0 && B <= 65535 && T > 0 && Hd > 0 && layers > 0 && layers <= 8 && V1 > 0 && blank >= 0 && blank < V1 && n_max > 0 &&
-                    max_steps > 0 && n_steps >= 0 && T < (1 << 30) && n_max < (1 << 30), DYN_E_ARG, "dyn_tdt_greedy_steps: bad sizes");
-    GreedyArgs a;
-    if (const int rc = check_durs(durations, D, a.durs, "dyn_tdt_greedy_steps")) return rc;
-    a.enc = enc; a.valid = valid; a.embed = embed; a.lstm = (const float* const*)lstm_ptrs; a.proj_w = proj_w; a.proj_b = proj_b;
-    a.head_w = head_w; a.head_b = head_b; a.istate = istate; a.h = h; a.c = c; a.h_new = h_new; a.dec = dec; a.logits = logits;
-    a.tokens = tokens; a.frames = frames;
-    a.B = (int32_t)B; a.T = (int32_t)T; a.Hd = (int32_t)Hd; a.L = (int32_t)layers; a.V1 = (int32_t)V1; a.N = (int32_t)(V1 + D);
-    a.blank = blank; a.n_max = (int32_t)n_max; a.max_steps = (int32_t)(max_steps < (1 << 30) ? max_steps : (1 << 30));
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 blk(256), gh((unsigned)dyn::cdiv(Hd, 4), (unsigned)B), gn((unsigned)dyn::cdiv(V1 + D, 4), (unsigned)B);
-    for (int s = 0; s < n_steps; ++s) {
-        for (int l = 0; l < layers; ++l) hipLaunchKernelGGL(greedy_lstm_kernel, gh, blk, 0, st, a, l);
-        hipLaunchKernelGGL(greedy_proj_kernel, gh, blk, 0, st, a);
-        hipLaunchKernelGGL(greedy_joint_kernel, gn, blk, 0, st, a);
-        hipLaunchKernelGGL(greedy_pick_kernel, dim3((unsigned)B), blk, 0, st, a);
-    }
-    return dyn::check_launch("dyn_tdt_greedy_steps");
-}
-
-// ==== RNN-T (ParakeetForRNNT, `model_type: "parakeet_rnnt"`) =================================================================
-// The plain transducer lattice of transformers.loss.loss_rnnt.rnnt_loss (a wrapper around torchaudio.functional.rnnt_loss): no
-// duration head (N == V1), from (t, u) a blank arc to (t + 1, u) and a label arc to (t, u + 1), the terminal alpha(T - 1, U) +
-// lp_blank(T - 1, U).  Every arc advances the anti-diagonal by exactly one, so a diagonal reads only the one before it and the base
-// difference it needs is the rint() it has just taken: the integer-base scheme of the TDT lattice above with one source diagonal.
-// State per cell: lp (blank, label) 8 bytes, lse 4, alpha 4, beta 4 = 20 bytes (TDT at D = 5: 44).  The same three passes, whole and
-// per chunk of frames; the reduction kernel, row_weight and the greedy LSTM / projector / joint kernels are the TDT ones.
-namespace {
-
-struct RnntDims {
-    int64_t B, T, U1;       // the lattice [B, T, U1]
-    int64_t t0, Tc;         // the row kernels' logits [B, Tc, U1, V1] hold the frames [t0, t0 + Tc)
-    int64_t V1, S;          // token classes (the blank among them); targets [B, S]
-    int32_t blank;
-};
-
-__device__ __forceinline__ int rnnt_row_T(const int32_t* ilen, int64_t b, const RnntDims& d) { return clampi(ilen[b], 0, (int)d.T); }
-__device__ __forceinline__ int rnnt_row_U(const int32_t* tlen, int64_t b, const RnntDims& d) {
-    return clampi(tlen[b], 0, (int)(d.U1 - 1 < d.S ? d.U1 - 1 : d.S));
-}
-__device__ __forceinline__ int rnnt_target(const int32_t* targets, int64_t b, int u, const RnntDims& d) {
-    const int k = targets[b * d.S + u];
-    return k < 0 ? 0 : (k >= d.V1 ? (int)d.V1 - 1 : k);               // ids are validated on the host; never read outside the row
-}
-
-// One wave per logits row (b, tc, u) of the frames [t0, t0 + Tc): lp[cell] = (blank, label) log-probs (label -inf at u >= U_b),
-// lse[cell] = the token log-sum-exp.  Rows of a chunk past the lattice's last frame are skipped.
-__global__ __launch_bounds__(64 * WPB) void rnnt_arcs_kernel(const float* __restrict__ logits, const int32_t* __restrict__ targets,
-                                                             const int32_t* __restrict__ tlen, float* __restrict__ lp, float* __restrict__ lse,
-                                                             RnntDims d) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t rows = d.B * d.Tc * d.U1;
-    for (int64_t crow = (int64_t)blockIdx.x * WPB + w; crow < rows; crow += (int64_t)gridDim.x * WPB) {
-        const int64_t u = crow % d.U1, b = crow / (d.U1 * d.Tc), t = d.t0 + (crow / d.U1) % d.Tc;
-        if (t >= d.T) continue;                                       // wave-uniform
-        const int64_t row = (b * d.T + t) * d.U1 + u;                 // the lattice cell
-        const float* x = logits + crow * d.V1;
-        float m = -INFINITY;
-        for (int c = lane; c < d.V1; c += 64) m = fmaxf(m, x[c]);
-        m = dyn::wave_max(m);
-        float s = 0.f;
-        for (int c = lane; c < d.V1; c += 64) s += expf(x[c] - m);
-        s = dyn::wave_sum(s);
-        const float lt = m + logf(s);
-        if (lane == 0) {
-            lp[2 * row] = x[d.blank] - lt;
-            lp[2 * row + 1] = u < rnnt_row_U(tlen, b, d) ? x[rnnt_target(targets, b, (int)u, d)] - lt : -INFINITY;
-            lse[row] = lt;
-        }
-    }
-}
-
-// Workspace per row b: lp [T, U1, 2], lse, alpha, beta [T, U1] (alpha / beta stored relative to the bases), abase, bbase [T + U1]
-// (floats holding integers), ll [2] = (integer part, fraction), -inf fraction when the terminal is unreachable, nll.
-TdtWs rnnt_carve(void* ws, int64_t B, int64_t T, int64_t U1) {
-    TdtWs w;
-    char* p = (char*)ws;
-    int64_t off = 0;
-    const int64_t cells = B * T * U1;
-    w.lp = (float*)(p + off); off += align_up(cells * 2 * 4, 256);
-    w.lse = (float*)(p + off); off += align_up(cells * 4, 256);
-    w.alpha = (float*)(p + off); off += align_up(cells * 4, 256);
-    w.beta = (float*)(p + off); off += align_up(cells * 4, 256);
-    w.abase = (float*)(p + off); off += align_up(B * (T + U1) * 4, 256);
-    w.bbase = (float*)(p + off); off += align_up(B * (T + U1) * 4, 256);
-    w.ll = (float*)(p + off); off += align_up(B * 2 * 4, 256);
-    w.nll = (float*)(p + off); off += align_up(B * 4, 256);
-    w.total = off;
-    return w;
-}
-
-// log(exp(a) + exp(b)), -inf when both are
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float c[2] = {a, b};
-    return lse_of(c, 2);
-}
-
-__global__ __launch_bounds__(LATTICE_T) void rnnt_lattice_kernel(const float* __restrict__ lp, const int32_t* __restrict__ ilen,
-                                                                 const int32_t* __restrict__ tlen, float* alpha, float* beta, float* abase,
-                                                                 float* bbase, float* ll_out, float* __restrict__ nll, RnntDims d) {
-    __shared__ float wmax[2][16];
-    const int64_t b = blockIdx.x;
-    const int U1 = (int)d.U1;
-    const int T = rnnt_row_T(ilen, b, d), U = rnnt_row_U(tlen, b, d);
-    const float* lpb = lp + b * d.T * d.U1 * 2;
-    const int ND = T > 0 ? T + U : 0;           // diagonals 0 .. T + U - 1; T_b == 0: no cell, no terminal
-    if (blockIdx.y == 0) {
-        float* al = alpha + b * d.T * d.U1;
-        float* bs = abase + b * (d.T + d.U1);
-        float base = 0.f;
-        for (int n = 0; n < ND; ++n) {
-            float off = 0.f;                    // base of diagonal n - 1 minus this one's
-            if (n > 0) {
-                const float mx = read_max(wmax, n - 1);
-                if (mx > -INFINITY) off = -rintf(mx);
-            }
-            base -= off;
-            if (threadIdx.x == 0) bs[n] = base;
-            float tmax = -INFINITY;
-            const int u_lo = n - T + 1 > 0 ? n - T + 1 : 0, u_hi = n < U ? n : U;
-            for (int u = u_lo + (int)threadIdx.x; u <= u_hi; u += blockDim.x) {
-                const int t = n - u;
-                float v = 0.f;
-                if (n > 0) {
-                    float cb = -INFINITY, cl = -INFINITY;
-                    if (t > 0) {
-                        const int64_t s = (int64_t)(t - 1) * U1 + u;
-                        cb = al[s] + off + lpb[2 * s];
-                    }
-                    if (u > 0) {
-                        const int64_t s = (int64_t)t * U1 + u - 1;
-                        cl = al[s] + off + lpb[2 * s + 1];
-                    }
-                    v = lse2(cb, cl);
-                }
-                al[(int64_t)t * U1 + u] = v;
-                tmax = fmaxf(tmax, v);
-            }
-            publish_max(tmax, wmax, n);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            float lf = -INFINITY;
-            if (T > 0) {
-                const int64_t s = (int64_t)(T - 1) * U1 + U;
-                lf = al[s] + lpb[2 * s];
-            }
-            ll_out[2 * b] = base;
-            ll_out[2 * b + 1] = lf;
-            nll[b] = lf > -INFINITY ? -(base + lf) : INFINITY;
-        }
-    } else {
-        float* be = beta + b * d.T * d.U1;
-        float* bs = bbase + b * (d.T + d.U1);
-        float base = 0.f;
-        for (int n = ND - 1; n >= 0; --n) {
-            float off = 0.f;                    // base of diagonal n + 1 minus this one's
-            if (n < ND - 1) {
-                const float mx = read_max(wmax, n + 1);
-                if (mx > -INFINITY) off = -rintf(mx);
-            }
-            base -= off;
-            if (threadIdx.x == 0) bs[n] = base;
-            float tmax = -INFINITY;
-            const int u_lo = n - T + 1 > 0 ? n - T + 1 : 0, u_hi = n < U ? n : U;
-            for (int u = u_lo + (int)threadIdx.x; u <= u_hi; u += blockDim.x) {
-                const int t = n - u;
-                const int64_t s = (int64_t)t * U1 + u;
-                float v;
-                if (t == T - 1 && u == U) {
-                    v = lpb[2 * s];                                   // the terminal, absolute 0 behind it (base is 0 here)
-                } else {
-                    float cb = -INFINITY, cl = -INFINITY;
-                    if (t + 1 < T) cb = lpb[2 * s] + be[s + U1] + off;
-                    if (u < U) cl = lpb[2 * s + 1] + be[s + 1] + off;
-                    v = lse2(cb, cl);
-                }
-                be[s] = v;
-                tmax = fmaxf(tmax, v);
-            }
-            publish_max(tmax, wmax, n);
-            __syncthreads();
-        }
-    }
-}
-
-// One wave per logits row (b, t, u): g_b = exp(alpha + lp_blank + beta(t + 1, u) - ll) (beta = 0 behind the terminal cell),
-// g_l = exp(alpha + lp_label + beta(t, u + 1) - ll) for u < U; dlogit[v] = softmax_v * (g_b + g_l) - g_b [v = blank] - g_l [v = target],
-// times grad_scale * row weight.  Rows at t >= T_b or u > U_b, and every row of an unreachable lattice, are zeros.  grad may be logits.
-__global__ __launch_bounds__(64 * WPB) void rnnt_grad_kernel(const float* logits, const int32_t* __restrict__ targets,
-                                                             const int32_t* __restrict__ ilen, const int32_t* __restrict__ tlen,
-                                                             const float* __restrict__ lp, const float* __restrict__ lse,
-                                                             const float* __restrict__ alpha, const float* __restrict__ beta,
-                                                             const float* __restrict__ abase, const float* __restrict__ bbase,
-                                                             const float* __restrict__ ll, float* grad, float grad_scale, int reduction, RnntDims d) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t rows = d.B * d.Tc * d.U1;
-    for (int64_t row = (int64_t)blockIdx.x * WPB + w; row < rows; row += (int64_t)gridDim.x * WPB) {
-        const int u = (int)(row % d.U1);
-        const int64_t b = row / (d.U1 * d.Tc), tt = d.t0 + (row / d.U1) % d.Tc;      // a chunk's frame may lie past the lattice: zeros
-        const int t = (int)(tt < d.T ? tt : d.T);
-        const int T = rnnt_row_T(ilen, b, d), U = rnnt_row_U(tlen, b, d);
-        const float* x = logits + row * d.V1;
-        float* g = grad + row * d.V1;
-        const float li = ll[2 * b], lf = ll[2 * b + 1];
-        if (t >= T || u > U || !(lf > -INFINITY)) {
-            for (int c = lane; c < d.V1; c += 64) g[c] = 0.f;
-            continue;
-        }
-        const int n = t + u;
-        const int64_t cell = (b * d.T + t) * d.U1 + u;
-        const float* ab = abase + b * (d.T + d.U1);
-        const float* bb = bbase + b * (d.T + d.U1);
-        const float a = alpha[cell], abn = ab[n];
-        float gb = 0.f, gl = 0.f;                                     // wave-uniform: every lane evaluates the same two posteriors
-        if (a > -INFINITY) {
-            const float lb = lp[2 * cell], llab = lp[2 * cell + 1];
-            float e = -INFINITY;
-            if (t == T - 1 && u == U) e = a + lb + ((abn - li) - lf);
-            else if (t + 1 < T) e = a + lb + beta[cell + d.U1] + ((abn + bb[n + 1] - li) - lf);
-            gb = e > -INFINITY ? expf(e) : 0.f;
-            if (u < U) {
-                e = a + llab + beta[cell + 1] + ((abn + bb[n + 1] - li) - lf);
-                gl = e > -INFINITY ? expf(e) : 0.f;
-            }
-        }
-        const float G = gb + gl;
-        const float sc = grad_scale * row_weight(reduction, tlen, d.B, b);
-        const float lt = lse[cell];
-        const int tgt = u < U ? rnnt_target(targets, b, u, d) : -1;
-        for (int c = lane; c < d.V1; c += 64) {
-            float v = expf(x[c] - lt) * G;
-            if (c == d.blank) v -= gb;
-            if (c == tgt) v -= gl;
-            g[c] = v * sc;
-        }
-    }
-}
-
-// argmax over the row (first maximum wins), then ParakeetRNNTGenerationMixin._update_model_kwargs_for_generation: a blank advances the
-// frame and resets the per-frame symbol counter; a non-blank is emitted and counted, and when the counter reaches max_symbols the frame
-// advances anyway and the counter resets (the forced step's token is still emitted and fed to the prediction network).
-enum { S_SYMBOLS = 6 };
-// `frame_base`: added to the frame RECORDED with an emitted token (0 offline; the absolute frame of a streamed chunk's frame 0).
-__global__ __launch_bounds__(256) void rnnt_greedy_pick_kernel(const GreedyArgs a, int max_symbols, int frame_base) {
-    __shared__ float rv[4];
-    __shared__ int ri[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int b = blockIdx.x;
-    if (ist(a, S_DONE)[b]) return;                 // uniform: the flag is written after the barrier below
-    const float* x = a.logits + (int64_t)b * a.N;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int c = threadIdx.x; c < a.V1; c += blockDim.x)
-        if (better(x[c], c, bv, bi)) { bv = x[c]; bi = c; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { rv[w] = bv; ri[w] = bi; }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int i = 1; i < 4; ++i)
-        if (better(rv[i], ri[i], bv, bi)) { bv = rv[i]; bi = ri[i]; }
-    const int tok = bi == 0x7fffffff ? a.blank : bi;
-    const bool is_blank = tok == a.blank;
-    const int frame = ist(a, S_FRAME)[b];
-    const int symbols = is_blank ? 0 : ist(a, S_SYMBOLS)[b] + 1;
-    const bool forced = symbols >= max_symbols;
-    const int adv = is_blank || forced ? 1 : 0;
-    int count = ist(a, S_COUNT)[b];
-    if (!is_blank && count < a.n_max) {
-        a.tokens[(int64_t)b * a.n_max + count] = tok;
-        a.frames[(int64_t)b * a.n_max + count] = frame + frame_base;
-        ++count;
-    }
-    const int steps = ist(a, S_STEPS)[b] + 1;
-    ist(a, S_COUNT)[b] = count;
-    ist(a, S_STEPS)[b] = steps;
-    ist(a, S_EMIT)[b] = is_blank ? 0 : 1;
-    ist(a, S_TOKEN)[b] = tok;
-    ist(a, S_FRAME)[b] = frame + adv;
-    ist(a, S_SYMBOLS)[b] = adv ? 0 : symbols;
-    if (frame + adv >= a.valid[b] || steps >= a.max_steps || count >= a.n_max) ist(a, S_DONE)[b] = 1;
-}
-
-// A streamed decode moves on to the next chunk of encoder frames: the frame pointer back to 0, the done flags, the per-frame symbol
-// counter and the chunk's output count and step count cleared.  h / c, the cached projector output, the last token and the emit flag stay.
-__global__ void rnnt_greedy_rebase_kernel(const GreedyArgs a) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.B) return;
-    ist(a, S_FRAME)[b] = 0;
-    ist(a, S_DONE)[b] = 0;
-    ist(a, S_COUNT)[b] = 0;
-    ist(a, S_STEPS)[b] = 0;
-    ist(a, S_SYMBOLS)[b] = 0;
-}
-
-// What every RNN-T entry does before its launches (tdt_setup without the durations)
-int rnnt_setup(const char* who, const char* over, int64_t B, int64_t T, int64_t U1, int64_t V1, int64_t S, int32_t blank, void* state,
-               int64_t state_bytes, int64_t budget_bytes, RnntDims& d, TdtWs& w) {
-    DYN_REQUIRE(B > 0 && T > 0 && U1 > 0 && V1 > 0 && S >= 1 && blank >= 0 && blank < V1, DYN_E_ARG, "%s: bad arguments", who);
-    DYN_REQUIRE(V1 < (1 << 30) && U1 < (1 << 24) && T + U1 < (1 << 24), DYN_E_UNSUPPORTED, "%s: %lld diagonals / %lld classes unsupported", who,
-                (long long)(T + U1), (long long)V1);
-    w = rnnt_carve(state, B, T, U1);
-    DYN_REQUIRE(budget_bytes <= 0 || w.total <= budget_bytes, DYN_E_WORKSPACE,
-                "%s: the lattice of [%lld, %lld, %lld] needs %lld bytes, over the workspace budget of %lld (%s)", who, (long long)B, (long long)T,
-                (long long)U1, (long long)w.total, (long long)budget_bytes, over);
-    DYN_REQUIRE(state && state_bytes >= w.total, DYN_E_WORKSPACE, "%s: workspace %lld < %lld bytes", who, (long long)state_bytes,
-                (long long)w.total);
-    d.B = B; d.T = T; d.U1 = U1; d.t0 = 0; d.Tc = T; d.V1 = V1; d.S = S; d.blank = blank;
-    return DYN_OK;
-}
-
-int rnnt_chunk(const char* who, int64_t t0, int64_t Tc, RnntDims& d) {
-    DYN_REQUIRE(t0 >= 0 && t0 < d.T && Tc > 0 && Tc < (1 << 24), DYN_E_ARG, "%s: the chunk [%lld, %lld + %lld) must start inside the %lld frames",
-                who, (long long)t0, (long long)t0, (long long)Tc, (long long)d.T);
-    d.t0 = t0; d.Tc = Tc;
-    return DYN_OK;
-}
-
-void rnnt_launch_arcs(const float* logits, const int32_t* targets, const int32_t* tlen, const TdtWs& w, const RnntDims& d, hipStream_t st) {
-    hipLaunchKernelGGL(rnnt_arcs_kernel, dim3(grid_for(d.B * d.Tc * d.U1, WPB)), dim3(64 * WPB), 0, st, logits, targets, tlen, w.lp, w.lse, d);
-}
-
-int rnnt_launch_lattice(const char* who, const int32_t* ilen, const int32_t* tlen, int reduction, float* loss, float* nll_per_row, bool both,
-                        const TdtWs& w, const RnntDims& d, hipStream_t st) {
-    const int64_t diag = d.T < d.U1 ? d.T : d.U1;
-    int threads = (int)((diag + 63) / 64 * 64);
-    if (threads > LATTICE_T) threads = LATTICE_T;
-    hipLaunchKernelGGL(rnnt_lattice_kernel, dim3((unsigned)d.B, both ? 2u : 1u), dim3(threads), 0, st, w.lp, ilen, tlen, w.alpha, w.beta, w.abase,
-                       w.bbase, w.ll, w.nll, d);
-    hipLaunchKernelGGL(tdt_loss_reduce_kernel, dim3(1), dim3(64), 0, st, w.nll, tlen, loss, d.B, reduction);
-    if (nll_per_row) {
-        hipError_t e = hipMemcpyAsync(nll_per_row, w.nll, d.B * sizeof(float), hipMemcpyDeviceToDevice, st);
-        DYN_REQUIRE(e == hipSuccess, DYN_E_LAUNCH, "%s: copy of the per-row nll failed", who);
-    }
-    return DYN_OK;
-}
-
-void rnnt_launch_grad(const float* logits, const int32_t* targets, const int32_t* ilen, const int32_t* tlen, float* grad, float grad_scale,
-                      int reduction, const TdtWs& w, const RnntDims& d, hipStream_t st) {
-    hipLaunchKernelGGL(rnnt_grad_kernel, dim3(grid_for(d.B * d.Tc * d.U1, WPB)), dim3(64 * WPB), 0, st, logits, targets, ilen, tlen, w.lp, w.lse,
-                       w.alpha, w.beta, w.abase, w.bbase, w.ll, grad, grad_scale, reduction, d);
-}
-
-}  // namespace
-
-extern "C" int64_t dyn_rnnt_loss_workspace_bytes(int64_t B, int64_t T, int64_t U1) {
-    if (B <= 0 || T <= 0 || U1 <= 0) return -1;
-    return rnnt_carve(nullptr, B, T, U1).total;
-}
-
-extern "C" int dyn_rnnt_loss_workspace_layout(int64_t B, int64_t T, int64_t U1, int64_t* offsets8) {
-    DYN_REQUIRE(offsets8 && B > 0 && T > 0 && U1 > 0, DYN_E_ARG, "dyn_rnnt_loss_workspace_layout: bad arguments");
-    const TdtWs w = rnnt_carve(nullptr, B, T, U1);
-    const float* ps[8] = {w.lp, w.lse, w.alpha, w.beta, w.abase, w.bbase, w.ll, w.nll};
-    for (int i = 0; i < 8; ++i) offsets8[i] = (const char*)ps[i] - (const char*)nullptr;
-    return DYN_OK;
+    return ::loss("dyn_tdt_loss", "chunking over t is not built", true, logits, B, T, U1, V1, durations, D, targets, S, logit_lengths,
+                  target_lengths, blank, sigma, reduction, grad_scale, loss, nll_per_row, grad, workspace, workspace_bytes, workspace_budget_bytes,
+                  stream);
 }
 
 extern "C" int dyn_rnnt_loss(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* targets, int64_t S,
                              const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank, int32_t reduction, float grad_scale,
                              float* loss, float* nll_per_row, float* grad, void* workspace, int64_t workspace_bytes,
                              int64_t workspace_budget_bytes, void* stream) {
-    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && loss && reduction >= 0 && reduction <= 4, DYN_E_ARG,
-                "dyn_rnnt_loss: bad arguments");
-    RnntDims d;
-    TdtWs w;
-    if (const int rc = rnnt_setup("dyn_rnnt_loss", OVER_STATE, B, T, U1, V1, S, blank, workspace, workspace_bytes, workspace_budget_bytes, d, w))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    rnnt_launch_arcs(logits, targets, target_lengths, w, d, st);
-    if (const int rc = rnnt_launch_lattice("dyn_rnnt_loss", logit_lengths, target_lengths, (int)reduction, loss, nll_per_row, grad != nullptr, w, d, st))
-        return rc;
-    if (grad) rnnt_launch_grad(logits, targets, logit_lengths, target_lengths, grad, grad_scale, (int)reduction, w, d, st);
-    return dyn::check_launch("dyn_rnnt_loss");
+    return ::loss("dyn_rnnt_loss", OVER_STATE, false, logits, B, T, U1, V1, nullptr, 0, targets, S, logit_lengths, target_lengths, blank, 0.f,
+                  reduction, grad_scale, loss, nll_per_row, grad, workspace, workspace_bytes, workspace_budget_bytes, stream);
+}
+
+extern "C" int dyn_tdt_arcs_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+                                  const int32_t* targets, int64_t S, const int32_t* target_lengths, int32_t blank, float sigma, int64_t t0,
+                                  int64_t Tc, void* state, int64_t state_bytes, int64_t state_budget_bytes, void* stream) {
+    return arcs_chunk("dyn_tdt_arcs_chunk", true, logits, B, T, U1, V1, durations, D, targets, S, target_lengths, blank, sigma, t0, Tc, state,
+                      state_bytes, state_budget_bytes, stream);
 }
 
 extern "C" int dyn_rnnt_arcs_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* targets, int64_t S,
                                    const int32_t* target_lengths, int32_t blank, int64_t t0, int64_t Tc, void* state, int64_t state_bytes,
                                    int64_t state_budget_bytes, void* stream) {
-    DYN_REQUIRE(logits && targets && target_lengths, DYN_E_ARG, "dyn_rnnt_arcs_chunk: bad arguments");
-    RnntDims d;
-    TdtWs w;
-    if (const int rc = rnnt_setup("dyn_rnnt_arcs_chunk", OVER_STATE, B, T, U1, V1, S, blank, state, state_bytes, state_budget_bytes, d, w)) return rc;
-    if (const int rc = rnnt_chunk("dyn_rnnt_arcs_chunk", t0, Tc, d)) return rc;
-    rnnt_launch_arcs(logits, targets, target_lengths, w, d, (hipStream_t)stream);
-    return dyn::check_launch("dyn_rnnt_arcs_chunk");
+    return arcs_chunk("dyn_rnnt_arcs_chunk", false, logits, B, T, U1, V1, nullptr, 0, targets, S, target_lengths, blank, 0.f, t0, Tc, state,
+                      state_bytes, state_budget_bytes, stream);
+}
+
+extern "C" int dyn_tdt_lattice_run(int64_t B, int64_t T, int64_t U1, const int32_t* durations, int64_t D, int64_t S,
+                                   const int32_t* logit_lengths, const int32_t* target_lengths, int32_t reduction, float* loss,
+                                   float* nll_per_row, int32_t want_beta, void* state, int64_t state_bytes, int64_t state_budget_bytes,
+                                   void* stream) {
+    return lattice_run("dyn_tdt_lattice_run", true, B, T, U1, durations, D, S, logit_lengths, target_lengths, reduction, loss, nll_per_row,
+                       want_beta, state, state_bytes, state_budget_bytes, stream);
 }
 
 extern "C" int dyn_rnnt_lattice_run(int64_t B, int64_t T, int64_t U1, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths,
                                     int32_t reduction, float* loss, float* nll_per_row, int32_t want_beta, void* state, int64_t state_bytes,
                                     int64_t state_budget_bytes, void* stream) {
-    DYN_REQUIRE(logit_lengths && target_lengths && loss && reduction >= 0 && reduction <= 4, DYN_E_ARG, "dyn_rnnt_lattice_run: bad arguments");
-    RnntDims d;
-    TdtWs w;
-    // the lattice reads neither the vocabulary nor the blank: one token class stands in for them
-    if (const int rc = rnnt_setup("dyn_rnnt_lattice_run", OVER_STATE, B, T, U1, 1, S, 0, state, state_bytes, state_budget_bytes, d, w)) return rc;
-    if (const int rc = rnnt_launch_lattice("dyn_rnnt_lattice_run", logit_lengths, target_lengths, (int)reduction, loss, nll_per_row, want_beta != 0,
-                                           w, d, (hipStream_t)stream))
-        return rc;
-    return dyn::check_launch("dyn_rnnt_lattice_run");
+    return lattice_run("dyn_rnnt_lattice_run", false, B, T, U1, nullptr, 0, S, logit_lengths, target_lengths, reduction, loss, nll_per_row,
+                       want_beta, state, state_bytes, state_budget_bytes, stream);
+}
+
+extern "C" int dyn_tdt_grad_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* durations, int64_t D,
+                                  const int32_t* targets, int64_t S, const int32_t* logit_lengths, const int32_t* target_lengths,
+                                  int32_t blank, int32_t reduction, float grad_scale, int64_t t0, int64_t Tc, float* grad, const void* state,
+                                  int64_t state_bytes, void* stream) {
+    return grad_chunk("dyn_tdt_grad_chunk", true, logits, B, T, U1, V1, durations, D, targets, S, logit_lengths, target_lengths, blank, reduction,
+                      grad_scale, t0, Tc, grad, state, state_bytes, stream);
 }
 
 extern "C" int dyn_rnnt_grad_chunk(const float* logits, int64_t B, int64_t T, int64_t U1, int64_t V1, const int32_t* targets, int64_t S,
                                    const int32_t* logit_lengths, const int32_t* target_lengths, int32_t blank, int32_t reduction,
                                    float grad_scale, int64_t t0, int64_t Tc, float* grad, const void* state, int64_t state_bytes, void* stream) {
-    DYN_REQUIRE(logits && targets && logit_lengths && target_lengths && grad && reduction >= 0 && reduction <= 4, DYN_E_ARG,
-                "dyn_rnnt_grad_chunk: bad arguments");
-    RnntDims d;
-    TdtWs w;
-    if (const int rc = rnnt_setup("dyn_rnnt_grad_chunk", OVER_STATE, B, T, U1, V1, S, blank, const_cast<void*>(state), state_bytes, 0, d, w))
-        return rc;
-    if (const int rc = rnnt_chunk("dyn_rnnt_grad_chunk", t0, Tc, d)) return rc;
-    rnnt_launch_grad(logits, targets, logit_lengths, target_lengths, grad, grad_scale, (int)reduction, w, d, (hipStream_t)stream);
-    return dyn::check_launch("dyn_rnnt_grad_chunk");
+    return grad_chunk("dyn_rnnt_grad_chunk", false, logits, B, T, U1, V1, nullptr, 0, targets, S, logit_lengths, target_lengths, blank, reduction,
+                      grad_scale, t0, Tc, grad, state, state_bytes, stream);
 }
 
+// ---- greedy decode: one launcher, the pick kernel chosen by the head ---------------------------------------------------------------
 namespace {
 
-int rnnt_greedy_launch(const char* who, const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
-                       const float* proj_w, const float* proj_b, const float* head_w, const float* head_b, int32_t* istate, float* h, float* c,
-                       float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd,
-                       int64_t layers, int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max, int64_t max_steps, int32_t n_steps,
-                       int64_t frame_base, bool rebase, void* stream) {
+// n_steps greedy steps of every live row.  `tdt`: argmax over the durations as well, greedy_pick_kernel; else max_symbols per frame,
+// rnnt_greedy_pick_kernel, frames recorded from frame_base, and with `rebase` the state first moved on to this chunk of frames.
+int greedy_launch(const char* who, bool tdt, const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
+                  const float* proj_w, const float* proj_b, const float* head_w, const float* head_b, int32_t* istate, float* h, float* c,
+                  float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B, int64_t T, int64_t Hd, int64_t layers,
+                  int64_t V1, const int32_t* durations, int64_t D, int32_t blank, int64_t max_symbols, int64_t n_max, int64_t max_steps,
+                  int32_t n_steps, int64_t frame_base, bool rebase, void* stream) {
     DYN_REQUIRE(enc && valid && embed && lstm_ptrs && proj_w && proj_b && head_w && head_b && istate && h && c && h_new && dec && logits &&
                     tokens && frames, DYN_E_ARG, "%s: null pointer", who);
     DYN_REQUIRE(B > 0 && B <= 65535 && T > 0 && Hd > 0 && layers > 0 && layers <= 8 && V1 > 0 && V1 < (1 << 30) && blank >= 0 && blank < V1 &&
@@ -1258,35 +1087,46 @@ int rnnt_greedy_launch(const char* who, const float* enc, const int32_t* valid, 
     DYN_REQUIRE(frame_base >= 0 && frame_base + T < (1ll << 31), DYN_E_ARG, "%s: frame_base=%lld leaves the int32 frames", who,
                 (long long)frame_base);
     GreedyArgs a;
-    a.durs.n = 0;
-    for (int i = 0; i < MAX_DUR; ++i) a.durs.d[i] = 0;
+    a.durs = Durs{};
+    if (tdt)
+        if (const int rc = check_durs(durations, D, a.durs, who)) return rc;
     a.enc = enc; a.valid = valid; a.embed = embed; a.lstm = (const float* const*)lstm_ptrs; a.proj_w = proj_w; a.proj_b = proj_b;
     a.head_w = head_w; a.head_b = head_b; a.istate = istate; a.h = h; a.c = c; a.h_new = h_new; a.dec = dec; a.logits = logits;
     a.tokens = tokens; a.frames = frames;
-    a.B = (int32_t)B; a.T = (int32_t)T; a.Hd = (int32_t)Hd; a.L = (int32_t)layers; a.V1 = (int32_t)V1; a.N = (int32_t)V1;
+    a.B = (int32_t)B; a.T = (int32_t)T; a.Hd = (int32_t)Hd; a.L = (int32_t)layers; a.V1 = (int32_t)V1; a.N = (int32_t)V1 + a.durs.n;
     a.blank = blank; a.n_max = (int32_t)n_max; a.max_steps = (int32_t)(max_steps < (1 << 30) ? max_steps : (1 << 30));
     const int ms = (int)(max_symbols < (1 << 30) ? max_symbols : (1 << 30));
     hipStream_t st = (hipStream_t)stream;
-    const dim3 blk(256), gh((unsigned)dyn::cdiv(Hd, 4), (unsigned)B), gn((unsigned)dyn::cdiv(V1, 4), (unsigned)B);
+    const dim3 blk(256), gh((unsigned)dyn::cdiv(Hd, 4), (unsigned)B), gn((unsigned)dyn::cdiv(a.N, 4), (unsigned)B);
     if (rebase) hipLaunchKernelGGL(rnnt_greedy_rebase_kernel, dim3((unsigned)dyn::cdiv(B, 256)), blk, 0, st, a);
     for (int s = 0; s < n_steps; ++s) {
         for (int l = 0; l < layers; ++l) hipLaunchKernelGGL(greedy_lstm_kernel, gh, blk, 0, st, a, l);
         hipLaunchKernelGGL(greedy_proj_kernel, gh, blk, 0, st, a);
         hipLaunchKernelGGL(greedy_joint_kernel, gn, blk, 0, st, a);
-        hipLaunchKernelGGL(rnnt_greedy_pick_kernel, dim3((unsigned)B), blk, 0, st, a, ms, (int)frame_base);
+        if (tdt) hipLaunchKernelGGL(greedy_pick_kernel, dim3((unsigned)B), blk, 0, st, a);
+        else hipLaunchKernelGGL(rnnt_greedy_pick_kernel, dim3((unsigned)B), blk, 0, st, a, ms, (int)frame_base);
     }
     return dyn::check_launch(who);
 }
 
 }  // namespace
 
+extern "C" int dyn_tdt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
+                                    const float* proj_w, const float* proj_b, const float* head_w, const float* head_b, int32_t* istate,
+                                    float* h, float* c, float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames,
+                                    int64_t B, int64_t T, int64_t Hd, int64_t layers, int64_t V1, const int32_t* durations, int64_t D,
+                                    int32_t blank, int64_t n_max, int64_t max_steps, int32_t n_steps, void* stream) {
+    return greedy_launch("dyn_tdt_greedy_steps", true, enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, istate, h, c, h_new, dec,
+                         logits, tokens, frames, B, T, Hd, layers, V1, durations, D, blank, 1, n_max, max_steps, n_steps, 0, false, stream);
+}
+
 extern "C" int dyn_rnnt_greedy_steps(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
                                      const float* proj_w, const float* proj_b, const float* head_w, const float* head_b, int32_t* istate,
                                      float* h, float* c, float* h_new, float* dec, float* logits, int32_t* tokens, int32_t* frames, int64_t B,
                                      int64_t T, int64_t Hd, int64_t layers, int64_t V1, int32_t blank, int64_t max_symbols, int64_t n_max,
                                      int64_t max_steps, int32_t n_steps, void* stream) {
-    return rnnt_greedy_launch("dyn_rnnt_greedy_steps", enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, istate, h, c, h_new, dec,
-                              logits, tokens, frames, B, T, Hd, layers, V1, blank, max_symbols, n_max, max_steps, n_steps, 0, false, stream);
+    return greedy_launch("dyn_rnnt_greedy_steps", false, enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, istate, h, c, h_new, dec,
+                         logits, tokens, frames, B, T, Hd, layers, V1, nullptr, 0, blank, max_symbols, n_max, max_steps, n_steps, 0, false, stream);
 }
 
 extern "C" int dyn_rnnt_greedy_steps_chunk(const float* enc, const int32_t* valid, const float* embed, const void* const* lstm_ptrs,
@@ -1296,7 +1136,8 @@ extern "C" int dyn_rnnt_greedy_steps_chunk(const float* enc, const int32_t* vali
                                            int64_t max_symbols, int64_t n_max, int64_t max_steps, int32_t n_steps, int64_t frame_base,
                                            int32_t rebase, void* stream) {
     DYN_REQUIRE(rebase == 0 || rebase == 1, DYN_E_ARG, "dyn_rnnt_greedy_steps_chunk: rebase=%d (0 or 1)", (int)rebase);
-    return rnnt_greedy_launch("dyn_rnnt_greedy_steps_chunk", enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, istate, h, c, h_new,
-                              dec, logits, tokens, frames, B, T, Hd, layers, V1, blank, max_symbols, n_max, max_steps, n_steps, frame_base,
-                              rebase != 0, stream);
+    return greedy_launch("dyn_rnnt_greedy_steps_chunk", false, enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, istate, h, c, h_new,
+                         dec, logits, tokens, frames, B, T, Hd, layers, V1, nullptr, 0, blank, max_symbols, n_max, max_steps, n_steps, frame_base,
+                         rebase != 0, stream);
 }
+

@@ -2214,8 +2214,11 @@ def check_durations(durations, what="durations"):
 
 
 def _durations_arg(durations):
+    """-> (the duration arguments of a C entry: (int32 array, D); none for `durations` None, a head without durations; D)."""
+    if durations is None:
+        return (), 0
     d = check_durations(durations)
-    return (ctypes.c_int32 * len(d))(*d), len(d)
+    return (ctypes.cast((ctypes.c_int32 * len(d))(*d), ctypes.c_void_p), len(d)), len(d)
 
 
 def lstm_cell(xg, hg, c_prev=None, save=False, out=None):
@@ -2295,34 +2298,161 @@ def joint_bwd(dz, z, dp_like, act="relu", want_de=True, want_dp=True, time_major
     return de, dp
 
 
+# One private function per pass for both transducer heads, behind the public tdt_* / rnnt_* names.  `durations` None: a plain RNN-T head,
+# whose C entries take neither the duration list nor sigma.  `who` is the public name: it opens every message and names the C entry
+# (dyn_<who>).
+def _transducer_args(who, logits, targets, target_lengths, blank, durations, T=1, state=None):
+    """Checks what every pass checks -> _durations_arg(durations)."""
+    _c(logits, who + ".logits"); _c(targets, who + ".targets", I32); _cc(target_lengths, who + ".target_lengths", I32)
+    if state is not None:
+        _cc(state, who + ".state", torch.uint8)
+    dur, D = _durations_arg(durations)
+    if logits.dim() != 4 or logits.shape[3] <= D:
+        raise DynError(f"{who}: logits {tuple(logits.shape)} must be [B, T, U + 1, V + 1 + {D}] ({D} duration columns)")
+    B = logits.shape[0]
+    if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or target_lengths.numel() != B or int(T) < 1:
+        raise DynError(f"{who}: targets {tuple(targets.shape)} must be [B, S >= 1], the lengths [B], T positive")
+    if not 0 <= int(blank) < logits.shape[3] - D:
+        raise DynError(f"{who}: blank={blank} lies outside the {logits.shape[3] - D} classes")
+    return dur, D
+
+
+def _transducer_reduction(who, reduction):
+    if reduction not in TDT_REDUCTIONS:
+        raise DynError(f"{who}: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
+    return TDT_REDUCTIONS[reduction]
+
+
+def _transducer_budget(durations, budget):
+    if budget is not None:
+        return int(budget)
+    return RNNT_WORKSPACE_BUDGET if durations is None else TDT_WORKSPACE_BUDGET
+
+
+def _transducer_loss(who, logits, targets, logit_lengths, target_lengths, blank, durations, sigma, reduction, grad_scale, want_grad, out, budget):
+    dur, D = _transducer_args(who, logits, targets, target_lengths, blank, durations)
+    _cc(logit_lengths, who + ".logit_lengths", I32)
+    red = _transducer_reduction(who, reduction)
+    B, T, U1, N = logits.shape
+    if logit_lengths.numel() != B:
+        raise DynError(f"{who}: the lengths must be [{B}]")
+    loss = torch.empty(1, device=logits.device, dtype=F32)
+    nll = torch.empty(B, device=logits.device, dtype=F32)
+    grad = None
+    if want_grad:
+        grad = torch.empty_like(logits) if out is None else _c(out, who + ".out")
+        if grad.shape != logits.shape:
+            raise DynError(f"{who}: out {tuple(grad.shape)} != logits {tuple(logits.shape)}")
+    ws = workspace(logits.device)
+    check(getattr(_L(), "dyn_" + who)(logits.data_ptr(), B, T, U1, N - D, *dur, targets.data_ptr(), targets.shape[1], logit_lengths.data_ptr(),
+                                      target_lengths.data_ptr(), int(blank), *((sigma,) if dur else ()), red, grad_scale, loss.data_ptr(),
+                                      nll.data_ptr(), 0 if grad is None else grad.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      _transducer_budget(durations, budget), _stream()), "dyn_" + who)
+    return loss, nll, grad
+
+
+def _transducer_state(who, B, T, U1, durations, device, budget):
+    if durations is None:
+        need = _L().dyn_rnnt_loss_workspace_bytes(B, T, U1)
+    else:
+        need = _L().dyn_tdt_loss_workspace_bytes(B, T, U1, len(check_durations(durations)))
+    budget = _transducer_budget(durations, budget)
+    if need < 0:
+        raise DynError(f"{who}: bad lattice [{B}, {T}, {U1}]")
+    if 0 < budget < need:
+        raise DynError(f"{who}: the lattice of [{B}, {T}, {U1}] needs {need} bytes of state, over the workspace budget of {budget} "
+                       "(chunking the lattice state is not built: only the joint streams over frame chunks)")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _transducer_arcs_chunk(who, logits, t0, T, targets, target_lengths, blank, durations, state, sigma, budget):
+    dur, D = _transducer_args(who, logits, targets, target_lengths, blank, durations, T, state)
+    B, Tc, U1, N = logits.shape
+    check(getattr(_L(), "dyn_" + who)(logits.data_ptr(), B, int(T), U1, N - D, *dur, targets.data_ptr(), targets.shape[1],
+                                      target_lengths.data_ptr(), int(blank), *((sigma,) if dur else ()), int(t0), Tc, state.data_ptr(),
+                                      state.numel(), _transducer_budget(durations, budget), _stream()), "dyn_" + who)
+
+
+def _transducer_lattice_run(who, B, T, U1, S, logit_lengths, target_lengths, durations, state, reduction, want_beta, budget):
+    _cc(logit_lengths, who + ".logit_lengths", I32); _cc(target_lengths, who + ".target_lengths", I32)
+    _cc(state, who + ".state", torch.uint8)
+    red = _transducer_reduction(who, reduction)
+    if logit_lengths.numel() != B or target_lengths.numel() != B:
+        raise DynError(f"{who}: the lengths must be [{B}]")
+    dur, _ = _durations_arg(durations)
+    loss = torch.empty(1, device=state.device, dtype=F32)
+    nll = torch.empty(B, device=state.device, dtype=F32)
+    check(getattr(_L(), "dyn_" + who)(B, T, U1, *dur, int(S), logit_lengths.data_ptr(), target_lengths.data_ptr(), red, loss.data_ptr(),
+                                      nll.data_ptr(), int(bool(want_beta)), state.data_ptr(), state.numel(),
+                                      _transducer_budget(durations, budget), _stream()), "dyn_" + who)
+    return loss, nll
+
+
+def _transducer_grad_chunk(who, logits, t0, T, targets, logit_lengths, target_lengths, blank, durations, state, reduction, grad_scale, out):
+    dur, D = _transducer_args(who, logits, targets, target_lengths, blank, durations, T, state)
+    _cc(logit_lengths, who + ".logit_lengths", I32)
+    red = _transducer_reduction(who, reduction)
+    B, Tc, U1, N = logits.shape
+    grad = torch.empty_like(logits) if out is None else _c(out, who + ".out")
+    if grad.shape != logits.shape or logit_lengths.numel() != B:
+        raise DynError(f"{who}: out {tuple(grad.shape)} != logits {tuple(logits.shape)}, or the lengths are not [{B}]")
+    check(getattr(_L(), "dyn_" + who)(logits.data_ptr(), B, int(T), U1, N - D, *dur, targets.data_ptr(), targets.shape[1], logit_lengths.data_ptr(),
+                                      target_lengths.data_ptr(), int(blank), red, grad_scale, int(t0), Tc, grad.data_ptr(), state.data_ptr(),
+                                      state.numel(), _stream()), "dyn_" + who)
+    return grad
+
+
+def _transducer_lattice(B, T, U1, D, device, state):
+    """(alpha, beta, lp [B, T, U1, 2 + D], lse [B, T, U1, 2]; D = 0, no duration head: lse [B, T, U1]) of the workspace or of `state`.  The
+    kernels store every anti-diagonal relative to an integer base; the bases are added back here in float64 (host arithmetic, for tests)."""
+    off = (ctypes.c_int64 * 8)()
+    if D:
+        check(_L().dyn_tdt_loss_workspace_layout(B, T, U1, D, ctypes.cast(off, ctypes.c_void_p)), "dyn_tdt_loss_workspace_layout")
+    else:
+        check(_L().dyn_rnnt_loss_workspace_layout(B, T, U1, ctypes.cast(off, ctypes.c_void_p)), "dyn_rnnt_loss_workspace_layout")
+    ws = workspace(device) if state is None else state
+    cells = B * T * U1
+
+    def view(i, n, shape):
+        return ws[off[i]:off[i] + 4 * n].view(F32).view(shape)
+
+    diag = (torch.arange(T, device=ws.device)[:, None] + torch.arange(U1, device=ws.device)[None, :]).expand(B, T, U1).reshape(B, -1)
+    alpha = view(2, cells, (B, T, U1)).double() + view(4, B * (T + U1), (B, T + U1)).double().gather(1, diag).view(B, T, U1)
+    beta = view(3, cells, (B, T, U1)).double() + view(5, B * (T + U1), (B, T + U1)).double().gather(1, diag).view(B, T, U1)
+    lse = view(1, cells * 2, (B, T, U1, 2)) if D else view(1, cells, (B, T, U1))
+    return alpha, beta, view(0, cells * (2 + D), (B, T, U1, 2 + D)), lse
+
+
+def _transducer_greedy_steps(who, enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, blank, durations, max_symbols, max_steps,
+                             n_steps, chunk=()):
+    """`durations` None: an RNN-T decode (RnntGreedyState, max_symbols per frame; `chunk` = (frame_base, rebase) of the chunk entry)."""
+    _cc(enc, who + ".enc"); _cc(valid, who + ".valid", I32); _cc(embed, who + ".embed"); _cc(lstm_ptrs, who + ".lstm_ptrs", torch.int64)
+    for t, n in ((proj_w, "proj_w"), (proj_b, "proj_b"), (head_w, "head_w"), (head_b, "head_b")):
+        _cc(t, f"{who}.{n}")
+    dur, D = _durations_arg(durations)
+    rows, head = (6, ()) if dur else (7, (int(max_symbols),))
+    B, T, Hd = enc.shape
+    layers = state.h.shape[0]
+    N = head_w.shape[0]
+    V1 = N - D
+    if (tuple(state.h.shape) != (layers, B, Hd) or lstm_ptrs.numel() != 4 * layers or embed.shape != (V1, Hd) or head_w.shape[1] != Hd
+            or tuple(proj_w.shape) != (Hd, Hd) or tuple(state.logits.shape) != (B, N) or tuple(state.istate.shape) != (rows, B)
+            or valid.numel() != B or head_b.numel() != N or not 0 <= blank < V1 or (head and head[0] < 1)):
+        raise DynError(f"{who}: shapes of the state ({'Rnnt' if rows == 7 else 'Tdt'}GreedyState), the weights and enc do not fit together")
+    check(getattr(_L(), "dyn_" + who)(enc.data_ptr(), valid.data_ptr(), embed.data_ptr(), lstm_ptrs.data_ptr(), proj_w.data_ptr(), proj_b.data_ptr(),
+                                      head_w.data_ptr(), head_b.data_ptr(), state.istate.data_ptr(), state.h.data_ptr(), state.c.data_ptr(),
+                                      state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(), state.tokens.data_ptr(),
+                                      state.frames.data_ptr(), B, T, Hd, layers, V1, *dur, int(blank), *head, state.n_max, int(max_steps),
+                                      int(n_steps), *chunk, _stream()), "dyn_" + who)
+
+
 def tdt_loss(logits, targets, logit_lengths, target_lengths, blank, durations, sigma=0.0, reduction="mean", grad_scale=1.0, want_grad=True,
              out=None, budget=None):
     """logits [B, T, U1, V1 + D] contiguous; targets int32 [B, S >= 1]; lengths int32 [B] (all on the device); `durations` a host list.
     Returns (loss [1], nll [B], grad [B, T, U1, V1 + D] of grad_scale * loss or None) with transformers' tdt_loss semantics
     (reduction "none": loss is the sum, the rows are nll).  `out` may be logits (the gradient written over them)."""
-    _c(logits, "tdt_loss.logits"); _c(targets, "tdt_loss.targets", I32)
-    _cc(logit_lengths, "tdt_loss.logit_lengths", I32); _cc(target_lengths, "tdt_loss.target_lengths", I32)
-    if reduction not in TDT_REDUCTIONS:
-        raise DynError(f"tdt_loss: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
-    dur, D = _durations_arg(durations)
-    if logits.dim() != 4 or logits.shape[3] <= D:
-        raise DynError(f"tdt_loss: logits {tuple(logits.shape)} must be [B, T, U + 1, V + 1 + {D}]")
-    B, T, U1, N = logits.shape
-    if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or logit_lengths.numel() != B or target_lengths.numel() != B:
-        raise DynError(f"tdt_loss: targets {tuple(targets.shape)} must be [B, S >= 1], the lengths [B]")
-    loss = torch.empty(1, device=logits.device, dtype=F32)
-    nll = torch.empty(B, device=logits.device, dtype=F32)
-    grad = None
-    if want_grad:
-        grad = torch.empty_like(logits) if out is None else _c(out, "tdt_loss.out")
-        if grad.shape != logits.shape:
-            raise DynError(f"tdt_loss: out {tuple(grad.shape)} != logits {tuple(logits.shape)}")
-    ws = workspace(logits.device)
-    check(_L().dyn_tdt_loss(logits.data_ptr(), B, T, U1, N - D, ctypes.cast(dur, ctypes.c_void_p), D, targets.data_ptr(), targets.shape[1],
-                            logit_lengths.data_ptr(), target_lengths.data_ptr(), blank, sigma, TDT_REDUCTIONS[reduction], grad_scale,
-                            loss.data_ptr(), nll.data_ptr(), 0 if grad is None else grad.data_ptr(), ws.data_ptr(), ws.numel(),
-                            TDT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_tdt_loss")
-    return loss, nll, grad
+    return _transducer_loss("tdt_loss", logits, targets, logit_lengths, target_lengths, blank, check_durations(durations), sigma, reduction, grad_scale, want_grad,
+                            out, budget)
 
 
 def joint_bwd_chunk(dz, z, de, dp, t0, accumulate, act="relu", time_major=False):
@@ -2359,72 +2489,28 @@ def tdt_state(B, T, U1, durations, device, budget=None):
     """A caller-owned lattice state for tdt_arcs_chunk / tdt_lattice_run / tdt_grad_chunk (uint8, dyn_tdt_loss_workspace_layout's
     layout; tdt_lattice(state=) reads it back).  Over `budget` (default TDT_WORKSPACE_BUDGET) it is refused by name before anything
     is allocated: the joint streams over frame chunks, the lattice state does not."""
-    D = len(check_durations(durations))
-    need = _L().dyn_tdt_loss_workspace_bytes(B, T, U1, D)
-    budget = TDT_WORKSPACE_BUDGET if budget is None else int(budget)
-    if need < 0:
-        raise DynError(f"tdt_state: bad lattice [{B}, {T}, {U1}]")
-    if 0 < budget < need:
-        raise DynError(f"tdt_state: the lattice of [{B}, {T}, {U1}] needs {need} bytes of state, over the workspace budget of {budget} "
-                       "(chunking the lattice state is not built: only the joint streams over frame chunks)")
-    return torch.empty(need, dtype=torch.uint8, device=device)
-
-
-def _tdt_chunk_args(who, logits, targets, target_lengths, T, durations, state):
-    _c(logits, who + ".logits"); _c(targets, who + ".targets", I32); _cc(target_lengths, who + ".target_lengths", I32)
-    _cc(state, who + ".state", torch.uint8)
-    dur, D = _durations_arg(durations)
-    if logits.dim() != 4 or logits.shape[3] <= D:
-        raise DynError(f"{who}: logits {tuple(logits.shape)} must be [B, Tc, U + 1, V + 1 + {D}]")
-    B = logits.shape[0]
-    if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or target_lengths.numel() != B or int(T) < 1:
-        raise DynError(f"{who}: targets {tuple(targets.shape)} must be [B, S >= 1], the lengths [B], T positive")
-    return dur, D
+    return _transducer_state("tdt_state", B, T, U1, check_durations(durations), device, budget)
 
 
 def tdt_arcs_chunk(logits, t0, T, targets, target_lengths, blank, durations, state, sigma=0.0, budget=None):
     """The arcs pass of tdt_loss on the frames [t0, t0 + Tc) of a lattice of T frames: logits [B, Tc, U1, V1 + D] (a chunk may overhang T,
     those rows are not read) -> lp and lse of those cells in `state` (tdt_state).  Every frame has to be covered before tdt_lattice_run."""
-    dur, D = _tdt_chunk_args("tdt_arcs_chunk", logits, targets, target_lengths, T, durations, state)
-    B, Tc, U1, N = logits.shape
-    check(_L().dyn_tdt_arcs_chunk(logits.data_ptr(), B, int(T), U1, N - D, ctypes.cast(dur, ctypes.c_void_p), D, targets.data_ptr(),
-                                  targets.shape[1], target_lengths.data_ptr(), blank, sigma, int(t0), Tc, state.data_ptr(), state.numel(),
-                                  TDT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_tdt_arcs_chunk")
+    _transducer_arcs_chunk("tdt_arcs_chunk", logits, t0, T, targets, target_lengths, blank, check_durations(durations), state, sigma,
+                           budget)
 
 
 def tdt_lattice_run(B, T, U1, S, logit_lengths, target_lengths, durations, state, reduction="mean", want_beta=True, budget=None):
     """The lattice and the reduction of tdt_loss on a state the arcs pass filled -> (loss [1], nll [B]); beta (the gradient pass needs
     it) only with want_beta.  S = the width of the targets tensor the arcs pass saw (it caps the target lengths)."""
-    _cc(logit_lengths, "tdt_lattice_run.logit_lengths", I32); _cc(target_lengths, "tdt_lattice_run.target_lengths", I32)
-    _cc(state, "tdt_lattice_run.state", torch.uint8)
-    if reduction not in TDT_REDUCTIONS:
-        raise DynError(f"tdt_lattice_run: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
-    if logit_lengths.numel() != B or target_lengths.numel() != B:
-        raise DynError(f"tdt_lattice_run: the lengths must be [{B}]")
-    dur, D = _durations_arg(durations)
-    loss = torch.empty(1, device=state.device, dtype=F32)
-    nll = torch.empty(B, device=state.device, dtype=F32)
-    check(_L().dyn_tdt_lattice_run(B, T, U1, ctypes.cast(dur, ctypes.c_void_p), D, int(S), logit_lengths.data_ptr(), target_lengths.data_ptr(),
-                                   TDT_REDUCTIONS[reduction], loss.data_ptr(), nll.data_ptr(), int(bool(want_beta)), state.data_ptr(),
-                                   state.numel(), TDT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_tdt_lattice_run")
-    return loss, nll
+    return _transducer_lattice_run("tdt_lattice_run", B, T, U1, S, logit_lengths, target_lengths, check_durations(durations), state, reduction,
+                                   want_beta, budget)
 
 
 def tdt_grad_chunk(logits, t0, T, targets, logit_lengths, target_lengths, blank, durations, state, reduction="mean", grad_scale=1.0, out=None):
     """The gradient pass of tdt_loss on the frames [t0, t0 + Tc): the gradient of grad_scale * loss w.r.t. the chunk's logits
     [B, Tc, U1, V1 + D], from a state tdt_lattice_run(want_beta=True) completed.  `out` may be the logits; rows past T are zeros."""
-    dur, D = _tdt_chunk_args("tdt_grad_chunk", logits, targets, target_lengths, T, durations, state)
-    _cc(logit_lengths, "tdt_grad_chunk.logit_lengths", I32)
-    if reduction not in TDT_REDUCTIONS:
-        raise DynError(f"tdt_grad_chunk: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
-    B, Tc, U1, N = logits.shape
-    grad = torch.empty_like(logits) if out is None else _c(out, "tdt_grad_chunk.out")
-    if grad.shape != logits.shape or logit_lengths.numel() != B:
-        raise DynError(f"tdt_grad_chunk: out {tuple(grad.shape)} != logits {tuple(logits.shape)}, or the lengths are not [{B}]")
-    check(_L().dyn_tdt_grad_chunk(logits.data_ptr(), B, int(T), U1, N - D, ctypes.cast(dur, ctypes.c_void_p), D, targets.data_ptr(),
-                                  targets.shape[1], logit_lengths.data_ptr(), target_lengths.data_ptr(), blank, TDT_REDUCTIONS[reduction],
-                                  grad_scale, int(t0), Tc, grad.data_ptr(), state.data_ptr(), state.numel(), _stream()), "dyn_tdt_grad_chunk")
-    return grad
+    return _transducer_grad_chunk("tdt_grad_chunk", logits, t0, T, targets, logit_lengths, target_lengths, blank, check_durations(durations), state,
+                                  reduction, grad_scale, out)
 
 
 def tdt_lattice(B, T, U1, D, device, state=None):
@@ -2432,18 +2518,9 @@ def tdt_lattice(B, T, U1, D, device, state=None):
     absolute values: (alpha [B, T, U1],
     beta [B, T, U1] (written only when a gradient was asked for), lp [B, T, U1, 2 + D], lse [B, T, U1, 2]).  The kernels store every
     anti-diagonal relative to an integer base; the bases are added back here in float64 (host arithmetic, for tests)."""
-    off = (ctypes.c_int64 * 8)()
-    check(_L().dyn_tdt_loss_workspace_layout(B, T, U1, D, ctypes.cast(off, ctypes.c_void_p)), "dyn_tdt_loss_workspace_layout")
-    ws = workspace(device) if state is None else state
-    cells = B * T * U1
-
-    def view(i, n, shape):
-        return ws[off[i]:off[i] + 4 * n].view(F32).view(shape)
-
-    diag = (torch.arange(T, device=ws.device)[:, None] + torch.arange(U1, device=ws.device)[None, :]).expand(B, T, U1)
-    alpha = view(2, cells, (B, T, U1)).double() + view(4, B * (T + U1), (B, T + U1)).double().gather(1, diag.reshape(B, -1)).view(B, T, U1)
-    beta = view(3, cells, (B, T, U1)).double() + view(5, B * (T + U1), (B, T + U1)).double().gather(1, diag.reshape(B, -1)).view(B, T, U1)
-    return alpha, beta, view(0, cells * (2 + D), (B, T, U1, 2 + D)), view(1, cells * 2, (B, T, U1, 2))
+    if int(D) < 1:
+        raise DynError(f"tdt_lattice: D={D} durations (a head without durations: rnnt_lattice)")
+    return _transducer_lattice(B, T, U1, int(D), device, state)
 
 
 class TdtGreedyState:
@@ -2464,44 +2541,12 @@ class TdtGreedyState:
 def tdt_greedy_steps(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, durations, blank, max_steps, n_steps):
     """n_steps greedy steps of every live row, queued from one call.  enc [B, T, Hd]; valid int32 [B]; lstm_ptrs int64 DEVICE tensor
     [4 * layers] of data pointers (w_ih, w_hh, b_ih, b_hh per layer); head_w [V1 + D, Hd]."""
-    _cc(enc, "tdt_greedy.enc"); _cc(valid, "tdt_greedy.valid", I32); _cc(embed, "tdt_greedy.embed"); _cc(lstm_ptrs, "tdt_greedy.lstm_ptrs", torch.int64)
-    for t, n in ((proj_w, "proj_w"), (proj_b, "proj_b"), (head_w, "head_w"), (head_b, "head_b")):
-        _cc(t, "tdt_greedy." + n)
-    dur, D = _durations_arg(durations)
-    B, T, Hd = enc.shape
-    layers = state.h.shape[0]
-    V1 = head_w.shape[0] - D
-    if (tuple(state.h.shape) != (layers, B, Hd) or lstm_ptrs.numel() != 4 * layers or embed.shape != (V1, Hd) or head_w.shape[1] != Hd
-            or tuple(proj_w.shape) != (Hd, Hd) or tuple(state.logits.shape) != (B, V1 + D) or valid.numel() != B or not 0 <= blank < V1):
-        raise DynError("tdt_greedy_steps: shapes of the state, the weights and enc do not fit together")
-    check(_L().dyn_tdt_greedy_steps(enc.data_ptr(), valid.data_ptr(), embed.data_ptr(), lstm_ptrs.data_ptr(), proj_w.data_ptr(), proj_b.data_ptr(),
-                                    head_w.data_ptr(), head_b.data_ptr(), state.istate.data_ptr(), state.h.data_ptr(), state.c.data_ptr(),
-                                    state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(), state.tokens.data_ptr(),
-                                    state.frames.data_ptr(), B, T, Hd, layers, V1, ctypes.cast(dur, ctypes.c_void_p), D, blank, state.n_max,
-                                    int(max_steps), int(n_steps), _stream()), "dyn_tdt_greedy_steps")
+    _transducer_greedy_steps("tdt_greedy_steps", enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, blank,
+                             check_durations(durations), None, max_steps, n_steps)
 
 
 # ----------------------------------------------------------------------------------------------- RNN-T (ParakeetForRNNT; csrc/transducer.hip)
 RNNT_WORKSPACE_BUDGET = TDT_WORKSPACE_BUDGET      # bytes of lattice state (20 B per cell) an RNN-T loss may ask for; the state is never chunked
-
-
-def _rnnt_args(who, logits, targets, target_lengths, blank, T=1, state=None):
-    _c(logits, who + ".logits"); _c(targets, who + ".targets", I32); _cc(target_lengths, who + ".target_lengths", I32)
-    if state is not None:
-        _cc(state, who + ".state", torch.uint8)
-    if logits.dim() != 4:
-        raise DynError(f"{who}: logits {tuple(logits.shape)} must be [B, T, U + 1, V + 1] (an RNN-T joint has no duration columns)")
-    B = logits.shape[0]
-    if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or target_lengths.numel() != B or int(T) < 1:
-        raise DynError(f"{who}: targets {tuple(targets.shape)} must be [B, S >= 1], the lengths [B], T positive")
-    if not 0 <= int(blank) < logits.shape[3]:
-        raise DynError(f"{who}: blank={blank} lies outside the {logits.shape[3]} classes")
-
-
-def _rnnt_reduction(who, reduction):
-    if reduction not in TDT_REDUCTIONS:
-        raise DynError(f"{who}: reduction={reduction!r} is not one of {sorted(TDT_REDUCTIONS)}")
-    return TDT_REDUCTIONS[reduction]
 
 
 def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank, reduction="mean_volume", grad_scale=1.0, want_grad=True, out=None,
@@ -2510,99 +2555,41 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank, reduction="
     Returns (loss [1], nll [B], grad [B, T, U1, V1] of grad_scale * loss or None) with transformers' rnnt_loss semantics: its five
     reductions under ops.TDT_REDUCTIONS' codes, default "mean_volume" (reduction "none": loss is the sum, the rows are nll).  `out` may
     be logits (the gradient written over them)."""
-    _rnnt_args("rnnt_loss", logits, targets, target_lengths, blank)
-    _cc(logit_lengths, "rnnt_loss.logit_lengths", I32)
-    red = _rnnt_reduction("rnnt_loss", reduction)
-    B, T, U1, V1 = logits.shape
-    if logit_lengths.numel() != B:
-        raise DynError(f"rnnt_loss: the lengths must be [{B}]")
-    loss = torch.empty(1, device=logits.device, dtype=F32)
-    nll = torch.empty(B, device=logits.device, dtype=F32)
-    grad = None
-    if want_grad:
-        grad = torch.empty_like(logits) if out is None else _c(out, "rnnt_loss.out")
-        if grad.shape != logits.shape:
-            raise DynError(f"rnnt_loss: out {tuple(grad.shape)} != logits {tuple(logits.shape)}")
-    ws = workspace(logits.device)
-    check(_L().dyn_rnnt_loss(logits.data_ptr(), B, T, U1, V1, targets.data_ptr(), targets.shape[1], logit_lengths.data_ptr(),
-                             target_lengths.data_ptr(), int(blank), red, grad_scale, loss.data_ptr(), nll.data_ptr(),
-                             0 if grad is None else grad.data_ptr(), ws.data_ptr(), ws.numel(),
-                             RNNT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_rnnt_loss")
-    return loss, nll, grad
+    return _transducer_loss("rnnt_loss", logits, targets, logit_lengths, target_lengths, blank, None, 0.0, reduction, grad_scale, want_grad, out,
+                            budget)
 
 
 def rnnt_state(B, T, U1, device, budget=None):
     """A caller-owned lattice state for rnnt_arcs_chunk / rnnt_lattice_run / rnnt_grad_chunk (uint8, dyn_rnnt_loss_workspace_layout's
     layout; rnnt_lattice(state=) reads it back).  Over `budget` (default RNNT_WORKSPACE_BUDGET) it is refused by name before anything
     is allocated: the joint streams over frame chunks, the lattice state does not."""
-    need = _L().dyn_rnnt_loss_workspace_bytes(B, T, U1)
-    budget = RNNT_WORKSPACE_BUDGET if budget is None else int(budget)
-    if need < 0:
-        raise DynError(f"rnnt_state: bad lattice [{B}, {T}, {U1}]")
-    if 0 < budget < need:
-        raise DynError(f"rnnt_state: the lattice of [{B}, {T}, {U1}] needs {need} bytes of state, over the workspace budget of {budget} "
-                       "(chunking the lattice state is not built: only the joint streams over frame chunks)")
-    return torch.empty(need, dtype=torch.uint8, device=device)
+    return _transducer_state("rnnt_state", B, T, U1, None, device, budget)
 
 
 def rnnt_arcs_chunk(logits, t0, T, targets, target_lengths, blank, state, budget=None):
     """The arcs pass of rnnt_loss on the frames [t0, t0 + Tc) of a lattice of T frames: logits [B, Tc, U1, V1] (a chunk may overhang T,
     those rows are not read) -> lp and lse of those cells in `state` (rnnt_state).  Every frame has to be covered before rnnt_lattice_run."""
-    _rnnt_args("rnnt_arcs_chunk", logits, targets, target_lengths, blank, T, state)
-    B, Tc, U1, V1 = logits.shape
-    check(_L().dyn_rnnt_arcs_chunk(logits.data_ptr(), B, int(T), U1, V1, targets.data_ptr(), targets.shape[1], target_lengths.data_ptr(),
-                                   int(blank), int(t0), Tc, state.data_ptr(), state.numel(),
-                                   RNNT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_rnnt_arcs_chunk")
+    _transducer_arcs_chunk("rnnt_arcs_chunk", logits, t0, T, targets, target_lengths, blank, None, state, 0.0, budget)
 
 
 def rnnt_lattice_run(B, T, U1, S, logit_lengths, target_lengths, state, reduction="mean_volume", want_beta=True, budget=None):
     """The lattice and the reduction of rnnt_loss on a state the arcs pass filled -> (loss [1], nll [B]); beta (the gradient pass needs
     it) only with want_beta.  S = the width of the targets tensor the arcs pass saw (it caps the target lengths)."""
-    _cc(logit_lengths, "rnnt_lattice_run.logit_lengths", I32); _cc(target_lengths, "rnnt_lattice_run.target_lengths", I32)
-    _cc(state, "rnnt_lattice_run.state", torch.uint8)
-    red = _rnnt_reduction("rnnt_lattice_run", reduction)
-    if logit_lengths.numel() != B or target_lengths.numel() != B:
-        raise DynError(f"rnnt_lattice_run: the lengths must be [{B}]")
-    loss = torch.empty(1, device=state.device, dtype=F32)
-    nll = torch.empty(B, device=state.device, dtype=F32)
-    check(_L().dyn_rnnt_lattice_run(B, T, U1, int(S), logit_lengths.data_ptr(), target_lengths.data_ptr(), red, loss.data_ptr(), nll.data_ptr(),
-                                    int(bool(want_beta)), state.data_ptr(), state.numel(),
-                                    RNNT_WORKSPACE_BUDGET if budget is None else int(budget), _stream()), "dyn_rnnt_lattice_run")
-    return loss, nll
+    return _transducer_lattice_run("rnnt_lattice_run", B, T, U1, S, logit_lengths, target_lengths, None, state, reduction, want_beta, budget)
 
 
 def rnnt_grad_chunk(logits, t0, T, targets, logit_lengths, target_lengths, blank, state, reduction="mean_volume", grad_scale=1.0, out=None):
     """The gradient pass of rnnt_loss on the frames [t0, t0 + Tc): the gradient of grad_scale * loss w.r.t. the chunk's logits
     [B, Tc, U1, V1], from a state rnnt_lattice_run(want_beta=True) completed.  `out` may be the logits; rows past T are zeros."""
-    _rnnt_args("rnnt_grad_chunk", logits, targets, target_lengths, blank, T, state)
-    _cc(logit_lengths, "rnnt_grad_chunk.logit_lengths", I32)
-    red = _rnnt_reduction("rnnt_grad_chunk", reduction)
-    B, Tc, U1, V1 = logits.shape
-    grad = torch.empty_like(logits) if out is None else _c(out, "rnnt_grad_chunk.out")
-    if grad.shape != logits.shape or logit_lengths.numel() != B:
-        raise DynError(f"rnnt_grad_chunk: out {tuple(grad.shape)} != logits {tuple(logits.shape)}, or the lengths are not [{B}]")
-    check(_L().dyn_rnnt_grad_chunk(logits.data_ptr(), B, int(T), U1, V1, targets.data_ptr(), targets.shape[1], logit_lengths.data_ptr(),
-                                   target_lengths.data_ptr(), int(blank), red, grad_scale, int(t0), Tc, grad.data_ptr(), state.data_ptr(),
-                                   state.numel(), _stream()), "dyn_rnnt_grad_chunk")
-    return grad
+    return _transducer_grad_chunk("rnnt_grad_chunk", logits, t0, T, targets, logit_lengths, target_lengths, blank, None, state, reduction,
+                                  grad_scale, out)
 
 
 def rnnt_lattice(B, T, U1, device, state=None):
     """What the last ops.rnnt_loss call of this (device, stream) left in the workspace (or what the chunk entries left in `state`), as
     absolute values: (alpha [B, T, U1], beta [B, T, U1] (written only when a gradient was asked for), lp [B, T, U1, 2], lse [B, T, U1]).
     The integer bases of the anti-diagonals are added back here in float64 (host arithmetic, for tests)."""
-    off = (ctypes.c_int64 * 8)()
-    check(_L().dyn_rnnt_loss_workspace_layout(B, T, U1, ctypes.cast(off, ctypes.c_void_p)), "dyn_rnnt_loss_workspace_layout")
-    ws = workspace(device) if state is None else state
-    cells = B * T * U1
-
-    def view(i, n, shape):
-        return ws[off[i]:off[i] + 4 * n].view(F32).view(shape)
-
-    diag = (torch.arange(T, device=ws.device)[:, None] + torch.arange(U1, device=ws.device)[None, :]).expand(B, T, U1).reshape(B, -1)
-    alpha = view(2, cells, (B, T, U1)).double() + view(4, B * (T + U1), (B, T + U1)).double().gather(1, diag).view(B, T, U1)
-    beta = view(3, cells, (B, T, U1)).double() + view(5, B * (T + U1), (B, T + U1)).double().gather(1, diag).view(B, T, U1)
-    return alpha, beta, view(0, cells * 2, (B, T, U1, 2)), view(1, cells, (B, T, U1))
+    return _transducer_lattice(B, T, U1, 0, device, state)
 
 
 class RnntGreedyState(TdtGreedyState):
@@ -2619,21 +2606,8 @@ class RnntGreedyState(TdtGreedyState):
 def rnnt_greedy_steps(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, blank, max_symbols, max_steps, n_steps):
     """n_steps greedy RNN-T steps of every live row, queued from one call.  enc [B, T, Hd]; valid int32 [B]; lstm_ptrs int64 DEVICE tensor
     [4 * layers] of data pointers (w_ih, w_hh, b_ih, b_hh per layer); head_w [V1, Hd]; `max_symbols`: max_symbols_per_step."""
-    _cc(enc, "rnnt_greedy.enc"); _cc(valid, "rnnt_greedy.valid", I32); _cc(embed, "rnnt_greedy.embed"); _cc(lstm_ptrs, "rnnt_greedy.lstm_ptrs", torch.int64)
-    for t, n in ((proj_w, "proj_w"), (proj_b, "proj_b"), (head_w, "head_w"), (head_b, "head_b")):
-        _cc(t, "rnnt_greedy." + n)
-    B, T, Hd = enc.shape
-    layers = state.h.shape[0]
-    V1 = head_w.shape[0]
-    if (tuple(state.h.shape) != (layers, B, Hd) or lstm_ptrs.numel() != 4 * layers or embed.shape != (V1, Hd) or head_w.shape[1] != Hd
-            or tuple(proj_w.shape) != (Hd, Hd) or tuple(state.logits.shape) != (B, V1) or tuple(state.istate.shape) != (7, B)
-            or valid.numel() != B or head_b.numel() != V1 or not 0 <= blank < V1 or int(max_symbols) < 1):
-        raise DynError("rnnt_greedy_steps: shapes of the state (RnntGreedyState), the weights and enc do not fit together")
-    check(_L().dyn_rnnt_greedy_steps(enc.data_ptr(), valid.data_ptr(), embed.data_ptr(), lstm_ptrs.data_ptr(), proj_w.data_ptr(), proj_b.data_ptr(),
-                                     head_w.data_ptr(), head_b.data_ptr(), state.istate.data_ptr(), state.h.data_ptr(), state.c.data_ptr(),
-                                     state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(), state.tokens.data_ptr(),
-                                     state.frames.data_ptr(), B, T, Hd, layers, V1, int(blank), int(max_symbols), state.n_max, int(max_steps),
-                                     int(n_steps), _stream()), "dyn_rnnt_greedy_steps")
+    _transducer_greedy_steps("rnnt_greedy_steps", enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, blank, None, max_symbols,
+                             max_steps, n_steps)
 
 
 # ----------------------------------------------------------------------------------------------- NemotronAsrStreamingForRNNT
@@ -2887,22 +2861,8 @@ def rnnt_greedy_steps_chunk(enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w
     """rnnt_greedy_steps on the frames enc [B, cs, Hd] of one streamed chunk; `rebase`: first move the state on to this chunk (frame pointer 0,
     done flags, per-frame counter, output and step counts cleared; h / c, the projector cache, the last token and the emit flag kept).
     Frames are recorded as frame_base + the frame inside the chunk."""
-    _cc(enc, "rnnt_greedy.enc"); _cc(valid, "rnnt_greedy.valid", I32); _cc(embed, "rnnt_greedy.embed"); _cc(lstm_ptrs, "rnnt_greedy.lstm_ptrs", torch.int64)
-    for t, n in ((proj_w, "proj_w"), (proj_b, "proj_b"), (head_w, "head_w"), (head_b, "head_b")):
-        _cc(t, "rnnt_greedy." + n)
-    B, T, Hd = enc.shape
-    layers = state.h.shape[0]
-    V1 = head_w.shape[0]
-    if (tuple(state.h.shape) != (layers, B, Hd) or lstm_ptrs.numel() != 4 * layers or embed.shape != (V1, Hd) or head_w.shape[1] != Hd
-            or tuple(proj_w.shape) != (Hd, Hd) or tuple(state.logits.shape) != (B, V1) or tuple(state.istate.shape) != (7, B)
-            or valid.numel() != B or head_b.numel() != V1 or not 0 <= blank < V1 or int(max_symbols) < 1):
-        raise DynError("rnnt_greedy_steps_chunk: shapes of the state (RnntGreedyState), the weights and enc do not fit together")
-    check(_L().dyn_rnnt_greedy_steps_chunk(enc.data_ptr(), valid.data_ptr(), embed.data_ptr(), lstm_ptrs.data_ptr(), proj_w.data_ptr(),
-                                           proj_b.data_ptr(), head_w.data_ptr(), head_b.data_ptr(), state.istate.data_ptr(), state.h.data_ptr(),
-                                           state.c.data_ptr(), state.h_new.data_ptr(), state.dec.data_ptr(), state.logits.data_ptr(),
-                                           state.tokens.data_ptr(), state.frames.data_ptr(), B, T, Hd, layers, V1, int(blank), int(max_symbols),
-                                           state.n_max, int(max_steps), int(n_steps), int(frame_base), int(bool(rebase)), _stream()),
-          "dyn_rnnt_greedy_steps_chunk")
+    _transducer_greedy_steps("rnnt_greedy_steps_chunk", enc, valid, embed, lstm_ptrs, proj_w, proj_b, head_w, head_b, state, blank, None,
+                             max_symbols, max_steps, n_steps, chunk=(int(frame_base), int(bool(rebase))))
 
 
 # ----------------------------------------------------------------------------------------------- Nemotron3_5AsrForRNNT, language-prompt fusion

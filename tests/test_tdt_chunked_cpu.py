@@ -125,3 +125,28 @@ def test_lattice_state_over_the_budget_is_refused_by_name_on_the_host():
     assert "budget" in str(e.value)
     with pytest.raises(ops.DynError):
         ops.tdt_state(2, 9, 6, (0, 2, 1), "cuda:0")
+
+
+@pytest.mark.parametrize("B,T,U1", [(1, 1, 1), (2, 9, 6), (64, 300, 41)])
+def test_lattice_state_layout_is_eight_segments_each_rounded_to_256_bytes(B, T, U1):
+    """The state layout both heads' entries and ops.tdt_lattice / ops.rnnt_lattice rely on, restated here: lp [cells, 2 + D], lse
+    [cells, 2] (no duration head, D = 0: [cells]), alpha, beta [cells], abase, bbase [B, T + U1], ll [B, 2], nll [B], floats, in this
+    order, each segment rounded up to 256 bytes.  dyn_tdt_loss_workspace_* at D in {1, 5, 8} and dyn_rnnt_loss_workspace_* (D = 0)
+    give exactly these offsets and this total (host-only entries)."""
+    from dynamic_asr_eval_amd import _lib
+    lib = _lib.load()
+    cells = B * T * U1
+    for D in (0, 1, 5, 8):
+        floats = (cells * (2 + D), cells * (2 if D else 1), cells, cells, B * (T + U1), B * (T + U1), B * 2, B)
+        want, at = [], 0
+        for n in floats:
+            want.append(at)
+            at += (4 * n + 255) // 256 * 256
+        off = (ctypes.c_int64 * 8)()
+        if D:
+            assert lib.dyn_tdt_loss_workspace_layout(B, T, U1, D, ctypes.cast(off, ctypes.c_void_p)) == 0
+            total = lib.dyn_tdt_loss_workspace_bytes(B, T, U1, D)
+        else:
+            assert lib.dyn_rnnt_loss_workspace_layout(B, T, U1, ctypes.cast(off, ctypes.c_void_p)) == 0
+            total = lib.dyn_rnnt_loss_workspace_bytes(B, T, U1)
+        assert list(off) == want and total == at, (D, list(off), want, total, at)
