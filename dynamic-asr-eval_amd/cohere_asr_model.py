@@ -23,7 +23,8 @@ other than hidden_size / heads or not a power of two in 4 .. 256, hidden_act oth
 multiple of 256 or above 4096, tie_word_embeddings, attention_bias false, `attention_mask` / `decoder_attention_mask`, do_sample,
 num_beams > 1, and whatever parakeet_model.make_config refuses of the encoder.  That last includes the released encoder's
 hidden_size 1280: the package's FastConformer is built at 256 / 512 / 768 / 1024, so the released checkpoint itself does not load yet;
-the decoder and the step are built and measured at the released decoder size.  Out of scope: the waveform front end, sampling, beam search, ragged encoder
+the decoder and the step are built and measured at the released decoder size.  Out of scope: the waveform front end (since built: feature_extractor() / generate_from_audio(), frontend.MelFeatures; rows longer than
+30 s, which the extractor splits at energy-based boundaries, are refused), sampling, beam search, ragged encoder
 lengths (since built: `input_lengths=` on encode / forward / generate, lengths[b] keys in row b's cross-attention; DESIGN.md, "Ragged
 batches"), hipGraph replay, lockstep groups, bf16.  No hub checkpoint is on the machine: transformers' CohereAsrForConditionalGeneration on
 the CPU with the same (random) state dict is the oracle in the tests."""
@@ -197,6 +198,7 @@ class CohereAsrForConditionalGeneration(PM.ParakeetForCTC):
     _param_spec = staticmethod(lambda c, pf="": param_spec(c))
     frozen_in_the_loop = FROZEN_IN_THE_LOOP
     greedy_chunk = 16                                    # decode steps queued per host call; the finished flags are read once per chunk
+    _feature_kind = "cohere_asr"                         # CohereAsrFeatureExtractor (frontend.MelFeatures): dither, rows of at most 30 s
 
     def __init__(self, config=None, device="cuda:0"):
         super().__init__(config, device)

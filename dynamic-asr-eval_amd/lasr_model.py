@@ -182,6 +182,7 @@ class LasrForCTC(PM.ParakeetForCTC):
     _layer_names = LAYER_NAMES
     _head_bias_names = ()
     downsampling_factor = 4                                    # two stride-2 stages
+    _feature_kind = "lasr"                                     # LasrFeatureExtractor (frontend.MelFeatures)
     frozen_in_the_loop = FROZEN_IN_THE_LOOP
     frames = staticmethod(frames)
 

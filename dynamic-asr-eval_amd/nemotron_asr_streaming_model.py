@@ -37,7 +37,8 @@ other than relu, `hidden_size` outside 256 / 512 / 768 / 1024; a negative or non
 `max_position_embeddings`; the `model_type` of any Parakeet head and "nemotron3_5_asr" (the multilingual sibling with a language-prompt
 projector: nemotron3_5_asr_model.py builds it on this class); `sigma`; batch_renorm_training() (there is no batch norm); and what
 the parents refuse of the head.
-Out of scope: gradients through a streaming session; ragged batches and rows that join or leave a session; a waveform front end; hipGraph
+Out of scope: gradients through a streaming session; ragged batches and rows that join or leave a session; a waveform front end (since built:
+feature_extractor() / generate_from_audio(), and push_audio() / flush() of a session; frontend.MelFeatures, MelStream); hipGraph
 replay of the offline calls and lockstep groups; the decode inside the captured streaming step;
 skipping fully masked tiles in the score and context GEMMs (the band is exploited in the position product and the softmax only).  No hub checkpoint is on the machine: transformers' class on the CPU with the same random state dict is the
 oracle in the tests."""
@@ -155,6 +156,7 @@ class NemotronAsrStreamingForRNNT(RM.ParakeetForRNNT):
             raise ops.DynError(f"{who}(num_lookahead_tokens={num_lookahead_tokens}) continues an encode that ran with "
                                f"num_lookahead_tokens={self._ctx_lookahead}")
 
+    _feature_kind = "nemotron_asr_streaming"                   # NemotronAsrStreamingFeatureExtractor: no normalisation, center=False for chunks
     _ragged = False                                            # the chunked attention mask and the causal subsampling know one length
 
     def encode(self, input_features, attention_mask=None, num_lookahead_tokens=None, input_lengths=None, **caches):

@@ -69,6 +69,7 @@ class StreamSession:
         self.greedy = model._greedy_state(B, self.cap)
         self._chunks = 0
         self._graph = self._pool = self._static_in = self._static_out = None
+        self._audio, self._pending, self._flushed = None, None, False     # push_audio()'s state, built at its first call
         with torch.no_grad(), ops.use_workspace(model._scratch()):
             tab = ops.stream_position_rows(geo, H).to(dev)
             self.pos = torch.stack([ops.linear(tab, model.P[f"encoder.layers.{l}.self_attn.linear_pos.weight"]) for l in range(L)])
@@ -94,6 +95,10 @@ class StreamSession:
         g.istate[1] = int(self.model.start_token)
         g.istate[2] = 1
         self._chunks = 0
+        if self._audio is not None:                            # the audio tail, the previous samples and the frames waiting for a chunk
+            self._audio.reset()
+            self._pending = self._pending[:, :0]
+        self._flushed = False
 
     def close(self):
         """Drops the captured step (never while a replay may be in flight)."""
@@ -222,6 +227,53 @@ class StreamSession:
         return SimpleNamespace(enc=enc.clone() if enc is self._static_out else enc, tokens=st.tokens.clone(), frames=st.frames.clone(),
                                count=st.istate[4].clone(), steps=st.istate[5].clone())
 
+    # ------------------------------------------------------------------ audio in (frontend.MelStream, csrc/melfeat.hip)
+    def _audio_state(self):
+        if self._audio is None:
+            from .frontend import MelStream
+            self._audio = MelStream(self.model.feature_extractor(), self.B)
+            self._pending = torch.zeros(self.B, 0, self.model.cfg["num_mel_bins"], device=self.model.device, dtype=torch.float32)
+        return self._audio
+
+    def _push_ready(self, new, pad_last=False):
+        """Appends the extracted frames `new` ([B, n, F] or None) and pushes every complete chunk; `pad_last`: a started last chunk is
+        filled up with zero frames.  The result of a chunk carries the feature frames it was fed as `features`."""
+        if new is not None:
+            self._pending = torch.cat([self._pending, new], dim=1)
+        outs = []
+        while True:
+            need = self.first_chunk_frames if self._chunks == 0 else self.chunk_frames
+            have = self._pending.shape[1]
+            if have < need and not (pad_last and have > 0):
+                return outs
+            chunk = self._pending[:, :need]
+            if have < need:
+                chunk = torch.nn.functional.pad(chunk, (0, 0, 0, need - have))
+            chunk, self._pending = chunk.contiguous(), self._pending[:, need:]
+            out = self.push(chunk)
+            out.features = chunk
+            outs.append(out)
+
+    def push_audio(self, samples):
+        """samples [B, n] float32 on the device, any n >= 0 (16 kHz mono; all streams advance together) -> the list of push() results of
+        the chunks these samples completed, possibly empty.  Feature frame t is extracted as soon as the samples below 160 t + 200 have
+        arrived; the extraction runs eagerly in front of the (possibly captured) encoder step."""
+        if self._flushed:
+            raise ops.DynError("push_audio after flush(): the stream has ended; reset() starts the next one")
+        return self._push_ready(self._audio_state().push(samples))
+
+    def flush(self):
+        """Ends the audio stream: the frames below total_samples // 160 that were still waiting for samples are extracted with zeros behind
+        the last sample; frame total_samples // 160, which the offline extractor emits and masks, follows as zeros, so the stream's
+        features are the offline pass's 1 + total_samples // 160 frames; the last chunk is filled up with zero frames -> the remaining
+        push() results.  The session then stands at the end of its stream: reset() starts the next one."""
+        a = self._audio_state()
+        if a.total == 0 or self._flushed:
+            return []
+        new, last = a.finish(), self._pending.new_zeros(self.B, 1, self._pending.shape[2])
+        self._flushed = True
+        return self._push_ready(last if new is None else torch.cat([new, last], dim=1), pad_last=True)
+
 
 def split_chunks(session, input_features):
     """[B, T, F] -> the list of a stream's chunks; T must be first_chunk_frames + k * chunk_frames."""
@@ -235,12 +287,19 @@ def split_chunks(session, input_features):
 
 def generate_streaming(model, input_features, num_lookahead_tokens=None, graph=False, **session_kw):
     """The greedy decode of a whole stream, chunk by chunk: `input_features` [B, T, F] (T = first_chunk_frames + k * chunk_frames) or an
-    iterable of chunks -> generate()'s fields, concatenated over the chunks (frames are absolute encoder frames).  `session_kw`: what
+    iterable of chunks, or 16 kHz mono waveforms [B, L] (push_audio + flush) -> generate()'s fields, concatenated over the chunks (frames are absolute encoder frames).  `session_kw`: what
     the model's stream() takes beyond these (nemotron3_5_asr_model.py: prompt_ids)."""
     chunks = input_features
-    if isinstance(input_features, torch.Tensor):
+    outs = None
+    if isinstance(input_features, torch.Tensor) and input_features.dim() == 2:        # waveforms [B, L]: the session extracts the features
+        if input_features.shape[1] < 160:
+            raise ops.DynError(f"generate_streaming: {input_features.shape[1]} samples give no valid feature frame (160 samples, one hop, are "
+                               "the shortest stream)")
+        session = model.stream(input_features.shape[0], num_lookahead_tokens, graph, **session_kw)
+        outs = session.push_audio(input_features.contiguous()) + session.flush()
+    elif isinstance(input_features, torch.Tensor):
         if input_features.dim() != 3:
-            raise ops.DynError("generate_streaming: input_features must be [B, T, num_mel_bins] or an iterable of chunks")
+            raise ops.DynError("generate_streaming: input_features must be [B, T, num_mel_bins], waveforms [B, L] or an iterable of chunks")
         session = model.stream(input_features.shape[0], num_lookahead_tokens, graph, **session_kw)
         chunks = split_chunks(session, input_features)
     else:
@@ -248,7 +307,8 @@ def generate_streaming(model, input_features, num_lookahead_tokens=None, graph=F
         if not chunks or not isinstance(chunks[0], torch.Tensor) or chunks[0].dim() != 3:
             raise ops.DynError("generate_streaming: input_features must be [B, T, num_mel_bins] or an iterable of chunks [B, frames, num_mel_bins]")
         session = model.stream(chunks[0].shape[0], num_lookahead_tokens, graph, **session_kw)
-    outs = [session.push(ch) for ch in chunks]
+    if outs is None:
+        outs = [session.push(ch) for ch in chunks]
     session.close()
     B, n_max, dev = session.B, session.cap, model.device
     tokens = torch.zeros(B, n_max * len(outs), dtype=torch.int32, device=dev)

@@ -5,7 +5,8 @@ Same call signature; `model` is this package's ParakeetForCTC (parakeet_model.py
 restates it, so no NeMo is needed, or a model of its family that says what the loop has to know about it (lasr_model.LasrForCTC: the
 attributes `downsampling_factor` and `frozen_in_the_loop`, read by loop_constants below).  The loop follows wav2vec2_lib.dynamic_eval_ctc_loss statement for statement; what differs, as in the
 reference:
-  * `spec` [1, n_mels, T] is a spectrogram, computed outside the loop (nvidia_ctc/lib.py:20-28), cut into windows along T (:116-125); every
+  * `spec` [1, n_mels, T] is a spectrogram, computed outside the loop (nvidia_ctc/lib.py:20-28; here get_spectrogram / preprocess
+    below, on the device), cut into windows along T (:116-125); every
     copy is transposed to [T, n_mels] on the device, the layout transformers' model takes;
   * SpecAugment (augment.SpecAugment, `spec_augment_config`) on the first `num_negatives` copies, one draw per copy in index order from the
     host torch RNG (`args.spec_augment_generator`, a torch.Generator, when given).  The reference's SpecAugment comes from an un-vendored
@@ -87,6 +88,48 @@ def loop_constants(model):
         raise ops.DynError(f"{type(model).__name__}: downsampling_factor={factor!r} / frozen_in_the_loop={frozen!r} are not a positive integer and "
                            "non-empty parameter-name prefixes")
     return factor, frozen
+
+
+def get_spectrogram(audio_signal, model, device=None):
+    """reference nvidia_ctc/lib.py:20-23: audio_signal [1, L] (16 kHz mono) -> spec [1, n_mels, T] on the device, through the model's own
+    front end (model.feature_extractor(): frontend.MelFeatures, csrc/melfeat.hip) in the loop's layout.  NeMo's preprocessor is not a
+    dependency, so the layout and the trimming are DEFINED here: the transformers extractor's features of the model's family, transposed,
+    cut to the row's valid frames (L // 160 for Parakeet; the extractor's last, masked frame is dropped).  `device` must be the model's
+    (None: the model's); anything else, the 'cpu' of the reference's `preprocess` included, is refused by name."""
+    if device is not None:
+        d, m = torch.device(device), torch.device(model.device)
+        if d.type != m.type or (d.index is not None and d.index != m.index):
+            raise ops.DynError(f"get_spectrogram: device={device!r} is not the model's ({model.device}): the front end runs where the model "
+                               "lives (there is no CPU path)")
+    x = torch.as_tensor(audio_signal)
+    if x.dim() == 1:
+        x = x[None, :]
+    if x.dim() != 2 or x.shape[0] != 1:
+        raise ops.DynError(f"get_spectrogram: audio_signal must be one mono recording [1, L], not {tuple(x.shape)} (multi-channel input is "
+                           "out of scope)")
+    x = x.to(device=model.device, dtype=torch.float32).contiguous()
+    spec, lens = model.feature_extractor()(x, layout="ft")
+    return spec[:, :, :lens[0]].contiguous()
+
+
+def preprocess(audio, model):
+    """reference nvidia_ctc/lib.py:25-28: a recording -> spec [1, n_mels, T] on the model's device.  `audio`: the path of a 16 kHz mono PCM
+    `.wav` (read with scipy.io.wavfile; integer PCM is scaled to [-1, 1) as torchaudio.load does), a tensor or an ndarray [L] / [1, L]."""
+    if isinstance(audio, (str, bytes)) or hasattr(audio, "__fspath__"):
+        import numpy as np
+        from scipy.io import wavfile
+        sr, data = wavfile.read(audio)
+        if sr != 16000:
+            raise ops.DynError(f"{audio}: sampling rate {sr} Hz is not built (16000; resampling is out of scope)")
+        if data.ndim != 1:
+            raise ops.DynError(f"{audio}: {data.shape[1]} channels; mono only (multi-channel input is out of scope)")
+        if np.issubdtype(data.dtype, np.integer):
+            if data.dtype == np.uint8:
+                data = (data.astype(np.float32) - 128.0) / 128.0
+            else:
+                data = data.astype(np.float32) / float(1 << (8 * data.dtype.itemsize - 1))
+        audio = torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))[None, :]
+    return get_spectrogram(audio, model, None)
 
 
 def disable_dropout(model):

@@ -1922,6 +1922,44 @@ def fbank_finish(mel, valid=None, mel_floor=FBANK_MEL_FLOOR, eps=1e-7):
     return out
 
 
+def melfeat_prep(x, lens, out, pad, preemphasis, noise=None, dither=0.0, prev=None):
+    """x [B, Lmax] waveforms, lens int32 CUDA [B] sample counts -> out [B, W] (W >= pad + Lmax, every element written): `pad` zeros, then
+    the row after dither (noise [B, Lmax], None: none), pre-emphasis over the whole signal (sample 0 kept, or filtered against prev[b], the
+    last sample of the chunk before) and the length mask (zeros at and past lens[b], whatever x holds there)."""
+    _c(x, "melfeat_prep.x"); _c(out, "melfeat_prep.out")
+    if x.dim() != 2 or out.dim() != 2 or out.shape[0] != x.shape[0]:
+        raise DynError("melfeat_prep: x must be [B, Lmax] and out [B, W]")
+    B, Lmax = x.shape
+    if noise is not None and _c(noise, "melfeat_prep.noise").shape != x.shape:
+        raise DynError("melfeat_prep: noise must have the shape of x")
+    if prev is not None and tuple(_c(prev, "melfeat_prep.prev").shape) != (B,):
+        raise DynError("melfeat_prep: prev must be [B]")
+    check(_L().dyn_melfeat_prep(x.data_ptr(), out.data_ptr(), _lens_ptr(lens, B, "melfeat_prep"), None if noise is None else noise.data_ptr(),
+                                None if prev is None else prev.data_ptr(), B, Lmax, pad, out.shape[1], preemphasis, dither, _stream()),
+          "dyn_melfeat_prep")
+    return out
+
+
+def melfeat_finish(mel, lens, guard, clamp, normalize, eps=1e-5, layout="tf", out=None):
+    """mel [B, T, F] energies, lens int32 CUDA [B] valid frames -> [B, T, F] (layout "tf") or [B, F, T] ("ft"): log(mel + guard), or
+    log(max(mel, guard)) when `clamp`; `normalize`: (v - mean) / (std + eps) per row and bin over the row's valid frames (unbiased std, centred
+    second pass, fixed order); frames >= lens[b] exact zeros."""
+    _c(mel, "melfeat_finish.mel")
+    if mel.dim() != 3 or layout not in ("tf", "ft"):
+        raise DynError("melfeat_finish: mel must be [B, T, F] and layout \"tf\" or \"ft\"")
+    B, T, F = mel.shape
+    shape = (B, T, F) if layout == "tf" else (B, F, T)
+    if out is None:
+        out = torch.empty(shape, device=mel.device, dtype=F32)
+    elif tuple(_c(out, "melfeat_finish.out").shape) != shape:
+        raise DynError(f"melfeat_finish: out must be {shape}")
+    ws = workspace(mel.device)
+    check(_L().dyn_melfeat_finish(mel.data_ptr(), out.data_ptr(), _lens_ptr(lens, B, "melfeat_finish"), B, T, F, guard, int(bool(clamp)),
+                                  int(bool(normalize)), eps, 0 if layout == "tf" else 1, ws.data_ptr(), ws.numel(), _stream()),
+          "dyn_melfeat_finish")
+    return out
+
+
 def relkey_embed_grad(dc2p, q, dE, scale, beta=1.0):
     """The gradient of Wav2Vec2-BERT's shared distance embedding E [P, D] (`self_attn.distance_embedding.weight`, one table for all heads):
         dE[p, :] = beta * dE[p, :] + scale * sum_{b, h, i} dC2P[b, h, i, P - 1 - p] * q[b, h, i, :]

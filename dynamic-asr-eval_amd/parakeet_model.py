@@ -8,8 +8,8 @@ batch norm into eval mode (:92-93) and then replaces that batch norm by a fresh,
 A subclass of Wav2Vec2ConformerForCTC: the two half-step FFNs, Transformer-XL attention with per-head `bias_u` / `bias_v` and a bias-free
 position projection (csrc/relshift.hip), the five attention products (_attn.py), the layer loop, flat parameters and the backward's deferred
 reductions are the parent's, found under the parent's names through an alias table (LAYER_NAMES, as sew_d_model.py does).  What differs:
-  * input: `input_features` [B, T, num_mel_bins] log-mel frames, as transformers takes them; no waveform front end (the reference computes
-    its spectrogram outside the loop, nvidia_ctc/lib.py:20-28).
+  * input: `input_features` [B, T, num_mel_bins] log-mel frames, as transformers takes them (the reference computes its spectrogram outside
+    the loop, nvidia_ctc/lib.py:20-28); feature_extractor() / generate_from_audio() start at the waveform (frontend.MelFeatures).
   * subsampling (ParakeetEncoderSubsamplingConv2D, x8 `dw_striding`): Conv2d(1 -> C, 3, s2) -> ReLU -> 2 x [depthwise Conv2d(C, 3, s2) -> 1x1
     -> ReLU] -> flatten -> Linear(C F / 8 -> H).  The stage structure of the project's own conformer (csrc/conv.hip) with ReLU fused into
     the depthwise loads (ops.dwconv2d_s2_*_act) and ops.relu in front of the flatten; the unfused stages (the reference freezes this part,
@@ -580,6 +580,38 @@ class ParakeetForCTC(WC.Wav2Vec2ConformerForCTC):
         if not self._below_frozen():
             self._subsample_bwd(cut(ctx["sub"]), dh, *(() if lens is None else (lens,)))
         return None
+
+    # ------------------------------------------------------------------ waveform front end (frontend.MelFeatures, csrc/melfeat.hip)
+    _feature_kind = "parakeet"                                 # the extractor class of the checkpoint family (frontend.MEL_KINDS)
+
+    def feature_extractor(self):
+        """The device form of this family's transformers feature extractor at the configuration's `num_mel_bins`, built once per model."""
+        fe = self.__dict__.get("_mel_features")
+        if fe is None:
+            from . import frontend
+            fe = self._mel_features = frontend.MelFeatures(self._feature_kind, self.cfg["num_mel_bins"], self.device)
+        return fe
+
+    def features_from_audio(self, waveforms, audio_lengths=None):
+        """waveforms [B, Lmax] float32 on the device (+ the valid samples per row) -> (input_features, input_lengths).  Rows with one and the
+        same count of VALID FRAMES (what the extractor's mask would show; 16000 and 16100 samples are both 100 frames, so equal sample
+        counts are not required):
+        the features are cut to their valid frames and input_lengths is None (what a model without per-row frame counts can run);
+        otherwise the extractor's [B, T, F] with zeros past each row's count, and the counts."""
+        feats, lens = self.feature_extractor()(waveforms, audio_lengths)
+        if len(set(lens)) == 1:
+            return feats[:, :lens[0]].contiguous(), None
+        return feats, lens
+
+    def generate_from_audio(self, waveforms, audio_lengths=None, **generate_kw):
+        """generate() from 16 kHz mono waveforms [B, Lmax] on the device; `audio_lengths`: the valid samples per row of a ragged batch
+        (a model that refuses `input_lengths` refuses it with its own message).  `generate_kw` goes to generate() unchanged."""
+        if "input_lengths" in generate_kw or "input_features" in generate_kw:
+            raise ops.DynError("generate_from_audio computes input_features and input_lengths itself: pass waveforms and audio_lengths")
+        feats, lens = self.features_from_audio(waveforms, audio_lengths)
+        if lens is not None:
+            generate_kw["input_lengths"] = lens
+        return self.generate(feats, **generate_kw)
 
     def generate(self, input_features, input_lengths=None):
         """Greedy CTC ids as transformers' ParakeetForCTC.generate returns them: the argmax of every frame's logits [B, T'] (int64, blanks

@@ -22,7 +22,7 @@ What differs:
 Refused by name before any launch: `model_type: "parakeet_tdt"` and any config that carries `durations` (parakeet_tdt_model builds
 those), `attention_mask`, `sigma != 0`, and what parakeet_tdt_model.make_config refuses of the head and the encoder (a `hidden_act` of the
 joint other than "relu", decoder sizes, ids outside the vocabulary).  Out of scope: beam / MAES decoding, ragged batches in the model (the
-loss kernel's per-row lengths are built), a waveform front end, hipGraph replay, chunking the lattice state, `hidden_act` other than relu.
+loss kernel's per-row lengths are built), a waveform front end (since built: ParakeetForCTC.generate_from_audio, frontend.MelFeatures), hipGraph replay, chunking the lattice state, `hidden_act` other than relu.
 torchaudio is not needed: the tests' oracle is a plain torch recursion with autograd on transformers' own ParakeetForRNNT logits (CPU, the
 same random state dict), a float64 closed form and a brute-force sum over all alignments."""
 from . import ops

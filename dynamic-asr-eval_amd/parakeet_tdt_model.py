@@ -29,7 +29,7 @@ transformers modeling_parakeet.py: ParakeetForTDT) as transformers builds it in 
 Refused by name before any launch: `attention_mask`, a `hidden_act` of the joint other than "relu", more than 8 durations, negative or
 unsorted durations, `model_type: "parakeet_rnnt"` (ParakeetForRNNT: no duration head; parakeet_rnnt_model builds it on this class), and whatever
 parakeet_model.make_config refuses of the encoder.  Out of scope: beam / MAES decoding, ragged batches in the model (the loss kernel's
-per-row lengths are built), a waveform front end, hipGraph replay and lockstep groups, chunking the joint over u or the lattice state, a
+per-row lengths are built), a waveform front end (since built: ParakeetForCTC.generate_from_audio, frontend.MelFeatures), hipGraph replay and lockstep groups, chunking the joint over u or the lattice state, a
 log-sum-exp in the GEMM's epilogue that never writes the logits.  No hub checkpoint is
 on the machine: transformers' ParakeetForTDT on the CPU with the same (random) state dict is the oracle in the tests."""
 from types import SimpleNamespace

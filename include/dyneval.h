@@ -1336,6 +1336,31 @@ int dyn_softmax_fwd_lens(const float* x, float* y, int64_t B, int64_t rows_per, 
                          void* stream);
 int dyn_seq2seq_steps_len(const dyn_seq2seq_desc* d, const int32_t* enc_lens, int32_t t0, int32_t n_steps, int32_t n_forced, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Waveform front end of the FastConformer family (csrc/melfeat.hip): the two ends of transformers' ParakeetFeatureExtractor /
+ * NemotronAsrStreamingFeatureExtractor / CohereAsrFeatureExtractor / LasrFeatureExtractor `__call__` around the strided-row STFT GEMM,
+ * dyn_stft_power and the mel GEMM, for a ragged batch.  The reference's third loop gets its `spec` from `get_spectrogram` / `preprocess`
+ * (nvidia_ctc/lib.py:20-28), NeMo's preprocessor on the CPU.
+ *   dyn_melfeat_prep     x [B, Lmax], lens int32 [B] on the device (clamped into [0, Lmax]) -> out [B, W], W >= pad + Lmax: element i of row b
+ *                        is sample j = i - pad after `waveform[:valid] += dither * noise` (noise [B, Lmax], null: none), the pre-emphasis
+ *                        `x[j] - preemphasis * x[j - 1]` over the whole signal (sample 0 kept, or filtered against prev[b] when `prev`
+ *                        [B] is given: the last sample of the chunk before, for streams; preemphasis 0: none) and
+ *                        `masked_fill(~timemask, 0.0)`: exact zeros for j < 0 and j >= lens[b], sample lens[b] included.  Every element of out
+ *                        is written; samples at or past lens[b] are never read.  One rounding per operation, as the extractor's float32.
+ *   dyn_melfeat_finish   mel [B, T, F] energies, lens int32 [B] valid frames per row (clamped into [0, T]) -> out [B, T, F] (layout 0) or
+ *                        [B, F, T] (layout 1): v = log(mel + guard) (clamp 0) or log(max(mel, guard)) (clamp 1); normalize != 0:
+ *                        (v - mean) / (std + eps) with the mean and the UNBIASED std per row and bin over the row's valid frames (the mean
+ *                        first, then the centred squares in a second pass, per 256-frame block and then over the blocks in double, in
+ *                        a fixed order, no float atomics; a bin of equal values gives exact zeros).  Frames >= lens[b] are exact zeros.
+ *                        F <= 256; out must not alias mel; workspace 8-byte aligned, dyn_melfeat_finish_workspace_bytes(B, T, F) bytes.
+ * Null pointers and sizes out of range -> DYN_E_ARG, a small or misaligned workspace -> DYN_E_WORKSPACE, before any launch.
+ * ------------------------------------------------------------------------------------------------ */
+int dyn_melfeat_prep(const float* x, float* out, const int32_t* lens, const float* noise, const float* prev, int64_t B, int64_t Lmax,
+                     int64_t pad, int64_t W, float preemphasis, float dither, void* stream);
+int64_t dyn_melfeat_finish_workspace_bytes(int64_t B, int64_t T, int64_t F);
+int dyn_melfeat_finish(const float* mel, float* out, const int32_t* lens, int64_t B, int64_t T, int64_t F, float guard, int32_t clamp,
+                       int32_t normalize, float eps, int32_t layout, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
